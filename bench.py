@@ -19,10 +19,16 @@ junction reduce, rows to the host), then the merged row table.
     python bench.py --gpus N --steps K --warmup W      (N > 1 without a launcher: starts the N ranks itself)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
-One JSON line on stdout.  Beside the contract's fields it carries `roofline` (dominant kernel, HIP events inside
-the timed region), `cpu_baseline` (the oracle over the WHOLE workload on the box's host cores, one thread per
-contig like the reference; every device row compared with it) and `e2e` (the same alignments as a BGZF BAM on
-disk -> `portcullis_amd junc` -> .tab, compared with the oracle's .tab).
+One JSON line on stdout.  A plain run does what the headline needs and no more: it generates the workload, warms up,
+times the --steps steps, writes the last step's outputs if --dump-outputs is given and prints the contract's fields
+(`metric`, `value`, `unit`, `higher_is_better`, `dtype`, `ms_per_step`, ...).  With --full the line also carries
+`roofline` and `kernels` (instrumented steps before the timed region, the dominant kernel's HIP events inside it),
+`back_to_back`, `cpu_baseline` (the oracle over the WHOLE workload on the box's host cores, one thread per contig like
+the reference; every device row compared with it), `e2e` (the same alignments as a BGZF BAM on disk ->
+`portcullis_amd junc` -> .tab, compared with the oracle's .tab) and, for N > 1, `multi_gpu_check`.
+
+    python bench.py --steps K --warmup W --dump-outputs DIR     (DIR/<name>.npy: see dump_outputs)
+    python bench.py --full                                       (every leg of the line)
 """
 import argparse
 import hashlib
@@ -181,7 +187,13 @@ def main():
     ap.add_argument("--e2e-workdir", default=os.environ.get("PJB_BENCH_WORKDIR", "/tmp/pjb_bench_e2e"))
     ap.add_argument("--no-verify", action="store_true", help="N > 1: skip rank 0's single-GPU re-run of the whole set")
     ap.add_argument("--no-back-to-back", action="store_true", help="skip the secondary measurement of passes queued back to back")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline: the instrumented steps (roofline, per-kernel table), passes back to back, the CPU "
+                         "baseline, the end-to-end leg and (N > 1) rank 0's single-GPU check of the merged table")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write the last timed step's outputs to DIR/<name>.npy (dump_outputs)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
     if args.config == "c5":
         args.reads, args.junctions, args.no_e2e = 1_000_000_000, 300_000, True
         args.queue = min(args.queue, 2)  # (a 335 M-read chain's scratch is ~45 GB: two of the three chains in flight beside the 73 GB of records)
@@ -234,7 +246,9 @@ def main():
     L = cfgs[0].read_len
     ORI = "FR"
 
-    ctx = ffi.Context(device=dev_index, orientation=ORI, flags=ffi.FLAG_KERNEL_TIMING, strandedness=1 if args.config == "c5" else 3)
+    # (kernel timing only for --full: without a kernel selection it brackets every launch with HIP events)
+    ctx = ffi.Context(device=dev_index, orientation=ORI, flags=ffi.FLAG_KERNEL_TIMING if args.full else 0,
+                      strandedness=1 if args.config == "c5" else 3)
     ctx.set_refs(lens)
     t_gen = time.time()
     contigs = {}  # tid -> dict(batch, n, P, C, S, Cs)
@@ -323,29 +337,30 @@ def main():
         xchg = pd.MirrorExchange(row_bytes, int(jmax.item()) * 5 // 4 + 64, dev)
         step()  # one untimed step with the exchange (buffers, communicator warm-up)
         xchg.finish()
-    # per-kernel table from a few fully instrumented steps (outside the timed region), one kernel at a time on one
-    # stream: in the timed region kernels of two contigs and of the side streams overlap, and a bracketed duration
-    # then includes whatever ran beside the kernel ...
-    ctx.reset_kernel_timing()
-    n_prof = 2
-    state["want_timing"] = True  # sort passes / generic pairs per contig, for the byte formulas
-    ctx.set_option("overlap", 0)
-    for _ in range(n_prof):
-        step()
-    ctx.set_option("overlap", 1)
-    state["want_timing"] = False
-    if xchg is not None:
-        xchg.finish()
-    kt_all = ctx.kernel_timing()
-    dominant = max(kt_all.items(), key=lambda kv: kv[1][1])[0] if kt_all else None
-    if multi:  # every rank brackets the same kernel (rank 0's choice)
-        names = sorted(kt_all)
-        pick = torch.tensor([names.index(dominant) if dominant else 0], dtype=torch.int64, device="cpu" if share else dev)
-        dist.broadcast(pick, 0)
-        dominant = names[int(pick.item())] if names else None
-    # ... and only the dominant kernel keeps its HIP-event bracket inside the timed region
-    ctx.select_timed_kernels([dominant] if dominant else [])
-    ctx.reset_kernel_timing()
+    n_prof, kt_all, dominant = 2, {}, None
+    if args.full:
+        # per-kernel table from a few fully instrumented steps (outside the timed region), one kernel at a time on one
+        # stream: in the timed region kernels of two contigs and of the side streams overlap, and a bracketed duration
+        # then includes whatever ran beside the kernel ...
+        ctx.reset_kernel_timing()
+        state["want_timing"] = True  # sort passes / generic pairs per contig, for the byte formulas
+        ctx.set_option("overlap", 0)
+        for _ in range(n_prof):
+            step()
+        ctx.set_option("overlap", 1)
+        state["want_timing"] = False
+        if xchg is not None:
+            xchg.finish()
+        kt_all = ctx.kernel_timing()
+        dominant = max(kt_all.items(), key=lambda kv: kv[1][1])[0] if kt_all else None
+        if multi:  # every rank brackets the same kernel (rank 0's choice)
+            names = sorted(kt_all)
+            pick = torch.tensor([names.index(dominant) if dominant else 0], dtype=torch.int64, device="cpu" if share else dev)
+            dist.broadcast(pick, 0)
+            dominant = names[int(pick.item())] if names else None
+        # ... and only the dominant kernel keeps its HIP-event bracket inside the timed region
+        ctx.select_timed_kernels([dominant] if dominant else [])
+        ctx.reset_kernel_timing()
     if world > 1:
         dist.barrier()
     torch.cuda.synchronize()
@@ -369,7 +384,7 @@ def main():
     # timed region above ends with its last chain's tail (junction ids, sort, reductions, rows over PCIe) alone on the chip; a queue
     # of samples hides it behind the next sample's K1 stage.  Rows of all passes stay in the table: each pass's must equal the step's.
     back_to_back = None
-    if not multi and not os.environ.get("PJB_BENCH_ABLATION") and not args.no_back_to_back and args.steps > 1:  # (no row exchange: its slot holds one pass)
+    if args.full and not multi and not os.environ.get("PJB_BENCH_ABLATION") and not args.no_back_to_back and args.steps > 1:  # (no row exchange: its slot holds one pass)
         def passes_back_to_back(k):
             ctx.clear_rows()
             inflight = []
@@ -430,10 +445,12 @@ def main():
         assert totals["spliced"] + totals["unspliced"] == N_total, (totals, N_total)
         assert totals["sum_len"] == N_total * L
     J_total = len(merged_rows) if rank == 0 else 0
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, merged_rows, regs if world == 1 else None)
 
     # ---- N > 1: the merged table must equal what ONE GPU produces for the whole set
     verify = None
-    if world > 1 and not args.no_verify:
+    if world > 1 and args.full and not args.no_verify:
         if rank == 0:
             t_v = time.time()
             ctx1 = ffi.Context(device=dev_index, orientation=ORI)
@@ -457,7 +474,9 @@ def main():
 
     # ---- per-kernel device time over the timed region (HIP events on the context's stream)
     result = None
-    if rank == 0:
+    # the batches carry their bases in 2 bits as well (synth; PJB_FFI_SEQ2=0 submits them without: A/B runs of the 4-bit compare)
+    two_bit = os.environ.get("PJB_FFI_SEQ2", "1") != "0" and os.environ.get("PJB_NO_SEQ2", "0") == "0"
+    if rank == 0 and args.full:
         kt_timed = state.get("kt_timed") or ctx.kernel_timing()
         kt = {k: (v[0] / n_prof * args.steps, v[1] / n_prof * args.steps) for k, v in kt_all.items()}
         dom_serial_ms = kt[dominant][1] / kt[dominant][0] if dominant and kt[dominant][0] else None
@@ -465,8 +484,6 @@ def main():
             kt[dominant] = kt_timed[dominant]  # measured live over the timed region (beside whatever overlapped it)
         per = state.get("per_chain", {})
         kern = []
-        # the batches carry their bases in 2 bits as well (synth; PJB_FFI_SEQ2=0 submits them without: A/B runs of the 4-bit compare)
-        two_bit = os.environ.get("PJB_FFI_SEQ2", "1") != "0" and os.environ.get("PJB_NO_SEQ2", "0") == "0"
         # (what the library plans the sort's digits from: the most junctions per read a chain of this context has had -- pjb_api.hip: junc_per_read)
         junc_per_read = max([sum(int(regs[t]["n_junctions"]) for t in g) / max(sum(contigs[t]["n"] for t in g), 1) for g in chains] + [0.0])
         for name, (launches, ms) in kt.items():
@@ -585,6 +602,28 @@ def main():
                 shutil.rmtree(args.e2e_workdir, ignore_errors=True)
 
         tot_bytes = sum((k["alg_bytes"] or 0) * k["launches"] / args.steps for k in kern)
+        full_fields = {
+            "roofline": roofline,
+            "cpu_baseline": cpu,
+            "e2e": e2e,
+            "multi_gpu_check": verify,
+            "device_kernel_ms_per_step": round(kernel_ms_per_step, 4),
+            "launches_per_step": round(sum(k["launches"] for k in kern) / args.steps, 1),
+            # sum of the kernels' own durations (one at a time) over the step's wall time: > 1 = what the streams overlap
+            "overlap_factor": round(kernel_ms_per_step / (elapsed / args.steps * 1e3), 4),
+            "back_to_back": back_to_back,
+            # a chain's stages on their own (the instrumented steps: one chain at a time, one kernel at a time, gaps included): what the
+            # LAST chain of a step costs behind its K1 stage, where no other chain runs beside it
+            "chain_stages_ms_alone": [dict(targets=len(g), **{k: round(float(v), 3) for k, v in state["per_chain"][tuple(g)]["stage_ms"].items()})
+                                      for g in chains if tuple(g) in state.get("per_chain", {})],
+            "pipeline_gbps": round(tot_bytes / (kernel_ms_per_step * 1e-3) / 1e9, 1) if kernel_ms_per_step else None,
+            "kernels": [dict(name=k["name"], launches_per_step=k["launches"] / args.steps, avg_ms=round(k["avg_ms"], 5),
+                             ms_per_step=round(k["total_ms"] / args.steps, 4),
+                             gbps=round(k["gbps"], 1) if k["gbps"] else None) for k in kern],
+            "kernels_note": "per-launch durations from the instrumented steps before the timed region (one kernel at a time); "
+                            "the roofline kernel's row is the one measured inside the timed region",
+        }
+    if rank == 0:
         cfg_name = "configs[4] (whole, on one GPU)" if args.config == "c5" else "configs[2]" if world == 1 else "configs[3]"
         result = {
             "metric": "junc_reads_per_sec",
@@ -616,28 +655,12 @@ def main():
                                 + f"{args.queue} chains queued at once, side by side on the device",
                        "hbm_resident_gb_rank0": round(hbm_gb, 2)},
             "junctions_per_sec": J_total * args.steps / elapsed,
-            "roofline": roofline,
-            "cpu_baseline": cpu,
-            "e2e": e2e,
-            "multi_gpu_check": verify,
-            "device_kernel_ms_per_step": round(kernel_ms_per_step, 4),
-            "launches_per_step": round(sum(k["launches"] for k in kern) / args.steps, 1),
-            # sum of the kernels' own durations (one at a time) over the step's wall time: > 1 = what the streams overlap
-            "overlap_factor": round(kernel_ms_per_step / (elapsed / args.steps * 1e3), 4),
-            "back_to_back": back_to_back,
             "host_queue_ms_per_step": round(host_queue_ms, 3),  # the calling thread inside pjb_submit_batch_device + pjb_finish_*_begin
-            # a chain's stages on their own (the instrumented steps: one chain at a time, one kernel at a time, gaps included): what the
-            # LAST chain of a step costs behind its K1 stage, where no other chain runs beside it
-            "chain_stages_ms_alone": [dict(targets=len(g), **{k: round(float(v), 3) for k, v in state["per_chain"][tuple(g)]["stage_ms"].items()})
-                                      for g in chains if tuple(g) in state.get("per_chain", {})],
-            "pipeline_gbps": round(tot_bytes / (kernel_ms_per_step * 1e-3) / 1e9, 1) if kernel_ms_per_step else None,
-            "kernels": [dict(name=k["name"], launches_per_step=k["launches"] / args.steps, avg_ms=round(k["avg_ms"], 5),
-                             ms_per_step=round(k["total_ms"] / args.steps, 4),
-                             gbps=round(k["gbps"], 1) if k["gbps"] else None) for k in kern],
-            "kernels_note": "per-launch durations from the instrumented steps before the timed region (one kernel at a time); "
-                            "the roofline kernel's row is the one measured inside the timed region",
             "datagen_s": round(t_gen, 2),
+            "full": args.full,
         }
+        if args.full:
+            result.update(full_fields)
         # a line from an ablation build or another library build says so: its results were not checked
         if world == 1 and os.environ.get("PJB_BENCH_AS_RANK"):
             # (experiment: this GPU held the targets ONE rank of an N-rank run would get -- no exchange, never a measurement of N GPUs;
@@ -654,6 +677,50 @@ def main():
     ctx.close()
     if multi:
         dist.destroy_process_group()
+
+
+DUMP_BYTES = 60 * 10**6  # what --dump-outputs may write in all (64 MB at most, with room for the file system's rounding)
+REGION_FIELDS = ("spliced", "unspliced", "sum_len", "min_len", "max_len", "n_reads", "n_pairs", "n_junctions")
+
+
+def dump_outputs(out_dir, rows, regs=None, budget=DUMP_BYTES, seed=20260101):
+    """--dump-outputs: what the last timed step handed its caller, as .npy files two builds can be compared by, file for file.
+
+    rows_<field>.npy   one file per field of the junction table (pjb_junction_row; padding left out), rows in (refid, start,
+                       end, read_strand, cons_strand) order: one-byte fields as float32, all others as float64 (exact for them).
+                       A table whose files would exceed the budget is a fixed, seeded sample of its rows.
+    rows_index.npy     the position of every written row in that order (0 .. n-1 when the table is whole).
+    regions.npy        one GPU only: a line per target -- tid, then REGION_FIELDS (pjb_region_result) -- float64.
+    Returns the bytes written."""
+    import numpy as np
+
+    os.makedirs(out_dir, exist_ok=True)
+    header = 128  # (an .npy header of these shapes)
+    fields = [f for f in rows.dtype.names if not f.startswith("_")]
+
+    def as_float(f):
+        return np.float32 if rows.dtype[f].base.itemsize == 1 else np.float64
+
+    arrays = {}
+    if regs is not None:
+        arrays["regions"] = np.array([[t] + [regs[t][k] for k in REGION_FIELDS] for t in sorted(regs)],
+                                     dtype=np.float64).reshape(-1, 1 + len(REGION_FIELDS))
+    row_bytes = 8 + sum(np.dtype(as_float(f)).itemsize * int(np.prod(rows.dtype[f].shape, dtype=np.int64)) for f in fields)
+    room = budget - sum(a.nbytes + header for a in arrays.values()) - header * (len(fields) + 1)
+    keep = min(len(rows), max(room // row_bytes, 0))
+    order = np.lexsort(tuple(rows[k] for k in ("cons_strand", "read_strand", "end", "start", "refid")))
+    idx = np.arange(len(rows)) if keep == len(rows) else np.sort(np.random.default_rng(seed).choice(len(rows), keep, replace=False))
+    sel = rows[order[idx]]
+    arrays["rows_index"] = idx.astype(np.float64)
+    for f in fields:
+        arrays["rows_" + f] = sel[f].astype(as_float(f))
+    total = 0
+    for name, a in arrays.items():
+        path = os.path.join(out_dir, name + ".npy")
+        np.save(path, a)
+        total += os.path.getsize(path)
+    assert total <= budget, (total, budget)
+    return total
 
 
 def csrc_hash():

@@ -129,7 +129,7 @@ def test_bench_two_ranks_share_one_gpu():
     (PJB_BENCH_SHARE_GPU=1: a debug mode for one-GPU boxes).  The contig set is sharded by read count, every rank's
     mirror slot accumulates its contigs' rows, and rank 0 checks the merged table byte for byte against the table a
     single context produces for all 25 contigs (BASELINE configs[3] in miniature)."""
-    d = _run_bench(["--gpus", "2"], {"PJB_BENCH_SHARE_GPU": "1"})
+    d = _run_bench(["--gpus", "2", "--full"], {"PJB_BENCH_SHARE_GPU": "1"})
     assert d["n_gpus"] == 2 and d["scaling"] == "strong"
     assert d["multi_gpu_check"]["merged_equals_single_gpu_table"] is True
     assert sorted(d["config"]["contigs_per_rank"]) == [12, 13] and d["config"]["junctions_total"] == d["multi_gpu_check"]["rows"]
@@ -139,7 +139,7 @@ def test_bench_eight_ranks_share_one_gpu():
     """BASELINE configs[3] / [4] in miniature: `bench.py --gpus 8`, eight ranks on one GPU (gloo exchange), the 25 targets dealt out
     by read count; rank 0's merged table equals the single-context table byte for byte, every rank got targets, and the line
     carries the balance of the deal (max shard / mean shard) that a real 8-GPU run can be held against."""
-    d = _run_bench(["--gpus", "8"], {"PJB_BENCH_SHARE_GPU": "1"}, timeout=1500)
+    d = _run_bench(["--gpus", "8", "--full"], {"PJB_BENCH_SHARE_GPU": "1"}, timeout=1500)
     assert d["n_gpus"] == 8 and d["scaling"] == "strong"
     assert d["multi_gpu_check"]["merged_equals_single_gpu_table"] is True
     per = d["config"]["contigs_per_rank"]
@@ -149,15 +149,37 @@ def test_bench_eight_ranks_share_one_gpu():
 
 
 def test_bench_line_small_workload(tmp_path):
-    """The whole bench line (roofline, cpu_baseline over every contig with parity, e2e through BAM bytes) on a
+    """The whole bench line (--full: roofline, cpu_baseline over every contig with parity, e2e through BAM bytes) on a
     scaled-down 25-contig set."""
-    d = _run_bench(["--e2e-workdir", str(tmp_path / "e2e")], {})
+    d = _run_bench(["--full", "--e2e-workdir", str(tmp_path / "e2e")], {})
     assert d["roofline"]["frac"] > 0 and d["roofline"]["alg_bytes_per_launch"] > 0
     assert d["cpu_baseline"]["value"] > 0 and "every device row" in d["cpu_baseline"]["sample"]
     assert "error" not in d["e2e"], d["e2e"]
     assert d["e2e"]["tab_identical_to_oracle"] is True and d["e2e"]["reads"] == d["config"]["reads_total"]
     er = d["e2e"]["early_return"]  # the opt-in early return is timed beside the default (one process): closed before the tree is gone
     assert er["wall_s_outputs_closed"] <= er["wall_s_process_tree"]
+
+
+def test_bench_plain_line_and_outputs(tmp_path):
+    """A plain run carries the contract's fields and none of --full's legs; --dump-outputs writes the last timed step's junction
+    table and region counters (float32 / float64, 64 MB at most), the same for two runs with the same arguments."""
+    import numpy as np
+
+    runs = []
+    for k in range(2):
+        d = _run_bench(["--dump-outputs", str(tmp_path / f"out{k}")], {})
+        assert {"metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"} <= d.keys()
+        assert d["steps"] == 3 and d["full"] is False and d["value"] > 0 and d["ms_per_step"] > 0
+        assert not {"roofline", "kernels", "cpu_baseline", "e2e", "back_to_back"} & d.keys()
+        files = sorted(os.listdir(tmp_path / f"out{k}"))
+        assert sum(os.path.getsize(tmp_path / f"out{k}" / f) for f in files) <= 64 * 10**6
+        runs.append({f: np.load(tmp_path / f"out{k}" / f) for f in files})
+    a, b = runs
+    assert all(x.dtype in (np.float32, np.float64) for x in a.values())
+    assert len(a["rows_start.npy"]) == d["config"]["junctions_total"]  # (a small table is written whole)
+    assert a["regions.npy"].shape[0] == 25 and a["regions.npy"][:, -1].sum() == d["config"]["junctions_total"]
+    assert a["rows_nb_raw.npy"].sum() == d["config"]["pairs_rank0"]
+    assert a.keys() == b.keys() and all(np.array_equal(a[f], b[f]) for f in a)
 
 
 # ---- BASELINE configs[2] at full size: 200 M paired-end reads over 25 GRCh38-sized contigs, one context

@@ -2,7 +2,7 @@
 #   ENVS="A=1;B=2 C=3;..." (';'-separated settings, each a space-separated list of VAR=value; "-" = nothing), REPS (default 6)
 OUT=gpurun_out; mkdir -p $OUT
 NAME=${NAME:-env_ab}
-PJB_BENCH_E2E_REPS=1 PJB_BENCH_E2E_EARLY_REPS=0 python bench.py --steps 2 --warmup 1 --no-cpu-baseline 2>/dev/null | python3 -c "
+PJB_BENCH_E2E_REPS=1 PJB_BENCH_E2E_EARLY_REPS=0 python bench.py --full --steps 2 --warmup 1 --no-cpu-baseline 2>/dev/null | python3 -c "
 import json,sys
 d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print('bench e2e runs', d['e2e'].get('runs_s'), d['e2e'].get('error'))"
 EXE=${EXE:-portcullis_amd/host/portcullis_amd}

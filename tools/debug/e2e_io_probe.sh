@@ -3,7 +3,7 @@
 # of the transfer knobs, alternating.
 OUT=gpurun_out; mkdir -p $OUT
 BAM=/tmp/pjb_bench_e2e/prep/portcullis.sorted.alignments.bam
-PJB_BENCH_E2E_REPS=3 PJB_BENCH_E2E_EARLY_REPS=0 python bench.py --steps 2 --warmup 1 --no-cpu-baseline 2>/dev/null | python3 -c "
+PJB_BENCH_E2E_REPS=3 PJB_BENCH_E2E_EARLY_REPS=0 python bench.py --full --steps 2 --warmup 1 --no-cpu-baseline 2>/dev/null | python3 -c "
 import json,sys
 d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print('bench e2e runs', d['e2e'].get('runs_s'), d['e2e'].get('error'))"
 ls -la $BAM; nproc; numactl -H 2>/dev/null | head -5; cat /sys/fs/cgroup/cpu.max 2>/dev/null

@@ -1,7 +1,7 @@
 # (experiment, round 6) does the program's slow state (a 1.5 - 2 s stall of the copies somewhere in the run) come from the process before it --
 # the driver clearing that process's 100+ GB of device memory?  Runs back to back against runs with a pause before them.
 OUT=gpurun_out; mkdir -p $OUT
-PJB_BENCH_E2E_REPS=1 PJB_BENCH_E2E_EARLY_REPS=0 python bench.py --steps 2 --warmup 1 --no-cpu-baseline 2>/dev/null | python3 -c "
+PJB_BENCH_E2E_REPS=1 PJB_BENCH_E2E_EARLY_REPS=0 python bench.py --full --steps 2 --warmup 1 --no-cpu-baseline 2>/dev/null | python3 -c "
 import json,sys
 d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print('bench e2e runs', d['e2e'].get('runs_s'), d['e2e'].get('error'))"
 EXE=portcullis_amd/host/portcullis_amd

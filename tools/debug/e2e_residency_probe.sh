@@ -1,7 +1,7 @@
 # (experiment, round 6) the program's slow state (4 - 6 s instead of 2): is the BAM still in the page cache?  Before every run: the cgroup's
 # memory numbers and the fraction of the file that is resident (mincore on a mapping).
 OUT=gpurun_out; mkdir -p $OUT
-PJB_BENCH_E2E_REPS=1 PJB_BENCH_E2E_EARLY_REPS=0 python bench.py --steps 2 --warmup 1 --no-cpu-baseline 2>/dev/null | python3 -c "
+PJB_BENCH_E2E_REPS=1 PJB_BENCH_E2E_EARLY_REPS=0 python bench.py --full --steps 2 --warmup 1 --no-cpu-baseline 2>/dev/null | python3 -c "
 import json,sys
 d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print('bench e2e runs', d['e2e'].get('runs_s'), d['e2e'].get('error'))"
 BAM=/tmp/pjb_bench_e2e/prep/portcullis.sorted.alignments.bam

@@ -1,5 +1,5 @@
 # (experiment, round 5) the program's host-side knobs on the bench's prepared BAM (made by the first call, kept in /tmp for the rest)
-run() { echo "== $1 ${3:-}"; PJB_BENCH_E2E_SWEEP="$1" PJB_BENCH_E2E_REPS=$2 PJB_BENCH_E2E_EARLY_REPS=0 python bench.py --steps 2 --warmup 1 --no-cpu-baseline 2>/dev/null | python3 -c "
+run() { echo "== $1 ${3:-}"; PJB_BENCH_E2E_SWEEP="$1" PJB_BENCH_E2E_REPS=$2 PJB_BENCH_E2E_EARLY_REPS=0 python bench.py --full --steps 2 --warmup 1 --no-cpu-baseline 2>/dev/null | python3 -c "
 import json,sys
 d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print(d['e2e'].get('runs_s'), d['e2e'].get('error'))"; }
 run "PJB_DUMMY=0,0,0" 3

@@ -1,7 +1,7 @@
 # (experiment, round 6) is the program's "stands still for seconds" state (more targets in transfer, more readers) the container's CPU quota?
 # cpu.stat of the cgroup before and after every run: usage_usec, nr_throttled, throttled_usec.
 OUT=gpurun_out; mkdir -p $OUT
-PJB_BENCH_E2E_REPS=1 PJB_BENCH_E2E_EARLY_REPS=0 python bench.py --steps 2 --warmup 1 --no-cpu-baseline 2>/dev/null | python3 -c "
+PJB_BENCH_E2E_REPS=1 PJB_BENCH_E2E_EARLY_REPS=0 python bench.py --full --steps 2 --warmup 1 --no-cpu-baseline 2>/dev/null | python3 -c "
 import json,sys
 d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print('bench e2e runs', d['e2e'].get('runs_s'), d['e2e'].get('error'))"
 cat /sys/fs/cgroup/cpu.max; cat /sys/fs/cgroup/cpu.stat | head -8

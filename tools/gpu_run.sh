@@ -5,7 +5,7 @@
 #   smoke            __graft_entry__.smoke()
 #   quick            bench.py without the BAM leg and the CPU baseline (10 steps)            -> gpurun_out/<TAG>_quick.json
 #   quick:<variant>  the same with tools/variants/libpjb_<variant>.so (tools/build_variants.sh)
-#   bench            bench.py with default flags, as the driver runs it                       -> gpurun_out/<TAG>_bench_C3.json
+#   bench            bench.py --full: every leg of the line                                   -> $OUT/<TAG>_bench_C3.json
 #   prof             tools/profile_round.sh: rocprofv3 kernel stats + FETCH/WRITE PMC passes + the bench line
 #   sq               SQ issue / stall counters per kernel (tools/pmc_sq.sh), condensed by tools/show_sq.py
 #   sqv:<variant>    instruction counts per kernel (the first two counter groups of pmc_sq.sh) of tools/variants/libpjb_<variant>.so
@@ -26,11 +26,11 @@ for step in "$@"; do
     tests) ( time timeout 2400 python -m pytest tests -m gpu -q -x > $OUT/${TAG}_pytest_full.log 2>&1 ); grep -v "^  File \"/usr/local/lib" $OUT/${TAG}_pytest_full.log | tail -60 | tee $OUT/${TAG}_pytest.log ;;
     tests:*) ( time timeout 2400 python -m pytest tests -m gpu -q -x -k "${step#tests:}" 2>&1 | tail -40 ) 2>&1 | tee $OUT/${TAG}_pytest_k.log ;;
     smoke) python -c "import __graft_entry__ as g; g.smoke()" 2>&1 | tail -5 ;;
-    quick) timeout 900 python bench.py --steps 10 --warmup 3 --no-e2e --no-cpu-baseline > $OUT/${TAG}_quick.json 2> $OUT/${TAG}_quick.err; tail -c 400 $OUT/${TAG}_quick.err
+    quick) timeout 900 python bench.py --full --steps 10 --warmup 3 --no-e2e --no-cpu-baseline > $OUT/${TAG}_quick.json 2> $OUT/${TAG}_quick.err; tail -c 400 $OUT/${TAG}_quick.err
            python3 tools/show_bench.py $OUT/${TAG}_quick.json ;;
-    quick:*) v=${step#quick:}; PJB_BENCH_ABLATION=1 PJB_LIB_PATH=$PWD/tools/variants/libpjb_$v.so timeout 900 python bench.py --steps 10 --warmup 3 --no-e2e --no-cpu-baseline > $OUT/${TAG}_quick_$v.json 2> $OUT/${TAG}_quick_$v.err; tail -c 300 $OUT/${TAG}_quick_$v.err
+    quick:*) v=${step#quick:}; PJB_BENCH_ABLATION=1 PJB_LIB_PATH=$PWD/tools/variants/libpjb_$v.so timeout 900 python bench.py --full --steps 10 --warmup 3 --no-e2e --no-cpu-baseline > $OUT/${TAG}_quick_$v.json 2> $OUT/${TAG}_quick_$v.err; tail -c 300 $OUT/${TAG}_quick_$v.err
            python3 tools/show_bench.py $OUT/${TAG}_quick_$v.json | head -12 ;;
-    bench) ( time python bench.py > $OUT/${TAG}_bench_C3.json 2> $OUT/${TAG}_bench.err ) 2>&1 | tail -4; tail -c 400 $OUT/${TAG}_bench.err
+    bench) ( time python bench.py --full > $OUT/${TAG}_bench_C3.json 2> $OUT/${TAG}_bench.err ) 2>&1 | tail -4; tail -c 400 $OUT/${TAG}_bench.err
            python3 tools/show_bench.py $OUT/${TAG}_bench_C3.json ;;
     prof) bash tools/profile_round.sh $TAG ${COMMIT:-unknown}; python3 tools/show_bench.py $OUT/${TAG}_bench_C3.json ;;
     sq) bash tools/pmc_sq.sh $TAG > $OUT/${TAG}_sq_summary.csv 2>&1; python3 tools/show_sq.py $OUT/sq_$TAG/summary.csv | tee $OUT/${TAG}_sq.txt ;;

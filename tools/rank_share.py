@@ -21,7 +21,7 @@ for n in ns:
         env = dict(os.environ)
         if n > 1:
             env["PJB_BENCH_AS_RANK"] = f"{r}/{n}"
-        p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "10", "--warmup", "3", "--no-e2e", "--no-cpu-baseline",
+        p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--steps", "10", "--warmup", "3", "--no-e2e", "--no-cpu-baseline",
                             "--no-back-to-back"], env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True)
         try:
             d = json.loads(p.stdout.strip().splitlines()[-1])
