@@ -4,7 +4,6 @@
 // is streamed in batches to the MI355X through the C ABI in include/portcullis_amd.h.
 #pragma once
 
-#include <functional>
 #include <future>
 #include <string>
 #include <vector>
@@ -13,8 +12,6 @@
 #include "bam/genome_mapper.hpp"
 #include "junction_system.hpp"
 #include "prepared_files.hpp"
-
-struct pjb_junction_row;
 
 namespace portcullis {
 
@@ -62,8 +59,9 @@ class JunctionBuilder {
     std::shared_ptr<class PinnedPool> genomePool;  // a few page-locked buffers for the FASTA bytes of the target sequences (same runs)
     size_t pieceMinTarget = 0;                     // targets with fewer bytes go over in one (pageable) block
     bool backgroundTeardown = false;               // contexts and page-locked rings are taken down beside the merge and the writers (the program sets it: it leaves with _exit; a library caller that returns from main must not have a thread inside the runtime then)
-    bool directPieces = true;                      // the threads that read the file hand the pieces to the device themselves (PORTCULLIS_DIRECT_PIECES=0: through the device thread's queue)
     bool deviceIngest = true;      // BGZF inflate + BAM record parse on the GPU (pjb_submit_bam); false: host threads
+
+    std::shared_ptr<const struct JuncEnv> env;  // the environment's switches, read once by the constructor (src/junction_builder.cc)
 
     std::shared_future<int> deviceCount;  // pjb_device_count() evaluated in the background
 
@@ -73,12 +71,25 @@ class JunctionBuilder {
     std::vector<RegionResult> results;
 
 protected:
+    // the steps of findJunctions, in their order; what they hand to each other is the JuncRun
     void findJunctions();
-    // decode one target sequence (worker body) and feed it to the thread that owns the GPU context
+    void planIngest(struct JuncRun& run);
+    void startDeviceThreads(JuncRun& run);
+    void worker(JuncRun& run, int w);
+    void completeDeferred(JuncRun& run);
+    void calcExtraMetrics(JuncRun& run);
+    void tearDown(JuncRun& run);
+    void mergeResults();
+    // one target sequence (worker body): its records or file bytes go to the thread that owns the GPU context by one of three
+    // routes, its genome follows, then the contig is finished
     void findJuncs(class DeviceThread& device, bam::BamReader& reader, bam::GenomeMapper& gmap, int32_t seq);
+    void decodeOnHost(DeviceThread& device, bam::BamReader& reader, int32_t seq, struct DeferredTarget& dt);
+    void sendWhole(DeviceThread& device, bam::BamReader& reader, int32_t seq, DeferredTarget& dt, uint64_t fileOff, size_t nb, uint32_t firstU);
+    void streamPieces(DeviceThread& device, bam::BamReader& reader, int32_t seq, DeferredTarget& dt, uint64_t fileOff, size_t nb, uint32_t firstU);
+    void uploadGenome(DeviceThread& device, bam::GenomeMapper& gmap, int32_t seq, DeferredTarget& dt);
     // group chains (the program's default for large inputs): a worker does not wait for its target's chain -- the group is queued when its
     // last member has been asked for -- and findJunctions completes the targets once every one of them has been asked for
-    void completeTarget(int32_t seq, struct DeferredTarget& dt);
+    void completeTarget(int32_t seq, DeferredTarget& dt);
     std::vector<std::shared_ptr<struct DeferredTarget>> deferredTargets;
     std::mutex deferredMu;
 

@@ -63,6 +63,38 @@ def test_no_device_is_a_loud_error():
         raise AssertionError("pjb_create succeeded without a device")
 
 
+def test_no_device_is_the_same_loud_error_on_every_ingest_route(tmp_path):
+    """Without a GPU `portcullis_amd junc` must leave with status 4 and the context's own message whichever way the targets' bytes
+    would have travelled: host decode, the whole-target block, file pieces (which must not read the file for a device that is not there)."""
+    import subprocess
+
+    from fuzzgen import make_reads
+    from portcullis_amd import ffi
+    from util_bam import make_prep_dir
+
+    if ffi.device_count() > 0:
+        return
+    exe = os.path.join(ROOT, "portcullis_amd", "host", "portcullis_amd")
+    if not os.path.exists(exe):
+        pytest.skip("host program not built")
+    refs, contigs, reads = [], [], []
+    for tid in range(3):
+        genome, rr = make_reads(70 + tid, n_reads=300, glen=20000 + 1000 * tid)
+        for r in rr:
+            r["tid"] = tid
+        refs.append((f"chr{tid + 1}", len(genome)))
+        contigs.append((f"chr{tid + 1}", genome))
+        reads += rr
+    prep = make_prep_dir(str(tmp_path / "prep"), refs, contigs, reads)
+    for ingest, env_extra in (("host", {}), ("device", {}), ("device", {"PORTCULLIS_PIECE_BYTES": "4096"})):
+        env = {k: v for k, v in os.environ.items() if not k.startswith(("PORTCULLIS_", "PJB_"))}
+        env.update(env_extra)
+        p = subprocess.run([exe, "junc", "-t", "3", "--ingest", ingest, "-o", str(tmp_path / "out" / "pc"), prep],
+                           capture_output=True, text=True, timeout=10, env=env)
+        assert p.returncode == 4, (ingest, env_extra, p.returncode, p.stderr[-500:])
+        assert "No MI355X (HIP device) is visible" in p.stderr, (ingest, env_extra, p.stderr[-500:])
+
+
 def test_host_library_builds_and_links():
     host = os.path.join(ROOT, "portcullis_amd", "host")
     assert os.path.exists(os.path.join(host, "libportcullis_host.so"))

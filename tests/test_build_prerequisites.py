@@ -35,5 +35,7 @@ def test_the_abi_header_rebuilds_the_host_layer():
     lib = os.path.join(d, "libportcullis_host.so")
     if not os.path.exists(lib):
         pytest.skip("host layer not built")
-    hdr = os.path.join(ROOT, "include", "portcullis_amd.h")
-    assert out_of_date_after_touch(d, lib, hdr) == 1, "editing include/portcullis_amd.h would not rebuild the host layer"
+    internal = sorted(glob.glob(os.path.join(d, "src", "*.hpp")))  # (the host layer's own headers beside its sources)
+    assert internal
+    for hdr in [os.path.join(ROOT, "include", "portcullis_amd.h")] + internal:
+        assert out_of_date_after_touch(d, lib, hdr) == 1, f"editing {os.path.relpath(hdr, ROOT)} would not rebuild the host layer"
