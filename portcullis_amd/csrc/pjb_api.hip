@@ -1,7 +1,7 @@
 // pjb_api.hip -- C ABI (include/portcullis_amd.h) over the HIP kernels: contexts, genomes, batches, the kernel chains, rows.
 // One context = one HIP device + its streams + grow-only scratch.  (--extra / bamfilt / filt: pjb_extra_api.hip; BGZF and BAM: pjb_ingest_api.hip.)
-#define PJB_KERNELS_CHAIN 1
 #include "pjb_host.hip.h"
+#include "pjb_kernels.hip.h"
 
 static int slot_init(pjb_ctx *c, int k);
 static void aux_streams(pjb_ctx *c) { // the rows stream and the row mirror's (15 - 20 ms each to create)
@@ -190,21 +190,6 @@ void pjb_destroy(pjb_ctx *c) {
             for (int i = 0; i < 12; i++) tot += h[i];
             static const char *nm[12] = {"block start", "prologue", "shapes (wait ops)", "windows issue", "next records issue", "stage wait", "next ops issue", "compare+emit", "lists", "cand flush", "span of bases", "bases issue"};
             for (int i = 0; i < 12; i++) fprintf(stderr, "[k1e_prof] %-20s %6.2f %%  %llu\n", nm[i], tot ? 100.0 * (double)h[i] / (double)tot : 0.0, h[i]);
-        }
-    }
-#endif
-#ifdef K1E_HIST
-    { // compare rounds per wavefront and trip of k1_emit: what ran (the longest lane's) against what the lanes needed
-        unsigned long long h[4][32] = {{0}};
-        if (hipMemcpyFromSymbol(h, HIP_SYMBOL(pjb::g_k1e_hist), sizeof h) == hipSuccess) {
-            unsigned long long trips = 0, run = 0, need = 0, lanes = 0;
-            for (int r = 0; r < 32; r++) trips += h[0][r], run += h[0][r] * (unsigned long long)r, need += h[1][r], lanes += h[2][r];
-            fprintf(stderr, "[k1e_hist] 2-bit rounds: %llu wavefront-trips, %.3f rounds run a trip, %.3f rounds a lane needs (max / mean %.3f)\n", trips,
-                    trips ? (double)run / (double)trips : 0.0, lanes ? (double)need / (double)lanes : 0.0,
-                    need ? ((double)run / (double)trips) / ((double)need / (double)lanes) : 0.0);
-            for (int r = 0; r < 32; r++)
-                if (h[0][r] || h[3][r])
-                    fprintf(stderr, "[k1e_hist]   %2d rounds: %10llu trips (2-bit)  %10llu trips (4-bit)\n", r, h[0][r], h[3][r]);
         }
     }
 #endif

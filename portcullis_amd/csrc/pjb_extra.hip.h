@@ -14,61 +14,14 @@
 //   * name multiplicities = one open-addressing table over the 64-bit codes of every spliced record.
 #pragma once
 
-#include "pjb_kernels.hip.h"
+#include "pjb_extra_types.hip.h"
 
 namespace pjb {
-
-// ---- std::hash<std::string> (libstdc++ _Hash_bytes, 64-bit: a MurmurHash64A variant, seed 0xc70f6907) of
-// BamAlignment::deriveName() (lib/src/bam_alignment.cc:233-242; lib/include/portcullis/junction.hpp:158).
-// `name` has `len` bytes without the NUL.  Used by the device record transcoder; the host transcoder has the
-// same function (portcullis/bam/name_hash.hpp).
-__host__ __device__ inline u64 std_hash_shift_mix(u64 v) { return v ^ (v >> 47); }
-__host__ __device__ inline u64 derive_name_hash(const uint8_t *name, u32 len, u32 flag) {
-    const u64 mul = (((u64)0xc6a4a793UL) << 32) + (u64)0x5bd1e995UL;
-    uint8_t suf[3] = {'_', 'R', '?'};
-    u32 total = len;
-    if (flag & 0x1u) {
-        suf[2] = (flag & 0x40u) ? '1' : (flag & 0x80u) ? '2' : '?';
-        total += 3;
-    }
-    auto at = [&](u32 i) -> u64 { return i < len ? name[i] : suf[i - len]; };
-    u64 hash = 0xc70f6907ULL ^ ((u64)total * mul);
-    const u32 aligned = total & ~7u;
-    for (u32 p = 0; p < aligned; p += 8) {
-        u64 w = 0;
-        for (int k = 7; k >= 0; k--) w = (w << 8) | at(p + (u32)k); // little-endian unaligned load
-        const u64 data = std_hash_shift_mix(w * mul) * mul;
-        hash ^= data;
-        hash *= mul;
-    }
-    if (total & 7u) {
-        u64 data = 0;
-        for (int n = (int)(total & 7u) - 1; n >= 0; n--) data = (data << 8) + at(aligned + (u32)n);
-        hash ^= data;
-        hash *= mul;
-    }
-    hash = std_hash_shift_mix(hash) * mul;
-    hash = std_hash_shift_mix(hash);
-    return hash;
-}
-
-constexpr u32 PLP_MAXCNT = 8000; // bam_plp_init, deps/htslib-1.3/sam.c:1622
-
-struct ExtraCounters { // one per contig, device memory
-    u32 n_zero;       // unspliced mapped records with no reference-consuming op (zlist entries)
-    u32 n_spliced;    // spliced records appended to the name-code list
-    u32 max_buffered; // max over unspliced records of the pileup's buffered-record upper bound (cap detection)
-    u32 n_unspliced;  // unspliced mapped records with a reference span
-    u32 hot_first, hot_last; // first / last record ordinal whose bound reaches the cap
-    u32 n_dropped;
-    u32 _pad;
-};
 
 // KX1: one thread per record (every record of the contig).  Classifies the record as the reference's
 // separateBams does, records its position / exclusive end for the rank queries, counts its end in `ce`
 // and adds its M / = / X runs to the depth difference array; the name codes of spliced records are appended
 // (order is irrelevant: they only feed a multiset).
-#ifdef PJB_KERNELS_EXTRA
 __global__ __launch_bounds__(256) void kx_classify(DevBatch b, int32_t ref_len, int32_t *x_pos,
                                                     int32_t *x_endx, uint8_t *q_flag, u32 *ce, int32_t *dd, u32 *zlist,
                                                     u32 zcap, ExtraCounters *cnt) {
@@ -119,13 +72,11 @@ __global__ __launch_bounds__(256) void kx_classify(DevBatch b, int32_t ref_len, 
         }
     }
 }
-#endif // PJB_KERNELS_EXTRA
 
 // The name codes of the spliced records, in BAM order, without a single atomic: k1_count left, per 1024-record tile,
 // the ordered list of its spliced records (spl_idx) and their number (tile_stats); one block scans the tile counts,
 // then a block per tile copies its records' codes to the tile's place.  (A wave-aggregated atomicAdd on one counter
 // per wavefront of records cost 1.1 ms per 10 M records: 156 k returning atomics on ONE address.)
-#ifdef PJB_KERNELS_EXTRA
 __global__ __launch_bounds__(1024) void kx_spliced_offsets(const TileStats *ts, u32 n_tiles, u32 *off, ExtraCounters *cnt) {
     __shared__ u32 wsum[16];
     __shared__ u32 carry_s;
@@ -152,37 +103,11 @@ __global__ __launch_bounds__(1024) void kx_spliced_offsets(const TileStats *ts, 
     }
     if (threadIdx.x == 0) cnt->n_spliced = carry_s;
 }
-#endif // PJB_KERNELS_EXTRA
-#ifdef PJB_KERNELS_EXTRA
 __global__ __launch_bounds__(256) void kx_spliced_codes(DevBatch b, const TileStats *ts, const u32 *spl_idx, const u32 *off, u64 *spl_codes) {
     const u32 tile = b.tile_base + blockIdx.x;
     const u32 nspl = ts[tile].spliced, o = off[tile];
     for (u32 ks = threadIdx.x; ks < nspl; ks += 256) spl_codes[o + ks] = b.name_hash[spl_idx[(size_t)tile * K1_TILE + ks]];
 }
-#endif // PJB_KERNELS_EXTRA
-
-
-// scan functors -----------------------------------------------------------------------------------------------
-struct ArrU32Fn {
-    const u32 *a;
-    __device__ u64 operator()(u64 i) const { return a[i]; }
-};
-struct ArrU8Fn {
-    const uint8_t *a;
-    __device__ u64 operator()(u64 i) const { return a[i]; }
-};
-struct ArrI32Fn { // signed terms, summed modulo 2^64
-    const int32_t *a;
-    __device__ u64 operator()(u64 i) const { return (u64)(int64_t)a[i]; }
-};
-struct ExclusiveU32Sink { // out[i] = sum of the terms before i (may alias the input)
-    u32 *out;
-    __device__ void operator()(u64 i, u64, u64 ex) const { out[i] = (u32)ex; }
-};
-struct InclusiveU32Sink { // out[i] = sum of the terms up to and including i (may alias the input)
-    u32 *out;
-    __device__ void operator()(u64 i, u64 v, u64 ex) const { out[i] = (u32)(ex + v); }
-};
 
 // KX3: the pileup's record cap.  bam_plp_push (sam.c:1906) drops a record that starts where the iterator
 // stands -- the start of the last record it kept -- while more than maxcnt list nodes exist: the kept records
@@ -190,7 +115,6 @@ struct InclusiveU32Sink { // out[i] = sum of the terms up to and including i (ma
 // endpos >= pos_i, kept or not = (unspliced records before i) - (unspliced records with endpos < pos_i).  If
 // the bound stays below maxcnt - 1 everywhere, nothing is dropped and the difference array already holds the
 // reference's depth (the normal case: it takes 8000-fold coverage of unspliced records).
-#ifdef PJB_KERNELS_EXTRA
 __global__ __launch_bounds__(256) void kx_cap_bound(const int32_t *x_pos, const uint8_t *q_flag, const u32 *prefix_q,
                                                      const u32 *pe, u32 n, int32_t ref_len, u32 *bound, ExtraCounters *cnt) {
     const u32 g = blockIdx.x * 256 + threadIdx.x;
@@ -213,13 +137,11 @@ __global__ __launch_bounds__(256) void kx_cap_bound(const int32_t *x_pos, const 
         atomicMax(&cnt->hot_last, g);
     }
 }
-#endif // PJB_KERNELS_EXTRA
 
 // KX3b: exact replay of the cap over the span of records whose bound reaches it (outside the span every record
 // is kept whatever happened before: its list is at most its bound).  Sequential by nature -- whether a record is
 // kept depends on which earlier ones were -- so one lane walks the span; `de` (zeroed, ref_len + 2 entries)
 // counts dropped records by endpos.  Kept records inside the list = bound - dropped records still inside.
-#ifdef PJB_KERNELS_EXTRA
 __global__ void kx_cap_replay(const int32_t *x_pos, const int32_t *x_endx, const uint8_t *q_flag, const u32 *bound, u32 n,
                               int32_t ref_len, u32 *de, uint8_t *dropped, ExtraCounters *cnt) {
     if (blockIdx.x != 0 || threadIdx.x != 0) return;
@@ -251,10 +173,8 @@ __global__ void kx_cap_replay(const int32_t *x_pos, const int32_t *x_endx, const
     }
     cnt->n_dropped = dtotal;
 }
-#endif // PJB_KERNELS_EXTRA
 
 // KX3c: take the dropped records' M / = / X runs back out of the difference array (before the scan).
-#ifdef PJB_KERNELS_EXTRA
 __global__ __launch_bounds__(256) void kx_undo_dropped(DevBatch b, int32_t ref_len, const uint8_t *dropped, int32_t *dd) {
     const int64_t r = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (r >= b.n || !dropped[b.base + (u32)r]) return;
@@ -275,7 +195,6 @@ __global__ __launch_bounds__(256) void kx_undo_dropped(DevBatch b, int32_t ref_l
         if (op_consumes_ref(ty)) x += ln;
     }
 }
-#endif // PJB_KERNELS_EXTRA
 
 __device__ __forceinline__ u32 lower_bound_i32(const int32_t *a, u32 n, int32_t v) { // first index with a[i] >= v
     u32 lo = 0, hi = n;
@@ -287,13 +206,6 @@ __device__ __forceinline__ u32 lower_bound_i32(const int32_t *a, u32 n, int32_t 
     return lo;
 }
 
-struct ExtraRow { // what pjb_extra_finish hands back, parallel to the junction rows
-    double mm_score, coverage;
-    u32 up_aln, down_aln;
-    u32 m_sum; // sum of name multiplicities (uint32 arithmetic as in junction.cc:916-919)
-    u32 _pad;
-};
-
 // KX4: flanking alignment counts, one thread per junction (processJunctionVicinity, junction.cc:651-677):
 //   up   = unspliced records with  intron.start > pos  and  leftAncStart <= getEnd()
 //   down = unspliced records with  rightAncEnd >= pos  and  intron.end < pos
@@ -303,7 +215,6 @@ struct ExtraRow { // what pjb_extra_finish hands back, parallel to the junction 
 // with getEnd() < x.  The reference's region query (sam_itr_queryi over [left - maxQueryLength - 1, right +
 // maxQueryLength + 1)) cannot exclude a record either test accepts.  Records without a reference span
 // (getEnd() == pos - 1) are tested one by one from `zlist`.
-#ifdef PJB_KERNELS_EXTRA
 __global__ __launch_bounds__(256) void kx_flank(const pjb_junction_row *rows, u32 n_rows, const int32_t *x_pos, u32 n_reads,
                                                  const u32 *prefix_q, const u32 *pe, int32_t ref_len, const u32 *zlist,
                                                  const ExtraCounters *cnt, u32 zcap, ExtraRow *out) {
@@ -324,10 +235,8 @@ __global__ __launch_bounds__(256) void kx_flank(const pjb_junction_row *rows, u3
     out[j].up_aln = up;
     out[j].down_aln = down;
 }
-#endif // PJB_KERNELS_EXTRA
 
 // KX5: per sorted pair, the name code of its record and the global row it belongs to (kept until pjb_extra_finish)
-#ifdef PJB_KERNELS_EXTRA
 __global__ __launch_bounds__(256) void kx_pair_codes(const u32 *sidx, const u32 *jid_of, const u32 *pair_g, const DevBatch *batches,
                                                       int n_batches, u32 n, u32 row_base,
                                                       u64 *pair_code, u32 *pair_row) {
@@ -339,7 +248,6 @@ __global__ __launch_bounds__(256) void kx_pair_codes(const u32 *sidx, const u32 
     pair_code[i] = batches[bi].name_hash[g - batches[bi].base];
     pair_row[i] = row_base + jid_of[i];
 }
-#endif // PJB_KERNELS_EXTRA
 
 // ---- the sparse path (round 3): no array of the target's length --------------------------------------------------
 // The depth of the unspliced records is only ever READ at 42 positions per junction (Junction::calcCoverage,
@@ -356,7 +264,6 @@ __global__ __launch_bounds__(256) void kx_pair_codes(const u32 *sidx, const u32 
 // above instead.
 // (SparseCounters, XOut: pjb_kernels.hip.h -- k1_count writes them when the records go through it; kx_classify_sparse is
 // the same classification for the records of a target that went through k1_walk)
-#ifdef PJB_KERNELS_EXTRA
 __global__ __launch_bounds__(256) void kx_classify_sparse(DevBatch b, int32_t *s_pos, int32_t *s_end, uint8_t *q_flag, u32 *zlist, u32 zcap,
                                                            SparseCounters *cnt) {
     const int64_t r = (int64_t)blockIdx.x * 256 + threadIdx.x;
@@ -403,7 +310,6 @@ __global__ __launch_bounds__(256) void kx_classify_sparse(DevBatch b, int32_t *s
     }
     if (many) atomicOr(&cnt->need_dense, 2u);
 }
-#endif // PJB_KERNELS_EXTRA
 
 // one scan over the records: (records with a span) | (gaps) << 32
 struct SparseFn {
@@ -412,9 +318,6 @@ struct SparseFn {
         const u32 v = q[i];
         return (u64)(v & 1u) | ((u64)(v >> 1) << 32);
     }
-};
-struct Gap {
-    int32_t start, end; // [start, end)
 };
 struct SparseSink { // the records with a span, compacted in rank order; gaps before every 256th record and every 256th rank
     int32_t *comp_pos, *comp_end;
@@ -433,7 +336,6 @@ struct SparseSink { // the records with a span, compacted in rank order; gaps be
 };
 // the gaps (D operations) of the unspliced records in record order: a block per 256 records (global ordinals, so that
 // gapoff[block] is the block's first entry), an exclusive scan of the records' gap counts inside the block
-#ifdef PJB_KERNELS_EXTRA
 __global__ __launch_bounds__(256) void kx_gaps(DevBatch b, const uint8_t *q, u32 n_total, const u32 *gapoff, Gap *gaps, u32 gap_cap, SparseCounters *cnt,
                                                 u32 n_blocks) {
     __shared__ u32 wsum[4];
@@ -465,17 +367,14 @@ __global__ __launch_bounds__(256) void kx_gaps(DevBatch b, const uint8_t *q, u32
         }
     }
 }
-#endif // PJB_KERNELS_EXTRA
 
 // the pileup's cap can only bite where PLP_MAXCNT - 1 records with a span start within max_span bases of each other
-#ifdef PJB_KERNELS_EXTRA
 __global__ __launch_bounds__(256) void kx_cap_check(const int32_t *comp_pos, SparseCounters *cnt) {
     const u32 n = (u32)cnt->total, K = PLP_MAXCNT - 1;
     const u32 r = blockIdx.x * 256 + threadIdx.x + K;
     if (r >= n) return;
     if ((int64_t)comp_pos[r] - (int64_t)comp_pos[r - K] <= (int64_t)cnt->max_span) atomicOr(&cnt->need_dense, 1u);
 }
-#endif // PJB_KERNELS_EXTRA
 
 __device__ __forceinline__ u32 lower_bound_i64(const int32_t *a, u32 n, int64_t v) { // first index with a[i] >= v
     u32 lo = 0, hi = n;
@@ -526,7 +425,6 @@ __device__ __forceinline__ void ranges_sum2(u32 i0, u32 i1, const Win w, F acc, 
 // KX4 without the ends histogram: a thread per junction.
 //   #{getEnd() < x} = (records with a span that start before x - max_span: all of them) + (those among the records starting
 //   in [x - max_span, x) whose last base lies before x); a record starting at or after x ends at or after x.
-#ifdef PJB_KERNELS_EXTRA
 __global__ __launch_bounds__(256) void kx_flank_sparse(const pjb_junction_row *rows, u32 n_rows, const int32_t *s_pos, const int32_t *s_end,
                                                         int32_t ref_len, const u32 *zlist, const SparseCounters *cnt, u32 zcap, ExtraRow *out) {
     const u32 n_reads = (u32)cnt->total; // (s_pos / s_end: the records with a span only, in rank order)
@@ -562,16 +460,7 @@ __global__ __launch_bounds__(256) void kx_flank_sparse(const pjb_junction_row *r
     out[j].up_aln = up;
     out[j].down_aln = down;
 }
-#endif // PJB_KERNELS_EXTRA
 
-// what a target keeps for pjb_extra_finish (device pointers): the records with a span in rank order, their gaps (record
-// order = rank order) and the number of gaps before every 256th of them
-struct SparseDepth {
-    const int32_t *s_pos, *s_end;
-    const Gap *gaps;
-    const u32 *gapoff;
-    u32 n_reads, n_gaps, max_span, max_gap;
-};
 __device__ __forceinline__ u32 span_overlap(int64_t x0, int64_t x1, int32_t plo, int32_t phi) { // |[x0, x1) n [plo, phi]|
     const int64_t lo = x0 > plo ? x0 : (int64_t)plo, hi = (x1 - 1) < phi ? (x1 - 1) : (int64_t)phi;
     return hi >= lo ? (u32)(hi - lo + 1) : 0u;
@@ -616,7 +505,6 @@ __device__ __forceinline__ void sparse_cov2(const SparseDepth D, int32_t len, bo
     sum2 = s2 - m2;
 }
 // Junction::calcCoverage (junction.cc:923-951) from a target's records instead of its depth vector: a thread per junction
-#ifdef PJB_KERNELS_EXTRA
 __global__ __launch_bounds__(256) void kx_coverage_sparse(const pjb_junction_row *rows, u32 row0, u32 n, SparseDepth D, int32_t len_src, ExtraRow *out) {
     const u32 k = blockIdx.x * 256 + threadIdx.x;
     const bool on = k < n;
@@ -631,7 +519,6 @@ __global__ __launch_bounds__(256) void kx_coverage_sparse(const pjb_junction_row
     const double acceptor = (1.0 / 10.0) * (double)a1 - (1.0 / 9.0) * (double)a2;
     out[j].coverage = donor + acceptor;
 }
-#endif // PJB_KERNELS_EXTRA
 
 // ---- phase 2 (all contigs done) ---------------------------------------------------------------------------
 constexpr u64 NAME_EMPTY = ~0ull;
@@ -661,17 +548,14 @@ __device__ __forceinline__ void name_add(NameSlot *tab, u32 slots, u64 key, u32 
     }
 }
 // the table has grown: every name of the old one into the new one
-#ifdef PJB_KERNELS_EXTRA
 __global__ __launch_bounds__(256) void kx_name_rehash(const NameSlot *old_tab, u32 old_slots, NameSlot *tab, u32 slots) {
     const u32 i = blockIdx.x * 256 + threadIdx.x;
     if (i >= old_slots) return;
     const NameSlot o = old_tab[i];
     if (o.key != NAME_EMPTY) name_add(tab, slots, o.key, o.count + 1u);
 }
-#endif // PJB_KERNELS_EXTRA
 // M of every junction: sum over its alignments of the map entry of their code (junction.cc:916-919, uint32).  Four pairs
 // per thread, a wavefront's 256 consecutive pairs in four rounds: the four random probes of a thread are in flight together.
-#ifdef PJB_KERNELS_EXTRA
 __global__ __launch_bounds__(256) void kx_name_sum(const u64 *pair_code, const u32 *pair_row, u32 n, const NameSlot *tab, u32 slots, ExtraRow *out) {
     const u32 base = (blockIdx.x * 4 + (threadIdx.x >> 6)) * 256 + (u32)lane_id();
     u64 key[4];
@@ -706,9 +590,7 @@ __global__ __launch_bounds__(256) void kx_name_sum(const u64 *pair_code, const u
         if (i < n && (lane_id() == 0 || prev != row[k])) atomicAdd(&out[row[k]].m_sum, cc);
     }
 }
-#endif // PJB_KERNELS_EXTRA
 // four codes per thread into the table (the probes of a thread in flight together)
-#ifdef PJB_KERNELS_EXTRA
 __global__ __launch_bounds__(256) void kx_name_insert4(const u64 *codes, u32 n, NameSlot *tab, u32 slots) {
     const u32 base = (blockIdx.x * 4 + (threadIdx.x >> 6)) * 256 + (u32)lane_id();
     u64 key[4];
@@ -730,7 +612,6 @@ __global__ __launch_bounds__(256) void kx_name_insert4(const u64 *codes, u32 n, 
         else name_add(tab, slots, key[k], 1u);
     }
 }
-#endif // PJB_KERNELS_EXTRA
 
 // Junction::calcCoverage (junction.cc:923-951) for the rows [row0, row0 + n) against the depth vector of one
 // target: levels[i] = cover[i - 1] (DepthParser stores a position's depth at pos + 1, depth_parser.cc:127,147),
@@ -742,7 +623,6 @@ __device__ __forceinline__ double cov_window(const u32 *cover, int32_t len, int3
         if (i >= 1 && i < len) readCount += cover[i - 1];
     return multiplier * (double)readCount;
 }
-#ifdef PJB_KERNELS_EXTRA
 __global__ __launch_bounds__(256) void kx_coverage(const pjb_junction_row *rows, u32 row0, u32 n, const u32 *cover, int32_t len_src, ExtraRow *out) {
     const u32 k = blockIdx.x * 256 + threadIdx.x;
     if (k >= n) return;
@@ -752,9 +632,7 @@ __global__ __launch_bounds__(256) void kx_coverage(const pjb_junction_row *rows,
     const double acceptor = cov_window(cover, len_src, e + 10, e + 20) - cov_window(cover, len_src, e, e + 9);
     out[j].coverage = donor + acceptor;
 }
-#endif // PJB_KERNELS_EXTRA
 // the finished columns of every junction, in the layout pjb_extra_finish hands out (mm_score = N / M, junction.cc:920)
-#ifdef PJB_KERNELS_EXTRA
 __global__ __launch_bounds__(256) void kx_rows_out(const pjb_junction_row *rows, const ExtraRow *x, u32 n, pjb_extra_row *out) {
     const u32 j = blockIdx.x * 256 + threadIdx.x;
     if (j >= n) return;
@@ -765,7 +643,6 @@ __global__ __launch_bounds__(256) void kx_rows_out(const pjb_junction_row *rows,
     o.down_aln = x[j].down_aln;
     out[j] = o;
 }
-#endif // PJB_KERNELS_EXTRA
 
 // ---- filt feature rows: ModelFeatures::setRow, lib/src/model_features.cc:161-212 ------------------
 struct DevModels {
@@ -817,7 +694,6 @@ __device__ double pos_score(const double *tab, const uint8_t *g, int32_t glen, i
     if (score == 0.0) return -300.0;
     return log(score);
 }
-#ifdef PJB_KERNELS_EXTRA
 __global__ __launch_bounds__(256) void kg_features(const pjb_junction_row *rows, u32 n, const GenomeRef *genomes, int n_refs, DevModels M,
                                                     double mean_read_length, u32 l95, double *out, int *bad) {
     const u32 r = blockIdx.x * 256 + threadIdx.x;
@@ -874,12 +750,10 @@ __global__ __launch_bounds__(256) void kg_features(const pjb_junction_row *rows,
         f[14 + i] = log2(Ni / Ei);
     }
 }
-#endif // PJB_KERNELS_EXTRA
 
 // ---- bamfilt: BamFilter::filter's decision per alignment, src/bam_filter.cc:75-150,190-225.
 // The walk is the reference's, including that it does not advance over an N operation (only the else-branch of
 // :86-96 adds to lEnd): the introns after a read's first one are looked up short of the earlier introns' lengths.
-#ifdef PJB_KERNELS_EXTRA
 __global__ __launch_bounds__(256) void kf_filter(const int32_t *pos, const u32 *cig_off, const u32 *cigar, u32 n, const u64 *keys, u32 n_keys,
                                                   int clip_mode, uint8_t *codes) {
     const u32 i = blockIdx.x * 256 + threadIdx.x;
@@ -912,6 +786,5 @@ __global__ __launch_bounds__(256) void kf_filter(const int32_t *pos, const u32 *
     }
     codes[i] = code;
 }
-#endif // PJB_KERNELS_EXTRA
 
 } // namespace pjb

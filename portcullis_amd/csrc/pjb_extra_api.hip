@@ -1,7 +1,7 @@
 // pjb_extra_api.hip -- the part of the C ABI behind `junc --extra` (depth, flanking counts, name multiplicities: pjb_extra_finish), `bamfilt`
 // (pjb_filter_*) and `filt`'s feature rows (pjb_filt_features); kernels in pjb_extra.hip.h.
-#define PJB_KERNELS_EXTRA 1
 #include "pjb_host.hip.h"
+#include "pjb_extra.hip.h"
 
 static int extra_contig_dense(pjb_ctx *c, int32_t tid, std::vector<DevBatch> &batches, int64_t n_reads, u64 n_spliced, u32 P, u32 J,
                               const u32 *sidx, const u32 *jid_sorted, const u32 *pair_g, size_t row_base, bool codes_in_table) {

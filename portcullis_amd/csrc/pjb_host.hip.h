@@ -1,11 +1,12 @@
 // pjb_host.hip.h -- what the translation units of the C ABI share: the context (pjb_ctx) and its parts, error / allocation / launch helpers.
 // The library is built from three units -- pjb_api.hip (contexts, uploads, batches, the kernel chains: pjb_kernels.hip.h), pjb_extra_api.hip
 // (--extra, bamfilt, filt features: pjb_extra.hip.h) and pjb_ingest_api.hip (BGZF inflate / deflate, BAM records: pjb_ingest.hip.h, pjb_deflate.hip.h) --
-// each of which compiles its own kernel family (the non-template kernels of a header are guarded by PJB_KERNELS_CHAIN / PJB_KERNELS_EXTRA), so an edit to
-// one family rebuilds one unit.  Helpers are inline functions of this header: one definition, one set of thread-local error strings for all units.
+// each of which includes its own kernel family behind this header and so is the only unit that compiles it; this header includes only what the
+// units share (pjb_device.hip.h, pjb_extra_types.hip.h).  (The Makefile makes every header a prerequisite of every unit: an edit to any of them
+// rebuilds the library.)  Helpers are inline functions of this header: one definition, one set of thread-local error strings for all units.
 #pragma once
-#include "pjb_kernels.hip.h"
-#include "pjb_extra.hip.h"
+#include "pjb_device.hip.h"
+#include "pjb_extra_types.hip.h"
 
 #include <algorithm>
 #include <sys/mman.h>

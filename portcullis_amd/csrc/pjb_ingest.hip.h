@@ -11,6 +11,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "pjb_extra_types.hip.h" // (derive_name_hash: the transcoder computes the records' name codes)
+
 namespace pjb {
 
 typedef unsigned long long iu64;

@@ -15,524 +15,13 @@
 // References in comments are file:line in the reference checkout.
 #pragma once
 
-#include <hip/hip_runtime.h>
-#include <stdint.h>
-
-#include "../../include/portcullis_amd.h"
+#include "pjb_device.hip.h"
 
 namespace pjb {
-
-typedef unsigned long long u64;
-typedef unsigned int u32;
-
-// ---------------------------------------------------------------------------------------------
-// device-side structures
-// ---------------------------------------------------------------------------------------------
-struct DevBatch {
-    const int32_t *pos;
-    const uint16_t *flag;
-    const uint8_t *mapq;
-    const uint8_t *xs;
-    const int32_t *l_qseq;
-    const int32_t *mtid;
-    const int32_t *mpos;
-    const uint32_t *cig_off;
-    const uint32_t *cigar;
-    const uint32_t *seq_off;
-    const uint8_t *seq4;
-    const u64 *name_hash; // --extra only (nullptr otherwise)
-    int64_t n;
-    uint32_t base;      // global read ordinal of record 0 within the contig
-    uint32_t tile_base; // first K1 tile index of this batch
-    int32_t prev_pos;   // pos of the last record of the previous batch (sortedness across batches)
-    int32_t member;     // the batch's target: its index among the chain's members (GroupTab)
-    const int32_t *prev_pos_ptr; // where that position is, when only the device knows it (nullptr: prev_pos holds it)
-    const uint32_t *seq2;        // pjb_batch.seq2 seen as words (two 16-bit granules each; nullptr: the batch has 4-bit bases only)
-    const uint32_t *seq_exc;     // pjb_batch.seq_exc
-};
-
-// error word: min over (ordinal << 8 | -code); ~0 = no error
-__device__ inline void set_error(u64 *err, u32 ordinal, int code) {
-    atomicMin(err, ((u64)ordinal << 8) | (u64)(u32)(-code));
-}
-
-struct TileStats { // per K1 tile
-    u32 spliced, unspliced;
-    u64 sum_len;
-    int32_t min_len, max_len;
-    int32_t max_end;   // max(pos + alignedLength)
-    int32_t max_nlen;  // longest N op
-    int32_t min_pos;
-    int32_t _pad;
-};
-
-// Per-contig control block in device memory.  The host sizes buffers and grids from LIMITS it chooses before anything
-// runs (pairs, junctions, key format); the kernels read the actual counts from here, and a count that exceeds its limit
-// raises an overflow bit and zeroes the count so that everything downstream does nothing.  pjb_finish_contig reads the
-// block back once, at the end, and repeats the contig with larger limits if a bit is set.
-enum : u32 { OVF_PAIRS = 1u, OVF_KEYFMT = 2u, OVF_JUNC = 4u, OVF_DENSE = 8u, OVF_LISTS = 16u };
-struct ContigStats {
-    u64 spliced, unspliced, sum_len;
-    int32_t min_len, max_len;
-    int32_t max_end, max_nlen, min_pos;
-    u32 n_tiles;
-    u64 n_pairs;   // pairs found (whatever the limit)
-    u64 err;
-    u32 n_junc, n_runs; // junctions / position runs found (whatever the limit)
-    u32 P;         // pairs the pipeline works on: n_pairs, or 0 after an overflow
-    u32 J, R;      // junctions / runs the pipeline works on
-    u32 n_slots;   // J + ceil(P / 64) fragment slots
-    u32 overflow;  // OVF_*
-    u32 n_cand;    // K2d: keys in the candidate list (every junction at least once, few of them more often)
-    u32 n_slices;  // ceil(P / 64): 64-pair slices of the sorted pair array (fragments, run masks)
-    u32 list_need; // OVF_LISTS: the fullest sub-list of the read lists (EmitLists) wanted this many entries
-};
-
-// A pair = one N operation walked (JunctionSystem::addJunctions, junction_system.cc:140-210).  k1_emit writes, in BAM order,
-// the pair's intron key (its own array: kd_assign and the sort's first pass stream over the keys alone) and ONE 32-byte record
-// with everything the per-junction reductions need; every later kernel that works in sorted order fetches a pair with one
-// 32-byte gather (two 16-byte loads from one sector).
-struct __attribute__((aligned(16))) PairRec {
-    u64 aux;         // per-pair match statistics (pack_res): written by k1_emit for the [S] M N M [S] shape, by k4b_generic for the rest
-    int32_t lstart;  // lStart  (left anchor start of this pair)
-    int32_t rend;    // rEndExc-1
-    int32_t pos;     // read position   (entropy / distinct-alignment runs)
-    int32_t aend;    // read end = pos + alignedLength - 1
-    u32 meta;        // bit field, see META_*
-    u32 updown;      // upjuncs | downjuncs << 16
-};
-static_assert(sizeof(PairRec) == 32, "PairRec is one 32-byte sector");
-struct Pairs {
-    u64 *key;     // packed intron key (see make_key), BAM order
-    PairRec *rec; // BAM order
-    u32 *g;       // global read ordinal of the pair's record -- written for PJB_FLAG_EXTRA contexts only (nullptr otherwise)
-};
-__device__ __forceinline__ void rec_store(PairRec *dst, const PairRec &r) {
-    uint4 *q = reinterpret_cast<uint4 *>(dst);
-    q[0] = make_uint4((u32)r.aux, (u32)(r.aux >> 32), (u32)r.lstart, (u32)r.rend);
-    q[1] = make_uint4((u32)r.pos, (u32)r.aend, r.meta, r.updown);
-}
-__device__ __forceinline__ PairRec rec_load(const PairRec *src) {
-    const uint4 *q = reinterpret_cast<const uint4 *>(src);
-    const uint4 a = q[0], b = q[1];
-    PairRec r;
-    r.aux = (u64)a.x | ((u64)a.y << 32);
-    r.lstart = (int32_t)a.z;
-    r.rend = (int32_t)a.w;
-    r.pos = (int32_t)b.x;
-    r.aend = (int32_t)b.y;
-    r.meta = b.z;
-    r.updown = b.w;
-    return r;
-}
-
-enum : u32 {
-    META_CAT_MASK = 3u,      // 0 r1pos, 1 r1neg, 2 r2pos, 3 r2neg   (junction.cc:483-498)
-    META_MULTI = 1u << 2,    // read has > 1 N op                    (junction.cc:499)
-    META_XS_SHIFT = 3,       // 2 bits: 0 unknown, 1 '+', 2 '-'
-    META_UM = 1u << 5,       // mapq >= 30                           (junction.cc:773)
-    META_BPP = 1u << 6,      // BAM proper-pair flag                 (junction.cc:780)
-    META_PPP = 1u << 7,      // calcIfProperPair                     (junction.cc:784)
-    META_REL = 1u << 8,      // reliable                             (junction.cc:792)
-    META_SIMPLE = 1u << 9,   // CIGAR is [S] M N M [S] and l_qseq matches it: both anchors are single contiguous compares
-                             // that do not depend on the junction-level window (k1_emit compares them itself)
-};
-// per-pair match statistics packed in 64 bits: minMatch | mmes << 20 | mismatches << 40
-__device__ __forceinline__ u64 pack_res(u32 minMatch, u32 mmes, u32 mis) {
-    return (u64)(minMatch & 0xfffffu) | ((u64)(mmes & 0xfffffu) << 20) | ((u64)mis << 40);
-}
-constexpr u32 RES_FIELD_MAX = 0xfffffu; // anchors longer than this take the generic path
-
-// ---------------------------------------------------------------------------------------------
-// Target GROUPS ("super-chains").  A chain of 45 kernels over one 8 M-read target leaves most of the chip idle in most of
-// its kernels; several targets finished together are ONE chain over a virtual sequence in which member i occupies
-// [voff_i, voff_i + len_i) (offsets 64-aligned, a gap between members).  k1_emit adds the offset to every coordinate it
-// emits, so keys, sort, grouping, anchors and reductions never see the difference -- an intron key still names one
-// junction of one target, and key order is (member, start, end).  Only what touches a target's OWN data converts back:
-// the genome of a pair / junction (k1_generic, k4b_generic, k5_finalize look the member up by index / position) and the rows
-// (refid, local coordinates).  A single target is a group of one with offset 0.
-// ---------------------------------------------------------------------------------------------
-constexpr int GROUP_MAX = 32;
-constexpr int32_t GROUP_GAP = 4096;
-struct GroupTab {
-    int32_t n;
-    int32_t voff[GROUP_MAX]; // ascending
-    int32_t len[GROUP_MAX];
-    int32_t tid[GROUP_MAX];
-    const uint8_t *d[GROUP_MAX];   // upper-cased bases
-    const u32 *codes[GROUP_MAX];   // 4-bit codes (nullptr: exotic member)
-    const u32 *codes2[GROUP_MAX];  // 2-bit codes and, behind them, the bitmap of the 64-base stretches that hold a character outside ACGT
-                                   // (k0_encode2; nullptr with codes)
-    u32 exc_members;               // bit m: member m's bitmap has a bit set at all (else k1_emit does not look at it)
-};
-struct Member {
-    int32_t idx, voff, len, tid;
-    const uint8_t *d;
-    const u32 *codes;
-};
-__device__ __forceinline__ Member member_of(const GroupTab &T, int32_t vpos) {
-    int m = 0;
-    if (T.n > 1) {
-#pragma unroll
-        for (int s = GROUP_MAX / 2; s >= 1; s >>= 1)
-            if (m + s < T.n && T.voff[m + s] <= vpos) m += s;
-    }
-    Member M;
-    M.idx = m;
-    M.voff = T.voff[m];
-    M.len = T.len[m];
-    M.tid = T.tid[m];
-    M.d = T.d[m];
-    M.codes = T.codes[m];
-    return M;
-}
-// per-member counters of a group (what pjb_region_result reports per target)
-struct MemberStats {
-    u64 spliced, unspliced, sum_len, n_pairs;
-    int32_t min_len, max_len;
-    u32 n_junc, _pad;
-};
-
-// key packing: normal case (start << lbits) | intron_len, fallback raw (start << 32) | (u32)end
-struct KeyFmt {
-    int raw;   // 1 = raw 64-bit (weird coordinates present)
-    int lbits; // bits of intron length
-    int total_bits;
-};
-__device__ __host__ inline u64 make_key(const KeyFmt &f, int32_t istart, int32_t iend) {
-    if (f.raw) return ((u64)(u32)istart << 32) | (u64)(u32)iend;
-    return ((u64)(u32)istart << f.lbits) | (u64)(u32)(iend - istart + 1);
-}
-__device__ __host__ inline void unpack_key(const KeyFmt &f, u64 k, int32_t &istart, int32_t &iend) {
-    if (f.raw) {
-        istart = (int32_t)(u32)(k >> 32);
-        iend = (int32_t)(u32)k;
-    } else {
-        istart = (int32_t)(u32)(k >> f.lbits);
-        iend = istart + (int32_t)(u32)(k & ((1ull << f.lbits) - 1)) - 1;
-    }
-}
-
-// CIGAR op classes by BAM op code "MIDNSHP=XB" (bam_alignment.hpp:75-99)
-__device__ __forceinline__ bool op_consumes_ref(u32 op) { return (0x18Du >> op) & 1u; }   // M D N = X
-__device__ __forceinline__ bool op_consumes_query(u32 op) { return (0x193u >> op) & 1u; } // M I S = X
-enum : u32 { OP_M = 0, OP_I = 1, OP_D = 2, OP_N = 3, OP_S = 4, OP_H = 5, OP_P = 6, OP_EQ = 7, OP_X = 8 };
-
-// ---------------------------------------------------------------------------------------------
-// wave / block primitives (wave = 64 lanes)
-// ---------------------------------------------------------------------------------------------
-__device__ __forceinline__ int lane_id() { return threadIdx.x & 63; }
-// A barrier that orders LDS traffic only.  __syncthreads() is a workgroup-scope fence as well: hipcc drains vmcnt before it, which
-// makes a wave wait for every load it has in flight and for its STORES to be acknowledged -- k1_emit keeps the next trip's loads in
-// flight across its barriers on purpose.  Nothing that other waves of the block read from global memory may depend on this.
-__device__ __forceinline__ void lds_barrier() {
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    __builtin_amdgcn_s_barrier();
-    asm volatile("" ::: "memory");
-}
-
-// A pointer that was READ from memory (a batch descriptor, a pair's sequence address) is a generic pointer to the compiler:
-// its loads are flat_load, which count against the LDS counter too and are waited for one by one.  Everything such pointers
-// name here is device memory: gload reads through a global pointer.
-template <class T>
-__device__ __forceinline__ T gload(const T *p) {
-    T v;
-    __builtin_memcpy(&v, (const __attribute__((address_space(1))) void *)p, sizeof(T));
-    return v;
-}
-// A batch descriptor fetched from device memory (one launch per chain: the block looks its batch up): the same fields as
-// pointers into GLOBAL memory, so that what is read through them are global_load / s_load instructions.
-#define PJB_GLOBAL __attribute__((address_space(1)))
-template <class T>
-__device__ __forceinline__ const PJB_GLOBAL T *as_global(const T *p) {
-    return (const PJB_GLOBAL T *)p;
-}
-template <class T, class U>
-__device__ __forceinline__ T gload_as(const PJB_GLOBAL U *p) { // a T at a global address
-    T v;
-    __builtin_memcpy(&v, (const PJB_GLOBAL void *)p, sizeof(T));
-    return v;
-}
-struct GBatch {
-    const PJB_GLOBAL int32_t *pos;
-    const PJB_GLOBAL uint16_t *flag;
-    const PJB_GLOBAL uint8_t *mapq;
-    const PJB_GLOBAL uint8_t *xs;
-    const PJB_GLOBAL int32_t *l_qseq;
-    const PJB_GLOBAL int32_t *mtid;
-    const PJB_GLOBAL int32_t *mpos;
-    const PJB_GLOBAL uint32_t *cig_off;
-    const PJB_GLOBAL uint32_t *cigar;
-    const PJB_GLOBAL uint32_t *seq_off;
-    const PJB_GLOBAL uint8_t *seq4;
-    int64_t n;
-    uint32_t base, tile_base;
-    int32_t prev_pos, member;
-    const PJB_GLOBAL int32_t *prev_pos_ptr;
-    const PJB_GLOBAL uint32_t *seq2, *seq_exc;
-};
-#define PJB_CONSTANT __attribute__((address_space(4)))
-__device__ __forceinline__ GBatch load_batch(const DevBatch *d) { // (through the constant address space: a uniform index gives scalar loads)
-    const PJB_CONSTANT DevBatch *g = (const PJB_CONSTANT DevBatch *)d;
-    GBatch b;
-    b.pos = as_global(g->pos);
-    b.flag = as_global(g->flag);
-    b.mapq = as_global(g->mapq);
-    b.xs = as_global(g->xs);
-    b.l_qseq = as_global(g->l_qseq);
-    b.mtid = as_global(g->mtid);
-    b.mpos = as_global(g->mpos);
-    b.cig_off = as_global(g->cig_off);
-    b.cigar = as_global(g->cigar);
-    b.seq_off = as_global(g->seq_off);
-    b.seq4 = as_global(g->seq4);
-    b.n = g->n;
-    b.base = g->base;
-    b.tile_base = g->tile_base;
-    b.prev_pos = g->prev_pos;
-    b.member = g->member;
-    b.prev_pos_ptr = as_global(g->prev_pos_ptr);
-    b.seq2 = as_global(g->seq2);
-    b.seq_exc = as_global(g->seq_exc);
-    return b;
-}
-// four consecutive words at a 4-byte aligned address (global_load_dwordx4 accepts that)
-struct __attribute__((packed, aligned(4))) Words4 {
-    u32 x, y, z, w;
-};
-
-template <typename T>
-__device__ __forceinline__ T wave_sum(T v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
-    return v;
-}
-template <typename T>
-__device__ __forceinline__ T wave_max(T v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        T t = __shfl_down(v, o, 64);
-        v = t > v ? t : v;
-    }
-    return v;
-}
-template <typename T>
-__device__ __forceinline__ T wave_min(T v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        T t = __shfl_down(v, o, 64);
-        v = t < v ? t : v;
-    }
-    return v;
-}
-// inclusive scan across the wave
-template <typename T>
-__device__ __forceinline__ T wave_iscan(T v) {
-    int l = lane_id();
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        T t = __shfl_up(v, o, 64);
-        if (l >= o) v += t;
-    }
-    return v;
-}
-
-// Whole-wave reductions on the DPP path (no LDS traffic, one VALU instruction per step; __shfl_* goes through
-// ds_bpermute): quads, half rows, rows of 16, then row_bcast:15 / row_bcast:31 carry the row totals up -- the result
-// is in lane 63 and is read back as a scalar.  `IDENT` is what lanes that a step does not write contribute.
-template <int CTRL, int ROW_MASK>
-__device__ __forceinline__ u32 dpp_move(u32 ident, u32 v) {
-    return (u32)__builtin_amdgcn_update_dpp((int)ident, (int)v, CTRL, ROW_MASK, 0xf, false);
-}
-struct DppAdd {
-    static constexpr u32 ident = 0u;
-    __device__ __forceinline__ static u32 op(u32 a, u32 b) { return a + b; }
-};
-struct DppMax {
-    static constexpr u32 ident = 0u;
-    __device__ __forceinline__ static u32 op(u32 a, u32 b) { return a > b ? a : b; }
-};
-struct DppMin {
-    static constexpr u32 ident = 0xffffffffu;
-    __device__ __forceinline__ static u32 op(u32 a, u32 b) { return a < b ? a : b; }
-};
-template <typename Op>
-__device__ __forceinline__ u32 wave_total(u32 v) {
-    v = Op::op(v, dpp_move<0xB1, 0xf>(Op::ident, v));  // quad_perm [1,0,3,2]
-    v = Op::op(v, dpp_move<0x4E, 0xf>(Op::ident, v));  // quad_perm [2,3,0,1]
-    v = Op::op(v, dpp_move<0x141, 0xf>(Op::ident, v)); // row_half_mirror
-    v = Op::op(v, dpp_move<0x140, 0xf>(Op::ident, v)); // row_mirror: every lane of a row holds the row's result
-    v = Op::op(v, dpp_move<0x142, 0xa>(Op::ident, v)); // row_bcast:15 into rows 1 and 3
-    v = Op::op(v, dpp_move<0x143, 0xc>(Op::ident, v)); // row_bcast:31 into rows 2 and 3
-    return (u32)__builtin_amdgcn_readlane((int)v, 63);
-}
-
-// exclusive scan over the 256 threads of a block in thread order; returns exclusive prefix, total in *total.
-// smem: at least 4 elements of T.  Contains __syncthreads (call uniformly).
-template <typename T>
-__device__ __forceinline__ T block_escan_256(T v, T *smem, T *total) {
-    T inc = wave_iscan(v);
-    int w = threadIdx.x >> 6, l = lane_id();
-    __syncthreads();
-    if (l == 63) smem[w] = inc;
-    __syncthreads();
-    T base = 0, tot = 0;
-#pragma unroll
-    for (int i = 0; i < 4; i++) {
-        T s = smem[i];
-        if (i < w) base += s;
-        tot += s;
-    }
-    *total = tot;
-    return base + inc - v;
-}
-
-// the same over NW wavefronts (NW = 1: no barrier, no shared memory traffic)
-template <int NW, typename T, bool LDS_ONLY = false>
-__device__ __forceinline__ T block_escan(T v, T *smem, T *total) {
-    T inc = wave_iscan(v);
-    if constexpr (NW == 1) {
-        *total = __shfl(inc, 63, 64);
-        return inc - v;
-    } else {
-        int w = threadIdx.x >> 6, l = lane_id();
-        if constexpr (LDS_ONLY) lds_barrier();
-        else __syncthreads();
-        if (l == 63) smem[w] = inc;
-        if constexpr (LDS_ONLY) lds_barrier();
-        else __syncthreads();
-        T base = 0, tot = 0;
-#pragma unroll
-        for (int i = 0; i < NW; i++) {
-            T s = smem[i];
-            if (i < w) base += s;
-            tot += s;
-        }
-        *total = tot;
-        return base + inc - v;
-    }
-}
-
-// ---------------------------------------------------------------------------------------------
-// generic multi-block exclusive scan of u64 values produced by a functor (3 kernels)
-// ---------------------------------------------------------------------------------------------
-constexpr int SCAN_TILE = 2048; // 256 threads x 8
-
-template <typename F>
-__global__ __launch_bounds__(256) void scan_reduce_kernel(F f, u64 n, u64 *tile_sums, const u32 *np) {
-    __shared__ u64 sm[4];
-    if (np) { // length known on the device only: the grid covers the host's limit, and a count beyond it (there is none) must not reach past the buffers
-        const u64 d = *np;
-        n = d < n ? d : n;
-    }
-    u64 base = (u64)blockIdx.x * SCAN_TILE;
-    u64 s = 0;
-#pragma unroll
-    for (int k = 0; k < 8; k++) {
-        u64 i = base + (u64)k * 256 + threadIdx.x;
-        if (i < n) s += f(i); // (fetching all eight terms first, unconditionally, as k1_count does, changed nothing here: 49 vs 45 us)
-    }
-    s = wave_sum(s);
-    if (lane_id() == 0) sm[threadIdx.x >> 6] = s;
-    __syncthreads();
-    if (threadIdx.x == 0) tile_sums[blockIdx.x] = sm[0] + sm[1] + sm[2] + sm[3];
-}
-
-// single block: in-place exclusive scan of tile sums; writes grand total to *total
-// (a template only so that every translation unit that scans -- chain, extra, ingest -- instantiates it for itself)
-template <int UNUSED = 0>
-__global__ __launch_bounds__(1024) void scan_tiles_kernel(u64 *tile_sums, u32 n_tiles, u64 *total) {
-    __shared__ u64 wsum[16];
-    __shared__ u64 carry_s;
-    if (threadIdx.x == 0) carry_s = 0;
-    __syncthreads();
-    for (u32 base = 0; base < n_tiles; base += 1024) {
-        u32 i = base + threadIdx.x;
-        u64 v = i < n_tiles ? tile_sums[i] : 0;
-        u64 inc = wave_iscan(v);
-        int w = threadIdx.x >> 6;
-        if (lane_id() == 63) wsum[w] = inc;
-        __syncthreads();
-        u64 wb = 0, tot = 0;
-        for (int k = 0; k < 16; k++) {
-            u64 s = wsum[k];
-            if (k < w) wb += s;
-            tot += s;
-        }
-        u64 carry = carry_s;
-        if (i < n_tiles) tile_sums[i] = carry + wb + inc - v;
-        __syncthreads();
-        if (threadIdx.x == 0) carry_s = carry + tot;
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) *total = carry_s;
-}
-
-// third kernel: recompute values, exclusive prefix handed to the sink g(i, value, exclusive_prefix)
-template <typename F, typename G>
-__global__ __launch_bounds__(256) void scan_apply_kernel(F f, G g, u64 n, const u64 *tile_sums, const u32 *np) {
-    __shared__ u64 sm[4];
-    if (np) {
-        const u64 d = *np;
-        n = d < n ? d : n;
-    }
-    if ((u64)blockIdx.x * SCAN_TILE >= n) return;
-    u64 base = (u64)blockIdx.x * SCAN_TILE;
-    u64 run = tile_sums[blockIdx.x];
-    // thread order within the tile must equal element order: round k covers [base+k*256, +256)
-#pragma unroll
-    for (int k = 0; k < 8; k++) {
-        u64 i = base + (u64)k * 256 + threadIdx.x;
-        u64 v = i < n ? f(i) : 0;
-        u64 tot;
-        u64 ex = block_escan_256<u64>(v, sm, &tot);
-        if (i < n) g(i, v, run + ex);
-        run += tot;
-    }
-}
-
-// ---------------------------------------------------------------------------------------------
-// The same scan in TWO kernels for contig-sized inputs: every block of the apply kernel adds up the sums of the
-// tiles before it itself (at most SCAN2_MAX_TILES plain loads from an L2-resident array, 16 per thread) instead of
-// waiting for a single-block kernel in between -- one dependent launch less per scan.  (A one-kernel scan with
-// decoupled look-back was built and measured: 2 600 resident tiles polling each other's granules through the fabric
-// cost 47-76 us against 29 us for three kernels, with or without fences; it is in the history, not in the tree.)
-// ---------------------------------------------------------------------------------------------
-constexpr u32 SCAN2_MAX_TILES = 4096;
-template <typename F, typename G>
-__global__ __launch_bounds__(256) void scan_apply2_kernel(F f, G g, u64 n, const u64 *tile_sums, const u32 *np, u64 *total) {
-    __shared__ u64 sm[4];
-    __shared__ u64 s_pref[4];
-    if (np) {
-        const u64 d = *np;
-        n = d < n ? d : n;
-    }
-    const u64 n_tiles = n == 0 ? 1 : (n + SCAN_TILE - 1) / SCAN_TILE; // (an empty input still gets its total written)
-    if (blockIdx.x >= n_tiles) return;
-    u64 acc = 0;
-    for (u32 t = threadIdx.x; t < blockIdx.x; t += 256) acc += tile_sums[t];
-    acc = wave_sum(acc);
-    if (lane_id() == 0) s_pref[threadIdx.x >> 6] = acc;
-    __syncthreads();
-    u64 run = s_pref[0] + s_pref[1] + s_pref[2] + s_pref[3];
-    if (blockIdx.x == n_tiles - 1 && threadIdx.x == 0) *total = run + tile_sums[blockIdx.x];
-    const u64 base = (u64)blockIdx.x * SCAN_TILE;
-    // thread order within the tile must equal element order: round k covers [base+k*256, +256)
-#pragma unroll
-    for (int k = 0; k < 8; k++) {
-        u64 i = base + (u64)k * 256 + threadIdx.x;
-        u64 v = i < n ? f(i) : 0;
-        u64 tot;
-        u64 ex = block_escan_256<u64>(v, sm, &tot);
-        if (i < n) g(i, v, run + ex);
-        run += tot;
-    }
-}
 
 // ---------------------------------------------------------------------------------------------
 // K0: upper-case contig bases in place (boost::to_upper on fetched strings, junction.cc:586-587,635-638)
 // ---------------------------------------------------------------------------------------------
-#ifdef PJB_KERNELS_CHAIN
 __global__ __launch_bounds__(256) void k0_upper(uint8_t *g, int64_t n, int do_upper, int *has_x) {
     int64_t i = ((int64_t)blockIdx.x * 256 + threadIdx.x) * 16;
     bool x = false;
@@ -564,13 +53,11 @@ __global__ __launch_bounds__(256) void k0_upper(uint8_t *g, int64_t n, int do_up
         }
     }
 }
-#endif // PJB_KERNELS_CHAIN
 
 // K0f: the sequence lines of one FASTA record, as they are in the file, -> its bases.  With the .fai's geometry (line_blen
 // bases per line, line_len bytes per line) base i sits at byte (i / line_blen) * line_len + i % line_blen; every base must be
 // a graphic character and every line terminator byte not one -- the test faidx's loader implies (deps/htslib-1.3/faidx.c
 // reads with isgraph).  Anything else raises `bad` and the host falls back to filtering the characters itself.
-#ifdef PJB_KERNELS_CHAIN
 __global__ __launch_bounds__(256) void k0_fasta(const uint8_t *raw, int64_t raw_bytes, int64_t n, int32_t line_blen, int32_t line_len,
                                                  uint8_t *out, int *bad) {
     const int64_t i0 = ((int64_t)blockIdx.x * 256 + threadIdx.x) * 16;
@@ -599,7 +86,6 @@ __global__ __launch_bounds__(256) void k0_fasta(const uint8_t *raw, int64_t raw_
     }
     if (__ballot(wrong) && lane_id() == 0) atomicOr(bad, 1);
 }
-#endif // PJB_KERNELS_CHAIN
 
 // K0b: contig bases -> 4-bit nt16 codes, two per byte, LOW nibble first (base i at bits 4*(i&7) of
 // word i>>3).  A byte outside the 16-letter alphabet "=ACMGRSVTWYHKDBN" has no code: the contig is
@@ -625,7 +111,6 @@ __device__ __forceinline__ u32 nt16_code(u32 c, bool &exotic) {
     default: exotic = true; return 0;
     }
 }
-#ifdef PJB_KERNELS_CHAIN
 __global__ __launch_bounds__(256) void k0_encode(const uint8_t *g, int64_t n, u32 *codes, int64_t n_words, int *exotic_flag) {
     const int64_t w = (int64_t)blockIdx.x * 256 + threadIdx.x;
     bool exotic = false;
@@ -641,7 +126,6 @@ __global__ __launch_bounds__(256) void k0_encode(const uint8_t *g, int64_t n, u3
     }
     if (__ballot(exotic) && lane_id() == 0) atomicOr(exotic_flag, 1);
 }
-#endif // PJB_KERNELS_CHAIN
 
 // K0c: the same bases in TWO bits (A 0, C 1, G 2, T 3; base i at bits 2 (i & 15) of word i >> 4; anything else is stored as 0) and
 // the exceptions: bit i >> 6 of the bitmap is set when one of the bases 64 (i >> 6) .. 64 (i >> 6) + 63 is not A, C, G or T.  k1_emit
@@ -653,7 +137,6 @@ constexpr int K0_CODES2_PAD = 8, K0_GEXC_PAD = 4;
 __host__ __device__ inline int64_t codes2_words(int64_t n) { return ((n + 63) / 64) * 4; }          // (whole stretches)
 __host__ __device__ inline int64_t gexc_words(int64_t n) { return (((n + 63) / 64 + 63) / 64) * 2; } // (whole u64s)
 __host__ __device__ inline int64_t codes2_alloc_words(int64_t n) { return codes2_words(n) + K0_CODES2_PAD + gexc_words(n) + K0_GEXC_PAD; }
-#ifdef PJB_KERNELS_CHAIN
 __global__ __launch_bounds__(256) void k0_encode2(const uint8_t *g, int64_t n, u32 *codes2, u32 *gexc, int *any_exc) {
     const int64_t s = (int64_t)blockIdx.x * 256 + threadIdx.x; // stretch
     const int64_t n_str = (n + 63) / 64;
@@ -691,31 +174,11 @@ __global__ __launch_bounds__(256) void k0_encode2(const uint8_t *g, int64_t n, u
     if (lane_id() == 0 && s < ((n_str + 63) / 64) * 64) reinterpret_cast<u64 *>(gexc)[s >> 6] = m;
     if (m && lane_id() == 0) atomicOr(any_exc, 1); // (a target without a single exception -- a telomere-to-telomere assembly, a bacterium -- is never asked)
 }
-#endif // PJB_KERNELS_CHAIN
 
 // ---------------------------------------------------------------------------------------------
 // K1a: per-read CIGAR walk, pass 1 (BamAlignment::init bam_alignment.cc:71-100, findJuncs length
 // stats src/junction_builder.cc:333-343).  One thread per read; a tile is 1024 consecutive reads.
 // ---------------------------------------------------------------------------------------------
-constexpr int K1_TILE = 1024;
-
-// --extra by-products of the first pass (pjb_extra.hip.h, "the sparse path"): which records belong to unspliced.bam and what
-// they span -- k1_count has every record's CIGAR in registers anyway
-struct SparseCounters { // one per target, device memory (zeroed)
-    u32 n_zero;       // unspliced mapped records with no reference-consuming op (zlist entries)
-    u32 max_span;     // longest reference span of an unspliced mapped record
-    u32 max_gap;      // longest D operation among them
-    u32 need_dense;   // bit 0: the pileup cap may bite; bit 1: a record with more than 126 gaps; bit 2: gap list full
-    u64 total;        // written by the scan: unspliced records with a span | gaps << 32
-};
-constexpr u32 SPARSE_GAP_MAX = 126;
-struct XOut {
-    int32_t *s_pos, *s_end; // per record (global ordinal): position, exclusive end of the span (= pos: no span / not unspliced.bam)
-    uint8_t *q;             // bit 0: has a span, bits 1-7: D operations
-    u32 *zlist;
-    u32 zcap;
-    SparseCounters *cnt;
-};
 
 // chk_ref_len > 0 (members of a group): a tile with an alignment that ends past the target reports max_end = INT32_MAX, so
 // that k1_scan_tiles sees "weird coordinates" whatever the group's virtual length is (the host then finishes the
@@ -729,9 +192,6 @@ __device__ __forceinline__ u32 spl_nlq(u32 n, bool seq_ok, int32_t lq) {
 #ifndef K1C_T
 #define K1C_T 256 // threads of a k1_count block (a tile is K1_TILE reads: 4 per thread).  512 threads x 2 reads need 64 registers instead of
                   // 84 but took 88 against 63 us a launch beside the other chains' kernels: a block of 8 wavefronts waits for 8 free slots on ONE CU
-#endif
-#ifndef K1C_NO_ROWS
-#define K1C_NO_ROWS 0 // 1: every tile takes the rounds (A/B builds)
 #endif
 #ifndef K1C_WAVES
 #define K1C_WAVES 7 // waves per SIMD the register allocation aims at: 5 / 6 / 7 / 8 = 423 / 412 / 408 / 490 us a chain (8: 27 registers spilled)
@@ -976,7 +436,6 @@ __global__ __launch_bounds__(K1C_T) __attribute__((amdgpu_waves_per_eu(K1C_WAVES
     const u32 tile_local = blockIdx.x - b.tile_base;
     const int32_t chk_ref_len = chk_members ? max(G.len[b.member], 1) : 0;
     int64_t base = (int64_t)tile_local * K1_TILE;
-#if !K1C_NO_ROWS
     if (base + K1_TILE <= b.n) { // (a whole tile whose operations fit in LDS: the fast path; else the rounds below)
         const u32 cA = b.cig_off[base], cB = b.cig_off[base + K1_TILE];
         if (cB - cA + 3u <= (u32)K1C_OPSW) {
@@ -984,7 +443,6 @@ __global__ __launch_bounds__(K1C_T) __attribute__((amdgpu_waves_per_eu(K1C_WAVES
             return;
         }
     }
-#endif
     u32 cnt = 0, spl = 0, uns = 0;
     u64 sum = 0;
     int32_t mn = INT32_MAX, mx = 0, max_end = 0, max_nlen = 0, min_pos = INT32_MAX;
@@ -1206,7 +664,6 @@ __host__ __device__ inline u32 k1s_blocks(u32 n_tiles) { // ~1024 tiles a block
     const u32 g = (n_tiles + 1023u) / 1024u;
     return g < 1u ? 1u : (g > (u32)K1S_BLOCKS ? (u32)K1S_BLOCKS : g);
 }
-#ifdef PJB_KERNELS_CHAIN
 __global__ __launch_bounds__(K1S_THREADS) void k1_scan_tiles(u32 *tile_cnt, const TileStats *ts, u32 n_tiles, ContigStats *out, u32 pair_limit,
                                                               KeyFmt kf, int32_t ref_len, const u64 *tile_desc, u32 *tile_soff, u32 *chunk_tile,
                                                               ScanPart *parts, u32 epoch) {
@@ -1430,7 +887,6 @@ __global__ __launch_bounds__(K1S_THREADS) void k1_scan_tiles(u32 *tile_cnt, cons
         out->n_cand = 0;
     }
 }
-#endif // PJB_KERNELS_CHAIN
 
 // ---------------------------------------------------------------------------------------------
 // Packed-base compare helpers (used by k1_emit for the simple shape and by the generic walks of k4b_generic)
@@ -1562,7 +1018,6 @@ __device__ __forceinline__ void cmp_words(const u32 *seqw, int32_t qi, int32_t q
     }
 }
 
-
 // ---------------------------------------------------------------------------------------------
 // K1b: per-read CIGAR walk, pass 2: emit one pair per N op in BAM order
 // (JunctionSystem::addJunctions junction_system.cc:140-210 restated iteratively:
@@ -1606,18 +1061,10 @@ __device__ __forceinline__ void ncursor_advance(NCursor &c, const Ops cig, u32 n
     }
 }
 
-#ifndef PJB_CLOSED_INDELS
-#define PJB_CLOSED_INDELS 1 // blocks with I / D operations in closed form too (emit_read_pairs): the walk list all but empties -- k4b_generic
-                            // 224 -> 140 us a chain, k1_generic 122 -> 162 -- 8.82 -> 8.64 ms a step.  (While these reads were walked by a few
-                            // lanes of k1_emit's blocks the same switch cost 60 us a k1_emit launch: 9.75 against 9.1 ms.)
-#endif
-#ifndef PJB_SIMPLE_NW
-#define PJB_SIMPLE_NW 8 // two 16-byte loads per stream and round, 56 bases a round (5: one 16-byte load and a word, 32 bases)
-#endif
 // (profiles/r04e_compare_variants.txt: 32 bases a round with both anchors' words in flight together / 56 together / 32 one anchor
 // after the other / 56 one after the other = 10.56 / 11.56 / 10.07 / 9.97 ms a step; since then an anchor is a block compared on
 // its own, one after the other)
-constexpr int SIMPLE_NW = PJB_SIMPLE_NW;
+constexpr int SIMPLE_NW = 8; // two 16-byte loads per stream and round, 56 bases a round (5: one 16-byte load and a word, 32 bases)
 // what the walks find comparing one anchor (a block of emitted positions): its length, mismatches, first and last mismatch
 struct CmpBlock {
     int32_t len, mism, first, last;
@@ -1653,6 +1100,9 @@ struct EmitRead {
     const u32 *gcodes;      // the target's 4-bit codes
     int32_t glen, voff;     // the target's length and its offset in the group's virtual sequence
 };
+// Blocks with I / D operations are in closed form too: the walk list all but empties -- k4b_generic 224 -> 140 us a chain, k1_generic
+// 122 -> 162 -- 8.82 -> 8.64 ms a step.  (While these reads were walked by a few lanes of k1_emit's blocks the same cost 60 us a k1_emit
+// launch: 9.75 against 9.1 ms.)
 // (reads of the simple shape never come here: k1_emit finishes them in closed form.)  on_pair(key, lStart, rEnd) is called
 // for every pair once its record is complete; the match statistics (PairRec::aux) of a read that is not `closed` are
 // k4b_generic's to fill in.
@@ -1816,11 +1266,8 @@ constexpr int K1E_LOOK = 16;
 #ifndef K1E_WAVES
 #define K1E_WAVES 4 // wavefronts per SIMD the register allocation aims at (tools/build_variants.sh builds the others for A/B runs)
 #endif
-#ifndef K1E_SET
-#define K1E_SET 1 // slots of the block's candidate set per thread (2: 8.82 against 8.75 ms a step)
-#endif
 constexpr int K1E_T = 256, K1E_SHIFT = 8; // threads of a block = list entries of one trip
-constexpr int KC_SLOTS = K1E_T * K1E_SET;     // the block's candidate set (LDS), flushed when a quarter full
+constexpr int KC_SLOTS = K1E_T;               // the block's candidate set (LDS), flushed when a quarter full: a slot per thread (two: 8.82 against 8.75 ms a step)
 constexpr u64 KD_EMPTY = ~0ull; // no key: a packed key has fewer than 64 bits
 constexpr u32 GEN_SHARDS = 256, GEN_CNT_STRIDE = 32;
 constexpr int KD_PAGE_SHIFT = 6; // a page of the start bitmap: 64 words, one wavefront
@@ -1861,42 +1308,15 @@ struct EmitShared {
     int32_t lo[KC_SLOTS], hi[KC_SLOTS];
     u32 set_n, base, scan[4];
 };
-// A kernel argument fetched where it is needed, not kept (-DK1E_LAZY_ARGS=1): k1_emit's rarely used arguments (the candidate list's pointers,
-// the error word, the control block) cost it twelve scalar registers that it spills into VGPR lanes and fetches back eight times a trip.  The
-// scalar load from the kernel-argument segment is cached; the empty asm keeps the compiler from hoisting it out of the rare branch.
-// (Both measured in round 6, profiles/r06_k1_experiments.txt section 6: fetching the rare arguments lazily takes the kernel's v_readlane from 150
-// to 59 a trip and makes it 15 % SLOWER -- 1 105 - 1 140 us a chain in the step against 940 - 970 --, not unrolling the probes halves its code and
-// changes nothing: both are off.)
-#ifndef K1E_PROBE_UNROLL
-#define K1E_PROBE_UNROLL 1
-#endif
-#ifndef K1E_LAZY_ARGS
-#define K1E_LAZY_ARGS 0
-#endif
-template <class T>
-__device__ __forceinline__ T kernarg_at(u32 byte_off) {
-    const PJB_CONSTANT char *p = (const PJB_CONSTANT char *)__builtin_amdgcn_kernarg_segment_ptr();
-    asm volatile("" : "+s"(p));
-    T v;
-    __builtin_memcpy(&v, p + byte_off, sizeof(T));
-    return v;
-}
-// LAZY_E / LAZY_CS: byte offsets of the EmitLists / the ContigStats pointer among the kernel's arguments (-1: the members below are used)
-template <int LAZY_E = -1, int LAZY_CS = -1>
-struct EmitCtxT {
+// (k1_emit keeps its rarely used arguments -- the candidate list's pointers, the error word, the control block -- in scalar registers and unrolls
+// the probes below: fetching them from the kernel-argument segment where they are used made it 15 % slower, not unrolling changed nothing --
+// profiles/r06_k1_experiments.txt section 6.)
+struct EmitCtx {
     EmitShared &sh;
-    const EmitLists &E; // (LAZY_E >= 0: only gen_list, gen_cnt, gen_cap, pack_nn are read through this)
+    const EmitLists &E;
     const KeyFmt kf;
-    ContigStats *cs_;
+    ContigStats *cs;
     const bool want_cand;
-    __device__ __forceinline__ EmitLists cold() const {
-        if constexpr (LAZY_E >= 0) return kernarg_at<EmitLists>((u32)LAZY_E);
-        else return E;
-    }
-    __device__ __forceinline__ ContigStats *cs() const {
-        if constexpr (LAZY_CS >= 0) return kernarg_at<ContigStats *>((u32)LAZY_CS);
-        else return cs_;
-    }
     __device__ __forceinline__ void init() {
         if (!want_cand) return;
 #pragma unroll
@@ -1918,9 +1338,6 @@ struct EmitCtxT {
     __device__ __forceinline__ void cand_insert(u64 k, int32_t lstart, int32_t rend) const {
         if (!want_cand) return;
         u32 h = (u32)((k * 0x9E3779B97F4A7C15ull) >> 40) & (KC_SLOTS - 1);
-#if !K1E_PROBE_UNROLL
-#pragma nounroll // (unrolled 24 times -- twice, a pair each -- the probes were half of k1_emit's code: the first probe is the one that runs)
-#endif
         for (int probe = 0; probe < 24; probe++) { // look first: most keys are there already, and a read of one address by many lanes is a broadcast
             u64 old = sh.set[h];
             if (old == KD_EMPTY) {
@@ -1938,11 +1355,10 @@ struct EmitCtxT {
             h = (h + 1) & (KC_SLOTS - 1);
         }
         // a crowded set (reads with hundreds of introns): straight to the list, where duplicates do no harm
-        const EmitLists C = cold();
-        const u32 at = atomicAdd(&cs()->n_cand, 1u);
-        C.cand[at] = k;
-        C.cand_anc[at] = (u64)(u32)lstart | ((u64)(u32)rend << 32);
-        cand_mark(C, k);
+        const u32 at = atomicAdd(&cs->n_cand, 1u);
+        E.cand[at] = k;
+        E.cand_anc[at] = (u64)(u32)lstart | ((u64)(u32)rend << 32);
+        cand_mark(E, k);
     }
     // appends the wavefront's entries to list `kind` (1: reads for k4b_generic's walks, 2: for its window check, 3: reads for
     // k1_generic): one returning atomic per wavefront; sub-list `shard` (callers deal 256-entry chunks round-robin: gen_list_cap)
@@ -2004,23 +1420,21 @@ struct EmitCtxT {
             u32 total;
             const u32 excl = block_escan<K1E_T / 64, u32, true>(cnt, sh.scan, &total);
             if (threadIdx.x == 0) {
-                sh.base = total ? atomicAdd(&cs()->n_cand, total) : 0u;
+                sh.base = total ? atomicAdd(&cs->n_cand, total) : 0u;
                 sh.set_n = 0;
             }
             lds_barrier();
-            const EmitLists C = cold();
             u32 o = sh.base + excl;
 #pragma unroll
             for (int i = 0; i < KC_SLOTS / K1E_T; i++)
                 if (mine[i] != KD_EMPTY) {
-                    C.cand[o] = mine[i];
-                    C.cand_anc[o++] = anc[i];
-                    cand_mark(C, mine[i]);
+                    E.cand[o] = mine[i];
+                    E.cand_anc[o++] = anc[i];
+                    cand_mark(E, mine[i]);
                 }
         }
     }
 };
-typedef EmitCtxT<> EmitCtx;
 
 // ---- bases in TWO bits (pjb_batch.seq2 / GroupTab::codes2).  Round 5 took the compares apart (profiles/r05_k1_experiments.txt sections
 // 9, 10, 13): they are bound twice -- by the texture addresser, which takes a 4-byte-aligned 16-byte gather one LANE a cycle (16 gathers a
@@ -2033,9 +1447,6 @@ typedef EmitCtxT<> EmitCtx;
 struct __attribute__((packed, aligned(4))) Words2 {
     u32 x, y;
 };
-#ifndef C2_SKIP_HI
-#define C2_SKIP_HI 1 // a round whose block has 48 bases or fewer left asks for ONE 16-byte gather per stream (the addresser takes a gather a LANE a cycle: lanes that do not ask cost nothing)
-#endif
 constexpr int C2_NW = 8;                      // words per stream and round: two 16-byte gathers, 7 words = 112 bases compared
 constexpr int32_t C2_ROUND = 16 * (C2_NW - 1);
 constexpr int32_t C2_MAX_BLOCK = 1900;        // a longer block of bases (31 stretches of the bitmap: one 8-byte load) takes the 4-bit rounds
@@ -2068,7 +1479,7 @@ __device__ __forceinline__ void chunk2_cmp_bits(const u32 (&qw)[NW], const u32 (
 // trip v + 1 are already on their way (in registers).
 //   (Round 5 also built the version that stages the wavefront's bases and genome windows through LDS with coalesced loads: 2.4 x fewer
 // vector-memory instructions, the same time -- profiles/r05_k1_experiments.txt section 1; it left the tree with round 6, git has it.)
-#if defined(K1E_PROF) && defined(PJB_KERNELS_CHAIN) // (debug builds: wave-cycles per section of k1_emit, summed over every wavefront; printed by pjb_destroy)
+#ifdef K1E_PROF // (debug builds: wave-cycles per section of k1_emit, summed over every wavefront; printed by pjb_destroy)
 __device__ unsigned long long g_k1e_prof[16];
 #define K1E_T0() unsigned long long prof_t = __builtin_amdgcn_s_memtime()
 #define K1E_MARK(i)                                                                  \
@@ -2080,9 +1491,6 @@ __device__ unsigned long long g_k1e_prof[16];
 #else
 #define K1E_T0() do {} while (0)
 #define K1E_MARK(i) do {} while (0)
-#endif
-#if defined(K1E_HIST) && defined(PJB_KERNELS_CHAIN) // (debug builds: per wavefront and trip, compare rounds run (the longest lane's) against the lanes' mean -- pjb_destroy prints the table)
-__device__ unsigned long long g_k1e_hist[4][32]; // [0]: trips by rounds run, [1]: sum of active lanes' rounds by rounds run, [2]: active lanes, [3]: 4-bit rounds run
 #endif
 constexpr int K1E_MAXB = 64; // batches one launch takes (the host splits longer lists)
 struct EmitRec { // a trip's list records (per lane)
@@ -2101,39 +1509,9 @@ struct EmitTrip { // (uniform)
     int bi;
     u32 chunk, s_begin, s_end;
 };
-#ifdef PJB_KERNELS_CHAIN
-// k1_emit's arguments as the kernel-argument segment lays them out (explicit arguments one after the other, each at its natural alignment):
-// what kernarg_at reads the rarely used ones from.  k1_emit's own parameter list below MUST stay in this order.
-struct K1EmitArgs {
-    const DevBatch *batches;
-    int n_batches;
-    u32 n_tiles_total;
-    const u32 *tile_off, *tile_soff, *chunk_tile, *spl_idx, *spl_poff;
-    const uint4 *spl_rec;
-    Pairs P;
-    EmitLists E;
-    KeyFmt kf;
-    GroupTab G;
-    int use_codes, orientation;
-    u64 *err;
-    ContigStats *cs;
-};
 __global__ __launch_bounds__(K1E_T) __attribute__((amdgpu_waves_per_eu(K1E_WAVES, K1E_WAVES))) void k1_emit(const DevBatch *batches, int n_batches, u32 n_tiles_total, const u32 *tile_off, const u32 *tile_soff,
                                                 const u32 *chunk_tile, const u32 *spl_idx, const u32 *spl_poff, const uint4 *spl_rec, Pairs P, EmitLists E, KeyFmt kf,
-                                                GroupTab G, int use_codes, int orientation, u64 *err_unused, ContigStats *cs_unused) {
-    // (the error word, the control block, the candidate list's pointers and the read ordinals' array are fetched from the kernel-argument
-    // segment where they are used -- rare branches, the block's last flush --, not kept in scalar registers: see kernarg_at)
-#if K1E_LAZY_ARGS
-    (void)err_unused;
-    (void)cs_unused;
-    auto err_ptr = [] { return kernarg_at<u64 *>((u32)offsetof(K1EmitArgs, err)); };
-    auto pg_ptr = [] { return kernarg_at<u32 *>((u32)(offsetof(K1EmitArgs, P) + offsetof(Pairs, g))); };
-    ContigStats *const cs = kernarg_at<ContigStats *>((u32)offsetof(K1EmitArgs, cs)); // (once: the test below)
-#else
-    auto err_ptr = [=] { return err_unused; };
-    auto pg_ptr = [=] { return P.g; };
-    ContigStats *const cs = cs_unused;
-#endif
+                                                GroupTab G, int use_codes, int orientation, u64 *err, ContigStats *cs) {
     __shared__ u32 s_soff[K1E_LOOK];
     __shared__ EmitShared sh;
     __shared__ u32 s_cfirst[K1E_MAXB + 1]; // trips before batch i
@@ -2142,14 +1520,9 @@ __global__ __launch_bounds__(K1E_T) __attribute__((amdgpu_waves_per_eu(K1E_WAVES
     __shared__ u32 s_wsum[4];
     if (cs->P == 0) return; // no pairs, or a limit was exceeded: the contig is repeated with larger buffers
     K1E_T0();
-    const bool want_g = pg_ptr() != nullptr; // (--extra contexts: the pairs' read ordinals)
-#if K1E_LAZY_ARGS
-    const bool want_cand = kernarg_at<u64 *>((u32)(offsetof(K1EmitArgs, E) + offsetof(EmitLists, cand))) != nullptr;
-    EmitCtxT<(int)offsetof(K1EmitArgs, E), (int)offsetof(K1EmitArgs, cs)> ctx{sh, E, kf, nullptr, want_cand};
-#else
+    const bool want_g = P.g != nullptr; // (--extra contexts: the pairs' read ordinals)
     const bool want_cand = E.cand != nullptr;
     EmitCtx ctx{sh, E, kf, cs, want_cand};
-#endif
     ctx.init();
     auto cand_insert = [&](u64 k, int32_t lstart, int32_t rend) { ctx.cand_insert(k, lstart, rend); };
     {
@@ -2409,7 +1782,7 @@ __global__ __launch_bounds__(K1E_T) __attribute__((amdgpu_waves_per_eu(K1E_WAVES
                     const int32_t iend = rStart - 1;
                     int32_t rEndExc = rStartU + (int32_t)lb;
                     if (rEndExc - 1 >= vlen) rEndExc = vlen; // junction_system.cc:172-174
-                    if (pr < npairs && rEndExc - 1 < iend) set_error(err_ptr(), g, PJB_ERR_MIN_ANCHOR); // intron.cc:76
+                    if (pr < npairs && rEndExc - 1 < iend) set_error(err, g, PJB_ERR_MIN_ANCHOR); // intron.cc:76
                     ist_[pr] = istart;
                     lst_[pr] = lst;
                     rend_[pr] = rEndExc - 1;
@@ -2441,9 +1814,6 @@ __global__ __launch_bounds__(K1E_T) __attribute__((amdgpu_waves_per_eu(K1E_WAVES
                 };
                 if (any_exc && use2 && (hit(x0, bg[0], bl[0]) || hit(x1, bg[1], bl[1]) || (two && hit(x2, bg[2], bl[2])))) use2 = false;
             }
-#ifdef K1E_HIST
-            u32 h_rounds = 0, h_mine = 0, h_rounds4 = 0;
-#endif
             if (__ballot(use2)) {
                 const u32 *seq2w = (const u32 *)b.seq2 + (so >> 1);
                 const int32_t q2_last = (int32_t)min(((seq_words + 1u) >> 1) - 1u - (so >> 1), 0x7fffffffu); // the batch's last word of 2-bit bases, from the read's first
@@ -2460,7 +1830,9 @@ __global__ __launch_bounds__(K1E_T) __attribute__((amdgpu_waves_per_eu(K1E_WAVES
                         const u32 qbit = qodd + 2u * (u32)(qi + t), gbit = 2u * (u32)(gi + t);
                         u32 qw[C2_NW], gw[C2_NW];
                         const int32_t qf = (int32_t)(qbit >> 5), gf = (int32_t)(gbit >> 5);
-                        if (C2_SKIP_HI && qf + C2_NW - 1 <= q2_last) { // (the genome's words are always there: K0_CODES2_PAD)
+                        // a round whose block has 48 bases or fewer left asks for ONE 16-byte gather per stream (the addresser takes a gather a LANE a cycle: lanes
+                        // that do not ask cost nothing); the else arm is the path for a batch's last words
+                        if (qf + C2_NW - 1 <= q2_last) { // (the genome's words are always there: K0_CODES2_PAD)
                             const Words4 qa = gload(reinterpret_cast<const Words4 *>(seq2w + qf)), ga = gload_as<Words4>(gcodes2 + gf);
                             Words4 qb = {0, 0, 0, 0}, gb = {0, 0, 0, 0};
                             if (l - t > 48) { // (words 4 .. 7 feed the bases from the 49th on)
@@ -2475,9 +1847,6 @@ __global__ __launch_bounds__(K1E_T) __attribute__((amdgpu_waves_per_eu(K1E_WAVES
                         }
                         chunk2_cmp_bits<C2_NW>(qw, gw, qbit & 31u, gbit & 31u, l, t, mism, fbit, lbit1);
                         t += C2_ROUND;
-#ifdef K1E_HIST
-                        h_mine++;
-#endif
                     }
                     if (k < nb && t >= l) { // the lane's block is finished: its results, the next block
                         const int32_t first = (int32_t)fbit >> 1, last = ((int32_t)lbit1 - 1) >> 1; // (-1: no mismatch)
@@ -2487,9 +1856,6 @@ __global__ __launch_bounds__(K1E_T) __attribute__((amdgpu_waves_per_eu(K1E_WAVES
                         k++;
                         t = 0, mism = 0, fbit = 0xffffffffu, lbit1 = 0;
                     }
-#ifdef K1E_HIST
-                    h_rounds++;
-#endif
                     if (!__ballot(k < nb)) break;
                 }
             }
@@ -2516,24 +1882,9 @@ __global__ __launch_bounds__(K1E_T) __attribute__((amdgpu_waves_per_eu(K1E_WAVES
                         k++;
                         t = 0, mism = 0, fbit = 0xffffffffu, lbit1 = 0;
                     }
-#ifdef K1E_HIST
-                    h_rounds4++;
-#endif
                     if (!__ballot(k < nb)) break;
                 }
             }
-#ifdef K1E_HIST
-            {
-                const u32 lanes = (u32)__popcll(__ballot(true)), sum = wave_total<DppAdd>(h_mine);
-                const u32 r_ = min(h_rounds, 31u), r4 = min(wave_total<DppMax>(h_rounds4), 31u);
-                if (lane_id() == (int)(__ffsll((long long)__ballot(true)) - 1)) {
-                    atomicAdd(&g_k1e_hist[0][r_], 1ull);
-                    atomicAdd(&g_k1e_hist[1][r_], (unsigned long long)sum);
-                    atomicAdd(&g_k1e_hist[2][r_], (unsigned long long)lanes);
-                    atomicAdd(&g_k1e_hist[3][r4], 1ull);
-                }
-            }
-#endif
 #pragma unroll
             for (u32 pr = 0; pr < 2; pr++) {
                 if (pr >= npairs) break;
@@ -2547,7 +1898,7 @@ __global__ __launch_bounds__(K1E_T) __attribute__((amdgpu_waves_per_eu(K1E_WAVES
                 Q.aux = cmp_blocks_res(res[pr], res[pr + 1]);
                 const u64 key = make_key(kf, ist_[pr], iend_[pr]);
                 P.key[off + pr] = key;
-                if (want_g) pg_ptr()[off + pr] = g;
+                if (want_g) P.g[off + pr] = g;
                 rec_store(P.rec + off + pr, Q);
                 if (want_cand) cand_insert(key, Q.lstart, Q.rend);
             }
@@ -2568,7 +1919,6 @@ __global__ __launch_bounds__(K1E_T) __attribute__((amdgpu_waves_per_eu(K1E_WAVES
         R1 = R2;
     }
 }
-#endif // PJB_KERNELS_CHAIN
 
 // The reads k1_emit did not finish (three and more introns, indels, = X P H operations, clamped ends, exotic targets, SEQ '*'):
 // a thread per read of the chain's third list, dense.  The read's operations are walked (emit_read_pairs): keys and records
@@ -2583,7 +1933,6 @@ __device__ __forceinline__ const DevBatch &find_batch_by_tile(const DevBatch *ba
     }
     return batches[lo];
 }
-#ifdef PJB_KERNELS_CHAIN
 __global__ __launch_bounds__(K1E_T) void k1_generic(const DevBatch *batches, int n_batches, const u32 *spl_idx, const uint4 *spl_rec, Pairs P, EmitLists E, KeyFmt kf,
                                                     GroupTab G, int use_codes, int orientation, u64 *err, ContigStats *cs) {
     __shared__ EmitShared sh;
@@ -2654,7 +2003,7 @@ __global__ __launch_bounds__(K1E_T) void k1_generic(const DevBatch *batches, int
                 if (op_consumes_query(ty)) qsum += ln;
                 const bool len_ok = ln > 0 && ln <= RES_FIELD_MAX;
                 if (ty == OP_M || ty == OP_EQ || ty == OP_X) shape = (shape == 0 || shape == 5 || shape == 2 || shape == 1 || shape == 6) && len_ok ? 1u : 4u;
-                else if (ty == OP_I || ty == OP_D) shape = PJB_CLOSED_INDELS && shape == 1 && len_ok ? 6u : 4u;
+                else if (ty == OP_I || ty == OP_D) shape = shape == 1 && len_ok ? 6u : 4u;
                 else if (ty == OP_N) shape = shape == 1 && ln > 0 ? 2u : 4u;
                 else if (ty == OP_S) shape = shape == 0 && len_ok ? 5u : shape == 1 && q + 1 == R.n ? 3u : 4u;
                 else shape = 4;
@@ -2684,13 +2033,11 @@ __global__ __launch_bounds__(K1E_T) void k1_generic(const DevBatch *batches, int
         ctx.cand_flush(item0 + gridDim.x * K1E_T >= n_items);
     }
 }
-#endif // PJB_KERNELS_CHAIN
 
 // per-member counters of a group, from the tile statistics of the member's tiles (before k1_scan_tiles turns the tile pair
 // counts into offsets): one block per member
 // (behind k1_scan_tiles and off the chain's K1 stage: a member's pairs are the difference of the scanned counts at its first tile and
 // the next member's)
-#ifdef PJB_KERNELS_CHAIN
 __global__ __launch_bounds__(256) void kg_member_stats(const u32 *tile_off, const TileStats *ts, const u32 *tile_lo, int n_members, MemberStats *out, u32 n_tiles,
                                                        const ContigStats *cs) {
     __shared__ u64 sm[4][4];
@@ -2739,7 +2086,6 @@ __global__ __launch_bounds__(256) void kg_member_stats(const u32 *tile_off, cons
         out[m] = S;
     }
 }
-#endif // PJB_KERNELS_CHAIN
 
 // ---------------------------------------------------------------------------------------------
 // K2d: ordered dense junction ids.  The intron key is 46-48 bits wide (contig coordinate + intron length): five radix
@@ -2775,7 +2121,6 @@ struct PopcFn {
     const u64 *words;
     __device__ u64 operator()(u64 i) const { return (u64)__popcll(words[i]); }
 };
-#ifdef PJB_KERNELS_CHAIN
 __global__ __launch_bounds__(256) void kd_ends(const u64 *cand, KeyFmt kf, const u64 *bitmap, const u32 *wrank, u32 junc_limit, u32 *ends,
                                                u32 *cand_rank, ContigStats *cs) {
     const u32 n = cs->n_cand; // (a few candidates per junction: the grid is small and strides)
@@ -2798,14 +2143,12 @@ __global__ __launch_bounds__(256) void kd_ends(const u64 *cand, KeyFmt kf, const
         if (!placed) atomicOr(&cs->overflow, OVF_DENSE);
     }
 }
-#endif // PJB_KERNELS_CHAIN
 // The ranks of the bitmap's words, page by page: the starts are few (a third of the pages of a human-sized chain hold one, fewer
 // where genes cluster), so the prefix sum runs over the PAGES' counts (k1_emit / k1_generic count a start when its bit is set for
 // the first time) and only the pages that hold a start are read: a wavefront per page, lane = word, the word's rank = the page's
 // rank + the popcounts of the page's words before it.  Words of pages without a start keep whatever rank they had: nobody asks
 // for it (kd_ends, kd_assign look up the words of their own starts).  (Until round 5 a three-kernel scan read all of the bitmap
 // twice and wrote every word's rank: 320 MB and 90 us a 1-Gb chain.)
-#ifdef PJB_KERNELS_CHAIN
 __global__ __launch_bounds__(256) void kd_rank_pages(const u64 *bitmap, const u32 *page_cnt, const u32 *page_rank, u32 *wrank, u32 n_pages, u32 n_words) {
     const u32 page = blockIdx.x * 4 + (threadIdx.x >> 6);
     if (page >= n_pages) return;
@@ -2815,10 +2158,8 @@ __global__ __launch_bounds__(256) void kd_rank_pages(const u64 *bitmap, const u3
     const u32 inc = wave_iscan(c);
     if (w < n_words) wrank[w] = page_rank[page] + inc - c;
 }
-#endif // PJB_KERNELS_CHAIN
 // Bitmap, page counts and end slots are all-clear at rest: instead of memsets over contig-sized buffers per contig, the
 // candidates wipe exactly what they set (after kd_assign has read it).
-#ifdef PJB_KERNELS_CHAIN
 __global__ __launch_bounds__(256) void kd_reset(const u64 *cand, const u32 *cand_rank, KeyFmt kf, u32 junc_limit, const ContigStats *cs,
                                                 u64 *bitmap, u32 *ends, u32 *page_cnt) {
     const u32 n = cs->n_cand;
@@ -2834,7 +2175,6 @@ __global__ __launch_bounds__(256) void kd_reset(const u64 *cand, const u32 *cand
         }
     }
 }
-#endif // PJB_KERNELS_CHAIN
 struct EndsCountFn {
     const u32 *ends;
     __device__ u64 operator()(u64 rs) const {
@@ -2866,21 +2206,6 @@ __device__ __forceinline__ u32 ends_below(const u32 *ends, u32 rs, u32 ue) { // 
 // whatever lies between them -- and one lane per junction touches the arrays, and only if the value would move them (a
 // read at L2 first: the arrays only ever move one way, so an older value errs on the side of one atomic too many).  (Folding
 // neighbouring lanes only left one atomic per lane wherever junctions alternate: 1.4 ms per chain on one L2 channel.)
-// segmented (by key) reduce towards the segment's FIRST lane; equal keys are contiguous across the lanes
-template <typename T, typename OP>
-__device__ __forceinline__ T seg_reduce_to_head(T v, u32 segkey, OP op) {
-    const int l = lane_id();
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        T t = __shfl_down(v, o, 64);
-        u32 k = __shfl_down(segkey, o, 64);
-        if (l + o < 64 && k == segkey) v = op(v, t);
-    }
-    return v;
-}
-struct OpMin { template <typename T> __device__ T operator()(T a, T b) const { return a < b ? a : b; } };
-struct OpMax { template <typename T> __device__ T operator()(T a, T b) const { return a > b ? a : b; } };
-struct OpAdd { template <typename T> __device__ T operator()(T a, T b) const { return a + b; } };
 __device__ __forceinline__ void anchors_fold(bool valid, u32 j, int32_t l, int32_t r, int32_t *anc_l, int32_t *anc_r) {
     const u32 lk = (u32)l ^ 0x80000000u, rk = (u32)r ^ 0x80000000u; // (signed order through the sign bit)
     u64 todo = __ballot(valid);
@@ -2902,7 +2227,6 @@ __device__ __forceinline__ void anchors_fold(bool valid, u32 j, int32_t l, int32
 // junction id -> intron key (every candidate writes its junction's entry: duplicates write the same value) and the junction's
 // anchors from the candidates' partial ones; thread 0 closes the chain -- P = 0, nothing downstream runs, the host repeats the
 // contig -- if a limit was exceeded while the ids were built
-#ifdef PJB_KERNELS_CHAIN
 __global__ __launch_bounds__(256) void kd_table(const u64 *cand, const u64 *cand_anc, const u32 *cand_rank, KeyFmt kf, u32 junc_limit, const u32 *ends,
                                                 const u32 *first_id, const u64 *total, u64 *jkey, int32_t *anc_l, int32_t *anc_r, ContigStats *cs,
                                                 const u32 *gen_cnt, u32 gen_cap, u32 sort_limit) {
@@ -2956,7 +2280,6 @@ __global__ __launch_bounds__(256) void kd_table(const u64 *cand, const u64 *cand
         }
     }
 }
-#endif // PJB_KERNELS_CHAIN
 
 // fragment record of the per-junction reductions: 48 words (see k4_pairs)
 enum {
@@ -2977,7 +2300,6 @@ __device__ __forceinline__ void acc_rest_state(u32 *acc, u64 n_junc) { // what k
 constexpr int KDA_TILE = 4096; // = RS_TILE
 __device__ __forceinline__ void wave_hist_add(u32 *h, u32 d, bool valid);
 constexpr int KDA_PER = 4;
-#ifdef PJB_KERNELS_CHAIN
 __global__ __launch_bounds__(256) void kd_assign(const u64 *key, const u32 *np, KeyFmt kf, const u64 *bitmap, const u32 *wrank, const u32 *ends,
                                                  const u32 *first_id, u32 junc_limit, const u64 *total, u32 *jid_bam, u32 *acc, const u64 *jkey,
                                                  const int32_t *anc_l, const int32_t *anc_r, u64 *err, ContigStats *cs_chk, int hist_bits, u32 *hist) {
@@ -3079,7 +2401,6 @@ __global__ __launch_bounds__(256) void kd_assign(const u64 *key, const u32 *np, 
         for (u32 d = threadIdx.x; d < nb; d += 256) hist[(size_t)blockIdx.x * nb + d] = s_h[d];
     }
 }
-#endif // PJB_KERNELS_CHAIN
 
 // ---------------------------------------------------------------------------------------------
 // K2: stable LSD radix sort of (key, pair index).  Classic 3-step passes: per-tile digit
@@ -3147,7 +2468,6 @@ __global__ __launch_bounds__(256) void rs_hist(const K *keys, const u32 *np, int
 // tiles and 144 us for a 0.5 Gb chain's 4 400.)  The scatter adds the number of keys with a smaller digit itself (a
 // block scan of the 2^bits totals), so the pass needs neither a scan of the whole matrix nor global atomics.
 constexpr u32 RSP_TILES = 64;
-#ifdef PJB_KERNELS_CHAIN
 __global__ __launch_bounds__(256) void rs_panel_sums(const u32 *hist, u32 n_tiles, u32 nb, u32 *psum) {
     const u32 d = blockIdx.y * 256 + threadIdx.x;
     if (d >= nb) return;
@@ -3162,8 +2482,6 @@ __global__ __launch_bounds__(256) void rs_panel_sums(const u32 *hist, u32 n_tile
     }
     psum[(size_t)blockIdx.x * nb + d] = sum;
 }
-#endif // PJB_KERNELS_CHAIN
-#ifdef PJB_KERNELS_CHAIN
 __global__ __launch_bounds__(256) void rs_panel_scan(const u32 *hist, const u32 *psum, u32 n_tiles, u32 nb, u32 *hist_scan, u32 *row_total) {
     const u32 d = blockIdx.y * 256 + threadIdx.x;
     if (d >= nb) return;
@@ -3189,7 +2507,6 @@ __global__ __launch_bounds__(256) void rs_panel_scan(const u32 *hist, const u32 
     }
     if (t1 == n_tiles) row_total[d] = run; // (the last panel)
 }
-#endif // PJB_KERNELS_CHAIN
 
 // LDS of one rs_scatter block: the tile's keys in digit order (reused for the pair indices), the offset
 // "global position - tile-local position" of every digit, and the digit counters of the 4 waves
@@ -3396,7 +2713,6 @@ struct HeadSink {
         if ((u32)v) run_start[r] = (u32)i;
     }
 };
-#ifdef PJB_KERNELS_CHAIN
 __global__ void k2_close(u64 *total, u32 *seg_off, u32 *run_first, u32 *run_start, ContigStats *cs, u32 junc_limit, const u32 *gen_cnt, u32 gen_cap) {
     const u32 n_pairs = cs->P;
     if (n_pairs == 0) return;
@@ -3425,7 +2741,6 @@ __global__ void k2_close(u64 *total, u32 *seg_off, u32 *run_first, u32 *run_star
     cs->R = R;
     cs->n_slots = J + (n_pairs + 63) / 64;
 }
-#endif // PJB_KERNELS_CHAIN
 
 // K2s for the chain on dense ids: k4_pairs left two bits per sorted pair (junction starts / position run starts), a scan over the
 // slices' popcounts numbers the runs, and this kernel writes what HeadSink writes -- from the masks and the sorted ids alone.
@@ -3434,7 +2749,6 @@ struct Popc64Fn {
     __device__ u64 operator()(u64 i) const { return (u64)__popcll(words[i]); }
 };
 constexpr int K2E_PER = 4;
-#ifdef PJB_KERNELS_CHAIN
 __global__ __launch_bounds__(256) void k2_expand(const u32 *sid, const u64 *head_mask, const u64 *run_mask, const u32 *run_base, const u64 *total,
                                                  u32 *seg_off, u32 *run_first, u32 *run_start, ContigStats *cs) {
     const u32 n = cs->P;
@@ -3462,14 +2776,12 @@ __global__ __launch_bounds__(256) void k2_expand(const u32 *sid, const u64 *head
         cs->n_runs = cs->R = R;
     }
 }
-#endif // PJB_KERNELS_CHAIN
 
 // ---------------------------------------------------------------------------------------------
 // The chain that sorted the FULL keys (PJB_DENSE_IDS off, raw keys, or a donor with more acceptors than K2d keeps) has its
 // junction ids only now: two small kernels give it what kd_assign gives the usual chain -- the rest state of anchors and
 // accumulators, the junction id of every pair in BAM order (k4b_generic works in BAM order) and the anchors.
 // ---------------------------------------------------------------------------------------------
-#ifdef PJB_KERNELS_CHAIN
 __global__ __launch_bounds__(256) void kf_init(u32 *acc, const u32 *n_junc_p, int32_t *anc_l, int32_t *anc_r) {
     const u32 n_junc = *n_junc_p;
     acc_rest_state(acc, n_junc);
@@ -3478,8 +2790,6 @@ __global__ __launch_bounds__(256) void kf_init(u32 *acc, const u32 *n_junc_p, in
         anc_r[t] = INT32_MIN;
     }
 }
-#endif // PJB_KERNELS_CHAIN
-#ifdef PJB_KERNELS_CHAIN
 __global__ __launch_bounds__(256) void kf_anchors(const u32 *sidx, const u32 *jid_of, const PairRec *rec, const u32 *np, u32 *jid_bam, int32_t *anc_l,
                                                    int32_t *anc_r) {
     const u32 n = *np;
@@ -3492,7 +2802,6 @@ __global__ __launch_bounds__(256) void kf_anchors(const u32 *sidx, const u32 *ji
     if (valid) jid_bam[p] = j;
     anchors_fold(valid, j, (int32_t)ra.z, (int32_t)ra.w, anc_l, anc_r);
 }
-#endif // PJB_KERNELS_CHAIN
 
 // ---------------------------------------------------------------------------------------------
 // K4: per-pair match statistics (AlignmentInfo::calcMatchStats junction.cc:147-240 on top of
@@ -3726,7 +3035,6 @@ __device__ __forceinline__ const DevBatch &find_batch(const DevBatch *batches, i
 // walked once; at every N operation the pair's junction-level anchors (kd_assign) are looked up and the two lock-step
 // walks start right there (op index and query offset are at hand: no hint has to travel with the pair).  The result
 // goes into the pair's record.  Runs on the side stream, beside the sort.
-#ifdef PJB_KERNELS_CHAIN
 __global__ __launch_bounds__(256) void k4b_generic(const u64 *list, const u32 *gen_cnt, u32 cap, const u64 *key, PairRec *rec, const u32 *jid_bam,
                                                     KeyFmt kf, const DevBatch *batches, int n_batches, const int32_t *anc_l, const int32_t *anc_r,
                                                     GroupTab G, int genome_has_x, int use_codes, u64 *err, const ContigStats *cs, u32 pack_nn) {
@@ -3828,7 +3136,6 @@ __global__ __launch_bounds__(256) void k4b_generic(const u64 *list, const u32 *g
     }
     } // items
 }
-#endif // PJB_KERNELS_CHAIN
 
 // K4: gather the pairs in sorted order -- one 32-byte record each -- and fold predicates and match statistics to fragment
 // heads with a segmented wave reduction (junction.cc:862-909 accumulators, :755-814 counters).
@@ -3841,7 +3148,6 @@ __global__ __launch_bounds__(256) void k4b_generic(const u64 *list, const u32 *g
 // masks (nullptr: the chain that sorted the full keys has its runs from the head scan): per 64-pair slice, the lanes where a
 // junction starts and the lanes where a run of equal read positions starts (entropy, junction.cc:730-749) -- this kernel holds
 // every pair's record anyway, k2_expand turns the bits into seg_off / run_first / run_start without touching a pair.
-#ifdef PJB_KERNELS_CHAIN
 __global__ __launch_bounds__(256) void k4_pairs(const u32 *sidx, const u32 *jid_of, const PairRec *rec, const u64 *jkey, KeyFmt kf, const u32 *np,
                                                  u32 *frag, int32_t *frag_j, u64 *head_mask, u64 *run_mask, const ContigStats *cs_chk, u64 *err_chk) {
     const u32 n = *np;
@@ -4010,7 +3316,6 @@ __global__ __launch_bounds__(256) void k4_pairs(const u32 *sidx, const u32 *jid_
     const u32 jprev = __shfl_up(j, 1, 64);
     if (valid && (lane == 0 || jprev != j)) store_fragment((u32)(mism64 >> 32));
 }
-#endif // PJB_KERNELS_CHAIN
 
 // K5a: fragment slots -> junction accumulators (acc pre-initialised: sums 0, max 0, min 100000000).
 // One wavefront walks 64 consecutive slots; lane k owns word k of the 48-word record, so every
@@ -4022,7 +3327,6 @@ __device__ __forceinline__ u32 frag_combine(int k, u32 a, u32 b) {
     return a + b; // sums; F_MISM_LO/HI are handled as one 64-bit add by the caller
 }
 constexpr int FRAG_SLOTS_PER_WAVE = 16; // short per-wave chains keep enough wavefronts in flight
-#ifdef PJB_KERNELS_CHAIN
 __global__ __launch_bounds__(256) void k5_frag_reduce(const u32 *frag, const int32_t *frag_j, const u32 *n_slots_p, u32 *acc) {
     const u32 n_slots = *n_slots_p;
     const u32 wave = (blockIdx.x * 256 + threadIdx.x) >> 6;
@@ -4072,41 +3376,11 @@ __global__ __launch_bounds__(256) void k5_frag_reduce(const u32 *frag, const int
     }
     flush(cur);
 }
-#endif // PJB_KERNELS_CHAIN
 
 // ---------------------------------------------------------------------------------------------
 // K5b: one thread per junction: strand from reads, entropy over position runs, splice motif,
 // hamming scores, suspicious flag -> output row.
 // ---------------------------------------------------------------------------------------------
-__device__ __forceinline__ uint8_t revcomp_char(uint8_t c) { // REVCOMP_LOOKUP seq_utils.hpp:33-40 (NUL outside A-Z)
-    switch (c) {
-    case 'A': return 'T';
-    case 'C': return 'G';
-    case 'D': return 'H';
-    case 'G': return 'C';
-    case 'H': return 'D';
-    case 'M': return 'K';
-    case 'N': return 'N';
-    case 'R': return 'Y';
-    case 'S': return 'W';
-    case 'T': return 'A';
-    case 'U': return 'A';
-    case 'V': return 'B';
-    case 'W': return 'S';
-    case 'X': return 'X';
-    case 'Y': return 'R';
-    default: return 0;
-    }
-}
-
-// faidx_fetch_seq clamping (deps/htslib-1.3/faidx.c:453-457): returns clamped [b,e]
-__device__ __forceinline__ void fetch_clamp(int32_t glen, int32_t &b, int32_t &e) {
-    if (e < b) b = e;
-    if (b < 0) b = 0;
-    else if (glen <= b) b = glen - 1;
-    if (e < 0) e = 0;
-    else if (glen <= e) e = glen - 1;
-}
 
 // Entropy terms, one thread per position run: p*log2(p) with the reference's grouping
 // (junction.cc:730-749): with runs r_0..r_m of equal read position the flush rule yields the counts
@@ -4118,7 +3392,6 @@ __device__ __forceinline__ void fetch_clamp(int32_t glen, int32_t &b, int32_t &e
 // lane its run's term from two neighbouring run starts -- folded in lane order (the chain of dependent adds is the
 // reference's, there is no chain of dependent loads).  (The terms had a kernel and an array of their own until
 // round 4.)
-#ifdef PJB_KERNELS_CHAIN
 __global__ __launch_bounds__(256) void k5_entropy_sum(const u32 *seg_off, const u32 *run_first, const u32 *run_start, const u32 *n_junc_p,
                                                        double *ent_sum) {
     // sixteen lanes per junction, four junctions per wavefront: most junctions have a handful of runs (a whole wavefront each spent
@@ -4152,9 +3425,7 @@ __global__ __launch_bounds__(256) void k5_entropy_sum(const u32 *seg_off, const 
     }
     if (valid && sl == 0) ent_sum[j] = sum;
 }
-#endif // PJB_KERNELS_CHAIN
 
-#ifdef PJB_KERNELS_CHAIN
 __global__ __launch_bounds__(256) void k5_finalize(const u64 *jkey, const u32 *seg_off, const u32 *run_first,
                                                     const u32 *run_start, const u32 *acc, const int32_t *anc_l,
                                                     const int32_t *anc_r, KeyFmt kf, GroupTab G, const u32 *n_junc_p, const double *ent_sum,
@@ -4322,7 +3593,6 @@ __global__ __launch_bounds__(256) void k5_finalize(const u64 *jkey, const u32 *s
     }
     rows[j] = R;
 }
-#endif // PJB_KERNELS_CHAIN
 
 // K6: the contig's rows leave the device inside the kernel chain -- the host does not know the row count when it
 // queues the work, so it cannot size a copy: 8-byte units go straight into page-locked host memory (mapped into the
@@ -4344,7 +3614,6 @@ __device__ __forceinline__ void publish_chain(const ContigStats *cs, u64 *err, u
 // Rows -> the row table, then -- the block that finishes last -- the chain's control block -> page-locked host memory, rest
 // states restored, the cursor advanced (publish_chain; a launch of its own until round 4).  The rows stream runs these
 // launches one after the other, so one counter in the cursor serves every slot.
-#ifdef PJB_KERNELS_CHAIN
 __global__ __launch_bounds__(256) void k6_rows_out(const u64 *rows, const ContigStats *cs, u64 *host_table, int64_t base, int64_t mirror_base,
                                                    RowCursor *cur, u64 *mirror_table, u32 mirror_room, u64 *err, u32 *gen_cnt, uint8_t *host_pub,
                                                    const MemberStats *members, u32 *member_junc, int n_members) {
@@ -4374,13 +3643,10 @@ __global__ __launch_bounds__(256) void k6_rows_out(const u64 *rows, const Contig
     if (threadIdx.x == 0) cur->blocks_done = 0;
     publish_chain(cs, err, gen_cnt, host_pub, base, mirror_base, cur, members, member_junc, n_members);
 }
-#endif // PJB_KERNELS_CHAIN
 
 // The last kernel of a contig: control block, error word and list counters go to page-locked host memory in one go
 // (three small copies otherwise), error word and counters return to their rest state for the contig that uses this
 // control slot next, and the row cursor moves on.
-constexpr int PUB_BASE_AT = 240, PUB_ERR_AT = 256, PUB_XCNT_AT = 320 /* --extra: the target's counters, 64 bytes */, PUB_CHECKED_AT = 384 /* reads on k4b_generic's second list */, PUB_GEN_AT = 512, PUB_MEMBERS_AT = 1536, PUB_GREADS_AT = 3072, PUB_BYTES = 4096; // byte offsets in the published block
-static_assert(PUB_MEMBERS_AT + GROUP_MAX * sizeof(MemberStats) <= PUB_BYTES && sizeof(MemberStats) % 8 == 0, "control block layout");
 __device__ __forceinline__ void publish_chain(const ContigStats *cs, u64 *err, u32 *gen_cnt, uint8_t *host, int64_t base, int64_t mirror_base,
                                               RowCursor *cur, const MemberStats *members, u32 *member_junc, int n_members) {
     const u32 t = threadIdx.x;
