@@ -206,7 +206,9 @@ typedef struct pjb_timing {
                               failed check walks the read without moving it to the other list) */
     /* ---- ABI 4 (not written for a context created with abi_version 3) ---- */
     int64_t repeats;        /* times the chain collected last was queued AGAIN because a limit it had been queued with turned out too small */
-    int64_t repeat_reasons; /* which limits, OR-ed over those repeats: 1 pairs, 2 key format, 4 junctions (or the sort's digits), 8 dense ids, 16 read lists */
+    int64_t repeat_reasons; /* which limits, OR-ed over those repeats: 1 pairs, 2 key format, 4 junctions (or the sort's digits), 8 dense ids, 16 read lists;
+                               32: the chain was a group that pjb_finish_group_end took apart -- its members were finished one by one, and the
+                               other fields describe the last member's chain */
 } pjb_timing;
 
 /* ---- entry points ------------------------------------------------------ */
@@ -263,7 +265,9 @@ int pjb_finish_contig(pjb_ctx *ctx, int32_t tid, pjb_region_result *result);
  * run side by side on the device --; they are collected in the order they were queued and their rows land in that order.  Between the two calls the contig's batches (and device
  * arrays lent by pjb_submit_batch_device) must stay as they are; batches for OTHER targets may be submitted, genomes
  * uploaded.  pjb_collect covers collected contigs only; pjb_clear_rows / pjb_set_row_mirror need an empty queue.
- * PJB_FLAG_EXTRA contexts queue like any other (the target's extra metrics are queued when its chain is collected). */
+ * PJB_FLAG_EXTRA contexts queue like any other -- single chains and group chains, mixed as the caller likes: the part of the
+ * extra metrics that needs the records only is queued with the chain and runs beside it, the part that needs the rows when
+ * the chain is collected. */
 #define PJB_MAX_QUEUED 8
 int pjb_finish_contig_begin(pjb_ctx *ctx, int32_t tid);
 int pjb_finish_contig_end(pjb_ctx *ctx, int32_t tid, pjb_region_result *result);
@@ -282,10 +286,18 @@ int pjb_finish_ready(pjb_ctx *ctx);
  * produced them (same rows, same per-target results).  Every target named must have had its batches submitted and its
  * genome uploaded; targets without alignments may be named.  _begin / _end pair up like pjb_finish_contig_begin / _end
  * and share their queue (PJB_MAX_QUEUED chains, collected in order; _end names the same targets in the same order).
- * PJB_ERR_ARG from _begin means "not as a group" (more than PJB_GROUP_MAX targets, 2^31 bases or more in all, a
- * PJB_FLAG_EXTRA context, a target whose genome holds characters outside the 16-letter nucleotide alphabet): finish the
- * targets one by one.  A member that turns out to hold alignments outside its own sequence makes _end finish the
- * members one by one itself. */
+ * PJB_ERR_ARG from _begin means "not as a group" (more than PJB_GROUP_MAX targets, 2^31 bases or more in all, a target
+ * whose genome holds characters outside the 16-letter nucleotide alphabet, a PJB_FLAG_EXTRA context with the option
+ * "extra_dense" set to 1 -- it builds a depth vector per target): nothing is queued, finish the targets one by one.  A
+ * member that turns out to hold alignments outside its own sequence makes _end finish the members one by one itself
+ * (pjb_timing.repeat_reasons, bit 32, says so).
+ *   PJB_FLAG_EXTRA contexts take groups like any other: rows, per-target results and the rows of pjb_extra_finish are what n
+ * calls of pjb_finish_contig on the same context would have produced, in the order of `tids`.  The group's unspliced records
+ * are kept in the coordinates of its virtual sequence, so that depth and flanking counts of all members' junctions are answered
+ * in one pass; the hand-over of a target's depth to the next target's junctions (pjb_extra_finish) still goes target by target,
+ * and source and junctions may lie in different chains.  A group with a member that needs the depth vector (htslib's 8000-record
+ * pileup cap may bite, a record with more than 126 deletions, more deletions than the list holds) or holds an unspliced record
+ * that leaves its sequence is taken apart by _end in the same way, before anything of it is committed. */
 #define PJB_GROUP_MAX 32
 int pjb_finish_group_begin(pjb_ctx *ctx, const int32_t *tids, int32_t n_tids);
 int pjb_finish_group_end(pjb_ctx *ctx, const int32_t *tids, int32_t n_tids, pjb_region_result *results /* n_tids of them */);
@@ -307,7 +319,8 @@ int pjb_plan_groups(const int32_t *ref_len, const int32_t *tids, int32_t n_tids,
  *   "dense_ids"  1 (default): the sort works on ordered dense junction ids; 0: on the full intron keys
  *   "extra_dense" 0 (default): PJB_FLAG_EXTRA answers depth and flanking counts from the unspliced records themselves
  *                (a few records per junction) and builds a target's per-base depth vector only where htslib's
- *                8000-record pileup cap may bite; 1: the depth vector for every target (round 2's path)
+ *                8000-record pileup cap may bite; 1: the depth vector for every target (round 2's path; groups are
+ *                then refused with PJB_ERR_ARG: the vector is per target)
  *   "sort_floor" 65536 (default): the sort's digits cover at least this many junction ids (and twice what the context's chains have
  *                had); n (test hook): a small floor, so that a chain with more junctions than planned for is repeated
  *   "list_cap"   0 (default): the kernels' read lists get the room the pair limit implies; n > 0 (test hook): the first attempt

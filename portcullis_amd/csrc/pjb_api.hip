@@ -820,7 +820,7 @@ static int queue_contig(pjb_ctx *c, Flight &f) {
         if (xk1) {
             const size_t N = (size_t)f.n_reads;
             if ((rc = ensure(c, S.x_q, N + 16)) || (rc = ensure(c, S.x_spos, N * 4 + 16)) || (rc = ensure(c, S.x_send, N * 4 + 16)) ||
-                (rc = ensure(c, S.x_zlist, (size_t)X_ZCAP * 4)) || (rc = ensure(c, S.x_scnt, sizeof(SparseCounters) + sizeof(ExtraCounters))))
+                (rc = ensure(c, S.x_zlist, (size_t)X_ZCAP * 4)) || (rc = ensure(c, S.x_scnt, X_SCNT_BYTES)))
                 return rc;
             HIP_TRY(c, hipMemsetAsync((uint8_t *)S.x_q.p + N, 0, 1, c->stream));
             HIP_TRY(c, hipMemsetAsync(S.x_scnt.p, 0, sizeof(SparseCounters) + sizeof(ExtraCounters), c->stream));
@@ -1285,7 +1285,8 @@ static int begin_flight(pjb_ctx *c, const int32_t *tids, int32_t n, const char *
                 if (t == tids[q]) return fail(c, PJB_ERR_STATE, "%s: target %d is queued already", who, t);
     if (n > 1) {
         // what a group needs (a caller that gets PJB_ERR_ARG here finishes the targets one by one)
-        if (c->extra) return fail(c, PJB_ERR_ARG, "%s: PJB_FLAG_EXTRA contexts finish one target at a time", who);
+        if (c->extra && c->extra_dense_only)
+            return fail(c, PJB_ERR_ARG, "%s: a PJB_FLAG_EXTRA context with \"extra_dense\" 1 builds a depth vector per target: finish them one by one", who);
         int64_t vlen = 0;
         for (int32_t k = 0; k < n; k++) {
             const Contig &G = c->contigs[(size_t)tids[k]];
@@ -1407,6 +1408,20 @@ static int collect_flight(pjb_ctx *c, pjb_region_result *res, bool *redo_single)
         if (cs.overflow & OVF_DENSE) lim.dense = false; // a donor with more alternative acceptors than K2d keeps: sort the full keys
         if (cs.overflow & OVF_LISTS) lim.list_cap = std::max(gen_list_cap(lim.pair_limit), (cs.list_need + cs.list_need / 4 + 511u) & ~255u); // (k1_generic's entries depend on the appends' order: some slack)
     }
+    if (c->extra && group) {
+        // --extra answers a group from its members' records in virtual coordinates; where that answer does not stand the group is taken
+        // apart before anything of it is committed.  (Its rows are in the table and the cursor has moved: the chains behind it are taken
+        // back, and the members' chains are queued with their place given.)
+        bool apart = false;
+        if ((rc = extra_group_apart(c, f, &apart))) return rc;
+        if (apart) {
+            unqueue_followers(c);
+            if (f.forked) (void)hipStreamSynchronize(c->sl[f.slot].side);
+            f.queued = f.forked = false;
+            *redo_single = true;
+            return PJB_OK;
+        }
+    }
     if (!lim.kf.raw) c->lbits_seen = std::max(c->lbits_seen, std::max(1, bits_of((uint64_t)cs.max_nlen)));
     const u32 P = cs.P, J = cs.J;
     // ---- one result per member
@@ -1486,7 +1501,7 @@ static int collect_flight(pjb_ctx *c, pjb_region_result *res, bool *redo_single)
         c->rows_copy_pending = true;
     }
     c->cur_slot = f.slot;
-    if (c->extra && (rc = extra_contig(c, f, tid, cs.spliced, P, J, old))) return rc;
+    if (c->extra && (rc = extra_contig(c, f, res, cs.spliced, P, J, old))) return rc;
     c->rows_n = old + J;
     c->last_rows_n = J;
     c->last_slot = f.slot;
@@ -1540,6 +1555,7 @@ static int end_flight(pjb_ctx *c, const int32_t *tids, int32_t n, pjb_region_res
         // a member holds alignments outside its own sequence: the members go through one by one, in this chain's slot
         const Flight whole = c->fl[0];
         size_t rows_total = 0;
+        if (c->extra) HIP_TRY(c, hipStreamSynchronize(c->stream)); // (the group's extra_pre reads the slot's scratch, which the members' chains write)
         for (int32_t m = 0; m < n; m++) {
             Flight one = Flight();
             one.slot = whole.slot;
@@ -1559,6 +1575,7 @@ static int end_flight(pjb_ctx *c, const int32_t *tids, int32_t n, pjb_region_res
         c->fl[0] = whole;
         c->fl[0].queued = c->fl[0].forked = false;
         c->last_rows_n = rows_total; // (pjb_collect_device covers the last member only: a caller of groups uses pjb_collect)
+        c->timing.repeat_reasons |= 32; // (the rest of the timing is the last member's chain)
     }
     if (res) memcpy(res, tmp.data(), tmp.size() * sizeof(pjb_region_result));
     closer.ok = true;

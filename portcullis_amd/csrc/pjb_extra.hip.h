@@ -213,8 +213,11 @@ __device__ __forceinline__ u32 lower_bound_i32(const int32_t *a, u32 n, int32_t 
 //   up = #{pos < start} - #{getEnd() < left};  down = #{pos <= right} - #{pos <= end}.
 // prefix_q[i] = such records among the first i records (all records are position sorted); pe[x] = such records
 // with getEnd() < x.  The reference's region query (sam_itr_queryi over [left - maxQueryLength - 1, right +
-// maxQueryLength + 1)) cannot exclude a record either test accepts.  Records without a reference span
+// maxQueryLength + 1), its end clamped to ref_len - 1: junction.cc:654-659) takes records with pos < its end, so it
+// excludes one record the tests accept: a record that starts on the target's LAST base, when the right anchor reaches
+// it -- `down` counts positions up to min(right, ref_len - 2) (flank_right).  Records without a reference span
 // (getEnd() == pos - 1) are tested one by one from `zlist`.
+__device__ __forceinline__ int32_t flank_right(int32_t r, int32_t ref_len) { return r < ref_len - 2 ? r : ref_len - 2; }
 __global__ __launch_bounds__(256) void kx_flank(const pjb_junction_row *rows, u32 n_rows, const int32_t *x_pos, u32 n_reads,
                                                  const u32 *prefix_q, const u32 *pe, int32_t ref_len, const u32 *zlist,
                                                  const ExtraCounters *cnt, u32 zcap, ExtraRow *out) {
@@ -223,14 +226,15 @@ __global__ __launch_bounds__(256) void kx_flank(const pjb_junction_row *rows, u3
     const int32_t s = rows[j].start, e = rows[j].end, l = rows[j].left, r = rows[j].right;
     auto before = [&](int32_t v) -> u32 { return prefix_q[lower_bound_i32(x_pos, n_reads, v)]; }; // #{pos < v}
     auto clampx = [&](int32_t v) -> int32_t { return v < 0 ? 0 : (v > ref_len + 1 ? ref_len + 1 : v); };
+    const int32_t rr = flank_right(r, ref_len);
     u32 up = before(s) - pe[clampx(l)];
-    u32 down = before(r == INT32_MAX ? r : r + 1) - before(e == INT32_MAX ? e : e + 1);
+    u32 down = rr > e ? before(rr + 1) - before(e + 1) : 0u;
     u32 nz = cnt->n_zero;
     if (nz > zcap) nz = zcap;
     for (u32 k = 0; k < nz; k++) {
         const int32_t pos = (int32_t)zlist[k], end = pos - 1;
         if (s > pos && l <= end) up++;
-        if (r >= pos && e < pos) down++;
+        if (rr >= pos && e < pos) down++;
     }
     out[j].up_aln = up;
     out[j].down_aln = down;
@@ -264,15 +268,22 @@ __global__ __launch_bounds__(256) void kx_pair_codes(const u32 *sidx, const u32 
 // above instead.
 // (SparseCounters, XOut: pjb_kernels.hip.h -- k1_count writes them when the records go through it; kx_classify_sparse is
 // the same classification for the records of a target that went through k1_walk)
-__global__ __launch_bounds__(256) void kx_classify_sparse(DevBatch b, int32_t *s_pos, int32_t *s_end, uint8_t *q_flag, u32 *zlist, u32 zcap,
-                                                           SparseCounters *cnt) {
+//   GROUP: the batch belongs to member `member` of a group (pjb_finish_group_begin), which lies at `voff` in the group's virtual
+// sequence and has `len` bases.  Positions and ends are written in virtual coordinates, so that the spans of the whole group are one
+// position-sorted list (members in the order of their offsets, records in file order inside a member); a record without a span keeps
+// its member beside its position (two words per zlist entry).  A record with a span that leaves its member's sequence would reach
+// into the gap behind it or the next member: the group is then taken apart (need_dense bit 3) and its members go one by one.
+template <bool GROUP>
+__global__ __launch_bounds__(256) void kx_classify_sparse(DevBatch b, int32_t voff, int32_t len, u32 member, int32_t *s_pos, int32_t *s_end,
+                                                           uint8_t *q_flag, u32 *zlist, u32 zcap, SparseCounters *cnt) {
     const int64_t r = (int64_t)blockIdx.x * 256 + threadIdx.x;
     u32 span = 0, gapmax = 0;
-    bool many = false;
+    bool many = false, leaves = false;
     if (r < b.n) {
         const u32 g = b.base + (u32)r;
         const u32 c0 = b.cig_off[r], c1 = b.cig_off[r + 1];
         const int32_t pos = b.pos[r];
+        const int32_t vpos = GROUP ? (int32_t)((u32)pos + (u32)voff) : pos;
         int32_t aligned = 0;
         u32 ngap = 0;
         bool spliced = false;
@@ -291,15 +302,19 @@ __global__ __launch_bounds__(256) void kx_classify_sparse(DevBatch b, int32_t *s
         const bool mapped = !(b.flag[r] & 0x4u);
         const bool unspliced = !spliced && mapped;
         const bool spans = unspliced && aligned > 0 && pos >= 0;
-        s_pos[g] = pos;
-        s_end[g] = spans ? pos + aligned : pos;
+        s_pos[g] = vpos;
+        s_end[g] = spans ? vpos + aligned : vpos;
+        if (GROUP && spans && (int64_t)pos + aligned > (int64_t)len) leaves = true;
         if (!spans) ngap = 0, gapmax = 0;
         if (ngap > SPARSE_GAP_MAX) many = true, ngap = SPARSE_GAP_MAX;
         q_flag[g] = (uint8_t)((spans ? 1u : 0u) | (ngap << 1));
         if (spans) span = (u32)aligned;
         if (unspliced && aligned == 0) {
             const u32 z = atomicAdd(&cnt->n_zero, 1u);
-            if (z < zcap) zlist[z] = (u32)pos;
+            if (z < zcap) {
+                if (GROUP) zlist[2 * (size_t)z] = (u32)pos, zlist[2 * (size_t)z + 1] = member;
+                else zlist[z] = (u32)pos;
+            }
         }
     }
     span = wave_max(span);
@@ -309,6 +324,7 @@ __global__ __launch_bounds__(256) void kx_classify_sparse(DevBatch b, int32_t *s
         if (gapmax > cnt->max_gap) atomicMax(&cnt->max_gap, gapmax);
     }
     if (many) atomicOr(&cnt->need_dense, 2u);
+    if (GROUP && leaves) atomicOr(&cnt->need_dense, 8u);
 }
 
 // one scan over the records: (records with a span) | (gaps) << 32
@@ -335,9 +351,10 @@ struct SparseSink { // the records with a span, compacted in rank order; gaps be
     }
 };
 // the gaps (D operations) of the unspliced records in record order: a block per 256 records (global ordinals, so that
-// gapoff[block] is the block's first entry), an exclusive scan of the records' gap counts inside the block
-__global__ __launch_bounds__(256) void kx_gaps(DevBatch b, const uint8_t *q, u32 n_total, const u32 *gapoff, Gap *gaps, u32 gap_cap, SparseCounters *cnt,
-                                                u32 n_blocks) {
+// gapoff[block] is the block's first entry), an exclusive scan of the records' gap counts inside the block.  `voff`: where the batch's
+// target lies in its group's virtual sequence (0: a target finished alone) -- the gaps are in the coordinates of the spans.
+__global__ __launch_bounds__(256) void kx_gaps(DevBatch b, int32_t voff, const uint8_t *q, u32 n_total, const u32 *gapoff, Gap *gaps, u32 gap_cap,
+                                                SparseCounters *cnt, u32 n_blocks) {
     __shared__ u32 wsum[4];
     if ((cnt->total >> 32) == 0) return; // (no gap in the whole target: the usual case for short reads; the grid is small for that)
     const u32 first_block = b.base >> 8;
@@ -357,7 +374,7 @@ __global__ __launch_bounds__(256) void kx_gaps(DevBatch b, const uint8_t *q, u32
             continue;
         }
         const u32 r = (u32)g - b.base;
-        int32_t x = b.pos[r];
+        int32_t x = b.pos[r] + voff;
         u32 k_out = 0;
         for (u32 k = b.cig_off[r]; k < b.cig_off[r + 1] && k_out < ngap; k++) {
             const u32 op = b.cigar[k], ty = op & 15u;
@@ -448,14 +465,88 @@ __global__ __launch_bounds__(256) void kx_flank_sparse(const pjb_junction_row *r
         if (s_end[i] - 1 < w.p1lo) a++;
     }, part, unused);
     if (!on) return;
+    const int32_t rr = flank_right(r, ref_len);
     u32 up = before(s) - (ended + part);
-    u32 down = before(r == INT32_MAX ? r : r + 1) - before(e == INT32_MAX ? e : e + 1);
+    u32 down = rr > e ? before(rr + 1) - before(e + 1) : 0u;
     u32 nz = cnt->n_zero;
     if (nz > zcap) nz = zcap;
     for (u32 k = 0; k < nz; k++) {
         const int32_t pos = (int32_t)zlist[k], end = pos - 1;
         if (s > pos && l <= end) up++;
-        if (r >= pos && e < pos) down++;
+        if (rr >= pos && e < pos) down++;
+    }
+    out[j].up_aln = up;
+    out[j].down_aln = down;
+}
+
+// The spans of a group's members per member, from the compacted list: member m's records are those whose virtual position lies in
+// [voff[m], voff[m + 1]) -- a record with a span starts inside its member (kx_classify_sparse<true> sends a group with one that does not
+// through its members one by one).  One wavefront, a lane per member.
+__global__ __launch_bounds__(64) void kx_member_spans(const int32_t *s_pos, const SparseCounters *cnt, XMembers M, GroupCounters *out) {
+    const u32 n_reads = (u32)cnt->total;
+    const int m = (int)threadIdx.x;
+    bool has = false;
+    if (m < M.n) {
+        const u32 lo = lower_bound_i64(s_pos, n_reads, (int64_t)M.voff[m]);
+        const u32 hi = m + 1 < M.n ? lower_bound_i64(s_pos, n_reads, (int64_t)M.voff[m + 1]) : n_reads;
+        has = hi > lo;
+    }
+    const u64 mask = __ballot(has);
+    if (m == 0) {
+        out->has_spans = (u32)mask;
+        out->_pad = 0;
+    }
+}
+
+// kx_flank_sparse for the rows of a whole group: s_pos / s_end hold the spans of every member in the coordinates of the group's virtual
+// sequence, the rows carry their target (refid) and its own coordinates.  A row finds its member in M, applies the reference's clamps in
+// the member's coordinates and searches in virtual ones; since a member's records start inside it, a position clamped to [0, len + 1]
+// separates them exactly as the unclamped one does for a target finished alone.
+//   The records of EARLIER members start before every position of this one and end inside their own member: they are counted by
+// before(s) and by `ended` alike -- among the records before the search window, or inside it with their last base before the anchor --
+// and cancel in `up`; in `down` they are in both terms.  A LATER member's records start behind voff + len + 1 (the gap between members
+// is 4096 bases) and are in neither.  max_span is the group's maximum: a larger one only widens the window that is walked.
+__global__ __launch_bounds__(256) void kx_flank_group(const pjb_junction_row *rows, u32 n_rows, const int32_t *s_pos, const int32_t *s_end, XMembers M,
+                                                       const u32 *zlist, const SparseCounters *cnt, u32 zcap, ExtraRow *out) {
+    const u32 n_reads = (u32)cnt->total;
+    const u32 j = blockIdx.x * 256 + threadIdx.x;
+    const bool on = j < n_rows;
+    int32_t s = 0, e = 0, l = 0, r = 0, refid = -1;
+    if (on) s = rows[j].start, e = rows[j].end, l = rows[j].left, r = rows[j].right, refid = rows[j].refid;
+    u32 member = 0;
+    int32_t voff = M.voff[0], ref_len = M.len[0];
+    for (int k = 1; k < M.n; k++) // (k is uniform: the table is read with scalar loads)
+        if (M.tid[k] == refid) member = (u32)k, voff = M.voff[k], ref_len = M.len[k];
+    auto before = [&](int64_t v) -> u32 { // #{records of earlier members} + #{this member's records with pos < v}
+        const int64_t vc = v < 0 ? 0 : (v > (int64_t)ref_len + 1 ? (int64_t)ref_len + 1 : v);
+        return lower_bound_i64(s_pos, n_reads, (int64_t)voff + vc);
+    };
+    const int32_t lc = l < 0 ? 0 : (l > ref_len + 1 ? ref_len + 1 : l);
+    const int32_t vlc = voff + lc;
+    u32 ended = 0, i0 = 0, i1 = 0;
+    if (on) {
+        if (lc == ref_len + 1) ended = before(lc); // (the histogram clamps every end to ref_len: every record of the member)
+        else {
+            i0 = lower_bound_i64(s_pos, n_reads, (int64_t)vlc - (int64_t)cnt->max_span);
+            i1 = lower_bound_i32(s_pos, n_reads, vlc);
+            ended = i0;
+        }
+    }
+    u32 part = 0, unused = 0;
+    ranges_sum2(i0, i1, Win{vlc, 0, 0, 0}, [&](u32 i, const Win w, u32 &a, u32 &) {
+        if (s_end[i] - 1 < w.p1lo) a++;
+    }, part, unused);
+    if (!on) return;
+    const int32_t rr = flank_right(r, ref_len);
+    u32 up = before(s) - (ended + part);
+    u32 down = rr > e ? before((int64_t)rr + 1) - before((int64_t)e + 1) : 0u;
+    u32 nz = cnt->n_zero;
+    if (nz > zcap) nz = zcap;
+    for (u32 k = 0; k < nz; k++) {
+        if (zlist[2 * (size_t)k + 1] != member) continue;
+        const int32_t pos = (int32_t)zlist[2 * (size_t)k], end = pos - 1;
+        if (s > pos && l <= end) up++;
+        if (rr >= pos && e < pos) down++;
     }
     out[j].up_aln = up;
     out[j].down_aln = down;
@@ -466,13 +557,15 @@ __device__ __forceinline__ u32 span_overlap(int64_t x0, int64_t x1, int32_t plo,
     return hi >= lo ? (u32)(hi - lo + 1) : 0u;
 }
 // sum over i in [a, b], 1 <= i < len, of the depth at position i - 1 -- for two windows [a1, b1], [a2, b2] at once; every lane of
-// the wavefront calls this (`on`: the lane has a junction)
-__device__ __forceinline__ void sparse_cov2(const SparseDepth D, int32_t len, bool on, int32_t a1, int32_t b1, int32_t a2, int32_t b2, u32 &sum1,
-                                            u32 &sum2) {
+// the wavefront calls this (`on`: the lane has a junction).  D may hold the records of a whole group in virtual coordinates, the
+// source target lying at `voff` in them: the windows are clipped to the target in its own coordinates and then moved there.  The
+// records of its neighbours that the search also meets lie inside their own members and overlap nothing of the windows.
+__device__ __forceinline__ void sparse_cov2(const SparseDepth D, int32_t len, int32_t voff, bool on, int32_t a1, int32_t b1, int32_t a2, int32_t b2,
+                                            u32 &sum1, u32 &sum2) {
     // window [a, b] in i -> positions [max(a, 1) - 1, min(b, len - 1) - 1]
     auto lo_of = [&](int32_t a) -> int32_t { return (a < 1 ? 1 : a) - 1; };
     auto hi_of = [&](int32_t b) -> int32_t { return b < 0 ? -1 : (b > len - 1 ? len - 1 : b) - 1; };
-    const Win w{lo_of(a1), hi_of(b1), lo_of(a2), hi_of(b2)};
+    const Win w{lo_of(a1) + voff, hi_of(b1) + voff, lo_of(a2) + voff, hi_of(b2) + voff};
     const bool e1 = w.p1hi >= w.p1lo, e2 = w.p2hi >= w.p2lo;
     int64_t lo = 0, hi = -1;
     if (e1) lo = w.p1lo, hi = w.p1hi;
@@ -505,15 +598,16 @@ __device__ __forceinline__ void sparse_cov2(const SparseDepth D, int32_t len, bo
     sum2 = s2 - m2;
 }
 // Junction::calcCoverage (junction.cc:923-951) from a target's records instead of its depth vector: a thread per junction
-__global__ __launch_bounds__(256) void kx_coverage_sparse(const pjb_junction_row *rows, u32 row0, u32 n, SparseDepth D, int32_t len_src, ExtraRow *out) {
+__global__ __launch_bounds__(256) void kx_coverage_sparse(const pjb_junction_row *rows, u32 row0, u32 n, SparseDepth D, int32_t len_src, int32_t voff_src,
+                                                           ExtraRow *out) {
     const u32 k = blockIdx.x * 256 + threadIdx.x;
     const bool on = k < n;
     const u32 j = row0 + (on ? k : 0u);
     int32_t s = 0, e = 0;
     if (on) s = rows[j].start, e = rows[j].end;
     u32 d1, d2, a1, a2;
-    sparse_cov2(D, len_src, on, s - 20, s - 11, s - 10, s, d1, d2);
-    sparse_cov2(D, len_src, on, e + 10, e + 20, e, e + 9, a1, a2);
+    sparse_cov2(D, len_src, voff_src, on, s - 20, s - 11, s - 10, s, d1, d2);
+    sparse_cov2(D, len_src, voff_src, on, e + 10, e + 20, e, e + 9, a1, a2);
     if (!on) return;
     const double donor = (1.0 / 9.0) * (double)d1 - (1.0 / 10.0) * (double)d2;
     const double acceptor = (1.0 / 10.0) * (double)a1 - (1.0 / 9.0) * (double)a2;

@@ -157,11 +157,27 @@ static int name_table_insert(pjb_ctx *c, const u64 *codes, u32 n) {
 // chains.  extra_contig needs the chain's rows and sorted pairs: queued when the chain is collected, beside the chains of
 // the targets queued after this one; one wait at its end.  A target where the pileup's cap may bite goes through
 // extra_contig_dense instead.
+//   A GROUP (several targets finished as one chain) is one such target in the coordinates of its virtual sequence: its records are
+// classified with their member's offset added, one scan compacts the spans of all members, and extra_contig answers the rows of all
+// members in one launch.  The launches here depend on the number of batches, as a single target's do, not on the number of members.
+// A group in which the sparse answer does not stand (extra_group_apart) is taken apart by its caller, member by member.
+static XMembers members_of(const pjb_ctx *c, const Flight &f) {
+    XMembers M;
+    memset(&M, 0, sizeof M);
+    M.n = (int32_t)f.tids.size();
+    for (size_t m = 0; m < f.tids.size(); m++) {
+        M.tid[m] = f.tids[m];
+        M.voff[m] = f.voff[m];
+        M.len[m] = c->ref_len[(size_t)f.tids[m]];
+    }
+    return M;
+}
 int extra_pre(pjb_ctx *c, Flight &f) {
     if (f.x_pre || c->extra_dense_only || f.empty) return PJB_OK;
     hipStream_t st = c->stream;
     CtlSlot &S = c->sl[f.slot];
     const size_t N = (size_t)f.n_reads;
+    const bool group = f.tids.size() > 1;
     int rc;
     f.x_gap_cap = (u32)std::min<size_t>(N / 16 + 1024, 0x7fffffffu);
     f.x_spos = (int32_t *)xarena_alloc(c, N * 4 + 16); // (compacted: the records with a span)
@@ -171,8 +187,8 @@ int extra_pre(pjb_ctx *c, Flight &f) {
     if (!f.x_spos || !f.x_send || !f.x_gapoff || !f.x_gaps)
         return fail(c, PJB_ERR_NOMEM, "extra: no device memory for what target %d keeps (%zu records)", f.tid, N);
     if ((rc = ensure(c, S.x_q, N + 16)) || (rc = ensure(c, S.x_spos, N * 4 + 16)) || (rc = ensure(c, S.x_send, N * 4 + 16)) ||
-        (rc = ensure(c, S.x_gapoff, (N / 256 + 2) * 4)) || (rc = ensure(c, S.x_zlist, (size_t)X_ZCAP * 4)) ||
-        (rc = ensure(c, S.x_scnt, sizeof(SparseCounters) + sizeof(ExtraCounters))))
+        (rc = ensure(c, S.x_gapoff, (N / 256 + 2) * 4)) || (rc = ensure(c, S.x_zlist, (size_t)X_ZCAP * (group ? 8 : 4))) ||
+        (rc = ensure(c, S.x_scnt, X_SCNT_BYTES)))
         return rc;
     uint8_t *q = (uint8_t *)S.x_q.p;
     SparseCounters *d_cnt = (SparseCounters *)S.x_scnt.p;
@@ -180,9 +196,15 @@ int extra_pre(pjb_ctx *c, Flight &f) {
     else {
         HIP_TRY(c, hipMemsetAsync(q + N, 0, 1, st));
         HIP_TRY(c, hipMemsetAsync(d_cnt, 0, sizeof(SparseCounters) + sizeof(ExtraCounters), st));
-        for (auto &b : f.batches)
-            LAUNCH(c, "kx_classify_sparse", kx_classify_sparse, dim3((unsigned)((b.n + 255) / 256)), dim3(256), b, (int32_t *)S.x_spos.p, (int32_t *)S.x_send.p,
-                   q, (u32 *)S.x_zlist.p, X_ZCAP, d_cnt);
+        for (auto &b : f.batches) {
+            if (b.n <= 0) continue;
+            if (group)
+                LAUNCH(c, "kx_classify_group", kx_classify_sparse<true>, dim3((unsigned)((b.n + 255) / 256)), dim3(256), b, f.voff[(size_t)b.member],
+                       c->ref_len[(size_t)f.tids[(size_t)b.member]], (u32)b.member, (int32_t *)S.x_spos.p, (int32_t *)S.x_send.p, q, (u32 *)S.x_zlist.p, X_ZCAP, d_cnt);
+            else
+                LAUNCH(c, "kx_classify_sparse", kx_classify_sparse<false>, dim3((unsigned)((b.n + 255) / 256)), dim3(256), b, 0, 0, 0u, (int32_t *)S.x_spos.p,
+                       (int32_t *)S.x_send.p, q, (u32 *)S.x_zlist.p, X_ZCAP, d_cnt);
+        }
     }
     if ((rc = run_scan(c, "kx_spans", SparseFn{q},
                        SparseSink{f.x_spos, f.x_send, (u32 *)S.x_gapoff.p, f.x_gapoff, (const int32_t *)S.x_spos.p, (const int32_t *)S.x_send.p, q}, (u64)N + 1,
@@ -192,16 +214,110 @@ int extra_pre(pjb_ctx *c, Flight &f) {
         if (b.n > 0)
         {
             const u32 nblk = (u32)((((u64)b.base + (u64)b.n + 255) >> 8) - (b.base >> 8));
-            LAUNCH(c, "kx_gaps", kx_gaps, dim3(std::min<u32>(nblk, 2048)), dim3(256), b, (const uint8_t *)q, (u32)N, (const u32 *)S.x_gapoff.p, f.x_gaps,
-                   f.x_gap_cap, d_cnt, nblk);
+            LAUNCH(c, "kx_gaps", kx_gaps, dim3(std::min<u32>(nblk, 2048)), dim3(256), b, group ? f.voff[(size_t)b.member] : 0, (const uint8_t *)q, (u32)N,
+                   (const u32 *)S.x_gapoff.p, f.x_gaps, f.x_gap_cap, d_cnt, nblk);
         }
     if (N >= PLP_MAXCNT)
         LAUNCH(c, "kx_cap_check", kx_cap_check, dim3((unsigned)((N + 255) / 256)), dim3(256), (const int32_t *)f.x_spos, d_cnt);
+    if (group)
+        LAUNCH(c, "kx_member_spans", kx_member_spans, dim3(1), dim3(64), (const int32_t *)f.x_spos, (const SparseCounters *)d_cnt, members_of(c, f),
+               (GroupCounters *)((uint8_t *)S.x_scnt.p + sizeof(SparseCounters) + sizeof(ExtraCounters)));
     f.x_pre = true;
     return PJB_OK;
 }
 
-int extra_contig(pjb_ctx *c, Flight &f, int32_t tid, u64 n_spliced, u32 P, u32 J, size_t row_base) {
+// Does the sparse answer stand for the group in fl[0]?  Asked when its chain has completed and BEFORE anything of the group is
+// committed (name table, c->xc, rows): *apart is set when a member needs the depth vector -- the pileup's cap may bite (a false alarm
+// where two members' records lie within max_span of each other in virtual coordinates only costs this), a record with more gaps than
+// a byte counts, the gap list full -- or holds a record that leaves its sequence, or when the group has more records without a span than
+// the list holds.  The members then go one by one through the path of a target finished alone, which decides for each of them.
+int extra_group_apart(pjb_ctx *c, Flight &f, bool *apart) {
+    *apart = false;
+    if (c->extra_dense_only || f.empty) return PJB_OK;
+    int rc;
+    if ((rc = extra_pre(c, f))) return rc;
+    CtlSlot &S = c->sl[f.slot];
+    SparseCounters &hc = *(SparseCounters *)(S.pub + PUB_XCNT_AT);
+    HIP_TRY(c, hipMemcpyAsync(&hc, S.x_scnt.p, sizeof(SparseCounters), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    *apart = hc.need_dense != 0 || hc.n_zero > X_ZCAP;
+    return PJB_OK;
+}
+
+// the rows part for a group: what extra_contig does for one target, once for all members, and one ExtraContig per member -- the
+// hand-over of the coverage in pjb_extra_finish goes target by target -- that share the group's records
+static int extra_contig_group(pjb_ctx *c, Flight &f, const pjb_region_result *res, u64 n_spliced, u32 P, u32 J, size_t row_base) {
+    int rc;
+    if ((rc = extra_pre(c, f))) return rc;
+    hipStream_t st = c->stream;
+    CtlSlot &S = c->sl[f.slot];
+    const size_t n_members = f.tids.size();
+    u64 pairs = 0, juncs = 0;
+    for (size_t m = 0; m < n_members; m++) pairs += (u64)res[m].n_pairs, juncs += (u64)res[m].n_junctions;
+    if (pairs != P || juncs != J)
+        return fail(c, PJB_ERR_STATE, "extra: the members of the group from target %d hold %llu pairs / %llu junctions, the chain %u / %u", f.tid,
+                    (unsigned long long)pairs, (unsigned long long)juncs, P, J);
+    ExtraRow *xr = J ? (ExtraRow *)xarena_alloc(c, (size_t)J * sizeof(ExtraRow)) : nullptr;
+    u64 *pair_code = J ? (u64 *)xarena_alloc(c, (size_t)P * 8 + 16) : nullptr;
+    u32 *pair_row = J ? (u32 *)xarena_alloc(c, (size_t)P * 4 + 16) : nullptr;
+    if (J && (!xr || !pair_code || !pair_row)) return fail(c, PJB_ERR_NOMEM, "extra: no device memory for the pairs of the group from target %d", f.tid);
+    if ((rc = ensure(c, S.x_codes, std::max<size_t>((size_t)n_spliced, 1) * 8))) return rc;
+    SparseCounters *d_cnt = (SparseCounters *)S.x_scnt.p;
+    ExtraCounters *d_xcnt = (ExtraCounters *)(d_cnt + 1);
+    {   // the spliced records' name codes (tile numbers run through the group) -> the name table
+        u32 n_tiles = 0;
+        for (auto &b : f.batches) n_tiles = std::max<u32>(n_tiles, b.tile_base + (u32)((b.n + K1_TILE - 1) / K1_TILE));
+        if ((rc = ensure(c, c->x_tileoff, (size_t)n_tiles * 4 + 16))) return rc;
+        LAUNCH(c, "kx_spliced_offsets", kx_spliced_offsets, dim3(1), dim3(1024), (const TileStats *)S.tile_stats.p, n_tiles, (u32 *)c->x_tileoff.p, d_xcnt);
+        for (auto &b : f.batches)
+            LAUNCH(c, "kx_spliced_codes", kx_spliced_codes, dim3((unsigned)((b.n + K1_TILE - 1) / K1_TILE)), dim3(256), b, (const TileStats *)S.tile_stats.p,
+                   (const u32 *)S.splidx.p, (const u32 *)c->x_tileoff.p, (u64 *)S.x_codes.p);
+        if ((rc = name_table_insert(c, (const u64 *)S.x_codes.p, (u32)n_spliced))) return rc;
+    }
+    if (J > 0) {
+        HIP_TRY(c, hipMemsetAsync(xr, 0, (size_t)J * sizeof(ExtraRow), st));
+        LAUNCH(c, "kx_flank_group", kx_flank_group, dim3((J + 255) / 256), dim3(256), (const pjb_junction_row *)S.rows.p, J, (const int32_t *)f.x_spos,
+               (const int32_t *)f.x_send, members_of(c, f), (const u32 *)S.x_zlist.p, (const SparseCounters *)d_cnt, X_ZCAP, xr);
+        LAUNCH(c, "kx_pair_codes", kx_pair_codes, dim3((P + 255) / 256), dim3(256), f.sidx, f.jid_sorted, f.pr.g, (const DevBatch *)S.batches.p,
+               (int)f.batches.size(), P, (u32)row_base, pair_code, pair_row);
+    }
+    SparseCounters &hc = *(SparseCounters *)(S.pub + PUB_XCNT_AT);
+    ExtraCounters &hx = *(ExtraCounters *)(S.pub + PUB_XCNT_AT + sizeof(SparseCounters));
+    GroupCounters &hg = *(GroupCounters *)(S.pub + PUB_XCNT_AT + sizeof(SparseCounters) + sizeof(ExtraCounters));
+    HIP_TRY(c, hipMemcpyAsync(&hc, d_cnt, X_SCNT_BYTES, hipMemcpyDeviceToHost, st));
+    HIP_TRY(c, hipStreamSynchronize(st));
+    if (c->ktime) ev_collect(c, MISC_POOL);
+    if (hx.n_spliced != (u32)n_spliced)
+        return fail(c, PJB_ERR_STATE, "extra: the group from target %d: %u spliced records in the tile lists, the chain counted %llu", f.tid, hx.n_spliced,
+                    (unsigned long long)n_spliced);
+    if (hc.need_dense || hc.n_zero > X_ZCAP) // (extra_group_apart has said no)
+        return fail(c, PJB_ERR_STATE, "extra: the group from target %d needs the depth vector", f.tid);
+    const SparseDepth D{f.x_spos, f.x_send, f.x_gaps, f.x_gapoff, (u32)hc.total, (u32)(hc.total >> 32), hc.max_span, hc.max_gap};
+    size_t row_at = 0, pair_at = 0; // (rows and sorted pairs are in the order of the junction ids: member after member)
+    for (size_t m = 0; m < n_members; m++) {
+        ExtraContig X;
+        X.tid = f.tids[m];
+        X.len = c->ref_len[(size_t)X.tid];
+        X.voff = f.voff[m];
+        X.row_base = row_base + row_at;
+        X.n_rows = (size_t)res[m].n_junctions;
+        X.n_pairs = (u32)res[m].n_pairs;
+        X.xr = X.n_rows ? xr + row_at : nullptr;
+        X.pair_code = X.n_rows ? pair_code + pair_at : nullptr;
+        X.pair_row = X.n_rows ? pair_row + pair_at : nullptr;
+        X.codes_in_table = true;
+        X.has_unspliced = (hg.has_spans >> m) & 1u;
+        X.sparse = D;
+        row_at += X.n_rows;
+        pair_at += X.n_pairs;
+        c->xc.push_back(X);
+    }
+    return PJB_OK;
+}
+
+int extra_contig(pjb_ctx *c, Flight &f, const pjb_region_result *res, u64 n_spliced, u32 P, u32 J, size_t row_base) {
+    if (f.tids.size() > 1) return extra_contig_group(c, f, res, n_spliced, P, J, row_base);
+    const int32_t tid = f.tid;
     std::vector<DevBatch> &batches = f.batches;
     if (c->extra_dense_only) return extra_contig_dense(c, tid, batches, f.n_reads, n_spliced, P, J, f.sidx, f.jid_sorted, f.pr.g, row_base, false);
     int rc;
@@ -337,7 +453,7 @@ int pjb_extra_finish(pjb_ctx *c, const pjb_extra_row **rows_out, int64_t *n_out)
                    (const u32 *)src->cover, src->len, xr);
         else
             LAUNCH(c, "kx_coverage_sparse", kx_coverage_sparse, dim3((unsigned)((x.n_rows + 255) / 256)), dim3(256), rows, (u32)x.row_base,
-                   (u32)x.n_rows, src->sparse, src->len, xr);
+                   (u32)x.n_rows, src->sparse, src->len, src->voff, xr);
     }
     XTRACE("finish: coverage");
     LAUNCH(c, "kx_rows_out", kx_rows_out, dim3((unsigned)((Jall + 255) / 256)), dim3(256), rows, (const ExtraRow *)xr, (u32)Jall, xout);

@@ -52,6 +52,17 @@ struct ExtraCounters { // one per contig, device memory
     u32 _pad;
 };
 
+// A group of targets finished as one chain keeps its unspliced records in the coordinates of the group's virtual sequence
+// (member m at voff[m], GroupTab): what the kernels that convert between a member's own coordinates and those need
+struct XMembers {
+    int32_t n;
+    int32_t tid[GROUP_MAX], voff[GROUP_MAX], len[GROUP_MAX];
+};
+struct GroupCounters { // behind a slot's SparseCounters and ExtraCounters
+    u32 has_spans; // bit m: member m has unspliced records with a span (the coverage hand-over asks per target)
+    u32 _pad;
+};
+
 struct ExtraRow { // what pjb_extra_finish hands back, parallel to the junction rows
     double mm_score, coverage;
     u32 up_aln, down_aln;

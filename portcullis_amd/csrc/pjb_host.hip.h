@@ -124,6 +124,7 @@ struct ExtraContig {
     bool dense = false;        // went through the dense path: `cover` and the other pointers are allocations of their own
     bool codes_in_table = false; // the spliced records' codes are in the name table already
     SparseDepth sparse = {nullptr, nullptr, nullptr, nullptr, 0, 0, 0, 0}; // else: the records' spans (arena memory)
+    int32_t voff = 0;          // a member of a group: `sparse` holds the whole group's records, this target's at this offset
 };
 
 // what the targets of a PJB_FLAG_EXTRA context keep until pjb_extra_finish comes from a few large allocations that are
@@ -651,7 +652,8 @@ int upload_staged(pjb_ctx *c, void *dst, const uint8_t *src, size_t bytes); // (
 int upload_staged(pjb_ctx *c, void *dst, const uint8_t *src, size_t bytes);                                   // pjb_ingest_api.hip (FASTA bytes through the staging buffers)
 void bam_stage_clear(pjb_ctx *c);                                                                              // pjb_ingest_api.hip (pjb_destroy)
 int extra_pre(pjb_ctx *c, Flight &f);                                                                          // pjb_extra_api.hip (the chain queues a target's extra metrics)
-int extra_contig(pjb_ctx *c, Flight &f, int32_t tid, u64 n_spliced, u32 P, u32 J, size_t row_base);            // pjb_extra_api.hip
+int extra_contig(pjb_ctx *c, Flight &f, const pjb_region_result *res, u64 n_spliced, u32 P, u32 J, size_t row_base); // pjb_extra_api.hip (res: one per member)
+int extra_group_apart(pjb_ctx *c, Flight &f, bool *apart);                                                     // pjb_extra_api.hip (a group that must go member by member)
 // the host row table is complete up to rows_n
 inline int rows_sync(pjb_ctx *c) {
     if (!c->rows_copy_pending) return PJB_OK;
@@ -660,5 +662,7 @@ inline int rows_sync(pjb_ctx *c) {
     return PJB_OK;
 }
 constexpr u32 X_ZCAP = 1u << 20; // --extra: room of the list of unspliced records without a span
+constexpr size_t X_SCNT_BYTES = sizeof(SparseCounters) + sizeof(ExtraCounters) + sizeof(GroupCounters); // a slot's --extra counters (CtlSlot::x_scnt)
+static_assert(PUB_XCNT_AT + X_SCNT_BYTES <= PUB_CHECKED_AT, "control block layout");
 void ingest_kernel_attributes();  // pjb_ingest_api.hip: the inflate kernel's dynamic LDS (pjb_create sets the kernels' attributes on a thread of its own)
 int ingest_lds_bytes();           // pjb_ingest_api.hip: LDS a workgroup of the inflate kernel takes (lanes of one launch)

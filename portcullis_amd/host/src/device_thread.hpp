@@ -117,7 +117,7 @@ private:
     // The chain plan (pjb_plan_groups over the targets this thread will be asked to finish, in index order): a FINISH of a target that
     // belongs to a group of several waits here until the group's last member has been asked for, then the group is queued as ONE
     // kernel chain (pjb_finish_group_begin) -- three chains for a human genome instead of twenty-five, which is what bench.py measures.
-    // Empty: every target is a chain of its own (several contexts share the targets, --extra, PORTCULLIS_CHAIN_PLAN=targets).
+    // Empty: every target is a chain of its own (several contexts share the targets, --extra unless PORTCULLIS_CHAIN_PLAN=groups, PORTCULLIS_CHAIN_PLAN=targets).
     std::vector<std::vector<int32_t>> plan;
     std::map<int32_t, size_t> groupOf;  // target -> its group in `plan`
     struct Waiting {                    // the members of a group that have been asked for so far

@@ -634,14 +634,17 @@ void JunctionBuilder::startDeviceThreads(JuncRun& run) {
     if (extra) nd = per = 1;  // the name multiplicities and the depth hand-over between targets are file-wide: one context
     // The chain plan.  ONE context serves every target (the default for large inputs): the targets that hold alignments, in index
     // order, are finished in the groups pjb_plan_groups makes of them -- what bench.py's step does.  Several contexts take their
-    // targets as the workers come (no telling which context a target goes to), and --extra contexts do not take groups: a
-    // chain per target.  PORTCULLIS_CHAIN_PLAN=targets | groups overrides (groups: only with one context); PORTCULLIS_GROUP_BASES
-    // sets the bases of a group (tests: small genomes in several groups).
+    // targets as the workers come (no telling which context a target goes to): a chain per target.  --extra (always one context)
+    // takes groups as well -- the unspliced records of a group are kept in the coordinates of its virtual sequence -- but plans a
+    // chain per target unless told otherwise (groups become its default when tools/bench_extra.py --targets shows them faster by more
+    // than the per-target runs' spread).
+    // PORTCULLIS_CHAIN_PLAN=targets | groups overrides (groups: only with one context); PORTCULLIS_GROUP_BASES sets the bases of a
+    // group (tests: small genomes in several groups).
     std::vector<int32_t> lens;
     for (auto& r : *refs) lens.push_back(r->length);
     std::vector<std::vector<int32_t>> chainPlan;
-    const bool wantGroups = env->chainGroups >= 0 ? env->chainGroups == 1 : (pinnedPool != nullptr);
-    if (wantGroups && nd * per == 1 && !extra) {
+    const bool wantGroups = env->chainGroups >= 0 ? env->chainGroups == 1 : (pinnedPool != nullptr && !extra);
+    if (wantGroups && nd * per == 1) {
         std::vector<int32_t> groupOf(run.with.size(), 0);
         const int ng = pjb_plan_groups(lens.data(), run.with.data(), (int32_t)run.with.size(), env->groupBases, groupOf.data());
         if (ng > 0) {
