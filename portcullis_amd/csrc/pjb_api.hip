@@ -703,7 +703,7 @@ static int queue_contig(pjb_ctx *c, Flight &f) {
     const u32 pair_blocks = std::max<u32>(1, (PL + 255) / 256);
     // entries per sub-list (list_cap_forced: the test hook pjb_set_option("list_cap", n) -- a first attempt with a room that overflows)
     const u32 gen_cap = lim.list_cap ? lim.list_cap : (c->list_cap_forced ? c->list_cap_forced : gen_list_cap(PL));
-    const u32 pack_nn = (u64)f.n_reads < (1ull << 28) ? 1u : 0u; // (EmitLists::pack_nn)
+    const u32 pack_nn = (u64)n_tiles * K1_TILE < (1ull << 28) ? 1u : 0u; // (EmitLists::pack_nn: the slots of the tiles' spliced lists fit 28 bits)
     if ((rc = ensure(c, S.genlist, (size_t)gen_cap * GEN_SHARDS * 8 * 3))) return rc; // (three lists: EmitLists)
     if ((rc = ensure(c, S.gencount, GEN_SHARDS * GEN_CNT_STRIDE * 4))) return rc; // a line per sub-list: reads, pairs
     // ---- junction-sized buffers
@@ -842,7 +842,7 @@ static int queue_contig(pjb_ctx *c, Flight &f) {
         }
         LAUNCH(c, "k1_scan_tiles", k1_scan_tiles, dim3(c->k1s_blocks_forced ? (u32)c->k1s_blocks_forced : k1s_blocks(n_tiles)), dim3(K1S_THREADS), (u32 *)S.tile_cnt.p, (const TileStats *)S.tile_stats.p,
                n_tiles, d_cs, PL, kf, group ? INT32_MAX - 1 : ref_len, (const u64 *)nullptr, (u32 *)S.tile_soff.p, (u32 *)S.chunk_tile.p,
-               (ScanPart *)S.scan_parts.p, ++S.scan_epoch);
+               (ScanPart *)S.scan_parts.p, ++S.scan_epoch, c->window_skip ? 1u : 0u);
         // ---- K1b: emit (coordinates in the group's virtual sequence): keys, the pairs' records -- complete for reads of the
         // simple shape --, K2d's candidate keys (free until the first scatter; they are used up before it), the list of
         // reads for k4b_generic
@@ -898,7 +898,7 @@ static int queue_contig(pjb_ctx *c, Flight &f) {
     auto launch_k4b = [&]() -> int {
         LAUNCH(c, "k4b_generic", k4b_generic, dim3(gen_grid), dim3(256), (const u64 *)S.genlist.p, (const u32 *)d_gen_cnt, gen_cap, (const u64 *)pr.key,
                pr.rec, (const u32 *)S.jidbam.p, kf, (const DevBatch *)S.batches.p, (int)batches.size(), (const int32_t *)S.ancl.p, (const int32_t *)S.ancr.p,
-               GT, any_x ? 1 : 0, any_x ? 0 : 1, d_err, (const ContigStats *)d_cs, pack_nn);
+               GT, any_x ? 1 : 0, any_x ? 0 : 1, d_err, (const ContigStats *)d_cs, pack_nn, (const u32 *)S.splidx.p, (const uint4 *)S.splrec.p);
         return PJB_OK;
     };
     auto fork_k4b = [&]() -> int { // (the main stream has just produced jid_bam and the anchors)
@@ -1773,6 +1773,7 @@ int pjb_set_option(pjb_ctx *c, const char *name, int64_t value) {
     else if (n == "dense_ids") c->dense_ids = value != 0;
     else if (n == "extra_dense") c->extra_dense_only = value != 0;
     else if (n == "sort_floor") c->sort_floor = (u32)std::max<int64_t>(1, std::min<int64_t>(value, 1 << 30));
+    else if (n == "window_skip") c->window_skip = value != 0;
     else if (n == "list_cap") c->list_cap_forced = (u32)std::max<int64_t>(0, std::min<int64_t>(value, 1 << 30));
     else return fail(c, PJB_ERR_ARG, "set_option: unknown option '%s'", name);
     return PJB_OK;

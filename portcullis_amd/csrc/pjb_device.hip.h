@@ -52,8 +52,9 @@ struct TileStats { // per K1 tile
     int32_t max_end;   // max(pos + alignedLength)
     int32_t max_nlen;  // longest N op
     int32_t min_pos;
-    int32_t _pad;
+    u32 max_span;      // longest alignment without its N operations (aligned length - sum of N lengths, saturating): see ContigStats::max_span
 };
+static_assert(sizeof(TileStats) == 40, "TileStats layout");
 
 // Per-contig control block in device memory.  The host sizes buffers and grids from LIMITS it chooses before anything
 // runs (pairs, junctions, key format); the kernels read the actual counts from here, and a count that exceeds its limit
@@ -75,7 +76,19 @@ struct ContigStats {
     u32 n_cand;    // K2d: keys in the candidate list (every junction at least once, few of them more often)
     u32 n_slices;  // ceil(P / 64): 64-pair slices of the sorted pair array (fragments, run masks)
     u32 list_need; // OVF_LISTS: the fullest sub-list of the read lists (EmitLists) wanted this many entries
+    u32 max_span;  // B: the chain's longest alignment without its N operations.  No pair of the chain has istart - lStart or rEnd - iend above
+                   // it (a pair's anchors are blocks of one read: junction_system.cc:140-210; the clamps only shorten them), so no junction's
+                   // window reaches further than B beyond its intron: k1_emit / k1_generic list a closed read for k4b_generic's window check
+                   // only where that can reach a neighbouring intron (window_reach).  All-ones: pjb_set_option("window_skip", 0), list them all
 };
+static_assert(sizeof(ContigStats) == 112, "ContigStats layout");
+// A closed read [S] B (N B)+ [S]: can some junction's window reach over the intron before / behind the block of `blk` reference positions
+// that lies between two of its introns (nl_prev, nl_next long)?  k4b_generic's tests: prev_istart >= anc_l[j], where prev_istart = istart -
+// blk - nl_prev and anc_l[j] >= istart - B; next_iend + 1 <= anc_r[j], where next_iend = iend + blk + nl_next and anc_r[j] <= iend + B.
+__device__ __forceinline__ bool window_reach(u32 blk, u32 nl_prev, u32 nl_next, u32 B) {
+    const u32 l = __builtin_elementwise_add_sat(blk, nl_prev), r = __builtin_elementwise_add_sat(__builtin_elementwise_add_sat(blk, nl_next), 1u);
+    return l <= B || r <= B; // (a sum that saturates: only an all-ones B lists the read, and that lists every read)
+}
 
 // A pair = one N operation walked (JunctionSystem::addJunctions, junction_system.cc:140-210).  k1_emit writes, in BAM order,
 // the pair's intron key (its own array: kd_assign and the sort's first pass stream over the keys alone) and ONE 32-byte record

@@ -293,6 +293,7 @@ struct pjb_ctx {
     int radix_max_bits = 11;
     double junc_per_read = 0;         // most junctions per read a chain of this context has had (the sort's digits of the next chain)
     u32 sort_floor = 1u << 16;        // pjb_set_option("sort_floor", n): the least number of junction ids the sort's digits are planned for (tests: small)
+    bool window_skip = true;          // pjb_set_option("window_skip", 0): every closed read of two and more introns goes on the window-check list (ContigStats::max_span)
     u32 list_cap_forced = 0;          // pjb_set_option("list_cap", n): the read lists' first room (tests of the OVF_LISTS repeat)
     bool k1_serial = true;            // PJB_K1_SERIAL=0: the chains' K1 stages side by side
     hipEvent_t last_k1_ev = nullptr;  // the K1 stage of the chain queued last

@@ -2,7 +2,8 @@
 // Portcullis `junc` hot path.  Integer / byte work bounded by HBM bandwidth; no MFMA.
 //
 // The chain of one target or group of targets (DESIGN.md section 4 has the table, the data layout and the byte counts):
-//   K1   k1_count, k1_scan_tiles   per-read CIGAR walk: N-op count, length stats, sortedness; the tiles' spliced lists     (a1,a2)
+//   K1   k1_count, k1_scan_tiles   per-read CIGAR walk: N-op count, length stats, sortedness, the block-span bound B;
+//                                  the tiles' spliced lists                                                               (a1,a2)
 //        k1_emit                   the spliced reads of the closed-form shapes: pairs (key, 32-byte record) complete       (a3,a5,a8,a12)
 //        k1_generic                every other spliced read: its operations walked, pairs, closed form where possible      (a3,a5,a8,a12)
 //   K2d  kd_*                      ordered dense junction ids from candidate keys; junction keys and anchors               (a3,a5)
@@ -189,6 +190,11 @@ __global__ __launch_bounds__(256) void k0_encode2(const uint8_t *g, int64_t n, u
 __device__ __forceinline__ u32 spl_nlq(u32 n, bool seq_ok, int32_t lq) {
     return (n < 0x7fffu ? n : 0x7fffu) | (seq_ok ? 0x8000u : 0u) | ((u32)lq < 0xffffu ? (u32)lq << 16 : 0xffff0000u);
 }
+// A spliced read's span without its introns (TileStats::max_span): aligned length - sum of its N lengths.  An aligned length that left 31
+// bits (nothing the walks' 32-bit coordinates can hold) or a sum that saturated gives all-ones: the chain's bound then excludes nothing.
+__device__ __forceinline__ u32 read_span(int32_t aligned, u32 nsum) {
+    return aligned < 0 || nsum > (u32)aligned ? 0xffffffffu : (u32)aligned - nsum;
+}
 #ifndef K1C_T
 #define K1C_T 256 // threads of a k1_count block (a tile is K1_TILE reads: 4 per thread).  512 threads x 2 reads need 64 registers instead of
                   // 84 but took 88 against 63 us a launch beside the other chains' kernels: a block of 8 wavefronts waits for 8 free slots on ONE CU
@@ -283,6 +289,7 @@ __device__ __forceinline__ void k1_count_rows(const GBatch &b, const u32 tile_lo
     u64 sum = 0;
     int32_t mn = INT32_MAX, mx = 0, max_end = 0, max_nlen = 0, min_pos = INT32_MAX;
     u32 cN[4], nlq[4];
+    u32 mspan = 0; // TileStats::max_span
     u32 xspan = 0, xgapmax = 0;
     bool xmany = false;
 #pragma unroll
@@ -298,7 +305,7 @@ __device__ __forceinline__ void k1_count_rows(const GBatch &b, const u32 tile_lo
         const u32 n = c[i + 1] - c[i];
         nlq[i] = spl_nlq(n, (u64)(so[i + 1] - so[i]) * 8ull >= (u64)(int64_t)lenv, lenv);
         const u32 *ops = s_ops + (c[i] - cA + shift);
-        u32 cc = 0, ngap = 0, gmax = 0;
+        u32 cc = 0, ngap = 0, gmax = 0, nsum = 0;
         int32_t al = 0;
         auto count_op = [&](u32 op) {
             const u32 ty = op & 15u;
@@ -307,6 +314,7 @@ __device__ __forceinline__ void k1_count_rows(const GBatch &b, const u32 tile_lo
             if (ty == OP_N) {
                 cc++;
                 max_nlen = ln > max_nlen ? ln : max_nlen;
+                nsum = __builtin_elementwise_add_sat(nsum, (u32)ln);
             }
             if (EXTRA && ty == OP_D && ln) { // inside the span, no depth
                 ngap++;
@@ -325,6 +333,7 @@ __device__ __forceinline__ void k1_count_rows(const GBatch &b, const u32 tile_lo
             const int32_t e = p + al;
             max_end = e > max_end ? e : max_end;
             min_pos = p < min_pos ? p : min_pos;
+            mspan = max(mspan, read_span(al, nsum));
         } else
             uns++;
         cN[i] = cc;
@@ -393,7 +402,9 @@ __device__ __forceinline__ void k1_count_rows(const GBatch &b, const u32 tile_lo
     max_end = smax(max_end);
     max_nlen = smax(max_nlen);
     min_pos = smin(min_pos);
+    mspan = wave_total<DppMax>(mspan);
     if (lane_id() == 0) {
+        r32[w][5] = (int32_t)mspan;
         r64[w][0] = ((u64)w_cnt << 32) | w_su;
         r64[w][1] = sum;
         r32[w][0] = mn;
@@ -407,8 +418,9 @@ __device__ __forceinline__ void k1_count_rows(const GBatch &b, const u32 tile_lo
         u64 pk = 0;
         TileStats ts;
         ts.sum_len = 0;
-        ts.min_len = INT32_MAX, ts.max_len = 0, ts.max_end = 0, ts.max_nlen = 0, ts.min_pos = INT32_MAX;
+        ts.min_len = INT32_MAX, ts.max_len = 0, ts.max_end = 0, ts.max_nlen = 0, ts.min_pos = INT32_MAX, ts.max_span = 0;
         for (int i = 0; i < NW; i++) {
+            ts.max_span = max(ts.max_span, (u32)r32[i][5]);
             pk += r64[i][0];
             ts.sum_len += r64[i][1];
             ts.min_len = min(ts.min_len, r32[i][0]);
@@ -420,7 +432,6 @@ __device__ __forceinline__ void k1_count_rows(const GBatch &b, const u32 tile_lo
         ts.spliced = (u32)((pk >> 16) & 0xffff);
         ts.unspliced = (u32)(pk & 0xffff);
         if (chk_ref_len > 0 && ts.max_end > chk_ref_len) ts.max_end = INT32_MAX;
-        ts._pad = 0;
         tile_stats[blockIdx.x] = ts;
         tile_cnt[blockIdx.x] = (u32)(pk >> 32);
     }
@@ -446,6 +457,7 @@ __global__ __launch_bounds__(K1C_T) __attribute__((amdgpu_waves_per_eu(K1C_WAVES
     u32 cnt = 0, spl = 0, uns = 0;
     u64 sum = 0;
     int32_t mn = INT32_MAX, mx = 0, max_end = 0, max_nlen = 0, min_pos = INT32_MAX;
+    u32 mspan = 0; // TileStats::max_span
     // all loads of the thread's 4 reads are issued before anything is consumed: offsets, then the first
     // K1_OPS ops of every CIGAR (longer CIGARs continue from global memory), then the per-read scalars
     constexpr int K1_OPS = 4;
@@ -505,7 +517,7 @@ __global__ __launch_bounds__(K1C_T) __attribute__((amdgpu_waves_per_eu(K1C_WAVES
             const int32_t p = pos4[it];
             if (bad & (1u << it)) set_error(err, b.base + (u32)r, PJB_ERR_UNSORTED);
             if (bad & (16u << it)) set_error(err, b.base + (u32)r, PJB_ERR_BAD_XS);
-            u32 c = 0, ngap = 0, gmax = 0;
+            u32 c = 0, ngap = 0, gmax = 0, nsum = 0;
             int32_t al = 0;
             auto count_op = [&](u32 op) {
                 const u32 ty = op & 15u;
@@ -514,6 +526,7 @@ __global__ __launch_bounds__(K1C_T) __attribute__((amdgpu_waves_per_eu(K1C_WAVES
                 if (ty == OP_N) {
                     c++;
                     max_nlen = ln > max_nlen ? ln : max_nlen;
+                    nsum = __builtin_elementwise_add_sat(nsum, (u32)ln);
                 }
                 if (EXTRA && ty == OP_D && ln) { // inside the span, no depth
                     ngap++;
@@ -529,6 +542,7 @@ __global__ __launch_bounds__(K1C_T) __attribute__((amdgpu_waves_per_eu(K1C_WAVES
                 int32_t e = p + al;
                 max_end = e > max_end ? e : max_end;
                 min_pos = p < min_pos ? p : min_pos;
+                mspan = max(mspan, read_span(al, nsum));
             } else
                 uns++;
             cthis = c;
@@ -604,6 +618,7 @@ __global__ __launch_bounds__(K1C_T) __attribute__((amdgpu_waves_per_eu(K1C_WAVES
     max_end = smax(max_end);
     max_nlen = smax(max_nlen);
     min_pos = smin(min_pos);
+    mspan = wave_total<DppMax>(mspan);
     int w = threadIdx.x >> 6;
     __shared__ u64 smp[NW];
     if (lane_id() == 0) {
@@ -614,14 +629,16 @@ __global__ __launch_bounds__(K1C_T) __attribute__((amdgpu_waves_per_eu(K1C_WAVES
         smi[w][2] = max_end;
         smi[w][3] = max_nlen;
         smi[w][4] = min_pos;
+        smi[w][5] = (int32_t)mspan;
     }
     __syncthreads();
     if (threadIdx.x == 0) {
         u64 p = 0;
         TileStats t;
         t.sum_len = 0;
-        t.min_len = INT32_MAX, t.max_len = 0, t.max_end = 0, t.max_nlen = 0, t.min_pos = INT32_MAX;
+        t.min_len = INT32_MAX, t.max_len = 0, t.max_end = 0, t.max_nlen = 0, t.min_pos = INT32_MAX, t.max_span = 0;
         for (int i = 0; i < NW; i++) {
+            t.max_span = max(t.max_span, (u32)smi[i][5]);
             p += smp[i];
             t.sum_len += sm64[i];
             t.min_len = min(t.min_len, smi[i][0]);
@@ -633,7 +650,6 @@ __global__ __launch_bounds__(K1C_T) __attribute__((amdgpu_waves_per_eu(K1C_WAVES
         t.spliced = (u32)((p >> 16) & 0xffff);
         t.unspliced = (u32)(p & 0xffff);
         if (chk_ref_len > 0 && t.max_end > chk_ref_len) t.max_end = INT32_MAX;
-        t._pad = 0;
         tile_stats[blockIdx.x] = t;
         tile_cnt[blockIdx.x] = (u32)(p >> 32);
     }
@@ -657,7 +673,7 @@ struct ScanPart { // what one block of k1_scan_tiles found in its range of tiles
     u64 pairs, spl, uns, sum;
     int32_t mn, mx, max_end, max_nlen, min_pos;
     u32 flag; // == the launch's epoch: the part is complete
-    u32 _pad[2];
+    u32 max_span, _pad;
 };
 static_assert(sizeof(ScanPart) == 64, "ScanPart layout");
 __host__ __device__ inline u32 k1s_blocks(u32 n_tiles) { // ~1024 tiles a block
@@ -666,14 +682,14 @@ __host__ __device__ inline u32 k1s_blocks(u32 n_tiles) { // ~1024 tiles a block
 }
 __global__ __launch_bounds__(K1S_THREADS) void k1_scan_tiles(u32 *tile_cnt, const TileStats *ts, u32 n_tiles, ContigStats *out, u32 pair_limit,
                                                               KeyFmt kf, int32_t ref_len, const u64 *tile_desc, u32 *tile_soff, u32 *chunk_tile,
-                                                              ScanPart *parts, u32 epoch) {
+                                                              ScanPart *parts, u32 epoch, u32 window_skip) {
     constexpr int NW = K1S_THREADS / 64;
     __shared__ u64 wsum[NW];
     __shared__ u32 wsum2[NW];
     __shared__ u32 carry2_s;
     __shared__ u64 carry_s;
     __shared__ u64 r_pairs[NW], r_spl[NW], r_uns[NW], r_sum[NW];
-    __shared__ int32_t r_i[NW][5];
+    __shared__ int32_t r_i[NW][6];
     __shared__ ScanPart total_s; // (last block: everything before it)
     const u32 nblk = gridDim.x, blk = blockIdx.x;
     // the block's range: whole rounds of 16 tiles per thread so that ranges start at multiples of 16
@@ -683,6 +699,7 @@ __global__ __launch_bounds__(K1S_THREADS) void k1_scan_tiles(u32 *tile_cnt, cons
     // ---- pass A: the range's sums
     u64 pairs = 0, spl = 0, uns = 0, sum = 0;
     int32_t mn = INT32_MAX, mx = 0, max_end = 0, max_nlen = 0, min_pos = INT32_MAX;
+    u32 max_span = 0;
     for (u32 base = lo; base < hi; base += K1S_THREADS * K1S_PER) {
         const u32 i0 = base + K1S_PER * threadIdx.x;
 #pragma unroll 4
@@ -700,6 +717,7 @@ __global__ __launch_bounds__(K1S_THREADS) void k1_scan_tiles(u32 *tile_cnt, cons
                 max_end = max(max_end, t.max_end);
                 max_nlen = max(max_nlen, t.max_nlen);
                 min_pos = min(min_pos, t.min_pos);
+                max_span = max(max_span, t.max_span);
             }
         }
     }
@@ -712,7 +730,9 @@ __global__ __launch_bounds__(K1S_THREADS) void k1_scan_tiles(u32 *tile_cnt, cons
     max_end = wave_max(max_end);
     max_nlen = wave_max(max_nlen);
     min_pos = wave_min(min_pos);
+    max_span = wave_max(max_span);
     if (lane_id() == 0) {
+        r_i[w][5] = (int32_t)max_span;
         r_pairs[w] = pairs;
         r_spl[w] = spl;
         r_uns[w] = uns;
@@ -726,8 +746,9 @@ __global__ __launch_bounds__(K1S_THREADS) void k1_scan_tiles(u32 *tile_cnt, cons
     __syncthreads();
     ScanPart mine;
     mine.pairs = mine.spl = mine.uns = mine.sum = 0;
-    mine.mn = INT32_MAX, mine.mx = 0, mine.max_end = 0, mine.max_nlen = 0, mine.min_pos = INT32_MAX;
+    mine.mn = INT32_MAX, mine.mx = 0, mine.max_end = 0, mine.max_nlen = 0, mine.min_pos = INT32_MAX, mine.max_span = 0;
     for (int k = 0; k < NW; k++) {
+        mine.max_span = max(mine.max_span, (u32)r_i[k][5]);
         mine.pairs += r_pairs[k];
         mine.spl += r_spl[k];
         mine.uns += r_uns[k];
@@ -749,6 +770,7 @@ __global__ __launch_bounds__(K1S_THREADS) void k1_scan_tiles(u32 *tile_cnt, cons
         o->max_end = mine.max_end;
         o->max_nlen = mine.max_nlen;
         o->min_pos = mine.min_pos;
+        o->max_span = mine.max_span;
         __hip_atomic_store(&o->flag, epoch, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);
     }
     // ---- what the blocks before this one hold: lane k of the first wavefront waits for block k
@@ -756,7 +778,7 @@ __global__ __launch_bounds__(K1S_THREADS) void k1_scan_tiles(u32 *tile_cnt, cons
         const u32 l = lane_id();
         ScanPart b;
         b.pairs = b.spl = b.uns = b.sum = 0;
-        b.mn = INT32_MAX, b.mx = 0, b.max_end = 0, b.max_nlen = 0, b.min_pos = INT32_MAX;
+        b.mn = INT32_MAX, b.mx = 0, b.max_end = 0, b.max_nlen = 0, b.min_pos = INT32_MAX, b.max_span = 0;
         if (l < blk) {
             const ScanPart *o = parts + l;
             while (__hip_atomic_load(&o->flag, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_AGENT) != epoch) __builtin_amdgcn_s_sleep(1);
@@ -770,6 +792,7 @@ __global__ __launch_bounds__(K1S_THREADS) void k1_scan_tiles(u32 *tile_cnt, cons
                 b.max_end = __hip_atomic_load(&o->max_end, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
                 b.max_nlen = __hip_atomic_load(&o->max_nlen, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
                 b.min_pos = __hip_atomic_load(&o->min_pos, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                b.max_span = __hip_atomic_load(&o->max_span, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             }
         }
         b.pairs = wave_sum(b.pairs);
@@ -782,6 +805,7 @@ __global__ __launch_bounds__(K1S_THREADS) void k1_scan_tiles(u32 *tile_cnt, cons
             b.max_end = wave_max(b.max_end);
             b.max_nlen = wave_max(b.max_nlen);
             b.min_pos = wave_min(b.min_pos);
+            b.max_span = wave_max(b.max_span);
         }
         if (l == 0) {
             carry_s = b.pairs;
@@ -885,6 +909,7 @@ __global__ __launch_bounds__(K1S_THREADS) void k1_scan_tiles(u32 *tile_cnt, cons
         out->n_junc = out->n_runs = 0;
         out->list_need = 0;
         out->n_cand = 0;
+        out->max_span = window_skip ? max(b.max_span, mine.max_span) : 0xffffffffu;
     }
 }
 
@@ -1039,6 +1064,65 @@ struct OpsViewT {
     __device__ __forceinline__ u32 operator[](u32 k) const { return k < (u32)NLDS ? lds[k * STRIDE] : gload(g + k); }
 };
 typedef OpsViewT<256, OPS_LDS> OpsView;
+// The first OPS_LDS operations of a read whose operations start at word c0 of its batch's `cig_words` words: two 16-byte loads (a lane's
+// eight words are neighbours: eight word gathers cost the addresser eight times as much).  The batch's last operations are read from
+// eight words before its end and shifted -- the loads never leave the array --; what lies behind the read's last operation is the next
+// read's, the caller masks it.
+__device__ __forceinline__ void fetch_ops8(const PJB_GLOBAL u32 *cigar, u32 c0, u32 cig_words, u32 (&w)[OPS_LDS]) {
+    static_assert(OPS_LDS == 8, "two 16-byte loads");
+    if (cig_words >= (u32)OPS_LDS) {
+        const u32 c0c = c0 + (u32)OPS_LDS <= cig_words ? c0 : cig_words - (u32)OPS_LDS;
+        const Words4 lo4 = gload_as<Words4>(cigar + c0c), hi4 = gload_as<Words4>(cigar + c0c + 4);
+        w[0] = lo4.x, w[1] = lo4.y, w[2] = lo4.z, w[3] = lo4.w, w[4] = hi4.x, w[5] = hi4.y, w[6] = hi4.z, w[7] = hi4.w;
+        if (c0c != c0) { // (shifted: at most seven words)
+            const u32 sh = c0 - c0c;
+#pragma unroll
+            for (int q = 0; q < OPS_LDS; q++) {
+                u32 v = 0;
+#pragma unroll
+                for (int j = q; j < OPS_LDS; j++) v = (u32)(j - q) == sh ? w[j] : v;
+                w[q] = v;
+            }
+        }
+    } else { // (a batch of fewer than eight operations: word by word, guarded)
+#pragma unroll
+        for (int q = 0; q < OPS_LDS; q++) w[q] = c0 + (u32)q < cig_words ? cigar[c0 + (u32)q] : 0u;
+    }
+}
+// What k1_generic and k4b_generic keep of the chain's batches in LDS, filled once per block (256 threads): a read's batch is found from
+// its tile without a load, and the ends of the batch's arrays -- nothing reads past them -- are at hand.  A chain of more batches than
+// the table holds searches the descriptors in device memory.
+constexpr int GEN_MAXB = 256;
+struct BatchTab {
+    u32 tbase[GEN_MAXB], seqw[GEN_MAXB], cigw[GEN_MAXB]; // the batch's first tile; words of packed bases / of operations in it
+    __device__ __forceinline__ void fill(const DevBatch *batches, int n_batches) { // (the caller's barrier follows)
+        if ((int)threadIdx.x < n_batches && threadIdx.x < (u32)GEN_MAXB) {
+            const PJB_GLOBAL DevBatch *d = as_global(batches + threadIdx.x);
+            tbase[threadIdx.x] = d->tile_base;
+            seqw[threadIdx.x] = as_global(d->seq_off)[d->n];
+            cigw[threadIdx.x] = as_global(d->cig_off)[d->n];
+        }
+    }
+    __device__ __forceinline__ int find(const DevBatch *batches, int n_batches, u32 tile) const { // the last batch with tile_base <= tile
+        int lo = 0, hi = n_batches - 1;
+        if (n_batches <= GEN_MAXB) {
+            while (lo < hi) {
+                const int mid = (lo + hi + 1) >> 1;
+                if (tbase[mid] <= tile) lo = mid;
+                else hi = mid - 1;
+            }
+        } else {
+            while (lo < hi) {
+                const int mid = (lo + hi + 1) >> 1;
+                if (gload(&batches[mid].tile_base) <= tile) lo = mid;
+                else hi = mid - 1;
+            }
+        }
+        return lo;
+    }
+    __device__ __forceinline__ u32 seq_words(const DevBatch &b, int bi) const { return bi < GEN_MAXB ? seqw[bi] : gload(b.seq_off + b.n); }
+    __device__ __forceinline__ u32 cig_words(const DevBatch &b, int bi) const { return bi < GEN_MAXB ? cigw[bi] : gload(b.cig_off + b.n); }
+};
 
 struct NCursor { // walks the N ops of one CIGAR yielding the unclamped position after each N
     u32 i;
@@ -1276,13 +1360,13 @@ struct EmitLists {
     u64 *bitmap;    // K2d's bitmap of intron starts (all-clear at rest): every candidate sets its start's bit as it is listed
     u32 *page_cnt;  // starts per PAGE of the bitmap (64 words = 4 096 bases; all-zero at rest): counted as their bits are set for the first time
     u64 *cand_anc;  // per candidate: min lStart | max rEnd << 32 over the pairs it stands for (the junction anchors' first level)
-    u64 *gen_list;  // [3][GEN_SHARDS][gen_cap].  Lists 1 and 2, for k4b_generic: global read ordinal | index of the read's first pair
-                    // << 32 -- the reads whose pairs need the generic walks; the reads whose closed form waits for the window check.
-                    // List 3, for k1_generic: the read's slot in the tiles' spliced lists | index of its first pair << 32.
+    u64 *gen_list;  // [3][GEN_SHARDS][gen_cap], every entry the read's slot in the tiles' spliced lists (spl_idx, spl_rec: what k1_count kept of it)
+                    // | index of its first pair << 32.  Lists 1 and 2, for k4b_generic: the reads whose pairs need the generic walks; the reads
+                    // whose closed form waits for the window check.  List 3, for k1_generic.
     u32 *gen_cnt;   // [GEN_SHARDS][GEN_CNT_STRIDE]: words 2 l - 2, 2 l - 1 = entries of list l's sub-list, pairs of those reads -- a cache
                     // line per shard: atomics on one line are served one after the other, whatever the address in it
     u32 gen_cap;    // room of one sub-list
-    u32 pack_nn;    // 1 (chains of fewer than 2^28 reads): entries of the second list carry min(N operations, 15) in bits 28-31 of the read ordinal
+    u32 pack_nn;    // 1 (chains of fewer than 2^28 slots): entries of the second list carry min(N operations, 15) in bits 28-31 of the slot
 };
 // Room of a sub-list (before anything says otherwise): k1_emit deals its chunks of 256 spliced reads round-robin to the sub-lists
 // (up to 256 entries a chunk on list 2 and on list 3), k1_generic its chunks of 256 items of list 3 (up to 256 entries on list 1
@@ -1519,6 +1603,7 @@ __global__ __launch_bounds__(K1E_T) __attribute__((amdgpu_waves_per_eu(K1E_WAVES
     __shared__ u32 s_seqw[K1E_MAXB], s_cigw[K1E_MAXB], s_tbase[K1E_MAXB]; // words of packed bases / operations in batch i; its first tile
     __shared__ u32 s_wsum[4];
     if (cs->P == 0) return; // no pairs, or a limit was exceeded: the contig is repeated with larger buffers
+    const u32 max_span = cs->max_span; // (uniform: a scalar load)
     K1E_T0();
     const bool want_g = P.g != nullptr; // (--extra contexts: the pairs' read ordinals)
     const bool want_cand = E.cand != nullptr;
@@ -1636,28 +1721,7 @@ __global__ __launch_bounds__(K1E_T) __attribute__((amdgpu_waves_per_eu(K1E_WAVES
             if (b.seq2 != nullptr) O.excw = b.seq_exc[r >> 5]; // (uniform test: the batch either has 2-bit bases or not)
             O.lq = (int32_t)(R.sr.w >> 16);
             if (O.lq == 0xffff) O.lq = b.l_qseq[r];
-            static_assert(OPS_LDS == 8, "two 16-byte loads");
-            if (cig_words >= (u32)OPS_LDS) {
-                // (the batch's last operations are read from eight words before its end: the loads never leave the array)
-                const u32 c0c = c0 + (u32)OPS_LDS <= cig_words ? c0 : cig_words - (u32)OPS_LDS;
-                const Words4 lo4 = gload_as<Words4>(b.cigar + c0c), hi4 = gload_as<Words4>(b.cigar + c0c + 4);
-                u32 w[OPS_LDS] = {lo4.x, lo4.y, lo4.z, lo4.w, hi4.x, hi4.y, hi4.z, hi4.w};
-                if (c0c != c0) { // (shifted: at most seven words)
-                    const u32 sh = c0 - c0c;
-#pragma unroll
-                    for (int q = 0; q < OPS_LDS; q++) {
-                        u32 v = 0;
-#pragma unroll
-                        for (int j = q; j < OPS_LDS; j++) v = (u32)(j - q) == sh ? w[j] : v;
-                        w[q] = v;
-                    }
-                }
-#pragma unroll
-                for (int q = 0; q < OPS_LDS; q++) O.op[q] = w[q];
-            } else { // (a batch of fewer than eight operations: word by word, guarded)
-#pragma unroll
-                for (int q = 0; q < OPS_LDS; q++) O.op[q] = c0 + (u32)q < cig_words ? b.cigar[c0 + (u32)q] : 0u;
-            }
+            fetch_ops8(b.cigar, c0, cig_words, O.op);
         }
         return O;
     };
@@ -1689,7 +1753,7 @@ __global__ __launch_bounds__(K1E_T) __attribute__((amdgpu_waves_per_eu(K1E_WAVES
         // A read of the shape [S] M N M [S] or [S] M N M N M [S] (l_qseq matching, bases present) is finished here, in closed form
         // (junction_system.cc:140-210 for one or two N operations); any other read goes on k1_generic's list: a few lanes of every
         // wavefront walking their reads kept the whole block waiting (84 of 307 us a launch for one read in twenty).
-        bool generic = false, simple = false, two = false;
+        bool generic = false, simple = false, two = false, chk2 = false; // (chk2: a read of two introns whose window check cannot be ruled out)
         u32 dS = 0, a = 0, nl = 0, b2 = 0, nl2 = 0, b3 = 0, meta = 0, off = 0, g = 0;
         if (on) {
             const u32 n = O.n;
@@ -1726,10 +1790,11 @@ __global__ __launch_bounds__(K1E_T) __attribute__((amdgpu_waves_per_eu(K1E_WAVES
                 }
             }
             two = two && simple;
+            chk2 = two && window_reach(b2, nl, nl2, max_span);
             generic = !simple;
         }
         const u32 shard = (chunk >> (8 - K1E_SHIFT)) % GEN_SHARDS;
-        const u32 base2 = ctx.list_reserve(2, two, 2u, shard), base3 = ctx.list_reserve(3, generic, 0u, shard);
+        const u32 base2 = ctx.list_reserve(2, chk2, 2u, shard), base3 = ctx.list_reserve(3, generic, 0u, shard);
         K1E_MARK(2); // shapes (waits for the operations)
         // ---- in 2 bits: the read is pure ACGT, lies inside its target (nothing clamped: block k of its bases starts at g2s[k]), no block
         // longer than the bitmap load covers.  The exception bitmap under the blocks -- bits g2s >> 6 .. (g2s + len - 1) >> 6, at most 31 of
@@ -1903,9 +1968,9 @@ __global__ __launch_bounds__(K1E_T) __attribute__((amdgpu_waves_per_eu(K1E_WAVES
                 if (want_cand) cand_insert(key, Q.lstart, Q.rend);
             }
         }
-        const u64 p1_entry = (u64)(E.pack_nn ? g | (2u << 28) : g) | ((u64)off << 32);
+        const u64 p1_entry = (u64)(E.pack_nn ? R.slot | (2u << 28) : R.slot) | ((u64)off << 32);
         K1E_MARK(7); // compares, records, candidates
-        ctx.list_write(2, two, base2, p1_entry, shard);
+        ctx.list_write(2, chk2, base2, p1_entry, shard);
         ctx.list_write(3, generic, base3, (u64)R.slot | ((u64)off << 32), shard); // (the read's place in the tiles' lists, its first pair)
         K1E_MARK(8); // list entries
         // (the candidate set is flushed when the block leaves: a set that fills up before that sends its keys straight to the list --
@@ -1923,29 +1988,24 @@ __global__ __launch_bounds__(K1E_T) __attribute__((amdgpu_waves_per_eu(K1E_WAVES
 // The reads k1_emit did not finish (three and more introns, indels, = X P H operations, clamped ends, exotic targets, SEQ '*'):
 // a thread per read of the chain's third list, dense.  The read's operations are walked (emit_read_pairs): keys and records
 // of its pairs, candidates, and -- for [S] B (N B)+ [S] -- the blocks' compares; then the read goes on one of k4b_generic's
-// lists.  One launch per chain, behind the chain's k1_emit launches.
-__device__ __forceinline__ const DevBatch &find_batch_by_tile(const DevBatch *batches, int n_batches, u32 tile) {
-    int lo = 0, hi = n_batches - 1;
-    while (lo < hi) {
-        const int mid = (lo + hi + 1) >> 1;
-        if (batches[mid].tile_base <= tile) lo = mid;
-        else hi = mid - 1;
-    }
-    return batches[lo];
-}
+// lists: the walks', or -- closed, and a window can reach over one of its introns (window_reach) -- the window check's; a closed
+// read that no window can reach is finished here.  One launch per chain, behind the chain's k1_emit launches.
 __global__ __launch_bounds__(K1E_T) void k1_generic(const DevBatch *batches, int n_batches, const u32 *spl_idx, const uint4 *spl_rec, Pairs P, EmitLists E, KeyFmt kf,
                                                     GroupTab G, int use_codes, int orientation, u64 *err, ContigStats *cs) {
     __shared__ EmitShared sh;
     __shared__ u32 s_ops[OPS_LDS][K1E_T];
     __shared__ u32 s_first[GEN_SHARDS + 1];
     __shared__ u32 s_wsum[4];
+    __shared__ BatchTab s_bt;
     if (cs->P == 0) return;
+    const u32 max_span = cs->max_span;
     const bool want_cand = E.cand != nullptr;
     EmitCtx ctx{sh, E, kf, cs, want_cand};
     ctx.init();
     static_assert(GEN_SHARDS == K1E_T, "a sub-list per thread");
     {
         const u32 c = E.gen_cnt[threadIdx.x * GEN_CNT_STRIDE + 4];
+        s_bt.fill(batches, n_batches);
         u32 total;
         const u32 ex = block_escan<K1E_T / 64>(c < E.gen_cap ? c : E.gen_cap, s_wsum, &total);
         s_first[threadIdx.x] = ex;
@@ -1964,7 +2024,8 @@ __global__ __launch_bounds__(K1E_T) void k1_generic(const DevBatch *batches, int
                 if (sub + step < GEN_SHARDS && s_first[sub + step] <= item) sub += step;
             const u64 e3 = E.gen_list[((size_t)2 * GEN_SHARDS + sub) * E.gen_cap + (item - s_first[sub])];
             const u32 slot = (u32)e3;
-            const DevBatch &b = find_batch_by_tile(batches, n_batches, slot / (u32)K1_TILE);
+            const int bi = s_bt.find(batches, n_batches, slot / (u32)K1_TILE);
+            const DevBatch &b = batches[bi];
             const u32 r = spl_idx[slot];
             const uint4 sr = spl_rec[slot];
             const int m = b.member;
@@ -1984,11 +2045,11 @@ __global__ __launch_bounds__(K1E_T) void k1_generic(const DevBatch *batches, int
             OpsViewT<K1E_T, OPS_LDS> cig;
             cig.g = b.cigar + sr.x;
             cig.lds = &s_ops[0][threadIdx.x];
+            {
+                u32 w[OPS_LDS];
+                fetch_ops8(as_global(b.cigar), sr.x, s_bt.cig_words(b, bi), w);
 #pragma unroll
-            for (int q = 0; q < OPS_LDS; q++) { // (unconditional loads, masked: see k1_count)
-                const bool has = (u32)q < R.n;
-                const u32 v = gload(has ? cig.g + q : b.cig_off);
-                s_ops[q][threadIdx.x] = has ? v : 0u;
+                for (int q = 0; q < OPS_LDS; q++) s_ops[q][threadIdx.x] = (u32)q < R.n ? w[q] : 0u;
             }
             // operations counted, and the shape [S] B (N B)+ [S] recognised, B = M = X I D operations that begin and end with bases on
             // both sides: state 0 at the first operation, 5 after a leading S, 1 after M = X, 6 after I or D, 2 after an N, 3 after the
@@ -1996,8 +2057,16 @@ __global__ __launch_bounds__(K1E_T) void k1_generic(const DevBatch *batches, int
             u32 nN = 0, shape = 0;
             int32_t aligned = 0;
             int64_t qsum = 0, bsum = 0; // query bases; positions the walks emit for the current block
+            u32 bref = 0, nl_prev = 0;  // reference positions of the current block; the N operation before it
+            bool reach = max_span == 0xffffffffu; // a window can reach over one of the read's introns from the next one (window_reach; no bound: every closed read)
             for (u32 q = 0; q < R.n; q++) {
                 const u32 o = cig[q], ty = o & 15u, ln = o >> 4;
+                if (ty == OP_N) {
+                    if (nN > 0) reach = reach || window_reach(bref, nl_prev, ln, max_span);
+                    nl_prev = ln;
+                    bref = 0;
+                } else if (op_consumes_ref(ty))
+                    bref = __builtin_elementwise_add_sat(bref, ln);
                 nN += (ty == OP_N);
                 if (op_consumes_ref(ty)) aligned += (int32_t)ln;
                 if (op_consumes_query(ty)) qsum += ln;
@@ -2017,14 +2086,14 @@ __global__ __launch_bounds__(K1E_T) void k1_generic(const DevBatch *batches, int
             const bool closed = gcodes != nullptr && (shape == 1 || shape == 3) && nN > 0 && R.seq_ok && R.lq > 1 && qsum == (int64_t)R.lq &&
                                 R.pos >= voff && R.aend < vlen;
             R.closed_seqw = closed ? reinterpret_cast<const u32 *>(b.seq4) + sr.z : nullptr;
-            R.q_limit = (int32_t)min(gload(b.seq_off + b.n) - 1u - sr.z, 0x7fffffffu);
+            R.q_limit = (int32_t)min(s_bt.seq_words(b, bi) - 1u - sr.z, 0x7fffffffu);
             R.gcodes = gcodes;
             R.glen = ref_len;
             R.voff = voff;
             emit_read_pairs(cig, R, P, kf, vlen, err, [&](u64 key, int32_t lstart, int32_t rend) { ctx.cand_insert(key, lstart, rend); });
             gen_pairs = nN;
-            gen_kind = closed ? 2u : 1u;
-            gen_entry = (u64)(closed && E.pack_nn ? R.g | ((nN < 15u ? nN : 15u) << 28) : R.g) | ((u64)R.off << 32);
+            gen_kind = !closed ? 1u : reach ? 2u : 0u; // (closed, no window can reach: its pairs are finished)
+            gen_entry = (u64)(closed && E.pack_nn ? slot | ((nN < 15u ? nN : 15u) << 28) : slot) | ((u64)R.off << 32);
         }
         // the read goes on k4b_generic's first list (the walks) or on its second (closed form done, window to be checked)
         const u32 shard = (item0 >> K1E_SHIFT) % GEN_SHARDS;
@@ -3020,27 +3089,21 @@ __device__ __forceinline__ u64 pair_stats_generic(const OpsView cig, u32 nc, int
     return pack_res(upM < downM ? upM : downM, tu < td ? tu : td, (u32)(L.mism + R.mism));
 }
 
-__device__ __forceinline__ const DevBatch &find_batch(const DevBatch *batches, int n_batches, u32 g) {
-    int lo = 0, hi = n_batches - 1;
-    while (lo < hi) {
-        const int mid = (lo + hi + 1) >> 1;
-        if (batches[mid].base <= g) lo = mid;
-        else hi = mid - 1;
-    }
-    return batches[lo];
-}
-
 // K4b: every pair that is not of the simple shape (multi-junction reads, indels, = X P H ops, exotic contigs, SEQ '*'), one
-// thread per READ of the list k1_emit compacted, in BAM order: the read's operations are fetched once (LDS column) and
+// thread per READ of the lists k1_emit and k1_generic compacted -- the second list holds only the closed reads whose window check
+// the chain's bound B could not rule out (ContigStats::max_span) --: the read's fields come from the record k1_count kept of it
+// (spl_rec), its batch from the block's table, its operations are fetched once (two 16-byte loads into an LDS column) and
 // walked once; at every N operation the pair's junction-level anchors (kd_assign) are looked up and the two lock-step
 // walks start right there (op index and query offset are at hand: no hint has to travel with the pair).  The result
 // goes into the pair's record.  Runs on the side stream, beside the sort.
 __global__ __launch_bounds__(256) void k4b_generic(const u64 *list, const u32 *gen_cnt, u32 cap, const u64 *key, PairRec *rec, const u32 *jid_bam,
                                                     KeyFmt kf, const DevBatch *batches, int n_batches, const int32_t *anc_l, const int32_t *anc_r,
-                                                    GroupTab G, int genome_has_x, int use_codes, u64 *err, const ContigStats *cs, u32 pack_nn) {
+                                                    GroupTab G, int genome_has_x, int use_codes, u64 *err, const ContigStats *cs, u32 pack_nn,
+                                                    const u32 *spl_idx, const uint4 *spl_rec) {
     __shared__ u32 s_ops[OPS_LDS][256];
     __shared__ u32 s_first[2 * GEN_SHARDS + 1]; // item index of every sub-list's first entry (both lists, one index space)
     __shared__ u32 s_wsum[4];
+    __shared__ BatchTab s_bt;
     if (cs->P == 0) return; // (a limit was exceeded while the junction ids were built: there are no ids, the chain is repeated)
     // The sub-lists are filled to different heights (sub-list `shard` of list `l` occupies [(l GEN_SHARDS + shard) cap, ... + its
     // count)): every block numbers their entries -- an exclusive scan over the 512 counts -- and the grid strides over the items.
@@ -3049,6 +3112,7 @@ __global__ __launch_bounds__(256) void k4b_generic(const u64 *list, const u32 *g
         const u32 c0 = gen_cnt[(i0 % GEN_SHARDS) * GEN_CNT_STRIDE + (i0 / GEN_SHARDS) * 2];
         const u32 c1 = gen_cnt[((i0 + 1) % GEN_SHARDS) * GEN_CNT_STRIDE + ((i0 + 1) / GEN_SHARDS) * 2];
         const u32 n0 = c0 < cap ? c0 : cap, n1 = c1 < cap ? c1 : cap;
+        s_bt.fill(batches, n_batches);
         u32 total;
         const u32 ex = block_escan<4>(n0 + n1, s_wsum, &total);
         s_first[i0] = ex;
@@ -3068,7 +3132,7 @@ __global__ __launch_bounds__(256) void k4b_generic(const u64 *list, const u32 *g
     const bool check_only = sub >= GEN_SHARDS;
     const u64 entry = list[(size_t)sub * cap + (item - s_first[sub])];
     const u32 p0 = (u32)(entry >> 32);
-    const u32 g = check_only && pack_nn ? (u32)entry & 0x0fffffffu : (u32)entry;
+    const u32 slot = check_only && pack_nn ? (u32)entry & 0x0fffffffu : (u32)entry; // the read's place in the tiles' spliced lists
     if (check_only) {
         // A read [S] M (N M)+ [S] whose pairs k1_emit finished with the M blocks as anchors.  That is what the walks produce
         // unless the junction's window reaches over a neighbouring intron of the read: on the left the walk starts at the
@@ -3092,32 +3156,38 @@ __global__ __launch_bounds__(256) void k4b_generic(const u64 *list, const u32 *g
         }
         if (ok) continue;
     }
-    const DevBatch &b = find_batch(batches, n_batches, g);
-    const u32 r = g - b.base;
-    const u32 *cig_off = b.cig_off;
-    const u32 c0 = gload(cig_off + r), c1 = gload(cig_off + r + 1);
-    const u32 nc = c1 - c0;
+    // what k1_count kept of the read (spl_rec: first operation, position, first word of the bases, operations | bases present | l_qseq --
+    // no gathers of cig_off, l_qseq, seq_off) and its batch, from the slot's tile
+    const int bi = s_bt.find(batches, n_batches, slot / (u32)K1_TILE);
+    const DevBatch &b = batches[bi];
+    const u32 r = spl_idx[slot];
+    const uint4 sr = spl_rec[slot];
+    const u32 g = gload(&b.base) + r;
+    const u32 c0 = sr.x;
+    u32 nc = sr.w & 0x7fffu;
+    if (nc == 0x7fffu) nc = gload(b.cig_off + r + 1) - c0; // (a count that did not fit the record)
     OpsView cig;
     cig.g = b.cigar + c0;
     cig.lds = &s_ops[0][threadIdx.x];
+    {
+        u32 w[OPS_LDS];
+        fetch_ops8(as_global(b.cigar), c0, s_bt.cig_words(b, bi), w);
 #pragma unroll
-    for (int k = 0; k < OPS_LDS; k++) { // (unconditional loads, masked: see k1_count)
-        const bool has = (u32)k < nc;
-        const u32 v = gload(has ? cig.g + k : cig_off);
-        s_ops[k][threadIdx.x] = has ? v : 0u;
+        for (int k = 0; k < OPS_LDS; k++) s_ops[k][threadIdx.x] = (u32)k < nc ? w[k] : 0u;
     }
     const uint4 rb = reinterpret_cast<const uint4 *>(rec + p0)[1]; // pos | aend | meta | updown of the read's first pair
     const int32_t vpos = (int32_t)rb.x, aend = (int32_t)rb.y;
     const Member M = member_of(G, vpos); // the read's target: everything below is in the target's own coordinates
     const int32_t pos = vpos - M.voff;
-    const int32_t lq = gload(b.l_qseq + r);
-    const u32 so0 = gload(b.seq_off + r), words = gload(b.seq_off + r + 1) - so0;
-    if (lq > 1 && (u64)words * 8ull < (u64)lq) {
+    int32_t lq = (int32_t)(sr.w >> 16);
+    if (lq == 0xffff) lq = gload(b.l_qseq + r);
+    const u32 so0 = sr.z;
+    if (lq > 1 && !(sr.w & 0x8000u)) { // (the record carries fewer than lq bases)
         set_error(err, g, PJB_ERR_NO_SEQ);
         continue; // (the records keep aux = 0)
     }
     const uint8_t *seq = b.seq4 + (size_t)so0 * 4;
-    const int32_t q_limit = (int32_t)min(gload(b.seq_off + b.n) - 1u - so0, 0x7fffffffu); // (to the end of the batch's bases: chunk_load)
+    const int32_t q_limit = (int32_t)min(s_bt.seq_words(b, bi) - 1u - so0, 0x7fffffffu); // (to the end of the batch's bases: chunk_load)
     u32 k = 0;
     int32_t qsum = 0; // query bases before the operation, soft clips not counted (anchor_side's qPos)
     for (u32 i = 0; i < nc; i++) {
