@@ -465,6 +465,54 @@ int pjb_bam_end(pjb_ctx* ctx, int32_t tid, int32_t first_uoffset, int64_t* n_rec
  * takes ~50 ms whatever its size, and most targets do not fill the chip). */
 int pjb_bam_inflate_done(pjb_ctx *ctx, int32_t tid);
 
+/* ---- the BAM index of a coordinate-sorted file (`portcullis_amd prep`) -------------------------------------------
+ * What `samtools index` does for the reference's prep (src/prepare.cc:290-332: Prepare::bamIndex shells out to it), on the
+ * device: BGZF inflate, the record walk of pjb_submit_bam over every target, and the BAI arithmetic of SAM spec 5.2 / 5.3 as
+ * BamWriter::indexRecord does it -- per record beg = pos, end = pos + max(1, reference span of the CIGAR) (clipped to the
+ * target's end), bin = reg2bin(beg, end); chunks per (target, bin), a record joining the bin's last chunk when that chunk
+ * ends where the record starts; per 16 kb window the virtual offset of the first record that overlaps it.  No metadata
+ * pseudo-bin, no count of unplaced records.  Records with refID < 0 add nothing.  The targets are those of pjb_set_refs.
+ *   pjb_index_begin  starts an index (drops one that was being built, and the last result);
+ *   pjb_index_piece  a run of whole BGZF blocks, in file order (host memory; page-locked memory is DMA'd directly, anything
+ *                    else goes through the context's staging buffers):
+ *                      file_offset   : offset of the piece's first block in the file;
+ *                      first_uoffset : where the first record not yet indexed starts in the piece's inflated bytes (the
+ *                                      low 16 bits of the last call's *next_voffset; behind the BAM header for the first
+ *                                      piece -- it may lie beyond the first block, a long header);
+ *                      last          : non-zero for the piece that ends the file.
+ *                    Every record that lies COMPLETELY inside the piece is indexed; *next_voffset receives the virtual
+ *                    offset of the first record that was not -- one that begins in this piece and ends beyond it, or the end
+ *                    of the data (then the start of the block behind the last data: the EOF block).  The next piece starts
+ *                    with the block it names (next_voffset >> 16): a straddling record's block is handed over twice, no
+ *                    bytes are carried.  The result does not depend on where the file was cut.
+ *   pjb_index_end    closes the last chunk, orders the chunks by (target, bin, file order) and hands the result over: host
+ *                    memory owned by the context until the next pjb_index_begin / pjb_destroy.
+ * Errors: PJB_ERR_UNSORTED a record lies before its predecessor in (refID as unsigned, pos) -- the message names its ordinal
+ * (0-based, over all alignment records); PJB_ERR_BGZF corrupt BGZF / DEFLATE / record data, a refID beyond the targets or a
+ * position outside its target, data that ends inside a record when last != 0; PJB_ERR_ARG "BAI cannot index this target": a
+ * record on a target of 2^29 bases or more; PJB_ERR_STATE calls out of order.  A failing piece call drops the index: begin
+ * again.  The one exception: a piece whose first record is longer than the piece fails with PJB_ERR_ARG and a message that
+ * says so, sets *next_voffset to that record and leaves the index as it was -- the same blocks may be handed over again with
+ * more blocks behind them.
+ * Threads: like pjb_bam_end, these calls belong to the thread that makes the context's other calls. */
+typedef struct pjb_index_chunk {
+    uint64_t vbeg, vend; /* virtual offsets: (offset of the BGZF block in the file) << 16 | offset in its inflated bytes */
+    int32_t tid;
+    uint32_t bin;
+} pjb_index_chunk;
+typedef struct pjb_index_result {
+    int64_t n_records;             /* all alignment records seen, unplaced ones included */
+    int64_t n_chunks;
+    const pjb_index_chunk *chunks; /* ordered by (tid, bin, file order) */
+    const int64_t *lin_off;        /* n_refs + 1: target t's windows are lin[lin_off[t] .. lin_off[t + 1]) */
+    const uint64_t *lin;           /* per target its n_intv = (largest window touched) + 1 entries; untouched windows are 0 (a
+                                      writer repeats the entry before them) */
+} pjb_index_result;
+int pjb_index_begin(pjb_ctx *ctx);
+int pjb_index_piece(pjb_ctx *ctx, const uint8_t *comp, int64_t comp_bytes, int64_t file_offset, int32_t first_uoffset, int32_t last,
+                    uint64_t *next_voffset);
+int pjb_index_end(pjb_ctx *ctx, pjb_index_result *out);
+
 /* ---- `portcullis filt` feature rows -------------------------------------------------------
  * ModelFeatures::setRow (lib/src/model_features.cc:161-212) for a list of junctions: the columns of VAR_NAMES +
  * JAD_NAMES (lib/include/portcullis/ml/model_features.hpp:45-60), i.e. the row getters, calcIntronScore

@@ -310,6 +310,7 @@ struct pjb_ctx {
     Buf b_inf_comp, b_inf_out, b_inf_blocks, b_inf_status, b_inf_scratch, b_inf_bitmap; // device-side BGZF inflate
     Buf b_dfl_in, b_dfl_sym, b_dfl_slots, b_dfl_size, b_dfl_off, b_dfl_packed;           // device-side BGZF deflate
     Buf b_bam_seg, b_bam_rec, b_bam_ctl;                                  // device-side BAM record parse
+    struct IndexState *index = nullptr;                                   // pjb_index_begin / _piece / _end (pjb_ingest_api.hip)
     // --extra
     bool extra = false;
     std::vector<ExtraContig> xc;

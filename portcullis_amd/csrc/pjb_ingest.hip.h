@@ -904,8 +904,9 @@ struct BamWalkOut {
                        // walk did not land on the next start, [2] smallest segment with an invalid record (atomicMin)
 };
 
-template <bool FILL>
-__global__ __launch_bounds__(256) void bam_walk(BamRegion R, iu32 n_seg, const iu64 *seg_start, BamWalkOut O) {
+// (ALL: the indexer's walk, pjb_index.hip.h -- records of every target, unplaced ones included, to the end of the data)
+template <bool FILL, bool ALL>
+__device__ __forceinline__ void bam_walk_body(BamRegion R, iu32 n_seg, const iu64 *seg_start, BamWalkOut O) {
     const iu32 s = blockIdx.x * 256 + threadIdx.x;
     if (s >= n_seg) return;
     iu64 cur = seg_start[s];
@@ -937,7 +938,7 @@ __global__ __launch_bounds__(256) void bam_walk(BamRegion R, iu32 n_seg, const i
             break;
         }
         const int32_t rt = (int32_t)ld32u(r), rp = (int32_t)ld32u(r + 4);
-        if (rt != R.tid || rp >= R.ref_len) { // first record that is not the target's: the region ends here
+        if (!ALL && (rt != R.tid || rp >= R.ref_len)) { // first record that is not the target's: the region ends here
             ended = true;
             break;
         }
@@ -962,6 +963,10 @@ __global__ __launch_bounds__(256) void bam_walk(BamRegion R, iu32 n_seg, const i
         else if (!partial && cur != limit) atomicMin(&O.ctl[1], s); // overshot the next start: that start was not a record
         if (partial && !ended) atomicMin(&O.ctl[6], s);             // the data ends inside one of the target's records
     }
+}
+template <bool FILL>
+__global__ __launch_bounds__(256) void bam_walk(BamRegion R, iu32 n_seg, const iu64 *seg_start, BamWalkOut O) {
+    bam_walk_body<FILL, false>(R, n_seg, seg_start, O);
 }
 
 // The walk of segment s (whose own start is verified: every earlier walk landed) ran past the start guessed for a later

@@ -1,8 +1,9 @@
 // pjb_ingest_api.hip -- the part of the C ABI that takes file bytes: BGZF inflate / deflate on the device, BAM record boundaries and transcoding
-// (pjb_inflate_bgzf, pjb_deflate_bgzf, pjb_submit_bam, pjb_bam_*); kernels in pjb_ingest.hip.h and pjb_deflate.hip.h.
+// (pjb_inflate_bgzf, pjb_deflate_bgzf, pjb_submit_bam, pjb_bam_*, pjb_index_*); kernels in pjb_ingest.hip.h, pjb_deflate.hip.h and pjb_index.hip.h.
 #include "pjb_host.hip.h"
 #include "pjb_deflate.hip.h"
 #include "pjb_ingest.hip.h"
+#include "pjb_index.hip.h"
 
 void ingest_kernel_attributes() { (void)hipFuncSetAttribute((const void *)bgzf_decode, hipFuncAttributeMaxDynamicSharedMemorySize, I3_LDS_BYTES); }
 int ingest_lds_bytes() { return I3_LDS_BYTES; }
@@ -575,7 +576,9 @@ static int stage_scan(pjb_ctx *c, BamStage &st, const uint8_t *p, int64_t p_at, 
     return PJB_OK;
 }
 
+static void index_clear(pjb_ctx *c);
 void bam_stage_clear(pjb_ctx *c) {
+    index_clear(c);
     for (auto &is : c->inf_streams)
         if (is) (void)hipStreamSynchronize(is);
     for (auto &kv : c->bam_stage) {
@@ -758,3 +761,340 @@ extern "C" int pjb_bam_end(pjb_ctx *c, int32_t tid, int32_t first_uoffset, int64
     return ingest_staged(c, tid, oc, (const uint8_t *)st->dev.p, st->blocks, st->total, st->total_out, first_uoffset, n_records, st->t_scan, st->t_up);
 }
 
+
+// ---- the BAM index of a sorted file, piece by piece (pjb_index_begin / _piece / _end, see the header; kernels in pjb_index.hip.h) ---------
+struct IndexState {
+    bool active = false, saw_last = false;
+    bool keep_on_error = false;   // the failing piece call left the index as it was
+    int64_t n_records = 0;
+    iu64 prev_sort = 0;           // (refID unsigned) << 32 | pos of the last record seen
+    iu64 open_key = BAI_NOKEY;    // (target, bin) of the run the last record belongs to: its chunk is the list's last, its end open
+    iu64 win_carry = 0;           // running window maximum
+    iu64 end_voffset = 0;         // where the data ended (the last piece)
+    size_t n_chunks = 0;
+    Buf chunks;                   // BaiChunk[n_chunks], file order
+    Buf lin, ref_len, lin_off;    // u64 per window of every target (0: untouched) | i32[n_ref] | u64[n_ref + 1]
+    size_t lin_total = 0;
+    std::vector<iu64> h_lin_cap;  // lin_off on the host
+    Buf key, vs, win, w0, heads, tab, ctl, tile_max; // a piece's scratch
+    Buf q[3], tid_start, sorted;  // pjb_index_end
+    // the result
+    std::vector<pjb_index_chunk> r_chunks;
+    std::vector<int64_t> r_lin_off;
+    std::vector<uint64_t> r_lin;
+};
+static_assert(sizeof(BaiChunk) == sizeof(pjb_index_chunk) && sizeof(pjb_index_chunk) == 24, "chunk layout");
+
+static void index_clear(pjb_ctx *c) {
+    IndexState *x = c->index;
+    if (!x) return;
+    for (Buf *b : {&x->chunks, &x->lin, &x->ref_len, &x->lin_off, &x->key, &x->vs, &x->win, &x->w0, &x->heads, &x->tab, &x->ctl, &x->tile_max, &x->q[0], &x->q[1],
+                   &x->q[2], &x->tid_start, &x->sorted})
+        release(*b);
+    delete x;
+    c->index = nullptr;
+}
+
+extern "C" int pjb_index_begin(pjb_ctx *c) {
+    if (!c) return PJB_ERR_ARG;
+    HIP_TRY(c, hipSetDevice(c->cfg.device));
+    if (!c->index) c->index = new (std::nothrow) IndexState();
+    IndexState *x = c->index;
+    if (!x) return fail(c, PJB_ERR_NOMEM, "index_begin: out of host memory");
+    x->active = false;
+    x->saw_last = false;
+    x->n_records = 0;
+    x->prev_sort = 0;
+    x->open_key = BAI_NOKEY;
+    x->win_carry = 0;
+    x->end_voffset = 0;
+    x->n_chunks = 0;
+    x->r_chunks.clear();
+    x->r_lin_off.clear();
+    x->r_lin.clear();
+    // a window of 16 kb per 2^14 bases of every target reg2bin covers (a record on a longer one is refused when it is met)
+    const size_t n_ref = c->ref_len.size();
+    x->h_lin_cap.assign(n_ref + 1, 0);
+    for (size_t t = 0; t < n_ref; t++) {
+        const int32_t len = c->ref_len[t];
+        x->h_lin_cap[t + 1] = x->h_lin_cap[t] + (len > 0 && len < BAI_MAX_LEN ? ((iu64)len + 16383) >> 14 : 0);
+    }
+    x->lin_total = (size_t)x->h_lin_cap[n_ref];
+    int rc;
+    if ((rc = ensure(c, x->lin, x->lin_total * 8 + 8)) || (rc = ensure(c, x->ref_len, n_ref * 4 + 4)) || (rc = ensure(c, x->lin_off, (n_ref + 1) * 8)) ||
+        (rc = ensure(c, x->ctl, BAI_CTL_WORDS * 8)))
+        return rc;
+    hipStream_t st = c->stream;
+    HIP_TRY(c, hipMemsetAsync(x->lin.p, 0, x->lin_total * 8 + 8, st));
+    if (n_ref) HIP_TRY(c, hipMemcpyAsync(x->ref_len.p, c->ref_len.data(), n_ref * 4, hipMemcpyHostToDevice, st));
+    HIP_TRY(c, hipMemcpyAsync(x->lin_off.p, x->h_lin_cap.data(), (n_ref + 1) * 8, hipMemcpyHostToDevice, st));
+    HIP_TRY(c, hipStreamSynchronize(st));
+    x->active = true;
+    return PJB_OK;
+}
+
+// the record boundaries of every record that lies completely in the inflated bytes: rec_off in b_bam_rec, their number in n, the
+// offset of the first byte that belongs to none of them in next_u (== total: the data ends on a record's end)
+static int index_walk(pjb_ctx *c, const uint8_t *d_out, int64_t total, int32_t first_uoffset, size_t &n, iu64 &next_u) {
+    hipStream_t st = c->stream;
+    int rc;
+    BamRegion R;
+    R.U = d_out;
+    R.total = (iu64)total;
+    R.first = (iu64)first_uoffset;
+    R.tid = -1;
+    R.ref_len = 0;
+    R.n_ref = (int32_t)c->ref_len.size();
+    const uint32_t n_seg = (uint32_t)(((iu64)total + BAM_SEG - 1) / BAM_SEG);
+    if ((rc = ensure(c, c->b_bam_seg, (size_t)n_seg * 28 + 64))) return rc;
+    if ((rc = ensure(c, c->b_bam_ctl, 64))) return rc;
+    iu64 *seg_start = (iu64 *)c->b_bam_seg.p;
+    iu64 *seg_base = seg_start + n_seg;
+    iu64 *land = seg_base + n_seg;
+    iu32 *seg_n = (iu32 *)(land + n_seg);
+    iu32 *ctl = (iu32 *)c->b_bam_ctl.p; // as ingest_parse: [1] mismatch, [2] bad segment, [3] repair failed, [4..5] scan total, [6] data ends in a record
+    iu64 *d_total = (iu64 *)(ctl + 4);
+    BamWalkOut O;
+    O.seg_n = seg_n;
+    O.land = land;
+    O.rec_off = nullptr;
+    O.seg_base = seg_base;
+    O.ctl = ctl;
+    LAUNCH(c, "bam_find_starts", bam_find_starts, dim3(n_seg), dim3(64), R, n_seg, seg_start);
+    uint32_t h_ctl[8];
+    uint32_t cut_seg = 0xffffffffu; // the segment whose walk met the record the data ends in
+    for (int attempt = 0;; attempt++) {
+        HIP_TRY(c, hipMemsetAsync(ctl, 0xff, 32, st));
+        LAUNCH(c, "bam_walk_all_count", bam_walk_all<false>, dim3((n_seg + 255) / 256), dim3(256), R, n_seg, (const iu64 *)seg_start, O);
+        HIP_TRY(c, hipMemcpyAsync(h_ctl, ctl, 32, hipMemcpyDeviceToHost, st));
+        HIP_TRY(c, hipStreamSynchronize(st));
+        cut_seg = h_ctl[6];
+        if (h_ctl[2] != 0xffffffffu && h_ctl[2] <= cut_seg && (h_ctl[1] == 0xffffffffu || h_ctl[2] <= h_ctl[1]))
+            return fail(c, PJB_ERR_BGZF, "Invalid BAM record layout (inflated offset %llu.. of the piece)", (unsigned long long)h_ctl[2] * BAM_SEG);
+        if (h_ctl[1] == 0xffffffffu || h_ctl[1] > cut_seg) break; // every walk up to the cut landed on the next start
+        if (attempt >= 16)
+            return fail(c, PJB_ERR_BGZF, "BAM record chain is inconsistent near inflated offset %llu of the piece", (unsigned long long)h_ctl[1] * BAM_SEG);
+        LAUNCH(c, "bam_repair_start", bam_repair_start, dim3(1), dim3(1), seg_start, n_seg, h_ctl[1], (const iu64 *)land, (iu64)total, ctl);
+        HIP_TRY(c, hipMemcpyAsync(h_ctl, ctl, 16, hipMemcpyDeviceToHost, st));
+        HIP_TRY(c, hipStreamSynchronize(st));
+        if (h_ctl[3] != 0xffffffffu)
+            return fail(c, PJB_ERR_BGZF, "Invalid BAM record (inflated offset %llu.. of the piece)", (unsigned long long)h_ctl[3] * BAM_SEG);
+    }
+    next_u = (iu64)total;
+    if (cut_seg != 0xffffffffu) {
+        // what the segments behind the cut found lies inside the cut record: not records
+        HIP_TRY(c, hipMemcpyAsync(ctl, &cut_seg, 4, hipMemcpyHostToDevice, st));
+        LAUNCH(c, "bam_trim_segments", bam_trim_segments, dim3((n_seg + 255) / 256), dim3(256), seg_n, n_seg, (const iu32 *)ctl);
+        HIP_TRY(c, hipMemcpyAsync(&next_u, land + cut_seg, 8, hipMemcpyDeviceToHost, st));
+    }
+    if ((rc = run_scan(c, "bam_seg", SegCountFn{seg_n}, SegBaseSink{seg_base}, n_seg, d_total))) return rc;
+    iu64 n64 = 0;
+    HIP_TRY(c, hipMemcpyAsync(&n64, d_total, 8, hipMemcpyDeviceToHost, st));
+    HIP_TRY(c, hipStreamSynchronize(st));
+    n = 0;
+    if (n64 == 0) return PJB_OK;
+    if (n64 >= 0xffffff00ull) return fail(c, PJB_ERR_ARG, "index_piece: more than 2^32 alignments in one piece are not supported");
+    n = (size_t)n64;
+    if ((rc = ensure(c, c->b_bam_rec, n * 8))) return rc;
+    O.rec_off = (iu64 *)c->b_bam_rec.p;
+    LAUNCH(c, "bam_walk_all_fill", bam_walk_all<true>, dim3((n_seg + 255) / 256), dim3(256), R, n_seg, (const iu64 *)seg_start, O);
+    return PJB_OK;
+}
+
+// a chunk list that must hold `need` chunks: a larger buffer takes over what the list holds
+static int index_grow_chunks(pjb_ctx *c, IndexState *x, size_t need) {
+    if (need * sizeof(BaiChunk) <= x->chunks.cap && x->chunks.p) return PJB_OK;
+    Buf nb;
+    int rc = ensure(c, nb, std::max<size_t>(need * 2, 4096) * sizeof(BaiChunk));
+    if (rc) return rc;
+    if (x->n_chunks) HIP_TRY(c, hipMemcpyAsync(nb.p, x->chunks.p, x->n_chunks * sizeof(BaiChunk), hipMemcpyDeviceToDevice, c->stream));
+    if (x->chunks.p) bury(c, x->chunks.p); // (the copy is on the stream: freed where a wait costs nothing)
+    x->chunks = nb;
+    return PJB_OK;
+}
+
+static int index_piece_body(pjb_ctx *c, IndexState *x, const uint8_t *comp, int64_t comp_bytes, int64_t file_offset, int32_t first_uoffset, int32_t last,
+                            uint64_t *next_voffset) {
+    std::vector<InfBlock> blocks;
+    int64_t total = 0;
+    int rc = scan_bgzf(c, comp, comp_bytes, blocks, total);
+    if (rc) return rc;
+    if ((int64_t)first_uoffset > total) return fail(c, PJB_ERR_ARG, "index_piece: first_uoffset %d lies behind the piece's %lld inflated bytes", first_uoffset, (long long)total);
+    // block starts: inflated offset | file offset, + the sentinel "end of the data, the file's next block"
+    const size_t nb = blocks.size();
+    std::vector<iu64> tab(2 * (nb + 1));
+    {
+        int64_t off = 0;
+        for (size_t b = 0; b < nb; b++) {
+            tab[b] = blocks[b].out_off;
+            tab[nb + 1 + b] = (iu64)(file_offset + off);
+            off = (int64_t)blocks[b].in_off + blocks[b].in_len + 8; // (the payload, CRC32 and ISIZE: the next block's first byte)
+        }
+        tab[nb] = (iu64)total;
+        tab[2 * nb + 1] = (iu64)(file_offset + comp_bytes);
+    }
+    auto voffset_of = [&](iu64 u) -> uint64_t { // bai_block_of on the host
+        size_t lo = 0, hi = nb + 1;
+        while (lo < hi) {
+            const size_t mid = lo + (hi - lo) / 2;
+            if (tab[mid] < u) lo = mid + 1;
+            else hi = mid;
+        }
+        if ((lo == nb + 1 || tab[lo] > u) && lo > 0) lo--;
+        return tab[nb + 1 + lo] << 16 | (u - tab[lo]);
+    };
+    size_t n = 0;
+    iu64 next_u = (iu64)first_uoffset;
+    hipStream_t st = c->stream;
+    if ((int64_t)first_uoffset < total) {
+        if ((rc = ensure(c, c->b_inf_comp, (size_t)comp_bytes + INF_PAD))) return rc;
+        hipPointerAttribute_t at; // page-locked input: one DMA, no staging copy (as pjb_submit_bam)
+        const bool pinned = hipPointerGetAttributes(&at, comp) == hipSuccess && at.type == hipMemoryTypeHost;
+        if (!pinned) (void)hipGetLastError();
+        if (pinned) HIP_TRY(c, hipMemcpyAsync(c->b_inf_comp.p, comp, (size_t)comp_bytes, hipMemcpyHostToDevice, st));
+        else if ((rc = upload_staged(c, c->b_inf_comp.p, comp, (size_t)comp_bytes))) return rc;
+        HIP_TRY(c, hipMemsetAsync((uint8_t *)c->b_inf_comp.p + comp_bytes, 0, INF_PAD, st));
+        if ((rc = ensure(c, c->b_inf_out, (size_t)total + 64))) return rc;
+        HIP_TRY(c, hipMemsetAsync((uint8_t *)c->b_inf_out.p + total, 0, 64, st));
+        if ((rc = inflate_on_device(c, (const uint8_t *)c->b_inf_comp.p, blocks, (uint8_t *)c->b_inf_out.p))) return rc;
+        if ((rc = index_walk(c, (const uint8_t *)c->b_inf_out.p, total, first_uoffset, n, next_u))) return rc;
+    }
+    if (next_u < (iu64)total) { // the data ends inside a record
+        if (last) return fail(c, PJB_ERR_BGZF, "the data ends inside an alignment record (virtual offset 0x%llx): truncated file", (unsigned long long)voffset_of(next_u));
+        if (n == 0) { // nothing was indexed and nothing changed: the caller may hand the same blocks over again with more behind them
+            x->keep_on_error = true;
+            if (next_voffset) *next_voffset = voffset_of(next_u);
+            return fail(c, PJB_ERR_ARG, "index_piece: the alignment record at virtual offset 0x%llx is longer than the piece (%lld bytes): hand over more blocks at once",
+                        (unsigned long long)voffset_of(next_u), (long long)comp_bytes);
+        }
+    }
+    if (n > 0) {
+        if ((rc = ensure(c, x->key, n * 8)) || (rc = ensure(c, x->vs, n * 8)) || (rc = ensure(c, x->win, n * 8)) || (rc = ensure(c, x->w0, n * 4)) ||
+            (rc = ensure(c, x->heads, n * 4)) || (rc = ensure(c, x->tab, tab.size() * 8)))
+            return rc;
+        iu64 *ctl = (iu64 *)x->ctl.p;
+        HIP_TRY(c, hipMemsetAsync(ctl, 0xff, BAI_CTL_WORDS * 8, st));
+        HIP_TRY(c, hipMemcpyAsync(x->tab.p, tab.data(), tab.size() * 8, hipMemcpyHostToDevice, st));
+        BaiTable T;
+        T.out_off = (const iu64 *)x->tab.p;
+        T.cstart = T.out_off + nb + 1;
+        T.n = (iu32)(nb + 1);
+        BaiRecOut O;
+        O.key = (iu64 *)x->key.p;
+        O.vs = (iu64 *)x->vs.p;
+        O.win = (iu64 *)x->win.p;
+        O.w0 = (iu32 *)x->w0.p;
+        O.ctl = ctl;
+        const iu64 *rec_off = (const iu64 *)c->b_bam_rec.p;
+        const unsigned grid = (unsigned)((n + 255) / 256);
+        LAUNCH(c, "bai_records", bai_records, dim3(grid), dim3(256), (const uint8_t *)c->b_inf_out.p, rec_off, (iu64)n, T, (const int32_t *)x->ref_len.p,
+               (int32_t)c->ref_len.size(), x->prev_sort, O);
+        if ((rc = run_scan(c, "bai_head", BaiHeadFn{O.key, x->open_key}, ExclusiveU32Sink{(u32 *)x->heads.p}, n, (u64 *)(ctl + BAI_CTL_HEADS)))) return rc;
+        iu64 h[BAI_CTL_WORDS];
+        HIP_TRY(c, hipMemcpyAsync(h, ctl, sizeof h, hipMemcpyDeviceToHost, st));
+        HIP_TRY(c, hipStreamSynchronize(st));
+        // the first offender decides (a record that cannot be is usually out of order as well)
+        const iu64 first_err = std::min(h[BAI_CTL_UNSORTED], std::min(h[BAI_CTL_BAD], h[BAI_CTL_LONG]));
+        if (first_err != ~0ull) {
+            const long long ord = (long long)(x->n_records + (int64_t)first_err);
+            if (h[BAI_CTL_BAD] == first_err)
+                return fail(c, PJB_ERR_BGZF, "alignment record %lld names a target or a position the header does not have (refID beyond the %zu targets, or pos outside its target)",
+                            ord, c->ref_len.size());
+            if (h[BAI_CTL_LONG] == first_err)
+                return fail(c, PJB_ERR_ARG, "BAI cannot index this target: alignment record %lld lies on a target of 2^29 bases or more (a CSI index is needed)", ord);
+            return fail(c, PJB_ERR_UNSORTED, "%s (alignment record %lld lies before its predecessor)", err_text(PJB_ERR_UNSORTED), ord);
+        }
+        const size_t n_heads = (size_t)h[BAI_CTL_HEADS];
+        if (x->n_chunks + n_heads >= 0xffffff00ull) return fail(c, PJB_ERR_ARG, "index_piece: more than 2^32 chunks are not supported");
+        if ((rc = index_grow_chunks(c, x, x->n_chunks + n_heads))) return rc;
+        LAUNCH(c, "bai_chunks", bai_chunks, dim3(grid), dim3(256), (const iu64 *)O.key, (const iu64 *)O.vs, (const iu32 *)x->heads.p, (iu64)n, x->open_key,
+               (BaiChunk *)x->chunks.p, (iu64)x->n_chunks, (iu64)(x->n_chunks + n_heads));
+        const iu32 nt = (iu32)((n + SCAN_TILE - 1) / SCAN_TILE);
+        if ((rc = ensure(c, x->tile_max, (size_t)nt * 8))) return rc;
+        LAUNCH(c, "bai_win_reduce", bai_win_reduce, dim3(nt), dim3(256), (const iu64 *)O.win, (iu64)n, (iu64 *)x->tile_max.p);
+        LAUNCH(c, "bai_win_tiles", bai_win_tiles, dim3(1), dim3(1024), (iu64 *)x->tile_max.p, nt, x->win_carry, ctl + BAI_CTL_WINMAX);
+        LAUNCH(c, "bai_win_apply", bai_win_apply, dim3(nt), dim3(256), (const iu64 *)O.win, (const iu32 *)O.w0, (const iu64 *)O.vs, (iu64)n,
+               (const iu64 *)x->tile_max.p, (const iu64 *)x->lin_off.p, (iu64 *)x->lin.p, (iu64)x->lin_total);
+        iu64 win_max = 0;
+        HIP_TRY(c, hipMemcpyAsync(&win_max, ctl + BAI_CTL_WINMAX, 8, hipMemcpyDeviceToHost, st));
+        HIP_TRY(c, hipStreamSynchronize(st));
+        if (c->ktime) ev_collect(c, MISC_POOL);
+        x->n_chunks += n_heads;
+        x->n_records += (int64_t)n;
+        x->prev_sort = h[BAI_CTL_LASTSORT];
+        x->open_key = h[BAI_CTL_LASTKEY];
+        x->win_carry = win_max;
+    }
+    const uint64_t nv = voffset_of(next_u);
+    if (next_voffset) *next_voffset = nv;
+    if (last) {
+        x->saw_last = true;
+        x->end_voffset = nv;
+    }
+    return PJB_OK;
+}
+
+extern "C" int pjb_index_piece(pjb_ctx *c, const uint8_t *comp, int64_t comp_bytes, int64_t file_offset, int32_t first_uoffset, int32_t last,
+                               uint64_t *next_voffset) {
+    if (!c) return PJB_ERR_ARG;
+    IndexState *x = c->index;
+    if (!x || !x->active) return fail(c, PJB_ERR_STATE, "index_piece: no index is being built (pjb_index_begin)");
+    if (x->saw_last) return fail(c, PJB_ERR_STATE, "index_piece: the last piece has been handed over (pjb_index_end)");
+    if (comp_bytes < 0 || (comp_bytes && !comp) || file_offset < 0 || first_uoffset < 0) return fail(c, PJB_ERR_ARG, "index_piece: bad arguments");
+    HIP_TRY(c, hipSetDevice(c->cfg.device));
+    x->keep_on_error = false;
+    const int rc = index_piece_body(c, x, comp, comp_bytes, file_offset, first_uoffset, last, next_voffset);
+    if (rc && !x->keep_on_error) { // the index is dropped: begin again
+        (void)hipStreamSynchronize(c->stream);
+        x->active = false;
+    }
+    return rc;
+}
+
+extern "C" int pjb_index_end(pjb_ctx *c, pjb_index_result *out) {
+    if (!c || !out) return fail(c, PJB_ERR_ARG, "index_end: bad arguments");
+    IndexState *x = c->index;
+    if (!x || !x->active) return fail(c, PJB_ERR_STATE, "index_end: no index is being built (pjb_index_begin)");
+    if (!x->saw_last) return fail(c, PJB_ERR_STATE, "index_end: the last piece has not been handed over (pjb_index_piece with last != 0)");
+    HIP_TRY(c, hipSetDevice(c->cfg.device));
+    x->active = false;
+    hipStream_t st = c->stream;
+    const size_t n = x->n_chunks, n_ref = c->ref_len.size();
+    int rc;
+    x->r_chunks.assign(n, pjb_index_chunk());
+    if (n) {
+        BaiChunk *chunks = (BaiChunk *)x->chunks.p;
+        // the last run ends where the data ends
+        if (x->open_key != BAI_NOKEY) HIP_TRY(c, hipMemcpyAsync(&chunks[n - 1].vend, &x->end_voffset, 8, hipMemcpyHostToDevice, st));
+        for (int p = 0; p < 3; p++)
+            if ((rc = ensure(c, x->q[p], (n + 1) * 8))) return rc;
+        if ((rc = ensure(c, x->tid_start, (n_ref + 1) * 4)) || (rc = ensure(c, x->sorted, n * sizeof(BaiChunk)))) return rc;
+        iu64 *ctl = (iu64 *)x->ctl.p;
+        for (int p = 0; p < 3; p++)
+            if ((rc = run_scan(c, "bai_level", BaiLevelFn{chunks, (iu64)n, (iu32)p}, BaiLevelSink{(iu64 *)x->q[p].p}, n + 1, (u64 *)(ctl + BAI_CTL_HEADS)))) return rc;
+        LAUNCH(c, "bai_tid_starts", bai_tid_starts, dim3((unsigned)((n + 256) / 256)), dim3(256), (const BaiChunk *)chunks, (iu64)n, (int32_t)n_ref, (iu32 *)x->tid_start.p);
+        LAUNCH(c, "bai_partition", bai_partition, dim3((unsigned)((n + 255) / 256)), dim3(256), (const BaiChunk *)chunks, (iu64)n, (int32_t)n_ref,
+               (const iu32 *)x->tid_start.p, (const iu64 *)x->q[0].p, (const iu64 *)x->q[1].p, (const iu64 *)x->q[2].p, (BaiChunk *)x->sorted.p);
+        HIP_TRY(c, hipMemcpyAsync(x->r_chunks.data(), x->sorted.p, n * sizeof(BaiChunk), hipMemcpyDeviceToHost, st));
+    }
+    // the windows: per target up to the last one a record touched (every touched window holds a virtual offset, and none is 0)
+    std::vector<uint64_t> all(x->lin_total);
+    if (x->lin_total) HIP_TRY(c, hipMemcpyAsync(all.data(), x->lin.p, x->lin_total * 8, hipMemcpyDeviceToHost, st));
+    HIP_TRY(c, hipStreamSynchronize(st));
+    if (c->ktime) ev_collect(c, MISC_POOL);
+    x->r_lin_off.assign(n_ref + 1, 0);
+    x->r_lin.clear();
+    for (size_t t = 0; t < n_ref; t++) {
+        const size_t a = (size_t)x->h_lin_cap[t];
+        size_t k = (size_t)x->h_lin_cap[t + 1] - a;
+        while (k > 0 && all[a + k - 1] == 0) k--;
+        x->r_lin.insert(x->r_lin.end(), all.begin() + (long)a, all.begin() + (long)(a + k));
+        x->r_lin_off[t + 1] = (int64_t)x->r_lin.size();
+    }
+    out->n_records = x->n_records;
+    out->n_chunks = (int64_t)n;
+    out->chunks = x->r_chunks.data();
+    out->lin_off = x->r_lin_off.data();
+    out->lin = x->r_lin.data();
+    return PJB_OK;
+}

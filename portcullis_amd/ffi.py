@@ -26,6 +26,7 @@ EXPORTS = [
     "pjb_clear_rows", "pjb_get_timing", "pjb_device_count", "pjb_get_kernel_timing", "pjb_reset_kernel_timing",
     "pjb_select_timed_kernels", "pjb_host_alloc", "pjb_host_free", "pjb_host_register", "pjb_host_unregister", "pjb_inflate_bgzf", "pjb_deflate_bgzf", "pjb_submit_bam", "pjb_collect_device", "pjb_set_row_mirror",
     "pjb_extra_finish", "pjb_set_option", "pjb_merge_rows", "pjb_plan_groups", "pjb_bam_begin", "pjb_bam_piece", "pjb_bam_pieces_done", "pjb_bam_end", "pjb_bam_inflate_done", "pjb_filter_set_junctions", "pjb_filter_batch", "pjb_filt_features",
+    "pjb_index_begin", "pjb_index_piece", "pjb_index_end",
 ]
 N_FEATURES = 34
 KMER_TABLE = 3125 * 5
@@ -64,6 +65,10 @@ class PjbTiming(C.Structure):
                 ("generic_pairs", C.c_int64), ("generic_reads", C.c_int64), ("position_runs", C.c_int64), ("candidates", C.c_int64), ("checked_reads", C.c_int64), ("repeats", C.c_int64), ("repeat_reasons", C.c_int64)]
 
 
+class PjbIndexResult(C.Structure):
+    _fields_ = [("n_records", C.c_int64), ("n_chunks", C.c_int64), ("chunks", C.c_void_p), ("lin_off", C.c_void_p), ("lin", C.c_void_p)]
+
+
 class PjbKernelTime(C.Structure):
     _fields_ = [("name", C.c_char * 32), ("launches", C.c_int64), ("total_ms", C.c_double)]
 
@@ -83,6 +88,8 @@ ROW_DTYPE = np.dtype(
 assert ROW_DTYPE.itemsize == 200
 EXTRA_DTYPE = np.dtype([("mm_score", "<f8"), ("coverage", "<f8"), ("up_aln", "<u4"), ("down_aln", "<u4")])
 assert EXTRA_DTYPE.itemsize == 24
+CHUNK_DTYPE = np.dtype([("vbeg", "<u8"), ("vend", "<u8"), ("tid", "<i4"), ("bin", "<u4")])  # pjb_index_chunk
+assert CHUNK_DTYPE.itemsize == 24
 
 
 class PjbError(RuntimeError):
@@ -142,6 +149,9 @@ def load():
         L.pjb_filter_set_junctions.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_int64]
         L.pjb_filter_batch.argtypes = [C.c_void_p, C.c_int32, C.POINTER(PjbBatch), C.c_int32, C.c_void_p]
         L.pjb_filt_features.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_double, C.c_uint32, C.POINTER(PjbMarkovModels), C.c_void_p]
+        L.pjb_index_begin.argtypes = [C.c_void_p]
+        L.pjb_index_piece.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int32, C.c_int32, C.POINTER(C.c_uint64)]
+        L.pjb_index_end.argtypes = [C.c_void_p, C.POINTER(PjbIndexResult)]
         L.pjb_host_alloc.restype = C.c_void_p
         L.pjb_host_alloc.argtypes = [C.c_size_t]
         L.pjb_host_free.restype = None
@@ -179,6 +189,57 @@ def merge_rows(gathered, n_ranks, slot_stride_bytes):
     return out[: n.value].copy(), {k: getattr(tot, k) for k, _ in PjbRegionResult._fields_}
 
 
+def bgzf_block_starts(data):
+    """File offsets of the BGZF blocks of `data` (BSIZE of the BC field), plus the end of the data."""
+    starts, o = [], 0
+    while o < len(data):
+        starts.append(o)
+        xlen = int.from_bytes(data[o + 10:o + 12], "little")
+        x, bsize = o + 12, None
+        while x + 4 <= o + 12 + xlen:
+            slen = int.from_bytes(data[x + 2:x + 4], "little")
+            if data[x:x + 2] == b"BC" and slen == 2:
+                bsize = int.from_bytes(data[x + 4:x + 6], "little") + 1
+            x += 4 + slen
+        if bsize is None:
+            raise ValueError(f"BGZF block at byte {o} has no BC field")
+        o += bsize
+    return starts + [o]
+
+
+def bam_header(data, starts=None):
+    """(target lengths, bytes of the BAM header in the inflated stream) of a BAM file's bytes."""
+    import struct
+    import zlib
+
+    starts = bgzf_block_starts(data) if starts is None else starts
+    head, k = b"", 0
+
+    def need(n):
+        nonlocal head, k
+        while len(head) < n:
+            if k + 1 >= len(starts):
+                raise ValueError("the BAM header is truncated")
+            head += zlib.decompress(data[starts[k]:starts[k + 1]], 31)
+            k += 1
+
+    need(12)
+    if head[:4] != b"BAM\x01":
+        raise ValueError("not a BAM file")
+    p = 8 + struct.unpack_from("<i", head, 4)[0]
+    need(p + 4)
+    (n_ref,) = struct.unpack_from("<i", head, p)
+    p += 4
+    lens = []
+    for _ in range(n_ref):
+        need(p + 4)
+        p += 4 + struct.unpack_from("<i", head, p)[0]
+        need(p + 4)
+        lens.append(struct.unpack_from("<i", head, p)[0])
+        p += 4
+    return lens, p
+
+
 _FIELDS = [("pos", np.int32), ("flag", np.uint16), ("mapq", np.uint8), ("xs", np.uint8), ("l_qseq", np.int32),
            ("mtid", np.int32), ("mpos", np.int32), ("cig_off", np.uint32), ("cigar", np.uint32),
            ("seq_off", np.uint32), ("seq4", np.uint8)]
@@ -197,6 +258,7 @@ class Context:
         rc = self._L.pjb_create(C.byref(self._h), C.byref(cfg))
         if rc:
             raise PjbError(rc, self._L.pjb_last_error(None).decode())
+        self._n_refs = 0
         self._keep = []
         self._keep_batch = {}  # tid -> device tensors lent to the context until the contig is collected
 
@@ -223,6 +285,7 @@ class Context:
 
     def set_refs(self, ref_lens):
         a = np.ascontiguousarray(ref_lens, dtype=np.int32)
+        self._n_refs = len(a)
         self._check(self._L.pjb_set_refs(self._h, len(a), a.ctypes.data))
 
     def upload_contig(self, tid, bases):
@@ -454,6 +517,52 @@ class Context:
         n = C.c_int64()
         self._check(self._L.pjb_submit_bam(self._h, tid, comp.ctypes.data_as(C.c_void_p), len(comp), first_uoffset, C.byref(n)))
         return n.value
+
+    def index_begin(self):
+        self._check(self._L.pjb_index_begin(self._h))
+
+    def index_piece(self, comp, file_offset, first_uoffset, last):
+        """One run of whole BGZF blocks (pjb_index_piece); returns next_voffset."""
+        comp = np.frombuffer(bytes(comp), dtype=np.uint8) if not isinstance(comp, np.ndarray) else comp
+        nv = C.c_uint64()
+        self._check(self._L.pjb_index_piece(self._h, comp.ctypes.data_as(C.c_void_p), len(comp), file_offset, first_uoffset, int(bool(last)), C.byref(nv)))
+        return nv.value
+
+    def index_end(self):
+        """-> dict(n_records, chunks [CHUNK_DTYPE, ordered by (tid, bin, file order)], lin_off [n_refs + 1], lin): views of the
+        context's memory, valid until the next index_begin / close."""
+        r = PjbIndexResult()
+        self._check(self._L.pjb_index_end(self._h, C.byref(r)))
+
+        def view(p, count, dt):
+            if count == 0:
+                return np.zeros(0, dtype=dt)
+            return np.frombuffer((C.c_char * (count * np.dtype(dt).itemsize)).from_address(p), dtype=dt, count=count)
+
+        lin_off = view(r.lin_off, self._n_refs + 1, np.int64)
+        return dict(n_records=r.n_records, chunks=view(r.chunks, r.n_chunks, CHUNK_DTYPE), lin_off=lin_off, lin=view(r.lin, int(lin_off[-1]), np.uint64))
+
+    def index_bam(self, path_or_bytes, piece_blocks=None):
+        """The BAI of a coordinate-sorted BAM (pjb_index_begin / _piece / _end), the file handed over in pieces of `piece_blocks`
+        BGZF blocks (None: one piece).  The targets come from the file's header (set_refs).  Returns index_end()'s dict plus
+        `next_voffsets`, what each piece call returned."""
+        data = path_or_bytes if isinstance(path_or_bytes, (bytes, bytearray)) else open(path_or_bytes, "rb").read()
+        starts = bgzf_block_starts(data)
+        ref_lens, header_bytes = bam_header(data, starts)
+        self.set_refs(ref_lens)
+        self.index_begin()
+        at = {o: k for k, o in enumerate(starts)}  # block start -> its number
+        k, uoff, nvs = 0, header_bytes, []
+        while True:
+            k1 = len(starts) - 1 if piece_blocks is None else min(k + int(piece_blocks), len(starts) - 1)
+            nv = self.index_piece(data[starts[k]:starts[k1]], starts[k], uoff, k1 == len(starts) - 1)
+            nvs.append(nv)
+            if k1 == len(starts) - 1:
+                break
+            k, uoff = at[nv >> 16], nv & 0xFFFF
+        out = self.index_end()
+        out["next_voffsets"] = nvs
+        return out
 
     def inflate_bgzf(self, comp):
         """Inflate a run of whole BGZF blocks (bytes-like) on the device; returns the inflated bytes."""

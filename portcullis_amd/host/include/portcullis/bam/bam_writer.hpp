@@ -51,6 +51,13 @@ struct HookAlloc {
 };
 typedef std::vector<uint8_t, HookAlloc<uint8_t>> ByteBuf;
 
+// A BAI index as it is built: per target the chunks of every bin (ascending bin number) and the linear index (0: a window
+// no record touched).  writeBai serialises it -- no metadata pseudo-bin, no count of unplaced records; an untouched window
+// repeats the entry before it -- for BamWriter::close and for `prep` (Prepare::bamIndex), whose index comes from the device.
+using BaiBins = std::vector<std::map<uint32_t, std::vector<std::pair<uint64_t, uint64_t>>>>;
+using BaiLinear = std::vector<std::vector<uint64_t>>;
+void writeBai(const std::string& baiPath, const BaiBins& bins, const BaiLinear& lin);
+
 class BamWriter {
     struct RecInfo {
         int32_t tid, pos, end;
@@ -67,8 +74,8 @@ class BamWriter {
     uint64_t cwritten = 0;             // compressed bytes written
     std::vector<RecInfo> recs;         // records since the last flush
     size_t nTargets = 0;
-    std::vector<std::map<uint32_t, std::vector<std::pair<uint64_t, uint64_t>>>> bins;
-    std::vector<std::vector<uint64_t>> lin;
+    BaiBins bins;
+    BaiLinear lin;
     bool havePrev = false;             // the previous record's end offset is still open
     int32_t prevTid = -1;
     uint32_t prevBin = 0;

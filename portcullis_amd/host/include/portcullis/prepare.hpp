@@ -1,0 +1,57 @@
+// Prepare: `portcullis_amd prep` -- the prepared directory `junc` starts from (the class surface of the reference's
+// src/prepare.hpp:147-230 and src/prepare.cc:89-332, 373-): the genome and its .fai, the coordinate-sorted BAM and its .bai,
+// linked or copied under the names of PreparedFiles.  Where the reference shells out to `samtools index`
+// (Prepare::bamIndex, src/prepare.cc:227-260) the index is built on the device: pjb_index_begin / _piece / _end over the
+// file's BGZF blocks, read through a ring of page-locked pieces.  Sorting and merging BAM files (bamSort / bamMerge,
+// src/prepare.cc:140-226) and CSI output are not built: such input is refused with a message that says what to do instead.
+#pragma once
+
+#include <cstdint>
+#include <string>
+#include <vector>
+
+#include "prepared_files.hpp"
+
+namespace portcullis {
+
+const std::string DEFAULT_PREP_OUTPUT_DIR = "portcullis_prep";  // src/prepare.hpp:59
+const uint16_t DEFAULT_PREP_THREADS = 1;
+
+class Prepare {
+    PreparedFiles output;
+    bool force = false;
+    bool useLinks = true;
+    uint16_t threads = DEFAULT_PREP_THREADS;
+    bool useCsi = false;
+    bool verbose = false;
+
+    // link or copy `from` to `to` unless `to` is there already (src/prepare.cc:98-128); true if `to` exists afterwards
+    bool copy(const std::string& from, const std::string& to, const std::string& msg, bool requireInputFileExists);
+    bool genomeIndex();
+    bool bamIndex(bool indexCopied);
+    void buildIndexOnDevice(const std::string& bamFile, const std::string& baiFile);
+
+public:
+    explicit Prepare(const std::string& outputDir);
+
+    void setForce(bool v) { force = v; }
+    void setUseLinks(bool v) { useLinks = v; }
+    void setUseCsi(bool v) { useCsi = v; }
+    void setThreads(uint16_t v) { threads = v; }
+    void setVerbose(bool v) { verbose = v; }
+    const PreparedFiles& getOutput() const { return output; }
+
+    // removes what a previous run left in the directory (PreparedFiles::clean, src/prepare.cc:77-86)
+    void clean();
+    void prepare(const std::vector<std::string>& bamFiles, const std::string& genomeFile);
+
+    static std::string title() { return "Portcullis Prepare Mode Help"; }
+    static std::string description() {
+        return "Prepares a genome and a coordinate-sorted BAM file for the junction analysis: links (or copies) both into the\n"
+               "output directory and indexes them.  A BAM index that is missing is built on the GPU.";
+    }
+    static std::string usage() { return "portcullis_amd prep [options] <genome-file> <bam-file>"; }
+    static int main(int argc, char* argv[]);
+};
+
+}  // namespace portcullis

@@ -1,5 +1,5 @@
 // PreparedFiles: the path contract of a `portcullis prep` output directory (src/prepare.hpp:84-145
-// and PreparedFiles::valid, src/prepare.cc:57-75).  `prep` itself is outside this library.
+// and PreparedFiles::valid, src/prepare.cc:57-75).  `prep` itself: prepare.hpp.
 #pragma once
 
 #include <string>

@@ -371,6 +371,11 @@ void BamWriter::close() {
         fprintf(stderr, "[writer profile] %s: gather %.3f s, compress %.3f s, fwrite %.3f s, index %.3f s, tail %.3f s\n", path.c_str(), g_prof.gather,
                 g_prof.compress, g_prof.fwrite_, g_prof.index, g_prof.tail);
     if (!wantIndex) return;
+    writeBai(path + ".bai", bins, lin);
+}
+
+void writeBai(const std::string& baiPath, const BaiBins& bins, const BaiLinear& lin) {
+    const size_t nTargets = bins.size();
     std::vector<uint8_t> o = {'B', 'A', 'I', 1};
     put32(o, (uint32_t)nTargets);
     for (size_t c = 0; c < nTargets; c++) {
@@ -390,10 +395,10 @@ void BamWriter::close() {
             put64(o, last);
         }
     }
-    FILE* f = fopen((path + ".bai").c_str(), "wb");
-    if (!f) throw BamException("Could not write BAM index: " + path + ".bai");
-    fwrite(o.data(), 1, o.size(), f);
-    fclose(f);
+    FILE* f = fopen(baiPath.c_str(), "wb");
+    if (!f) throw BamException("Could not write BAM index: " + baiPath);
+    const bool ok = fwrite(o.data(), 1, o.size(), f) == o.size();
+    if (fclose(f) != 0 || !ok) throw BamException("Could not write BAM index: " + baiPath);
 }
 
 }  // namespace bam

@@ -1,0 +1,519 @@
+// Prepare (`portcullis_amd prep`): see prepare.hpp.  Mirrors src/prepare.cc:89-332 (Prepare::copy, genomeIndex, bamIndex,
+// prepare) and 373- (Prepare::main) of the reference; the BAM index is built on the device instead of by `samtools index`.
+#include <portcullis/bam/bam_writer.hpp>
+#include <portcullis/bam/genome_mapper.hpp>
+#include <portcullis/prepare.hpp>
+
+#include <fcntl.h>
+#include <sys/stat.h>
+#include <unistd.h>
+#include <zlib.h>
+
+#include <algorithm>
+#include <chrono>
+#include <climits>
+#include <condition_variable>
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+#include <deque>
+#include <fstream>
+#include <iostream>
+#include <mutex>
+#include <thread>
+
+#include "../../../include/portcullis_amd.h"
+#include "pinned_pool.hpp"
+
+using std::cout;
+using std::endl;
+using std::string;
+
+namespace portcullis {
+
+namespace {
+
+bool lexists(const string& p) {
+    struct stat st;
+    return lstat(p.c_str(), &st) == 0;
+}
+bool fileExists(const string& p) {  // (follows links: a dangling link is not a file)
+    struct stat st;
+    return stat(p.c_str(), &st) == 0;
+}
+bool makeDirs(const string& dir) {
+    string cur;
+    for (size_t i = 0; i <= dir.size(); i++) {
+        if (i == dir.size() || dir[i] == '/') {
+            if (!cur.empty() && !fileExists(cur) && mkdir(cur.c_str(), 0777) != 0 && errno != EEXIST) return false;
+        }
+        if (i < dir.size()) cur += dir[i];
+    }
+    return true;
+}
+double nowSeconds() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
+
+constexpr int64_t BAI_MAX_TARGET = (int64_t)1 << 29;  // reg2bin covers [0, 2^29)
+
+// One BGZF block header at p (n bytes in reach): the block's size, 0 if the header is not complete yet; throws if it is none.
+size_t bgzfBlockSize(const uint8_t* p, size_t n, int64_t fileOffset) {
+    if (n < 18) return 0;
+    if (p[0] != 31 || p[1] != 139 || p[2] != 8 || !(p[3] & 4)) throw PrepareException("Not a BGZF block header at byte " + std::to_string(fileOffset) + " of the BAM file");
+    const size_t xlen = p[10] | (size_t)p[11] << 8;
+    if (n < 12 + xlen) return 0;
+    size_t bsize = 0;
+    for (size_t x = 0; x + 4 <= xlen;) {
+        const uint8_t* f = p + 12 + x;
+        const size_t slen = f[2] | (size_t)f[3] << 8;
+        if (f[0] == 'B' && f[1] == 'C' && slen == 2 && x + 6 <= xlen) bsize = (size_t)(f[4] | (size_t)f[5] << 8) + 1;
+        x += 4 + slen;
+    }
+    if (bsize < xlen + 20) throw PrepareException("BGZF block at byte " + std::to_string(fileOffset) + " of the BAM file has no valid BC field");
+    return bsize;
+}
+
+// What the indexer needs of a BAM file's header: the targets, and where the first alignment record starts.
+struct BamHead {
+    std::vector<string> names;
+    std::vector<int32_t> lens;
+    int64_t firstBlock = 0;  // file offset of the block that holds the first record's first byte (or follows the header)
+    int32_t firstUoffset = 0;
+};
+
+BamHead readBamHead(const string& bamFile) {
+    FILE* f = fopen(bamFile.c_str(), "rb");
+    if (!f) throw PrepareException("Could not open BAM file: " + bamFile);
+    struct Closer {
+        FILE* f;
+        ~Closer() { fclose(f); }
+    } closer{f};
+    std::vector<uint8_t> head;              // inflated bytes so far
+    std::vector<std::pair<int64_t, size_t>> blocks;  // (file offset, inflated bytes before it)
+    int64_t at = 0;
+    std::vector<uint8_t> out(65536);
+    auto need = [&](size_t n) {
+        while (head.size() < n) {
+            uint8_t h[18 + 65536];
+            if (fseeko(f, (off_t)at, SEEK_SET) != 0) throw PrepareException("Could not read BAM file: " + bamFile);
+            const size_t got = fread(h, 1, sizeof h, f);
+            const size_t bsize = got ? bgzfBlockSize(h, got, at) : 0;
+            if (bsize == 0 || bsize > got) throw PrepareException("The header of BAM file " + bamFile + " is truncated");
+            const size_t xlen = h[10] | (size_t)h[11] << 8;
+            z_stream zs;
+            memset(&zs, 0, sizeof zs);
+            if (inflateInit2(&zs, -15) != Z_OK) throw PrepareException("zlib: inflateInit2 failed");
+            zs.next_in = h + 12 + xlen;
+            zs.avail_in = (uInt)(bsize - xlen - 20);
+            zs.next_out = out.data();
+            zs.avail_out = (uInt)out.size();
+            const int zr = inflate(&zs, Z_FINISH);
+            const size_t made = out.size() - zs.avail_out;
+            inflateEnd(&zs);
+            if (zr != Z_STREAM_END) throw PrepareException("Corrupt BGZF block at byte " + std::to_string(at) + " of " + bamFile);
+            blocks.push_back({at, head.size()});
+            head.insert(head.end(), out.begin(), out.begin() + (long)made);
+            at += (int64_t)bsize;
+        }
+    };
+    auto rd32 = [&](size_t o) { return (int32_t)((uint32_t)head[o] | (uint32_t)head[o + 1] << 8 | (uint32_t)head[o + 2] << 16 | (uint32_t)head[o + 3] << 24); };
+    need(12);
+    if (memcmp(head.data(), "BAM\1", 4) != 0) throw PrepareException("Not a BAM file: " + bamFile);
+    const int32_t lText = rd32(4);
+    if (lText < 0) throw PrepareException("Corrupt BAM header: " + bamFile);
+    size_t p = 8 + (size_t)lText;
+    need(p + 4);
+    const int32_t nRef = rd32(p);
+    p += 4;
+    if (nRef < 0) throw PrepareException("Corrupt BAM header: " + bamFile);
+    BamHead H;
+    for (int32_t t = 0; t < nRef; t++) {
+        need(p + 4);
+        const int32_t lName = rd32(p);
+        if (lName < 1) throw PrepareException("Corrupt BAM header: " + bamFile);
+        p += 4;
+        need(p + (size_t)lName + 4);
+        H.names.emplace_back((const char*)&head[p], (size_t)lName - 1);
+        p += (size_t)lName;
+        H.lens.push_back(rd32(p));
+        p += 4;
+    }
+    // the block in which inflated byte p lies; the block behind the header when the header ends with its block
+    H.firstBlock = at;
+    H.firstUoffset = 0;
+    for (size_t b = 0; b < blocks.size(); b++) {
+        const size_t end = b + 1 < blocks.size() ? blocks[b + 1].second : head.size();
+        if (blocks[b].second <= p && p < end) {
+            H.firstBlock = blocks[b].first;
+            H.firstUoffset = (int32_t)(p - blocks[b].second);
+        }
+    }
+    return H;
+}
+
+// The file's bytes in pieces of a ring of page-locked buffers, read ahead by a thread of its own.  A buffer holds two pieces'
+// worth: the piece is read into its second half, and what the piece before it left unconsumed (a block cut by the piece's end,
+// the block of a record that straddles it) is copied in front of it, so that the indexer sees whole blocks in one run of memory.
+struct PieceReader {
+    struct Piece {
+        uint8_t* buf = nullptr;  // the ring buffer (nullptr: the end of the file, or an error)
+        size_t got = 0;
+        bool last = false;
+    };
+    PinnedPool pool;
+    size_t piece;
+    int fd;
+    int64_t size, from;
+    std::mutex mu;
+    std::condition_variable cv;
+    std::deque<Piece> ready;
+    string error;
+    std::thread th;
+
+    PieceReader(int fd_, int64_t from_, int64_t size_, size_t pieceBytes) : pool(3, 2 * pieceBytes), piece(pieceBytes), fd(fd_), size(size_), from(from_) {
+        th = std::thread([this] { run(); });
+    }
+    ~PieceReader() {  // (also an early exit: the reader gets every buffer back and sees `stop`)
+        std::unique_lock<std::mutex> lk(mu);
+        stop = true;
+        for (;;) {
+            while (!ready.empty()) {
+                if (ready.front().buf) pool.release(ready.front().buf);
+                ready.pop_front();
+            }
+            if (exited) break;
+            cv.wait(lk);
+        }
+        lk.unlock();
+        th.join();
+    }
+    void run() {
+        struct Exit {
+            PieceReader& r;
+            ~Exit() {
+                std::lock_guard<std::mutex> lk(r.mu);
+                r.exited = true;
+                r.cv.notify_all();
+            }
+        } onExit{*this};
+        int64_t at = from;
+        for (;;) {
+            Piece pc;
+            pc.buf = pool.acquire(2 * piece);
+            if (!pc.buf) {
+                push(Piece(), "Could not allocate page-locked memory for the BAM file's pieces");
+                return;
+            }
+            {
+                std::lock_guard<std::mutex> lk(mu);
+                if (stop) {
+                    pool.release(pc.buf);
+                    return;
+                }
+            }
+            const size_t want = (size_t)std::min<int64_t>((int64_t)piece, size - at);
+            size_t got = 0;
+            while (got < want) {
+                const ssize_t r = pread(fd, pc.buf + piece + got, want - got, (off_t)(at + (int64_t)got));
+                if (r < 0 && errno == EINTR) continue;
+                if (r <= 0) {
+                    pool.release(pc.buf);
+                    push(Piece(), "Could not read the BAM file");
+                    return;
+                }
+                got += (size_t)r;
+            }
+            pc.got = got;
+            at += (int64_t)got;
+            pc.last = at >= size;
+            const bool last = pc.last;
+            push(pc, "");
+            if (last) return;
+        }
+    }
+    void push(const Piece& pc, const string& err) {
+        std::lock_guard<std::mutex> lk(mu);
+        if (!err.empty()) error = err;
+        ready.push_back(pc);
+        cv.notify_all();
+    }
+    Piece next() {
+        std::unique_lock<std::mutex> lk(mu);
+        cv.wait(lk, [&] { return !ready.empty(); });
+        Piece pc = ready.front();
+        ready.pop_front();
+        if (!pc.buf) throw PrepareException(error);
+        return pc;
+    }
+    void release(uint8_t* buf) { pool.release(buf); }
+    bool stop = false, exited = false;
+};
+
+}  // namespace
+
+Prepare::Prepare(const string& outputDir) : output(outputDir) {
+    struct stat st;
+    if (stat(outputDir.c_str(), &st) != 0) {
+        if (!makeDirs(outputDir) || stat(outputDir.c_str(), &st) != 0) throw PrepareException("Could not create output directory at: " + outputDir);
+    } else if (!S_ISDIR(st.st_mode))
+        throw PrepareException("File exists with name of suggested output directory: " + outputDir);
+}
+
+void Prepare::clean() {
+    for (const string& p : {output.getUnsortedBamFilePath(), output.getSortedBamFilePath(), output.getBamIndexFilePath(false), output.getBamIndexFilePath(true),
+                            output.getGenomeFilePath(), output.getGenomeIndexFilePath()})
+        if (lexists(p)) unlink(p.c_str());
+}
+
+bool Prepare::copy(const string& from, const string& to, const string& msg, bool requireInputFileExists) {
+    if (lexists(to)) cout << "Prepped " << msg << " file detected: " << to << endl;
+    else if (requireInputFileExists || lexists(from)) {
+        if (useLinks) {
+            char real[PATH_MAX];
+            if (!realpath(from.c_str(), real)) throw PrepareException("Could not resolve " + msg + " file: " + from);
+            if (symlink(real, to.c_str()) != 0) throw PrepareException("Could not create symlink from " + from + " to " + to);
+            cout << "Created symlink from " << from << " to " << to << endl;
+        } else {
+            const double t0 = nowSeconds();
+            cout << "Copying from " << from << " to " << to << " ... ";
+            cout.flush();
+            std::ifstream src(from, std::ios::binary);
+            std::ofstream dst(to, std::ios::binary);
+            if (!src || !dst) throw PrepareException("Could not copy " + from + " to " + to);
+            dst << src.rdbuf();
+            dst.close();
+            if (!dst) throw PrepareException("Could not copy " + from + " to " + to);
+            cout << "done." << endl;
+            printf(" - Copy %s - Wall time taken: %.1fs\n\n", msg.c_str(), nowSeconds() - t0);
+        }
+    } else
+        cout << "Existing " << msg << " not found.  Will create later." << endl;
+    return lexists(to);
+}
+
+bool Prepare::genomeIndex() {
+    const string indexFile = output.getGenomeIndexFilePath();
+    if (lexists(indexFile)) cout << "Pre-indexed genome detected: " << indexFile << endl;
+    else {
+        const double t0 = nowSeconds();
+        cout << "Indexing genome " << output.getGenomeFilePath() << " ... ";
+        cout.flush();
+        bam::GenomeMapper(output.getGenomeFilePath()).buildFastaIndex();
+        cout << "done." << endl << "Genome index file created at: " << indexFile << endl;
+        printf(" - Genome Index - Wall time taken: %.1fs\n\n", nowSeconds() - t0);
+    }
+    return fileExists(indexFile);
+}
+
+bool Prepare::bamIndex(bool indexCopied) {
+    const string indexFile = output.getBamIndexFilePath(useCsi);
+    if (indexCopied || lexists(indexFile)) cout << "Pre-indexed BAM detected: " << indexFile << endl;
+    else {
+        const double t0 = nowSeconds();
+        cout << "Indexing " << output.getSortedBamFilePath() << " on the GPU ... ";
+        cout.flush();
+        buildIndexOnDevice(output.getSortedBamFilePath(), indexFile);
+        cout << "done." << endl << "BAM index created at: " << indexFile << endl;
+        printf(" - BAM Index - Wall time taken: %.1fs\n\n", nowSeconds() - t0);
+    }
+    return lexists(indexFile);
+}
+
+void Prepare::buildIndexOnDevice(const string& bamFile, const string& baiFile) {
+    const BamHead H = readBamHead(bamFile);
+    for (size_t t = 0; t < H.lens.size(); t++)
+        if ((int64_t)H.lens[t] >= BAI_MAX_TARGET)
+            throw PrepareException("BAI cannot index this target: " + H.names[t] + " has " + std::to_string(H.lens[t]) +
+                                   " bases, and a BAI index reaches 2^29.  Index the file with `samtools index -c` and use the CSI index (junc --use_csi): writing "
+                                   "CSI is not built into portcullis_amd prep.");
+    if (pjb_device_count() <= 0)
+        throw PrepareException("No MI355X (HIP device) is visible: the BAM index is built on the GPU and has no CPU fallback.  Put an index made elsewhere "
+                               "(samtools index) beside the BAM file, or run prep where the GPU is.");
+    struct Ctx {
+        pjb_ctx* c = nullptr;
+        ~Ctx() {
+            if (c) pjb_destroy(c);
+        }
+    } ctx;
+    pjb_config cfg;
+    memset(&cfg, 0, sizeof cfg);
+    cfg.abi_version = PJB_ABI_VERSION;
+    cfg.flags = PJB_FLAG_NO_CHAINS;
+    if (pjb_create(&ctx.c, &cfg) != PJB_OK) throw PrepareException(string("pjb_create: ") + pjb_last_error(nullptr));
+    auto check = [&](int rc, const char* what) {
+        if (rc == PJB_OK) return;
+        const string msg = pjb_last_error(ctx.c);
+        if (rc == PJB_ERR_UNSORTED)
+            throw PrepareException("The BAM file is not in coordinate order: " + msg + ".  Sort it first (samtools sort): sorting is not built into portcullis_amd prep.");
+        if (rc == PJB_ERR_ARG && msg.find("BAI cannot index") != string::npos)
+            throw PrepareException(msg + ".  Index the file with `samtools index -c` and use the CSI index (junc --use_csi).");
+        throw PrepareException(string(what) + ": " + msg);
+    };
+    check(pjb_set_refs(ctx.c, (int32_t)H.lens.size(), H.lens.data()), "pjb_set_refs");
+    check(pjb_index_begin(ctx.c), "pjb_index_begin");
+
+    const int fd = open(bamFile.c_str(), O_RDONLY);
+    if (fd < 0) throw PrepareException("Could not open BAM file: " + bamFile);
+    struct Fd {
+        int fd;
+        ~Fd() { close(fd); }
+    } fdGuard{fd};
+    struct stat st;
+    if (fstat(fd, &st) != 0) throw PrepareException("Could not stat BAM file: " + bamFile);
+    const int64_t size = (int64_t)st.st_size;
+    // PORTCULLIS_PIECE_BYTES (tests) / PORTCULLIS_PIECE_MB as in junc: what is read and handed to the device at a time.  The default is
+    // larger than junc's 64 MB: a piece is one inflate launch, and a launch takes ~27 ms whatever its size (a 3.4 GB file of 20 M records:
+    // 1.91 s with pieces of 64 MB, 0.96 s with 256 MB, 1.03 s with 1 GB -- page-locking the ring then costs what the launches save).
+    size_t piece = (size_t)std::max(1, getenv("PORTCULLIS_PIECE_MB") ? atoi(getenv("PORTCULLIS_PIECE_MB")) : 256) << 20;
+    if (const char* e = getenv("PORTCULLIS_PIECE_BYTES"))
+        if (atoi(e) > 0) piece = (size_t)std::max(64, atoi(e));
+    piece = (size_t)std::min<int64_t>((int64_t)piece, std::max<int64_t>(size - H.firstBlock, 64));
+
+    // `carry`: the bytes from file offset carryOff on that have been read and not consumed
+    std::vector<uint8_t> carry, big;
+    int64_t carryOff = H.firstBlock;
+    int32_t uoff = H.firstUoffset;
+    bool done = false;
+    if (H.firstBlock >= size) {  // a header and nothing else (not even the EOF block)
+        uint64_t nv = 0;
+        check(pjb_index_piece(ctx.c, nullptr, 0, H.firstBlock, 0, 1, &nv), "pjb_index_piece");
+        done = true;
+    }
+    if (!done) {
+        PieceReader reader(fd, H.firstBlock, size, piece);
+        while (!done) {
+            PieceReader::Piece pc = reader.next();
+            struct Release {
+                PieceReader& r;
+                uint8_t* b;
+                ~Release() { r.release(b); }
+            } rel{reader, pc.buf};
+            uint8_t* region;
+            const size_t regionBytes = carry.size() + pc.got;
+            if (carry.size() <= piece) {  // the usual case: in front of the piece, in its page-locked buffer
+                region = pc.buf + piece - carry.size();
+                if (!carry.empty()) memcpy(region, carry.data(), carry.size());
+            } else {  // a block or a record longer than a piece: a run of pageable memory as long as it takes
+                big.resize(regionBytes);
+                memcpy(big.data(), carry.data(), carry.size());
+                memcpy(big.data() + carry.size(), pc.buf + piece, pc.got);
+                region = big.data();
+            }
+            // whole blocks
+            size_t whole = 0;
+            while (whole < regionBytes) {
+                const size_t bs = bgzfBlockSize(region + whole, regionBytes - whole, carryOff + (int64_t)whole);
+                if (bs == 0 || whole + bs > regionBytes) break;
+                whole += bs;
+            }
+            if (pc.last && whole != regionBytes) throw PrepareException("The BAM file ends inside a BGZF block (truncated file): " + bamFile);
+            size_t consumed = 0;
+            if (whole > 0) {
+                uint64_t nv = ~0ull;
+                const int rc = pjb_index_piece(ctx.c, region, (int64_t)whole, carryOff, uoff, pc.last ? 1 : 0, &nv);
+                if (rc == PJB_ERR_ARG && nv != ~0ull && !pc.last) {
+                    // the first record is longer than these blocks: the same blocks again, with the next piece behind them
+                } else {
+                    check(rc, "pjb_index_piece");
+                    consumed = (size_t)((int64_t)(nv >> 16) - carryOff);
+                    uoff = (int32_t)(nv & 0xffff);
+                }
+            }
+            if (pc.last) done = true;
+            else {
+                std::vector<uint8_t> rest(region + consumed, region + regionBytes);
+                carry.swap(rest);
+                carryOff += (int64_t)consumed;
+            }
+        }
+    }
+    pjb_index_result res;
+    check(pjb_index_end(ctx.c, &res), "pjb_index_end");
+    // the chunk list is ordered by (target, bin, file order): the maps below only group it
+    const size_t nRef = H.lens.size();
+    bam::BaiBins bins(nRef);
+    bam::BaiLinear lin(nRef);
+    for (int64_t k = 0; k < res.n_chunks; k++) {
+        const pjb_index_chunk& ch = res.chunks[k];
+        bins[(size_t)ch.tid][ch.bin].push_back({ch.vbeg, ch.vend});
+    }
+    for (size_t t = 0; t < nRef; t++) lin[t].assign(res.lin + res.lin_off[t], res.lin + res.lin_off[t + 1]);
+    const string tmp = baiFile + ".tmp";
+    bam::writeBai(tmp, bins, lin);
+    if (rename(tmp.c_str(), baiFile.c_str()) != 0) throw PrepareException("Could not write BAM index: " + baiFile);
+    if (verbose) cout << endl << "Indexed " << res.n_records << " alignment records: " << res.n_chunks << " chunks." << endl;
+}
+
+void Prepare::prepare(const std::vector<string>& bamFiles, const string& genomeFile) {
+    if (useCsi)
+        throw PrepareException("Writing CSI indexes is not built into portcullis_amd prep.  Build the directory without --use_csi (a BAI index covers targets "
+                               "below 2^29 bases), or put a CSI index made with `samtools index -c` beside the BAM file and link the files by hand.");
+    if (bamFiles.empty()) throw PrepareException("No BAM files to process");
+    if (bamFiles.size() > 1)
+        throw PrepareException("More than one BAM file was given, and merging is not built into portcullis_amd prep.  Merge them first (samtools merge) and "
+                               "pass the one coordinate-sorted file.");
+    if (!fileExists(bamFiles[0])) throw PrepareException("Could not find BAM file at: " + bamFiles[0]);
+    if (force) {
+        cout << "Cleaning output dir " << output.getPrepDir() << " ... ";
+        cout.flush();
+        clean();
+        cout << "done." << endl;
+    }
+    if (!copy(genomeFile, output.getGenomeFilePath(), "genome", true)) throw PrepareException("Could not copy/symlink genome file to: " + output.getGenomeFilePath());
+    copy(genomeFile + ".fai", output.getGenomeIndexFilePath(), "genome index", false);
+    if (!genomeIndex()) throw PrepareException("Could not create genome index");
+    if (!copy(bamFiles[0], output.getSortedBamFilePath(), "BAM", true)) throw PrepareException("Could not copy/symlink BAM file to: " + output.getSortedBamFilePath());
+    // the index beside the input if there is one (src/prepare.cc:316), else it is built (no device is touched before this point)
+    const bool indexCopied = copy(bamFiles[0] + ".bai", output.getBamIndexFilePath(false), "BAM index", false);
+    if (!bamIndex(indexCopied)) throw PrepareException("Failed to index: " + output.getSortedBamFilePath());
+}
+
+int Prepare::main(int argc, char* argv[]) {
+    std::vector<string> positional;
+    string outputDir = DEFAULT_PREP_OUTPUT_DIR;
+    bool force = false, copy = false, useCsi = false, verbose = false, help = false;
+    int threads = DEFAULT_PREP_THREADS;
+    auto need = [&](int& i) -> string {
+        if (i + 1 >= argc) throw PrepareException(string("Missing value for option ") + argv[i]);
+        return argv[++i];
+    };
+    for (int i = 1; i < argc; i++) {
+        const string a = argv[i];
+        if (a == "-o" || a == "--output") outputDir = need(i);
+        else if (a == "--force") force = true;
+        else if (a == "--copy") copy = true;
+        else if (a == "-c" || a == "--use_csi") useCsi = true;
+        else if (a == "-t" || a == "--threads") threads = atoi(need(i).c_str());
+        else if (a == "-v" || a == "--verbose") verbose = true;
+        else if (a == "--help" || a == "-h") help = true;
+        else if (!a.empty() && a[0] == '-') throw PrepareException("Unknown option: " + a);
+        else positional.push_back(a);
+    }
+    if (help || positional.size() < 2) {
+        cout << title() << endl << endl << description() << endl << endl << "Usage: " << usage() << endl
+             << "  -o, --output <dir>   Output directory for prepared files (default " << DEFAULT_PREP_OUTPUT_DIR << ")" << endl
+             << "      --force          Clean the output directory first, so that everything is prepared again" << endl
+             << "      --copy           Copy the input files into the output directory instead of linking them" << endl
+             << "  -c, --use_csi        CSI instead of BAI indexing (not built: refused)" << endl
+             << "  -t, --threads <n>    Accepted for compatibility (the index is built on the GPU)" << endl
+             << "  -v, --verbose        Print extra information" << endl
+             << "      --help           Produce this message" << endl;
+        return help ? 0 : 1;
+    }
+    const string genomeFile = positional[0];
+    const std::vector<string> bamFiles(positional.begin() + 1, positional.end());
+    if (!lexists(genomeFile)) throw PrepareException("Could not find genome file at: " + genomeFile);
+    const double t0 = nowSeconds();
+    cout << "Running portcullis in prepare mode" << endl << "----------------------------------" << endl << endl;
+    Prepare prep(outputDir);
+    prep.setForce(force);
+    prep.setUseLinks(!copy);
+    prep.setUseCsi(useCsi);
+    prep.setThreads((uint16_t)std::max(1, threads));
+    prep.setVerbose(verbose);
+    prep.prepare(bamFiles, genomeFile);
+    prep.getOutput().valid(false);
+    printf("\nPortcullis prep completed.\nTotal runtime: %.1fs\n\n", nowSeconds() - t0);
+    return 0;
+}
+
+}  // namespace portcullis
