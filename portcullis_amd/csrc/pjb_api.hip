@@ -267,8 +267,7 @@ int pjb_set_refs(pjb_ctx *c, int32_t n_refs, const int32_t *ref_len) {
 // record that was not laid out as stated returns 1 and leaves the context as it was
 static int upload_common(pjb_ctx *c, int32_t tid, uint8_t *d, int64_t len, bool owned, bool do_upper, size_t d_cap = 0, bool fasta_flag = false) {
     static const bool prof = getenv("PJB_PROFILE_HOST") != nullptr;
-    auto now = [] { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
-    const double t_up0 = now();
+    const double t_up0 = wall_now();
     double t_alloc = 0;
     HIP_TRY(c, hipSetDevice(c->cfg.device));
     // the kernels' three flags (an 'X' among the bases, a character outside the 16-letter alphabet, a character outside ACGT) come back in
@@ -291,9 +290,9 @@ static int upload_common(pjb_ctx *c, int32_t tid, uint8_t *d, int64_t len, bool 
     const size_t c2_at = ((size_t)(n_words + 2) + 3) & ~(size_t)3;                       // (the 2-bit codes start on a 16-byte boundary)
     const size_t c2_words = len > 0 && !no_seq2 ? (size_t)codes2_alloc_words(len) : 0;
     if (len > 0) {
-        const double ta = now();
+        const double ta = wall_now();
         codes = (u32 *)genome_take(c->genome_pool, (c2_at + c2_words) * 4, codes_cap);
-        t_alloc = now() - ta;
+        t_alloc = wall_now() - ta;
         if (!codes) return fail(c, PJB_ERR_NOMEM, "hipMalloc(genome codes, %zu bytes) failed", (c2_at + c2_words) * 4);
         (void)hipMemsetAsync(codes + n_words, 0, 8, c->stream);
         hipLaunchKernelGGL(k0_encode, dim3((unsigned)((n_words + 255) / 256)), dim3(256), 0, c->stream, (const uint8_t *)d, len,
@@ -312,7 +311,7 @@ static int upload_common(pjb_ctx *c, int32_t tid, uint8_t *d, int64_t len, bool 
     }
     int flags[4] = {0, 0, 1, 0};
     HIP_TRY(c, hipMemcpyAsync(flags, d_flags, (fasta_flag ? 4 : 3) * sizeof(int), hipMemcpyDeviceToHost, c->stream));
-    const double t_sync0 = now();
+    const double t_sync0 = wall_now();
     hipError_t se = hipStreamSynchronize(c->stream);
     if (se != hipSuccess) {
         if (codes) (void)hipFree(codes);
@@ -320,7 +319,7 @@ static int upload_common(pjb_ctx *c, int32_t tid, uint8_t *d, int64_t len, bool 
     }
     if (prof)
         fprintf(stderr, "[host profile] genome tid %d (%lld bases): codes allocation %.4f, launches %.4f, wait for the stream %.4f s\n", tid, (long long)len, t_alloc,
-                t_sync0 - t_up0 - t_alloc, now() - t_sync0);
+                t_sync0 - t_up0 - t_alloc, wall_now() - t_sync0);
     if (fasta_flag && flags[3]) { // (the bytes were not a FASTA record of that geometry: nothing of this upload is kept)
         if (codes) (void)hipFree(codes);
         return 1;
@@ -402,23 +401,18 @@ int pjb_upload_contig_fasta(pjb_ctx *c, int32_t tid, const uint8_t *raw, int64_t
     if ((rc = ensure(c, c->b_fasta_raw, (size_t)std::max<int64_t>(raw_bytes, 16)))) return rc;
     if ((rc = ensure(c, c->b_hasx, 4 * sizeof(int)))) return rc;
     size_t d_cap = 0;
-    const double t_a0 = std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count();
+    const double t_a0 = wall_now();
     uint8_t *d = (uint8_t *)genome_take(c->genome_pool, (size_t)std::max<int64_t>(len, 16), d_cap);
     if (!d) return fail(c, PJB_ERR_NOMEM, "hipMalloc(genome %lld) failed", (long long)len);
     if (getenv("PJB_PROFILE_HOST"))
-        fprintf(stderr, "[host profile] genome tid %d: bases allocation %.4f s\n", tid, std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count() - t_a0);
+        fprintf(stderr, "[host profile] genome tid %d: bases allocation %.4f s\n", tid, wall_now() - t_a0);
     struct Guard {
         uint8_t *d;
         ~Guard() {
             if (d) (void)hipFree(d);
         }
     } guard{d};
-    // page-locked input (pjb_host_alloc): one DMA; otherwise through the staging buffers
-    hipPointerAttribute_t at;
-    const bool pinned = raw_bytes > 0 && hipPointerGetAttributes(&at, raw) == hipSuccess && at.type == hipMemoryTypeHost;
-    if (!pinned) (void)hipGetLastError();
-    if (pinned) HIP_TRY(c, hipMemcpyAsync(c->b_fasta_raw.p, raw, (size_t)raw_bytes, hipMemcpyHostToDevice, c->stream));
-    else if (raw_bytes > 0 && (rc = upload_staged(c, c->b_fasta_raw.p, raw, (size_t)raw_bytes))) return rc;
+    if (raw_bytes > 0 && (rc = upload_host(c, c->b_fasta_raw.p, raw, (size_t)raw_bytes))) return rc;
     // (k0_fasta's verdict is read with the other kernels' flags, behind the last of them: one wait a genome)
     HIP_TRY(c, hipMemsetAsync((int *)c->b_hasx.p + 3, 0, sizeof(int), c->stream));
     if (len > 0) {

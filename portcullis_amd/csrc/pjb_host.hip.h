@@ -447,6 +447,9 @@ inline int check_device_error(pjb_ctx *c, u64 e) {
     return fail(c, code, "%s (alignment ordinal %llu on target %d)", err_text(code), ord, c->cur_tid);
 }
 
+// the host's monotonic clock in seconds (differences only)
+inline double wall_now() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
+
 // host-side copy into page-locked staging memory, split over a few threads for large blocks
 inline void parallel_copy(void *dst, const void *src, size_t bytes) {
     const size_t MIN_SLICE = (size_t)4 << 20;
@@ -648,10 +651,9 @@ inline int close_contig(pjb_ctx *c, int32_t tid) {
     return PJB_OK;
 }
 
-int upload_staged(pjb_ctx *c, void *dst, const uint8_t *src, size_t bytes); // (defined with the ingest code)
-
 // ---- defined in one unit, used by another
-int upload_staged(pjb_ctx *c, void *dst, const uint8_t *src, size_t bytes);                                   // pjb_ingest_api.hip (FASTA bytes through the staging buffers)
+int upload_staged(pjb_ctx *c, void *dst, const uint8_t *src, size_t bytes);                                   // pjb_ingest_api.hip (pageable bytes through the staging buffers)
+int upload_host(pjb_ctx *c, void *dst, const uint8_t *src, size_t bytes);                                     // pjb_ingest_api.hip (page-locked bytes: one DMA, else upload_staged)
 void bam_stage_clear(pjb_ctx *c);                                                                              // pjb_ingest_api.hip (pjb_destroy)
 int extra_pre(pjb_ctx *c, Flight &f);                                                                          // pjb_extra_api.hip (the chain queues a target's extra metrics)
 int extra_contig(pjb_ctx *c, Flight &f, const pjb_region_result *res, u64 n_spliced, u32 P, u32 J, size_t row_base); // pjb_extra_api.hip (res: one per member)

@@ -10,6 +10,9 @@ int ingest_lds_bytes() { return I3_LDS_BYTES; }
 
 
 // ---- device-side ingest ---------------------------------------------------------------------------
+// Each step has one driver, whoever asks: bgzf_header (a block header through a byte reader: scan_bgzf over a buffer, stage_scan over
+// pieces), inflate_queue (one inflate launch on a stream: inflate_on_device waits for it, inflate_early does not), walk_records (record
+// boundaries of a target's region or, `all`, of an indexer's piece), upload_host (host bytes to the device).
 const char *inf_text(int code) {
     switch (code) {
     case INF_ERR_BTYPE: return "reserved DEFLATE block type";
@@ -23,38 +26,48 @@ const char *inf_text(int code) {
     }
 }
 
-// hop over the BGZF block headers (bgzf.c:348-356 check_header, BSIZE from the BC extra subfield)
+// One BGZF block header (bgzf.c:348-356 check_header, BSIZE from the BC extra subfield).  `at(o)` reads byte o of the stream, the block
+// starts at `off`, the bytes before `end` have arrived, the stream ends at `total`.  PJB_OK: `b` (but for out_off) and `bsize` are set;
+// BGZF_SHORT_*: that part of the block has not all arrived; else the error.
+enum { BGZF_SHORT_HEADER = 1, BGZF_SHORT_EXTRA, BGZF_SHORT_FOOTER };
+template <typename At>
+static int bgzf_header(pjb_ctx *c, At at, int64_t off, int64_t end, int64_t total, InfBlock &b, int64_t &bsize) {
+    auto le16 = [&](int64_t o) { return (uint32_t)at(o) | (uint32_t)at(o + 1) << 8; };
+    if (off + 18 > end) return BGZF_SHORT_HEADER;
+    if (at(off) != 31 || at(off + 1) != 139 || at(off + 2) != 8 || !(at(off + 3) & 4))
+        return fail(c, PJB_ERR_BGZF, "not a BGZF block header at byte %lld", (long long)off);
+    const uint32_t xlen = le16(off + 10);
+    if (off + 12 + xlen > end) return BGZF_SHORT_EXTRA;
+    bsize = -1;
+    for (uint32_t x = 0; x + 4 <= xlen;) {
+        const int64_t f = off + 12 + x;
+        const uint32_t slen = le16(f + 2);
+        if (at(f) == 'B' && at(f + 1) == 'C' && slen == 2 && x + 6 <= xlen) bsize = (int64_t)le16(f + 4) + 1;
+        x += 4 + slen;
+    }
+    if (bsize < 0) return fail(c, PJB_ERR_BGZF, "BGZF block at byte %lld has no BC field", (long long)off);
+    if (bsize < (int64_t)xlen + 20 || off + bsize > total)
+        return fail(c, PJB_ERR_BGZF, "BGZF block at byte %lld has an impossible size %lld", (long long)off, (long long)bsize);
+    if (off + bsize > end) return BGZF_SHORT_FOOTER;
+    const uint32_t isize = le16(off + bsize - 4) | le16(off + bsize - 2) << 16;
+    if (isize > 65536u) return fail(c, PJB_ERR_BGZF, "BGZF block at byte %lld declares %u inflated bytes", (long long)off, isize);
+    b.in_off = (iu64)(off + 12 + xlen);
+    b.in_len = (iu32)(bsize - xlen - 20);
+    b.out_len = isize;
+    return PJB_OK;
+}
+
+// hop over the BGZF block headers of a whole buffer
 int scan_bgzf(pjb_ctx *c, const uint8_t *comp, int64_t n, std::vector<InfBlock> &blocks, int64_t &total_out) {
-    int64_t off = 0;
     total_out = 0;
-    while (off < n) {
-        if (off + 18 > n) return fail(c, PJB_ERR_BGZF, "truncated BGZF block header at byte %lld", (long long)off);
-        const uint8_t *h = comp + off;
-        if (h[0] != 31 || h[1] != 139 || h[2] != 8 || !(h[3] & 4))
-            return fail(c, PJB_ERR_BGZF, "not a BGZF block header at byte %lld", (long long)off);
-        const uint32_t xlen = h[10] | (uint32_t)h[11] << 8;
-        if (off + 12 + xlen > n) return fail(c, PJB_ERR_BGZF, "truncated BGZF extra field at byte %lld", (long long)off);
-        int64_t bsize = -1;
-        for (uint32_t x = 0; x + 4 <= xlen;) {
-            const uint8_t *f = h + 12 + x;
-            const uint32_t slen = f[2] | (uint32_t)f[3] << 8;
-            if (f[0] == 'B' && f[1] == 'C' && slen == 2 && x + 6 <= xlen) bsize = (int64_t)(f[4] | (uint32_t)f[5] << 8) + 1;
-            x += 4 + slen;
-        }
-        if (bsize < 0) return fail(c, PJB_ERR_BGZF, "BGZF block at byte %lld has no BC field", (long long)off);
-        if (bsize < (int64_t)xlen + 20 || off + bsize > n)
-            return fail(c, PJB_ERR_BGZF, "BGZF block at byte %lld has an impossible size %lld", (long long)off, (long long)bsize);
-        const uint8_t *foot = comp + off + bsize - 8;
-        const uint32_t isize = foot[4] | (uint32_t)foot[5] << 8 | (uint32_t)foot[6] << 16 | (uint32_t)foot[7] << 24;
-        if (isize > 65536u) return fail(c, PJB_ERR_BGZF, "BGZF block at byte %lld declares %u inflated bytes", (long long)off, isize);
+    for (int64_t off = 0, bsize = 0; off < n; off += bsize) {
         InfBlock b;
-        b.in_off = (iu64)(off + 12 + xlen);
-        b.in_len = (iu32)(bsize - xlen - 20);
+        const int rc = bgzf_header(c, [&](int64_t o) { return comp[o]; }, off, n, n, b, bsize);
+        if (rc > 0) return fail(c, PJB_ERR_BGZF, rc == BGZF_SHORT_HEADER ? "truncated BGZF block header at byte %lld" : "truncated BGZF extra field at byte %lld", (long long)off);
+        if (rc) return rc;
         b.out_off = (iu64)total_out;
-        b.out_len = isize;
         blocks.push_back(b);
-        total_out += isize;
-        off += bsize;
+        total_out += b.out_len;
     }
     return PJB_OK;
 }
@@ -87,8 +100,17 @@ int upload_staged(pjb_ctx *c, void *dst, const uint8_t *src, size_t bytes) {
     return PJB_OK;
 }
 
+// host memory -> device on the main stream: page-locked input (pjb_host_alloc) is one DMA without a staging copy
+int upload_host(pjb_ctx *c, void *dst, const uint8_t *src, size_t bytes) {
+    hipPointerAttribute_t at;
+    if (hipPointerGetAttributes(&at, src) == hipSuccess && at.type == hipMemoryTypeHost) {
+        HIP_TRY(c, hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, c->stream));
+        return PJB_OK;
+    }
+    (void)hipGetLastError();
+    return upload_staged(c, dst, src, bytes);
+}
 
-// comp already on the device (padded); blocks on the host
 // the status words of a finished bgzf_inflate (d_status[nb] = "some block failed")
 int inflate_status(pjb_ctx *c, const std::vector<InfBlock> &blocks, const int *d_status) {
     const size_t nb = blocks.size();
@@ -103,36 +125,57 @@ int inflate_status(pjb_ctx *c, const std::vector<InfBlock> &blocks, const int *d
     return fail(c, PJB_ERR_BGZF, "BGZF inflate failed");
 }
 
+// One launch inflates a list of blocks: as many lanes as the chip holds at once (two 64-lane workgroups per CU: the tables' LDS), each
+// taking block after block from a counter.
+static size_t inflate_lanes(pjb_ctx *c, size_t nb) {
+    size_t lanes = (size_t)c->inflate_lanes;
+    if (const char *e = getenv("PJB_INF_BLOCKS_PER_LAUNCH")) lanes = (size_t)std::max(64, atoi(e)) / 64 * 64; // tests: few lanes, long lists
+    return std::min<size_t>((nb + 63) / 64 * 64, lanes);
+}
+
+// Queues the inflate of `blocks` (d_comp: their bytes, padded) on `st`: the block table and the control words go up (`ctl` must live
+// until that copy is over), then decode (lane per block: literals in place, a token + a bitmap bit per match) and the copies (wave per
+// block).  Waits for nothing and fails nothing: the caller decides what an error means.  Buffers for nb blocks: InfBlock[nb] | int[nb]
+// status, "some block failed", the block counter | INF_SCRATCH_PER_LANE per lane | INF_BITMAP_WORDS u64 per block.
+static hipError_t inflate_queue(pjb_ctx *c, hipStream_t st, const uint8_t *d_comp, const std::vector<InfBlock> &blocks, size_t lanes, iu32 *ctl,
+                                const Buf &b_blocks, const Buf &b_status, const Buf &b_scratch, const Buf &b_bitmap, uint8_t *d_out) {
+    const size_t nb = blocks.size();
+    int *d_status = (int *)b_status.p;
+    int *d_any = d_status + nb;
+    iu32 *d_next = (iu32 *)(d_any + 1);
+    ctl[0] = 0u;
+    ctl[1] = (iu32)lanes;
+    hipError_t e;
+    if ((e = hipMemcpyAsync(b_blocks.p, blocks.data(), nb * sizeof(InfBlock), hipMemcpyHostToDevice, st)) != hipSuccess ||
+        (e = hipMemcpyAsync(d_any, ctl, 8, hipMemcpyHostToDevice, st)) != hipSuccess ||
+        (e = hipMemsetAsync(b_bitmap.p, 0, nb * INF_BITMAP_WORDS * 8, st)) != hipSuccess)
+        return e;
+    const bool t_dec = st == c->stream && ktime_wanted(c, "bgzf_decode"), t_res = st == c->stream && ktime_wanted(c, "bgzf_resolve");
+    if (t_dec) ev_begin(c, "bgzf_decode");
+    hipLaunchKernelGGL(bgzf_decode, dim3((unsigned)(lanes / 64)), dim3(64), I3_LDS_BYTES, st, d_comp, (const InfBlock *)b_blocks.p, (iu32)nb, d_out,
+                       (uint8_t *)b_scratch.p, d_status, d_any, d_next, (iu64 *)b_bitmap.p, 8);
+    if (t_dec) ev_end(c);
+    if (t_res) ev_begin(c, "bgzf_resolve");
+    hipLaunchKernelGGL(bgzf_resolve, dim3((unsigned)((nb + 3) / 4)), dim3(256), 0, st, (const InfBlock *)b_blocks.p, (iu32)nb, d_out,
+                       (const iu64 *)b_bitmap.p, (const int *)d_status);
+    if (t_res) ev_end(c);
+    return hipGetLastError();
+}
+
+// comp already on the device (padded); blocks on the host
 int inflate_on_device(pjb_ctx *c, const uint8_t *d_comp, const std::vector<InfBlock> &blocks, uint8_t *d_out) {
     int rc;
     const size_t nb = blocks.size();
     if (nb == 0) return PJB_OK;
-    if ((rc = ensure(c, c->b_inf_blocks, nb * sizeof(InfBlock)))) return rc;
-    if ((rc = ensure(c, c->b_inf_status, nb * 4 + 16))) return rc;
-    // one launch: as many lanes as the chip holds at once (two 64-lane workgroups per CU: the tables' LDS), each taking
-    // block after block from a counter
-    size_t lanes = std::min<size_t>((nb + 63) / 64 * 64, (size_t)c->inflate_lanes);
-    if (const char *e = getenv("PJB_INF_BLOCKS_PER_LAUNCH")) lanes = std::min<size_t>((nb + 63) / 64 * 64, (size_t)std::max(64, atoi(e)) / 64 * 64); // tests: few lanes, long lists
-    if ((rc = ensure(c, c->b_inf_scratch, lanes * INF_SCRATCH_PER_LANE))) return rc;
-    hipStream_t st = c->stream;
-    HIP_TRY(c, hipMemcpyAsync(c->b_inf_blocks.p, blocks.data(), nb * sizeof(InfBlock), hipMemcpyHostToDevice, st));
-    int *d_status = (int *)c->b_inf_status.p;
-    int *d_any = d_status + nb;
-    iu32 *d_next = (iu32 *)(d_any + 1);
-    const iu32 ctl[2] = {0u, (iu32)lanes};
-    HIP_TRY(c, hipMemcpyAsync(d_any, ctl, 8, hipMemcpyHostToDevice, st));
-    {
-        // decode (lane per block: literals in place, a token + a bitmap bit per match), then the copies (wave per block)
-        if ((rc = ensure(c, c->b_inf_bitmap, nb * INF_BITMAP_WORDS * 8))) return rc;
-        HIP_TRY(c, hipMemsetAsync(c->b_inf_bitmap.p, 0, nb * INF_BITMAP_WORDS * 8, st));
-        LAUNCH_LDS(c, "bgzf_decode", bgzf_decode, dim3((unsigned)(lanes / 64)), dim3(64), I3_LDS_BYTES, d_comp, (const InfBlock *)c->b_inf_blocks.p, (iu32)nb,
-                   d_out, (uint8_t *)c->b_inf_scratch.p, d_status, d_any, d_next, (iu64 *)c->b_inf_bitmap.p, 8);
-        LAUNCH(c, "bgzf_resolve", bgzf_resolve, dim3((unsigned)((nb + 3) / 4)), dim3(256), (const InfBlock *)c->b_inf_blocks.p, (iu32)nb, d_out,
-               (const iu64 *)c->b_inf_bitmap.p, (const int *)d_status);
-    }
-    HIP_TRY(c, hipStreamSynchronize(st));
+    const size_t lanes = inflate_lanes(c, nb);
+    if ((rc = ensure(c, c->b_inf_blocks, nb * sizeof(InfBlock))) || (rc = ensure(c, c->b_inf_status, nb * 4 + 16)) ||
+        (rc = ensure(c, c->b_inf_scratch, lanes * INF_SCRATCH_PER_LANE)) || (rc = ensure(c, c->b_inf_bitmap, nb * INF_BITMAP_WORDS * 8)))
+        return rc;
+    iu32 ctl[2];
+    HIP_TRY(c, inflate_queue(c, c->stream, d_comp, blocks, lanes, ctl, c->b_inf_blocks, c->b_inf_status, c->b_inf_scratch, c->b_inf_bitmap, d_out));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
     if (c->ktime) ev_collect(c, MISC_POOL);
-    return inflate_status(c, blocks, d_status);
+    return inflate_status(c, blocks, (const int *)c->b_inf_status.p);
 }
 
 extern "C" int pjb_inflate_bgzf(pjb_ctx *c, const uint8_t *comp, int64_t comp_bytes, uint8_t *out, int64_t out_cap,
@@ -208,48 +251,46 @@ extern "C" int pjb_deflate_bgzf(pjb_ctx *c, const uint8_t *in, int64_t n_bytes, 
     return PJB_OK;
 }
 
-static int ingest_parse(pjb_ctx *c, int32_t tid, OpenContig &oc, const uint8_t *d_out, size_t n_blocks, int64_t comp_bytes, int64_t total,
-                        int32_t first_uoffset, int64_t *n_records, double t_scan, double t_up, double t_inf);
-
-// the part of pjb_submit_bam behind the upload: `d_comp` holds the target's BGZF bytes (padded), `blocks` their layout
-static int ingest_staged(pjb_ctx *c, int32_t tid, OpenContig &oc, const uint8_t *d_comp, const std::vector<InfBlock> &blocks, int64_t comp_bytes,
-                         int64_t total, int32_t first_uoffset, int64_t *n_records, double t_scan, double t_up) {
-    auto now = [] { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
-    const double t0 = now();
-    int rc;
-    if ((rc = ensure(c, c->b_inf_out, (size_t)total + 64))) return rc;
-    HIP_TRY(c, hipMemsetAsync((uint8_t *)c->b_inf_out.p + total, 0, 64, c->stream));
-    if ((rc = inflate_on_device(c, d_comp, blocks, (uint8_t *)c->b_inf_out.p))) return rc;
-    return ingest_parse(c, tid, oc, (const uint8_t *)c->b_inf_out.p, blocks.size(), comp_bytes, total, first_uoffset, n_records, t_scan, t_up, now() - t0);
+// ---- record boundaries ------------------------------------------------------------------------------------------
+// `total` inflated bytes at U whose first record starts at `first`; tid -1: no target's in particular (the indexer)
+static BamRegion bam_region(pjb_ctx *c, const uint8_t *U, int64_t total, int32_t first, int32_t tid) {
+    BamRegion R;
+    R.U = U;
+    R.total = (iu64)total;
+    R.first = (iu64)first;
+    R.tid = tid;
+    R.ref_len = tid < 0 ? 0 : c->ref_len[(size_t)tid];
+    R.n_ref = (int32_t)c->ref_len.size();
+    return R;
 }
 
-// the inflated bytes of one target's region (d_out, `total` of them followed by 64 zero bytes) -> the SoA batch of the target
-static int ingest_parse(pjb_ctx *c, int32_t tid, OpenContig &oc, const uint8_t *d_out, size_t n_blocks, int64_t comp_bytes, int64_t total,
-                        int32_t first_uoffset, int64_t *n_records, double t_scan, double t_up, double t_inf) {
-    const bool prof = getenv("PJB_PROFILE_HOST") != nullptr;
-    auto now = [] { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
-    double t0 = now(), t_walk;
+// What a walk over the inflated bytes R found.  The records' offsets are in b_bam_rec.
+struct RecordWalk {
+    size_t n = 0;                   // records
+    uint32_t end_seg = 0xffffffffu; // the segment in which the target ended (a record of another target, or past the target's end)
+    uint32_t cut_seg = 0xffffffffu; // the first segment whose walk met a record the data ends in
+    iu64 next_u = 0;                // all: the first byte that belongs to no complete record (R.total: the data ends on a record's end)
+};
+
+// The one driver of the record kernels (pjb_ingest.hip.h): a start guessed per 64 KB segment, the walks from start to start counted and
+// verified (a start that a verified walk contradicts is replaced by the boundary that walk reached, at most 16 times), the segments behind
+// the stop trimmed, the counts scanned, the offsets filled in.  `all`: the indexer's walk -- records of every target, up to the record
+// the data ends in; else the records of target R.tid, up to the first record that is not the target's.  `where` places the errors.
+static int walk_records(pjb_ctx *c, const BamRegion &R, bool all, const char *where, RecordWalk &w) {
     hipStream_t st = c->stream;
     int rc;
-    // ---- record boundaries
-    BamRegion R;
-    R.U = d_out;
-    R.total = (iu64)total;
-    R.first = (iu64)first_uoffset;
-    R.tid = tid;
-    R.ref_len = c->ref_len[(size_t)tid];
-    R.n_ref = (int32_t)c->ref_len.size();
-    const uint32_t n_seg = (uint32_t)(((iu64)total + BAM_SEG - 1) / BAM_SEG);
+    const uint32_t NONE = 0xffffffffu;
+    const uint32_t n_seg = (uint32_t)((R.total + BAM_SEG - 1) / BAM_SEG);
+    const dim3 seg_grid((n_seg + 255) / 256), seg_block(256);
     // seg_start u64 | seg_base u64 | land u64 | seg_n u32
-    if ((rc = ensure(c, c->b_bam_seg, (size_t)n_seg * 28 + 64))) return rc;
-    if ((rc = ensure(c, c->b_bam_ctl, 64))) return rc;
+    if ((rc = ensure(c, c->b_bam_seg, (size_t)n_seg * 28 + 64)) || (rc = ensure(c, c->b_bam_ctl, 64))) return rc;
     iu64 *seg_start = (iu64 *)c->b_bam_seg.p;
     iu64 *seg_base = seg_start + n_seg;
     iu64 *land = seg_base + n_seg;
     iu32 *seg_n = (iu32 *)(land + n_seg);
-    iu32 *ctl = (iu32 *)c->b_bam_ctl.p; // [0..2] end / mismatch / bad segment, [4..5] u64 total of a scan
+    // [0] the target ended, [1] mismatch, [2] bad segment, [3] repair failed, [4..5] u64 total of the scan, [6] the data ends in a record
+    iu32 *ctl = (iu32 *)c->b_bam_ctl.p;
     iu64 *d_total = (iu64 *)(ctl + 4);
-    HIP_TRY(c, hipMemsetAsync(ctl, 0xff, 16, st));
     BamWalkOut O;
     O.seg_n = seg_n;
     O.land = land;
@@ -271,48 +312,69 @@ static int ingest_parse(pjb_ctx *c, int32_t tid, OpenContig &oc, const uint8_t *
         }
     }
     uint32_t h_ctl[8];
-    uint32_t end_seg = 0xffffffffu;
+    uint32_t stop = NONE; // the segment behind which nothing counts
     for (int attempt = 0;; attempt++) {
-        HIP_TRY(c, hipMemsetAsync(ctl, 0xff, 16, st));
-        HIP_TRY(c, hipMemsetAsync(ctl + 6, 0xff, 4, st));
-        LAUNCH(c, "bam_walk_count", bam_walk<false>, dim3((n_seg + 255) / 256), dim3(256), R, n_seg, (const iu64 *)seg_start, O);
+        HIP_TRY(c, hipMemsetAsync(ctl, 0xff, 32, st));
+        if (all) LAUNCH(c, "bam_walk_all_count", bam_walk_all<false>, seg_grid, seg_block, R, n_seg, (const iu64 *)seg_start, O);
+        else LAUNCH(c, "bam_walk_count", bam_walk<false>, seg_grid, seg_block, R, n_seg, (const iu64 *)seg_start, O);
         HIP_TRY(c, hipMemcpyAsync(h_ctl, ctl, 32, hipMemcpyDeviceToHost, st));
         HIP_TRY(c, hipStreamSynchronize(st));
-        end_seg = h_ctl[0];
-        if (h_ctl[2] != 0xffffffffu && h_ctl[2] <= end_seg && (h_ctl[1] == 0xffffffffu || h_ctl[2] <= h_ctl[1]))
-            return fail(c, PJB_ERR_BGZF, "Invalid BAM record layout on target %d (inflated offset %llu..)", tid,
-                        (unsigned long long)h_ctl[2] * BAM_SEG);
-        if (h_ctl[1] == 0xffffffffu || h_ctl[1] > end_seg) break; // every walk landed on the next start
+        stop = h_ctl[all ? 6 : 0];
+        if (h_ctl[2] != NONE && h_ctl[2] <= stop && (h_ctl[1] == NONE || h_ctl[2] <= h_ctl[1]))
+            return fail(c, PJB_ERR_BGZF, "Invalid BAM record layout %s (inflated offset %llu..)", where, (unsigned long long)h_ctl[2] * BAM_SEG);
+        if (h_ctl[1] == NONE || h_ctl[1] > stop) break; // every walk up to the stop landed on the next start
         // a guessed start was not a record boundary: replace it by the boundary the verified walk reached, walk again
         if (attempt >= 16)
-            return fail(c, PJB_ERR_BGZF, "BAM record chain of target %d is inconsistent near inflated offset %llu", tid,
-                        (unsigned long long)h_ctl[1] * BAM_SEG);
-        LAUNCH(c, "bam_repair_start", bam_repair_start, dim3(1), dim3(1), seg_start, n_seg, h_ctl[1], (const iu64 *)land, (iu64)total, ctl);
+            return fail(c, PJB_ERR_BGZF, "BAM record chain %s is inconsistent near inflated offset %llu", where, (unsigned long long)h_ctl[1] * BAM_SEG);
+        LAUNCH(c, "bam_repair_start", bam_repair_start, dim3(1), dim3(1), seg_start, n_seg, h_ctl[1], (const iu64 *)land, R.total, ctl);
         HIP_TRY(c, hipMemcpyAsync(h_ctl, ctl, 16, hipMemcpyDeviceToHost, st));
         HIP_TRY(c, hipStreamSynchronize(st));
-        if (h_ctl[3] != 0xffffffffu)
-            return fail(c, PJB_ERR_BGZF, "Invalid BAM record on target %d (inflated offset %llu..)", tid, (unsigned long long)h_ctl[3] * BAM_SEG);
+        if (h_ctl[3] != NONE) return fail(c, PJB_ERR_BGZF, "Invalid BAM record %s (inflated offset %llu..)", where, (unsigned long long)h_ctl[3] * BAM_SEG);
     }
+    w.end_seg = h_ctl[0];
+    w.cut_seg = h_ctl[6];
+    w.next_u = R.total;
+    if (stop != NONE) {
+        // what the segments behind the stop found are not records: they lie inside the cut record, or are not the target's
+        if (all) HIP_TRY(c, hipMemcpyAsync(ctl, &stop, 4, hipMemcpyHostToDevice, st)); // (bam_trim_segments reads ctl[0])
+        LAUNCH(c, "bam_trim_segments", bam_trim_segments, seg_grid, seg_block, seg_n, n_seg, (const iu32 *)ctl);
+        if (all) HIP_TRY(c, hipMemcpyAsync(&w.next_u, land + stop, 8, hipMemcpyDeviceToHost, st));
+    }
+    if ((rc = run_scan(c, "bam_seg", SegCountFn{seg_n}, SegBaseSink{seg_base}, n_seg, d_total))) return rc;
+    iu64 n64 = 0;
+    HIP_TRY(c, hipMemcpyAsync(&n64, d_total, 8, hipMemcpyDeviceToHost, st));
+    HIP_TRY(c, hipStreamSynchronize(st));
+    w.n = (size_t)n64;
+    if (n64 == 0 || n64 >= 0xffffff00ull) return PJB_OK; // (more than the callers take: nothing to fill)
+    if ((rc = ensure(c, c->b_bam_rec, w.n * 8))) return rc;
+    O.rec_off = (iu64 *)c->b_bam_rec.p;
+    if (all) LAUNCH(c, "bam_walk_all_fill", bam_walk_all<true>, seg_grid, seg_block, R, n_seg, (const iu64 *)seg_start, O);
+    else LAUNCH(c, "bam_walk_fill", bam_walk<true>, seg_grid, seg_block, R, n_seg, (const iu64 *)seg_start, O);
+    return PJB_OK;
+}
+
+// the inflated bytes of one target's region (d_out, `total` of them followed by 64 zero bytes) -> the SoA batch of the target
+static int ingest_parse(pjb_ctx *c, int32_t tid, OpenContig &oc, const uint8_t *d_out, size_t n_blocks, int64_t comp_bytes, int64_t total,
+                        int32_t first_uoffset, int64_t *n_records, double t_scan, double t_up, double t_inf) {
+    const bool prof = getenv("PJB_PROFILE_HOST") != nullptr;
+    double t0 = wall_now(), t_walk;
+    hipStream_t st = c->stream;
+    int rc;
+    const BamRegion R = bam_region(c, d_out, total, first_uoffset, tid);
+    RecordWalk w;
+    if ((rc = walk_records(c, R, false, ("on target " + std::to_string(tid)).c_str(), w))) return rc;
     // The data ends inside a record of this target and no record of another target (or past the target's end) was seen:
     // the bytes handed over stop short of the target's last alignment (a stale index, a truncated file).  The reference
     // fails on a truncated file too (bgzf_read / bam_read1); dropping the tail silently would change counts.
-    if (end_seg == 0xffffffffu && h_ctl[6] != 0xffffffffu)
+    if (w.end_seg == 0xffffffffu && w.cut_seg != 0xffffffffu)
         return fail(c, PJB_ERR_BGZF, "the data for target %d ends inside an alignment record (inflated offset %llu..): truncated "
-                                     "file, or the index's span for the target is too short", tid, (unsigned long long)h_ctl[6] * BAM_SEG);
-    LAUNCH(c, "bam_trim_segments", bam_trim_segments, dim3((n_seg + 255) / 256), dim3(256), seg_n, n_seg, (const iu32 *)ctl);
-    if ((rc = run_scan(c, "bam_seg", SegCountFn{seg_n}, SegBaseSink{seg_base}, n_seg, d_total))) return rc;
-    HIP_TRY(c, hipMemcpyAsync(h_ctl, ctl, 24, hipMemcpyDeviceToHost, st));
-    HIP_TRY(c, hipStreamSynchronize(st));
-    t_walk = now() - t0;
-    t0 = now();
-    iu64 n64;
-    memcpy(&n64, &h_ctl[4], 8);
-    if (n64 == 0) return PJB_OK;
-    if (n64 >= 0xffffff00ull) return fail(c, PJB_ERR_ARG, "submit_bam: more than 2^32 alignments on one target are not supported");
-    const size_t n = (size_t)n64;
-    if ((rc = ensure(c, c->b_bam_rec, n * 8))) return rc;
-    O.rec_off = (iu64 *)c->b_bam_rec.p;
-    LAUNCH(c, "bam_walk_fill", bam_walk<true>, dim3((n_seg + 255) / 256), dim3(256), R, n_seg, (const iu64 *)seg_start, O);
+                                     "file, or the index's span for the target is too short", tid, (unsigned long long)w.cut_seg * BAM_SEG);
+    t_walk = wall_now() - t0;
+    t0 = wall_now();
+    if (w.n == 0) return PJB_OK;
+    if (w.n >= 0xffffff00ull) return fail(c, PJB_ERR_ARG, "submit_bam: more than 2^32 alignments on one target are not supported");
+    const size_t n = w.n;
+    iu64 *d_total = (iu64 *)((iu32 *)c->b_bam_ctl.p + 4); // (the scans' total)
 
     // ---- SoA arrays in the target's slabs (same packing as a host-submitted batch)
     // (150-base paired-end records: fields + operations + 4- and 2-bit bases of the spliced third are 0.28 of the inflated bytes)
@@ -371,7 +433,7 @@ static int ingest_parse(pjb_ctx *c, int32_t tid, OpenContig &oc, const uint8_t *
     if (prof)
         fprintf(stderr, "[host profile] submit_bam tid %d: %zu blocks, %.1f MB -> %.1f MB, %zu records: header scan %.3f, upload %.3f, inflate %.3f, "
                         "boundaries %.3f, fill+sizes+transcode %.3f s\n",
-                tid, n_blocks, comp_bytes / 1e6, total / 1e6, n, t_scan, t_up, t_inf, t_walk, now() - t0);
+                tid, n_blocks, comp_bytes / 1e6, total / 1e6, n, t_scan, t_up, t_inf, t_walk, wall_now() - t0);
     DevBatch d;
     memset(&d, 0, sizeof d);
     d.n = (int64_t)n;
@@ -389,6 +451,17 @@ static int ingest_parse(pjb_ctx *c, int32_t tid, OpenContig &oc, const uint8_t *
     return PJB_OK;
 }
 
+// the part of pjb_submit_bam behind the upload: `d_comp` holds the target's BGZF bytes (padded), `blocks` their layout
+static int ingest_staged(pjb_ctx *c, int32_t tid, OpenContig &oc, const uint8_t *d_comp, const std::vector<InfBlock> &blocks, int64_t comp_bytes,
+                         int64_t total, int32_t first_uoffset, int64_t *n_records, double t_scan, double t_up) {
+    const double t0 = wall_now();
+    int rc;
+    if ((rc = ensure(c, c->b_inf_out, (size_t)total + 64))) return rc;
+    HIP_TRY(c, hipMemsetAsync((uint8_t *)c->b_inf_out.p + total, 0, 64, c->stream));
+    if ((rc = inflate_on_device(c, d_comp, blocks, (uint8_t *)c->b_inf_out.p))) return rc;
+    return ingest_parse(c, tid, oc, (const uint8_t *)c->b_inf_out.p, blocks.size(), comp_bytes, total, first_uoffset, n_records, t_scan, t_up, wall_now() - t0);
+}
+
 extern "C" int pjb_submit_bam(pjb_ctx *c, int32_t tid, const uint8_t *comp, int64_t comp_bytes, int32_t first_uoffset,
                               int64_t *n_records) {
     if (!c) return PJB_ERR_ARG;
@@ -400,28 +473,20 @@ extern "C" int pjb_submit_bam(pjb_ctx *c, int32_t tid, const uint8_t *comp, int6
     OpenContig &oc = c->open[tid];
     if (!oc.batches.empty()) return fail(c, PJB_ERR_STATE, "submit_bam: target %d already has batches (one call per target)", tid);
     const bool prof = getenv("PJB_PROFILE_HOST") != nullptr;
-    auto now = [] { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
-    double t0 = now(), t_scan, t_up;
+    double t0 = wall_now(), t_scan, t_up;
     std::vector<InfBlock> blocks;
     int64_t total = 0;
     int rc = scan_bgzf(c, comp, comp_bytes, blocks, total);
     if (rc) return rc;
     if (total == 0 || (int64_t)first_uoffset >= total) return PJB_OK;
-    t_scan = now() - t0;
-    t0 = now();
+    t_scan = wall_now() - t0;
+    t0 = wall_now();
     hipStream_t st = c->stream;
     if ((rc = ensure(c, c->b_inf_comp, (size_t)comp_bytes + INF_PAD))) return rc;
-    {
-        // page-locked input (pjb_host_alloc): one DMA, no staging copy
-        hipPointerAttribute_t at;
-        const bool pinned = hipPointerGetAttributes(&at, comp) == hipSuccess && at.type == hipMemoryTypeHost;
-        if (!pinned) (void)hipGetLastError();
-        if (pinned) HIP_TRY(c, hipMemcpyAsync(c->b_inf_comp.p, comp, (size_t)comp_bytes, hipMemcpyHostToDevice, st));
-        else if ((rc = upload_staged(c, c->b_inf_comp.p, comp, (size_t)comp_bytes))) return rc;
-    }
+    if ((rc = upload_host(c, c->b_inf_comp.p, comp, (size_t)comp_bytes))) return rc;
     HIP_TRY(c, hipMemsetAsync((uint8_t *)c->b_inf_comp.p + comp_bytes, 0, INF_PAD, st));
     if (prof) (void)hipStreamSynchronize(st);
-    t_up = now() - t0;
+    t_up = wall_now() - t0;
     return ingest_staged(c, tid, oc, (const uint8_t *)c->b_inf_comp.p, blocks, comp_bytes, total, first_uoffset, n_records, t_scan, t_up);
 }
 
@@ -477,8 +542,7 @@ static void stage_release(pjb_ctx *c, BamStage &st) { // (after the work that us
 static void inflate_early(pjb_ctx *c, BamStage &st) {
     const size_t nb = st.blocks.size();
     if (st.launched || nb == 0 || st.total_out <= 0) return;
-    size_t lanes = std::min<size_t>((nb + 63) / 64 * 64, (size_t)c->inflate_lanes);
-    if (const char *e = getenv("PJB_INF_BLOCKS_PER_LAUNCH")) lanes = std::min<size_t>((nb + 63) / 64 * 64, (size_t)std::max(64, atoi(e)) / 64 * 64);
+    const size_t lanes = inflate_lanes(c, nb);
     if (pool_take(c, c->out_pool, st.out, (size_t)st.total_out + 64) || pool_take(c, c->misc_pool, st.d_blocks, nb * sizeof(InfBlock)) ||
         pool_take(c, c->misc_pool, st.d_status, nb * 4 + 16) || pool_take(c, c->misc_pool, st.d_scratch, lanes * INF_SCRATCH_PER_LANE) ||
         pool_take(c, c->out_pool, st.d_bitmap, nb * INF_BITMAP_WORDS * 8)) {
@@ -496,25 +560,11 @@ static void inflate_early(pjb_ctx *c, BamStage &st) {
         if (hipStreamCreateWithPriority(&is, hipStreamNonBlocking, lo) != hipSuccess) return;
     }
     if (hipEventCreateWithFlags(&st.ev_last, hipEventDisableTiming) != hipSuccess || hipEventCreateWithFlags(&st.ev_inf, hipEventDisableTiming) != hipSuccess) return;
-    int *d_status = (int *)st.d_status.p;
-    int *d_any = d_status + nb;
-    iu32 *d_next = (iu32 *)(d_any + 1);
-    st.ctl[0] = 0u;
-    st.ctl[1] = (iu32)lanes;
-    bool ok = hipEventRecord(st.ev_last, c->stream_up) == hipSuccess && hipStreamWaitEvent(is, st.ev_last, 0) == hipSuccess &&
-              hipMemsetAsync((uint8_t *)st.out.p + st.total_out, 0, 64, is) == hipSuccess &&
-              hipMemcpyAsync(st.d_blocks.p, st.blocks.data(), nb * sizeof(InfBlock), hipMemcpyHostToDevice, is) == hipSuccess &&
-              hipMemcpyAsync(d_any, st.ctl, 8, hipMemcpyHostToDevice, is) == hipSuccess;
-    if (ok) {
-        ok = hipMemsetAsync(st.d_bitmap.p, 0, nb * INF_BITMAP_WORDS * 8, is) == hipSuccess;
-        if (ok) {
-            hipLaunchKernelGGL(bgzf_decode, dim3((unsigned)(lanes / 64)), dim3(64), I3_LDS_BYTES, is, (const uint8_t *)st.dev.p, (const InfBlock *)st.d_blocks.p,
-                               (iu32)nb, (uint8_t *)st.out.p, (uint8_t *)st.d_scratch.p, d_status, d_any, d_next, (iu64 *)st.d_bitmap.p, 8);
-            hipLaunchKernelGGL(bgzf_resolve, dim3((unsigned)((nb + 3) / 4)), dim3(256), 0, is, (const InfBlock *)st.d_blocks.p, (iu32)nb, (uint8_t *)st.out.p,
-                               (const iu64 *)st.d_bitmap.p, (const int *)d_status);
-            ok = hipGetLastError() == hipSuccess && hipEventRecord(st.ev_inf, is) == hipSuccess;
-        }
-    }
+    const bool ok = hipEventRecord(st.ev_last, c->stream_up) == hipSuccess && hipStreamWaitEvent(is, st.ev_last, 0) == hipSuccess &&
+                    hipMemsetAsync((uint8_t *)st.out.p + st.total_out, 0, 64, is) == hipSuccess &&
+                    inflate_queue(c, is, (const uint8_t *)st.dev.p, st.blocks, lanes, st.ctl, st.d_blocks, st.d_status, st.d_scratch, st.d_bitmap,
+                                  (uint8_t *)st.out.p) == hipSuccess &&
+                    hipEventRecord(st.ev_inf, is) == hipSuccess;
     if (!ok) { // whatever was queued must be over before the buffers are used again
         (void)hipStreamSynchronize(is);
         (void)hipGetLastError();
@@ -526,52 +576,20 @@ static void inflate_early(pjb_ctx *c, BamStage &st) {
 // block headers that are complete with the bytes received so far (the last `avail` bytes of the stream are at `p`, the
 // first of them is byte `p_at` of the target's bytes); leaves st.next at the first block it cannot finish yet
 static int stage_scan(pjb_ctx *c, BamStage &st, const uint8_t *p, int64_t p_at, int64_t avail) {
-    auto byte_at = [&](int64_t off) -> int { // a byte of the stream that is still in reach (this piece or the kept tail)
-        if (off >= p_at && off < p_at + avail) return p[off - p_at];
-        if (off >= st.keep_at && off < st.keep_at + st.keep_n) return st.keep[off - st.keep_at];
-        return -1;
-    };
-    const int64_t end = p_at + avail;
+    // what lies before this piece is in the kept tail, which ends where the piece begins
+    if (st.next < p_at && (st.next < st.keep_at || st.keep_at + st.keep_n != p_at))
+        return fail(c, PJB_ERR_STATE, "bam_piece: internal: header byte %lld out of reach", (long long)st.next);
+    auto byte_at = [&](int64_t off) { return off >= p_at ? p[off - p_at] : st.keep[off - st.keep_at]; };
     while (st.next < st.total) {
-        const int64_t off = st.next;
-        if (off + 18 > end) break;
-        uint8_t h[18];
-        for (int k = 0; k < 18; k++) {
-            const int v = byte_at(off + k);
-            if (v < 0) return fail(c, PJB_ERR_STATE, "bam_piece: internal: header byte %lld out of reach", (long long)(off + k));
-            h[k] = (uint8_t)v;
-        }
-        if (h[0] != 31 || h[1] != 139 || h[2] != 8 || !(h[3] & 4)) return fail(c, PJB_ERR_BGZF, "not a BGZF block header at byte %lld", (long long)off);
-        const uint32_t xlen = h[10] | (uint32_t)h[11] << 8;
-        if (off + 12 + xlen > end) break;
-        int64_t bsize = -1;
-        for (uint32_t x = 0; x + 4 <= xlen;) {
-            int f[6];
-            for (int k = 0; k < 6; k++) f[k] = x + (uint32_t)k < xlen ? byte_at(off + 12 + x + k) : 0;
-            if (f[0] < 0 || f[1] < 0 || f[2] < 0 || f[3] < 0) return fail(c, PJB_ERR_STATE, "bam_piece: internal: extra field out of reach");
-            const uint32_t slen = (uint32_t)f[2] | (uint32_t)f[3] << 8;
-            if (f[0] == 'B' && f[1] == 'C' && slen == 2 && x + 6 <= xlen) bsize = (int64_t)((uint32_t)f[4] | (uint32_t)f[5] << 8) + 1;
-            x += 4 + slen;
-        }
-        if (bsize < 0) return fail(c, PJB_ERR_BGZF, "BGZF block at byte %lld has no BC field", (long long)off);
-        if (bsize < (int64_t)xlen + 20 || off + bsize > st.total)
-            return fail(c, PJB_ERR_BGZF, "BGZF block at byte %lld has an impossible size %lld", (long long)off, (long long)bsize);
-        if (off + bsize > end) break; // its footer has not arrived
-        uint32_t isize = 0;
-        for (int k = 0; k < 4; k++) {
-            const int v = byte_at(off + bsize - 4 + k);
-            if (v < 0) return fail(c, PJB_ERR_STATE, "bam_piece: internal: footer byte out of reach");
-            isize |= (uint32_t)v << (8 * k);
-        }
-        if (isize > 65536u) return fail(c, PJB_ERR_BGZF, "BGZF block at byte %lld declares %u inflated bytes", (long long)off, isize);
         InfBlock b;
-        b.in_off = (iu64)(off + 12 + xlen);
-        b.in_len = (iu32)(bsize - xlen - 20);
+        int64_t bsize = 0;
+        const int rc = bgzf_header(c, byte_at, st.next, p_at + avail, st.total, b, bsize);
+        if (rc > 0) break; // the rest of it has not arrived
+        if (rc) return rc;
         b.out_off = (iu64)st.total_out;
-        b.out_len = isize;
         st.blocks.push_back(b);
-        st.total_out += isize;
-        st.next = off + bsize;
+        st.total_out += b.out_len;
+        st.next += bsize;
     }
     return PJB_OK;
 }
@@ -607,18 +625,8 @@ extern "C" int pjb_bam_begin(pjb_ctx *c, int32_t tid, int64_t total_bytes) {
     HIP_TRY(c, hipSetDevice(c->cfg.device));
     std::unique_ptr<BamStage> st(new (std::nothrow) BamStage());
     if (!st) return fail(c, PJB_ERR_NOMEM, "bam_begin: out of host memory");
-    // device buffer: the smallest free one of the pool that fits, else a new one
-    const size_t need = (size_t)total_bytes + INF_PAD;
-    int best = -1;
-    for (size_t k = 0; k < c->stage_pool.size(); k++)
-        if (c->stage_pool[k].cap >= need && (best < 0 || c->stage_pool[k].cap < c->stage_pool[(size_t)best].cap)) best = (int)k;
-    if (best >= 0) {
-        st->dev = c->stage_pool[(size_t)best];
-        c->stage_pool.erase(c->stage_pool.begin() + best);
-    } else {
-        int rc = ensure(c, st->dev, need);
-        if (rc) return rc;
-    }
+    int rc = pool_take(c, c->stage_pool, st->dev, (size_t)total_bytes + INF_PAD);
+    if (rc) return rc;
     st->total = total_bytes;
     hipError_t he = hipSuccess;
     if (!c->stream_up) he = hipStreamCreateWithFlags(&c->stream_up, hipStreamNonBlocking);
@@ -653,8 +661,7 @@ extern "C" int pjb_bam_piece(pjb_ctx *c, int32_t tid, const uint8_t *piece, int6
 static int bam_piece_body(pjb_ctx *c, int32_t tid, BamStage &st, const uint8_t *piece, int64_t bytes, int64_t *ticket) {
     if (st.got + bytes > st.total) return fail(c, PJB_ERR_ARG, "bam_piece: target %d: more bytes than announced", tid);
     HIP_TRY(c, hipSetDevice(c->cfg.device));
-    auto now = [] { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
-    double t0 = now();
+    double t0 = wall_now();
     // the copy first (asynchronous, on the upload stream), the header hop meanwhile
     HIP_TRY(c, hipMemcpyAsync((uint8_t *)st.dev.p + st.got, piece, (size_t)bytes, hipMemcpyHostToDevice, c->stream_up));
     const int64_t tk = ++c->up_ticket;
@@ -665,8 +672,8 @@ static int bam_piece_body(pjb_ctx *c, int32_t tid, BamStage &st, const uint8_t *
         c->up_done = std::max<int64_t>(c->up_done, tk - (int64_t)PJB_UP_EVENTS);
     }
     HIP_TRY(c, hipEventRecord(ev, c->stream_up));
-    st.t_up += now() - t0;
-    t0 = now();
+    st.t_up += wall_now() - t0;
+    t0 = wall_now();
     int rc = stage_scan(c, st, piece, st.got, bytes);
     if (rc) return rc;
     st.got += bytes;
@@ -686,7 +693,7 @@ static int bam_piece_body(pjb_ctx *c, int32_t tid, BamStage &st, const uint8_t *
         st.keep_n = n;
     } else
         st.keep_n = 0;
-    st.t_scan += now() - t0;
+    st.t_scan += wall_now() - t0;
     if (ticket) *ticket = tk;
     if (st.got == st.total && st.next == st.total) inflate_early(c, st);
     return PJB_OK;
@@ -746,13 +753,12 @@ extern "C" int pjb_bam_end(pjb_ctx *c, int32_t tid, int32_t first_uoffset, int64
     if (!oc.batches.empty()) return fail(c, PJB_ERR_STATE, "bam_end: target %d already has batches (one call per target)", tid);
     if (st->total_out == 0 || (int64_t)first_uoffset >= st->total_out) return PJB_OK;
     if (st->launched) { // the inflate started with the last piece: wait for it, look at its status words, go on with the records
-        auto now = [] { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
-        const double t0 = now();
+            const double t0 = wall_now();
         HIP_TRY(c, hipEventSynchronize(st->ev_inf));
         int rc = inflate_status(c, st->blocks, (const int *)st->d_status.p);
         if (rc) return rc;
         return ingest_parse(c, tid, oc, (const uint8_t *)st->out.p, st->blocks.size(), st->total, st->total_out, first_uoffset, n_records, st->t_scan, st->t_up,
-                            now() - t0);
+                            wall_now() - t0);
     }
     // the service stream picks up behind the last copy
     if (!c->ev_up) HIP_TRY(c, hipEventCreateWithFlags(&c->ev_up, hipEventDisableTiming));
@@ -833,74 +839,6 @@ extern "C" int pjb_index_begin(pjb_ctx *c) {
     return PJB_OK;
 }
 
-// the record boundaries of every record that lies completely in the inflated bytes: rec_off in b_bam_rec, their number in n, the
-// offset of the first byte that belongs to none of them in next_u (== total: the data ends on a record's end)
-static int index_walk(pjb_ctx *c, const uint8_t *d_out, int64_t total, int32_t first_uoffset, size_t &n, iu64 &next_u) {
-    hipStream_t st = c->stream;
-    int rc;
-    BamRegion R;
-    R.U = d_out;
-    R.total = (iu64)total;
-    R.first = (iu64)first_uoffset;
-    R.tid = -1;
-    R.ref_len = 0;
-    R.n_ref = (int32_t)c->ref_len.size();
-    const uint32_t n_seg = (uint32_t)(((iu64)total + BAM_SEG - 1) / BAM_SEG);
-    if ((rc = ensure(c, c->b_bam_seg, (size_t)n_seg * 28 + 64))) return rc;
-    if ((rc = ensure(c, c->b_bam_ctl, 64))) return rc;
-    iu64 *seg_start = (iu64 *)c->b_bam_seg.p;
-    iu64 *seg_base = seg_start + n_seg;
-    iu64 *land = seg_base + n_seg;
-    iu32 *seg_n = (iu32 *)(land + n_seg);
-    iu32 *ctl = (iu32 *)c->b_bam_ctl.p; // as ingest_parse: [1] mismatch, [2] bad segment, [3] repair failed, [4..5] scan total, [6] data ends in a record
-    iu64 *d_total = (iu64 *)(ctl + 4);
-    BamWalkOut O;
-    O.seg_n = seg_n;
-    O.land = land;
-    O.rec_off = nullptr;
-    O.seg_base = seg_base;
-    O.ctl = ctl;
-    LAUNCH(c, "bam_find_starts", bam_find_starts, dim3(n_seg), dim3(64), R, n_seg, seg_start);
-    uint32_t h_ctl[8];
-    uint32_t cut_seg = 0xffffffffu; // the segment whose walk met the record the data ends in
-    for (int attempt = 0;; attempt++) {
-        HIP_TRY(c, hipMemsetAsync(ctl, 0xff, 32, st));
-        LAUNCH(c, "bam_walk_all_count", bam_walk_all<false>, dim3((n_seg + 255) / 256), dim3(256), R, n_seg, (const iu64 *)seg_start, O);
-        HIP_TRY(c, hipMemcpyAsync(h_ctl, ctl, 32, hipMemcpyDeviceToHost, st));
-        HIP_TRY(c, hipStreamSynchronize(st));
-        cut_seg = h_ctl[6];
-        if (h_ctl[2] != 0xffffffffu && h_ctl[2] <= cut_seg && (h_ctl[1] == 0xffffffffu || h_ctl[2] <= h_ctl[1]))
-            return fail(c, PJB_ERR_BGZF, "Invalid BAM record layout (inflated offset %llu.. of the piece)", (unsigned long long)h_ctl[2] * BAM_SEG);
-        if (h_ctl[1] == 0xffffffffu || h_ctl[1] > cut_seg) break; // every walk up to the cut landed on the next start
-        if (attempt >= 16)
-            return fail(c, PJB_ERR_BGZF, "BAM record chain is inconsistent near inflated offset %llu of the piece", (unsigned long long)h_ctl[1] * BAM_SEG);
-        LAUNCH(c, "bam_repair_start", bam_repair_start, dim3(1), dim3(1), seg_start, n_seg, h_ctl[1], (const iu64 *)land, (iu64)total, ctl);
-        HIP_TRY(c, hipMemcpyAsync(h_ctl, ctl, 16, hipMemcpyDeviceToHost, st));
-        HIP_TRY(c, hipStreamSynchronize(st));
-        if (h_ctl[3] != 0xffffffffu)
-            return fail(c, PJB_ERR_BGZF, "Invalid BAM record (inflated offset %llu.. of the piece)", (unsigned long long)h_ctl[3] * BAM_SEG);
-    }
-    next_u = (iu64)total;
-    if (cut_seg != 0xffffffffu) {
-        // what the segments behind the cut found lies inside the cut record: not records
-        HIP_TRY(c, hipMemcpyAsync(ctl, &cut_seg, 4, hipMemcpyHostToDevice, st));
-        LAUNCH(c, "bam_trim_segments", bam_trim_segments, dim3((n_seg + 255) / 256), dim3(256), seg_n, n_seg, (const iu32 *)ctl);
-        HIP_TRY(c, hipMemcpyAsync(&next_u, land + cut_seg, 8, hipMemcpyDeviceToHost, st));
-    }
-    if ((rc = run_scan(c, "bam_seg", SegCountFn{seg_n}, SegBaseSink{seg_base}, n_seg, d_total))) return rc;
-    iu64 n64 = 0;
-    HIP_TRY(c, hipMemcpyAsync(&n64, d_total, 8, hipMemcpyDeviceToHost, st));
-    HIP_TRY(c, hipStreamSynchronize(st));
-    n = 0;
-    if (n64 == 0) return PJB_OK;
-    if (n64 >= 0xffffff00ull) return fail(c, PJB_ERR_ARG, "index_piece: more than 2^32 alignments in one piece are not supported");
-    n = (size_t)n64;
-    if ((rc = ensure(c, c->b_bam_rec, n * 8))) return rc;
-    O.rec_off = (iu64 *)c->b_bam_rec.p;
-    LAUNCH(c, "bam_walk_all_fill", bam_walk_all<true>, dim3((n_seg + 255) / 256), dim3(256), R, n_seg, (const iu64 *)seg_start, O);
-    return PJB_OK;
-}
-
 // a chunk list that must hold `need` chunks: a larger buffer takes over what the list holds
 static int index_grow_chunks(pjb_ctx *c, IndexState *x, size_t need) {
     if (need * sizeof(BaiChunk) <= x->chunks.cap && x->chunks.p) return PJB_OK;
@@ -948,16 +886,17 @@ static int index_piece_body(pjb_ctx *c, IndexState *x, const uint8_t *comp, int6
     hipStream_t st = c->stream;
     if ((int64_t)first_uoffset < total) {
         if ((rc = ensure(c, c->b_inf_comp, (size_t)comp_bytes + INF_PAD))) return rc;
-        hipPointerAttribute_t at; // page-locked input: one DMA, no staging copy (as pjb_submit_bam)
-        const bool pinned = hipPointerGetAttributes(&at, comp) == hipSuccess && at.type == hipMemoryTypeHost;
-        if (!pinned) (void)hipGetLastError();
-        if (pinned) HIP_TRY(c, hipMemcpyAsync(c->b_inf_comp.p, comp, (size_t)comp_bytes, hipMemcpyHostToDevice, st));
-        else if ((rc = upload_staged(c, c->b_inf_comp.p, comp, (size_t)comp_bytes))) return rc;
+        if ((rc = upload_host(c, c->b_inf_comp.p, comp, (size_t)comp_bytes))) return rc;
         HIP_TRY(c, hipMemsetAsync((uint8_t *)c->b_inf_comp.p + comp_bytes, 0, INF_PAD, st));
         if ((rc = ensure(c, c->b_inf_out, (size_t)total + 64))) return rc;
         HIP_TRY(c, hipMemsetAsync((uint8_t *)c->b_inf_out.p + total, 0, 64, st));
         if ((rc = inflate_on_device(c, (const uint8_t *)c->b_inf_comp.p, blocks, (uint8_t *)c->b_inf_out.p))) return rc;
-        if ((rc = index_walk(c, (const uint8_t *)c->b_inf_out.p, total, first_uoffset, n, next_u))) return rc;
+        // every record that lies completely in the inflated bytes, of whatever target
+        RecordWalk w;
+        if ((rc = walk_records(c, bam_region(c, (const uint8_t *)c->b_inf_out.p, total, first_uoffset, -1), true, "in the piece", w))) return rc;
+        if (w.n >= 0xffffff00ull) return fail(c, PJB_ERR_ARG, "index_piece: more than 2^32 alignments in one piece are not supported");
+        n = w.n;
+        next_u = w.next_u;
     }
     if (next_u < (iu64)total) { // the data ends inside a record
         if (last) return fail(c, PJB_ERR_BGZF, "the data ends inside an alignment record (virtual offset 0x%llx): truncated file", (unsigned long long)voffset_of(next_u));

@@ -56,6 +56,19 @@ def test_bytes_equal_write_bam(ctx, mixed, block_size):
     assert sum(len(c) > 1 for c in bins.values()) > 10
 
 
+@pytest.mark.parametrize("seg", [1, 2, 5])
+def test_false_record_start_is_repaired(mixed, monkeypatch, seg):
+    """The indexer's record walk repairs a guessed start that is not a boundary (the PJB_TEST_FALSE_START hook moves the start
+    of one 64 KB segment by a byte), as the ingest's does: in one piece the input is 14 segments, and the index is the same."""
+    p = mixed[0xFF00]
+    monkeypatch.setenv("PJB_TEST_FALSE_START", str(seg))
+    with ffi.Context(flags=ffi.FLAG_KERNEL_TIMING | ffi.FLAG_NO_CHAINS) as c:
+        got, res = device_bai(c, p, len(im.MIXED_REFS), None)
+        assert "bam_repair_start" in c.kernel_timing()  # (the hook was not inert)
+    assert got == open(p + ".bai", "rb").read()
+    assert res["n_records"] == len(im.mixed_reads())
+
+
 # ---- 2. the cut does not matter
 def test_the_cut_does_not_matter(ctx, mixed):
     p = mixed[777]

@@ -505,5 +505,6 @@ def test_false_record_start_is_repaired(orc, tmp_path, monkeypatch, seg):
     path = str(tmp_path / "f.bam")
     write_bam(path, [("chr1", len(genome))], rs)
     monkeypatch.setenv("PJB_TEST_FALSE_START", str(seg))
-    with ffi.Context(0, "UNKNOWN") as ctx:
+    with ffi.Context(0, "UNKNOWN", flags=ffi.FLAG_KERNEL_TIMING) as ctx:
         assert run_targets_from_bam(ctx, orc, path, {0: genome.encode()}) > 10
+        assert "bam_repair_start" in ctx.kernel_timing()  # (the hook was not inert)
