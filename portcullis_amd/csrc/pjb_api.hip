@@ -814,7 +814,7 @@ static int queue_contig(pjb_ctx *c, Flight &f) {
         if (xk1) {
             const size_t N = (size_t)f.n_reads;
             if ((rc = ensure(c, S.x_q, N + 16)) || (rc = ensure(c, S.x_spos, N * 4 + 16)) || (rc = ensure(c, S.x_send, N * 4 + 16)) ||
-                (rc = ensure(c, S.x_zlist, (size_t)X_ZCAP * 4)) || (rc = ensure(c, S.x_scnt, X_SCNT_BYTES)))
+                (rc = ensure(c, S.x_zlist, (size_t)X_ZCAP * 8)) || (rc = ensure(c, S.x_scnt, X_SCNT_BYTES)))
                 return rc;
             HIP_TRY(c, hipMemsetAsync((uint8_t *)S.x_q.p + N, 0, 1, c->stream));
             HIP_TRY(c, hipMemsetAsync(S.x_scnt.p, 0, sizeof(SparseCounters) + sizeof(ExtraCounters), c->stream));

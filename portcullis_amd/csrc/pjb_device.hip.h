@@ -578,17 +578,57 @@ struct SparseCounters { // one per target, device memory (zeroed)
     u32 n_zero;       // unspliced mapped records with no reference-consuming op (zlist entries)
     u32 max_span;     // longest reference span of an unspliced mapped record
     u32 max_gap;      // longest D operation among them
-    u32 need_dense;   // bit 0: the pileup cap may bite; bit 1: a record with more than 126 gaps; bit 2: gap list full
+    u32 need_dense;   // bit 0: the pileup cap may bite; bit 1: a record with more than 126 gaps; bit 2: gap list full;
+                      // bit 3: a span leaves its member (chains of several members only)
     u64 total;        // written by the scan: unspliced records with a span | gaps << 32
 };
 constexpr u32 SPARSE_GAP_MAX = 126;
 struct XOut {
     int32_t *s_pos, *s_end; // per record (global ordinal): position, exclusive end of the span (= pos: no span / not unspliced.bam)
     uint8_t *q;             // bit 0: has a span, bits 1-7: D operations
-    u32 *zlist;
-    u32 zcap;
+    u32 *zlist;             // the unspliced records without a span, two words an entry: its position in its member at [z], the member at
+    u32 zcap;               // [zcap + z] (two plain word stores: as one 8-byte store they cost k1_count<true> 16 more spilled registers)
     SparseCounters *cnt;
 };
+// The one classification of the sparse path: a record's part in unspliced.bam (junction_builder.cc:168-186).  Record `g` of its
+// chain starts at `pos`, covers `aligned` bases of the reference and has `ngap` D operations, the longest of `gapmax` bases; it
+// belongs to member `member`, which lies at `voff` in the chain's virtual sequence and has `len` bases (a lone target: member 0
+// at 0).  Positions and ends are written in virtual coordinates, so that the spans of a whole chain are one position-sorted list; a
+// record without a span keeps its own position beside its member.  With several members (`many_members`, uniform) a span that
+// leaves its member would reach into the gap behind it or into the next member and is reported; a lone target's may leave it.
+struct XLane { // what a lane's records add to the SparseCounters (x_counters)
+    u32 span = 0, gapmax = 0; // longest span, longest D operation of a record with a span
+    bool many = false;        // a record with more than SPARSE_GAP_MAX gaps
+    bool leaves = false;      // a span that leaves its member
+};
+__device__ __forceinline__ void x_classify(const XOut &X, u32 g, int32_t pos, int32_t aligned, u32 ngap, u32 gapmax, bool spliced, u32 flag,
+                                           int32_t voff, int32_t len, u32 member, bool many_members, XLane &a) {
+    const bool unspliced = !spliced && !(flag & 0x4u);
+    const bool spans = unspliced && aligned > 0 && pos >= 0;
+    const int32_t vpos = (int32_t)((u32)pos + (u32)voff);
+    X.s_pos[g] = vpos;
+    X.s_end[g] = spans ? vpos + aligned : vpos;
+    if (!spans) ngap = 0, gapmax = 0;
+    if (ngap > SPARSE_GAP_MAX) a.many = true, ngap = SPARSE_GAP_MAX;
+    X.q[g] = (uint8_t)((spans ? 1u : 0u) | (ngap << 1));
+    if (spans) a.span = max(a.span, (u32)aligned);
+    a.gapmax = max(a.gapmax, gapmax);
+    if (many_members && spans && (int64_t)pos + aligned > (int64_t)len) a.leaves = true;
+    if (unspliced && aligned == 0) { // getEnd() == pos - 1: tested one by one by the flank kernels (practically never)
+        const u32 z = atomicAdd(&X.cnt->n_zero, 1u);
+        if (z < X.zcap) X.zlist[z] = (u32)pos, X.zlist[X.zcap + z] = member;
+    }
+}
+// the lanes' contributions into the counters; every lane of the wavefront calls this
+__device__ __forceinline__ void x_counters(SparseCounters *cnt, const XLane &a) {
+    const u32 span = wave_max(a.span), gapmax = wave_max(a.gapmax);
+    if (lane_id() == 0) { // (look first: the maxima settle after a few waves)
+        if (span > cnt->max_span) atomicMax(&cnt->max_span, span);
+        if (gapmax > cnt->max_gap) atomicMax(&cnt->max_gap, gapmax);
+    }
+    if (a.many) atomicOr(&cnt->need_dense, 2u);
+    if (a.leaves) atomicOr(&cnt->need_dense, 8u);
+}
 
 // what k5_finalize and kg_features (pjb_extra.hip.h) both do to a target's bases
 __device__ __forceinline__ uint8_t revcomp_char(uint8_t c) { // REVCOMP_LOOKUP seq_utils.hpp:33-40 (NUL outside A-Z)

@@ -18,6 +18,26 @@
 
 namespace pjb {
 
+// a record's M / = / X runs, clipped to the target, into the depth difference array (sign -1: out of it again)
+__device__ __forceinline__ void depth_runs(const u32 *cigar, u32 c0, u32 c1, int32_t pos, int32_t ref_len, int32_t *dd, int32_t sign) {
+    int32_t x = pos;
+    for (u32 k = c0; k < c1; k++) {
+        const u32 op = cigar[k];
+        const u32 ty = op & 15u;
+        const int32_t ln = (int32_t)(op >> 4);
+        if (ty == OP_M || ty == OP_EQ || ty == OP_X) {
+            int32_t a = x, bb = x + ln;
+            if (a < 0) a = 0;
+            if (bb > ref_len) bb = ref_len;
+            if (a < bb) {
+                atomicAdd(&dd[a], sign);
+                atomicAdd(&dd[bb], -sign);
+            }
+        }
+        if (op_consumes_ref(ty)) x += ln;
+    }
+}
+
 // KX1: one thread per record (every record of the contig).  Classifies the record as the reference's
 // separateBams does, records its position / exclusive end for the rank queries, counts its end in `ce`
 // and adds its M / = / X runs to the depth difference array; the name codes of spliced records are appended
@@ -53,22 +73,7 @@ __global__ __launch_bounds__(256) void kx_classify(DevBatch b, int32_t ref_len, 
             int32_t e = pos + aligned - 1; // getEnd()
             if (e > ref_len) e = ref_len;
             atomicAdd(&ce[e], 1u);
-            int32_t x = pos;
-            for (u32 k = c0; k < c1; k++) {
-                const u32 op = b.cigar[k];
-                const u32 ty = op & 15u;
-                const int32_t ln = (int32_t)(op >> 4);
-                if (ty == OP_M || ty == 7u || ty == 8u) {
-                    int32_t a = x, bb = x + ln;
-                    if (a < 0) a = 0;
-                    if (bb > ref_len) bb = ref_len;
-                    if (a < bb) {
-                        atomicAdd(&dd[a], 1);
-                        atomicAdd(&dd[bb], -1);
-                    }
-                }
-                if (op_consumes_ref(ty)) x += ln;
-            }
+            depth_runs(b.cigar, c0, c1, pos, ref_len, dd, 1);
         }
     }
 }
@@ -178,22 +183,7 @@ __global__ void kx_cap_replay(const int32_t *x_pos, const int32_t *x_endx, const
 __global__ __launch_bounds__(256) void kx_undo_dropped(DevBatch b, int32_t ref_len, const uint8_t *dropped, int32_t *dd) {
     const int64_t r = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (r >= b.n || !dropped[b.base + (u32)r]) return;
-    int32_t x = b.pos[r];
-    for (u32 k = b.cig_off[r]; k < b.cig_off[r + 1]; k++) {
-        const u32 op = b.cigar[k];
-        const u32 ty = op & 15u;
-        const int32_t ln = (int32_t)(op >> 4);
-        if (ty == OP_M || ty == 7u || ty == 8u) {
-            int32_t a = x, bb = x + ln;
-            if (a < 0) a = 0;
-            if (bb > ref_len) bb = ref_len;
-            if (a < bb) {
-                atomicAdd(&dd[a], -1);
-                atomicAdd(&dd[bb], 1);
-            }
-        }
-        if (op_consumes_ref(ty)) x += ln;
-    }
+    depth_runs(b.cigar, b.cig_off[r], b.cig_off[r + 1], b.pos[r], ref_len, dd, -1);
 }
 
 __device__ __forceinline__ u32 lower_bound_i32(const int32_t *a, u32 n, int32_t v) { // first index with a[i] >= v
@@ -266,65 +256,32 @@ __global__ __launch_bounds__(256) void kx_pair_codes(const u32 *sidx, const u32 
 //   htslib's 8000-record cap (kx_cap_*) is only possible where 7999 consecutive unspliced records start within max_span
 // bases (kx_cap_check); such a target -- and one with more gaps than the list holds -- goes through the dense path
 // above instead.
-// (SparseCounters, XOut: pjb_kernels.hip.h -- k1_count writes them when the records go through it; kx_classify_sparse is
-// the same classification for the records of a target that went through k1_walk)
-//   GROUP: the batch belongs to member `member` of a group (pjb_finish_group_begin), which lies at `voff` in the group's virtual
-// sequence and has `len` bases.  Positions and ends are written in virtual coordinates, so that the spans of the whole group are one
-// position-sorted list (members in the order of their offsets, records in file order inside a member); a record without a span keeps
-// its member beside its position (two words per zlist entry).  A record with a span that leaves its member's sequence would reach
-// into the gap behind it or the next member: the group is then taken apart (need_dense bit 3) and its members go one by one.
-template <bool GROUP>
-__global__ __launch_bounds__(256) void kx_classify_sparse(DevBatch b, int32_t voff, int32_t len, u32 member, int32_t *s_pos, int32_t *s_end,
-                                                           uint8_t *q_flag, u32 *zlist, u32 zcap, SparseCounters *cnt) {
+//   A chain of several targets (a group, pjb_finish_group_begin) is ONE such target in the coordinates of its virtual sequence: member m
+// lies at voff[m] there, positions and ends are kept in virtual coordinates, and the spans of the whole chain are one position-sorted
+// list (members in the order of their offsets, records in file order inside a member).  A lone target is the chain of one member at 0.
+//   The classification itself is x_classify (pjb_device.hip.h).  A lone target's records get it inside the chain's k1_count, which has
+// every CIGAR in registers anyway; kx_classify_sparse does the same for the batches of a chain of several members, whose k1_count does
+// not.  There a span that leaves its member's sequence takes the group apart (need_dense bit 3): its members then go one by one.
+__global__ __launch_bounds__(256) void kx_classify_sparse(DevBatch b, int32_t voff, int32_t len, bool many_members, XOut X) {
     const int64_t r = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    u32 span = 0, gapmax = 0;
-    bool many = false, leaves = false;
+    XLane a;
     if (r < b.n) {
-        const u32 g = b.base + (u32)r;
-        const u32 c0 = b.cig_off[r], c1 = b.cig_off[r + 1];
-        const int32_t pos = b.pos[r];
-        const int32_t vpos = GROUP ? (int32_t)((u32)pos + (u32)voff) : pos;
         int32_t aligned = 0;
-        u32 ngap = 0;
+        u32 ngap = 0, gapmax = 0;
         bool spliced = false;
-        for (u32 k = c0; k < c1; k++) {
+        for (u32 k = b.cig_off[r]; k < b.cig_off[r + 1]; k++) {
             const u32 op = b.cigar[k];
             const u32 ty = op & 15u;
             if (ty == OP_N) spliced = true;
-            if (op_consumes_ref(ty)) {
-                aligned += (int32_t)(op >> 4);
-                if (ty == 2u && (op >> 4)) { // D: inside the span, no depth
-                    ngap++;
-                    gapmax = max(gapmax, op >> 4);
-                }
+            if (op_consumes_ref(ty)) aligned += (int32_t)(op >> 4);
+            if (ty == OP_D && (op >> 4)) { // inside the span, no depth
+                ngap++;
+                gapmax = max(gapmax, op >> 4);
             }
         }
-        const bool mapped = !(b.flag[r] & 0x4u);
-        const bool unspliced = !spliced && mapped;
-        const bool spans = unspliced && aligned > 0 && pos >= 0;
-        s_pos[g] = vpos;
-        s_end[g] = spans ? vpos + aligned : vpos;
-        if (GROUP && spans && (int64_t)pos + aligned > (int64_t)len) leaves = true;
-        if (!spans) ngap = 0, gapmax = 0;
-        if (ngap > SPARSE_GAP_MAX) many = true, ngap = SPARSE_GAP_MAX;
-        q_flag[g] = (uint8_t)((spans ? 1u : 0u) | (ngap << 1));
-        if (spans) span = (u32)aligned;
-        if (unspliced && aligned == 0) {
-            const u32 z = atomicAdd(&cnt->n_zero, 1u);
-            if (z < zcap) {
-                if (GROUP) zlist[2 * (size_t)z] = (u32)pos, zlist[2 * (size_t)z + 1] = member;
-                else zlist[z] = (u32)pos;
-            }
-        }
+        x_classify(X, b.base + (u32)r, b.pos[r], aligned, ngap, gapmax, spliced, b.flag[r], voff, len, (u32)b.member, many_members, a);
     }
-    span = wave_max(span);
-    gapmax = wave_max(gapmax);
-    if (lane_id() == 0) { // (look first: the maxima settle after a few waves)
-        if (span > cnt->max_span) atomicMax(&cnt->max_span, span);
-        if (gapmax > cnt->max_gap) atomicMax(&cnt->max_gap, gapmax);
-    }
-    if (many) atomicOr(&cnt->need_dense, 2u);
-    if (GROUP && leaves) atomicOr(&cnt->need_dense, 8u);
+    x_counters(X.cnt, a);
 }
 
 // one scan over the records: (records with a span) | (gaps) << 32
@@ -439,49 +396,9 @@ __device__ __forceinline__ void ranges_sum2(u32 i0, u32 i1, const Win w, F acc, 
     }
 }
 
-// KX4 without the ends histogram: a thread per junction.
-//   #{getEnd() < x} = (records with a span that start before x - max_span: all of them) + (those among the records starting
-//   in [x - max_span, x) whose last base lies before x); a record starting at or after x ends at or after x.
-__global__ __launch_bounds__(256) void kx_flank_sparse(const pjb_junction_row *rows, u32 n_rows, const int32_t *s_pos, const int32_t *s_end,
-                                                        int32_t ref_len, const u32 *zlist, const SparseCounters *cnt, u32 zcap, ExtraRow *out) {
-    const u32 n_reads = (u32)cnt->total; // (s_pos / s_end: the records with a span only, in rank order)
-    const u32 j = blockIdx.x * 256 + threadIdx.x;
-    const bool on = j < n_rows;
-    int32_t s = 0, e = 0, l = 0, r = 0;
-    if (on) s = rows[j].start, e = rows[j].end, l = rows[j].left, r = rows[j].right;
-    auto before = [&](int32_t v) -> u32 { return lower_bound_i32(s_pos, n_reads, v); }; // #{pos < v}
-    const int32_t lc = l < 0 ? 0 : (l > ref_len + 1 ? ref_len + 1 : l);
-    u32 ended = 0, i0 = 0, i1 = 0;
-    if (on) {
-        if (lc == ref_len + 1) ended = n_reads; // (the histogram clamps every end to ref_len)
-        else {
-            i0 = lower_bound_i64(s_pos, n_reads, (int64_t)lc - (int64_t)cnt->max_span);
-            i1 = lower_bound_i32(s_pos, n_reads, lc);
-            ended = i0;
-        }
-    }
-    u32 part = 0, unused = 0;
-    ranges_sum2(i0, i1, Win{lc, 0, 0, 0}, [&](u32 i, const Win w, u32 &a, u32 &) {
-        if (s_end[i] - 1 < w.p1lo) a++;
-    }, part, unused);
-    if (!on) return;
-    const int32_t rr = flank_right(r, ref_len);
-    u32 up = before(s) - (ended + part);
-    u32 down = rr > e ? before(rr + 1) - before(e + 1) : 0u;
-    u32 nz = cnt->n_zero;
-    if (nz > zcap) nz = zcap;
-    for (u32 k = 0; k < nz; k++) {
-        const int32_t pos = (int32_t)zlist[k], end = pos - 1;
-        if (s > pos && l <= end) up++;
-        if (rr >= pos && e < pos) down++;
-    }
-    out[j].up_aln = up;
-    out[j].down_aln = down;
-}
-
 // The spans of a group's members per member, from the compacted list: member m's records are those whose virtual position lies in
-// [voff[m], voff[m + 1]) -- a record with a span starts inside its member (kx_classify_sparse<true> sends a group with one that does not
-// through its members one by one).  One wavefront, a lane per member.
+// [voff[m], voff[m + 1]) -- a record with a span starts inside its member (a group with one that does not goes
+// through its members one by one: need_dense bit 3).  One wavefront, a lane per member.
 __global__ __launch_bounds__(64) void kx_member_spans(const int32_t *s_pos, const SparseCounters *cnt, XMembers M, GroupCounters *out) {
     const u32 n_reads = (u32)cnt->total;
     const int m = (int)threadIdx.x;
@@ -498,15 +415,20 @@ __global__ __launch_bounds__(64) void kx_member_spans(const int32_t *s_pos, cons
     }
 }
 
-// kx_flank_sparse for the rows of a whole group: s_pos / s_end hold the spans of every member in the coordinates of the group's virtual
-// sequence, the rows carry their target (refid) and its own coordinates.  A row finds its member in M, applies the reference's clamps in
-// the member's coordinates and searches in virtual ones; since a member's records start inside it, a position clamped to [0, len + 1]
-// separates them exactly as the unclamped one does for a target finished alone.
+// KX4 without the ends histogram: a thread per junction, for the rows of a whole chain.
+//   #{getEnd() < x} = (records with a span that start before x - max_span: all of them) + (those among the records starting
+//   in [x - max_span, x) whose last base lies before x); a record starting at or after x ends at or after x.
+// s_pos / s_end hold the spans of every member in the coordinates of the chain's virtual sequence, the rows carry their target (refid)
+// and its own coordinates.  A row finds its member in M, applies the reference's clamps in the member's coordinates and searches in
+// virtual ones.  A row lies inside its target (a junction that reaches past the end stops the chain: PJB_ERR_SPLICE_SITE_LEN), so the
+// positions searched for -- start, end + 1, flank_right + 1 -- are inside [0, len + 1] already; the clamp only says so.
 //   The records of EARLIER members start before every position of this one and end inside their own member: they are counted by
 // before(s) and by `ended` alike -- among the records before the search window, or inside it with their last base before the anchor --
 // and cancel in `up`; in `down` they are in both terms.  A LATER member's records start behind voff + len + 1 (the gap between members
-// is 4096 bases) and are in neither.  max_span is the group's maximum: a larger one only widens the window that is walked.
-__global__ __launch_bounds__(256) void kx_flank_group(const pjb_junction_row *rows, u32 n_rows, const int32_t *s_pos, const int32_t *s_end, XMembers M,
+// is 4096 bases) and are in neither.  max_span is the chain's maximum: a larger one only widens the window that is walked.  A lone
+// target is the chain with M.n == 1: no other member, offset 0 -- and its records may start or end past its end, which no searched
+// position reaches.
+__global__ __launch_bounds__(256) void kx_flank_sparse(const pjb_junction_row *rows, u32 n_rows, const int32_t *s_pos, const int32_t *s_end, XMembers M,
                                                        const u32 *zlist, const SparseCounters *cnt, u32 zcap, ExtraRow *out) {
     const u32 n_reads = (u32)cnt->total;
     const u32 j = blockIdx.x * 256 + threadIdx.x;
@@ -543,8 +465,8 @@ __global__ __launch_bounds__(256) void kx_flank_group(const pjb_junction_row *ro
     u32 nz = cnt->n_zero;
     if (nz > zcap) nz = zcap;
     for (u32 k = 0; k < nz; k++) {
-        if (zlist[2 * (size_t)k + 1] != member) continue;
-        const int32_t pos = (int32_t)zlist[2 * (size_t)k], end = pos - 1;
+        if (zlist[zcap + k] != member) continue;
+        const int32_t pos = (int32_t)zlist[k], end = pos - 1;
         if (s > pos && l <= end) up++;
         if (rr >= pos && e < pos) down++;
     }

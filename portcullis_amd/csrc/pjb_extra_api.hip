@@ -3,11 +3,28 @@
 #include "pjb_host.hip.h"
 #include "pjb_extra.hip.h"
 
-static int extra_contig_dense(pjb_ctx *c, int32_t tid, std::vector<DevBatch> &batches, int64_t n_reads, u64 n_spliced, u32 P, u32 J,
-                              const u32 *sidx, const u32 *jid_sorted, const u32 *pair_g, size_t row_base, bool codes_in_table) {
+// The name codes of a chain's spliced records, in BAM order, to `codes`; their number to cnt->n_spliced.  Through the tile lists the
+// chain's first kernels left in its slot (tile numbers run through the chain).
+static int spliced_codes(pjb_ctx *c, const Flight &f, ExtraCounters *cnt, u64 *codes) {
+    CtlSlot &S = c->sl[f.slot];
+    u32 n_tiles = 0;
+    for (auto &b : f.batches) n_tiles = std::max<u32>(n_tiles, b.tile_base + (u32)((b.n + K1_TILE - 1) / K1_TILE));
+    int rc;
+    if ((rc = ensure(c, c->x_tileoff, (size_t)n_tiles * 4 + 16))) return rc;
+    LAUNCH(c, "kx_spliced_offsets", kx_spliced_offsets, dim3(1), dim3(1024), (const TileStats *)S.tile_stats.p, n_tiles, (u32 *)c->x_tileoff.p, cnt);
+    for (auto &b : f.batches)
+        LAUNCH(c, "kx_spliced_codes", kx_spliced_codes, dim3((unsigned)((b.n + K1_TILE - 1) / K1_TILE)), dim3(256), b, (const TileStats *)S.tile_stats.p,
+               (const u32 *)S.splidx.p, (const u32 *)c->x_tileoff.p, codes);
+    return PJB_OK;
+}
+
+// a lone target through the depth vector (the dense path of pjb_extra.hip.h)
+static int extra_contig_dense(pjb_ctx *c, Flight &f, u64 n_spliced, u32 P, u32 J, size_t row_base, bool codes_in_table) {
     hipStream_t st = c->stream;
+    const int32_t tid = f.tid;
+    std::vector<DevBatch> &batches = f.batches;
     const int32_t L = c->ref_len[(size_t)tid];
-    const size_t N = (size_t)n_reads;
+    const size_t N = (size_t)f.n_reads;
     ExtraContig X;
     X.dense = true;
     X.codes_in_table = codes_in_table;
@@ -53,16 +70,7 @@ static int extra_contig_dense(pjb_ctx *c, int32_t tid, std::vector<DevBatch> &ba
     for (auto &b : batches)
         LAUNCH(c, "kx_classify", kx_classify, dim3((unsigned)((b.n + 255) / 256)), dim3(256), b, L, x_pos, x_endx, x_q, ce,
                (int32_t *)X.cover, (u32 *)c->x_zlist.p, X_ZCAP, d_cnt);
-    {   // the spliced records' name codes, through the tile lists the contig's first kernels left in its slot
-        CtlSlot &S = c->sl[c->cur_slot];
-        u32 n_tiles = 0;
-        for (auto &b : batches) n_tiles = std::max<u32>(n_tiles, b.tile_base + (u32)((b.n + K1_TILE - 1) / K1_TILE));
-        if ((rc = ensure(c, c->x_tileoff, (size_t)n_tiles * 4 + 16))) return rc;
-        LAUNCH(c, "kx_spliced_offsets", kx_spliced_offsets, dim3(1), dim3(1024), (const TileStats *)S.tile_stats.p, n_tiles, (u32 *)c->x_tileoff.p, d_cnt);
-        for (auto &b : batches)
-            LAUNCH(c, "kx_spliced_codes", kx_spliced_codes, dim3((unsigned)((b.n + K1_TILE - 1) / K1_TILE)), dim3(256), b, (const TileStats *)S.tile_stats.p,
-                   (const u32 *)S.splidx.p, (const u32 *)c->x_tileoff.p, X.spl_codes);
-    }
+    if ((rc = spliced_codes(c, f, d_cnt, X.spl_codes))) return rc;
     if ((rc = run_scan(c, "kx_ends", ArrU32Fn{ce}, ExclusiveU32Sink{ce}, (u64)L + 2, (u64 *)c->b_xtotal.p))) return rc;
     if ((rc = run_scan(c, "kx_unspl", ArrU8Fn{x_q}, ExclusiveU32Sink{prefq}, (u64)N + 1, (u64 *)c->b_xtotal.p))) return rc;
     LAUNCH(c, "kx_cap_bound", kx_cap_bound, dim3((unsigned)((N + 255) / 256)), dim3(256), (const int32_t *)x_pos, (const uint8_t *)x_q,
@@ -94,12 +102,12 @@ static int extra_contig_dense(pjb_ctx *c, int32_t tid, std::vector<DevBatch> &ba
     if (J > 0) {
         if (hipMalloc((void **)&X.xr, (size_t)J * sizeof(ExtraRow)) != hipSuccess) return fail(c, PJB_ERR_NOMEM, "extra: rows of target %d", tid);
         HIP_TRY(c, hipMemsetAsync(X.xr, 0, (size_t)J * sizeof(ExtraRow), st));
-        LAUNCH(c, "kx_flank", kx_flank, dim3((J + 255) / 256), dim3(256), (const pjb_junction_row *)c->sl[c->cur_slot].rows.p, J, (const int32_t *)x_pos,
+        LAUNCH(c, "kx_flank", kx_flank, dim3((J + 255) / 256), dim3(256), (const pjb_junction_row *)c->sl[f.slot].rows.p, J, (const int32_t *)x_pos,
                (u32)N, (const u32 *)prefq, (const u32 *)ce, L, (const u32 *)c->x_zlist.p, (const ExtraCounters *)d_cnt, X_ZCAP, X.xr);
         if (hipMalloc((void **)&X.pair_code, (size_t)P * 8) != hipSuccess || hipMalloc((void **)&X.pair_row, (size_t)P * 4) != hipSuccess)
             return fail(c, PJB_ERR_NOMEM, "extra: pair codes of target %d", tid);
-        LAUNCH(c, "kx_pair_codes", kx_pair_codes, dim3((P + 255) / 256), dim3(256), sidx, jid_sorted, pair_g,
-               (const DevBatch *)c->sl[c->cur_slot].batches.p, (int)batches.size(), P, (u32)row_base, X.pair_code, X.pair_row);
+        LAUNCH(c, "kx_pair_codes", kx_pair_codes, dim3((P + 255) / 256), dim3(256), f.sidx, f.jid_sorted, f.pr.g,
+               (const DevBatch *)c->sl[f.slot].batches.p, (int)batches.size(), P, (u32)row_base, X.pair_code, X.pair_row);
     }
     HIP_TRY(c, hipStreamSynchronize(st));
     if (c->ktime) ev_collect(c, MISC_POOL);
@@ -152,15 +160,13 @@ static int name_table_insert(pjb_ctx *c, const u64 *codes, u32 n) {
     return PJB_OK;
 }
 
-// The same per-target work without an array of the target's length (pjb_extra.hip.h, "the sparse path"), in two parts.
-// extra_pre needs the records only: queued on the service stream when the target's chain is queued, it runs beside the
-// chains.  extra_contig needs the chain's rows and sorted pairs: queued when the chain is collected, beside the chains of
-// the targets queued after this one; one wait at its end.  A target where the pileup's cap may bite goes through
-// extra_contig_dense instead.
-//   A GROUP (several targets finished as one chain) is one such target in the coordinates of its virtual sequence: its records are
-// classified with their member's offset added, one scan compacts the spans of all members, and extra_contig answers the rows of all
-// members in one launch.  The launches here depend on the number of batches, as a single target's do, not on the number of members.
-// A group in which the sparse answer does not stand (extra_group_apart) is taken apart by its caller, member by member.
+// The same work without an array of the target's length (pjb_extra.hip.h, "the sparse path"), in two parts, for a CHAIN: a lone
+// target, or a group of targets finished as one chain -- one such target in the coordinates of its virtual sequence (members_of; a lone
+// target is the chain of one member at offset 0).  extra_pre needs the records only: queued on the service stream when the chain is
+// queued, it runs beside the chains.  extra_contig needs the chain's rows and sorted pairs: queued when the chain is collected, beside
+// the chains queued after this one; one wait at its end.  The launches depend on the number of batches, not on the number of members.
+//   Where the sparse answer does not stand (SparseCounters::need_dense) a lone target goes through extra_contig_dense instead; a group
+// (extra_group_apart) is taken apart by its caller, and its members come back here one by one.
 static XMembers members_of(const pjb_ctx *c, const Flight &f) {
     XMembers M;
     memset(&M, 0, sizeof M);
@@ -187,24 +193,23 @@ int extra_pre(pjb_ctx *c, Flight &f) {
     if (!f.x_spos || !f.x_send || !f.x_gapoff || !f.x_gaps)
         return fail(c, PJB_ERR_NOMEM, "extra: no device memory for what target %d keeps (%zu records)", f.tid, N);
     if ((rc = ensure(c, S.x_q, N + 16)) || (rc = ensure(c, S.x_spos, N * 4 + 16)) || (rc = ensure(c, S.x_send, N * 4 + 16)) ||
-        (rc = ensure(c, S.x_gapoff, (N / 256 + 2) * 4)) || (rc = ensure(c, S.x_zlist, (size_t)X_ZCAP * (group ? 8 : 4))) ||
+        (rc = ensure(c, S.x_gapoff, (N / 256 + 2) * 4)) || (rc = ensure(c, S.x_zlist, (size_t)X_ZCAP * 8)) ||
         (rc = ensure(c, S.x_scnt, X_SCNT_BYTES)))
         return rc;
     uint8_t *q = (uint8_t *)S.x_q.p;
     SparseCounters *d_cnt = (SparseCounters *)S.x_scnt.p;
     if (f.x_k1) HIP_TRY(c, hipStreamWaitEvent(st, S.ev_xk1, 0)); // (the chain's k1_count classified the records)
     else {
+        // Only a group comes here.  queue_chain calls queue_contig first, and queue_contig has k1_count classify the records of every lone
+        // target of a context that gets this far (no "extra_dense") the first time its chain is queued: x_k1 is set, a repeat keeps it, and
+        // the members of a group that came apart are fresh flights that go through queue_contig like any other.
+        const XOut xo{(int32_t *)S.x_spos.p, (int32_t *)S.x_send.p, q, (u32 *)S.x_zlist.p, X_ZCAP, d_cnt};
         HIP_TRY(c, hipMemsetAsync(q + N, 0, 1, st));
         HIP_TRY(c, hipMemsetAsync(d_cnt, 0, sizeof(SparseCounters) + sizeof(ExtraCounters), st));
-        for (auto &b : f.batches) {
-            if (b.n <= 0) continue;
-            if (group)
-                LAUNCH(c, "kx_classify_group", kx_classify_sparse<true>, dim3((unsigned)((b.n + 255) / 256)), dim3(256), b, f.voff[(size_t)b.member],
-                       c->ref_len[(size_t)f.tids[(size_t)b.member]], (u32)b.member, (int32_t *)S.x_spos.p, (int32_t *)S.x_send.p, q, (u32 *)S.x_zlist.p, X_ZCAP, d_cnt);
-            else
-                LAUNCH(c, "kx_classify_sparse", kx_classify_sparse<false>, dim3((unsigned)((b.n + 255) / 256)), dim3(256), b, 0, 0, 0u, (int32_t *)S.x_spos.p,
-                       (int32_t *)S.x_send.p, q, (u32 *)S.x_zlist.p, X_ZCAP, d_cnt);
-        }
+        for (auto &b : f.batches)
+            if (b.n > 0)
+                LAUNCH(c, "kx_classify_sparse", kx_classify_sparse, dim3((unsigned)((b.n + 255) / 256)), dim3(256), b, f.voff[(size_t)b.member],
+                       c->ref_len[(size_t)f.tids[(size_t)b.member]], group, xo);
     }
     if ((rc = run_scan(c, "kx_spans", SparseFn{q},
                        SparseSink{f.x_spos, f.x_send, (u32 *)S.x_gapoff.p, f.x_gapoff, (const int32_t *)S.x_spos.p, (const int32_t *)S.x_send.p, q}, (u64)N + 1,
@@ -214,12 +219,12 @@ int extra_pre(pjb_ctx *c, Flight &f) {
         if (b.n > 0)
         {
             const u32 nblk = (u32)((((u64)b.base + (u64)b.n + 255) >> 8) - (b.base >> 8));
-            LAUNCH(c, "kx_gaps", kx_gaps, dim3(std::min<u32>(nblk, 2048)), dim3(256), b, group ? f.voff[(size_t)b.member] : 0, (const uint8_t *)q, (u32)N,
+            LAUNCH(c, "kx_gaps", kx_gaps, dim3(std::min<u32>(nblk, 2048)), dim3(256), b, f.voff[(size_t)b.member], (const uint8_t *)q, (u32)N,
                    (const u32 *)S.x_gapoff.p, f.x_gaps, f.x_gap_cap, d_cnt, nblk);
         }
     if (N >= PLP_MAXCNT)
         LAUNCH(c, "kx_cap_check", kx_cap_check, dim3((unsigned)((N + 255) / 256)), dim3(256), (const int32_t *)f.x_spos, d_cnt);
-    if (group)
+    if (group) // (which members have records with a span; a lone target has if there are any: extra_contig)
         LAUNCH(c, "kx_member_spans", kx_member_spans, dim3(1), dim3(64), (const int32_t *)f.x_spos, (const SparseCounters *)d_cnt, members_of(c, f),
                (GroupCounters *)((uint8_t *)S.x_scnt.p + sizeof(SparseCounters) + sizeof(ExtraCounters)));
     f.x_pre = true;
@@ -244,141 +249,91 @@ int extra_group_apart(pjb_ctx *c, Flight &f, bool *apart) {
     return PJB_OK;
 }
 
-// the rows part for a group: what extra_contig does for one target, once for all members, and one ExtraContig per member -- the
-// hand-over of the coverage in pjb_extra_finish goes target by target -- that share the group's records
-static int extra_contig_group(pjb_ctx *c, Flight &f, const pjb_region_result *res, u64 n_spliced, u32 P, u32 J, size_t row_base) {
+// The rows part, once for the whole chain, and one ExtraContig per member -- the hand-over of the coverage in pjb_extra_finish goes
+// target by target -- that share the chain's records.
+int extra_contig(pjb_ctx *c, Flight &f, const pjb_region_result *res, u64 n_spliced, u32 P, u32 J, size_t row_base) {
+    if (c->extra_dense_only) return extra_contig_dense(c, f, n_spliced, P, J, row_base, false); // (lone targets only: begin_flight)
     int rc;
     if ((rc = extra_pre(c, f))) return rc;
     hipStream_t st = c->stream;
     CtlSlot &S = c->sl[f.slot];
     const size_t n_members = f.tids.size();
-    u64 pairs = 0, juncs = 0;
-    for (size_t m = 0; m < n_members; m++) pairs += (u64)res[m].n_pairs, juncs += (u64)res[m].n_junctions;
-    if (pairs != P || juncs != J)
-        return fail(c, PJB_ERR_STATE, "extra: the members of the group from target %d hold %llu pairs / %llu junctions, the chain %u / %u", f.tid,
-                    (unsigned long long)pairs, (unsigned long long)juncs, P, J);
+    const bool lone = n_members == 1;
+    const char *who = lone ? "target" : "the group from target";
+    // rows and sorted pairs are in the order of the junction ids, member after member: how many each member holds (a lone target: all)
+    std::vector<std::pair<size_t, u32>> share(n_members, std::make_pair((size_t)J, P));
+    if (!lone) {
+        u64 pairs = 0, juncs = 0;
+        for (size_t m = 0; m < n_members; m++) {
+            share[m] = std::make_pair((size_t)res[m].n_junctions, (u32)res[m].n_pairs);
+            pairs += (u64)res[m].n_pairs, juncs += (u64)res[m].n_junctions;
+        }
+        if (pairs != P || juncs != J)
+            return fail(c, PJB_ERR_STATE, "extra: the members of the group from target %d hold %llu pairs / %llu junctions, the chain %u / %u", f.tid,
+                        (unsigned long long)pairs, (unsigned long long)juncs, P, J);
+    }
     ExtraRow *xr = J ? (ExtraRow *)xarena_alloc(c, (size_t)J * sizeof(ExtraRow)) : nullptr;
     u64 *pair_code = J ? (u64 *)xarena_alloc(c, (size_t)P * 8 + 16) : nullptr;
     u32 *pair_row = J ? (u32 *)xarena_alloc(c, (size_t)P * 4 + 16) : nullptr;
-    if (J && (!xr || !pair_code || !pair_row)) return fail(c, PJB_ERR_NOMEM, "extra: no device memory for the pairs of the group from target %d", f.tid);
+    if (J && (!xr || !pair_code || !pair_row)) return fail(c, PJB_ERR_NOMEM, "extra: no device memory for the pairs of %s %d", who, f.tid);
     if ((rc = ensure(c, S.x_codes, std::max<size_t>((size_t)n_spliced, 1) * 8))) return rc;
+    const bool xtrace = getenv("PJB_XTRACE") != nullptr;
+    auto xt0 = std::chrono::steady_clock::now();
+    XTRACE("post: pre-part done");
     SparseCounters *d_cnt = (SparseCounters *)S.x_scnt.p;
-    ExtraCounters *d_xcnt = (ExtraCounters *)(d_cnt + 1);
-    {   // the spliced records' name codes (tile numbers run through the group) -> the name table
-        u32 n_tiles = 0;
-        for (auto &b : f.batches) n_tiles = std::max<u32>(n_tiles, b.tile_base + (u32)((b.n + K1_TILE - 1) / K1_TILE));
-        if ((rc = ensure(c, c->x_tileoff, (size_t)n_tiles * 4 + 16))) return rc;
-        LAUNCH(c, "kx_spliced_offsets", kx_spliced_offsets, dim3(1), dim3(1024), (const TileStats *)S.tile_stats.p, n_tiles, (u32 *)c->x_tileoff.p, d_xcnt);
-        for (auto &b : f.batches)
-            LAUNCH(c, "kx_spliced_codes", kx_spliced_codes, dim3((unsigned)((b.n + K1_TILE - 1) / K1_TILE)), dim3(256), b, (const TileStats *)S.tile_stats.p,
-                   (const u32 *)S.splidx.p, (const u32 *)c->x_tileoff.p, (u64 *)S.x_codes.p);
-        if ((rc = name_table_insert(c, (const u64 *)S.x_codes.p, (u32)n_spliced))) return rc;
-    }
+    // the spliced records' name codes -> the name table
+    if ((rc = spliced_codes(c, f, (ExtraCounters *)(d_cnt + 1), (u64 *)S.x_codes.p))) return rc;
+    XTRACE("post: codes");
+    if ((rc = name_table_insert(c, (const u64 *)S.x_codes.p, (u32)n_spliced))) return rc;
+    XTRACE("post: insert");
     if (J > 0) {
         HIP_TRY(c, hipMemsetAsync(xr, 0, (size_t)J * sizeof(ExtraRow), st));
-        LAUNCH(c, "kx_flank_group", kx_flank_group, dim3((J + 255) / 256), dim3(256), (const pjb_junction_row *)S.rows.p, J, (const int32_t *)f.x_spos,
+        LAUNCH(c, "kx_flank_sparse", kx_flank_sparse, dim3((J + 255) / 256), dim3(256), (const pjb_junction_row *)S.rows.p, J, (const int32_t *)f.x_spos,
                (const int32_t *)f.x_send, members_of(c, f), (const u32 *)S.x_zlist.p, (const SparseCounters *)d_cnt, X_ZCAP, xr);
         LAUNCH(c, "kx_pair_codes", kx_pair_codes, dim3((P + 255) / 256), dim3(256), f.sidx, f.jid_sorted, f.pr.g, (const DevBatch *)S.batches.p,
                (int)f.batches.size(), P, (u32)row_base, pair_code, pair_row);
     }
+    // one wait: the counters decide whether the sparse answer stands
     SparseCounters &hc = *(SparseCounters *)(S.pub + PUB_XCNT_AT);
     ExtraCounters &hx = *(ExtraCounters *)(S.pub + PUB_XCNT_AT + sizeof(SparseCounters));
     GroupCounters &hg = *(GroupCounters *)(S.pub + PUB_XCNT_AT + sizeof(SparseCounters) + sizeof(ExtraCounters));
+    XTRACE("post: flank + pair codes");
     HIP_TRY(c, hipMemcpyAsync(&hc, d_cnt, X_SCNT_BYTES, hipMemcpyDeviceToHost, st));
     HIP_TRY(c, hipStreamSynchronize(st));
+    XTRACE("post: counters");
     if (c->ktime) ev_collect(c, MISC_POOL);
+    // What depends on the number of members, all of it here.  A lone target with more records without a span than the list holds is
+    // refused, and one that needs the depth vector -- the pileup's cap may bite, or the gap list is too small -- gets it; for a group
+    // extra_group_apart has said no to both before anything was committed.  Whether a member has unspliced records with a span: a lone
+    // target has if the chain has any, a group's members were asked by kx_member_spans (extra_pre).
+    if (lone && hc.n_zero > X_ZCAP)
+        return fail(c, PJB_ERR_ARG, "extra: target %d has %u mapped records without a reference span (limit %u)", f.tid, hc.n_zero, X_ZCAP);
     if (hx.n_spliced != (u32)n_spliced)
-        return fail(c, PJB_ERR_STATE, "extra: the group from target %d: %u spliced records in the tile lists, the chain counted %llu", f.tid, hx.n_spliced,
+        return fail(c, PJB_ERR_STATE, "extra: %s %d: %u spliced records in the tile lists, the chain counted %llu", who, f.tid, hx.n_spliced,
                     (unsigned long long)n_spliced);
-    if (hc.need_dense || hc.n_zero > X_ZCAP) // (extra_group_apart has said no)
-        return fail(c, PJB_ERR_STATE, "extra: the group from target %d needs the depth vector", f.tid);
+    if (lone && hc.need_dense) return extra_contig_dense(c, f, n_spliced, P, J, row_base, true);
+    if (hc.need_dense || hc.n_zero > X_ZCAP) return fail(c, PJB_ERR_STATE, "extra: the group from target %d needs the depth vector", f.tid);
+    const u32 has_spans = lone ? ((u32)hc.total > 0 ? 1u : 0u) : hg.has_spans;
     const SparseDepth D{f.x_spos, f.x_send, f.x_gaps, f.x_gapoff, (u32)hc.total, (u32)(hc.total >> 32), hc.max_span, hc.max_gap};
-    size_t row_at = 0, pair_at = 0; // (rows and sorted pairs are in the order of the junction ids: member after member)
+    size_t row_at = 0, pair_at = 0;
     for (size_t m = 0; m < n_members; m++) {
         ExtraContig X;
         X.tid = f.tids[m];
         X.len = c->ref_len[(size_t)X.tid];
         X.voff = f.voff[m];
         X.row_base = row_base + row_at;
-        X.n_rows = (size_t)res[m].n_junctions;
-        X.n_pairs = (u32)res[m].n_pairs;
+        X.n_rows = share[m].first;
+        X.n_pairs = share[m].second;
         X.xr = X.n_rows ? xr + row_at : nullptr;
         X.pair_code = X.n_rows ? pair_code + pair_at : nullptr;
         X.pair_row = X.n_rows ? pair_row + pair_at : nullptr;
         X.codes_in_table = true;
-        X.has_unspliced = (hg.has_spans >> m) & 1u;
+        X.has_unspliced = (has_spans >> m) & 1u;
         X.sparse = D;
         row_at += X.n_rows;
         pair_at += X.n_pairs;
         c->xc.push_back(X);
     }
-    return PJB_OK;
-}
-
-int extra_contig(pjb_ctx *c, Flight &f, const pjb_region_result *res, u64 n_spliced, u32 P, u32 J, size_t row_base) {
-    if (f.tids.size() > 1) return extra_contig_group(c, f, res, n_spliced, P, J, row_base);
-    const int32_t tid = f.tid;
-    std::vector<DevBatch> &batches = f.batches;
-    if (c->extra_dense_only) return extra_contig_dense(c, tid, batches, f.n_reads, n_spliced, P, J, f.sidx, f.jid_sorted, f.pr.g, row_base, false);
-    int rc;
-    if ((rc = extra_pre(c, f))) return rc;
-    hipStream_t st = c->stream;
-    const int32_t L = c->ref_len[(size_t)tid];
-    CtlSlot &S = c->sl[f.slot];
-    ExtraContig X;
-    X.tid = tid;
-    X.len = L;
-    X.row_base = row_base;
-    X.n_rows = J;
-    X.n_pairs = P;
-    X.xr = J ? (ExtraRow *)xarena_alloc(c, (size_t)J * sizeof(ExtraRow)) : nullptr;
-    X.pair_code = J ? (u64 *)xarena_alloc(c, (size_t)P * 8 + 16) : nullptr;
-    X.pair_row = J ? (u32 *)xarena_alloc(c, (size_t)P * 4 + 16) : nullptr;
-    if (J && (!X.xr || !X.pair_code || !X.pair_row)) return fail(c, PJB_ERR_NOMEM, "extra: no device memory for the pairs of target %d", tid);
-    if ((rc = ensure(c, S.x_codes, std::max<size_t>((size_t)n_spliced, 1) * 8))) return rc;
-    const bool xtrace = getenv("PJB_XTRACE") != nullptr;
-    auto xt0 = std::chrono::steady_clock::now();
-    XTRACE("post: pre-part done");
-    SparseCounters *d_cnt = (SparseCounters *)S.x_scnt.p;
-    ExtraCounters *d_xcnt = (ExtraCounters *)(d_cnt + 1);
-    {   // the spliced records' name codes, through the tile lists the target's first kernels left in its slot -> the name table
-        u32 n_tiles = 0;
-        for (auto &b : batches) n_tiles = std::max<u32>(n_tiles, b.tile_base + (u32)((b.n + K1_TILE - 1) / K1_TILE));
-        if ((rc = ensure(c, c->x_tileoff, (size_t)n_tiles * 4 + 16))) return rc;
-        LAUNCH(c, "kx_spliced_offsets", kx_spliced_offsets, dim3(1), dim3(1024), (const TileStats *)S.tile_stats.p, n_tiles, (u32 *)c->x_tileoff.p, d_xcnt);
-        for (auto &b : batches)
-            LAUNCH(c, "kx_spliced_codes", kx_spliced_codes, dim3((unsigned)((b.n + K1_TILE - 1) / K1_TILE)), dim3(256), b, (const TileStats *)S.tile_stats.p,
-                   (const u32 *)S.splidx.p, (const u32 *)c->x_tileoff.p, (u64 *)S.x_codes.p);
-        XTRACE("post: codes");
-        if ((rc = name_table_insert(c, (const u64 *)S.x_codes.p, (u32)n_spliced))) return rc;
-        X.codes_in_table = true;
-        XTRACE("post: insert");
-    }
-    if (J > 0) {
-        HIP_TRY(c, hipMemsetAsync(X.xr, 0, (size_t)J * sizeof(ExtraRow), st));
-        LAUNCH(c, "kx_flank_sparse", kx_flank_sparse, dim3((J + 255) / 256), dim3(256), (const pjb_junction_row *)S.rows.p, J,
-               (const int32_t *)f.x_spos, (const int32_t *)f.x_send, L, (const u32 *)S.x_zlist.p, (const SparseCounters *)d_cnt, X_ZCAP, X.xr);
-        LAUNCH(c, "kx_pair_codes", kx_pair_codes, dim3((P + 255) / 256), dim3(256), f.sidx, f.jid_sorted, f.pr.g, (const DevBatch *)S.batches.p,
-               (int)batches.size(), P, (u32)row_base, X.pair_code, X.pair_row);
-    }
-    // one wait: the counters decide whether the sparse answer stands
-    SparseCounters &hc = *(SparseCounters *)(S.pub + PUB_XCNT_AT);
-    ExtraCounters &hx = *(ExtraCounters *)(S.pub + PUB_XCNT_AT + sizeof(SparseCounters));
-    XTRACE("post: flank + pair codes");
-    HIP_TRY(c, hipMemcpyAsync(&hc, d_cnt, sizeof(SparseCounters) + sizeof(ExtraCounters), hipMemcpyDeviceToHost, st));
-    HIP_TRY(c, hipStreamSynchronize(st));
-    XTRACE("post: counters");
-    if (c->ktime) ev_collect(c, MISC_POOL);
-    if (hc.n_zero > X_ZCAP)
-        return fail(c, PJB_ERR_ARG, "extra: target %d has %u mapped records without a reference span (limit %u)", tid, hc.n_zero, X_ZCAP);
-    if (hx.n_spliced != (u32)n_spliced)
-        return fail(c, PJB_ERR_STATE, "extra: target %d: %u spliced records in the tile lists, the chain counted %llu", tid, hx.n_spliced, (unsigned long long)n_spliced);
-    if (hc.need_dense) // the pileup's cap may bite (or the gap list is too small): the depth vector, as in round 2
-        return extra_contig_dense(c, tid, batches, f.n_reads, n_spliced, P, J, f.sidx, f.jid_sorted, f.pr.g, row_base, true);
-    X.has_unspliced = (u32)hc.total > 0;
-    X.n_spl = hx.n_spliced;
-    X.sparse = SparseDepth{f.x_spos, f.x_send, f.x_gaps, f.x_gapoff, (u32)hc.total, (u32)(hc.total >> 32), hc.max_span, hc.max_gap};
-    c->xc.push_back(X);
     return PJB_OK;
 }
 

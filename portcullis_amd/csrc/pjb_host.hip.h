@@ -212,7 +212,7 @@ struct Flight {
     Pairs pr;
     // --extra: what the part that only needs the records (extra_pre) left for the part that needs the rows (extra_contig)
     bool x_pre = false;
-    bool x_k1 = false; // k1_count classified the records (else: kx_classify_sparse)
+    bool x_k1 = false; // k1_count classified the records (every lone target; a group's: kx_classify_sparse)
     int32_t *x_spos = nullptr, *x_send = nullptr;
     u32 *x_gapoff = nullptr;
     Gap *x_gaps = nullptr;

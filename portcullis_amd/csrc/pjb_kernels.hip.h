@@ -290,8 +290,7 @@ __device__ __forceinline__ void k1_count_rows(const GBatch &b, const u32 tile_lo
     int32_t mn = INT32_MAX, mx = 0, max_end = 0, max_nlen = 0, min_pos = INT32_MAX;
     u32 cN[4], nlq[4];
     u32 mspan = 0; // TileStats::max_span
-    u32 xspan = 0, xgapmax = 0;
-    bool xmany = false;
+    XLane xl; // (EXTRA; a chain of one member: offset 0, spans may leave it)
 #pragma unroll
     for (int i = 0; i < 4; i++) {
         const int64_t r = r0 + i;
@@ -337,33 +336,9 @@ __device__ __forceinline__ void k1_count_rows(const GBatch &b, const u32 tile_lo
         } else
             uns++;
         cN[i] = cc;
-        if (EXTRA) { // the record's part in unspliced.bam (junction_builder.cc:168-186)
-            const u32 g = b.base + (u32)r;
-            const u32 fv = (u32)(fl4 >> (16 * i)) & 0xffffu;
-            const bool unspliced = cc == 0 && !(fv & 0x4u);
-            const bool spans = unspliced && al > 0 && p >= 0;
-            X.s_pos[g] = p;
-            X.s_end[g] = spans ? p + al : p;
-            if (!spans) ngap = 0, gmax = 0;
-            if (ngap > SPARSE_GAP_MAX) xmany = true, ngap = SPARSE_GAP_MAX;
-            X.q[g] = (uint8_t)((spans ? 1u : 0u) | (ngap << 1));
-            if (spans) xspan = max(xspan, (u32)al);
-            xgapmax = max(xgapmax, gmax);
-            if (unspliced && al == 0) {
-                const u32 z = atomicAdd(&X.cnt->n_zero, 1u);
-                if (z < X.zcap) X.zlist[z] = (u32)p;
-            }
-        }
+        if (EXTRA) x_classify(X, b.base + (u32)r, p, al, ngap, gmax, cc != 0, (u32)(fl4 >> (16 * i)) & 0xffffu, 0, 0, (u32)b.member, false, xl);
     }
-    if (EXTRA) {
-        xspan = wave_max(xspan);
-        xgapmax = wave_max(xgapmax);
-        if (lane_id() == 0) { // (look first: the maxima settle after a few waves)
-            if (xspan > X.cnt->max_span) atomicMax(&X.cnt->max_span, xspan);
-            if (xgapmax > X.cnt->max_gap) atomicMax(&X.cnt->max_gap, xgapmax);
-        }
-        if (xmany) atomicOr(&X.cnt->need_dense, 2u);
-    }
+    if (EXTRA) x_counters(X.cnt, xl);
     // ---- ordered compaction of the tile's spliced reads: slot k holds the k-th of them (batch-local index) and the tile-local offset
     // of its first pair.  Thread order is read order: one scan of the threads' counts.
     {
@@ -465,8 +440,8 @@ __global__ __launch_bounds__(K1C_T) __attribute__((amdgpu_waves_per_eu(K1C_WAVES
     int32_t pos4[RPT];
     u32 c4[RPT], so4[RPT], nlq4[RPT]; // (nlq4: spl_nlq -- what the spliced list keeps of operations count, l_qseq and the presence of bases)
     u32 bad = 0;                // bit it: read `it` lies before its predecessor; bit 4 + it: its XS code is not one
-    u32 xflag4[RPT] = {}, xspan = 0, xgapmax = 0; // (EXTRA)
-    bool xmany = false;
+    u32 xflag4[RPT] = {}; // (EXTRA)
+    XLane xl;             // (EXTRA; a chain of one member: offset 0, spans may leave it)
     // (Every load below is UNCONDITIONAL -- a lane past the batch's end reads the last record, an operation past a CIGAR's end
     // reads a word that is always there -- and the value is masked afterwards.  Written as `cond ? load : 0` the compiler
     // may not speculate the load, turns it into a branch and waits for each one before issuing the next: the 16 CIGAR loads
@@ -546,34 +521,11 @@ __global__ __launch_bounds__(K1C_T) __attribute__((amdgpu_waves_per_eu(K1C_WAVES
             } else
                 uns++;
             cthis = c;
-            if (EXTRA) { // the record's part in unspliced.bam (junction_builder.cc:168-186)
-                const u32 g = b.base + (u32)r;
-                const bool unspliced = c == 0 && !(xflag4[it] & 0x4u);
-                const bool spans = unspliced && al > 0 && p >= 0;
-                X.s_pos[g] = p;
-                X.s_end[g] = spans ? p + al : p;
-                if (!spans) ngap = 0, gmax = 0;
-                if (ngap > SPARSE_GAP_MAX) xmany = true, ngap = SPARSE_GAP_MAX;
-                X.q[g] = (uint8_t)((spans ? 1u : 0u) | (ngap << 1));
-                if (spans) xspan = max(xspan, (u32)al);
-                xgapmax = max(xgapmax, gmax);
-                if (unspliced && al == 0) {
-                    const u32 z = atomicAdd(&X.cnt->n_zero, 1u);
-                    if (z < X.zcap) X.zlist[z] = (u32)p;
-                }
-            }
+            if (EXTRA) x_classify(X, b.base + (u32)r, p, al, ngap, gmax, c != 0, xflag4[it], 0, 0, (u32)b.member, false, xl);
         }
         c4[it] = cthis;
     }
-    if (EXTRA) {
-        xspan = wave_max(xspan);
-        xgapmax = wave_max(xgapmax);
-        if (lane_id() == 0) { // (look first: the maxima settle after a few waves)
-            if (xspan > X.cnt->max_span) atomicMax(&X.cnt->max_span, xspan);
-            if (xgapmax > X.cnt->max_gap) atomicMax(&X.cnt->max_gap, xgapmax);
-        }
-        if (xmany) atomicOr(&X.cnt->need_dense, 2u);
-    }
+    if (EXTRA) x_counters(X.cnt, xl);
     // ordered compaction of the spliced reads of this tile: slot k holds the k-th spliced read
     // (batch-local index) and the tile-local offset of its first pair.  Read order is round-major
     // (r = base + it * 256 + thread): one wave scan per round, one barrier for all four.

@@ -3,7 +3,7 @@ through the C ABI (PJB_FLAG_EXTRA contexts, pjb_extra_finish)."""
 import numpy as np
 import pytest
 
-from extra_util import add_names, assert_extra_equal, device_extra, oracle_extra
+from extra_util import add_names, assert_extra_equal, batch_with_names, device_extra, oracle_extra
 from fuzzgen import make_reads
 from parity import assert_rows_equal
 
@@ -108,6 +108,53 @@ def test_extra_zero_span_and_edges(ffi, orc):
     rows, extra = device_extra(ffi, orc, contigs)
     assert_rows_equal(rows, orows)
     assert_extra_equal(rows, extra, orows)
+
+
+_PAST_THE_END = {"nothing": [],
+                 "a span that leaves the target": [dict(pos=595, cigar="30M", seq="A" * 30, name="x0")],
+                 "a record that starts past the end": [dict(pos=650, cigar="30M", seq="A" * 30, name="x0")],
+                 "records on the last base, one without a span": [dict(pos=599, cigar="5M", seq="A" * 5, name="x0"),
+                                                                  dict(pos=599, cigar="6S", seq="A" * 6, name="x1")]}
+
+
+@pytest.mark.parametrize("adds", list(_PAST_THE_END))
+def test_extra_lone_target_records_at_and_past_the_end(ffi, orc, adds):
+    """A lone target is a chain of one member: finished alone, as a group of one through the group entry points and through the depth
+    vector it gives the oracle's rows -- the two sparse runs the same bytes -- also where its unspliced records end past its end, start
+    past it or sit on its last base, which a member of a larger group may not.  Only the span that leaves the target, starting inside
+    the right anchor of the last junction and before the last base, is a right-flanking alignment."""
+    from test_gpu_extra_groups import assert_same_bits
+    g = "ACGTTGCAAC" * 60
+    reads = [dict(pos=0, cigar="10M20N30M", seq="A" * 40, name="e0", xs="+"),
+             dict(pos=9, cigar="30M", seq="A" * 30, name="u0"),
+             dict(pos=540, cigar="30M20N10M", seq="A" * 40, name="e1", xs="-"),
+             dict(pos=585, cigar="9M", seq="A" * 9, name="u1")] + [dict(r) for r in _PAST_THE_END[adds]]
+    contigs = [(g, reads)]
+    orows, _ = oracle_extra(orc, contigs)
+    assert [(int(r["start"]), int(r["end"])) for r in orows] == [(10, 29), (570, 589)]
+    assert int(orows["up_aln"][0]) == 1
+    assert int(orows["down_aln"][1]) == (1 if adds == "a span that leaves the target" else 0)
+
+    def run(how):
+        with ffi.Context(0, "UNKNOWN", flags=ffi.FLAG_EXTRA) as ctx:
+            ctx.set_refs([len(g)])
+            ctx.clear_rows()
+            if how == "dense":
+                ctx.set_option("extra_dense", 1)
+            ctx.upload_contig(0, g.encode())
+            ctx.submit_batch(0, batch_with_names(orc, reads))
+            if how == "group of one":
+                ctx.finish_group_begin([0])
+                regs = ctx.finish_group_end([0])
+            else:
+                regs = {0: ctx.finish_contig(0)}
+            return ctx.collect(), ctx.extra_finish(), regs
+
+    runs = {how: run(how) for how in ("alone", "group of one", "dense")}
+    for how, (rows, extra, _) in runs.items():
+        assert_rows_equal(rows, orows)
+        assert_extra_equal(rows, extra, orows)
+    assert_same_bits(runs["group of one"], runs["alone"], adds)
 
 
 def test_extra_gaps_and_dense_fallbacks(ffi, orc):
