@@ -208,7 +208,9 @@ typedef struct pjb_timing {
     int64_t repeats;        /* times the chain collected last was queued AGAIN because a limit it had been queued with turned out too small */
     int64_t repeat_reasons; /* which limits, OR-ed over those repeats: 1 pairs, 2 key format, 4 junctions (or the sort's digits), 8 dense ids, 16 read lists;
                                32: the chain was a group that pjb_finish_group_end took apart -- its members were finished one by one, and the
-                               other fields describe the last member's chain */
+                               other fields describe the last member's chain; 64: a tile of the sort held junction ids that do not lie in a
+                               window of 2 048 (or the list of the tiles' id runs was full): repeated with the radix passes, which the
+                               context's later chains then plan themselves */
 } pjb_timing;
 
 /* ---- entry points ------------------------------------------------------ */

@@ -217,7 +217,7 @@ void pjb_destroy(pjb_ctx *c) {
         Buf *sb[] = {&S.x_q, &S.x_spos, &S.x_send, &S.x_gapoff, &S.x_zlist, &S.x_scnt, &S.x_codes, &S.cstats, &S.err, &S.gencount, &S.batches, &S.rows, &S.tile_cnt, &S.tile_stats, &S.splidx, &S.splpoff, &S.splrec, &S.tile_soff, &S.chunk_tile, &S.scan_parts, &S.members, &S.okey, &S.g,
                      &S.rec, &S.jidbam, &S.jkey, &S.total, &S.bitmap, &S.wrank, &S.pagecnt, &S.pagerank, &S.ends, &S.firstid,
                      &S.key[0], &S.key[1], &S.idx[0], &S.idx[1], &S.hist, &S.hist_scan, &S.hist_part, &S.bintotal, &S.scan_tiles, &S.jid, &S.seg, &S.runfirst,
-                     &S.runstart, &S.ent, &S.entsum, &S.frag, &S.fragj, &S.masks, &S.acc, &S.ancl, &S.ancr, &S.genlist};
+                     &S.runstart, &S.ent, &S.entsum, &S.frag, &S.fragj, &S.masks, &S.acc, &S.ancl, &S.ancr, &S.genlist, &S.runs};
         for (Buf *b : sb) release(*b);
         hipEvent_t evs[] = {S.ev_k1, S.ev_xk1, S.ev_fork, S.ev_join, S.ev_fork2, S.ev_join2};
         for (hipEvent_t e : evs)
@@ -915,6 +915,7 @@ static int queue_contig(pjb_ctx *c, Flight &f) {
     int n_pass = 1;
     std::vector<int> pass_bits;
     bool first_hist_done = false;
+    u32 plan_tiles = rs_tiles; // (the run route sorts its run list instead of the pairs: fewer tiles)
     auto plan_passes = [&]() -> int {
         n_pass = (sort_bits + c->radix_max_bits - 1) / c->radix_max_bits;
         if (n_pass < 1) n_pass = 1;
@@ -922,12 +923,45 @@ static int queue_contig(pjb_ctx *c, Flight &f) {
         for (int p = 0; p < sort_bits % n_pass; p++) pass_bits[(size_t)p]++;
         const int dbits = pass_bits[0];
         int rc2;
-        if ((rc2 = ensure(c, S.hist, (size_t)rs_tiles * (1u << dbits) * 4))) return rc2;
-        if ((rc2 = ensure(c, S.hist_scan, (size_t)rs_tiles * (1u << dbits) * 4))) return rc2;
+        if ((rc2 = ensure(c, S.hist, (size_t)plan_tiles * (1u << dbits) * 4))) return rc2;
+        if ((rc2 = ensure(c, S.hist_scan, (size_t)plan_tiles * (1u << dbits) * 4))) return rc2;
         if ((rc2 = ensure(c, S.bintotal, (size_t)4 << dbits))) return rc2;
-        if ((rc2 = ensure(c, S.hist_part, (size_t)((rs_tiles + RSP_TILES - 1) / RSP_TILES) * (1u << dbits) * 4))) return rc2;
+        if ((rc2 = ensure(c, S.hist_part, (size_t)((plan_tiles + RSP_TILES - 1) / RSP_TILES) * (1u << dbits) * 4))) return rc2;
         return PJB_OK;
     };
+    // the run route (ContigLimits::run_sort): the slot's scratch, carved from one buffer -- counters, the tiles' entries, the run list
+    // (room: an eighth of the pair limit and 64 entries a tile; chains have 0.4 % of their pairs), its sort's ping-pong buffers
+    // (one tile of slack each: rs_scatter loads whole tiles unguarded)
+    const bool run_route = lim.dense && lim.run_sort;
+    RunOut ro;
+    memset(&ro, 0, sizeof ro);
+    const u32 run_cap = (u32)std::min<u64>((u64)PL / 8 + 64ull * rs_tiles, 0xfff00000ull);
+    const u32 ro_tiles = (run_cap + RS_TILE - 1) / RS_TILE;
+    u64 *ro_total = nullptr, *ro_key[2] = {nullptr, nullptr};
+    u32 *run_dest = nullptr, *ro_idx[2] = {nullptr, nullptr};
+    if (run_route) {
+        auto al = [](size_t b) { return (b + 255) & ~(size_t)255; };
+        const size_t slack = (size_t)run_cap + RS_TILE;
+        const size_t at_tf = 256, at_tn = at_tf + al((size_t)rs_tiles * 4), at_key = at_tn + al((size_t)rs_tiles * 4), at_cnt = at_key + al(slack * 8),
+                     at_dest = at_cnt + al((size_t)run_cap * 4), at_k0 = at_dest + al((size_t)run_cap * 4), at_k1 = at_k0 + al(slack * 8),
+                     at_i0 = at_k1 + al(slack * 8), at_i1 = at_i0 + al(slack * 4), at_end = at_i1 + al(slack * 4);
+        if ((rc = ensure(c, S.runs, at_end))) return rc;
+        uint8_t *b = (uint8_t *)S.runs.p;
+        ro.n_runs = (u32 *)b;
+        ro_total = (u64 *)(b + 8);
+        ro.tile_first = (u32 *)(b + at_tf);
+        ro.tile_n = (u32 *)(b + at_tn);
+        ro.key = (u64 *)(b + at_key);
+        ro.cnt = (u32 *)(b + at_cnt);
+        run_dest = (u32 *)(b + at_dest);
+        ro_key[0] = (u64 *)(b + at_k0);
+        ro_key[1] = (u64 *)(b + at_k1);
+        ro_idx[0] = (u32 *)(b + at_i0);
+        ro_idx[1] = (u32 *)(b + at_i1);
+        ro.cap = run_cap;
+        ro.window = c->run_window ? std::min<u32>(c->run_window, RUN_W) : RUN_W;
+        ro.tile_bits = std::max(1, bits_of((uint64_t)rs_tiles));
+    }
     if (lim.dense) {
         const u32 cand_blocks = std::min<u32>(pair_blocks, 1024u); // (a few candidates per junction: these kernels stride)
         const u64 *okey = (const u64 *)pr.key;
@@ -946,14 +980,16 @@ static int queue_contig(pjb_ctx *c, Flight &f) {
             return rc;
         LAUNCH(c, "kd_table", kd_table, dim3(cand_blocks), dim3(256), (const u64 *)cand, (const u64 *)S.ent.p, (const u32 *)cand_rank, kf, JL,
                (const u32 *)S.ends.p, (const u32 *)S.firstid.p, (const u64 *)S.total.p, (u64 *)S.jkey.p, (int32_t *)S.ancl.p, (int32_t *)S.ancr.p, d_cs,
-               (const u32 *)d_gen_cnt, gen_cap, SL);
-        // (a block per tile of the sort: it leaves the tile's counts of the ids' first digit -- the first pass below has no rs_hist)
-        sort_bits = std::max(1, bits_of((uint64_t)SL));
+               (const u32 *)d_gen_cnt, gen_cap, SL, ro.n_runs);
+        // (a block per tile of the sort: it leaves the tile's counts of the ids' first digit -- the first pass below has no rs_hist --,
+        // or, on the run route, the tile's id runs: the digits planned are then those of the run list's keys)
+        sort_bits = std::max(1, bits_of((uint64_t)SL)) + (run_route ? ro.tile_bits : 0);
+        if (run_route) plan_tiles = ro_tiles;
         if ((rc = plan_passes())) return rc;
         LAUNCH(c, "kd_assign", kd_assign, dim3(rs_tiles), dim3(256), okey, d_P, kf, (const u64 *)S.bitmap.p, (const u32 *)S.wrank.p,
                (const u32 *)S.ends.p, (const u32 *)S.firstid.p, JL, (const u64 *)S.total.p, (u32 *)S.jidbam.p, (u32 *)S.acc.p, (const u64 *)S.jkey.p,
-               (const int32_t *)S.ancl.p, (const int32_t *)S.ancr.p, d_err, d_cs, pass_bits[0], (u32 *)S.hist.p);
-        first_hist_done = true;
+               (const int32_t *)S.ancl.p, (const int32_t *)S.ancr.p, d_err, d_cs, run_route ? 0 : pass_bits[0], (u32 *)S.hist.p, ro);
+        first_hist_done = !run_route;
         if ((rc = fork_k4b())) return rc;
         LAUNCH(c, "kd_reset", kd_reset, dim3(cand_blocks), dim3(256), (const u64 *)cand, (const u32 *)cand_rank, kf, JL, (const ContigStats *)d_cs,
                (u64 *)S.bitmap.p, (u32 *)S.ends.p, (u32 *)S.pagecnt.p);
@@ -964,21 +1000,26 @@ static int queue_contig(pjb_ctx *c, Flight &f) {
     int cur = 0, shift = 0;
     // digit passes.  Dense ids are 32-bit keys: pass 0 reads them where kd_assign left them (BAM order; k4b_generic reads that array
     // beside the sort, so no pass writes to it), the ping-pong buffers are the first halves of the 64-bit key buffers.
-    auto sort_pass = [&](auto key_tag, const void *kin_v, void *kout_v, const u32 *vin, u32 *vout, int bits) -> int {
+    // (the run route's launches go by names of their own, kept in this table: bench.py's byte formulas are written for the pair-sized
+    // passes and describe none of them -- they appear under its kernels_without_formula)
+    static const char *const rs_names[4] = {"rs_hist", "rs_panel_sums", "rs_panel_scan", "rs_scatter"};
+    static const char *const ro_names[6] = {"ro_hist", "ro_panel_sums", "ro_panel_scan", "ro_scatter", "ro_offsets", "rs_place"};
+    auto sort_pass = [&](auto key_tag, const void *kin_v, void *kout_v, const u32 *vin, u32 *vout, int bits, const u32 *d_n, u32 tiles,
+                         const char *const *names) -> int {
         using K = decltype(key_tag);
         const K *kin = (const K *)kin_v;
         K *kout = (K *)kout_v;
         if (!(shift == 0 && first_hist_done)) // (dense ids: kd_assign counted the first digit)
-            LAUNCH(c, "rs_hist", rs_hist<K>, dim3(rs_tiles), dim3(256), kin, d_P, shift, bits, (u32 *)S.hist.p, rs_tiles);
+            LAUNCH(c, names[0], rs_hist<K>, dim3(tiles), dim3(256), kin, d_n, shift, bits, (u32 *)S.hist.p, tiles);
         {
-            const u32 nb = 1u << bits, n_panels = (rs_tiles + RSP_TILES - 1) / RSP_TILES;
-            LAUNCH(c, "rs_panel_sums", rs_panel_sums, dim3(n_panels, (nb + 255) / 256), dim3(256), (const u32 *)S.hist.p, rs_tiles, nb, (u32 *)S.hist_part.p);
-            LAUNCH(c, "rs_panel_scan", rs_panel_scan, dim3(n_panels, (nb + 255) / 256), dim3(256), (const u32 *)S.hist.p, (const u32 *)S.hist_part.p, rs_tiles, nb,
+            const u32 nb = 1u << bits, n_panels = (tiles + RSP_TILES - 1) / RSP_TILES;
+            LAUNCH(c, names[1], rs_panel_sums, dim3(n_panels, (nb + 255) / 256), dim3(256), (const u32 *)S.hist.p, tiles, nb, (u32 *)S.hist_part.p);
+            LAUNCH(c, names[2], rs_panel_scan, dim3(n_panels, (nb + 255) / 256), dim3(256), (const u32 *)S.hist.p, (const u32 *)S.hist_part.p, tiles, nb,
                    (u32 *)S.hist_scan.p, (u32 *)S.bintotal.p);
         }
 #define RS_SCATTER(B)                                                                                                                          \
-    LAUNCH_LDS(c, "rs_scatter", (rs_scatter<B, K>), dim3(rs_tiles), dim3(256), rs_scatter_lds_bytes(bits, sizeof(K)), kin, vin, kout, vout, d_P, \
-               shift, bits, (const u32 *)S.hist_scan.p, (const u32 *)S.bintotal.p, rs_tiles)
+    LAUNCH_LDS(c, names[3], (rs_scatter<B, K>), dim3(tiles), dim3(256), rs_scatter_lds_bytes(bits, sizeof(K)), kin, vin, kout, vout, d_n, \
+               shift, bits, (const u32 *)S.hist_scan.p, (const u32 *)S.bintotal.p, tiles)
         switch (bits) { // the usual digit widths get an unrolled match loop
         case 9: RS_SCATTER(9); break;
         case 10: RS_SCATTER(10); break;
@@ -991,13 +1032,29 @@ static int queue_contig(pjb_ctx *c, Flight &f) {
     for (int p = 0; p < n_pass; p++) {
         const int bits = pass_bits[(size_t)p];
         if (bits <= 0) break;
-        const u32 *vin = p == 0 ? nullptr : (const u32 *)S.idx[cur].p;
-        u32 *vout = (u32 *)S.idx[cur ^ 1].p;
-        if (lim.dense) rc = sort_pass((u32)0, p == 0 ? S.jidbam.p : S.key[cur].p, S.key[cur ^ 1].p, vin, vout, bits);
-        else rc = sort_pass((u64)0, p == 0 ? S.okey.p : S.key[cur].p, S.key[cur ^ 1].p, vin, vout, bits);
+        if (run_route) { // (the run list: 64-bit keys whatever the chain's size, its length is on the device)
+            rc = sort_pass((u64)0, p == 0 ? (const void *)ro.key : (const void *)ro_key[cur], ro_key[cur ^ 1], p == 0 ? nullptr : (const u32 *)ro_idx[cur],
+                           ro_idx[cur ^ 1], bits, (const u32 *)ro.n_runs, ro_tiles, ro_names);
+        } else {
+            const u32 *vin = p == 0 ? nullptr : (const u32 *)S.idx[cur].p;
+            u32 *vout = (u32 *)S.idx[cur ^ 1].p;
+            if (lim.dense) rc = sort_pass((u32)0, p == 0 ? S.jidbam.p : S.key[cur].p, S.key[cur ^ 1].p, vin, vout, bits, d_P, rs_tiles, rs_names);
+            else rc = sort_pass((u64)0, p == 0 ? S.okey.p : S.key[cur].p, S.key[cur ^ 1].p, vin, vout, bits, d_P, rs_tiles, rs_names);
+        }
         if (rc) return rc;
         cur ^= 1;
         shift += bits;
+    }
+    if (run_route) {
+        // where every run's first pair goes: the counts summed in key order, written back at the run's own index; then the one pass
+        // over the pairs
+        const u32 *order = ro_idx[cur];
+        if ((rc = run_scan(c, ro_names[4], RunCountFn{(const u32 *)ro.cnt, order}, RunDestSink{run_dest, order}, (u64)run_cap, ro_total, (const u32 *)ro.n_runs)))
+            return rc;
+        cur = 1;
+        LAUNCH(c, ro_names[5], rs_place, dim3(rs_tiles), dim3(256), (const u32 *)S.jidbam.p, d_P, (const u64 *)ro.key, (const u32 *)run_dest,
+               (const u32 *)ro.tile_first, (const u32 *)ro.tile_n, run_cap, ro.tile_bits, (u32 *)S.key[cur].p, (u32 *)S.idx[cur].p);
+        n_pass = 1;
     }
     f.n_pass = n_pass;
     const u32 *sidx = (const u32 *)S.idx[cur].p;
@@ -1229,6 +1286,7 @@ static void prepare_flight(pjb_ctx *c, Flight &f) {
     lim.kf.lbits = std::max(1, c->lbits_seen);
     lim.kf.total_bits = lim.kf.lbits + std::max(1, bits_of((uint64_t)std::max<int64_t>(f.vlen, 1)));
     lim.dense = c->dense_ids;
+    lim.run_sort = c->run_sort;
     // (twice what a chain of this context's targets has had, per member; a chain with more is repeated with digits for junc_limit)
     // (junctions per read: chains of one file have about the same, whatever their targets' number and size)
     lim.sort_limit = c->junc_per_read > 0 ? std::min<u32>(lim.junc_limit, std::max<u32>(c->sort_floor, (u32)std::min<double>(4.0e9, 2.0 * c->junc_per_read * (double)f.n_reads + 64.0))) : 0u;
@@ -1399,6 +1457,11 @@ static int collect_flight(pjb_ctx *c, pjb_region_result *res, bool *redo_single)
         const bool sort_only = (cs.overflow & OVF_JUNC) && lim.sort_limit && cs.n_junc <= lim.junc_limit; // (the buffers were large enough)
         if (cs.overflow & OVF_JUNC) lim.sort_limit = 0;
         if ((cs.overflow & OVF_JUNC) && !sort_only) lim.junc_limit = std::max<u32>(cs.n_junc + 64, (cs.overflow & OVF_DENSE) || !lim.dense ? 0u : lim.junc_limit * 4);
+        if (cs.overflow & OVF_RUNS) { // tiles whose ids do not lie in a window (an unsorted or pathological file), or more runs than the list
+                                      // holds: the radix route, for this chain, those taken back behind it and those to come
+            c->run_sort = false;
+            for (int k = 0; k < c->n_fl; k++) c->fl[k].lim.run_sort = false;
+        }
         if (cs.overflow & OVF_DENSE) lim.dense = false; // a donor with more alternative acceptors than K2d keeps: sort the full keys
         if (cs.overflow & OVF_LISTS) lim.list_cap = std::max(gen_list_cap(lim.pair_limit), (cs.list_need + cs.list_need / 4 + 511u) & ~255u); // (k1_generic's entries depend on the appends' order: some slack)
     }
@@ -1768,7 +1831,11 @@ int pjb_set_option(pjb_ctx *c, const char *name, int64_t value) {
     else if (n == "extra_dense") c->extra_dense_only = value != 0;
     else if (n == "sort_floor") c->sort_floor = (u32)std::max<int64_t>(1, std::min<int64_t>(value, 1 << 30));
     else if (n == "window_skip") c->window_skip = value != 0;
-    else if (n == "list_cap") c->list_cap_forced = (u32)std::max<int64_t>(0, std::min<int64_t>(value, 1 << 30));
+    else if (n == "run_sort") c->run_sort = value != 0;
+    else if (n == "run_window") {
+        if (value < 0 || value > (int64_t)RUN_W) return fail(c, PJB_ERR_ARG, "set_option: run_window takes 0 (the default, %u) to %u", RUN_W, RUN_W);
+        c->run_window = (u32)value;
+    } else if (n == "list_cap") c->list_cap_forced = (u32)std::max<int64_t>(0, std::min<int64_t>(value, 1 << 30));
     else return fail(c, PJB_ERR_ARG, "set_option: unknown option '%s'", name);
     return PJB_OK;
 }

@@ -60,7 +60,7 @@ static_assert(sizeof(TileStats) == 40, "TileStats layout");
 // runs (pairs, junctions, key format); the kernels read the actual counts from here, and a count that exceeds its limit
 // raises an overflow bit and zeroes the count so that everything downstream does nothing.  pjb_finish_contig reads the
 // block back once, at the end, and repeats the contig with larger limits if a bit is set.
-enum : u32 { OVF_PAIRS = 1u, OVF_KEYFMT = 2u, OVF_JUNC = 4u, OVF_DENSE = 8u, OVF_LISTS = 16u };
+enum : u32 { OVF_PAIRS = 1u, OVF_KEYFMT = 2u, OVF_JUNC = 4u, OVF_DENSE = 8u, OVF_LISTS = 16u, OVF_RUNS = 64u /* (32: the host's "group taken apart") */ };
 struct ContigStats {
     u64 spliced, unspliced, sum_len;
     int32_t min_len, max_len;

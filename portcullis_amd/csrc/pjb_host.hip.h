@@ -147,6 +147,7 @@ struct ContigLimits {
                         // of 4096 pairs (61 MB a launch, round 4's PMC pass) where a chain has 2^17 junctions
     KeyFmt kf;
     bool dense = false; // sort ordered dense junction ids (K2d) instead of the full keys
+    bool run_sort = false; // dense ids: order the pairs by the tiles' id runs (rs_place) instead of the radix passes
 };
 
 // What two queued contigs must not share: control block, error word, list counters, batch descriptors and the device
@@ -167,6 +168,7 @@ struct CtlSlot {
     // the rest of the chain's scratch, and its streams: the chains of the two slots run side by side (most kernels of a
     // contig-sized chain are latency-bound and leave the chip half idle)
     Buf total, bitmap, wrank, ends, firstid, key[2], idx[2], hist, hist_scan, hist_part, bintotal, scan_tiles;
+    Buf runs;              // the run route of the sort: counters, the tiles' entries, the run list and what sorting it needs (queue_contig)
     Buf pagecnt, pagerank; // K2d: starts per page of the bitmap (all-zero at rest), their exclusive prefix
     Buf jid, seg, runfirst, runstart, ent, entsum, frag, fragj, acc, ancl, ancr, jkey, genlist, masks;
     bool dense_at_rest = false;
@@ -294,6 +296,9 @@ struct pjb_ctx {
     double junc_per_read = 0;         // most junctions per read a chain of this context has had (the sort's digits of the next chain)
     u32 sort_floor = 1u << 16;        // pjb_set_option("sort_floor", n): the least number of junction ids the sort's digits are planned for (tests: small)
     bool window_skip = true;          // pjb_set_option("window_skip", 0): every closed read of two and more introns goes on the window-check list (ContigStats::max_span)
+    bool run_sort = true;             // pjb_set_option("run_sort", 0): dense ids through the radix passes.  Cleared by a chain whose tiles' ids do not
+                                      // lie in a window (OVF_RUNS): the chains behind it plan the radix route themselves
+    u32 run_window = 0;               // pjb_set_option("run_window", n): a tile's ids must span less than n (tests; 0: RUN_W)
     u32 list_cap_forced = 0;          // pjb_set_option("list_cap", n): the read lists' first room (tests of the OVF_LISTS repeat)
     bool k1_serial = true;            // PJB_K1_SERIAL=0: the chains' K1 stages side by side
     hipEvent_t last_k1_ev = nullptr;  // the K1 stage of the chain queued last

@@ -2250,7 +2250,7 @@ __device__ __forceinline__ void anchors_fold(bool valid, u32 j, int32_t l, int32
 // contig -- if a limit was exceeded while the ids were built
 __global__ __launch_bounds__(256) void kd_table(const u64 *cand, const u64 *cand_anc, const u32 *cand_rank, KeyFmt kf, u32 junc_limit, const u32 *ends,
                                                 const u32 *first_id, const u64 *total, u64 *jkey, int32_t *anc_l, int32_t *anc_r, ContigStats *cs,
-                                                const u32 *gen_cnt, u32 gen_cap, u32 sort_limit) {
+                                                const u32 *gen_cnt, u32 gen_cap, u32 sort_limit, u32 *n_runs) {
     const u32 p = blockIdx.x * 256 + threadIdx.x;
     if (blockIdx.x == 0) { // (the read lists: every sub-list within its room?)
         static_assert(GEN_SHARDS == 256, "a shard per thread of the first block");
@@ -2259,6 +2259,7 @@ __global__ __launch_bounds__(256) void kd_table(const u64 *cand, const u64 *cand
         if (__syncthreads_or((int)over) && threadIdx.x == 0) cs->overflow |= OVF_LISTS;
     }
     if (p == 0) {
+        if (n_runs) *n_runs = 0; // (the run list kd_assign fills: see RunOut)
         const u64 J = *total;
         u32 ovf = cs->overflow;
         // (sort_limit: the ids the sort's digits were planned for -- what chains of this context have had so far, with room; junc_limit:
@@ -2321,13 +2322,41 @@ __device__ __forceinline__ void acc_rest_state(u32 *acc, u64 n_junc) { // what k
 constexpr int KDA_TILE = 4096; // = RS_TILE
 __device__ __forceinline__ void wave_hist_add(u32 *h, u32 d, bool valid);
 constexpr int KDA_PER = 4;
+// The id runs of the tiles (the run route of the sort, see rs_place): pairs arrive in BAM order and ids are handed out in (start, end)
+// order, so the 4 096 ids of a tile lie in a window of a few dozen consecutive ids.  kd_assign counts them in a table indexed by
+// id & (RUN_W - 1) -- exact while max - min < RUN_W -- and appends one entry per (tile, id) to the chain's run list: the key
+// id << tile_bits | tile and the number of pairs.  Sorted by key, the exclusive prefix sum of the counts is where the run's first
+// pair belongs in the sorted pair array.
+constexpr u32 RUN_W = 2048;
+struct RunOut {
+    u64 *key;         // [cap] id << tile_bits | tile, in the order the tiles reserved their room
+    u32 *cnt;         // [cap] pairs of the run
+    u32 *tile_first;  // [tiles] the tile's first entry,
+    u32 *tile_n;      //         and how many it has (ascending ids)
+    u32 *n_runs;      // entries reserved so far (kd_table zeroes it)
+    u32 cap;
+    u32 window;       // 0: the radix route (nothing of the above is touched); else a tile's ids must span less than this (<= RUN_W)
+    int tile_bits;
+};
+static_assert(RUN_W == 256 * 8, "kd_assign compacts eight table entries a thread");
+// a tile's ids span more than the window, or the run list is full: the chain is closed (as kd_table closes it) and repeated on the radix route
+__device__ __forceinline__ void runs_close_chain(ContigStats *cs) {
+    atomicOr(&cs->overflow, OVF_RUNS);
+    cs->P = 0;
+    cs->J = 0;
+    cs->n_slots = 0;
+    cs->n_slices = 0;
+}
 __global__ __launch_bounds__(256) void kd_assign(const u64 *key, const u32 *np, KeyFmt kf, const u64 *bitmap, const u32 *wrank, const u32 *ends,
                                                  const u32 *first_id, u32 junc_limit, const u64 *total, u32 *jid_bam, u32 *acc, const u64 *jkey,
-                                                 const int32_t *anc_l, const int32_t *anc_r, u64 *err, ContigStats *cs_chk, int hist_bits, u32 *hist) {
+                                                 const int32_t *anc_l, const int32_t *anc_r, u64 *err, ContigStats *cs_chk, int hist_bits, u32 *hist,
+                                                 RunOut ro) {
     // A block takes one TILE of the sort (4 096 pairs, four chunks of 1 024) and leaves the tile's counts of the ids' first digit
     // where rs_hist would have put them (hist_bits > 0): the sort's first pass starts at its scan -- the ids are not read a second
-    // time to be counted.
-    __shared__ u32 s_h[4096]; // (RS_MAX_BINS)
+    // time to be counted.  On the run route (ro.window, hist_bits = 0) it leaves the tile's id runs instead.
+    __shared__ u32 s_h[4096]; // (RS_MAX_BINS; the run route: RUN_W counters)
+    __shared__ u32 s_run[4];  // the tile's least and largest id, its first entry in the run list
+    __shared__ u32 s_rscan[4];
     const u32 n = *np;
     if (n == 0) { // (a chain without pairs, or closed by an overflow: the tile's counts are still this kernel's to write -- zeros --, the
                   // panel kernels behind it read them)
@@ -2340,8 +2369,13 @@ __global__ __launch_bounds__(256) void kd_assign(const u64 *key, const u32 *np, 
         acc_rest_state(acc, J < (u64)junc_limit ? J : (u64)junc_limit);
     }
     const u32 nb = hist_bits > 0 ? 1u << hist_bits : 0u;
-    for (u32 d = threadIdx.x; d < nb; d += 256) s_h[d] = 0;
-    if (nb) __syncthreads();
+    for (u32 d = threadIdx.x; d < (ro.window ? RUN_W : nb); d += 256) s_h[d] = 0;
+    if (threadIdx.x == 0) {
+        s_run[0] = 0xffffffffu;
+        s_run[1] = 0u;
+    }
+    if (nb || ro.window) __syncthreads();
+    u32 id_lo = 0xffffffffu, id_hi = 0u; // (this thread's pairs)
     for (u32 chunk = blockIdx.x * (KDA_TILE / (KDA_PER * 256)); chunk < (blockIdx.x + 1) * (KDA_TILE / (KDA_PER * 256)); chunk++) {
     if (chunk * (KDA_PER * 256) >= n) break;
     // KDA_PER pairs a thread, their loads side by side: a pair is a chain of three dependent look-ups (key -> bitmap word and rank ->
@@ -2392,6 +2426,13 @@ __global__ __launch_bounds__(256) void kd_assign(const u64 *key, const u32 *np, 
         eb[q] = 0;
         if (pp[q] < n) jid_bam[pp[q]] = id; // (the sort's first pass reads the ids from here; k4b_generic looks its pairs' junctions up)
         if (nb) wave_hist_add(s_h, id & (nb - 1u), pp[q] < n);
+        if (ro.window) {
+            wave_hist_add(s_h, id & (RUN_W - 1u), pp[q] < n);
+            if (pp[q] < n) {
+                id_lo = id < id_lo ? id : id_lo;
+                id_hi = id > id_hi ? id : id_hi;
+            }
+        }
     }
 #ifdef PJB_SELFCHECK
     const u32 p = pp[0];
@@ -2420,6 +2461,60 @@ __global__ __launch_bounds__(256) void kd_assign(const u64 *key, const u32 *np, 
     if (nb) {
         __syncthreads();
         for (u32 d = threadIdx.x; d < nb; d += 256) hist[(size_t)blockIdx.x * nb + d] = s_h[d];
+    }
+    if (ro.window) {
+        // the tile's runs: the non-zero counters of [least id, largest id], in id order
+        id_lo = wave_total<DppMin>(id_lo);
+        id_hi = wave_total<DppMax>(id_hi);
+        if (lane_id() == 0) {
+            atomicMin(&s_run[0], id_lo);
+            atomicMax(&s_run[1], id_hi);
+        }
+        __syncthreads();
+        const u32 lo = s_run[0], hi = s_run[1];
+        if (lo > hi) { // (a tile past the pairs)
+            if (threadIdx.x == 0) ro.tile_n[blockIdx.x] = 0;
+            return;
+        }
+        if (hi - lo >= ro.window) {
+            if (threadIdx.x == 0) {
+                ro.tile_n[blockIdx.x] = 0;
+                runs_close_chain(cs_chk);
+            }
+            return;
+        }
+        const u32 span = hi - lo + 1u; // (<= RUN_W)
+        u32 c[8], nz = 0;
+#pragma unroll
+        for (int k = 0; k < 8; k++) {
+            const u32 o = threadIdx.x * 8u + (u32)k;
+            c[k] = o < span ? s_h[(lo + o) & (RUN_W - 1u)] : 0u;
+            nz += c[k] != 0u;
+        }
+        u32 tot;
+        u32 at = block_escan_256<u32>(nz, s_rscan, &tot);
+        if (threadIdx.x == 0) { // room in the chain's run list (a reservation that does not fit is taken back: the count never stays above the room)
+            u32 b = atomicAdd(ro.n_runs, tot);
+            if (b > ro.cap || tot > ro.cap - b) {
+                atomicSub(ro.n_runs, tot);
+                b = 0xffffffffu;
+                runs_close_chain(cs_chk);
+            }
+            s_run[2] = b;
+            ro.tile_first[blockIdx.x] = b == 0xffffffffu ? 0u : b;
+            ro.tile_n[blockIdx.x] = b == 0xffffffffu ? 0u : tot;
+        }
+        __syncthreads();
+        const u32 first = s_run[2];
+        if (first == 0xffffffffu) return;
+        at += first;
+#pragma unroll
+        for (int k = 0; k < 8; k++)
+            if (c[k]) {
+                ro.key[at] = ((u64)(lo + threadIdx.x * 8u + (u32)k) << ro.tile_bits) | (u64)blockIdx.x;
+                ro.cnt[at] = c[k];
+                at++;
+            }
     }
 }
 
@@ -2692,6 +2787,82 @@ __global__ __launch_bounds__(256, 3) void rs_scatter(const K *kin, const u32 *vi
     for (int r = 0; r < RS_ITEMS; r++) {
         const u32 j = r * 256 + threadIdx.x;
         if (j < cnt) vout[delta[(digp[r >> 1] >> ((r & 1) * 16)) & 0xffffu] + j] = ibuf[j];
+    }
+}
+
+// ---------------------------------------------------------------------------------------------
+// The run route of the dense-id sort: a stable counting sort in ONE pass over the pairs.  kd_assign left one entry per
+// (tile, id) run; the run list -- about as many entries as the chain has junctions -- is sorted by id << tile_bits | tile with
+// the radix kernels above, and a scan of the counts in that order gives every run the place of its first pair (RunDestSink
+// writes it back at the run's own index).  rs_place then ranks the pairs of a tile within their runs -- wave w owns the w-th
+// quarter of the tile, rounds are contiguous 64-pair slices, equal ids inside a round are ranked by lane: memory order, as in
+// rs_scatter, so the result is the stable sort's, bit for bit -- and writes id and pair index straight to their places.  A
+// slice holds one or two distinct ids: the lanes of an id write consecutive addresses without an exchange through LDS, and
+// instead of one ballot per digit bit the wavefront takes its distinct ids one after the other.
+// ---------------------------------------------------------------------------------------------
+struct RunCountFn { // counts in sorted order
+    const u32 *cnt, *order;
+    __device__ u64 operator()(u64 i) const { return cnt[order[i]]; }
+};
+struct RunDestSink {
+    u32 *dest;
+    const u32 *order;
+    __device__ void operator()(u64 i, u64, u64 ex) const { dest[order[i]] = (u32)ex; }
+};
+__global__ __launch_bounds__(256) void rs_place(const u32 *jid_bam, const u32 *np, const u64 *run_key, const u32 *run_dest, const u32 *tile_first,
+                                                const u32 *tile_n, u32 run_cap, int tile_bits, u32 *kout, u32 *vout) {
+    __shared__ u32 s_dest[RUN_W];               // first place of the tile's pairs of id d, at d & (RUN_W - 1)
+    __shared__ unsigned short s_wcnt[4][RUN_W]; // pairs of that id per wave (16 bit: a wave owns 1 024 pairs)
+    const u32 n = *np;
+    const u32 tile = blockIdx.x;
+    if ((u64)tile * RS_TILE >= n) return; // the grid covers the host's limit (and a closed chain has no pairs)
+    for (u32 d = threadIdx.x; d < 2 * RUN_W; d += 256) ((u32 *)&s_wcnt[0][0])[d] = 0;
+    const u32 tf = tile_first[tile], tn = tf < run_cap ? min(tile_n[tile], min(RUN_W, run_cap - tf)) : 0u;
+    for (u32 e = threadIdx.x; e < tn; e += 256) s_dest[(u32)(run_key[tf + e] >> tile_bits) & (RUN_W - 1u)] = run_dest[tf + e];
+    const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = lane_id();
+    unsigned short *wc = s_wcnt[w];
+    const u32 base = tile * RS_TILE + w * (RS_TILE / 4);
+    const u64 lt = (1ull << lane) - 1;
+    u32 id[RS_ITEMS];
+    u32 rkp[RS_ITEMS / 2]; // ranks within the wave's quarter (< 1 024), two per register
+    // (the id buffer has one tile of slack: the last tile loads unguarded, lanes past n are masked below)
+    const u32 *kp = jid_bam + base;
+#pragma unroll
+    for (int r = 0; r < RS_ITEMS; r++) id[r] = kp[r * 64 + lane];
+    __syncthreads();
+#pragma unroll
+    for (int r = 0; r < RS_ITEMS; r++) {
+        const bool valid = base + r * 64 + lane < n;
+        const u32 d = id[r] & (RUN_W - 1u);
+        u32 rank = 0;
+        u64 todo = __ballot(valid);
+        while (todo) {
+            const int first = __ffsll((long long)todo) - 1;
+            const u32 idc = (u32)__builtin_amdgcn_readlane((int)id[r], first);
+            const bool mine = valid && id[r] == idc;
+            const u64 m = __ballot(mine);
+            u32 before = 0;
+            if (lane == first) {
+                before = wc[d];
+                wc[d] = (unsigned short)(before + (u32)__popcll(m));
+            }
+            before = (u32)__builtin_amdgcn_readlane((int)before, first);
+            if (mine) rank = before + (u32)__popcll(m & lt);
+            todo &= ~m;
+        }
+        rkp[r >> 1] = (r & 1) ? (rkp[r >> 1] | (rank << 16)) : rank;
+    }
+    __syncthreads();
+#pragma unroll
+    for (int r = 0; r < RS_ITEMS; r++) {
+        const u32 i = base + r * 64 + lane;
+        const u32 d = id[r] & (RUN_W - 1u);
+        u32 dst = s_dest[d] + ((rkp[r >> 1] >> ((r & 1) * 16)) & 0xffffu);
+        for (int q = 0; q < w; q++) dst += s_wcnt[q][d]; // the id's pairs in the waves before this one
+        if (i < n && dst < n) { // (dst < n always: every id of the tile has its entry)
+            kout[dst] = id[r];
+            vout[dst] = i;
+        }
     }
 }
 
