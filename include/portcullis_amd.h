@@ -540,6 +540,42 @@ typedef struct pjb_markov_models {
 int pjb_filt_features(pjb_ctx *ctx, const pjb_junction_row *rows, int64_t n_rows, double mean_read_length, uint32_t l95,
                       const pjb_markov_models *models, double *features_out /* n_rows x PJB_N_FEATURES, host */);
 
+/* ---- `portcullis filt` forest stage: a saved ranger probability forest walked on the device -------------------
+ * Tree::predict (deps/ranger-0.3.8/src/Tree.cpp:125-180) and ForestProbability::predictInternal
+ * (src/ForestProbability.cpp:111-131): from node 0, value <= split value goes left, anything else (a NaN too) right; at
+ * the terminal node counts[c] / n_trees is added for every class, tree after tree in file order.  The predictions are
+ * bit-equal to that sequential sum.  A forest is plain arrays: the nodes of all trees one after the other. */
+typedef struct pjb_forest {
+    int32_t n_trees, n_classes, n_vars; /* n_vars: columns of the data matrix, the dependent one included */
+    int32_t dependent_var;              /* its column: present in the matrix, never read */
+    const uint8_t *is_ordered;          /* n_vars; NULL = every variable ordered */
+    const int64_t *tree_off;            /* n_trees + 1: tree t owns the nodes tree_off[t] .. tree_off[t + 1] */
+    const int32_t *left, *right;        /* per node: children as indices inside the tree; both -1 at a terminal node */
+    const int32_t *split_var;           /* per node (read at internal nodes only) */
+    const double *split_value;
+    const int64_t *count_off;           /* per node: where its class counts start in `counts`; -1 = the node has none */
+    const double *counts;               /* n_classes values per terminal node */
+    int64_t n_counts;                   /* length of `counts` */
+} pjb_forest;
+/* Host arithmetic only (no context, no device).  PJB_OK: the forest can be walked by a kernel and every walk ends: n_trees >= 1,
+ * 1..PJB_FOREST_MAX_CLASSES classes, 1..PJB_FOREST_MAX_VARS variables, every tree has a node, every node 0 or 2 children, both
+ * inside the tree and behind their parent (ranger numbers children after parents), no node the child of two, every terminal
+ * node n_classes counts inside `counts`, split variables < n_vars, ordered and not the dependent one.  Anything else is
+ * PJB_ERR_ARG with the tree and the node in msg (len bytes, may be NULL). */
+#define PJB_FOREST_MAX_CLASSES 16
+#define PJB_FOREST_MAX_VARS 2048
+int pjb_forest_check(const pjb_forest *forest, char *msg, int len);
+/* Checks (a forest that fails never reaches the device), packs and uploads: one forest per context, a new one replaces the old,
+ * pjb_destroy frees it. */
+int pjb_forest_load(pjb_ctx *ctx, const pjb_forest *forest);
+/* data: row-major n_rows x n_cols, n_cols == the forest's n_vars; pred: n_rows x n_classes.  PJB_ERR_STATE without a forest. */
+int pjb_forest_predict(pjb_ctx *ctx, const double *data, int64_t n_rows, int32_t n_cols, double *pred);
+/* The fused path of `filt`: the feature rows of pjb_filt_features stay on the device and are walked there.  var_feature[v] is
+ * the column of the PJB_N_FEATURES row that is the forest's variable v (the dependent variable's entry is not read).
+ * features_out (optional): n_rows x PJB_N_FEATURES, the rows pjb_filt_features would have returned. */
+int pjb_filt_scores(pjb_ctx *ctx, const pjb_junction_row *rows, int64_t n_rows, double mean_read_length, uint32_t l95,
+                    const pjb_markov_models *models, const int32_t *var_feature, double *pred, double *features_out);
+
 /* ---- `portcullis bamfilt` ----------------------------------------------------------------
  * The per-alignment decision of BamFilter::filter (src/bam_filter.cc:152-247): walk the CIGAR as
  * BamFilter::containsJunctionInSystem / clipMSR do (src/bam_filter.cc:75-150) and probe the set of junctions that

@@ -1,7 +1,9 @@
 // pjb_extra_api.hip -- the part of the C ABI behind `junc --extra` (depth, flanking counts, name multiplicities: pjb_extra_finish), `bamfilt`
-// (pjb_filter_*) and `filt`'s feature rows (pjb_filt_features); kernels in pjb_extra.hip.h.
+// (pjb_filter_*) and `filt`'s feature rows and forest (pjb_filt_features, pjb_forest_*, pjb_filt_scores); kernels in pjb_extra.hip.h and
+// pjb_forest.hip.h.
 #include "pjb_host.hip.h"
 #include "pjb_extra.hip.h"
+#include "pjb_forest.hip.h"
 
 // The name codes of a chain's spliced records, in BAM order, to `codes`; their number to cnt->n_spliced.  Through the tile lists the
 // chain's first kernels left in its slot (tile numbers run through the chain).
@@ -342,6 +344,59 @@ int extra_contig(pjb_ctx *c, Flight &f, const pjb_region_result *res, u64 n_spli
 // counts from the control block in device memory (ContigStats) and stand still when a limit is exceeded.  Nothing
 // here waits for the device: the last kernels (rows stream) write rows and control block into page-locked host memory
 // and pjb_finish_contig_end waits for their event -- by which time the next contig may be queued behind this one.
+// `filt`: uploads the junctions and the models and queues kg_features on the context's stream; the rows are in c->g_out, the "a genome is
+// missing" flag in c->g_bad.  Nothing waits here (rows and models are pageable: the caller's wait comes before it returns).
+static int features_queue(pjb_ctx *c, const pjb_junction_row *rows, size_t n, double mean_read_length, uint32_t l95, const pjb_markov_models *models) {
+    hipStream_t st = c->stream;
+    int rc;
+    if ((rc = ensure(c, c->g_rows, n * sizeof(pjb_junction_row)))) return rc;
+    if ((rc = ensure(c, c->g_models, ((size_t)6 * PJB_KMER_TABLE + 2 * PJB_PW_LEN * 5) * sizeof(double)))) return rc;
+    if ((rc = ensure(c, c->g_refs, std::max<size_t>(c->contigs.size(), 1) * sizeof(GenomeRef)))) return rc;
+    if ((rc = ensure(c, c->g_out, n * PJB_N_FEATURES * sizeof(double)))) return rc;
+    if ((rc = ensure(c, c->g_bad, sizeof(int)))) return rc;
+    HIP_TRY(c, hipMemcpyAsync(c->g_rows.p, rows, n * sizeof(pjb_junction_row), hipMemcpyHostToDevice, st));
+    DevModels M;
+    memset(&M, 0, sizeof M);
+    double *dm = (double *)c->g_models.p;
+    const double *src[8] = {models->exon, models->intron, models->donor_t, models->donor_f, models->acceptor_t, models->acceptor_f,
+                            models->donor_pw, models->acceptor_pw};
+    const double **dst[8] = {&M.exon, &M.intron, &M.don_t, &M.don_f, &M.acc_t, &M.acc_f, &M.don_pw, &M.acc_pw};
+    size_t at = 0;
+    for (int k = 0; k < 8; k++) {
+        const size_t cnt = k < 6 ? (size_t)PJB_KMER_TABLE : (size_t)PJB_PW_LEN * 5;
+        if (src[k]) {
+            HIP_TRY(c, hipMemcpyAsync(dm + at, src[k], cnt * sizeof(double), hipMemcpyHostToDevice, st));
+            *dst[k] = dm + at;
+        }
+        at += cnt;
+    }
+    M.exon_size = models->exon ? models->exon_size : 0;
+    M.intron_size = models->intron ? models->intron_size : 0;
+    M.don_pw_size = models->donor_pw ? models->donor_pw_size : 0;
+    M.acc_pw_size = models->acceptor_pw ? models->acceptor_pw_size : 0;
+    std::vector<GenomeRef> refs(std::max<size_t>(c->contigs.size(), 1));
+    for (size_t t = 0; t < c->contigs.size(); t++) {
+        refs[t].d = c->contigs[t].present ? c->contigs[t].d : nullptr;
+        refs[t].len = (int32_t)c->contigs[t].len;
+    }
+    HIP_TRY(c, hipMemcpyAsync(c->g_refs.p, refs.data(), refs.size() * sizeof(GenomeRef), hipMemcpyHostToDevice, st));
+    HIP_TRY(c, hipMemsetAsync(c->g_bad.p, 0, sizeof(int), st));
+    LAUNCH(c, "kg_features", kg_features, dim3((unsigned)((n + 255) / 256)), dim3(256), (const pjb_junction_row *)c->g_rows.p, (u32)n,
+           (const GenomeRef *)c->g_refs.p, (int)c->contigs.size(), M, mean_read_length, (u32)l95, (double *)c->g_out.p, (int *)c->g_bad.p);
+    return PJB_OK;
+}
+
+// queues the walk of the context's forest over n rows of `data` (device; `stride` doubles a row); predictions to c->r_pred
+static int forest_queue(pjb_ctx *c, const double *data, size_t n, u32 stride, const int32_t *colmap) {
+    int rc;
+    if ((rc = ensure(c, c->r_pred, n * (size_t)c->r_classes * sizeof(double)))) return rc;
+    const size_t lds = (size_t)FOREST_BLOCK * (size_t)c->r_classes * sizeof(double) + (size_t)c->r_vars * sizeof(int32_t);
+    LAUNCH_LDS(c, "kr_forest", kr_forest, dim3((unsigned)((n + FOREST_BLOCK - 1) / FOREST_BLOCK)), dim3(FOREST_BLOCK), lds, (const ForestNode *)c->r_nodes.p,
+               (const u32 *)c->r_roots.p, (u32)c->r_trees, (u32)c->r_classes, (u32)c->r_vars, (const double *)c->r_leaf.p, data, (u32)n, stride, colmap,
+               (double *)c->r_pred.p);
+    return PJB_OK;
+}
+
 extern "C" {
 int pjb_extra_finish(pjb_ctx *c, const pjb_extra_row **rows_out, int64_t *n_out) {
     if (!c || !rows_out || !n_out) return PJB_ERR_ARG;
@@ -489,46 +544,158 @@ int pjb_filt_features(pjb_ctx *c, const pjb_junction_row *rows, int64_t n_rows, 
     hipStream_t st = c->stream;
     const size_t n = (size_t)n_rows;
     int rc;
-    if ((rc = ensure(c, c->g_rows, n * sizeof(pjb_junction_row)))) return rc;
-    if ((rc = ensure(c, c->g_models, ((size_t)6 * PJB_KMER_TABLE + 2 * PJB_PW_LEN * 5) * sizeof(double)))) return rc;
-    if ((rc = ensure(c, c->g_refs, std::max<size_t>(c->contigs.size(), 1) * sizeof(GenomeRef)))) return rc;
-    if ((rc = ensure(c, c->g_out, n * PJB_N_FEATURES * sizeof(double)))) return rc;
-    if ((rc = ensure(c, c->g_bad, sizeof(int)))) return rc;
-    HIP_TRY(c, hipMemcpyAsync(c->g_rows.p, rows, n * sizeof(pjb_junction_row), hipMemcpyHostToDevice, st));
-    DevModels M;
-    memset(&M, 0, sizeof M);
-    double *dm = (double *)c->g_models.p;
-    const double *src[8] = {models->exon, models->intron, models->donor_t, models->donor_f, models->acceptor_t, models->acceptor_f,
-                            models->donor_pw, models->acceptor_pw};
-    const double **dst[8] = {&M.exon, &M.intron, &M.don_t, &M.don_f, &M.acc_t, &M.acc_f, &M.don_pw, &M.acc_pw};
-    size_t at = 0;
-    for (int k = 0; k < 8; k++) {
-        const size_t cnt = k < 6 ? (size_t)PJB_KMER_TABLE : (size_t)PJB_PW_LEN * 5;
-        if (src[k]) {
-            HIP_TRY(c, hipMemcpyAsync(dm + at, src[k], cnt * sizeof(double), hipMemcpyHostToDevice, st));
-            *dst[k] = dm + at;
-        }
-        at += cnt;
-    }
-    M.exon_size = models->exon ? models->exon_size : 0;
-    M.intron_size = models->intron ? models->intron_size : 0;
-    M.don_pw_size = models->donor_pw ? models->donor_pw_size : 0;
-    M.acc_pw_size = models->acceptor_pw ? models->acceptor_pw_size : 0;
-    std::vector<GenomeRef> refs(std::max<size_t>(c->contigs.size(), 1));
-    for (size_t t = 0; t < c->contigs.size(); t++) {
-        refs[t].d = c->contigs[t].present ? c->contigs[t].d : nullptr;
-        refs[t].len = (int32_t)c->contigs[t].len;
-    }
-    HIP_TRY(c, hipMemcpyAsync(c->g_refs.p, refs.data(), refs.size() * sizeof(GenomeRef), hipMemcpyHostToDevice, st));
-    HIP_TRY(c, hipMemsetAsync(c->g_bad.p, 0, sizeof(int), st));
-    LAUNCH(c, "kg_features", kg_features, dim3((unsigned)((n + 255) / 256)), dim3(256), (const pjb_junction_row *)c->g_rows.p, (u32)n,
-           (const GenomeRef *)c->g_refs.p, (int)c->contigs.size(), M, mean_read_length, (u32)l95, (double *)c->g_out.p, (int *)c->g_bad.p);
+    if ((rc = features_queue(c, rows, n, mean_read_length, l95, models))) return rc;
     int bad = 0;
     HIP_TRY(c, hipMemcpyAsync(features_out, c->g_out.p, n * PJB_N_FEATURES * sizeof(double), hipMemcpyDeviceToHost, st));
     HIP_TRY(c, hipMemcpyAsync(&bad, c->g_bad.p, sizeof(int), hipMemcpyDeviceToHost, st));
     HIP_TRY(c, hipStreamSynchronize(st));
     if (c->ktime) ev_collect(c, MISC_POOL);
     if (bad) return fail(c, PJB_ERR_STATE, "pjb_filt_features: a junction lies on a target whose genome was not uploaded");
+    return PJB_OK;
+}
+
+int pjb_forest_check(const pjb_forest *f, char *msg, int len) {
+    auto no = [&](const char *fmt, long long a, long long b) {
+        if (msg && len > 0) snprintf(msg, (size_t)len, fmt, a, b);
+        return PJB_ERR_ARG;
+    };
+    if (!f) return no("pjb_forest_check: no forest", 0, 0);
+    if (f->n_trees < 1) return no("forest: %lld trees (at least one is needed)", f->n_trees, 0);
+    if (f->n_classes < 1 || f->n_classes > PJB_FOREST_MAX_CLASSES) return no("forest: %lld classes (1 to %lld can be walked)", f->n_classes, PJB_FOREST_MAX_CLASSES);
+    if (f->n_vars < 1 || f->n_vars > PJB_FOREST_MAX_VARS) return no("forest: %lld variables (1 to %lld can be walked)", f->n_vars, PJB_FOREST_MAX_VARS);
+    if (f->dependent_var < 0 || f->dependent_var >= f->n_vars) return no("forest: dependent variable %lld of %lld variables", f->dependent_var, f->n_vars);
+    if (!f->tree_off || !f->left || !f->right || !f->split_var || !f->split_value || !f->count_off || (!f->counts && f->n_counts > 0) || f->n_counts < 0)
+        return no("forest: an array is missing", 0, 0);
+    if (f->is_ordered)
+        for (int32_t v = 0; v < f->n_vars; v++)
+            if (!f->is_ordered[v]) return no("forest: variable %lld is unordered (only ordered variables can be walked)", v, 0);
+    if (f->tree_off[0] != 0) return no("forest: the first tree starts at node %lld", (long long)f->tree_off[0], 0);
+    if (f->tree_off[f->n_trees] > 0x7ffffff0ll) return no("forest: %lld nodes", (long long)f->tree_off[f->n_trees], 0);
+    std::vector<uint8_t> has_parent;
+    for (int32_t t = 0; t < f->n_trees; t++) {
+        const int64_t base = f->tree_off[t], n = f->tree_off[t + 1] - base;
+        if (n < 1 || n > 0x7ffffff0ll) return no("forest: tree %lld has %lld nodes", t, (long long)n);
+        has_parent.assign((size_t)n, 0);
+        for (int64_t k = 0; k < n; k++) {
+            const int64_t l = f->left[base + k], r = f->right[base + k];
+            if (l < 0 && r < 0) { // terminal
+                const int64_t at = f->count_off[base + k];
+                if (at < 0 || at > f->n_counts - f->n_classes) return no("forest: tree %lld, node %lld: a terminal node without its class counts", t, (long long)k);
+                continue;
+            }
+            if (l < 0 || r < 0) return no("forest: tree %lld, node %lld has one child only", t, (long long)k);
+            if (l >= n || r >= n) return no("forest: tree %lld, node %lld: a child lies outside the tree", t, (long long)k);
+            if (l <= k || r <= k) return no("forest: tree %lld, node %lld: a child is not behind its parent", t, (long long)k);
+            if (l == r || has_parent[(size_t)l] || has_parent[(size_t)r]) return no("forest: tree %lld, node %lld: a child has two parents", t, (long long)k);
+            has_parent[(size_t)l] = has_parent[(size_t)r] = 1;
+            const int32_t v = f->split_var[base + k];
+            if (v < 0 || v >= f->n_vars) return no("forest: tree %lld, node %lld splits on a variable the data does not have", t, (long long)k);
+            if (v == f->dependent_var) return no("forest: tree %lld, node %lld splits on the dependent variable", t, (long long)k);
+        }
+    }
+    return PJB_OK;
+}
+
+int pjb_forest_load(pjb_ctx *c, const pjb_forest *f) {
+    if (!c) return PJB_ERR_ARG;
+    char msg[200] = "";
+    if (pjb_forest_check(f, msg, (int)sizeof msg) != PJB_OK) return fail(c, PJB_ERR_ARG, "pjb_forest_load: %s", msg);
+    // pack: each tree breadth first from its root, so that the two children of a node are neighbours (nodes nothing leads to are dropped)
+    std::vector<ForestNode> nodes;
+    std::vector<double> leaf;
+    std::vector<u32> roots((size_t)f->n_trees);
+    std::vector<int64_t> order;
+    nodes.reserve((size_t)f->tree_off[f->n_trees]);
+    for (int32_t t = 0; t < f->n_trees; t++) {
+        const int64_t base = f->tree_off[t];
+        const size_t first = nodes.size();
+        roots[(size_t)t] = (u32)first;
+        order.assign(1, 0);
+        for (size_t at = 0; at < order.size(); at++) {
+            const int64_t k = base + order[at];
+            ForestNode nd;
+            if (f->left[k] < 0) {
+                nd.split = 0.0;
+                nd.child = (u32)(leaf.size() / (size_t)f->n_classes);
+                nd.var = FOREST_LEAF;
+                for (int32_t cl = 0; cl < f->n_classes; cl++) leaf.push_back(f->counts[f->count_off[k] + cl] / (double)f->n_trees);
+            } else {
+                nd.split = f->split_value[k];
+                nd.child = (u32)(first + order.size());
+                nd.var = (u32)f->split_var[k];
+                order.push_back(f->left[k]);
+                order.push_back(f->right[k]);
+            }
+            nodes.push_back(nd);
+        }
+    }
+    HIP_TRY(c, hipSetDevice(c->cfg.device));
+    hipStream_t st = c->stream;
+    HIP_TRY(c, hipStreamSynchronize(st)); // (the arrays below are pageable, and a walk of the old forest may be queued)
+    c->r_trees = 0;
+    int rc;
+    if ((rc = ensure(c, c->r_nodes, nodes.size() * sizeof(ForestNode)))) return rc;
+    if ((rc = ensure(c, c->r_leaf, leaf.size() * sizeof(double)))) return rc;
+    if ((rc = ensure(c, c->r_roots, roots.size() * sizeof(u32)))) return rc;
+    HIP_TRY(c, hipMemcpyAsync(c->r_nodes.p, nodes.data(), nodes.size() * sizeof(ForestNode), hipMemcpyHostToDevice, st));
+    HIP_TRY(c, hipMemcpyAsync(c->r_leaf.p, leaf.data(), leaf.size() * sizeof(double), hipMemcpyHostToDevice, st));
+    HIP_TRY(c, hipMemcpyAsync(c->r_roots.p, roots.data(), roots.size() * sizeof(u32), hipMemcpyHostToDevice, st));
+    HIP_TRY(c, hipStreamSynchronize(st));
+    c->r_trees = f->n_trees;
+    c->r_classes = f->n_classes;
+    c->r_vars = f->n_vars;
+    c->r_dep = f->dependent_var;
+    return PJB_OK;
+}
+
+int pjb_forest_predict(pjb_ctx *c, const double *data, int64_t n_rows, int32_t n_cols, double *pred) {
+    if (!c) return PJB_ERR_ARG;
+    if (!c->r_trees) return fail(c, PJB_ERR_STATE, "pjb_forest_predict: no forest was loaded (pjb_forest_load)");
+    if (n_rows < 0 || n_rows > 0xfffffff0ll || (n_rows > 0 && (!data || !pred))) return fail(c, PJB_ERR_ARG, "pjb_forest_predict: bad arguments");
+    if (n_cols != c->r_vars) return fail(c, PJB_ERR_ARG, "pjb_forest_predict: the data has %d columns, the forest %d variables", n_cols, c->r_vars);
+    if (n_rows == 0) return PJB_OK;
+    HIP_TRY(c, hipSetDevice(c->cfg.device));
+    hipStream_t st = c->stream;
+    const size_t n = (size_t)n_rows;
+    int rc;
+    if ((rc = ensure(c, c->r_data, n * (size_t)n_cols * sizeof(double)))) return rc;
+    HIP_TRY(c, hipMemcpyAsync(c->r_data.p, data, n * (size_t)n_cols * sizeof(double), hipMemcpyHostToDevice, st));
+    if ((rc = forest_queue(c, (const double *)c->r_data.p, n, (u32)n_cols, nullptr))) return rc;
+    HIP_TRY(c, hipMemcpyAsync(pred, c->r_pred.p, n * (size_t)c->r_classes * sizeof(double), hipMemcpyDeviceToHost, st));
+    HIP_TRY(c, hipStreamSynchronize(st));
+    if (c->ktime) ev_collect(c, MISC_POOL);
+    return PJB_OK;
+}
+
+int pjb_filt_scores(pjb_ctx *c, const pjb_junction_row *rows, int64_t n_rows, double mean_read_length, uint32_t l95,
+                    const pjb_markov_models *models, const int32_t *var_feature, double *pred, double *features_out) {
+    if (!c) return PJB_ERR_ARG;
+    if (!c->r_trees) return fail(c, PJB_ERR_STATE, "pjb_filt_scores: no forest was loaded (pjb_forest_load)");
+    if (n_rows < 0 || (n_rows > 0 && (!rows || !pred)) || !models || !var_feature || n_rows > 0xfffffff0ll)
+        return fail(c, PJB_ERR_ARG, "pjb_filt_scores: bad arguments");
+    std::vector<int32_t> colmap((size_t)c->r_vars, 0);
+    for (int32_t v = 0; v < c->r_vars; v++) {
+        if (v == c->r_dep) continue; // (never read)
+        if (var_feature[v] < 0 || var_feature[v] >= PJB_N_FEATURES)
+            return fail(c, PJB_ERR_ARG, "pjb_filt_scores: variable %d is column %d of a feature row of %d", v, var_feature[v], PJB_N_FEATURES);
+        colmap[(size_t)v] = var_feature[v];
+    }
+    if (n_rows == 0) return PJB_OK;
+    HIP_TRY(c, hipSetDevice(c->cfg.device));
+    hipStream_t st = c->stream;
+    const size_t n = (size_t)n_rows;
+    int rc;
+    if ((rc = ensure(c, c->r_colmap, colmap.size() * sizeof(int32_t)))) return rc;
+    HIP_TRY(c, hipMemcpyAsync(c->r_colmap.p, colmap.data(), colmap.size() * sizeof(int32_t), hipMemcpyHostToDevice, st));
+    if ((rc = features_queue(c, rows, n, mean_read_length, l95, models))) return rc;
+    if ((rc = forest_queue(c, (const double *)c->g_out.p, n, (u32)PJB_N_FEATURES, (const int32_t *)c->r_colmap.p))) return rc;
+    int bad = 0;
+    HIP_TRY(c, hipMemcpyAsync(pred, c->r_pred.p, n * (size_t)c->r_classes * sizeof(double), hipMemcpyDeviceToHost, st));
+    if (features_out) HIP_TRY(c, hipMemcpyAsync(features_out, c->g_out.p, n * PJB_N_FEATURES * sizeof(double), hipMemcpyDeviceToHost, st));
+    HIP_TRY(c, hipMemcpyAsync(&bad, c->g_bad.p, sizeof(int), hipMemcpyDeviceToHost, st));
+    HIP_TRY(c, hipStreamSynchronize(st)); // (the one wait; colmap is pageable and lives until here)
+    if (c->ktime) ev_collect(c, MISC_POOL);
+    if (bad) return fail(c, PJB_ERR_STATE, "pjb_filt_scores: a junction lies on a target whose genome was not uploaded");
     return PJB_OK;
 }
 

@@ -322,6 +322,8 @@ struct pjb_ctx {
     std::map<int32_t, std::pair<u64 *, u32>> filter_keys; // bamfilt: passing junctions per target (device, sorted)
     Buf f_pos, f_cigoff, f_cigar, f_codes;
     Buf g_rows, g_models, g_refs, g_out, g_bad; // filt feature rows
+    Buf r_nodes, r_leaf, r_roots, r_data, r_pred, r_colmap; // filt forest (pjb_forest.hip.h): packed nodes, leaf rows, tree roots; matrix, predictions, columns
+    int32_t r_trees = 0, r_classes = 0, r_vars = 0, r_dep = 0; // r_trees == 0: no forest loaded
     Buf x_pos, x_endx, x_q, x_prefq, x_ce, x_bound, x_de, x_dropped, x_zlist, x_cnt, x_tabk, x_tabc, x_rs, x_re, x_rr, x_tileoff;
     Buf x_xrall, x_tab; // x_tab: the name table (NameSlot), x_tab_slots slots, holding the codes of x_tab_n spliced records
     size_t x_tab_slots = 0, x_tab_n = 0;

@@ -27,6 +27,7 @@ EXPORTS = [
     "pjb_select_timed_kernels", "pjb_host_alloc", "pjb_host_free", "pjb_host_register", "pjb_host_unregister", "pjb_inflate_bgzf", "pjb_deflate_bgzf", "pjb_submit_bam", "pjb_collect_device", "pjb_set_row_mirror",
     "pjb_extra_finish", "pjb_set_option", "pjb_merge_rows", "pjb_plan_groups", "pjb_bam_begin", "pjb_bam_piece", "pjb_bam_pieces_done", "pjb_bam_end", "pjb_bam_inflate_done", "pjb_filter_set_junctions", "pjb_filter_batch", "pjb_filt_features",
     "pjb_index_begin", "pjb_index_piece", "pjb_index_end",
+    "pjb_forest_check", "pjb_forest_load", "pjb_forest_predict", "pjb_filt_scores",
 ]
 N_FEATURES = 34
 KMER_TABLE = 3125 * 5
@@ -53,6 +54,11 @@ class PjbBatch(C.Structure):
 class PjbMarkovModels(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in ("exon", "intron", "donor_t", "donor_f", "acceptor_t", "acceptor_f", "donor_pw", "acceptor_pw")] + [
         (n, C.c_int32) for n in ("exon_size", "intron_size", "donor_pw_size", "acceptor_pw_size")]
+
+
+class PjbForest(C.Structure):
+    _fields_ = [("n_trees", C.c_int32), ("n_classes", C.c_int32), ("n_vars", C.c_int32), ("dependent_var", C.c_int32)] + [
+        (n, C.c_void_p) for n in ("is_ordered", "tree_off", "left", "right", "split_var", "split_value", "count_off", "counts")] + [("n_counts", C.c_int64)]
 
 
 class PjbRegionResult(C.Structure):
@@ -149,6 +155,11 @@ def load():
         L.pjb_filter_set_junctions.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_int64]
         L.pjb_filter_batch.argtypes = [C.c_void_p, C.c_int32, C.POINTER(PjbBatch), C.c_int32, C.c_void_p]
         L.pjb_filt_features.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_double, C.c_uint32, C.POINTER(PjbMarkovModels), C.c_void_p]
+        L.pjb_forest_check.argtypes = [C.POINTER(PjbForest), C.c_char_p, C.c_int]
+        L.pjb_forest_load.argtypes = [C.c_void_p, C.POINTER(PjbForest)]
+        L.pjb_forest_predict.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p]
+        L.pjb_filt_scores.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_double, C.c_uint32, C.POINTER(PjbMarkovModels), C.c_void_p, C.c_void_p,
+                                      C.c_void_p]
         L.pjb_index_begin.argtypes = [C.c_void_p]
         L.pjb_index_piece.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int32, C.c_int32, C.POINTER(C.c_uint64)]
         L.pjb_index_end.argtypes = [C.c_void_p, C.POINTER(PjbIndexResult)]
@@ -465,11 +476,8 @@ class Context:
         self._check(self._L.pjb_filter_batch(self._h, tid, C.byref(pb), mode, out.ctypes.data_as(C.c_void_p)))
         return out[: batch.n]
 
-    def filt_features(self, rows, mean_read_length, l95, models):
-        """ModelFeatures::setRow for `rows` (ROW_DTYPE): float64 [n, N_FEATURES].  models: dict name -> float64 table
-        (exon, intron, donor_t, donor_f, acceptor_t, acceptor_f: KMER_TABLE; donor_pw, acceptor_pw: PW_LEN * 5; missing /
-        None = untrained) plus exon_size, intron_size, donor_pw_size, acceptor_pw_size."""
-        rows = np.ascontiguousarray(rows, dtype=ROW_DTYPE)
+    @staticmethod
+    def _markov_models(models):
         m = PjbMarkovModels()
         keep = []
         for name in ("exon", "intron", "donor_t", "donor_f", "acceptor_t", "acceptor_f", "donor_pw", "acceptor_pw"):
@@ -481,10 +489,43 @@ class Context:
                 setattr(m, name, t.ctypes.data)
         for name in ("exon_size", "intron_size", "donor_pw_size", "acceptor_pw_size"):
             setattr(m, name, int(models.get(name, 0)))
+        return m, keep
+
+    def filt_features(self, rows, mean_read_length, l95, models):
+        """ModelFeatures::setRow for `rows` (ROW_DTYPE): float64 [n, N_FEATURES].  models: dict name -> float64 table
+        (exon, intron, donor_t, donor_f, acceptor_t, acceptor_f: KMER_TABLE; donor_pw, acceptor_pw: PW_LEN * 5; missing /
+        None = untrained) plus exon_size, intron_size, donor_pw_size, acceptor_pw_size."""
+        rows = np.ascontiguousarray(rows, dtype=ROW_DTYPE)
+        m, keep = self._markov_models(models)
         out = np.zeros((max(len(rows), 1), N_FEATURES), dtype=np.float64)
         self._check(self._L.pjb_filt_features(self._h, rows.ctypes.data_as(C.c_void_p), len(rows), float(mean_read_length), int(l95),
                                               C.byref(m), out.ctypes.data_as(C.c_void_p)))
         return out[: len(rows)]
+
+    def forest_load(self, forest):
+        """pjb_forest_load: `forest` is a Forest (checked first; one per context, a new one replaces the old)."""
+        self._check(self._L.pjb_forest_load(self._h, C.byref(forest.struct())))
+        self._forest_classes = forest.n_classes
+
+    def forest_predict(self, data):
+        """pjb_forest_predict: data float64 [n, n_vars] -> float64 [n, n_classes]."""
+        data = np.ascontiguousarray(data, dtype=np.float64)
+        assert data.ndim == 2
+        out = np.zeros((max(len(data), 1), max(getattr(self, "_forest_classes", 1), 1)), dtype=np.float64)
+        self._check(self._L.pjb_forest_predict(self._h, data.ctypes.data_as(C.c_void_p), data.shape[0], data.shape[1], out.ctypes.data_as(C.c_void_p)))
+        return out[: len(data)]
+
+    def filt_scores(self, rows, mean_read_length, l95, models, var_feature, want_features=False):
+        """pjb_filt_scores: feature rows and forest walk in one call; float64 [n, n_classes] (and the [n, N_FEATURES] rows if asked)."""
+        rows = np.ascontiguousarray(rows, dtype=ROW_DTYPE)
+        m, keep = self._markov_models(models)
+        vf = np.ascontiguousarray(var_feature, dtype=np.int32)
+        out = np.zeros((max(len(rows), 1), max(getattr(self, "_forest_classes", 1), 1)), dtype=np.float64)
+        feat = np.zeros((max(len(rows), 1), N_FEATURES), dtype=np.float64) if want_features else None
+        self._check(self._L.pjb_filt_scores(self._h, rows.ctypes.data_as(C.c_void_p), len(rows), float(mean_read_length), int(l95), C.byref(m),
+                                            vf.ctypes.data_as(C.c_void_p), out.ctypes.data_as(C.c_void_p),
+                                            feat.ctypes.data_as(C.c_void_p) if want_features else None))
+        return (out[: len(rows)], feat[: len(rows)]) if want_features else out[: len(rows)]
 
     def clear_rows(self):
         self._check(self._L.pjb_clear_rows(self._h))
@@ -648,3 +689,90 @@ def plan_groups(ref_lens, tids, max_bases=1 << 30):
     if n < 0:
         raise PjbError(n, "pjb_plan_groups: bad arguments")
     return [[tids[k] for k in range(len(tids)) if g[k] == i] for i in range(n)]
+
+
+class Forest:
+    """A probability forest as the plain arrays of pjb_forest.  trees: a list of dicts with left / right (int, -1 at a terminal node),
+    split_var, split_value and counts (one list of n_classes values per node, empty at an internal node)."""
+
+    def __init__(self, n_vars, n_classes, trees, dependent_var=0, is_ordered=None):
+        self.n_trees, self.n_classes, self.n_vars, self.dependent_var = len(trees), int(n_classes), int(n_vars), int(dependent_var)
+        self.is_ordered = None if is_ordered is None else np.ascontiguousarray(is_ordered, dtype=np.uint8)
+        off, coff, counts = [0], [], []
+        for t in trees:
+            off.append(off[-1] + len(t["left"]))
+            for cnt in t["counts"]:
+                if len(cnt):
+                    coff.append(len(counts))
+                    counts.extend(float(v) for v in cnt)
+                else:
+                    coff.append(-1)
+        cat = lambda k, dt: np.ascontiguousarray(np.concatenate([np.asarray(t[k], dtype=dt) for t in trees]) if trees else np.zeros(0, dtype=dt))
+        self.tree_off = np.asarray(off, dtype=np.int64)
+        self.left, self.right, self.split_var = cat("left", np.int32), cat("right", np.int32), cat("split_var", np.int32)
+        self.split_value = cat("split_value", np.float64)
+        self.count_off = np.asarray(coff, dtype=np.int64)
+        self.counts = np.asarray(counts, dtype=np.float64)
+
+    def struct(self):
+        f = PjbForest()
+        f.n_trees, f.n_classes, f.n_vars, f.dependent_var = self.n_trees, self.n_classes, self.n_vars, self.dependent_var
+        f.is_ordered = None if self.is_ordered is None else self.is_ordered.ctypes.data
+        for name in ("tree_off", "left", "right", "split_var", "split_value", "count_off", "counts"):
+            a = getattr(self, name)
+            setattr(f, name, a.ctypes.data if a.size else None)
+        f.n_counts = len(self.counts)
+        return f
+
+    def check(self):
+        """pjb_forest_check (host arithmetic, no device): None if the forest can be walked, else the message."""
+        msg = C.create_string_buffer(256)
+        rc = load().pjb_forest_check(C.byref(self.struct()), msg, len(msg))
+        return None if rc == 0 else msg.value.decode()
+
+    @classmethod
+    def from_file(cls, path):
+        """ranger 0.3.8's saved probability forest (Forest::saveToFile): the layout host/src/forest.cc reads."""
+        import struct
+        raw = open(path, "rb").read()
+        at = 0
+
+        def take(fmt):
+            nonlocal at
+            if at + struct.calcsize(fmt) > len(raw):
+                raise ValueError("forest file is truncated")
+            v = struct.unpack_from("<" + fmt, raw, at)
+            at += struct.calcsize(fmt)
+            return v
+
+        def vec(fmt):
+            (n,) = take("Q")
+            if n > len(raw):
+                raise ValueError("forest file is truncated")
+            return list(take(f"{n}{fmt}"))
+
+        dep, n_trees = take("QQ")
+        ordered = vec("B")
+        (n_vars,) = take("Q")
+        (treetype,) = take("i")
+        if treetype != 9:
+            raise ValueError(f"not a probability forest (tree type {treetype})")
+        class_values = vec("d")
+        trees = []
+        for _ in range(n_trees):
+            (n_nodes,) = take("Q")
+            children = [vec("Q") for _ in range(n_nodes)]
+            split_var, split_value = vec("Q"), vec("d")
+            terminal = vec("Q")
+            (n_term,) = take("Q")
+            counts = [[] for _ in range(n_nodes)]
+            term_counts = [vec("d") for _ in range(n_term)]
+            for node, cnt in zip(terminal, term_counts):
+                counts[node] = cnt
+            trees.append(dict(left=[ch[0] if len(ch) else -1 for ch in children], right=[ch[1] if len(ch) > 1 else -1 for ch in children],
+                              split_var=split_var, split_value=split_value, counts=counts))
+        if at != len(raw):
+            raise ValueError("forest file is longer than its forest")
+        f = cls(n_vars, len(class_values), trees, dep, ordered)
+        f.class_values = class_values
+        return f

@@ -2,8 +2,9 @@
 // lib/src/model_features.cc:42-235): intron-size threshold, the Markov models trained from junction sets, and the
 // feature matrix.  Training walks genome windows on the host (it is a k-mer count); the matrix -- every junction's
 // windows scored against six k-mer and two position models -- comes from the device (pjb_filt_features).
-// The random-forest side (ranger) is not part of this build: juncs2FeatureVectors returns a plain row-major matrix
-// whose columns are VAR_NAMES + Junction::JAD_NAMES.
+// juncs2FeatureVectors returns a plain row-major matrix whose columns are VAR_NAMES + Junction::JAD_NAMES.  The random-forest
+// side: a saved forest (ml/forest.hpp) is walked on the device over the same rows without the matrix leaving it (forestPredict);
+// growing a forest (self-training) is not part of this build.
 #pragma once
 
 #include <string>
@@ -11,6 +12,7 @@
 
 #include "../bam/genome_mapper.hpp"
 #include "../junction.hpp"
+#include "forest.hpp"
 #include "markov_model.hpp"
 
 namespace portcullis {
@@ -44,6 +46,14 @@ public:
     static std::vector<std::string> featureNames();
     // row-major [x.size()][featureNames().size()] -- ModelFeatures::setRow for every junction of x
     std::vector<double> juncs2FeatureVectors(const JunctionList& x);
+    // the columns of that matrix the reference's filter leaves active, in order: the variables of its forests (29, "Genuine" first)
+    static const std::vector<int32_t>& activeFeatures();
+    // ForestProbability::predictInternal over the rows of x: row-major [x.size()][forest.classValues.size()], feature rows and walk on
+    // the device in one call (pjb_filt_scores).  featuresOut (optional): the full matrix as juncs2FeatureVectors lays it out, with the
+    // device's own columns 0 and 8.  Throws ForestException for a forest that cannot be walked or has other variables.
+    // host arithmetic only (pjb_forest_check and the number of variables): throws ForestException for a forest forestPredict would refuse
+    static void checkForest(const Forest& forest);
+    std::vector<double> forestPredict(const JunctionList& x, const Forest& forest, std::vector<double>* featuresOut = nullptr);
 };
 
 }  // namespace ml

@@ -1,0 +1,371 @@
+// JunctionFilter: see portcullis/junction_filter.hpp.  Line numbers refer to src/junction_filter.cc of the reference.
+#include <portcullis/junction_filter.hpp>
+
+#include <sys/stat.h>
+
+#include <algorithm>
+#include <chrono>
+#include <cstdio>
+#include <cstdlib>
+#include <fstream>
+#include <iomanip>
+#include <iostream>
+#include <unordered_set>
+
+#include "rule_filter.hpp"
+
+using std::cout;
+using std::endl;
+using std::string;
+
+namespace portcullis {
+
+namespace {
+bool exists(const string& p) {
+    struct stat st;
+    return stat(p.c_str(), &st) == 0;
+}
+bool isDirectory(const string& p) {
+    struct stat st;
+    return stat(p.c_str(), &st) == 0 && S_ISDIR(st.st_mode);
+}
+bool createDirectories(const string& p) {
+    string cur;
+    for (size_t i = 0; i <= p.size(); i++) {
+        if (i == p.size() || p[i] == '/') {
+            if (!cur.empty() && !exists(cur) && mkdir(cur.c_str(), 0777) != 0 && !exists(cur)) return false;
+        }
+        if (i < p.size()) cur.push_back(p[i]);
+    }
+    return isDirectory(p);
+}
+std::vector<string> splitOn(const string& s, char sep, bool compress) {
+    std::vector<string> parts(1);
+    for (const char c : s) {
+        if (c != sep) parts.back().push_back(c);
+        else if (!compress || !parts.back().empty() || parts.size() == 1) parts.emplace_back();
+    }
+    return parts;
+}
+string trim(const string& s) {
+    size_t a = 0, b = s.size();
+    while (a < b && isspace((unsigned char)s[a])) a++;
+    while (b > a && isspace((unsigned char)s[b - 1])) b--;
+    return s.substr(a, b - a);
+}
+string locationAsString(const Junction& j) { return j.getIntron()->toString() + bam::strandToChar(j.getConsensusStrand()); }
+}  // namespace
+
+void JunctionFilter::setCanonical(const string& canonical) {  // junction_filter.hpp:277-307
+    std::vector<string> modes;
+    for (const string& m : splitOn(canonical, ',', true))
+        if (!m.empty() || modes.empty()) modes.push_back(m);
+    if (modes.size() > 3) throw JuncFilterException("Canonical filter mode contains too many modes.  Max is 2.");
+    filterCanonical = filterSemi = filterNovel = true;
+    for (string n : modes) {
+        std::transform(n.begin(), n.end(), n.begin(), [](unsigned char c) { return (char)toupper(c); });
+        if (n == "OFF") filterCanonical = filterSemi = filterNovel = false;
+        else if (n == "C") filterCanonical = false;
+        else if (n == "S") filterSemi = false;
+        else if (n == "N") filterNovel = false;
+    }
+}
+
+void JunctionFilter::printFilteringResults(const JunctionList& in, const JunctionList& pass, const JunctionList& fail, const string& prefix) {  // :607-620
+    (void)fail;
+    const size_t diff = in.size() - pass.size();
+    cout << endl << prefix << endl << "-------------------------" << endl << "Input contained " << in.size() << " junctions." << endl
+         << "Output contains " << pass.size() << " junctions." << endl << "Filtered out " << diff << " junctions." << endl;
+}
+
+void JunctionFilter::forestPredict(const JunctionList& all, JunctionList& pass, JunctionList& fail, ml::ModelFeatures& mf, const ml::Forest& forest) {  // :646-738
+    cout << "Creating feature vector" << endl << "Initialising random forest" << endl << "Making predictions" << endl;
+    std::vector<double> features;
+    mf.setDevice(device);
+    const std::vector<double> pred = mf.forestPredict(all, forest, saveFeatures ? &features : nullptr);
+    const size_t nClasses = forest.classValues.size();
+    if (saveFeatures) {  // :649-657: the active columns, default stream formatting
+        std::ofstream fout((output + ".features.testing").c_str());
+        const std::vector<string> names = ml::ModelFeatures::featureNames();
+        const std::vector<int32_t>& active = ml::ModelFeatures::activeFeatures();
+        fout << Intron::locationOutputHeader();
+        for (const int32_t k : active) fout << "\t" << names[(size_t)k];
+        fout << endl;
+        for (size_t i = 0; i < all.size(); i++) {
+            fout << *(all[i]->getIntron());
+            for (const int32_t k : active) fout << "\t" << features[i * names.size() + (size_t)k];
+            fout << endl;
+        }
+    }
+    for (size_t i = 0; i < all.size(); i++) all[i]->setScore(1.0 - pred[i * nClasses]);  // 1 - P(class_values[0])
+    cout << "Threshold set at " << threshold << endl;
+    for (size_t i = 0; i < all.size(); i++) {  // categorise, :730-738
+        if ((1.0 - pred[i * nClasses]) >= threshold) pass.push_back(all[i]);
+        else fail.push_back(all[i]);
+    }
+}
+
+void JunctionFilter::filter() {  // :153-596
+    size_t slash = output.find_last_of('/');
+    string outputDir = slash == string::npos ? string(".") : output.substr(0, slash);
+    const string outputPrefix = slash == string::npos ? output : output.substr(slash + 1);
+    if (outputDir.empty()) outputDir = "/";
+    if (train)
+        throw JuncFilterException("Self-training a random forest model is not built into portcullis_amd filt.  Pass a saved model with --model_file (the "
+                                  "<prefix>.selftrain.forest file a reference run leaves), or filter with rules only: --no_ml with --filter_file.");
+    if (!exists(junctionFile)) throw JuncFilterException("Could not find junction file at: " + junctionFile);
+    if (!exists(prepData.getGenomeFilePath())) throw JuncFilterException("Could not find prepared genome file at: " + prepData.getGenomeFilePath());
+    if (!modelFile.empty() && !exists(modelFile)) throw JuncFilterException("Could not find filter model file at: " + modelFile);
+    if (!filterFile.empty() && !exists(filterFile)) throw JuncFilterException("Could not find filter configuration file at: " + filterFile);
+    if (!referenceFile.empty() && !exists(referenceFile)) throw JuncFilterException("Could not find reference BED file at: " + referenceFile);
+    if (!exists(outputDir)) {
+        if (!createDirectories(outputDir)) throw JuncFilterException("Could not create output directory at: " + outputDir);
+    } else if (!isDirectory(outputDir))
+        throw JuncFilterException("File exists with name of suggested output directory: " + outputDir);
+    cout << "Loading junctions from " << junctionFile << " ...";
+    cout.flush();
+    JunctionSystem originalJuncs(junctionFile);
+    cout << " done." << endl << "Found " << originalJuncs.getJunctions().size() << " junctions." << endl << endl;
+    JunctionList currentJuncs = originalJuncs.getJunctions();
+
+    std::unordered_set<string> ref;
+    if (!referenceFile.empty()) {  // :204-224
+        cout << "Loading junctions from reference: " << referenceFile << " ...";
+        cout.flush();
+        std::ifstream ifs(referenceFile.c_str());
+        string line;
+        while (std::getline(ifs, line)) {
+            const std::vector<string> parts = splitOn(trim(line), '\t', true);
+            if (parts.size() == 12) {  // any other line is no entry
+                const int end = std::stoi(parts[7]) - 1;  // BED to portcullis coordinates
+                ref.insert(parts[0] + "(" + parts[6] + "," + std::to_string(end) + ")" + parts[5]);
+            }
+        }
+        cout << " done." << endl << "Found " << ref.size() << " junctions in reference." << endl << endl;
+    }
+
+    JunctionSystem discardedJuncs;
+    if (!modelFile.empty()) {  // :441-456
+        const ml::Forest forest = ml::Forest::load(modelFile);  // (read and checked before the genome or a device is touched)
+        ml::ModelFeatures::checkForest(forest);
+        ml::ModelFeatures mf;  // L95 = 0, untrained Markov models: nothing was trained in this run
+        mf.initGenomeMapper(prepData.getGenomeFilePath());
+        cout << "Predicting valid junctions using random forest model" << endl << "----------------------------------------------------" << endl << endl;
+        JunctionList passJuncs, failJuncs;
+        forestPredict(currentJuncs, passJuncs, failJuncs, mf, forest);
+        printFilteringResults(currentJuncs, passJuncs, failJuncs, "Random Forest filtering results");
+        currentJuncs = passJuncs;
+        for (auto& j : failJuncs) discardedJuncs.addJunction(j);
+    }
+
+    if (currentJuncs.empty()) {
+        cout << "WARNING: No junctions left from input.  Will not apply any further filters." << endl;
+    } else {
+        if (!filterFile.empty()) {  // :463-503, without the script and its intermediate files
+            RuleFilter rules = RuleFilter::load(filterFile);
+            std::vector<string> fieldnames = splitOn(Junction::junctionOutputHeader(), '\t', false);
+            const size_t scoreAt = (size_t)(std::find(fieldnames.begin(), fieldnames.end(), "score") - fieldnames.begin());
+            fieldnames.erase(fieldnames.begin());  // (the index column is the table's index, not a field)
+            std::vector<std::vector<string>> table;
+            table.reserve(currentJuncs.size());
+            string row;
+            for (auto& j : currentJuncs) {
+                row.clear();
+                j->appendTabRow(row);  // what the .rules_in table would hold
+                std::vector<string> cells = splitOn(row, '\t', false);
+                j->setScore(strtod(cells.at(scoreAt).c_str(), nullptr));  // the junctions come back from a table: the score as printed (the one value not read from one)
+                cells.erase(cells.begin());
+                table.push_back(std::move(cells));
+            }
+            const std::vector<char> passed = rules.evaluate(fieldnames, table);
+            JunctionList passJuncs, failJuncs;
+            for (size_t i = 0; i < currentJuncs.size(); i++) (passed[i] ? passJuncs : failJuncs).push_back(currentJuncs[i]);
+            std::sort(passJuncs.begin(), passJuncs.end(), JunctionComparator());  // posSystem.sort() / negSystem.sort()
+            std::sort(failJuncs.begin(), failJuncs.end(), JunctionComparator());
+            currentJuncs = passJuncs;
+            for (auto& j : failJuncs) discardedJuncs.addJunction(j);
+        }
+        if (currentJuncs.empty()) {
+            cout << "WARNING: Rule-based filter discarded all junctions from input.  Will not apply any further filters." << endl;
+        } else if (maxLength > 0 || doCanonicalFiltering() || minCov > 1) {  // :509-546
+            JunctionList passJuncs, failJuncs;
+            for (auto& j : currentJuncs) {
+                bool pass = true;
+                if (maxLength > 0 && j->getIntronSize() > maxLength) pass = false;
+                if (pass && doCanonicalFiltering()) {
+                    if (filterNovel && j->getSpliceSiteType() == CanonicalSS::NO) pass = false;
+                    if (filterSemi && j->getSpliceSiteType() == CanonicalSS::SEMI_CANONICAL) pass = false;
+                    if (filterCanonical && j->getSpliceSiteType() == CanonicalSS::CANONICAL) pass = false;
+                }
+                if (pass && getMinCov() > j->getNbSplicedAlignments()) pass = false;
+                if (pass) passJuncs.push_back(j);
+                else {
+                    failJuncs.push_back(j);
+                    discardedJuncs.addJunction(j);
+                }
+            }
+            printFilteringResults(currentJuncs, passJuncs, failJuncs, "Post filtering (length and/or canonical) results");
+            currentJuncs = passJuncs;
+        }
+    }
+    cout << endl;
+    JunctionSystem filteredJuncs, refKeptJuncs;
+    if (currentJuncs.empty()) {
+        cout << "WARNING: Filters discarded all junctions from input." << endl;
+    } else {  // :555-580
+        cout << "Recalculating junction grouping and distance stats based on new junction list that passed filters ...";
+        cout.flush();
+        for (auto& j : currentJuncs) filteredJuncs.addJunction(j);
+        uint32_t inref = 0;
+        if (!referenceFile.empty()) {
+            for (auto& j : currentJuncs)
+                if (ref.count(locationAsString(*j)) > 0) inref++;
+            for (auto& j : discardedJuncs.getJunctions())
+                if (ref.count(locationAsString(*j)) > 0) {
+                    filteredJuncs.addJunction(j);
+                    refKeptJuncs.addJunction(j);
+                    inref++;
+                }
+        }
+        filteredJuncs.calcJunctionStats();
+        cout << " done." << endl << endl;
+        if (!referenceFile.empty()) {
+            cout << "Brought back " << refKeptJuncs.size() << " junctions that were discarded by filters but were present in reference file." << endl;
+            cout << "Your sample contains " << inref << " / " << ref.size() << " (" << ((double)inref / (double)ref.size()) * 100.0
+                 << "%) junctions from the reference." << endl << endl;
+        }
+    }
+    printFilteringResults(originalJuncs.getJunctions(), filteredJuncs.getJunctions(), discardedJuncs.getJunctions(), "Overall results");
+    cout << endl << "Saving junctions passing filter to disk:" << endl;
+    filteredJuncs.saveAll(outputDir + "/" + outputPrefix + ".pass", source + "_pass", true, outputExonGFF, outputIntronGFF);
+    if (saveBad) {
+        cout << "Saving junctions failing filter to disk:" << endl;
+        discardedJuncs.saveAll(outputDir + "/" + outputPrefix + ".fail", source + "_fail", true, outputExonGFF, outputIntronGFF);
+        if (!referenceFile.empty()) {
+            cout << "Saving junctions failing filters but present in reference:" << endl;
+            refKeptJuncs.saveAll(outputDir + "/" + outputPrefix + ".ref", source + "_ref", true, outputExonGFF, outputIntronGFF);
+        }
+    }
+}
+
+string JunctionFilter::description() {
+    return "Filters out junctions that are unlikely to be genuine or that have too little\n"
+           "supporting evidence.  A saved random forest model (--model_file) scores every\n"
+           "junction on the GPU; rule files (--filter_file), the length, canonical and\n"
+           "coverage filters and a reference annotation apply after it.  Self-training a\n"
+           "model on the input is not built: pass --model_file, or --no_ml with --filter_file.";
+}
+
+string JunctionFilter::helpMessage() {
+    return title() + "\n\n" + description() + "\n\nUsage: " + usage() + "\n\n" +
+           "System options:\n"
+           "  -t [ --threads ] arg (=1)            Accepted for compatibility (the forest is walked on the GPU)\n"
+           "  --devices arg                        Number of GPUs offered; the forest stage uses the first (no GPU is opened without a model)\n"
+           "  -v [ --verbose ]                     Print extra information\n"
+           "  --help                               Produce help message\n\n"
+           "Output options:\n"
+           "  -o [ --output ] arg (=" + DEFAULT_FILTER_OUTPUT + ")\n"
+           "                                       Output prefix for files generated by this program.\n"
+           "  -b [ --save_bad ]                    Saves bad junctions (i.e. junctions that fail the filter), as well as good junctions (those that pass)\n"
+           "  --exon_gff                           Output exon-based junctions in GFF format.\n"
+           "  --intron_gff                         Output intron-based junctions in GFF format.\n"
+           "  --source arg (=" + DEFAULT_FILTER_SOURCE + ")            The value to enter into the \"source\" field in GFF files.\n\n"
+           "Filtering options:\n"
+           "  -f [ --filter_file ] arg             Rule-based filtering: a JSON file with the rules to apply (parameters and expression).\n"
+           "  -r [ --reference ] arg               Reference annotation of junctions in BED format.  Junctions found in it are kept regardless of any other filter.\n"
+           "  -n [ --no_ml ]                       Disables machine learning filtering\n"
+           "  -m [ --model_file ] arg              A saved random forest model (a .forest file, e.g. <prefix>.selftrain.forest of a reference run) to score the junctions with.\n"
+           "  --max_length arg (=0)                Filter junctions longer than this value.  Default (0) is to not filter based on length.\n"
+           "  --canonical arg (=OFF)               Keep junctions based on their splice site status.  Valid options: OFF,C,S,N.  User can separate options by a comma to keep two categories.\n"
+           "  --min_cov arg (=1)                   Only keep junctions with a number of split reads greater than or equal to this number\n"
+           "  --threshold arg (=0.5)               The threshold score at which we determine a junction to be genuine or not.\n"
+           "  --save_features                      Save the feature rows of all junctions to <output>.features.testing\n\n"
+           "Not built (refused): self-training (neither --model_file nor --no_ml), --training_rule, --no_smote, --enn, --save_layers, -g [ --genuine ]\n";
+}
+
+int JunctionFilter::main(int argc, char* argv[]) {
+    std::vector<string> positional;
+    string output = DEFAULT_FILTER_OUTPUT, source = DEFAULT_FILTER_SOURCE, filterFile, referenceFile, modelFile, canonical = "OFF";
+    bool saveBad = false, exongff = false, introngff = false, noMl = false, saveFeatures = false, verbose = false, help = false;
+    int threads = DEFAULT_FILTER_THREADS;
+    uint32_t maxLength = 0, minCov = 1;
+    double threshold = DEFAULT_FILTER_THRESHOLD;
+    // long options take their value as the next argument or after '='
+    for (int i = 1; i < argc; i++) {
+        string a = argv[i], inlineValue;
+        bool hasInline = false;
+        if (a.rfind("--", 0) == 0 && a.find('=') != string::npos) {
+            inlineValue = a.substr(a.find('=') + 1);
+            a = a.substr(0, a.find('='));
+            hasInline = true;
+        }
+        auto need = [&]() -> string {
+            if (hasInline) return inlineValue;
+            if (i + 1 >= argc) throw JuncFilterException("Option " + a + " needs a value");
+            return argv[++i];
+        };
+        auto notBuilt = [&](const string& what, const string& wayOut) {
+            throw JuncFilterException(what + " is not built into portcullis_amd filt.  " + wayOut);
+        };
+        const string selfTrainOut = "It belongs to self-training; pass a saved model with --model_file, or --no_ml with --filter_file.";
+        if (a == "-o" || a == "--output") output = need();
+        else if (a == "-b" || a == "--save_bad") saveBad = true;
+        else if (a == "--exon_gff") exongff = true;
+        else if (a == "--intron_gff") introngff = true;
+        else if (a == "--source") source = need();
+        else if (a == "-f" || a == "--filter_file") filterFile = need();
+        else if (a == "-r" || a == "--reference") referenceFile = need();
+        else if (a == "-n" || a == "--no_ml") noMl = true;
+        else if (a == "-m" || a == "--model_file") modelFile = need();
+        else if (a == "--max_length") maxLength = (uint32_t)std::stoul(need());
+        else if (a == "--canonical") canonical = need();
+        else if (a == "--min_cov") minCov = (uint32_t)std::stoul(need());
+        else if (a == "--threshold") threshold = std::stod(need());
+        else if (a == "--save_features") saveFeatures = true;
+        else if (a == "-t" || a == "--threads") threads = std::stoi(need());
+        else if (a == "--devices") (void)need();
+        else if (a == "-v" || a == "--verbose") verbose = true;
+        else if (a == "--help") help = true;
+        else if (a == "--training_rule") notBuilt("--training_rule (the rule sets of the self-training's initial layers)", selfTrainOut);
+        else if (a == "--no_smote") notBuilt("--no_smote (synthetic oversampling of the training set)", selfTrainOut);
+        else if (a == "--enn") notBuilt("--enn (Edited Nearest Neighbour cleaning of the training set)", selfTrainOut);
+        else if (a == "--save_layers") notBuilt("--save_layers (the layers of the training set)", selfTrainOut);
+        else if (a == "-g" || a == "--genuine")
+            notBuilt("--genuine (performance tables against a list of known labels)", "Run without it; the .pass and .fail tables can be compared with the labels afterwards.");
+        else if (!a.empty() && a[0] == '-' && a.size() > 1) throw JuncFilterException("Unknown option: " + a);
+        else positional.push_back(a);
+    }
+    if (help || argc <= 1 || positional.size() < 2) {
+        cout << helpMessage() << endl;
+        return 1;
+    }
+    const auto t0 = std::chrono::steady_clock::now();
+    cout << "Running portcullis in junction filter mode" << endl << "------------------------------------------" << endl << endl;
+    JunctionFilter filter(positional[0], positional[1], output);
+    filter.setSaveBad(saveBad);
+    filter.setSource(source);
+    filter.setVerbose(verbose);
+    filter.setThreads((uint16_t)std::max(1, threads));
+    filter.setMaxLength(maxLength);
+    filter.setCanonical(canonical);
+    filter.setMinCov(minCov);
+    filter.setOutputExonGFF(exongff);
+    filter.setOutputIntronGFF(introngff);
+    filter.setFilterFile(filterFile);
+    if (modelFile.empty() && !noMl) filter.setTrain(true);  // the reference's default: refused by filter()
+    else {
+        filter.setTrain(false);
+        if (!noMl) filter.setModelFile(modelFile);
+    }
+    filter.setSaveFeatures(saveFeatures);
+    filter.setReferenceFile(referenceFile);
+    filter.setThreshold(threshold);
+    filter.filter();
+    const double s = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+    std::ios::fmtflags f(cout.flags());
+    cout << endl << "Portcullis junction filter completed." << endl << "Total runtime: " << std::fixed << std::setprecision(1) << s << "s" << endl << endl;
+    cout.flags(f);
+    return 0;
+}
+
+}  // namespace portcullis

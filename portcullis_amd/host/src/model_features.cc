@@ -2,6 +2,7 @@
 #include <portcullis/ml/model_features.hpp>
 
 #include <algorithm>
+#include <cmath>
 #include <cstring>
 
 #include <portcullis/seq_utils.hpp>
@@ -84,23 +85,29 @@ std::vector<std::string> ModelFeatures::featureNames() {
     return n;
 }
 
-std::vector<double> ModelFeatures::juncs2FeatureVectors(const JunctionList& x) {  // :214-230 with setRow :161-212
+// One context with the genomes of the targets the junctions lie on, the junctions as device rows and the models as the C ABI takes them:
+// what the feature matrix and the fused forest walk both start from.
+namespace {
+struct DeviceRun {
+    pjb_ctx* ctx = nullptr;
+    std::vector<pjb_junction_row> rows;
+    pjb_markov_models m;
+    ~DeviceRun() { pjb_destroy(ctx); }
+    void check(int rc, const char* what) const {
+        if (rc != PJB_OK) throw JunctionException(std::string(what) + ": " + pjb_last_error(ctx));
+    }
+};
+}  // namespace
+
+static void openRun(DeviceRun& run, ModelFeatures& mf, bam::GenomeMapper* gmap, int device, const JunctionList& x) {
     if (!gmap) throw JunctionException("ModelFeatures: initGenomeMapper was not called");
-    std::vector<double> out(x.size() * PJB_N_FEATURES, 0.0);
-    if (x.empty()) return out;
-    // one context, the genomes of the targets the junctions lie on
     pjb_config cfg;
     memset(&cfg, 0, sizeof cfg);
     cfg.abi_version = PJB_ABI_VERSION;
     cfg.device = device;
     cfg.orientation = PJB_OR_UNKNOWN;
     cfg.strandedness = PJB_SS_UNKNOWN;
-    pjb_ctx* ctx = nullptr;
-    if (pjb_create(&ctx, &cfg) != PJB_OK) throw JunctionException(std::string("pjb_create: ") + pjb_last_error(nullptr));
-    struct Closer {
-        pjb_ctx* c;
-        ~Closer() { pjb_destroy(c); }
-    } closer{ctx};
+    if (pjb_create(&run.ctx, &cfg) != PJB_OK) throw JunctionException(std::string("pjb_create: ") + pjb_last_error(nullptr));
     int32_t maxRef = 0;
     for (const auto& j : x) maxRef = std::max(maxRef, j->getIntron()->ref.index);
     std::vector<int32_t> lens((size_t)maxRef + 1, 0);
@@ -109,20 +116,17 @@ std::vector<double> ModelFeatures::juncs2FeatureVectors(const JunctionList& x) {
         lens[(size_t)j->getIntron()->ref.index] = j->getIntron()->ref.length;
         names[(size_t)j->getIntron()->ref.index] = j->getIntron()->ref.name;
     }
-    auto check = [&](int rc, const char* what) {
-        if (rc != PJB_OK) throw JunctionException(std::string(what) + ": " + pjb_last_error(ctx));
-    };
-    check(pjb_set_refs(ctx, (int32_t)lens.size(), lens.data()), "pjb_set_refs");
+    run.check(pjb_set_refs(run.ctx, (int32_t)lens.size(), lens.data()), "pjb_set_refs");
     for (size_t t = 0; t < lens.size(); t++) {
         if (names[t].empty()) continue;
         const std::string contig = gmap->fetchContig(names[t]);
-        check(pjb_upload_contig(ctx, (int32_t)t, (const uint8_t*)contig.data(), (int64_t)contig.size()), "pjb_upload_contig");
+        run.check(pjb_upload_contig(run.ctx, (int32_t)t, (const uint8_t*)contig.data(), (int64_t)contig.size()), "pjb_upload_contig");
     }
-    std::vector<pjb_junction_row> rows(x.size());
-    memset(rows.data(), 0, rows.size() * sizeof(pjb_junction_row));
+    run.rows.resize(x.size());
+    memset(run.rows.data(), 0, run.rows.size() * sizeof(pjb_junction_row));
     for (size_t i = 0; i < x.size(); i++) {
         const Junction& j = *x[i];
-        pjb_junction_row& r = rows[i];
+        pjb_junction_row& r = run.rows[i];
         r.refid = j.getIntron()->ref.index;
         r.start = j.getIntron()->start;
         r.end = j.getIntron()->end;
@@ -138,28 +142,75 @@ std::vector<double> ModelFeatures::juncs2FeatureVectors(const JunctionList& x) {
         r.maxmmes = j.getMaxMMES();
         r.hamming5p = j.getHammingDistance5p();
         r.hamming3p = j.getHammingDistance3p();
+        // a junction parsed from a .tab has the mean only, at the six digits the writer prints: the integer sum the device divides again
+        const double sum = j.getMeanMismatches() * (double)j.getNbSplicedAlignments();
+        r.sum_mismatches = sum > 0.0 && sum < 4294967295.0 ? (uint64_t)std::llround(sum) : 0;
         for (int k = 0; k < 20; k++) r.jad[k] = j.getJunctionAnchorDepth((size_t)k);
     }
-    pjb_markov_models m;
+    pjb_markov_models& m = run.m;
     memset(&m, 0, sizeof m);
-    m.exon = exonModel.table();
-    m.intron = intronModel.table();
-    m.donor_t = donorTModel.table();
-    m.donor_f = donorFModel.table();
-    m.acceptor_t = acceptorTModel.table();
-    m.acceptor_f = acceptorFModel.table();
-    m.donor_pw = donorPWModel.table();
-    m.acceptor_pw = acceptorPWModel.table();
-    m.exon_size = (int32_t)exonModel.size();
-    m.intron_size = (int32_t)intronModel.size();
-    m.donor_pw_size = (int32_t)donorPWModel.size();
-    m.acceptor_pw_size = (int32_t)acceptorPWModel.size();
-    check(pjb_filt_features(ctx, rows.data(), (int64_t)rows.size(), x[0]->getMeanReadLength(), L95, &m, out.data()), "pjb_filt_features");
+    m.exon = mf.exonModel.table();
+    m.intron = mf.intronModel.table();
+    m.donor_t = mf.donorTModel.table();
+    m.donor_f = mf.donorFModel.table();
+    m.acceptor_t = mf.acceptorTModel.table();
+    m.acceptor_f = mf.acceptorFModel.table();
+    m.donor_pw = mf.donorPWModel.table();
+    m.acceptor_pw = mf.acceptorPWModel.table();
+    m.exon_size = (int32_t)mf.exonModel.size();
+    m.intron_size = (int32_t)mf.intronModel.size();
+    m.donor_pw_size = (int32_t)mf.donorPWModel.size();
+    m.acceptor_pw_size = (int32_t)mf.acceptorPWModel.size();
+}
+
+std::vector<double> ModelFeatures::juncs2FeatureVectors(const JunctionList& x) {  // :214-230 with setRow :161-212
+    if (!gmap) throw JunctionException("ModelFeatures: initGenomeMapper was not called");
+    std::vector<double> out(x.size() * PJB_N_FEATURES, 0.0);
+    if (x.empty()) return out;
+    DeviceRun run;
+    openRun(run, *this, gmap, device, x);
+    run.check(pjb_filt_features(run.ctx, run.rows.data(), (int64_t)run.rows.size(), x[0]->getMeanReadLength(), L95, &run.m, out.data()), "pjb_filt_features");
     for (size_t i = 0; i < x.size(); i++) {
         out[i * PJB_N_FEATURES + 0] = x[i]->isGenuine() ? 1.0 : 0.0;
         out[i * PJB_N_FEATURES + 8] = x[i]->getMeanMismatches();  // the junction's own value (a row parsed from a .tab has no integer sum)
     }
     return out;
+}
+
+const std::vector<int32_t>& ModelFeatures::activeFeatures() {  // src/junction_filter.cc:246-258 of the reference
+    static const std::vector<int32_t> a = [] {
+        std::vector<int32_t> v = {0, 3, 5, 7, 8, 9, 10, 12, 13};
+        for (int32_t k = 14; k < PJB_N_FEATURES; k++) v.push_back(k);
+        return v;
+    }();
+    return a;
+}
+
+void ModelFeatures::checkForest(const Forest& forest) {
+    pjb_forest view;
+    forest.view(view);
+    char msg[200] = "";
+    if (pjb_forest_check(&view, msg, (int)sizeof msg) != PJB_OK) throw ForestException(std::string("The forest model cannot be used: ") + msg);
+    if ((size_t)forest.nVars != activeFeatures().size())
+        throw ForestException("The forest model was trained on " + std::to_string(forest.nVars) + " variables; this filter makes the " +
+                              std::to_string(activeFeatures().size()) + " columns the reference leaves active (Genuine and 28 features)");
+}
+
+std::vector<double> ModelFeatures::forestPredict(const JunctionList& x, const Forest& forest, std::vector<double>* featuresOut) {
+    const size_t nClasses = forest.classValues.size();
+    std::vector<double> pred(x.size() * nClasses, 0.0);
+    if (featuresOut) featuresOut->assign(x.size() * PJB_N_FEATURES, 0.0);
+    if (x.empty()) return pred;
+    checkForest(forest);  // (before a device is opened)
+    pjb_forest view;
+    forest.view(view);
+    DeviceRun run;
+    openRun(run, *this, gmap, device, x);
+    run.check(pjb_forest_load(run.ctx, &view), "pjb_forest_load");
+    run.check(pjb_filt_scores(run.ctx, run.rows.data(), (int64_t)run.rows.size(), x[0]->getMeanReadLength(), L95, &run.m, activeFeatures().data(), pred.data(),
+                              featuresOut ? featuresOut->data() : nullptr),
+              "pjb_filt_scores");
+    return pred;
 }
 
 }  // namespace ml
