@@ -1,6 +1,6 @@
 """Edge cases the reference's code paths treat specially (clamps at contig ends, clipping quirks,
 zero-length operations, exotic genome characters, error conditions).  For every case the HIP path
-and the oracle must either both fail or produce identical rows."""
+and the oracle must either both fail with the same code or produce identical rows, and every case states which it is."""
 import numpy as np
 import pytest
 
@@ -10,8 +10,7 @@ from portcullis_amd.records import ReadBatch
 
 pytestmark = pytest.mark.gpu
 
-RNG = np.random.default_rng(99)
-G = "".join(RNG.choice(list("ACGT"), size=6000))
+from error_cases import G  # 6000 random bases (seed 99): the catalogue of faulty records stands on the same contig
 
 
 def both(ffi, orc, genome, reads, orientation="UNKNOWN", ref_len=None):
@@ -34,6 +33,8 @@ def both(ffi, orc, genome, reads, orientation="UNKNOWN", ref_len=None):
         region_equal(dreg, oreg)
         assert_rows_equal(drows, orows)
         return "ok", orows
+    # (every failing case here has one faulty read, or several with the same fault: reference order and ordinal order agree)
+    assert oerr.code == derr.code, f"oracle error: {oerr}; device error: {derr}"
     return "error", (oerr.code, derr.code)
 
 
@@ -88,11 +89,27 @@ CASES = {
 }
 
 
+# what each case is meant to give: rows ("ok"), or the code of the reference's condition on both sides
+EXPECTED = {name: "ok" for name in CASES}
+EXPECTED.update({
+    "bad_xs_value": -1, "bad_xs_on_unspliced_read": -1,
+    "cigar_starts_with_refskip": -2, "cigar_ends_with_refskip": -2,
+    "zero_length_match_in_anchor": -3,
+    "sequence_shorter_than_cigar": -4,
+    "read_runs_off_contig_end": -7, "refskip_runs_off_contig_end": -7, "two_introns_back_to_back": -7,
+    "softclip_longer_than_read": -13,
+})
+
+
 @pytest.mark.parametrize("name", sorted(CASES))
 def test_edge_case(ffi, orc, name):
     reads = sorted(CASES[name], key=lambda r: r["pos"])
-    both(ffi, orc, G, reads)
-    both(ffi, orc, G, reads, orientation="FR")
+    for orientation in ("UNKNOWN", "FR"):
+        status, what = both(ffi, orc, G, reads, orientation=orientation)
+        if EXPECTED[name] == "ok":
+            assert status == "ok", (name, orientation, what)
+        else:
+            assert status == "error" and what == (EXPECTED[name], EXPECTED[name]), (name, orientation, what)
 
 
 def test_exotic_genome_characters(ffi, orc):

@@ -125,14 +125,16 @@ def test_error_cigar_ends_with_refskip(ffi, orc):
     genome = "ACGT" * 500
     reads = [dict(pos=100, cigar="30M100N", seq="A" * 30, xs="+")]
     b = ReadBatch.from_reads(reads)
-    with pytest.raises(orc.OracleError):
+    with pytest.raises(orc.OracleError) as oe:
         orc.find_juncs(0, len(genome), genome, b, "UNKNOWN")
+    assert oe.value.code == -2
     with ffi.Context(0) as ctx:
         ctx.set_refs([len(genome)])
         ctx.upload_contig(0, genome.encode())
         ctx.submit_batch(0, b)
-        with pytest.raises(ffi.PjbError):
+        with pytest.raises(ffi.PjbError) as e:
             ctx.finish_contig(0)
+        assert e.value.code == -2
 
 
 def test_seq_star_fallback(ffi, orc):
