@@ -576,6 +576,31 @@ int pjb_forest_predict(pjb_ctx *ctx, const double *data, int64_t n_rows, int32_t
 int pjb_filt_scores(pjb_ctx *ctx, const pjb_junction_row *rows, int64_t n_rows, double mean_read_length, uint32_t l95,
                     const pjb_markov_models *models, const int32_t *var_feature, double *pred, double *features_out);
 
+/* ---- `train`: a ranger probability forest grown on the device ------------------------------------------------
+ * Forest::grow with the trees of ForestProbability as ModelFeatures::trainInstance sets them up (lib/src/model_features.cc:422-440:
+ * no replacement, sample fraction 1, no case weights, every variable ordered): Forest.cpp:409-416 (the trees' seeds),
+ * Tree::grow / splitNode / createPossibleSplitVarSubset (deps/ranger-0.3.8/src/Tree.cpp:88-123, 232-300),
+ * drawWithoutReplacementSimple (src/utility.cpp:108-131) and TreeProbability::splitNodeInternal / findBestSplit /
+ * findBestSplitValueSmallQ / LargeQ / addToTerminalNodes (src/TreeProbability.cpp:57-73, 91-312).  The result, written with
+ * Forest::saveToFile's layout, is byte for byte the file ranger 0.3.8 (built against libstdc++ 11) saves for the same matrix.
+ * data: row-major n_rows x n_cols, host; column dependent_col holds the labels 0 / 1.
+ * PJB_ERR_ARG, found on the host before anything is launched: a value that is not finite; a label other than 0 or 1;
+ * n_trees < 1, n_rows < 1, n_cols < 2; mtry >= n_cols / 2 (ranger then draws by Knuth's algorithm, utility.cpp:101-105, which is
+ * not built; with mtry 0 this refuses n_cols < 4); more than PJB_FOREST_MAX_VARS columns.  Works on any context
+ * (PJB_FLAG_NO_CHAINS too); the forest pjb_forest_load put on the device is left alone. */
+typedef struct pjb_grow_params {
+    int32_t n_trees;
+    uint32_t seed;         /* trainInstance: 1236456789 */
+    int32_t mtry;          /* 0 = floor(sqrt(n_cols - 1)) */
+    int32_t min_node_size; /* 0 = 10 */
+    int32_t dependent_col;
+} pjb_grow_params;
+typedef struct pjb_grow_result {
+    pjb_forest forest;          /* host memory, owned by the context until the next pjb_forest_grow / pjb_destroy */
+    const double *class_values; /* n_classes, ascending */
+} pjb_grow_result;
+int pjb_forest_grow(pjb_ctx *ctx, const double *data, int64_t n_rows, int32_t n_cols, const pjb_grow_params *p, pjb_grow_result *out);
+
 /* ---- `portcullis bamfilt` ----------------------------------------------------------------
  * The per-alignment decision of BamFilter::filter (src/bam_filter.cc:152-247): walk the CIGAR as
  * BamFilter::containsJunctionInSystem / clipMSR do (src/bam_filter.cc:75-150) and probe the set of junctions that

@@ -1,9 +1,10 @@
 // pjb_extra_api.hip -- the part of the C ABI behind `junc --extra` (depth, flanking counts, name multiplicities: pjb_extra_finish), `bamfilt`
-// (pjb_filter_*) and `filt`'s feature rows and forest (pjb_filt_features, pjb_forest_*, pjb_filt_scores); kernels in pjb_extra.hip.h and
-// pjb_forest.hip.h.
+// (pjb_filter_*), `filt`'s feature rows and forest (pjb_filt_features, pjb_forest_*, pjb_filt_scores) and `train`'s growing of one
+// (pjb_forest_grow); kernels in pjb_extra.hip.h, pjb_forest.hip.h and pjb_grow.hip.h.
 #include "pjb_host.hip.h"
 #include "pjb_extra.hip.h"
 #include "pjb_forest.hip.h"
+#include "pjb_grow.hip.h"
 
 // The name codes of a chain's spliced records, in BAM order, to `codes`; their number to cnt->n_spliced.  Through the tile lists the
 // chain's first kernels left in its slot (tile numbers run through the chain).
@@ -696,6 +697,194 @@ int pjb_filt_scores(pjb_ctx *c, const pjb_junction_row *rows, int64_t n_rows, do
     HIP_TRY(c, hipStreamSynchronize(st)); // (the one wait; colmap is pageable and lives until here)
     if (c->ktime) ev_collect(c, MISC_POOL);
     if (bad) return fail(c, PJB_ERR_STATE, "pjb_filt_scores: a junction lies on a target whose genome was not uploaded");
+    return PJB_OK;
+}
+
+// Device memory one batch of trees may take (lists, nodes, candidates, scores); more trees than fit are grown batch after batch.
+static constexpr size_t GROW_POOL_BYTES = (size_t)6 << 30;
+
+// Forest::grow for ForestProbability as ModelFeatures::trainInstance sets it up: see include/portcullis_amd.h and pjb_grow.hip.h.
+int pjb_forest_grow(pjb_ctx *c, const double *data, int64_t n_rows, int32_t n_cols, const pjb_grow_params *p, pjb_grow_result *out) {
+    if (!c) return PJB_ERR_ARG;
+    if (!p || !out) return fail(c, PJB_ERR_ARG, "pjb_forest_grow: bad arguments");
+    if (p->n_trees < 1) return fail(c, PJB_ERR_ARG, "pjb_forest_grow: %d trees (at least one is needed)", p->n_trees);
+    if (n_rows < 1) return fail(c, PJB_ERR_ARG, "pjb_forest_grow: %lld rows (at least one is needed)", (long long)n_rows);
+    if (n_cols < 2) return fail(c, PJB_ERR_ARG, "pjb_forest_grow: %d columns (the labels and one variable at least)", n_cols);
+    if (n_cols > PJB_FOREST_MAX_VARS) return fail(c, PJB_ERR_ARG, "pjb_forest_grow: %d variables (1 to %d can be walked)", n_cols, PJB_FOREST_MAX_VARS);
+    if (!data || n_rows > (1ll << 28) || p->n_trees > (1 << 24)) return fail(c, PJB_ERR_ARG, "pjb_forest_grow: bad arguments");
+    if (p->dependent_col < 0 || p->dependent_col >= n_cols)
+        return fail(c, PJB_ERR_ARG, "pjb_forest_grow: dependent column %d of %d columns", p->dependent_col, n_cols);
+    if (p->mtry < 0 || p->min_node_size < 0) return fail(c, PJB_ERR_ARG, "pjb_forest_grow: mtry %d, node size %d", p->mtry, p->min_node_size);
+    // ForestProbability::initInternal (ForestProbability.cpp:64-75)
+    const u32 mtry = p->mtry ? (u32)p->mtry : std::max<u32>(1, (u32)sqrt((double)(n_cols - 1)));
+    const u32 min_node = p->min_node_size ? (u32)p->min_node_size : 10u;
+    if (mtry >= (u32)n_cols / 2)
+        return fail(c, PJB_ERR_ARG, "pjb_forest_grow: mtry %u of %d columns: from n_cols / 2 on ranger draws by Knuth's algorithm, which is not built", mtry, n_cols);
+    const size_t n = (size_t)n_rows, C = (size_t)n_cols, dep = (size_t)p->dependent_col;
+    std::vector<double> colmajor(C * n);
+    std::vector<uint8_t> label(n);
+    u32 label_sum = 0;
+    for (size_t r = 0; r < n; r++)
+        for (size_t k = 0; k < C; k++) {
+            const double v = data[r * C + k];
+            if (!std::isfinite(v)) return fail(c, PJB_ERR_ARG, "pjb_forest_grow: row %zu, column %zu is not finite", r, k);
+            if (k == dep) {
+                if (v != 0.0 && v != 1.0) return fail(c, PJB_ERR_ARG, "pjb_forest_grow: row %zu has the label %g (0 or 1)", r, v);
+                label[r] = v == 1.0;
+                label_sum += label[r];
+            }
+            colmajor[k * n + r] = v;
+        }
+    // one sort per column, shared by all trees (Data::sort's order of values; rows of one value in row order)
+    std::vector<u32> sorted(C * n);
+    for (size_t k = 0; k < C; k++) {
+        u32 *s = sorted.data() + k * n;
+        for (size_t r = 0; r < n; r++) s[r] = (u32)r;
+        if (k == dep) continue;
+        const double *v = colmajor.data() + k * n;
+        std::stable_sort(s, s + n, [v](u32 a, u32 b) { return v[a] < v[b]; });
+    }
+    // the room of one batch of T trees
+    const size_t M = 2 * n;
+    auto up = [](size_t b) { return (b + 255) & ~(size_t)255; };
+    const size_t shared_bytes = up(C * n * 8) + up(n) + up(C * n * 4) + 256;
+    const size_t tree_bytes = 2 * C * n * 4 + n * 4 + M * (5 * 4 + 8) + M * mtry * (2 + sizeof(GrowBest)) + (GROW_MT_N + 1) * 8 + 2 * 4;
+    size_t batch = c->grow_batch ? c->grow_batch : std::max<size_t>(1, GROW_POOL_BYTES / tree_bytes);
+    batch = std::min<size_t>(std::min<size_t>(batch, (size_t)p->n_trees), 32768);
+    HIP_TRY(c, hipSetDevice(c->cfg.device));
+    hipStream_t st = c->stream;
+    int rc;
+    if ((rc = ensure(c, c->w_pool, shared_bytes + batch * tree_bytes + 16 * 256))) return rc;
+    uint8_t *at = (uint8_t *)c->w_pool.p;
+    auto carve = [&](size_t bytes) {
+        uint8_t *q = at;
+        at += up(bytes);
+        return q;
+    };
+    double *d_col = (double *)carve(C * n * 8);
+    uint8_t *d_label = carve(n);
+    u32 *d_sorted = (u32 *)carve(C * n * 4);
+    u32 *d_new = (u32 *)carve(4);
+    u32 *d_lists[2] = {(u32 *)carve(batch * C * n * 4), (u32 *)carve(batch * C * n * 4)};
+    u32 *d_node_of = (u32 *)carve(batch * n * 4);
+    GrowNodes nd;
+    nd.start = (u32 *)carve(batch * M * 4);
+    nd.count = (u32 *)carve(batch * M * 4);
+    nd.sum = (u32 *)carve(batch * M * 4);
+    nd.child = (u32 *)carve(batch * M * 4);
+    nd.var = (u32 *)carve(batch * M * 4);
+    nd.val = (double *)carve(batch * M * 8);
+    uint16_t *d_cand = (uint16_t *)carve(batch * M * mtry * 2);
+    GrowBest *d_best = (GrowBest *)carve(batch * M * mtry * sizeof(GrowBest));
+    u64 *d_state = (u64 *)carve(batch * (GROW_MT_N + 1) * 8);
+    u32 *d_lvl = (u32 *)carve(batch * 2 * 4);
+    HIP_TRY(c, hipMemcpyAsync(d_col, colmajor.data(), C * n * 8, hipMemcpyHostToDevice, st));
+    HIP_TRY(c, hipMemcpyAsync(d_label, label.data(), n, hipMemcpyHostToDevice, st));
+    HIP_TRY(c, hipMemcpyAsync(d_sorted, sorted.data(), C * n * 4, hipMemcpyHostToDevice, st));
+
+    pjb_ctx::GrowOut &G = c->grow_out;
+    G = pjb_ctx::GrowOut();
+    G.is_ordered.assign(C, 1);
+    if (label_sum < n) G.class_values.push_back(0.0);
+    if (label_sum > 0) G.class_values.push_back(1.0);
+    const size_t K = G.class_values.size();
+    G.tree_off.push_back(0);
+    std::vector<u32> lvl, h_child, h_var, h_count, h_sum;
+    std::vector<double> h_val;
+    std::vector<u64> off;
+    for (size_t t0 = 0; t0 < (size_t)p->n_trees; t0 += batch) {
+        const u32 T = (u32)std::min<size_t>(batch, (size_t)p->n_trees - t0);
+        LAUNCH(c, "kt_seed", kt_seed, dim3((T + 63) / 64), dim3(64), d_state, T, (u32)t0, (u32)p->seed, nd, (u32)M, d_lvl, (u32)n, label_sum);
+        const u64 total = (u64)T * C * n;
+        LAUNCH(c, "kt_fill", kt_fill, dim3((unsigned)((total + 255) / 256)), dim3(256), (const u32 *)d_sorted, d_lists[0], (u64)(C * n), total);
+        HIP_TRY(c, hipMemsetAsync(d_node_of, 0, (size_t)T * n * 4, st));
+        int cur = 0;
+        // one trip per level: at most n_rows levels (every split leaves both children smaller); the one read-back says whether nodes were made
+        for (size_t level = 0; level <= n; level++) {
+            u32 n_new = 0;
+            HIP_TRY(c, hipMemsetAsync(d_new, 0, 4, st));
+            LAUNCH(c, "kt_draw", kt_draw, dim3((T + GROW_DRAW_TREES - 1) / GROW_DRAW_TREES), dim3(GROW_DRAW_TREES), d_state, T, (const u32 *)d_lvl, (u32)C, (u32)dep,
+                   mtry, d_cand, (u32)M);
+            LAUNCH(c, "kt_split", kt_split, dim3((unsigned)C, T), dim3(64), (const u32 *)d_lists[cur], (const u32 *)d_node_of, (const double *)d_col,
+                   (const uint8_t *)d_label, (const u32 *)d_lvl, T, nd, (const uint16_t *)d_cand, d_best, (u32)n, (u32)C, (u32)dep, mtry, (u32)M);
+            LAUNCH(c, "kt_decide", kt_decide, dim3(T), dim3(64), (const u32 *)d_lists[cur], (const double *)d_col, d_lvl, T, nd, (const uint16_t *)d_cand,
+                   (const GrowBest *)d_best, (u32)n, (u32)C, mtry, (u32)M, min_node, d_new);
+            HIP_TRY(c, hipMemcpyAsync(&n_new, d_new, 4, hipMemcpyDeviceToHost, st));
+            HIP_TRY(c, hipStreamSynchronize(st));
+            if (c->ktime) ev_collect(c, MISC_POOL);
+            if (!n_new) break;
+            LAUNCH(c, "kt_partition", kt_partition, dim3((unsigned)C, T), dim3(64), (const u32 *)d_lists[cur], d_lists[cur ^ 1], (const u32 *)d_node_of,
+                   (const double *)d_col, (const u32 *)d_lvl, T, nd, (u32)n, (u32)C, (u32)dep, (u32)M);
+            LAUNCH(c, "kt_assign", kt_assign, dim3((unsigned)((n + 255) / 256), T), dim3(256), d_node_of, (const double *)d_col, nd, (u32)n, (u32)M);
+            cur ^= 1;
+        }
+        // the trees' nodes, packed one tree after the other
+        lvl.resize((size_t)2 * T);
+        HIP_TRY(c, hipMemcpyAsync(lvl.data(), d_lvl, (size_t)2 * T * 4, hipMemcpyDeviceToHost, st));
+        HIP_TRY(c, hipStreamSynchronize(st));
+        off.assign((size_t)T + 1, 0);
+        u32 most = 0;
+        for (u32 t = 0; t < T; t++) {
+            const u32 nodes = lvl[(size_t)T + t]; // (the end of the last level: the tree's node count)
+            if (lvl[t] != nodes || nodes < 1 || nodes >= M) return fail(c, PJB_ERR_STATE, "pjb_forest_grow: tree %zu did not finish (%u nodes)", t0 + t, nodes);
+            off[t + 1] = off[t] + nodes;
+            most = std::max(most, nodes);
+        }
+        const size_t N = (size_t)off[T];
+        if ((rc = ensure(c, c->w_pack, up((T + 1) * 8) + 4 * up(N * 4) + up(N * 8)))) return rc;
+        uint8_t *q = (uint8_t *)c->w_pack.p;
+        u64 *d_off = (u64 *)q;
+        q += up((T + 1) * 8);
+        u32 *p_child = (u32 *)q, *p_var = (u32 *)(q + up(N * 4)), *p_count = (u32 *)(q + 2 * up(N * 4)), *p_sum = (u32 *)(q + 3 * up(N * 4));
+        double *p_val = (double *)(q + 4 * up(N * 4));
+        HIP_TRY(c, hipMemcpyAsync(d_off, off.data(), (T + 1) * 8, hipMemcpyHostToDevice, st));
+        LAUNCH(c, "kt_pack", kt_pack, dim3((most + 255) / 256, T), dim3(256), nd, (u32)M, (const u64 *)d_off, p_child, p_var, p_val, p_count, p_sum);
+        h_child.resize(N), h_var.resize(N), h_count.resize(N), h_sum.resize(N), h_val.resize(N);
+        HIP_TRY(c, hipMemcpyAsync(h_child.data(), p_child, N * 4, hipMemcpyDeviceToHost, st));
+        HIP_TRY(c, hipMemcpyAsync(h_var.data(), p_var, N * 4, hipMemcpyDeviceToHost, st));
+        HIP_TRY(c, hipMemcpyAsync(h_count.data(), p_count, N * 4, hipMemcpyDeviceToHost, st));
+        HIP_TRY(c, hipMemcpyAsync(h_sum.data(), p_sum, N * 4, hipMemcpyDeviceToHost, st));
+        HIP_TRY(c, hipMemcpyAsync(h_val.data(), p_val, N * 8, hipMemcpyDeviceToHost, st));
+        HIP_TRY(c, hipStreamSynchronize(st));
+        if (c->ktime) ev_collect(c, MISC_POOL);
+        for (u32 t = 0; t < T; t++) {
+            for (u64 k = off[t]; k < off[t + 1]; k++) {
+                if (h_child[k]) {
+                    G.left.push_back((int32_t)h_child[k]);
+                    G.right.push_back((int32_t)h_child[k] + 1);
+                    G.count_off.push_back(-1);
+                } else { // addToTerminalNodes: count[class] / n, one division each
+                    G.left.push_back(-1);
+                    G.right.push_back(-1);
+                    G.count_off.push_back((int64_t)G.counts.size());
+                    const double cnt = (double)h_count[k], ones = (double)h_sum[k];
+                    if (K == 2) G.counts.push_back((cnt - ones) / cnt);
+                    G.counts.push_back((K == 2 || label_sum > 0 ? ones : cnt) / cnt);
+                }
+                G.split_var.push_back((int32_t)h_var[k]);
+                G.split_value.push_back(h_val[k]);
+            }
+            G.tree_off.push_back((int64_t)G.left.size());
+        }
+    }
+    pjb_forest &f = out->forest;
+    memset(&f, 0, sizeof f);
+    f.n_trees = p->n_trees;
+    f.n_classes = (int32_t)K;
+    f.n_vars = n_cols;
+    f.dependent_var = p->dependent_col;
+    f.is_ordered = G.is_ordered.data();
+    f.tree_off = G.tree_off.data();
+    f.left = G.left.data();
+    f.right = G.right.data();
+    f.split_var = G.split_var.data();
+    f.split_value = G.split_value.data();
+    f.count_off = G.count_off.data();
+    f.counts = G.counts.data();
+    f.n_counts = (int64_t)G.counts.size();
+    out->class_values = G.class_values.data();
+    char msg[200] = "";
+    if (pjb_forest_check(&f, msg, (int)sizeof msg) != PJB_OK) return fail(c, PJB_ERR_STATE, "pjb_forest_grow: the grown forest cannot be walked: %s", msg);
     return PJB_OK;
 }
 

@@ -324,6 +324,14 @@ struct pjb_ctx {
     Buf g_rows, g_models, g_refs, g_out, g_bad; // filt feature rows
     Buf r_nodes, r_leaf, r_roots, r_data, r_pred, r_colmap; // filt forest (pjb_forest.hip.h): packed nodes, leaf rows, tree roots; matrix, predictions, columns
     int32_t r_trees = 0, r_classes = 0, r_vars = 0, r_dep = 0; // r_trees == 0: no forest loaded
+    Buf w_pool, w_pack;      // pjb_forest_grow (pjb_grow.hip.h): the matrix, the trees' lists and nodes of one batch; the packed nodes
+    u32 grow_batch = 0;      // pjb_set_option("grow_batch", n): trees grown side by side (tests; 0: as many as GROW_POOL_BYTES holds)
+    struct GrowOut {         // the forest of the last pjb_forest_grow: what pjb_grow_result points to
+        std::vector<uint8_t> is_ordered;
+        std::vector<int64_t> tree_off, count_off;
+        std::vector<int32_t> left, right, split_var;
+        std::vector<double> split_value, counts, class_values;
+    } grow_out;
     Buf x_pos, x_endx, x_q, x_prefq, x_ce, x_bound, x_de, x_dropped, x_zlist, x_cnt, x_tabk, x_tabc, x_rs, x_re, x_rr, x_tileoff;
     Buf x_xrall, x_tab; // x_tab: the name table (NameSlot), x_tab_slots slots, holding the codes of x_tab_n spliced records
     size_t x_tab_slots = 0, x_tab_n = 0;

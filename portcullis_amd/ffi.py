@@ -27,7 +27,7 @@ EXPORTS = [
     "pjb_select_timed_kernels", "pjb_host_alloc", "pjb_host_free", "pjb_host_register", "pjb_host_unregister", "pjb_inflate_bgzf", "pjb_deflate_bgzf", "pjb_submit_bam", "pjb_collect_device", "pjb_set_row_mirror",
     "pjb_extra_finish", "pjb_set_option", "pjb_merge_rows", "pjb_plan_groups", "pjb_bam_begin", "pjb_bam_piece", "pjb_bam_pieces_done", "pjb_bam_end", "pjb_bam_inflate_done", "pjb_filter_set_junctions", "pjb_filter_batch", "pjb_filt_features",
     "pjb_index_begin", "pjb_index_piece", "pjb_index_end",
-    "pjb_forest_check", "pjb_forest_load", "pjb_forest_predict", "pjb_filt_scores",
+    "pjb_forest_check", "pjb_forest_load", "pjb_forest_predict", "pjb_filt_scores", "pjb_forest_grow",
 ]
 N_FEATURES = 34
 KMER_TABLE = 3125 * 5
@@ -59,6 +59,14 @@ class PjbMarkovModels(C.Structure):
 class PjbForest(C.Structure):
     _fields_ = [("n_trees", C.c_int32), ("n_classes", C.c_int32), ("n_vars", C.c_int32), ("dependent_var", C.c_int32)] + [
         (n, C.c_void_p) for n in ("is_ordered", "tree_off", "left", "right", "split_var", "split_value", "count_off", "counts")] + [("n_counts", C.c_int64)]
+
+
+class PjbGrowParams(C.Structure):
+    _fields_ = [("n_trees", C.c_int32), ("seed", C.c_uint32), ("mtry", C.c_int32), ("min_node_size", C.c_int32), ("dependent_col", C.c_int32)]
+
+
+class PjbGrowResult(C.Structure):
+    _fields_ = [("forest", PjbForest), ("class_values", C.c_void_p)]
 
 
 class PjbRegionResult(C.Structure):
@@ -160,6 +168,7 @@ def load():
         L.pjb_forest_predict.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p]
         L.pjb_filt_scores.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_double, C.c_uint32, C.POINTER(PjbMarkovModels), C.c_void_p, C.c_void_p,
                                       C.c_void_p]
+        L.pjb_forest_grow.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.POINTER(PjbGrowParams), C.POINTER(PjbGrowResult)]
         L.pjb_index_begin.argtypes = [C.c_void_p]
         L.pjb_index_piece.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int32, C.c_int32, C.POINTER(C.c_uint64)]
         L.pjb_index_end.argtypes = [C.c_void_p, C.POINTER(PjbIndexResult)]
@@ -515,6 +524,16 @@ class Context:
         self._check(self._L.pjb_forest_predict(self._h, data.ctypes.data_as(C.c_void_p), data.shape[0], data.shape[1], out.ctypes.data_as(C.c_void_p)))
         return out[: len(data)]
 
+    def forest_grow(self, data, n_trees, seed=1236456789, mtry=0, min_node_size=0, dependent_col=0):
+        """pjb_forest_grow: data float64 [n, n_cols] with the labels 0 / 1 in column `dependent_col` -> Forest (a copy: it outlives the
+        next call), bit for bit the forest ranger 0.3.8 grows as ModelFeatures::trainInstance calls it."""
+        data = np.ascontiguousarray(data, dtype=np.float64)
+        assert data.ndim == 2
+        p = PjbGrowParams(int(n_trees), int(seed) & 0xFFFFFFFF, int(mtry), int(min_node_size), int(dependent_col))
+        r = PjbGrowResult()
+        self._check(self._L.pjb_forest_grow(self._h, data.ctypes.data_as(C.c_void_p), data.shape[0], data.shape[1], C.byref(p), C.byref(r)))
+        return Forest._from_struct(r.forest, r.class_values)
+
     def filt_scores(self, rows, mean_read_length, l95, models, var_feature, want_features=False):
         """pjb_filt_scores: feature rows and forest walk in one call; float64 [n, n_classes] (and the [n, N_FEATURES] rows if asked)."""
         rows = np.ascontiguousarray(rows, dtype=ROW_DTYPE)
@@ -723,6 +742,52 @@ class Forest:
             setattr(f, name, a.ctypes.data if a.size else None)
         f.n_counts = len(self.counts)
         return f
+
+    @classmethod
+    def grow(cls, ctx, data, n_trees=250, **kw):
+        """A forest grown on the device of `ctx` (Context.forest_grow)."""
+        return ctx.forest_grow(data, n_trees, **kw)
+
+    @classmethod
+    def _from_struct(cls, f, class_values):
+        def view(p, count, dt):
+            if count == 0 or not p:
+                return np.zeros(0, dtype=dt)
+            return np.frombuffer((C.c_char * (count * np.dtype(dt).itemsize)).from_address(p), dtype=dt, count=count).copy()
+
+        self = cls.__new__(cls)
+        self.n_trees, self.n_classes, self.n_vars, self.dependent_var = f.n_trees, f.n_classes, f.n_vars, f.dependent_var
+        self.is_ordered = view(f.is_ordered, f.n_vars, np.uint8) if f.is_ordered else None
+        self.tree_off = view(f.tree_off, f.n_trees + 1, np.int64)
+        n = int(self.tree_off[-1])
+        self.left, self.right, self.split_var = view(f.left, n, np.int32), view(f.right, n, np.int32), view(f.split_var, n, np.int32)
+        self.split_value, self.count_off = view(f.split_value, n, np.float64), view(f.count_off, n, np.int64)
+        self.counts = view(f.counts, f.n_counts, np.float64)
+        self.class_values = [float(v) for v in view(class_values, f.n_classes, np.float64)]
+        return self
+
+    def to_bytes(self):
+        """The forest as ranger 0.3.8 saves it (Forest::saveToFile): the inverse of from_file.  Needs class_values (from_file and grow
+        set them); a variable without an `is_ordered` entry is ordered."""
+        import struct
+        ordered = np.ones(self.n_vars, dtype=np.uint8) if self.is_ordered is None else self.is_ordered
+        out = [struct.pack("<QQQ", self.dependent_var, self.n_trees, len(ordered)), ordered.astype(np.uint8).tobytes(), struct.pack("<QiQ", self.n_vars, 9, len(self.class_values)),
+               np.asarray(self.class_values, dtype="<f8").tobytes()]
+        for t in range(self.n_trees):
+            a, b = int(self.tree_off[t]), int(self.tree_off[t + 1])
+            out.append(struct.pack("<Q", b - a))
+            for k in range(a, b):
+                ch = [c for c in (int(self.left[k]), int(self.right[k])) if c >= 0]
+                out.append(struct.pack(f"<Q{len(ch)}Q", len(ch), *ch))
+            out.append(struct.pack("<Q", b - a) + self.split_var[a:b].astype("<u8").tobytes())
+            out.append(struct.pack("<Q", b - a) + self.split_value[a:b].astype("<f8").tobytes())
+            term = [k for k in range(a, b) if self.count_off[k] >= 0]
+            out.append(struct.pack("<Q", len(term)) + np.asarray([k - a for k in term], dtype="<u8").tobytes())
+            out.append(struct.pack("<Q", len(term)))
+            for k in term:
+                at = int(self.count_off[k])
+                out.append(struct.pack("<Q", self.n_classes) + self.counts[at:at + self.n_classes].astype("<f8").tobytes())
+        return b"".join(out)
 
     def check(self):
         """pjb_forest_check (host arithmetic, no device): None if the forest can be walked, else the message."""

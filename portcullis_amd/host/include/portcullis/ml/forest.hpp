@@ -33,6 +33,12 @@ struct Forest {
     // Throws ForestException for a file that cannot be opened, is not a probability forest, ends early or goes on after its last tree.
     static Forest load(const std::string& path);
     static Forest parse(const uint8_t* data, size_t size, const std::string& name);
+    // The exact inverse of load / parse: the bytes Forest::saveToFile, ForestProbability::saveToFileInternal, Tree::appendToFile and
+    // TreeProbability::appendToFileInternal write.  save throws ForestException for a file that cannot be written.
+    std::vector<uint8_t> serialize() const;
+    void save(const std::string& path) const;
+    // a copy of the arrays the C ABI hands out (pjb_forest_grow's result) with their class values
+    static Forest fromView(const pjb_forest& view, const double* classValues);
     // the view the C ABI takes (valid while this object lives and is not changed)
     void view(pjb_forest& out) const;
 };

@@ -4,7 +4,7 @@
 // windows scored against six k-mer and two position models -- comes from the device (pjb_filt_features).
 // juncs2FeatureVectors returns a plain row-major matrix whose columns are VAR_NAMES + Junction::JAD_NAMES.  The random-forest
 // side: a saved forest (ml/forest.hpp) is walked on the device over the same rows without the matrix leaving it (forestPredict);
-// growing a forest (self-training) is not part of this build.
+// growing a forest from labelled junctions (growForest, pjb_forest_grow) is `train`'s; choosing the labels (self-training) is not built.
 #pragma once
 
 #include <string>
@@ -54,6 +54,10 @@ public:
     // host arithmetic only (pjb_forest_check and the number of variables): throws ForestException for a forest forestPredict would refuse
     static void checkForest(const Forest& forest);
     std::vector<double> forestPredict(const JunctionList& x, const Forest& forest, std::vector<double>* featuresOut = nullptr);
+    // ForestProbability grown as trainInstance grows it (lib/src/model_features.cc:422-440) on the rows of x: the feature rows are the
+    // device's (pjb_filt_features: what forestPredict walks), column 0 the junctions' isGenuine(), the variables activeFeatures();
+    // the forest is grown on the same device (pjb_forest_grow).  featuresOut (optional): the full matrix, as forestPredict returns it.
+    Forest growForest(const JunctionList& x, int32_t nTrees, uint32_t seed, std::vector<double>* featuresOut = nullptr);
 };
 
 }  // namespace ml

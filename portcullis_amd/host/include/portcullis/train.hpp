@@ -1,0 +1,49 @@
+// Train: the `train` mode -- a random forest model for `filt --model_file` grown on the device from two junction tables, one of junctions
+// known to be genuine and one of junctions known not to be.  It is the last step of the reference's ModelFeatures::trainInstance
+// (lib/src/model_features.cc:297-304, 422-440): combine the sets, sort them, make the feature rows, grow a ranger probability forest of
+// `trees` trees and save it.  What the reference does before that step is not built: choosing the sets by layered rules,
+// L95 and the Markov models (the rows are made as `filt` makes them: untrained models, L95 = 0, so that model and scoring agree), SMOTE,
+// ENN, the under-sampling, variable importance and the out-of-bag error (every row is in bag: there is none to report).
+#pragma once
+
+#include <string>
+
+#include "junction_system.hpp"
+#include "prepared_files.hpp"
+
+namespace portcullis {
+
+struct TrainException : public PortcullisException {
+    explicit TrainException(const std::string& m) : PortcullisException(m) {}
+};
+
+const std::string DEFAULT_TRAIN_OUTPUT = "portcullis_train/portcullis";
+const int32_t DEFAULT_TRAIN_TREES = 250;
+const uint32_t DEFAULT_TRAIN_SEED = 1236456789;  // ModelFeatures::trainInstance
+
+class Train {
+    PreparedFiles prepData;
+    std::string positiveFile, negativeFile, output;
+    int32_t trees = DEFAULT_TRAIN_TREES;
+    uint32_t seed = DEFAULT_TRAIN_SEED;
+    bool saveFeatures = false, verbose = false;
+    int device = 0;
+
+public:
+    Train(const std::string& prepDir, const std::string& positiveFile, const std::string& negativeFile, const std::string& output)
+        : prepData(prepDir), positiveFile(positiveFile), negativeFile(negativeFile), output(output) {}
+
+    void setTrees(int32_t v) { trees = v; }
+    void setSeed(uint32_t v) { seed = v; }
+    void setSaveFeatures(bool v) { saveFeatures = v; }
+    void setVerbose(bool v) { verbose = v; }
+    void setDevice(int v) { device = v; }
+
+    void train();
+
+    static std::string usage() { return "portcullis_amd train [options] <prep_data_dir> <positive_tab_file> <negative_tab_file>"; }
+    static std::string helpMessage();
+    static int main(int argc, char* argv[]);
+};
+
+}  // namespace portcullis

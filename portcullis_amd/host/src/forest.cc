@@ -103,6 +103,75 @@ Forest Forest::load(const std::string& path) {
     return parse((const uint8_t*)raw.data(), raw.size(), path);
 }
 
+std::vector<uint8_t> Forest::serialize() const {
+    std::vector<uint8_t> out;
+    auto put = [&out](const void* p, size_t n) { out.insert(out.end(), (const uint8_t*)p, (const uint8_t*)p + n); };
+    auto u64 = [&put](uint64_t v) { put(&v, 8); };
+    u64((uint64_t)dependentVar);
+    u64((uint64_t)nTrees);
+    u64(isOrdered.size());  // saveVector1D of a vector<bool>: the length, a byte an element
+    put(isOrdered.data(), isOrdered.size());
+    u64((uint64_t)nVars);
+    const int32_t treeType = 9;  // TREE_PROBABILITY
+    put(&treeType, 4);
+    u64(classValues.size());
+    put(classValues.data(), classValues.size() * 8);
+    const size_t nClasses = classValues.size();
+    for (int32_t t = 0; t < nTrees; t++) {
+        const size_t a = (size_t)treeOff[(size_t)t], b = (size_t)treeOff[(size_t)t + 1];
+        u64(b - a);  // child_nodeIDs: a vector per node, empty at a terminal node
+        for (size_t k = a; k < b; k++) {
+            const int nc = (left[k] >= 0) + (right[k] >= 0 && left[k] >= 0);
+            u64((uint64_t)nc);
+            if (nc > 0) u64((uint64_t)left[k]);
+            if (nc > 1) u64((uint64_t)right[k]);
+        }
+        u64(b - a);
+        for (size_t k = a; k < b; k++) u64((uint64_t)splitVar[k]);
+        u64(b - a);
+        put(splitValue.data() + a, (b - a) * 8);
+        size_t terminal = 0;
+        for (size_t k = a; k < b; k++) terminal += countOff[k] >= 0;
+        u64(terminal);
+        for (size_t k = a; k < b; k++)
+            if (countOff[k] >= 0) u64(k - a);
+        u64(terminal);
+        for (size_t k = a; k < b; k++)
+            if (countOff[k] >= 0) {
+                u64(nClasses);
+                put(counts.data() + countOff[k], nClasses * 8);
+            }
+    }
+    return out;
+}
+
+void Forest::save(const std::string& path) const {
+    const std::vector<uint8_t> raw = serialize();
+    std::ofstream out(path, std::ios::binary);
+    if (out.good()) out.write((const char*)raw.data(), (std::streamsize)raw.size());
+    out.close();
+    if (!out.good()) throw ForestException("Could not write to output file: " + path + ".");
+}
+
+Forest Forest::fromView(const pjb_forest& v, const double* classValues) {
+    Forest f;
+    f.nTrees = v.n_trees;
+    f.nVars = v.n_vars;
+    f.dependentVar = v.dependent_var;
+    if (v.is_ordered) f.isOrdered.assign(v.is_ordered, v.is_ordered + v.n_vars);
+    else f.isOrdered.assign((size_t)v.n_vars, 1);
+    f.classValues.assign(classValues, classValues + v.n_classes);
+    f.treeOff.assign(v.tree_off, v.tree_off + v.n_trees + 1);
+    const size_t n = (size_t)f.treeOff.back();
+    f.left.assign(v.left, v.left + n);
+    f.right.assign(v.right, v.right + n);
+    f.splitVar.assign(v.split_var, v.split_var + n);
+    f.splitValue.assign(v.split_value, v.split_value + n);
+    f.countOff.assign(v.count_off, v.count_off + n);
+    f.counts.assign(v.counts, v.counts + v.n_counts);
+    return f;
+}
+
 void Forest::view(pjb_forest& out) const {
     memset(&out, 0, sizeof out);
     out.n_trees = nTrees;

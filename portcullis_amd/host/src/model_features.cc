@@ -213,5 +213,27 @@ std::vector<double> ModelFeatures::forestPredict(const JunctionList& x, const Fo
     return pred;
 }
 
+Forest ModelFeatures::growForest(const JunctionList& x, int32_t nTrees, uint32_t seed, std::vector<double>* featuresOut) {
+    if (x.empty()) throw ForestException("No junctions to grow a forest on");
+    const size_t F = PJB_N_FEATURES;
+    std::vector<double> rows(x.size() * F, 0.0);
+    DeviceRun run;
+    openRun(run, *this, gmap, device, x);
+    run.check(pjb_filt_features(run.ctx, run.rows.data(), (int64_t)run.rows.size(), x[0]->getMeanReadLength(), L95, &run.m, rows.data()), "pjb_filt_features");
+    for (size_t i = 0; i < x.size(); i++) rows[i * F] = x[i]->isGenuine() ? 1.0 : 0.0;
+    const std::vector<int32_t>& active = activeFeatures();
+    std::vector<double> matrix(x.size() * active.size());
+    for (size_t i = 0; i < x.size(); i++)
+        for (size_t k = 0; k < active.size(); k++) matrix[i * active.size() + k] = rows[i * F + (size_t)active[k]];
+    pjb_grow_params p;
+    memset(&p, 0, sizeof p);
+    p.n_trees = nTrees;
+    p.seed = seed;
+    pjb_grow_result r;
+    run.check(pjb_forest_grow(run.ctx, matrix.data(), (int64_t)x.size(), (int32_t)active.size(), &p, &r), "pjb_forest_grow");
+    if (featuresOut) featuresOut->swap(rows);
+    return Forest::fromView(r.forest, r.class_values);
+}
+
 }  // namespace ml
 }  // namespace portcullis

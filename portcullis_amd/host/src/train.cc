@@ -1,0 +1,180 @@
+// Train: see portcullis/train.hpp.
+#include <portcullis/train.hpp>
+
+#include <sys/stat.h>
+
+#include <chrono>
+#include <fstream>
+#include <iomanip>
+#include <iostream>
+
+#include <portcullis/ml/model_features.hpp>
+
+#include "../../../include/portcullis_amd.h"
+
+using std::cout;
+using std::endl;
+using std::string;
+
+namespace portcullis {
+
+namespace {
+bool exists(const string& p) {
+    struct stat st;
+    return stat(p.c_str(), &st) == 0;
+}
+bool isDirectory(const string& p) {
+    struct stat st;
+    return stat(p.c_str(), &st) == 0 && S_ISDIR(st.st_mode);
+}
+bool createDirectories(const string& p) {
+    string cur;
+    for (size_t i = 0; i <= p.size(); i++) {
+        if (i == p.size() || p[i] == '/') {
+            if (!cur.empty() && !exists(cur) && mkdir(cur.c_str(), 0777) != 0 && !exists(cur)) return false;
+        }
+        if (i < p.size()) cur.push_back(p[i]);
+    }
+    return isDirectory(p);
+}
+}  // namespace
+
+void Train::train() {
+    size_t slash = output.find_last_of('/');
+    string outputDir = slash == string::npos ? string(".") : output.substr(0, slash);
+    if (outputDir.empty()) outputDir = "/";
+    if (trees < 1) throw TrainException("--trees must be at least 1");
+    if (!exists(positiveFile)) throw TrainException("Could not find positive junction file at: " + positiveFile);
+    if (!exists(negativeFile)) throw TrainException("Could not find negative junction file at: " + negativeFile);
+    if (!exists(prepData.getGenomeFilePath())) throw TrainException("Could not find prepared genome file at: " + prepData.getGenomeFilePath());
+    if (!exists(outputDir)) {
+        if (!createDirectories(outputDir)) throw TrainException("Could not create output directory at: " + outputDir);
+    } else if (!isDirectory(outputDir))
+        throw TrainException("File exists with name of suggested output directory: " + outputDir);
+    cout << "Loading positive junctions from " << positiveFile << " ...";
+    cout.flush();
+    JunctionSystem pos(positiveFile);
+    cout << " done." << endl << "Found " << pos.getJunctions().size() << " junctions." << endl;
+    cout << "Loading negative junctions from " << negativeFile << " ...";
+    cout.flush();
+    JunctionSystem neg(negativeFile);
+    cout << " done." << endl << "Found " << neg.getJunctions().size() << " junctions." << endl << endl;
+    if (pos.getJunctions().empty()) throw TrainException("The positive set is empty: " + positiveFile);
+    if (neg.getJunctions().empty()) throw TrainException("The negative set is empty: " + negativeFile);
+    for (const auto& j : neg.getJunctions())
+        if (pos.getJunction(*(j->getIntron())) != nullptr)
+            throw TrainException("Junction " + j->getIntron()->toString() + " is in the positive and in the negative set");
+    // no device: said before the genome is read, in the words `prep` has for it
+    if (pjb_device_count() <= 0)
+        throw TrainException("No MI355X (HIP device) is visible: the forest is grown on the GPU and has no CPU fallback.  Run train where the GPU is.");
+    // lib/src/model_features.cc:297-304: positives, then negatives, sorted as one system
+    JunctionList training;
+    training.reserve(pos.getJunctions().size() + neg.getJunctions().size());
+    for (const auto& j : pos.getJunctions()) {
+        j->setGenuine(true);
+        training.push_back(j);
+    }
+    for (const auto& j : neg.getJunctions()) {
+        j->setGenuine(false);
+        training.push_back(j);
+    }
+    JunctionSystem trainingSystem(training);
+    trainingSystem.sort();
+    const JunctionList& x = trainingSystem.getJunctions();
+    cout << "Training a random forest model" << endl << "------------------------------" << endl << endl;
+    cout << "Creating feature vector for " << x.size() << " junctions (" << pos.getJunctions().size() << " positive, " << neg.getJunctions().size()
+         << " negative)" << endl;
+    ml::ModelFeatures mf;  // L95 = 0, untrained Markov models: the rows `filt --model_file` scores
+    mf.setDevice(device);
+    mf.initGenomeMapper(prepData.getGenomeFilePath());
+    std::vector<double> features;
+    cout << "Growing " << trees << " trees" << endl;
+    const ml::Forest forest = mf.growForest(x, trees, seed, saveFeatures ? &features : nullptr);
+    ml::ModelFeatures::checkForest(forest);  // (what filt will ask of it)
+    if (verbose) cout << "Grown " << forest.treeOff.back() << " nodes in " << forest.nTrees << " trees" << endl;
+    if (saveFeatures) {  // lib/src/model_features.cc:402-410: the active columns, default stream formatting
+        const string file = output + ".features.training";
+        if (verbose) cout << "Saving feature vector to disk: " << file << endl;
+        std::ofstream fout(file.c_str());
+        const std::vector<string> names = ml::ModelFeatures::featureNames();
+        const std::vector<int32_t>& active = ml::ModelFeatures::activeFeatures();
+        fout << Intron::locationOutputHeader();
+        for (const int32_t k : active) fout << "\t" << names[(size_t)k];
+        fout << endl;
+        for (size_t i = 0; i < x.size(); i++) {
+            fout << *(x[i]->getIntron());
+            for (const int32_t k : active) fout << "\t" << features[i * names.size() + (size_t)k];
+            fout << endl;
+        }
+    }
+    forest.save(output + ".forest");
+    cout << "Saved forest to file " << output << ".forest" << endl;
+}
+
+string Train::helpMessage() {
+    return string("Portcullis Train Mode Help\n\n") +
+           "Grows the random forest model that `filt --model_file` scores junctions with, on the GPU, from a\n"
+           "table of junctions known to be genuine and a table of junctions known not to be.  The model is the\n"
+           "file ranger 0.3.8 saves for the same feature rows (byte for byte).\n\n"
+           "Usage: " + usage() + "\n\n" +
+           "Options:\n"
+           "  -o [ --output ] arg (=" + DEFAULT_TRAIN_OUTPUT + ")  Output prefix: <prefix>.forest is written.\n"
+           "  --trees arg (=250)                   The number of trees in the forest.\n"
+           "  --seed arg (=1236456789)             The forest's seed (the reference's is the default).\n"
+           "  --save_features                      Also write <prefix>.features.training: the feature rows the forest was grown on.\n"
+           "  -v [ --verbose ]                     Print extra information\n"
+           "  --help                               Produce help message\n\n"
+           "Not built: choosing the two sets (the reference's self-training layers), L95 and Markov model training, SMOTE, ENN,\n"
+           "under-sampling, --genuine, variable importance and the out-of-bag error (every row is in bag).\n";
+}
+
+int Train::main(int argc, char* argv[]) {
+    std::vector<string> positional;
+    string output = DEFAULT_TRAIN_OUTPUT;
+    int32_t trees = DEFAULT_TRAIN_TREES;
+    uint32_t seed = DEFAULT_TRAIN_SEED;
+    bool saveFeatures = false, verbose = false, help = false;
+    // long options take their value as the next argument or after '='
+    for (int i = 1; i < argc; i++) {
+        string a = argv[i], inlineValue;
+        bool hasInline = false;
+        if (a.rfind("--", 0) == 0 && a.find('=') != string::npos) {
+            inlineValue = a.substr(a.find('=') + 1);
+            a = a.substr(0, a.find('='));
+            hasInline = true;
+        }
+        auto need = [&]() -> string {
+            if (hasInline) return inlineValue;
+            if (i + 1 >= argc) throw TrainException("Option " + a + " needs a value");
+            return argv[++i];
+        };
+        if (a == "-o" || a == "--output") output = need();
+        else if (a == "--trees") trees = (int32_t)std::stol(need());
+        else if (a == "--seed") seed = (uint32_t)std::stoul(need());
+        else if (a == "--save_features") saveFeatures = true;
+        else if (a == "--devices") (void)need();
+        else if (a == "-v" || a == "--verbose") verbose = true;
+        else if (a == "--help") help = true;
+        else if (!a.empty() && a[0] == '-' && a.size() > 1) throw TrainException("Unknown option: " + a);
+        else positional.push_back(a);
+    }
+    if (help || argc <= 1 || positional.size() < 3) {
+        cout << helpMessage() << endl;
+        return 1;
+    }
+    const auto t0 = std::chrono::steady_clock::now();
+    cout << "Running portcullis in train mode" << endl << "--------------------------------" << endl << endl;
+    Train t(positional[0], positional[1], positional[2], output);
+    t.setTrees(trees);
+    t.setSeed(seed);
+    t.setSaveFeatures(saveFeatures);
+    t.setVerbose(verbose);
+    t.train();
+    const double s = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+    std::ios::fmtflags f(cout.flags());
+    cout << endl << "Portcullis train completed." << endl << "Total runtime: " << std::fixed << std::setprecision(1) << s << "s" << endl << endl;
+    cout.flags(f);
+    return 0;
+}
+
+}  // namespace portcullis
