@@ -601,6 +601,22 @@ typedef struct pjb_grow_result {
 } pjb_grow_result;
 int pjb_forest_grow(pjb_ctx *ctx, const double *data, int64_t n_rows, int32_t n_cols, const pjb_grow_params *p, pjb_grow_result *out);
 
+/* ---- self-training: brute-force K nearest neighbours, the search under SMOTE and ENN ---------------------------
+ * KNN::doSlice (lib/src/knn.cc:46-99).  data: row-major n_rows x n_cols, host.  The distance of two rows is
+ * s = sum over the columns, in ascending column order, of (base[c] - test[c])^2 in f64, the subtraction, the product and the sum
+ * each rounded on their own.  A row's own index takes part (distance 0).  nn_out (n_rows x k, host) gets, per row, the indices of
+ * the k rows that are smallest under the total order (s, index), in that order: the reference walks the base rows in ascending
+ * order and puts a candidate behind the entries of equal distance.  k is what the caller passes; KNN's constructor rule
+ * (k = rows if rows < defaultK && rows < 100) is the caller's.  The result does not depend on how the base range is cut into
+ * chunks (pjb_set_option("knn_chunk", n) forces the chunk length; 0 is the default sizing).
+ * PJB_ERR_ARG, found on the host before anything is launched: k < 1, k > PJB_KNN_MAX_K or k > n_rows; n_cols < 1 or
+ * > PJB_KNN_MAX_COLS; n_rows < 1 or > 2^22; a value that is not finite or larger than 1e153 in magnitude (a distance could
+ * overflow; the reference puts a NaN distance at the front of its list, which is not reproduced).
+ * Works on any context (PJB_FLAG_NO_CHAINS too). */
+#define PJB_KNN_MAX_K 8
+#define PJB_KNN_MAX_COLS 32
+int pjb_knn(pjb_ctx *ctx, const double *data, int64_t n_rows, int32_t n_cols, int32_t k, uint32_t *nn_out);
+
 /* ---- `portcullis bamfilt` ----------------------------------------------------------------
  * The per-alignment decision of BamFilter::filter (src/bam_filter.cc:152-247): walk the CIGAR as
  * BamFilter::containsJunctionInSystem / clipMSR do (src/bam_filter.cc:75-150) and probe the set of junctions that

@@ -232,7 +232,7 @@ void pjb_destroy(pjb_ctx *c) {
     }
     Buf *all[] = {&c->b_cursor, &c->b_scan_tiles, &c->b_hasx, &c->b_xtotal, &c->b_fasta_raw, &c->b_inf_comp, &c->b_inf_out, &c->b_inf_blocks, &c->b_inf_status, &c->b_inf_scratch, &c->b_inf_bitmap,
                   &c->b_bam_seg, &c->b_bam_rec, &c->b_bam_ctl, &c->f_pos, &c->f_cigoff, &c->f_cigar, &c->f_codes, &c->g_rows, &c->g_models, &c->g_refs,
-                  &c->g_out, &c->g_bad, &c->r_nodes, &c->r_leaf, &c->r_roots, &c->r_data, &c->r_pred, &c->r_colmap, &c->w_pool, &c->w_pack,
+                  &c->g_out, &c->g_bad, &c->r_nodes, &c->r_leaf, &c->r_roots, &c->r_data, &c->r_pred, &c->r_colmap, &c->w_pool, &c->w_pack, &c->n_data, &c->n_part_d, &c->n_part_i, &c->n_out,
                   &c->x_pos, &c->x_endx, &c->x_q, &c->x_prefq, &c->x_ce, &c->x_bound, &c->x_de, &c->x_dropped, &c->x_zlist, &c->x_cnt,
                   &c->x_tabk, &c->x_tabc, &c->x_rs, &c->x_re, &c->x_rr, &c->x_tileoff, &c->x_xrall, &c->x_tab,
                   &c->b_dfl_in, &c->b_dfl_sym, &c->b_dfl_slots, &c->b_dfl_size, &c->b_dfl_off, &c->b_dfl_packed};
@@ -1838,6 +1838,9 @@ int pjb_set_option(pjb_ctx *c, const char *name, int64_t value) {
     } else if (n == "grow_batch") {
         if (value < 0 || value > 32768) return fail(c, PJB_ERR_ARG, "set_option: grow_batch takes 0 (the default: what the pool holds) to 32768 trees");
         c->grow_batch = (u32)value;
+    } else if (n == "knn_chunk") {
+        if (value < 0 || value > (1 << 22)) return fail(c, PJB_ERR_ARG, "set_option: knn_chunk takes 0 (the default: sized to fill the chip) to %d base rows", 1 << 22);
+        c->knn_chunk = (u32)value;
     } else if (n == "list_cap") c->list_cap_forced = (u32)std::max<int64_t>(0, std::min<int64_t>(value, 1 << 30));
     else return fail(c, PJB_ERR_ARG, "set_option: unknown option '%s'", name);
     return PJB_OK;

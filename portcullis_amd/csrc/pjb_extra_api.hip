@@ -1,10 +1,12 @@
 // pjb_extra_api.hip -- the part of the C ABI behind `junc --extra` (depth, flanking counts, name multiplicities: pjb_extra_finish), `bamfilt`
 // (pjb_filter_*), `filt`'s feature rows and forest (pjb_filt_features, pjb_forest_*, pjb_filt_scores) and `train`'s growing of one
-// (pjb_forest_grow); kernels in pjb_extra.hip.h, pjb_forest.hip.h and pjb_grow.hip.h.
+// (pjb_forest_grow) and self-training's nearest neighbours (pjb_knn); kernels in pjb_extra.hip.h, pjb_forest.hip.h, pjb_grow.hip.h
+// and pjb_knn.hip.h.
 #include "pjb_host.hip.h"
 #include "pjb_extra.hip.h"
 #include "pjb_forest.hip.h"
 #include "pjb_grow.hip.h"
+#include "pjb_knn.hip.h"
 
 // The name codes of a chain's spliced records, in BAM order, to `codes`; their number to cnt->n_spliced.  Through the tile lists the
 // chain's first kernels left in its slot (tile numbers run through the chain).
@@ -885,6 +887,62 @@ int pjb_forest_grow(pjb_ctx *c, const double *data, int64_t n_rows, int32_t n_co
     out->class_values = G.class_values.data();
     char msg[200] = "";
     if (pjb_forest_check(&f, msg, (int)sizeof msg) != PJB_OK) return fail(c, PJB_ERR_STATE, "pjb_forest_grow: the grown forest cannot be walked: %s", msg);
+    return PJB_OK;
+}
+
+// Waves the default chunking of pjb_knn aims at: 256 CUs x 4 SIMDs x 4 waves, so that scalar-load latency has other waves to hide behind.
+static constexpr size_t KNN_WAVES = 4096;
+// A chunk shorter than this spends its time filling the lists (every one of the first rows of a chunk is an insertion).
+static constexpr size_t KNN_MIN_CHUNK = 256;
+// |value| <= this: 32 squared differences cannot overflow (32 * (2e153)^2 = 1.28e308), so every distance is finite and ordered.
+static constexpr double KNN_MAX_ABS = 1e153;
+static_assert(KN_LIST == PJB_KNN_MAX_K, "the lists of pjb_knn.hip.h hold PJB_KNN_MAX_K entries");
+
+// KNN::execute (lib/src/knn.cc): see include/portcullis_amd.h and pjb_knn.hip.h.
+int pjb_knn(pjb_ctx *c, const double *data, int64_t n_rows, int32_t n_cols, int32_t k, uint32_t *nn_out) {
+    if (!c) return PJB_ERR_ARG;
+    if (!data || !nn_out) return fail(c, PJB_ERR_ARG, "pjb_knn: bad arguments");
+    if (n_cols < 1 || n_cols > PJB_KNN_MAX_COLS) return fail(c, PJB_ERR_ARG, "pjb_knn: %d columns (1 to %d)", n_cols, PJB_KNN_MAX_COLS);
+    if (n_rows < 1 || n_rows > (1ll << 22)) return fail(c, PJB_ERR_ARG, "pjb_knn: %lld rows (1 to %d)", (long long)n_rows, 1 << 22);
+    if (k < 1 || k > PJB_KNN_MAX_K || k > n_rows)
+        return fail(c, PJB_ERR_ARG, "pjb_knn: k = %d (1 to %d, and no more than the %lld rows)", k, PJB_KNN_MAX_K, (long long)n_rows);
+    const size_t n = (size_t)n_rows, C = (size_t)n_cols;
+    const size_t NC = n_cols <= 28 ? 28 : 32; // the compiled widths: the 28 features of self-training, and the limit
+    std::vector<double> padded(n * NC, 0.0);
+    for (size_t r = 0; r < n; r++)
+        for (size_t j = 0; j < C; j++) {
+            const double v = data[r * C + j];
+            if (!(fabs(v) <= KNN_MAX_ABS)) // (a NaN too)
+                return fail(c, PJB_ERR_ARG, "pjb_knn: row %zu, column %zu is %g: not finite, or so large that a distance could overflow", r, j, v);
+            padded[r * NC + j] = v;
+        }
+    size_t chunk = c->knn_chunk;
+    if (!chunk) {
+        const size_t row_waves = (n + 63) / 64;
+        const size_t want = (KNN_WAVES + row_waves - 1) / row_waves;
+        chunk = std::max(KNN_MIN_CHUNK, (n + want - 1) / want);
+    }
+    chunk = std::min(chunk, n);
+    const size_t n_chunks = (n + chunk - 1) / chunk;
+    if (n_chunks > 65535) return fail(c, PJB_ERR_ARG, "pjb_knn: knn_chunk %zu makes %zu chunks of %zu rows (65535 at most)", chunk, n_chunks, n);
+    HIP_TRY(c, hipSetDevice(c->cfg.device));
+    hipStream_t st = c->stream;
+    int rc;
+    if ((rc = ensure(c, c->n_data, n * NC * sizeof(double)))) return rc;
+    if ((rc = ensure(c, c->n_part_d, n_chunks * KN_LIST * n * sizeof(double)))) return rc;
+    if ((rc = ensure(c, c->n_part_i, n_chunks * KN_LIST * n * sizeof(u32)))) return rc;
+    if ((rc = ensure(c, c->n_out, n * (size_t)k * sizeof(u32)))) return rc;
+    HIP_TRY(c, hipMemcpyAsync(c->n_data.p, padded.data(), n * NC * sizeof(double), hipMemcpyHostToDevice, st));
+    const dim3 grid((unsigned)((n + 63) / 64), (unsigned)n_chunks);
+    if (NC == 28)
+        LAUNCH(c, "kn_partial", kn_partial<28>, grid, dim3(64), (const double *)c->n_data.p, (u32)n, (u32)chunk, (double *)c->n_part_d.p, (u32 *)c->n_part_i.p);
+    else
+        LAUNCH(c, "kn_partial", kn_partial<32>, grid, dim3(64), (const double *)c->n_data.p, (u32)n, (u32)chunk, (double *)c->n_part_d.p, (u32 *)c->n_part_i.p);
+    LAUNCH(c, "kn_merge", kn_merge, dim3((unsigned)((n + 255) / 256)), dim3(256), (const double *)c->n_part_d.p, (const u32 *)c->n_part_i.p, (u32)n,
+           (u32)n_chunks, (u32)k, (u32 *)c->n_out.p);
+    HIP_TRY(c, hipMemcpyAsync(nn_out, c->n_out.p, n * (size_t)k * sizeof(u32), hipMemcpyDeviceToHost, st));
+    HIP_TRY(c, hipStreamSynchronize(st)); // (the one wait; `padded` is pageable and lives until here)
+    if (c->ktime) ev_collect(c, MISC_POOL);
     return PJB_OK;
 }
 

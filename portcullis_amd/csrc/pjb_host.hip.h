@@ -326,6 +326,8 @@ struct pjb_ctx {
     int32_t r_trees = 0, r_classes = 0, r_vars = 0, r_dep = 0; // r_trees == 0: no forest loaded
     Buf w_pool, w_pack;      // pjb_forest_grow (pjb_grow.hip.h): the matrix, the trees' lists and nodes of one batch; the packed nodes
     u32 grow_batch = 0;      // pjb_set_option("grow_batch", n): trees grown side by side (tests; 0: as many as GROW_POOL_BYTES holds)
+    Buf n_data, n_part_d, n_part_i, n_out; // pjb_knn (pjb_knn.hip.h): the padded matrix, the chunks' lists (distances, indices), the neighbours
+    u32 knn_chunk = 0;       // pjb_set_option("knn_chunk", n): base rows per chunk (tests; 0: sized so that the grid fills the chip)
     struct GrowOut {         // the forest of the last pjb_forest_grow: what pjb_grow_result points to
         std::vector<uint8_t> is_ordered;
         std::vector<int64_t> tree_off, count_off;

@@ -27,7 +27,7 @@ EXPORTS = [
     "pjb_select_timed_kernels", "pjb_host_alloc", "pjb_host_free", "pjb_host_register", "pjb_host_unregister", "pjb_inflate_bgzf", "pjb_deflate_bgzf", "pjb_submit_bam", "pjb_collect_device", "pjb_set_row_mirror",
     "pjb_extra_finish", "pjb_set_option", "pjb_merge_rows", "pjb_plan_groups", "pjb_bam_begin", "pjb_bam_piece", "pjb_bam_pieces_done", "pjb_bam_end", "pjb_bam_inflate_done", "pjb_filter_set_junctions", "pjb_filter_batch", "pjb_filt_features",
     "pjb_index_begin", "pjb_index_piece", "pjb_index_end",
-    "pjb_forest_check", "pjb_forest_load", "pjb_forest_predict", "pjb_filt_scores", "pjb_forest_grow",
+    "pjb_forest_check", "pjb_forest_load", "pjb_forest_predict", "pjb_filt_scores", "pjb_forest_grow", "pjb_knn",
 ]
 N_FEATURES = 34
 KMER_TABLE = 3125 * 5
@@ -169,6 +169,7 @@ def load():
         L.pjb_filt_scores.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_double, C.c_uint32, C.POINTER(PjbMarkovModels), C.c_void_p, C.c_void_p,
                                       C.c_void_p]
         L.pjb_forest_grow.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.POINTER(PjbGrowParams), C.POINTER(PjbGrowResult)]
+        L.pjb_knn.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_void_p]
         L.pjb_index_begin.argtypes = [C.c_void_p]
         L.pjb_index_piece.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int32, C.c_int32, C.POINTER(C.c_uint64)]
         L.pjb_index_end.argtypes = [C.c_void_p, C.POINTER(PjbIndexResult)]
@@ -533,6 +534,15 @@ class Context:
         r = PjbGrowResult()
         self._check(self._L.pjb_forest_grow(self._h, data.ctypes.data_as(C.c_void_p), data.shape[0], data.shape[1], C.byref(p), C.byref(r)))
         return Forest._from_struct(r.forest, r.class_values)
+
+    def knn(self, data, k):
+        """pjb_knn: data float64 [n, n_cols] -> uint32 [n, k], per row the k rows nearest under (squared distance, index), the row
+        itself among them: bit for bit KNN::doSlice's lists."""
+        data = np.ascontiguousarray(data, dtype=np.float64)
+        assert data.ndim == 2
+        out = np.zeros((max(len(data), 1), max(int(k), 1)), dtype=np.uint32)
+        self._check(self._L.pjb_knn(self._h, data.ctypes.data_as(C.c_void_p), data.shape[0], data.shape[1], int(k), out.ctypes.data_as(C.c_void_p)))
+        return out[: len(data)]
 
     def filt_scores(self, rows, mean_read_length, l95, models, var_feature, want_features=False):
         """pjb_filt_scores: feature rows and forest walk in one call; float64 [n, n_classes] (and the [n, N_FEATURES] rows if asked)."""

@@ -2,7 +2,9 @@
 // a model: a saved random-forest model (walked on the device, fused with the feature rows: ModelFeatures::forestPredict), rule files
 // (rule_filter.hpp: no Python), the length / canonical / coverage filters, the rescue of junctions found in a reference BED, and the
 // .pass / .fail / .ref outputs.  Same setters, same messages, same order of stages.  Self-training -- the reference's default when
-// neither a model nor --no_ml is given -- is refused with the way out.  Deviations: INTEGRATION.md, "Known deviations".
+// neither a model nor --no_ml is given -- is built behind --self_train <data_dir> (selfTrain(): the layered rule sets choose the
+// initial sets, ModelFeatures::trainInstance balances them and grows the forest on the device); without that flag it is refused with
+// the way out.  Deviations: INTEGRATION.md, "Known deviations".
 #pragma once
 
 #include <string>
@@ -27,6 +29,8 @@ class JunctionFilter {
     PreparedFiles prepData;
     std::string modelFile, filterFile, referenceFile, output;
     bool train = false;
+    std::string selfTrainDir, trainingRule = "balanced";  // --self_train: the reference's data/ directory; a rule set in it (or a directory)
+    bool smote = true, enn = false, saveLayers = false, saveMatrix = false;
     uint16_t threads = DEFAULT_FILTER_THREADS;
     bool saveBad = false, saveFeatures = false, outputExonGFF = false, outputIntronGFF = false;
     uint32_t maxLength = 0, minCov = 1;
@@ -37,6 +41,9 @@ class JunctionFilter {
     int device = 0;
 
     void forestPredict(const JunctionList& all, JunctionList& pass, JunctionList& fail, ml::ModelFeatures& mf, const ml::Forest& forest);
+    // src/junction_filter.cc:278-437: true if a forest was trained (mf holds L95 and the Markov models, <output>.selftrain.forest is
+    // written); false if the lenient rule file took its place (filterFile is set)
+    bool selfTrain(const JunctionList& all, ml::ModelFeatures& mf, ml::Forest& forest);
     void printFilteringResults(const JunctionList& in, const JunctionList& pass, const JunctionList& fail, const std::string& prefix);
 
 public:
@@ -58,6 +65,12 @@ public:
     void setModelFile(const std::string& v) { modelFile = v; }
     void setReferenceFile(const std::string& v) { referenceFile = v; }
     void setTrain(bool v) { train = v; }
+    void setSelfTrainDir(const std::string& v) { selfTrainDir = v; }
+    void setTrainingRule(const std::string& v) { trainingRule = v; }
+    void setSmote(bool v) { smote = v; }
+    void setENN(bool v) { enn = v; }
+    void setSaveLayers(bool v) { saveLayers = v; }
+    void setSaveMatrix(bool v) { saveMatrix = v; }
     void setSaveFeatures(bool v) { saveFeatures = v; }
     void setThreshold(double v) { threshold = v; }
     void setDevice(int v) { device = v; }

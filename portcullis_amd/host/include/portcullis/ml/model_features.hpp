@@ -4,7 +4,8 @@
 // windows scored against six k-mer and two position models -- comes from the device (pjb_filt_features).
 // juncs2FeatureVectors returns a plain row-major matrix whose columns are VAR_NAMES + Junction::JAD_NAMES.  The random-forest
 // side: a saved forest (ml/forest.hpp) is walked on the device over the same rows without the matrix leaving it (forestPredict);
-// growing a forest from labelled junctions (growForest, pjb_forest_grow) is `train`'s; choosing the labels (self-training) is not built.
+// growing a forest from labelled junctions (growForest, pjb_forest_grow) is `train`'s; trainInstance is self-training's: the two sets
+// balanced (SMOTE or under-sampling), optionally cleaned (ENN), and grown; the nearest neighbours of both come from pjb_knn.
 #pragma once
 
 #include <string>
@@ -58,6 +59,19 @@ public:
     // device's (pjb_filt_features: what forestPredict walks), column 0 the junctions' isGenuine(), the variables activeFeatures();
     // the forest is grown on the same device (pjb_forest_grow).  featuresOut (optional): the full matrix, as forestPredict returns it.
     Forest growForest(const JunctionList& x, int32_t nTrees, uint32_t seed, std::vector<double>* featuresOut = nullptr);
+    // ModelFeatures::trainInstance (lib/src/model_features.cc:252-447) for a probability forest.  pos / neg: sorted, genuine flags set.
+    // N = |pos| / |neg| - 1.  With smote: N > 0 adds N synthetic rows per negative (Smote, k = 5), N <= 0 erases random negatives until
+    // there are no more than positives.  With enn: rows whose 3 nearest neighbours (itself among them) do not all carry their label
+    // are dropped; unlike the reference, which sizes the cleaned matrix by the old row count and trains on an uninitialised tail, the
+    // matrix then holds the kept rows only.  The matrix -- the label and the 28 active features of sorted(pos + kept negatives), then
+    // the synthetic rows with label 0 -- is grown with the reference's seed.  matrixOut (optional): that matrix, row-major, 29 columns.
+    // outputPrefix + ".features" is written if saveFeatures (the real rows, before ENN).
+    struct TrainOptions {
+        int32_t trees = 250;  // DEFAULT_SELFTRAIN_TREES
+        bool smote = true, enn = false, saveFeatures = false, verbose = false;
+        std::string outputPrefix;
+    };
+    Forest trainInstance(const JunctionList& pos, const JunctionList& neg, const TrainOptions& o, std::vector<double>* matrixOut = nullptr);
 };
 
 }  // namespace ml

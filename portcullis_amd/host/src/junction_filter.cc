@@ -12,7 +12,9 @@
 #include <iostream>
 #include <unordered_set>
 
+#include "../../../include/portcullis_amd.h"
 #include "rule_filter.hpp"
+#include "self_train.hpp"
 
 using std::cout;
 using std::endl;
@@ -82,8 +84,17 @@ void JunctionFilter::forestPredict(const JunctionList& all, JunctionList& pass, 
     cout << "Creating feature vector" << endl << "Initialising random forest" << endl << "Making predictions" << endl;
     std::vector<double> features;
     mf.setDevice(device);
-    const std::vector<double> pred = mf.forestPredict(all, forest, saveFeatures ? &features : nullptr);
+    const std::vector<double> pred = mf.forestPredict(all, forest, saveFeatures || saveMatrix ? &features : nullptr);
     const size_t nClasses = forest.classValues.size();
+    if (saveMatrix) {  // the 29 active columns of every junction as scored: little-endian f64, no header
+        const std::vector<int32_t>& active = ml::ModelFeatures::activeFeatures();
+        const size_t F = ml::ModelFeatures::featureNames().size();
+        std::vector<double> m(all.size() * active.size());
+        for (size_t i = 0; i < all.size(); i++)
+            for (size_t k = 0; k < active.size(); k++) m[i * active.size() + k] = features[i * F + (size_t)active[k]];
+        std::ofstream fout((output + ".testing.matrix.f64").c_str(), std::ios::binary);
+        fout.write((const char*)m.data(), (std::streamsize)(m.size() * sizeof(double)));
+    }
     if (saveFeatures) {  // :649-657: the active columns, default stream formatting
         std::ofstream fout((output + ".features.testing").c_str());
         const std::vector<string> names = ml::ModelFeatures::featureNames();
@@ -105,14 +116,127 @@ void JunctionFilter::forestPredict(const JunctionList& all, JunctionList& pass, 
     }
 }
 
+namespace {
+// the junctions as the table the rule engine reads: the columns but the index, one vector of cells per junction
+void asTable(const JunctionList& juncs, std::vector<string>& fieldnames, std::vector<std::vector<string>>& table) {
+    fieldnames = splitOn(Junction::junctionOutputHeader(), '\t', false);
+    fieldnames.erase(fieldnames.begin());  // (the index column is the table's index, not a field)
+    table.clear();
+    table.reserve(juncs.size());
+    string row;
+    for (auto& j : juncs) {
+        row.clear();
+        j->appendTabRow(row);
+        std::vector<string> cells = splitOn(row, '\t', false);
+        cells.erase(cells.begin());
+        table.push_back(std::move(cells));
+    }
+}
+void saveTab(const string& path, const JunctionList& all, const std::vector<size_t>& rows) {
+    std::ofstream out(path.c_str());
+    out << Junction::junctionOutputHeader() << "\n";
+    for (const size_t r : rows) out << *all[r] << "\n";
+    if (!out.good()) throw JuncFilterException("Could not write " + path);
+}
+}  // namespace
+
+bool JunctionFilter::selfTrain(const JunctionList& all, ml::ModelFeatures& mf, ml::Forest& forest) {  // :278-437
+    const string lowJuncs = selfTrainDir + "/low_juncs_filter.json";
+    if (all.size() < 200) {
+        cout << "Less that 200 junctions found in input set.  This is not enough to build a trained model.  Will apply a lenient rule-based filter instead." << endl;
+        filterFile = lowJuncs;
+        return false;
+    }
+    if (all.size() < 500)  // rule_filter.py:142-143 raises here, and the reference dies of it
+        throw JuncFilterException("Not enough junctions to create training set: self-training needs 500 junctions at least and the input holds " +
+                                  std::to_string(all.size()) + " (the reference's script raises here and the reference ends).  With fewer than 200 a lenient rule file "
+                                  "is applied instead; between the two, pass a model with --model_file, or --no_ml with --filter_file.");
+    cout << "Self training mode activated." << endl << endl;
+    const selftrain::Layers layers = selftrain::findLayers(trainingRule, selfTrainDir);
+    cout << "Applying the following set of rule-based filters to create initial positive set." << endl;
+    for (size_t i = 0; i < layers.pos.size(); i++) cout << i + 1 << "\t" << layers.pos[i] << endl;
+    cout << "Applying a set of rule-based filters to create initial negative set." << endl;
+    for (size_t i = 0; i < layers.neg.size(); i++) cout << i + 1 << "\t" << layers.neg[i] << endl;
+    std::vector<string> fieldnames;
+    std::vector<std::vector<string>> table;
+    asTable(all, fieldnames, table);
+    const selftrain::TrainingSets sets = selftrain::createTrainingSets(fieldnames, table, layers.pos, layers.neg);
+    cout << sets.log << endl;
+    const string prefix = output + ".selftrain.initialset";
+    {
+        std::ofstream l95out((prefix + ".L95_intron_size.txt").c_str());
+        l95out << "Length of intron at 95th percentile" << "\n" << sets.L95 << "\n";
+    }
+    if (saveLayers) {
+        for (size_t i = 0; i < sets.posLayers.size(); i++) {
+            const bool sizeLayer = sets.posSizeLayer && i + 1 == sets.posLayers.size();
+            saveTab(prefix + (sizeLayer ? string(".pos_layer_intronsize.tab") : ".pos_layer_" + std::to_string(i + 1) + ".tab"), all, sets.posLayers[i]);
+        }
+        for (size_t i = 0; i < sets.negLayers.size(); i++) {
+            const bool sizeLayer = i + 1 == sets.negLayers.size();
+            saveTab(prefix + (sizeLayer ? string(".neg_layer_intronsize.tab") : ".neg_layer_" + std::to_string(i + 1) + ".tab"), all, sets.negLayers[i]);
+        }
+    }
+    saveTab(prefix + ".pos.junctions.tab", all, sets.pos);
+    saveTab(prefix + ".neg.junctions.tab", all, sets.neg);
+    JunctionList pos, neg;
+    for (const size_t r : sets.pos) pos.push_back(all[r]);
+    for (const size_t r : sets.neg) neg.push_back(all[r]);
+    std::sort(pos.begin(), pos.end(), JunctionComparator());  // posSystem.sort() / negSystem.sort()
+    std::sort(neg.begin(), neg.end(), JunctionComparator());
+    cout << "Initial training set consists of " << pos.size() << " positive and " << neg.size() << " negative junctions." << endl << endl;
+    if (pos.size() < 50 || neg.size() < 50) {
+        cout << "Training set is of insufficient size to reliably use machine learning, we will filter junctions using a lenient rule-based filter instead." << endl;
+        filterFile = lowJuncs;
+        return false;
+    }
+    if (pjb_device_count() <= 0)
+        throw JuncFilterException("No MI355X (HIP device) is visible: self-training searches neighbours and grows its forest on the GPU and has no CPU fallback.  "
+                                  "Run filt where the GPU is.");
+    // the reference's sets are junctions of their own, read back from the two tables; here they are the input's, and get their flags back
+    std::vector<bool> genuineBefore;
+    for (auto& j : all) genuineBefore.push_back(j->isGenuine());
+    for (auto& j : pos) j->setGenuine(true);
+    for (auto& j : neg) j->setGenuine(false);
+    cout << "Pos to neg ratio: " << 1.0 - ((double)pos.size() / (double)(pos.size() + neg.size())) << endl << endl;
+    mf.initGenomeMapper(prepData.getGenomeFilePath());
+    mf.L95 = sets.L95;
+    cout << "Confirming intron length L95 is: " << mf.L95 << endl;
+    cout << "Feature learning from training set ...";
+    cout.flush();
+    mf.trainCodingPotentialModel(pos);
+    mf.trainSplicingModels(pos, neg);
+    cout << " done." << endl << endl;
+    cout << "Training Random Forest" << endl << "----------------------" << endl << endl;
+    ml::ModelFeatures::TrainOptions o;
+    o.smote = smote;
+    o.enn = enn;
+    o.saveFeatures = saveFeatures;
+    o.verbose = verbose;
+    o.outputPrefix = output + ".selftrain";
+    std::vector<double> matrix;
+    mf.setDevice(device);
+    forest = mf.trainInstance(pos, neg, o, saveMatrix ? &matrix : nullptr);
+    for (size_t i = 0; i < all.size(); i++) all[i]->setGenuine(genuineBefore[i]);
+    if (saveMatrix) {
+        std::ofstream fout((output + ".selftrain.matrix.f64").c_str(), std::ios::binary);
+        fout.write((const char*)matrix.data(), (std::streamsize)(matrix.size() * sizeof(double)));
+    }
+    forest.save(output + ".selftrain.forest");
+    cout << "Saved forest to file " << output << ".selftrain.forest" << endl << endl;
+    return true;
+}
+
 void JunctionFilter::filter() {  // :153-596
     size_t slash = output.find_last_of('/');
     string outputDir = slash == string::npos ? string(".") : output.substr(0, slash);
     const string outputPrefix = slash == string::npos ? output : output.substr(slash + 1);
     if (outputDir.empty()) outputDir = "/";
-    if (train)
-        throw JuncFilterException("Self-training a random forest model is not built into portcullis_amd filt.  Pass a saved model with --model_file (the "
-                                  "<prefix>.selftrain.forest file a reference run leaves), or filter with rules only: --no_ml with --filter_file.");
+    if (train && selfTrainDir.empty())
+        throw JuncFilterException("Self-training a random forest model is not the default of portcullis_amd filt.  Ask for it with --self_train <data_dir> (the "
+                                  "directory of the rule sets), pass a saved model with --model_file (the <prefix>.selftrain.forest file a self-training run "
+                                  "leaves), or filter with rules only: --no_ml with --filter_file.");
+    if (train && !isDirectory(selfTrainDir)) throw JuncFilterException("Could not find the self-training data directory at: " + selfTrainDir);
     if (!exists(junctionFile)) throw JuncFilterException("Could not find junction file at: " + junctionFile);
     if (!exists(prepData.getGenomeFilePath())) throw JuncFilterException("Could not find prepared genome file at: " + prepData.getGenomeFilePath());
     if (!modelFile.empty() && !exists(modelFile)) throw JuncFilterException("Could not find filter model file at: " + modelFile);
@@ -145,6 +269,20 @@ void JunctionFilter::filter() {  // :153-596
     }
 
     JunctionSystem discardedJuncs;
+    if (train) {  // :278-456
+        ml::ModelFeatures mf;  // (the genome is opened only if a forest is trained)
+        ml::Forest forest;
+        if (selfTrain(currentJuncs, mf, forest)) {
+            ml::ModelFeatures::checkForest(forest);
+            cout << "Predicting valid junctions using random forest model" << endl << "----------------------------------------------------" << endl << endl;
+            JunctionList passJuncs, failJuncs;
+            forestPredict(currentJuncs, passJuncs, failJuncs, mf, forest);  // the same ModelFeatures: the trained models and L95 score every junction
+            printFilteringResults(currentJuncs, passJuncs, failJuncs, "Random Forest filtering results");
+            currentJuncs = passJuncs;
+            for (auto& j : failJuncs) discardedJuncs.addJunction(j);
+        } else if (!exists(filterFile))
+            throw JuncFilterException("Could not find filter configuration file at: " + filterFile);
+    }
     if (!modelFile.empty()) {  // :441-456
         const ml::Forest forest = ml::Forest::load(modelFile);  // (read and checked before the genome or a device is touched)
         ml::ModelFeatures::checkForest(forest);
@@ -252,8 +390,10 @@ string JunctionFilter::description() {
     return "Filters out junctions that are unlikely to be genuine or that have too little\n"
            "supporting evidence.  A saved random forest model (--model_file) scores every\n"
            "junction on the GPU; rule files (--filter_file), the length, canonical and\n"
-           "coverage filters and a reference annotation apply after it.  Self-training a\n"
-           "model on the input is not built: pass --model_file, or --no_ml with --filter_file.";
+           "coverage filters and a reference annotation apply after it.  --self_train trains\n"
+           "the model on the input itself (layered rule sets choose the initial junctions; the\n"
+           "nearest-neighbour search and the forest run on the GPU); without it pass\n"
+           "--model_file, or --no_ml with --filter_file.";
 }
 
 string JunctionFilter::helpMessage() {
@@ -280,13 +420,26 @@ string JunctionFilter::helpMessage() {
            "  --min_cov arg (=1)                   Only keep junctions with a number of split reads greater than or equal to this number\n"
            "  --threshold arg (=0.5)               The threshold score at which we determine a junction to be genuine or not.\n"
            "  --save_features                      Save the feature rows of all junctions to <output>.features.testing\n\n"
-           "Not built (refused): self-training (neither --model_file nor --no_ml), --training_rule, --no_smote, --enn, --save_layers, -g [ --genuine ]\n";
+           "Self-training options (refused without --self_train):\n"
+           "  --self_train arg                     Train the model on the input: arg is the directory of the rule sets (laid out as the reference's data/:\n"
+           "                                       <ruleset>/selftrain_initial_{pos,neg}.layerN.json and low_juncs_filter.json).  Not with --no_ml or --model_file.\n"
+           "                                       Fewer than 200 junctions: low_juncs_filter.json is applied instead; 200 to 499: refused.\n"
+           "  --training_rule arg (=balanced)      The rule set of the initial sets: a directory, or a name under the --self_train directory (balanced, precise).\n"
+           "  --no_smote                           Disable the balancing of the two sets (synthetic oversampling, or under-sampling)\n"
+           "  --enn                                Enable Edited Nearest Neighbour to clean the decision region\n"
+           "  --save_layers                        Save each layer produced when creating the training set\n"
+           "  --save_matrix                        Save <output>.selftrain.matrix.f64 (the training matrix, rows x 29) and <output>.testing.matrix.f64\n"
+           "                                       (the 29 columns of every junction as scored): little-endian doubles, no header\n\n"
+           "Not built (refused): self-training without --self_train (neither --model_file nor --no_ml), -g [ --genuine ]\n";
 }
 
 int JunctionFilter::main(int argc, char* argv[]) {
     std::vector<string> positional;
     string output = DEFAULT_FILTER_OUTPUT, source = DEFAULT_FILTER_SOURCE, filterFile, referenceFile, modelFile, canonical = "OFF";
+    string selfTrainDir, trainingRule = "balanced";
     bool saveBad = false, exongff = false, introngff = false, noMl = false, saveFeatures = false, verbose = false, help = false;
+    bool noSmote = false, enn = false, saveLayers = false, saveMatrix = false;
+    std::vector<std::pair<string, string>> selfTrainOnly;  // the options that belong to self-training, as given: refused without --self_train
     int threads = DEFAULT_FILTER_THREADS;
     uint32_t maxLength = 0, minCov = 1;
     double threshold = DEFAULT_FILTER_THRESHOLD;
@@ -326,10 +479,23 @@ int JunctionFilter::main(int argc, char* argv[]) {
         else if (a == "--devices") (void)need();
         else if (a == "-v" || a == "--verbose") verbose = true;
         else if (a == "--help") help = true;
-        else if (a == "--training_rule") notBuilt("--training_rule (the rule sets of the self-training's initial layers)", selfTrainOut);
-        else if (a == "--no_smote") notBuilt("--no_smote (synthetic oversampling of the training set)", selfTrainOut);
-        else if (a == "--enn") notBuilt("--enn (Edited Nearest Neighbour cleaning of the training set)", selfTrainOut);
-        else if (a == "--save_layers") notBuilt("--save_layers (the layers of the training set)", selfTrainOut);
+        else if (a == "--self_train") selfTrainDir = need();
+        else if (a == "--training_rule") {
+            trainingRule = need();
+            selfTrainOnly.emplace_back("--training_rule (the rule sets of the self-training's initial layers)", selfTrainOut);
+        } else if (a == "--no_smote") {
+            noSmote = true;
+            selfTrainOnly.emplace_back("--no_smote (synthetic oversampling of the training set)", selfTrainOut);
+        } else if (a == "--enn") {
+            enn = true;
+            selfTrainOnly.emplace_back("--enn (Edited Nearest Neighbour cleaning of the training set)", selfTrainOut);
+        } else if (a == "--save_layers") {
+            saveLayers = true;
+            selfTrainOnly.emplace_back("--save_layers (the layers of the training set)", selfTrainOut);
+        } else if (a == "--save_matrix") {
+            saveMatrix = true;
+            selfTrainOnly.emplace_back("--save_matrix (the training and the testing matrix of self-training)", selfTrainOut);
+        }
         else if (a == "-g" || a == "--genuine")
             notBuilt("--genuine (performance tables against a list of known labels)", "Run without it; the .pass and .fail tables can be compared with the labels afterwards.");
         else if (!a.empty() && a[0] == '-' && a.size() > 1) throw JuncFilterException("Unknown option: " + a);
@@ -339,6 +505,10 @@ int JunctionFilter::main(int argc, char* argv[]) {
         cout << helpMessage() << endl;
         return 1;
     }
+    if (selfTrainDir.empty() && !selfTrainOnly.empty())
+        throw JuncFilterException(selfTrainOnly[0].first + " is not built into portcullis_amd filt without --self_train <data_dir>.  " + selfTrainOnly[0].second);
+    if (!selfTrainDir.empty() && (noMl || !modelFile.empty()))
+        throw JuncFilterException("--self_train trains the model on the input: it cannot be combined with --no_ml or --model_file.");
     const auto t0 = std::chrono::steady_clock::now();
     cout << "Running portcullis in junction filter mode" << endl << "------------------------------------------" << endl << endl;
     JunctionFilter filter(positional[0], positional[1], output);
@@ -357,6 +527,12 @@ int JunctionFilter::main(int argc, char* argv[]) {
         filter.setTrain(false);
         if (!noMl) filter.setModelFile(modelFile);
     }
+    filter.setSelfTrainDir(selfTrainDir);
+    filter.setTrainingRule(trainingRule);
+    filter.setSmote(!noSmote);
+    filter.setENN(enn);
+    filter.setSaveLayers(saveLayers);
+    filter.setSaveMatrix(saveMatrix);
     filter.setSaveFeatures(saveFeatures);
     filter.setReferenceFile(referenceFile);
     filter.setThreshold(threshold);

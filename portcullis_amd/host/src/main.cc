@@ -1,5 +1,5 @@
 // portcullis_amd: command line entry: the `junc` mode, `filt` with a saved model and / or rules, `train` (a model grown from two labelled
-// junction tables), `bamfilt` and `prep` for a BAM that is sorted already; filt's self-training (and prep's sort / merge) remain the reference's programs and interoperate through the prep
+// junction tables), `bamfilt` and `prep` for a BAM that is sorted already; filt's self-training is behind `filt --self_train`; prep's sort / merge remain the reference's programs and interoperate through the prep
 // directory, the .tab file and the saved .forest model.
 #include <dirent.h>
 #include <portcullis/bam_filter.hpp>

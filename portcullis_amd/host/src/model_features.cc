@@ -4,10 +4,14 @@
 #include <algorithm>
 #include <cmath>
 #include <cstring>
+#include <fstream>
+#include <iostream>
 
+#include <portcullis/junction_system.hpp>
 #include <portcullis/seq_utils.hpp>
 
 #include "../../../include/portcullis_amd.h"
+#include "self_train.hpp"
 
 namespace portcullis {
 namespace ml {
@@ -233,6 +237,118 @@ Forest ModelFeatures::growForest(const JunctionList& x, int32_t nTrees, uint32_t
     run.check(pjb_forest_grow(run.ctx, matrix.data(), (int64_t)x.size(), (int32_t)active.size(), &p, &r), "pjb_forest_grow");
     if (featuresOut) featuresOut->swap(rows);
     return Forest::fromView(r.forest, r.class_values);
+}
+
+Forest ModelFeatures::trainInstance(const JunctionList& pos, const JunctionList& neg, const TrainOptions& o, std::vector<double>* matrixOut) {
+    using std::cout;
+    using std::endl;
+    if (pos.empty() || neg.empty()) throw ForestException("trainInstance needs a positive and a negative junction at least");
+    const int N = (int)(pos.size() / neg.size()) - 1;  // the number of times to duplicate the negative set
+    JunctionList neg2 = neg;
+    if (N <= 0 && o.smote) {
+        cout << "Undersampling negative set to balance with positive set" << endl;
+        neg2.clear();
+        for (const size_t i : selftrain::undersample(neg.size(), pos.size())) neg2.push_back(neg[i]);
+    }
+    if (o.verbose) cout << endl << "Combining positive, negative " << (N > 0 ? "and synthetic negative " : "") << "datasets." << endl;
+    JunctionList training;
+    training.reserve(pos.size() + neg2.size());
+    training.insert(training.end(), pos.begin(), pos.end());
+    training.insert(training.end(), neg2.begin(), neg2.end());
+    JunctionSystem trainingSystem(training);
+    trainingSystem.sort();
+    const JunctionList& x = trainingSystem.getJunctions();
+    // the feature rows of the real junctions: the device's (what forestPredict walks), column 0 the genuine flag
+    const size_t F = PJB_N_FEATURES;
+    const std::vector<int32_t>& active = activeFeatures();
+    const size_t C = active.size(), SC = C - 1;
+    std::vector<double> rows(x.size() * F, 0.0);
+    DeviceRun run;
+    openRun(run, *this, gmap, device, x);
+    run.check(pjb_filt_features(run.ctx, run.rows.data(), (int64_t)run.rows.size(), x[0]->getMeanReadLength(), L95, &run.m, rows.data()), "pjb_filt_features");
+    std::vector<double> matrix(x.size() * C);
+    for (size_t i = 0; i < x.size(); i++) {
+        matrix[i * C] = x[i]->isGenuine() ? 1.0 : 0.0;
+        for (size_t k = 1; k < C; k++) matrix[i * C + k] = rows[i * F + (size_t)active[k]];
+    }
+    auto nearest = [&](const std::vector<double>& m, size_t n, int32_t defaultK, std::vector<uint32_t>& nn) {
+        const int32_t k = selftrain::effectiveK(n, defaultK);
+        nn.assign(n * (size_t)k, 0);
+        run.check(pjb_knn(run.ctx, m.data(), (int64_t)n, (int32_t)SC, k, nn.data()), "pjb_knn");
+        return (size_t)k;
+    };
+    if (N > 0 && o.smote) {
+        cout << "Oversampling negative set to balance with positive set using SMOTE" << endl;
+        // the negatives' features in the sorted negative set's order: the negatives of x, which the same comparator sorted
+        std::vector<double> nm;
+        size_t at = 0;
+        for (size_t i = 0; i < x.size(); i++) {
+            if (x[i]->isGenuine()) continue;
+            if (at >= neg.size() || x[i] != neg[at++]) throw ForestException("trainInstance: the negative set is not sorted");
+            nm.insert(nm.end(), matrix.begin() + (std::ptrdiff_t)(i * C + 1), matrix.begin() + (std::ptrdiff_t)((i + 1) * C));
+        }
+        if (at != neg.size()) throw ForestException("trainInstance: a junction is in the positive and in the negative set");
+        std::vector<uint32_t> nn;
+        const size_t k = nearest(nm, neg.size(), 5, nn);
+        const std::vector<double> synthetic = selftrain::smoteSynthesize(nm.data(), neg.size(), SC, nn.data(), k, (uint32_t)N);
+        const size_t nSynth = synthetic.size() / SC;
+        for (size_t i = 0; i < nSynth; i++) {
+            matrix.push_back(0.0);  // not genuine
+            matrix.insert(matrix.end(), synthetic.begin() + (std::ptrdiff_t)(i * SC), synthetic.begin() + (std::ptrdiff_t)((i + 1) * SC));
+        }
+        cout << "Number of synthesized entries: " << nSynth << endl;
+    }
+    if (o.saveFeatures) {  // :402-410: the real rows, default stream formatting
+        const std::string file = o.outputPrefix + ".features";
+        if (o.verbose) cout << "Saving feature vector to disk: " << file << endl;
+        std::ofstream fout(file.c_str());
+        const std::vector<std::string> names = featureNames();
+        fout << Intron::locationOutputHeader();
+        for (const int32_t k : active) fout << "\t" << names[(size_t)k];
+        fout << endl;
+        for (size_t i = 0; i < x.size(); i++) {
+            fout << *(x[i]->getIntron());
+            for (size_t k = 0; k < C; k++) fout << "\t" << matrix[i * C + k];
+            fout << endl;
+        }
+    }
+    if (o.enn) {
+        const size_t n = matrix.size() / C;
+        std::vector<double> m(n * SC);
+        std::vector<char> labels(n);
+        size_t p = 0;
+        for (size_t i = 0; i < n; i++) {
+            labels[i] = matrix[i * C] == 1.0;
+            p += labels[i] != 0;
+            std::copy(matrix.begin() + (std::ptrdiff_t)(i * C + 1), matrix.begin() + (std::ptrdiff_t)((i + 1) * C), m.begin() + (std::ptrdiff_t)(i * SC));
+        }
+        cout << "P: " << p << "; N: " << n - p << "; O: 0" << endl;
+        cout << endl << "Starting Wilson's Edited Nearest Neighbour (ENN) to clean decision region" << endl;
+        std::vector<uint32_t> nn;
+        const size_t k = nearest(m, n, 3, nn);
+        const std::vector<char> keep = selftrain::ennKeep(nn.data(), n, k, labels, 3);
+        std::vector<double> kept;
+        size_t pcount = 0, ncount = 0;
+        for (size_t i = 0; i < n; i++) {
+            if (!keep[i]) continue;
+            kept.insert(kept.end(), matrix.begin() + (std::ptrdiff_t)(i * C), matrix.begin() + (std::ptrdiff_t)((i + 1) * C));
+            (labels[i] ? pcount : ncount)++;
+        }
+        cout << "Marked " << pcount + ncount << " to be kept and " << n - pcount - ncount << " to be discarded." << endl;
+        cout << "Final training set contains " << pcount << " positive entries and " << ncount << " negative entries" << endl;
+        matrix.swap(kept);
+    }
+    if (matrix.empty()) throw ForestException("trainInstance: ENN left no row to train on");
+    if (o.verbose) cout << "Initialising random forest" << endl << "Training" << endl;
+    pjb_grow_params gp;
+    memset(&gp, 0, sizeof gp);
+    gp.n_trees = o.trees;
+    gp.seed = 1236456789u;  // the reference's fixed seed
+    pjb_grow_result r;
+    run.check(pjb_forest_grow(run.ctx, matrix.data(), (int64_t)(matrix.size() / C), (int32_t)C, &gp, &r), "pjb_forest_grow");
+    Forest forest = Forest::fromView(r.forest, r.class_values);
+    if (matrixOut) matrixOut->swap(matrix);
+    return forest;
 }
 
 }  // namespace ml
