@@ -13,11 +13,19 @@ the seeds, and the tests import it from here (importing this module touches neit
   G4  10 and 11 rows, 4 trees each: the node size test is `<=`
   G5  1500 rows, 8 trees: lists of 24 trips of 64 positions, nodes larger and smaller than a trip, nodes across trip borders
 
+and one per case of MORE below, grown by `ranger_witness train` with its nine arguments -- column count, label column, mtry, node
+size and seed as the case names them: levels wider than one and than two waves of nodes (W1, W2), 250 and 17 trees (T250, T17),
+the label in another column (D1, D2), 4 to 130 columns (C4, C33, C65, C130), the smallest and the largest mtry of the simple draw
+(M1, Mmax), node sizes 1 and 3 (N1, N3), the class 0 alone (Z0), a column with both zeros (ZS), seed 7 (S2).  Of these cases.json
+records SHA-256, length and node count of ranger's bytes, and the file is committed only where it is smaller than G5.forest:
+tests/grow_model.py restates ranger's growing and supplies the bytes of the others (tests/test_grow_model.py).
+
 Never run by a test or by build().
 
     python tests/golden/make_forest_grow_fixture.py        (needs /root/reference)
 """
 import glob
+import hashlib
 import json
 import os
 import subprocess
@@ -44,12 +52,57 @@ CASES = [
     dict(name="G4b", kind="matrix", rows=11, trees=4, rng=7104, file="G4b.forest"),
     dict(name="G5", kind="matrix", rows=1500, trees=8, rng=7105, file="G5.forest"),
 ]
+# The cases below call `ranger_witness train` with all nine arguments.  cols, dep (the label's column), mtry, min_node and seed default
+# to 29, 0, 0, 0 (ranger's defaults: floor(sqrt(cols - 1)) and 10) and SEED.  Recorded: SHA-256, length and node count of ranger's bytes;
+# the file itself only where it is smaller than G5.forest (tests/grow_model.py supplies every byte of the others).
+MORE = [
+    dict(name="W1", kind="round1", rows=4000, trees=2, rng=4029),
+    dict(name="W2", kind="round1", rows=2500, cols=6, mtry=2, min_node=1, trees=2, rng=2506),
+    dict(name="T250", kind="round1", rows=64, trees=250, rng=93),
+    dict(name="T17", kind="round1", rows=40, trees=17, rng=69),
+    dict(name="D1", kind="round1", rows=200, cols=12, dep=7, trees=4, rng=212),
+    dict(name="D2", kind="round1", rows=200, cols=12, dep=11, trees=4, rng=213),
+    dict(name="C4", kind="ints", rows=150, cols=4, mtry=1, min_node=1, trees=4, rng=154),
+    dict(name="C33", kind="round1", rows=120, cols=33, trees=4, rng=153),
+    dict(name="C65", kind="round1", rows=120, cols=65, trees=4, rng=185),
+    dict(name="C130", kind="round1", rows=120, cols=130, trees=4, rng=250),
+    dict(name="M1", kind="round1", rows=300, mtry=1, trees=4, rng=329),
+    dict(name="Mmax", kind="round1", rows=300, mtry=13, trees=4, rng=330),
+    dict(name="N1", kind="round1", rows=129, min_node=1, trees=4, rng=158),
+    dict(name="N3", kind="round1", rows=129, min_node=3, trees=4, rng=159),
+    dict(name="Z0", kind="zero_class", rows=30, trees=4, rng=59),
+    dict(name="ZS", kind="signed_zeros", rows=80, cols=5, mtry=1, trees=8, rng=85),
+    dict(name="S2", kind="round1", rows=300, seed=7, trees=4, rng=331),
+]
+LARGEST_FILE = 136793  # G5.forest: no larger forest is committed
+
+
+def case_args(case):
+    """(cols, dep, mtry, min_node, seed) of a case: what `Forest.grow`, the model and `ranger_witness train` are given"""
+    return case.get("cols", N_COLS), case.get("dep", 0), case.get("mtry", 0), case.get("min_node", 0), case.get("seed", SEED)
 
 
 def case_matrix(case):
-    """The case's training matrix, float64 [rows, 29], column 0 the label."""
+    """The case's training matrix, float64 [rows, cols]: 29 columns and the label in column 0 unless the case says otherwise."""
     rng = np.random.RandomState(case["rng"])
     n = case["rows"]
+    cols, dep = case.get("cols", N_COLS), case.get("dep", 0)
+    if case["kind"] in ("round1", "zero_class", "ints"):  # unlearnable labels: the trees grow as deep as the node size lets them
+        # (`+ 0.0`: rounding leaves -0.0 behind, and a column with both zeros is the business of ZS alone)
+        m = rng.randint(0, 4, (n, cols)).astype(np.float64) if case["kind"] == "ints" else rng.normal(size=(n, cols)).round(1) + 0.0
+        m[:, dep] = 0.0 if case["kind"] == "zero_class" else rng.randint(0, 2, n)
+        return m
+    if case["kind"] == "signed_zeros":
+        # column 1: both zeros, in no order, and a few positive values; the label is `column 1 > 0` but for a few rows, so the split
+        # at zero is the best one of column 1 and its left child (zeros only) has both labels
+        m = rng.normal(size=(n, cols)).round(1) + 0.0
+        m[:, 1] = np.where(rng.randint(0, 2, n) == 1, 0.0, -0.0)
+        pos = rng.choice(n, 12, replace=False)
+        m[pos, 1] = rng.randint(1, 4, 12)
+        m[:, dep] = m[:, 1] > 0
+        flip = rng.choice(n, 6, replace=False)
+        m[flip, dep] = 1.0 - m[flip, dep]
+        return m
     if case["kind"] == "ties":
         m = rng.randint(0, 4, (n, N_COLS)).astype(np.float64)
         m[:, 10] = m[:, 9]
@@ -165,6 +218,28 @@ def main():
             rec["crosses"] = (f"{trips} trip(s) of {TRIP} positions a list" + ("; nodes above and below a trip, nodes across trip borders" if trips > 1 else
                                                                             "; every node inside one trip"))
             print(f"{case['name']}: {len(raw)} bytes, {rec['nodes']} nodes, {forest.n_classes} classes; {rec['crosses']}")
+            out_cases.append(rec)
+        for case in MORE:
+            m = case_matrix(case)
+            cols, dep, mtry, min_node, seed = case_args(case)
+            assert m.shape == (case["rows"], cols)
+            m.astype("<f8").tofile(os.path.join(d, "train.f64"))
+            subprocess.check_call([exe, "train", os.path.join(d, "train.f64"), str(case["rows"]), str(case["trees"]), os.path.join(d, case["name"])] +
+                                  [str(v) for v in (cols, dep, mtry, min_node, seed)])
+            raw = open(os.path.join(d, case["name"] + ".forest"), "rb").read()
+            keep = len(raw) < LARGEST_FILE
+            rec = dict(case, file=case["name"] + ".forest" if keep else None, bytes=len(raw), sha256=hashlib.sha256(raw).hexdigest())
+            if keep:
+                open(forest_path(rec), "wb").write(raw)
+            forest = ffi.Forest.from_file(os.path.join(d, case["name"] + ".forest"))
+            assert forest.n_trees == case["trees"] and forest.n_vars == cols and forest.dependent_var == dep and forest.check() is None
+            rec.update(nodes=int(forest.tree_off[-1]), n_classes=forest.n_classes)
+            sizes = np.diff(forest.tree_off)
+            for t in range(case["trees"]):
+                if sizes[t] > 1:
+                    root = forest.split_var[forest.tree_off[t]]
+                    assert root in root_candidates(t, cols, dep, mtry or max(1, int((cols - 1) ** 0.5)), seed), (case["name"], t)
+            print(f"{case['name']}: {len(raw)} bytes, {rec['nodes']} nodes, {forest.n_classes} classes" + ("" if keep else "; the hash only"))
             out_cases.append(rec)
     with open(os.path.join(OUT, "cases.json"), "w") as f:
         json.dump(dict(seed=SEED, n_cols=N_COLS, trip=TRIP, cases=out_cases), f, indent=1)

@@ -49,6 +49,12 @@ KNN_CASES = [
     dict(name="I32", kind="ints", rows=200, cols=32, k=5, rng=8132),
     # several chunks of the base range
     dict(name="C2500", kind="normal", rows=2500, cols=28, k=5, rng=8141, copies=25),
+    # the anchors of tests/knn_model.py beyond k = 5 and the compiled widths: whole lists of 8, a width between 28 and 32, and
+    # small integers in one and in two columns -- far more than 8 base rows at one distance, lying in several chunks of 64
+    dict(name="K8", kind="normal", rows=200, cols=28, k=8, rng=8151, copies=10),
+    dict(name="C31", kind="normal", rows=200, cols=31, k=5, rng=8152),
+    dict(name="T1", kind="ints", rows=300, cols=1, k=8, rng=8153, chunk=64),
+    dict(name="T2", kind="ints", rows=300, cols=2, k=8, rng=8154, chunk=64),
 ]
 SMOTE_CASES = [
     dict(name="S120", kind="normal", rows=120, cols=28, smoteness=2, rng=8201, copies=6),
@@ -243,7 +249,12 @@ def main():
             assert np.array_equal(nn, order), "the reference's lists are not in (distance, index) order"
             ties = int(sum(len(np.unique(r)) < len(r) for r in dist))
             np.save(path(case["name"] + ".nn.npy"), nn)
-            rec["knn"].append(dict(case, k_used=int(nn.shape[1]), rows_with_equal_distances=ties))
+            more = {}
+            if "chunk" in case:  # (stated by the model of tests/knn_model.py, which the tests hold against these very lists)
+                sys.path.insert(0, os.path.join(ROOT, "tests"))
+                import knn_model
+                more["rows_tied_across_chunks"] = knn_model.rows_tied_across_chunks(m, nn.shape[1], case["chunk"])
+            rec["knn"].append(dict(case, k_used=int(nn.shape[1]), rows_with_equal_distances=ties, **more))
             print(f"{case['name']}: {nn.shape}, {ties} rows with equal distances in their list")
         for case in SMOTE_CASES:
             m = case_matrix(case)

@@ -3,6 +3,9 @@
 // (make_forest_fixture.py does it), never by a test or by build().
 //   ranger_witness train <train.f64> <n_rows> <n_trees> <output prefix>      -> <prefix>.forest
 //       as ModelFeatures::trainInstance calls Forest::init (lib/src/model_features.cc:422-440), then saveToFile()
+//   ranger_witness train <train.f64> <n_rows> <n_trees> <output prefix> <n_cols> <label column> <mtry> <min_node_size> <seed>
+//       the same call with the values trainInstance fixes made arguments (mtry and min_node_size 0: ranger's defaults); the name
+//       "Genuine" goes to <label column>, the other columns are called x<number>
 //   ranger_witness predict <forest file> <test.f64> <n_rows> <pred.f64>      -> n_rows x n_classes predictions
 //       as JunctionFilter::forestPredict loads the saved model and runs it (src/junction_filter.cc:660-686)
 // The matrices are raw little-endian doubles, row major, one column per name of the header below: "Genuine" and the 28 other
@@ -28,8 +31,13 @@ static std::vector<std::string> header() {
     return h;
 }
 
-static Data* loadMatrix(const char* path, size_t rows) {
-    const std::vector<std::string> h = header();
+static std::vector<std::string> header(size_t cols, size_t label) {
+    std::vector<std::string> h;
+    for (size_t i = 0; i < cols; i++) h.push_back(i == label ? std::string("Genuine") : "x" + std::to_string(i));
+    return h;
+}
+
+static Data* loadMatrix(const char* path, size_t rows, const std::vector<std::string>& h = header()) {
     std::vector<double> v(rows * h.size());
     FILE* f = fopen(path, "rb");
     if (!f || fread(v.data(), sizeof(double), v.size(), f) != v.size()) {
@@ -46,6 +54,22 @@ static Data* loadMatrix(const char* path, size_t rows) {
 
 int main(int argc, char* argv[]) {
     std::vector<std::string> catVars;
+    if (argc == 11 && strcmp(argv[1], "train") == 0) {
+        const size_t cols = (size_t)atol(argv[6]), label = (size_t)atol(argv[7]);
+        if (cols < 2 || label >= cols || strtoul(argv[10], 0, 10) == 0) {
+            fprintf(stderr, "train: %zu columns, label column %zu, seed %s (seed 0 makes ranger draw one at random)\n", cols, label, argv[10]);
+            return 2;
+        }
+        Data* d = loadMatrix(argv[2], (size_t)atol(argv[3]), header(cols, label));
+        std::shared_ptr<Forest> f = std::make_shared<ForestProbability>();
+        f->init("Genuine", MEM_DOUBLE, d, (uint)atoi(argv[8]), argv[5], (uint)atoi(argv[4]), (uint)strtoul(argv[10], 0, 10), 1, IMP_GINI, (uint)atoi(argv[9]), "",
+                false, false, catVars, false, AUC, false, 1.0);
+        f->setVerboseOut(&std::cerr);
+        f->run(false);
+        f->saveToFile();
+        delete d;
+        return 0;
+    }
     if (argc == 6 && strcmp(argv[1], "train") == 0) {
         Data* d = loadMatrix(argv[2], (size_t)atol(argv[3]));
         std::shared_ptr<Forest> f = std::make_shared<ForestProbability>();
@@ -72,6 +96,6 @@ int main(int argc, char* argv[]) {
         delete d;
         return 0;
     }
-    fprintf(stderr, "usage: ranger_witness train <train.f64> <rows> <trees> <prefix> | predict <forest> <test.f64> <rows> <pred.f64>\n");
+    fprintf(stderr, "usage: ranger_witness train <train.f64> <rows> <trees> <prefix> [<cols> <label column> <mtry> <min_node_size> <seed>] | predict <forest> <test.f64> <rows> <pred.f64>\n");
     return 1;
 }

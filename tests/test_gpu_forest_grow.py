@@ -1,6 +1,11 @@
 """A forest grown on the device (pjb_forest_grow, kernels kt_* of pjb_grow.hip.h) against the files ranger 0.3.8 saved for the same
 matrices (tests/golden/forest_grow and filt_forest/witness.forest, made by tests/golden/make_forest_grow_fixture.py with the reference's
-library).  The matrices are made again from the seeds in cases.json.  Every comparison is bit for bit."""
+library).  The matrices are made again from the seeds in cases.json.  Every comparison is bit for bit.
+
+Seventeen more cases (W1 .. S2 of cases.json) and a seeded sweep are compared with tests/grow_model.py, the plain restatement of
+ranger's growing that tests/test_grow_model.py pins to ranger without a device -- the model supplies every byte and the place of the
+first difference -- and the cases with SHA-256 and length of the bytes ranger itself saved."""
+import hashlib
 import os
 import sys
 
@@ -8,13 +13,16 @@ import numpy as np
 import pytest
 
 import forest_util as fu
+import grow_model as gm
 
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden"))
 import make_forest_grow_fixture as fx  # noqa: E402  (the generator of the matrices; it touches nothing on import)
 
 pytestmark = pytest.mark.gpu
 
-CASES = {c["name"]: c for c in fx.load_cases()}
+ALL = {c["name"]: c for c in fx.load_cases()}
+CASES = {n: c for n, c in ALL.items() if "sha256" not in c}  # G1 .. G5: ranger's files
+MORE = {n: c for n, c in ALL.items() if "sha256" in c}       # W1 .. S2: the model's bytes and ranger's hash
 ARRAYS = ("tree_off", "left", "right", "split_var", "count_off")
 
 
@@ -75,9 +83,31 @@ def assert_same_forest(got, ref, raw=None):
         assert got.to_bytes() == raw
 
 
+@pytest.fixture(scope="module")
+def model():
+    """name -> (matrix, the model's forest, its bytes) of the cases W1 .. S2; made once, never changed"""
+    out = {}
+    for name, case in MORE.items():
+        cols, dep, mtry, min_node, seed = fx.case_args(case)
+        m = fx.case_matrix(case)
+        m.setflags(write=False)
+        forest = gm.grow(m, case["trees"], seed, mtry, min_node, dep)[0]
+        out[name] = (m, forest, forest.to_bytes())
+    return out
+
+
+def grow_case(ffi, ctx, case, m):
+    cols, dep, mtry, min_node, seed = fx.case_args(case)
+    return ffi.Forest.grow(ctx, m, n_trees=case["trees"], seed=seed, mtry=mtry, min_node_size=min_node, dependent_col=dep)
+
+
 def test_cases_cover_the_issue():
     assert set(CASES) == {"G1", "G2", "G3", "G4a", "G4b", "G5"}
     assert CASES["G1"]["file"].endswith("filt_forest/witness.forest") and CASES["G5"]["rows"] > 20 * fx.TRIP
+    # (what each of these reaches is asserted from the model's facts, without a device: tests/test_grow_model.py)
+    assert set(MORE) == {"W1", "W2", "T250", "T17", "D1", "D2", "C4", "C33", "C65", "C130", "M1", "Mmax", "N1", "N3", "Z0", "ZS", "S2"}
+    assert (MORE["W1"]["rows"], MORE["W2"]["rows"], MORE["T250"]["trees"], MORE["T17"]["trees"]) == (4000, 2500, 250, 17)
+    assert all(len(c["sha256"]) == 64 and c["bytes"] > 0 for c in MORE.values())
 
 
 @pytest.mark.parametrize("name", sorted(CASES))
@@ -87,6 +117,53 @@ def test_grown_forest_is_rangers_file(ffi, ctx, want, name):
     assert_same_forest(got, ref, raw)
     if name == "G3":
         assert got.n_classes == 1 and got.class_values == [1.0] and list(np.diff(got.tree_off)) == [1] * 4 and list(got.counts) == [1.0] * 4
+
+
+@pytest.mark.parametrize("name", sorted(MORE))
+def test_grown_forest_is_the_models_and_has_rangers_hash(ffi, ctx, model, name):
+    """levels of two and three waves of nodes, 250 and 17 trees, the label in other columns, 4 to 130 columns, both ends of mtry,
+    node sizes 1 and 3, the class 0 alone, a column with both zeros, another seed"""
+    m, ref, raw = model[name]
+    got = grow_case(ffi, ctx, MORE[name], m)
+    assert_same_forest(got, ref, raw)
+    if name != "ZS":
+        assert (len(raw), hashlib.sha256(got.to_bytes()).hexdigest()) == (MORE[name]["bytes"], MORE[name]["sha256"])
+    if name == "Z0":
+        assert got.n_classes == 1 and got.class_values == [0.0] and list(np.diff(got.tree_off)) == [1] * 4 and list(got.counts) == [1.0] * 4
+
+
+def test_signed_zeros(ffi, model):
+    """ZS: where a column holds -0.0 and +0.0, ranger saves the zero its std::sort left first, the device the zero of the last row
+    of the left child.  Equal but for that sign, and the same predictions bit for bit."""
+    m, _, raw = model["ZS"]
+    ranger = ffi.Forest.from_file(fx.forest_path(MORE["ZS"]))
+    with ffi.Context(0) as c:
+        got = grow_case(ffi, c, MORE["ZS"], m)
+        assert got.to_bytes() == raw
+        assert_same_forest(gm.clear_zero_signs(got), gm.clear_zero_signs(ranger), gm.clear_zero_signs(ranger).to_bytes())
+        c.forest_load(got)
+        mine = c.forest_predict(m)
+        c.forest_load(ranger)
+        assert np.array_equal(bits(mine), bits(c.forest_predict(m)))
+    assert len(np.unique(bits(mine))) > 2
+
+
+def test_250_trees_in_batches_of_48(ffi, model):
+    """five full batches and one of 10 trees: a tree depends on its number only"""
+    m, ref, raw = model["T250"]
+    with ffi.Context(0, flags=ffi.FLAG_NO_CHAINS) as c:
+        c.set_option("grow_batch", 48)
+        got = grow_case(ffi, c, MORE["T250"], m)
+    assert_same_forest(got, ref, raw)
+    assert hashlib.sha256(got.to_bytes()).hexdigest() == MORE["T250"]["sha256"]
+
+
+@pytest.mark.parametrize("shape", gm.sweep_shapes(), ids=gm.sweep_id)
+def test_sweep_against_the_model(ffi, ctx, shape):
+    m = gm.sweep_matrix(shape)
+    ref = gm.grow(m, shape["trees"], fx.SEED, 0, shape["min_node"], shape["dep"])[0]
+    got = ffi.Forest.grow(ctx, m, n_trees=shape["trees"], min_node_size=shape["min_node"], dependent_col=shape["dep"])
+    assert_same_forest(got, ref, ref.to_bytes())
 
 
 def test_g1_end_to_end(ffi, want):
