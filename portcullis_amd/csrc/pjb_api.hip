@@ -1,5 +1,5 @@
 // pjb_api.hip -- C ABI (include/portcullis_amd.h) over the HIP kernels: contexts, genomes, batches, the kernel chains, rows.
-// One context = one HIP device + its streams + grow-only scratch.  (--extra / bamfilt / filt: pjb_extra_api.hip; BGZF and BAM: pjb_ingest_api.hip.)
+// One context = one HIP device + its streams + grow-only scratch.  (--extra / bamfilt: pjb_extra_api.hip; filt / train: pjb_model_api.hip; BGZF and BAM: pjb_ingest_api.hip.)
 #include "pjb_host.hip.h"
 #include "pjb_kernels.hip.h"
 
@@ -231,12 +231,12 @@ void pjb_destroy(pjb_ctx *c) {
         if (c->stage_ev[k]) (void)hipEventDestroy(c->stage_ev[k]);
     }
     Buf *all[] = {&c->b_cursor, &c->b_scan_tiles, &c->b_hasx, &c->b_xtotal, &c->b_fasta_raw, &c->b_inf_comp, &c->b_inf_out, &c->b_inf_blocks, &c->b_inf_status, &c->b_inf_scratch, &c->b_inf_bitmap,
-                  &c->b_bam_seg, &c->b_bam_rec, &c->b_bam_ctl, &c->f_pos, &c->f_cigoff, &c->f_cigar, &c->f_codes, &c->g_rows, &c->g_models, &c->g_refs,
-                  &c->g_out, &c->g_bad, &c->r_nodes, &c->r_leaf, &c->r_roots, &c->r_data, &c->r_pred, &c->r_colmap, &c->w_pool, &c->w_pack, &c->n_data, &c->n_part_d, &c->n_part_i, &c->n_out,
+                  &c->b_bam_seg, &c->b_bam_rec, &c->b_bam_ctl, &c->f_pos, &c->f_cigoff, &c->f_cigar, &c->f_codes,
                   &c->x_pos, &c->x_endx, &c->x_q, &c->x_prefq, &c->x_ce, &c->x_bound, &c->x_de, &c->x_dropped, &c->x_zlist, &c->x_cnt,
                   &c->x_tabk, &c->x_tabc, &c->x_rs, &c->x_re, &c->x_rr, &c->x_tileoff, &c->x_xrall, &c->x_tab,
                   &c->b_dfl_in, &c->b_dfl_sym, &c->b_dfl_slots, &c->b_dfl_size, &c->b_dfl_off, &c->b_dfl_packed};
     for (Buf *b : all) release(*b);
+    c->model.release_all();
     for (auto &ch : c->xarena.chunks) (void)hipFree(ch.p);
     if (c->xrows_pinned) (void)hipHostFree(c->xrows_pinned);
     for (auto &pool : c->pools)
@@ -589,6 +589,11 @@ static size_t rows_upper_bound(const pjb_ctx *c) {
 }
 
 constexpr unsigned K6_BLOCKS = 128;
+// The device work of one contig, queued in one go.  The host does not learn a single count while the kernels run:
+// buffers and grids are sized from LIMITS (pair_limit, junc_limit, the key format kf), the kernels read the actual
+// counts from the control block in device memory (ContigStats) and stand still when a limit is exceeded.  Nothing
+// here waits for the device: the last kernels (rows stream) write rows and control block into page-locked host memory
+// and pjb_finish_contig_end waits for their event -- by which time the next contig may be queued behind this one.
 static int queue_contig(pjb_ctx *c, Flight &f) {
     std::vector<DevBatch> &batches = f.batches;
     CtlSlot &S = c->sl[f.slot];
@@ -1837,10 +1842,10 @@ int pjb_set_option(pjb_ctx *c, const char *name, int64_t value) {
         c->run_window = (u32)value;
     } else if (n == "grow_batch") {
         if (value < 0 || value > 32768) return fail(c, PJB_ERR_ARG, "set_option: grow_batch takes 0 (the default: what the pool holds) to 32768 trees");
-        c->grow_batch = (u32)value;
+        c->model.grow_batch = (u32)value;
     } else if (n == "knn_chunk") {
         if (value < 0 || value > (1 << 22)) return fail(c, PJB_ERR_ARG, "set_option: knn_chunk takes 0 (the default: sized to fill the chip) to %d base rows", 1 << 22);
-        c->knn_chunk = (u32)value;
+        c->model.knn_chunk = (u32)value;
     } else if (n == "list_cap") c->list_cap_forced = (u32)std::max<int64_t>(0, std::min<int64_t>(value, 1 << 30));
     else return fail(c, PJB_ERR_ARG, "set_option: unknown option '%s'", name);
     return PJB_OK;

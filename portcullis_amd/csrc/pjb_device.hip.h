@@ -1,7 +1,7 @@
 // pjb_device.hip.h -- what more than one translation unit needs on the device side: the types the units share (batches, control block,
 // pairs, groups, key format), the wave / block primitives, the generic multi-block scan (pjb_host.hip.h launches it for every unit) and the
 // constants that two units size buffers from.  The kernels themselves are in the headers of their family: pjb_kernels.hip.h (the junc chain),
-// pjb_extra.hip.h, pjb_ingest.hip.h / pjb_deflate.hip.h.
+// pjb_extra.hip.h, pjb_features.hip.h / pjb_forest.hip.h / pjb_grow.hip.h / pjb_knn.hip.h (filt and train), pjb_ingest.hip.h / pjb_deflate.hip.h.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -630,7 +630,7 @@ __device__ __forceinline__ void x_counters(SparseCounters *cnt, const XLane &a) 
     if (a.leaves) atomicOr(&cnt->need_dense, 8u);
 }
 
-// what k5_finalize and kg_features (pjb_extra.hip.h) both do to a target's bases
+// what k5_finalize and kg_features (pjb_features.hip.h) both do to a target's bases
 __device__ __forceinline__ uint8_t revcomp_char(uint8_t c) { // REVCOMP_LOOKUP seq_utils.hpp:33-40 (NUL outside A-Z)
     switch (c) {
     case 'A': return 'T';

@@ -1,12 +1,7 @@
 // pjb_extra_api.hip -- the part of the C ABI behind `junc --extra` (depth, flanking counts, name multiplicities: pjb_extra_finish), `bamfilt`
-// (pjb_filter_*), `filt`'s feature rows and forest (pjb_filt_features, pjb_forest_*, pjb_filt_scores) and `train`'s growing of one
-// (pjb_forest_grow) and self-training's nearest neighbours (pjb_knn); kernels in pjb_extra.hip.h, pjb_forest.hip.h, pjb_grow.hip.h
-// and pjb_knn.hip.h.
+// (pjb_filter_*); kernels in pjb_extra.hip.h.
 #include "pjb_host.hip.h"
 #include "pjb_extra.hip.h"
-#include "pjb_forest.hip.h"
-#include "pjb_grow.hip.h"
-#include "pjb_knn.hip.h"
 
 // The name codes of a chain's spliced records, in BAM order, to `codes`; their number to cnt->n_spliced.  Through the tile lists the
 // chain's first kernels left in its slot (tile numbers run through the chain).
@@ -342,64 +337,6 @@ int extra_contig(pjb_ctx *c, Flight &f, const pjb_region_result *res, u64 n_spli
     return PJB_OK;
 }
 
-// The device work of one contig, queued in one go.  The host does not learn a single count while the kernels run:
-// buffers and grids are sized from LIMITS (pair_limit, junc_limit, the key format kf), the kernels read the actual
-// counts from the control block in device memory (ContigStats) and stand still when a limit is exceeded.  Nothing
-// here waits for the device: the last kernels (rows stream) write rows and control block into page-locked host memory
-// and pjb_finish_contig_end waits for their event -- by which time the next contig may be queued behind this one.
-// `filt`: uploads the junctions and the models and queues kg_features on the context's stream; the rows are in c->g_out, the "a genome is
-// missing" flag in c->g_bad.  Nothing waits here (rows and models are pageable: the caller's wait comes before it returns).
-static int features_queue(pjb_ctx *c, const pjb_junction_row *rows, size_t n, double mean_read_length, uint32_t l95, const pjb_markov_models *models) {
-    hipStream_t st = c->stream;
-    int rc;
-    if ((rc = ensure(c, c->g_rows, n * sizeof(pjb_junction_row)))) return rc;
-    if ((rc = ensure(c, c->g_models, ((size_t)6 * PJB_KMER_TABLE + 2 * PJB_PW_LEN * 5) * sizeof(double)))) return rc;
-    if ((rc = ensure(c, c->g_refs, std::max<size_t>(c->contigs.size(), 1) * sizeof(GenomeRef)))) return rc;
-    if ((rc = ensure(c, c->g_out, n * PJB_N_FEATURES * sizeof(double)))) return rc;
-    if ((rc = ensure(c, c->g_bad, sizeof(int)))) return rc;
-    HIP_TRY(c, hipMemcpyAsync(c->g_rows.p, rows, n * sizeof(pjb_junction_row), hipMemcpyHostToDevice, st));
-    DevModels M;
-    memset(&M, 0, sizeof M);
-    double *dm = (double *)c->g_models.p;
-    const double *src[8] = {models->exon, models->intron, models->donor_t, models->donor_f, models->acceptor_t, models->acceptor_f,
-                            models->donor_pw, models->acceptor_pw};
-    const double **dst[8] = {&M.exon, &M.intron, &M.don_t, &M.don_f, &M.acc_t, &M.acc_f, &M.don_pw, &M.acc_pw};
-    size_t at = 0;
-    for (int k = 0; k < 8; k++) {
-        const size_t cnt = k < 6 ? (size_t)PJB_KMER_TABLE : (size_t)PJB_PW_LEN * 5;
-        if (src[k]) {
-            HIP_TRY(c, hipMemcpyAsync(dm + at, src[k], cnt * sizeof(double), hipMemcpyHostToDevice, st));
-            *dst[k] = dm + at;
-        }
-        at += cnt;
-    }
-    M.exon_size = models->exon ? models->exon_size : 0;
-    M.intron_size = models->intron ? models->intron_size : 0;
-    M.don_pw_size = models->donor_pw ? models->donor_pw_size : 0;
-    M.acc_pw_size = models->acceptor_pw ? models->acceptor_pw_size : 0;
-    std::vector<GenomeRef> refs(std::max<size_t>(c->contigs.size(), 1));
-    for (size_t t = 0; t < c->contigs.size(); t++) {
-        refs[t].d = c->contigs[t].present ? c->contigs[t].d : nullptr;
-        refs[t].len = (int32_t)c->contigs[t].len;
-    }
-    HIP_TRY(c, hipMemcpyAsync(c->g_refs.p, refs.data(), refs.size() * sizeof(GenomeRef), hipMemcpyHostToDevice, st));
-    HIP_TRY(c, hipMemsetAsync(c->g_bad.p, 0, sizeof(int), st));
-    LAUNCH(c, "kg_features", kg_features, dim3((unsigned)((n + 255) / 256)), dim3(256), (const pjb_junction_row *)c->g_rows.p, (u32)n,
-           (const GenomeRef *)c->g_refs.p, (int)c->contigs.size(), M, mean_read_length, (u32)l95, (double *)c->g_out.p, (int *)c->g_bad.p);
-    return PJB_OK;
-}
-
-// queues the walk of the context's forest over n rows of `data` (device; `stride` doubles a row); predictions to c->r_pred
-static int forest_queue(pjb_ctx *c, const double *data, size_t n, u32 stride, const int32_t *colmap) {
-    int rc;
-    if ((rc = ensure(c, c->r_pred, n * (size_t)c->r_classes * sizeof(double)))) return rc;
-    const size_t lds = (size_t)FOREST_BLOCK * (size_t)c->r_classes * sizeof(double) + (size_t)c->r_vars * sizeof(int32_t);
-    LAUNCH_LDS(c, "kr_forest", kr_forest, dim3((unsigned)((n + FOREST_BLOCK - 1) / FOREST_BLOCK)), dim3(FOREST_BLOCK), lds, (const ForestNode *)c->r_nodes.p,
-               (const u32 *)c->r_roots.p, (u32)c->r_trees, (u32)c->r_classes, (u32)c->r_vars, (const double *)c->r_leaf.p, data, (u32)n, stride, colmap,
-               (double *)c->r_pred.p);
-    return PJB_OK;
-}
-
 extern "C" {
 int pjb_extra_finish(pjb_ctx *c, const pjb_extra_row **rows_out, int64_t *n_out) {
     if (!c || !rows_out || !n_out) return PJB_ERR_ARG;
@@ -533,415 +470,6 @@ int pjb_filter_batch(pjb_ctx *c, int32_t tid, const pjb_batch *b, int32_t clip_m
            (const u32 *)c->f_cigar.p, (u32)n, keys, n_keys, (int)clip_mode, (uint8_t *)c->f_codes.p);
     HIP_TRY(c, hipMemcpyAsync(codes_out, c->f_codes.p, n, hipMemcpyDeviceToHost, st));
     HIP_TRY(c, hipStreamSynchronize(st));
-    if (c->ktime) ev_collect(c, MISC_POOL);
-    return PJB_OK;
-}
-
-int pjb_filt_features(pjb_ctx *c, const pjb_junction_row *rows, int64_t n_rows, double mean_read_length, uint32_t l95,
-                      const pjb_markov_models *models, double *features_out) {
-    if (!c) return PJB_ERR_ARG;
-    if (n_rows < 0 || (n_rows > 0 && (!rows || !features_out)) || !models || n_rows > 0xfffffff0ll)
-        return fail(c, PJB_ERR_ARG, "pjb_filt_features: bad arguments");
-    if (n_rows == 0) return PJB_OK;
-    HIP_TRY(c, hipSetDevice(c->cfg.device));
-    hipStream_t st = c->stream;
-    const size_t n = (size_t)n_rows;
-    int rc;
-    if ((rc = features_queue(c, rows, n, mean_read_length, l95, models))) return rc;
-    int bad = 0;
-    HIP_TRY(c, hipMemcpyAsync(features_out, c->g_out.p, n * PJB_N_FEATURES * sizeof(double), hipMemcpyDeviceToHost, st));
-    HIP_TRY(c, hipMemcpyAsync(&bad, c->g_bad.p, sizeof(int), hipMemcpyDeviceToHost, st));
-    HIP_TRY(c, hipStreamSynchronize(st));
-    if (c->ktime) ev_collect(c, MISC_POOL);
-    if (bad) return fail(c, PJB_ERR_STATE, "pjb_filt_features: a junction lies on a target whose genome was not uploaded");
-    return PJB_OK;
-}
-
-int pjb_forest_check(const pjb_forest *f, char *msg, int len) {
-    auto no = [&](const char *fmt, long long a, long long b) {
-        if (msg && len > 0) snprintf(msg, (size_t)len, fmt, a, b);
-        return PJB_ERR_ARG;
-    };
-    if (!f) return no("pjb_forest_check: no forest", 0, 0);
-    if (f->n_trees < 1) return no("forest: %lld trees (at least one is needed)", f->n_trees, 0);
-    if (f->n_classes < 1 || f->n_classes > PJB_FOREST_MAX_CLASSES) return no("forest: %lld classes (1 to %lld can be walked)", f->n_classes, PJB_FOREST_MAX_CLASSES);
-    if (f->n_vars < 1 || f->n_vars > PJB_FOREST_MAX_VARS) return no("forest: %lld variables (1 to %lld can be walked)", f->n_vars, PJB_FOREST_MAX_VARS);
-    if (f->dependent_var < 0 || f->dependent_var >= f->n_vars) return no("forest: dependent variable %lld of %lld variables", f->dependent_var, f->n_vars);
-    if (!f->tree_off || !f->left || !f->right || !f->split_var || !f->split_value || !f->count_off || (!f->counts && f->n_counts > 0) || f->n_counts < 0)
-        return no("forest: an array is missing", 0, 0);
-    if (f->is_ordered)
-        for (int32_t v = 0; v < f->n_vars; v++)
-            if (!f->is_ordered[v]) return no("forest: variable %lld is unordered (only ordered variables can be walked)", v, 0);
-    if (f->tree_off[0] != 0) return no("forest: the first tree starts at node %lld", (long long)f->tree_off[0], 0);
-    if (f->tree_off[f->n_trees] > 0x7ffffff0ll) return no("forest: %lld nodes", (long long)f->tree_off[f->n_trees], 0);
-    std::vector<uint8_t> has_parent;
-    for (int32_t t = 0; t < f->n_trees; t++) {
-        const int64_t base = f->tree_off[t], n = f->tree_off[t + 1] - base;
-        if (n < 1 || n > 0x7ffffff0ll) return no("forest: tree %lld has %lld nodes", t, (long long)n);
-        has_parent.assign((size_t)n, 0);
-        for (int64_t k = 0; k < n; k++) {
-            const int64_t l = f->left[base + k], r = f->right[base + k];
-            if (l < 0 && r < 0) { // terminal
-                const int64_t at = f->count_off[base + k];
-                if (at < 0 || at > f->n_counts - f->n_classes) return no("forest: tree %lld, node %lld: a terminal node without its class counts", t, (long long)k);
-                continue;
-            }
-            if (l < 0 || r < 0) return no("forest: tree %lld, node %lld has one child only", t, (long long)k);
-            if (l >= n || r >= n) return no("forest: tree %lld, node %lld: a child lies outside the tree", t, (long long)k);
-            if (l <= k || r <= k) return no("forest: tree %lld, node %lld: a child is not behind its parent", t, (long long)k);
-            if (l == r || has_parent[(size_t)l] || has_parent[(size_t)r]) return no("forest: tree %lld, node %lld: a child has two parents", t, (long long)k);
-            has_parent[(size_t)l] = has_parent[(size_t)r] = 1;
-            const int32_t v = f->split_var[base + k];
-            if (v < 0 || v >= f->n_vars) return no("forest: tree %lld, node %lld splits on a variable the data does not have", t, (long long)k);
-            if (v == f->dependent_var) return no("forest: tree %lld, node %lld splits on the dependent variable", t, (long long)k);
-        }
-    }
-    return PJB_OK;
-}
-
-int pjb_forest_load(pjb_ctx *c, const pjb_forest *f) {
-    if (!c) return PJB_ERR_ARG;
-    char msg[200] = "";
-    if (pjb_forest_check(f, msg, (int)sizeof msg) != PJB_OK) return fail(c, PJB_ERR_ARG, "pjb_forest_load: %s", msg);
-    // pack: each tree breadth first from its root, so that the two children of a node are neighbours (nodes nothing leads to are dropped)
-    std::vector<ForestNode> nodes;
-    std::vector<double> leaf;
-    std::vector<u32> roots((size_t)f->n_trees);
-    std::vector<int64_t> order;
-    nodes.reserve((size_t)f->tree_off[f->n_trees]);
-    for (int32_t t = 0; t < f->n_trees; t++) {
-        const int64_t base = f->tree_off[t];
-        const size_t first = nodes.size();
-        roots[(size_t)t] = (u32)first;
-        order.assign(1, 0);
-        for (size_t at = 0; at < order.size(); at++) {
-            const int64_t k = base + order[at];
-            ForestNode nd;
-            if (f->left[k] < 0) {
-                nd.split = 0.0;
-                nd.child = (u32)(leaf.size() / (size_t)f->n_classes);
-                nd.var = FOREST_LEAF;
-                for (int32_t cl = 0; cl < f->n_classes; cl++) leaf.push_back(f->counts[f->count_off[k] + cl] / (double)f->n_trees);
-            } else {
-                nd.split = f->split_value[k];
-                nd.child = (u32)(first + order.size());
-                nd.var = (u32)f->split_var[k];
-                order.push_back(f->left[k]);
-                order.push_back(f->right[k]);
-            }
-            nodes.push_back(nd);
-        }
-    }
-    HIP_TRY(c, hipSetDevice(c->cfg.device));
-    hipStream_t st = c->stream;
-    HIP_TRY(c, hipStreamSynchronize(st)); // (the arrays below are pageable, and a walk of the old forest may be queued)
-    c->r_trees = 0;
-    int rc;
-    if ((rc = ensure(c, c->r_nodes, nodes.size() * sizeof(ForestNode)))) return rc;
-    if ((rc = ensure(c, c->r_leaf, leaf.size() * sizeof(double)))) return rc;
-    if ((rc = ensure(c, c->r_roots, roots.size() * sizeof(u32)))) return rc;
-    HIP_TRY(c, hipMemcpyAsync(c->r_nodes.p, nodes.data(), nodes.size() * sizeof(ForestNode), hipMemcpyHostToDevice, st));
-    HIP_TRY(c, hipMemcpyAsync(c->r_leaf.p, leaf.data(), leaf.size() * sizeof(double), hipMemcpyHostToDevice, st));
-    HIP_TRY(c, hipMemcpyAsync(c->r_roots.p, roots.data(), roots.size() * sizeof(u32), hipMemcpyHostToDevice, st));
-    HIP_TRY(c, hipStreamSynchronize(st));
-    c->r_trees = f->n_trees;
-    c->r_classes = f->n_classes;
-    c->r_vars = f->n_vars;
-    c->r_dep = f->dependent_var;
-    return PJB_OK;
-}
-
-int pjb_forest_predict(pjb_ctx *c, const double *data, int64_t n_rows, int32_t n_cols, double *pred) {
-    if (!c) return PJB_ERR_ARG;
-    if (!c->r_trees) return fail(c, PJB_ERR_STATE, "pjb_forest_predict: no forest was loaded (pjb_forest_load)");
-    if (n_rows < 0 || n_rows > 0xfffffff0ll || (n_rows > 0 && (!data || !pred))) return fail(c, PJB_ERR_ARG, "pjb_forest_predict: bad arguments");
-    if (n_cols != c->r_vars) return fail(c, PJB_ERR_ARG, "pjb_forest_predict: the data has %d columns, the forest %d variables", n_cols, c->r_vars);
-    if (n_rows == 0) return PJB_OK;
-    HIP_TRY(c, hipSetDevice(c->cfg.device));
-    hipStream_t st = c->stream;
-    const size_t n = (size_t)n_rows;
-    int rc;
-    if ((rc = ensure(c, c->r_data, n * (size_t)n_cols * sizeof(double)))) return rc;
-    HIP_TRY(c, hipMemcpyAsync(c->r_data.p, data, n * (size_t)n_cols * sizeof(double), hipMemcpyHostToDevice, st));
-    if ((rc = forest_queue(c, (const double *)c->r_data.p, n, (u32)n_cols, nullptr))) return rc;
-    HIP_TRY(c, hipMemcpyAsync(pred, c->r_pred.p, n * (size_t)c->r_classes * sizeof(double), hipMemcpyDeviceToHost, st));
-    HIP_TRY(c, hipStreamSynchronize(st));
-    if (c->ktime) ev_collect(c, MISC_POOL);
-    return PJB_OK;
-}
-
-int pjb_filt_scores(pjb_ctx *c, const pjb_junction_row *rows, int64_t n_rows, double mean_read_length, uint32_t l95,
-                    const pjb_markov_models *models, const int32_t *var_feature, double *pred, double *features_out) {
-    if (!c) return PJB_ERR_ARG;
-    if (!c->r_trees) return fail(c, PJB_ERR_STATE, "pjb_filt_scores: no forest was loaded (pjb_forest_load)");
-    if (n_rows < 0 || (n_rows > 0 && (!rows || !pred)) || !models || !var_feature || n_rows > 0xfffffff0ll)
-        return fail(c, PJB_ERR_ARG, "pjb_filt_scores: bad arguments");
-    std::vector<int32_t> colmap((size_t)c->r_vars, 0);
-    for (int32_t v = 0; v < c->r_vars; v++) {
-        if (v == c->r_dep) continue; // (never read)
-        if (var_feature[v] < 0 || var_feature[v] >= PJB_N_FEATURES)
-            return fail(c, PJB_ERR_ARG, "pjb_filt_scores: variable %d is column %d of a feature row of %d", v, var_feature[v], PJB_N_FEATURES);
-        colmap[(size_t)v] = var_feature[v];
-    }
-    if (n_rows == 0) return PJB_OK;
-    HIP_TRY(c, hipSetDevice(c->cfg.device));
-    hipStream_t st = c->stream;
-    const size_t n = (size_t)n_rows;
-    int rc;
-    if ((rc = ensure(c, c->r_colmap, colmap.size() * sizeof(int32_t)))) return rc;
-    HIP_TRY(c, hipMemcpyAsync(c->r_colmap.p, colmap.data(), colmap.size() * sizeof(int32_t), hipMemcpyHostToDevice, st));
-    if ((rc = features_queue(c, rows, n, mean_read_length, l95, models))) return rc;
-    if ((rc = forest_queue(c, (const double *)c->g_out.p, n, (u32)PJB_N_FEATURES, (const int32_t *)c->r_colmap.p))) return rc;
-    int bad = 0;
-    HIP_TRY(c, hipMemcpyAsync(pred, c->r_pred.p, n * (size_t)c->r_classes * sizeof(double), hipMemcpyDeviceToHost, st));
-    if (features_out) HIP_TRY(c, hipMemcpyAsync(features_out, c->g_out.p, n * PJB_N_FEATURES * sizeof(double), hipMemcpyDeviceToHost, st));
-    HIP_TRY(c, hipMemcpyAsync(&bad, c->g_bad.p, sizeof(int), hipMemcpyDeviceToHost, st));
-    HIP_TRY(c, hipStreamSynchronize(st)); // (the one wait; colmap is pageable and lives until here)
-    if (c->ktime) ev_collect(c, MISC_POOL);
-    if (bad) return fail(c, PJB_ERR_STATE, "pjb_filt_scores: a junction lies on a target whose genome was not uploaded");
-    return PJB_OK;
-}
-
-// Device memory one batch of trees may take (lists, nodes, candidates, scores); more trees than fit are grown batch after batch.
-static constexpr size_t GROW_POOL_BYTES = (size_t)6 << 30;
-
-// Forest::grow for ForestProbability as ModelFeatures::trainInstance sets it up: see include/portcullis_amd.h and pjb_grow.hip.h.
-int pjb_forest_grow(pjb_ctx *c, const double *data, int64_t n_rows, int32_t n_cols, const pjb_grow_params *p, pjb_grow_result *out) {
-    if (!c) return PJB_ERR_ARG;
-    if (!p || !out) return fail(c, PJB_ERR_ARG, "pjb_forest_grow: bad arguments");
-    if (p->n_trees < 1) return fail(c, PJB_ERR_ARG, "pjb_forest_grow: %d trees (at least one is needed)", p->n_trees);
-    if (n_rows < 1) return fail(c, PJB_ERR_ARG, "pjb_forest_grow: %lld rows (at least one is needed)", (long long)n_rows);
-    if (n_cols < 2) return fail(c, PJB_ERR_ARG, "pjb_forest_grow: %d columns (the labels and one variable at least)", n_cols);
-    if (n_cols > PJB_FOREST_MAX_VARS) return fail(c, PJB_ERR_ARG, "pjb_forest_grow: %d variables (1 to %d can be walked)", n_cols, PJB_FOREST_MAX_VARS);
-    if (!data || n_rows > (1ll << 28) || p->n_trees > (1 << 24)) return fail(c, PJB_ERR_ARG, "pjb_forest_grow: bad arguments");
-    if (p->dependent_col < 0 || p->dependent_col >= n_cols)
-        return fail(c, PJB_ERR_ARG, "pjb_forest_grow: dependent column %d of %d columns", p->dependent_col, n_cols);
-    if (p->mtry < 0 || p->min_node_size < 0) return fail(c, PJB_ERR_ARG, "pjb_forest_grow: mtry %d, node size %d", p->mtry, p->min_node_size);
-    // ForestProbability::initInternal (ForestProbability.cpp:64-75)
-    const u32 mtry = p->mtry ? (u32)p->mtry : std::max<u32>(1, (u32)sqrt((double)(n_cols - 1)));
-    const u32 min_node = p->min_node_size ? (u32)p->min_node_size : 10u;
-    if (mtry >= (u32)n_cols / 2)
-        return fail(c, PJB_ERR_ARG, "pjb_forest_grow: mtry %u of %d columns: from n_cols / 2 on ranger draws by Knuth's algorithm, which is not built", mtry, n_cols);
-    const size_t n = (size_t)n_rows, C = (size_t)n_cols, dep = (size_t)p->dependent_col;
-    std::vector<double> colmajor(C * n);
-    std::vector<uint8_t> label(n);
-    u32 label_sum = 0;
-    for (size_t r = 0; r < n; r++)
-        for (size_t k = 0; k < C; k++) {
-            const double v = data[r * C + k];
-            if (!std::isfinite(v)) return fail(c, PJB_ERR_ARG, "pjb_forest_grow: row %zu, column %zu is not finite", r, k);
-            if (k == dep) {
-                if (v != 0.0 && v != 1.0) return fail(c, PJB_ERR_ARG, "pjb_forest_grow: row %zu has the label %g (0 or 1)", r, v);
-                label[r] = v == 1.0;
-                label_sum += label[r];
-            }
-            colmajor[k * n + r] = v;
-        }
-    // one sort per column, shared by all trees (Data::sort's order of values; rows of one value in row order)
-    std::vector<u32> sorted(C * n);
-    for (size_t k = 0; k < C; k++) {
-        u32 *s = sorted.data() + k * n;
-        for (size_t r = 0; r < n; r++) s[r] = (u32)r;
-        if (k == dep) continue;
-        const double *v = colmajor.data() + k * n;
-        std::stable_sort(s, s + n, [v](u32 a, u32 b) { return v[a] < v[b]; });
-    }
-    // the room of one batch of T trees
-    const size_t M = 2 * n;
-    auto up = [](size_t b) { return (b + 255) & ~(size_t)255; };
-    const size_t shared_bytes = up(C * n * 8) + up(n) + up(C * n * 4) + 256;
-    const size_t tree_bytes = 2 * C * n * 4 + n * 4 + M * (5 * 4 + 8) + M * mtry * (2 + sizeof(GrowBest)) + (GROW_MT_N + 1) * 8 + 2 * 4;
-    size_t batch = c->grow_batch ? c->grow_batch : std::max<size_t>(1, GROW_POOL_BYTES / tree_bytes);
-    batch = std::min<size_t>(std::min<size_t>(batch, (size_t)p->n_trees), 32768);
-    HIP_TRY(c, hipSetDevice(c->cfg.device));
-    hipStream_t st = c->stream;
-    int rc;
-    if ((rc = ensure(c, c->w_pool, shared_bytes + batch * tree_bytes + 16 * 256))) return rc;
-    uint8_t *at = (uint8_t *)c->w_pool.p;
-    auto carve = [&](size_t bytes) {
-        uint8_t *q = at;
-        at += up(bytes);
-        return q;
-    };
-    double *d_col = (double *)carve(C * n * 8);
-    uint8_t *d_label = carve(n);
-    u32 *d_sorted = (u32 *)carve(C * n * 4);
-    u32 *d_new = (u32 *)carve(4);
-    u32 *d_lists[2] = {(u32 *)carve(batch * C * n * 4), (u32 *)carve(batch * C * n * 4)};
-    u32 *d_node_of = (u32 *)carve(batch * n * 4);
-    GrowNodes nd;
-    nd.start = (u32 *)carve(batch * M * 4);
-    nd.count = (u32 *)carve(batch * M * 4);
-    nd.sum = (u32 *)carve(batch * M * 4);
-    nd.child = (u32 *)carve(batch * M * 4);
-    nd.var = (u32 *)carve(batch * M * 4);
-    nd.val = (double *)carve(batch * M * 8);
-    uint16_t *d_cand = (uint16_t *)carve(batch * M * mtry * 2);
-    GrowBest *d_best = (GrowBest *)carve(batch * M * mtry * sizeof(GrowBest));
-    u64 *d_state = (u64 *)carve(batch * (GROW_MT_N + 1) * 8);
-    u32 *d_lvl = (u32 *)carve(batch * 2 * 4);
-    HIP_TRY(c, hipMemcpyAsync(d_col, colmajor.data(), C * n * 8, hipMemcpyHostToDevice, st));
-    HIP_TRY(c, hipMemcpyAsync(d_label, label.data(), n, hipMemcpyHostToDevice, st));
-    HIP_TRY(c, hipMemcpyAsync(d_sorted, sorted.data(), C * n * 4, hipMemcpyHostToDevice, st));
-
-    pjb_ctx::GrowOut &G = c->grow_out;
-    G = pjb_ctx::GrowOut();
-    G.is_ordered.assign(C, 1);
-    if (label_sum < n) G.class_values.push_back(0.0);
-    if (label_sum > 0) G.class_values.push_back(1.0);
-    const size_t K = G.class_values.size();
-    G.tree_off.push_back(0);
-    std::vector<u32> lvl, h_child, h_var, h_count, h_sum;
-    std::vector<double> h_val;
-    std::vector<u64> off;
-    for (size_t t0 = 0; t0 < (size_t)p->n_trees; t0 += batch) {
-        const u32 T = (u32)std::min<size_t>(batch, (size_t)p->n_trees - t0);
-        LAUNCH(c, "kt_seed", kt_seed, dim3((T + 63) / 64), dim3(64), d_state, T, (u32)t0, (u32)p->seed, nd, (u32)M, d_lvl, (u32)n, label_sum);
-        const u64 total = (u64)T * C * n;
-        LAUNCH(c, "kt_fill", kt_fill, dim3((unsigned)((total + 255) / 256)), dim3(256), (const u32 *)d_sorted, d_lists[0], (u64)(C * n), total);
-        HIP_TRY(c, hipMemsetAsync(d_node_of, 0, (size_t)T * n * 4, st));
-        int cur = 0;
-        // one trip per level: at most n_rows levels (every split leaves both children smaller); the one read-back says whether nodes were made
-        for (size_t level = 0; level <= n; level++) {
-            u32 n_new = 0;
-            HIP_TRY(c, hipMemsetAsync(d_new, 0, 4, st));
-            LAUNCH(c, "kt_draw", kt_draw, dim3((T + GROW_DRAW_TREES - 1) / GROW_DRAW_TREES), dim3(GROW_DRAW_TREES), d_state, T, (const u32 *)d_lvl, (u32)C, (u32)dep,
-                   mtry, d_cand, (u32)M);
-            LAUNCH(c, "kt_split", kt_split, dim3((unsigned)C, T), dim3(64), (const u32 *)d_lists[cur], (const u32 *)d_node_of, (const double *)d_col,
-                   (const uint8_t *)d_label, (const u32 *)d_lvl, T, nd, (const uint16_t *)d_cand, d_best, (u32)n, (u32)C, (u32)dep, mtry, (u32)M);
-            LAUNCH(c, "kt_decide", kt_decide, dim3(T), dim3(64), (const u32 *)d_lists[cur], (const double *)d_col, d_lvl, T, nd, (const uint16_t *)d_cand,
-                   (const GrowBest *)d_best, (u32)n, (u32)C, mtry, (u32)M, min_node, d_new);
-            HIP_TRY(c, hipMemcpyAsync(&n_new, d_new, 4, hipMemcpyDeviceToHost, st));
-            HIP_TRY(c, hipStreamSynchronize(st));
-            if (c->ktime) ev_collect(c, MISC_POOL);
-            if (!n_new) break;
-            LAUNCH(c, "kt_partition", kt_partition, dim3((unsigned)C, T), dim3(64), (const u32 *)d_lists[cur], d_lists[cur ^ 1], (const u32 *)d_node_of,
-                   (const double *)d_col, (const u32 *)d_lvl, T, nd, (u32)n, (u32)C, (u32)dep, (u32)M);
-            LAUNCH(c, "kt_assign", kt_assign, dim3((unsigned)((n + 255) / 256), T), dim3(256), d_node_of, (const double *)d_col, nd, (u32)n, (u32)M);
-            cur ^= 1;
-        }
-        // the trees' nodes, packed one tree after the other
-        lvl.resize((size_t)2 * T);
-        HIP_TRY(c, hipMemcpyAsync(lvl.data(), d_lvl, (size_t)2 * T * 4, hipMemcpyDeviceToHost, st));
-        HIP_TRY(c, hipStreamSynchronize(st));
-        off.assign((size_t)T + 1, 0);
-        u32 most = 0;
-        for (u32 t = 0; t < T; t++) {
-            const u32 nodes = lvl[(size_t)T + t]; // (the end of the last level: the tree's node count)
-            if (lvl[t] != nodes || nodes < 1 || nodes >= M) return fail(c, PJB_ERR_STATE, "pjb_forest_grow: tree %zu did not finish (%u nodes)", t0 + t, nodes);
-            off[t + 1] = off[t] + nodes;
-            most = std::max(most, nodes);
-        }
-        const size_t N = (size_t)off[T];
-        if ((rc = ensure(c, c->w_pack, up((T + 1) * 8) + 4 * up(N * 4) + up(N * 8)))) return rc;
-        uint8_t *q = (uint8_t *)c->w_pack.p;
-        u64 *d_off = (u64 *)q;
-        q += up((T + 1) * 8);
-        u32 *p_child = (u32 *)q, *p_var = (u32 *)(q + up(N * 4)), *p_count = (u32 *)(q + 2 * up(N * 4)), *p_sum = (u32 *)(q + 3 * up(N * 4));
-        double *p_val = (double *)(q + 4 * up(N * 4));
-        HIP_TRY(c, hipMemcpyAsync(d_off, off.data(), (T + 1) * 8, hipMemcpyHostToDevice, st));
-        LAUNCH(c, "kt_pack", kt_pack, dim3((most + 255) / 256, T), dim3(256), nd, (u32)M, (const u64 *)d_off, p_child, p_var, p_val, p_count, p_sum);
-        h_child.resize(N), h_var.resize(N), h_count.resize(N), h_sum.resize(N), h_val.resize(N);
-        HIP_TRY(c, hipMemcpyAsync(h_child.data(), p_child, N * 4, hipMemcpyDeviceToHost, st));
-        HIP_TRY(c, hipMemcpyAsync(h_var.data(), p_var, N * 4, hipMemcpyDeviceToHost, st));
-        HIP_TRY(c, hipMemcpyAsync(h_count.data(), p_count, N * 4, hipMemcpyDeviceToHost, st));
-        HIP_TRY(c, hipMemcpyAsync(h_sum.data(), p_sum, N * 4, hipMemcpyDeviceToHost, st));
-        HIP_TRY(c, hipMemcpyAsync(h_val.data(), p_val, N * 8, hipMemcpyDeviceToHost, st));
-        HIP_TRY(c, hipStreamSynchronize(st));
-        if (c->ktime) ev_collect(c, MISC_POOL);
-        for (u32 t = 0; t < T; t++) {
-            for (u64 k = off[t]; k < off[t + 1]; k++) {
-                if (h_child[k]) {
-                    G.left.push_back((int32_t)h_child[k]);
-                    G.right.push_back((int32_t)h_child[k] + 1);
-                    G.count_off.push_back(-1);
-                } else { // addToTerminalNodes: count[class] / n, one division each
-                    G.left.push_back(-1);
-                    G.right.push_back(-1);
-                    G.count_off.push_back((int64_t)G.counts.size());
-                    const double cnt = (double)h_count[k], ones = (double)h_sum[k];
-                    if (K == 2) G.counts.push_back((cnt - ones) / cnt);
-                    G.counts.push_back((K == 2 || label_sum > 0 ? ones : cnt) / cnt);
-                }
-                G.split_var.push_back((int32_t)h_var[k]);
-                G.split_value.push_back(h_val[k]);
-            }
-            G.tree_off.push_back((int64_t)G.left.size());
-        }
-    }
-    pjb_forest &f = out->forest;
-    memset(&f, 0, sizeof f);
-    f.n_trees = p->n_trees;
-    f.n_classes = (int32_t)K;
-    f.n_vars = n_cols;
-    f.dependent_var = p->dependent_col;
-    f.is_ordered = G.is_ordered.data();
-    f.tree_off = G.tree_off.data();
-    f.left = G.left.data();
-    f.right = G.right.data();
-    f.split_var = G.split_var.data();
-    f.split_value = G.split_value.data();
-    f.count_off = G.count_off.data();
-    f.counts = G.counts.data();
-    f.n_counts = (int64_t)G.counts.size();
-    out->class_values = G.class_values.data();
-    char msg[200] = "";
-    if (pjb_forest_check(&f, msg, (int)sizeof msg) != PJB_OK) return fail(c, PJB_ERR_STATE, "pjb_forest_grow: the grown forest cannot be walked: %s", msg);
-    return PJB_OK;
-}
-
-// Waves the default chunking of pjb_knn aims at: 256 CUs x 4 SIMDs x 4 waves, so that scalar-load latency has other waves to hide behind.
-static constexpr size_t KNN_WAVES = 4096;
-// A chunk shorter than this spends its time filling the lists (every one of the first rows of a chunk is an insertion).
-static constexpr size_t KNN_MIN_CHUNK = 256;
-// |value| <= this: 32 squared differences cannot overflow (32 * (2e153)^2 = 1.28e308), so every distance is finite and ordered.
-static constexpr double KNN_MAX_ABS = 1e153;
-static_assert(KN_LIST == PJB_KNN_MAX_K, "the lists of pjb_knn.hip.h hold PJB_KNN_MAX_K entries");
-
-// KNN::execute (lib/src/knn.cc): see include/portcullis_amd.h and pjb_knn.hip.h.
-int pjb_knn(pjb_ctx *c, const double *data, int64_t n_rows, int32_t n_cols, int32_t k, uint32_t *nn_out) {
-    if (!c) return PJB_ERR_ARG;
-    if (!data || !nn_out) return fail(c, PJB_ERR_ARG, "pjb_knn: bad arguments");
-    if (n_cols < 1 || n_cols > PJB_KNN_MAX_COLS) return fail(c, PJB_ERR_ARG, "pjb_knn: %d columns (1 to %d)", n_cols, PJB_KNN_MAX_COLS);
-    if (n_rows < 1 || n_rows > (1ll << 22)) return fail(c, PJB_ERR_ARG, "pjb_knn: %lld rows (1 to %d)", (long long)n_rows, 1 << 22);
-    if (k < 1 || k > PJB_KNN_MAX_K || k > n_rows)
-        return fail(c, PJB_ERR_ARG, "pjb_knn: k = %d (1 to %d, and no more than the %lld rows)", k, PJB_KNN_MAX_K, (long long)n_rows);
-    const size_t n = (size_t)n_rows, C = (size_t)n_cols;
-    const size_t NC = n_cols <= 28 ? 28 : 32; // the compiled widths: the 28 features of self-training, and the limit
-    std::vector<double> padded(n * NC, 0.0);
-    for (size_t r = 0; r < n; r++)
-        for (size_t j = 0; j < C; j++) {
-            const double v = data[r * C + j];
-            if (!(fabs(v) <= KNN_MAX_ABS)) // (a NaN too)
-                return fail(c, PJB_ERR_ARG, "pjb_knn: row %zu, column %zu is %g: not finite, or so large that a distance could overflow", r, j, v);
-            padded[r * NC + j] = v;
-        }
-    size_t chunk = c->knn_chunk;
-    if (!chunk) {
-        const size_t row_waves = (n + 63) / 64;
-        const size_t want = (KNN_WAVES + row_waves - 1) / row_waves;
-        chunk = std::max(KNN_MIN_CHUNK, (n + want - 1) / want);
-    }
-    chunk = std::min(chunk, n);
-    const size_t n_chunks = (n + chunk - 1) / chunk;
-    if (n_chunks > 65535) return fail(c, PJB_ERR_ARG, "pjb_knn: knn_chunk %zu makes %zu chunks of %zu rows (65535 at most)", chunk, n_chunks, n);
-    HIP_TRY(c, hipSetDevice(c->cfg.device));
-    hipStream_t st = c->stream;
-    int rc;
-    if ((rc = ensure(c, c->n_data, n * NC * sizeof(double)))) return rc;
-    if ((rc = ensure(c, c->n_part_d, n_chunks * KN_LIST * n * sizeof(double)))) return rc;
-    if ((rc = ensure(c, c->n_part_i, n_chunks * KN_LIST * n * sizeof(u32)))) return rc;
-    if ((rc = ensure(c, c->n_out, n * (size_t)k * sizeof(u32)))) return rc;
-    HIP_TRY(c, hipMemcpyAsync(c->n_data.p, padded.data(), n * NC * sizeof(double), hipMemcpyHostToDevice, st));
-    const dim3 grid((unsigned)((n + 63) / 64), (unsigned)n_chunks);
-    if (NC == 28)
-        LAUNCH(c, "kn_partial", kn_partial<28>, grid, dim3(64), (const double *)c->n_data.p, (u32)n, (u32)chunk, (double *)c->n_part_d.p, (u32 *)c->n_part_i.p);
-    else
-        LAUNCH(c, "kn_partial", kn_partial<32>, grid, dim3(64), (const double *)c->n_data.p, (u32)n, (u32)chunk, (double *)c->n_part_d.p, (u32 *)c->n_part_i.p);
-    LAUNCH(c, "kn_merge", kn_merge, dim3((unsigned)((n + 255) / 256)), dim3(256), (const double *)c->n_part_d.p, (const u32 *)c->n_part_i.p, (u32)n,
-           (u32)n_chunks, (u32)k, (u32 *)c->n_out.p);
-    HIP_TRY(c, hipMemcpyAsync(nn_out, c->n_out.p, n * (size_t)k * sizeof(u32), hipMemcpyDeviceToHost, st));
-    HIP_TRY(c, hipStreamSynchronize(st)); // (the one wait; `padded` is pageable and lives until here)
     if (c->ktime) ev_collect(c, MISC_POOL);
     return PJB_OK;
 }

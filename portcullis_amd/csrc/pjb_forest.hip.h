@@ -1,5 +1,5 @@
 // pjb_forest.hip.h -- `filt`'s forest stage: a saved ranger probability forest walked on the device (kr_forest), behind
-// pjb_forest_load / pjb_forest_predict / pjb_filt_scores (pjb_extra_api.hip).
+// pjb_forest_load / pjb_forest_predict / pjb_filt_scores (pjb_model_api.hip).
 //   Semantics: Tree::predict (deps/ranger-0.3.8/src/Tree.cpp:125-180) and ForestProbability::predictInternal
 // (src/ForestProbability.cpp:111-131): from the root, value <= split value goes left, anything else -- a NaN too -- goes right; the
 // terminal node's counts[c] / n_trees are added class by class, tree after tree in file order.

@@ -1,5 +1,5 @@
 // pjb_grow.hip.h -- `train`'s forest stage: a ranger 0.3.8 probability forest grown on the device, behind pjb_forest_grow
-// (pjb_extra_api.hip).  The saved forest is byte for byte the one Forest::saveToFile leaves when ModelFeatures::trainInstance
+// (pjb_model_api.hip).  The saved forest is byte for byte the one Forest::saveToFile leaves when ModelFeatures::trainInstance
 // calls it (no replacement, sample fraction 1: every tree trains on every row).
 //   Semantics: Tree::grow (deps/ranger-0.3.8/src/Tree.cpp:88-123), Tree::splitNode / createPossibleSplitVarSubset (Tree.cpp:232-300),
 // drawWithoutReplacementSimple (src/utility.cpp:108-131), TreeProbability::splitNodeInternal / findBestSplit* / addToTerminalNodes

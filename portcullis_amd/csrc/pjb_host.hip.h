@@ -1,7 +1,8 @@
 // pjb_host.hip.h -- what the translation units of the C ABI share: the context (pjb_ctx) and its parts, error / allocation / launch helpers.
-// The library is built from three units -- pjb_api.hip (contexts, uploads, batches, the kernel chains: pjb_kernels.hip.h), pjb_extra_api.hip
-// (--extra, bamfilt, filt features: pjb_extra.hip.h) and pjb_ingest_api.hip (BGZF inflate / deflate, BAM records: pjb_ingest.hip.h, pjb_deflate.hip.h) --
-// each of which includes its own kernel family behind this header and so is the only unit that compiles it; this header includes only what the
+// The library is built from four units -- pjb_api.hip (contexts, uploads, batches, the kernel chains: pjb_kernels.hip.h), pjb_extra_api.hip
+// (--extra, bamfilt: pjb_extra.hip.h), pjb_model_api.hip (filt and train -- feature rows, the forest walk, forest growing, KNN:
+// pjb_features.hip.h, pjb_forest.hip.h, pjb_grow.hip.h, pjb_knn.hip.h) and pjb_ingest_api.hip (BGZF inflate / deflate, BAM records:
+// pjb_ingest.hip.h, pjb_deflate.hip.h) -- each of which includes its own kernel family behind this header and so is the only unit that compiles it; this header includes only what the
 // units share (pjb_device.hip.h, pjb_extra_types.hip.h).  (The Makefile makes every header a prerequisite of every unit: an edit to any of them
 // rebuilds the library.)  Helpers are inline functions of this header: one definition, one set of thread-local error strings for all units.
 #pragma once
@@ -221,6 +222,34 @@ struct Flight {
     u32 x_gap_cap = 0;
 };
 
+inline void release(Buf &b) {
+    if (b.p) (void)hipFree(b.p);
+    b.p = nullptr;
+    b.cap = 0;
+}
+
+// what a context keeps for `filt` and `train` (pjb_model_api.hip); a device buffer added here is added to release_all() below it
+struct ModelState {
+    Buf g_rows, g_models, g_refs, g_out, g_bad; // filt feature rows
+    Buf r_nodes, r_leaf, r_roots, r_data, r_pred, r_colmap; // filt forest (pjb_forest.hip.h): packed nodes, leaf rows, tree roots; matrix, predictions, columns
+    int32_t r_trees = 0, r_classes = 0, r_vars = 0, r_dep = 0; // r_trees == 0: no forest loaded
+    Buf w_pool, w_pack;      // pjb_forest_grow (pjb_grow.hip.h): the matrix, the trees' lists and nodes of one batch; the packed nodes
+    u32 grow_batch = 0;      // pjb_set_option("grow_batch", n): trees grown side by side (tests; 0: as many as GROW_POOL_BYTES holds)
+    Buf n_data, n_part_d, n_part_i, n_out; // pjb_knn (pjb_knn.hip.h): the padded matrix, the chunks' lists (distances, indices), the neighbours
+    u32 knn_chunk = 0;       // pjb_set_option("knn_chunk", n): base rows per chunk (tests; 0: sized so that the grid fills the chip)
+    struct GrowOut {         // the forest of the last pjb_forest_grow: what pjb_grow_result points to
+        std::vector<uint8_t> is_ordered;
+        std::vector<int64_t> tree_off, count_off;
+        std::vector<int32_t> left, right, split_var;
+        std::vector<double> split_value, counts, class_values;
+    } grow_out;
+    void release_all() { // (pjb_destroy)
+        for (Buf *b : {&g_rows, &g_models, &g_refs, &g_out, &g_bad, &r_nodes, &r_leaf, &r_roots, &r_data, &r_pred, &r_colmap, &w_pool, &w_pack,
+                       &n_data, &n_part_d, &n_part_i, &n_out})
+            release(*b);
+    }
+};
+
 constexpr size_t PJB_UP_EVENTS = 64;
 struct pjb_ctx {
     pjb_config cfg;
@@ -321,19 +350,7 @@ struct pjb_ctx {
     std::vector<ExtraContig> xc;
     std::map<int32_t, std::pair<u64 *, u32>> filter_keys; // bamfilt: passing junctions per target (device, sorted)
     Buf f_pos, f_cigoff, f_cigar, f_codes;
-    Buf g_rows, g_models, g_refs, g_out, g_bad; // filt feature rows
-    Buf r_nodes, r_leaf, r_roots, r_data, r_pred, r_colmap; // filt forest (pjb_forest.hip.h): packed nodes, leaf rows, tree roots; matrix, predictions, columns
-    int32_t r_trees = 0, r_classes = 0, r_vars = 0, r_dep = 0; // r_trees == 0: no forest loaded
-    Buf w_pool, w_pack;      // pjb_forest_grow (pjb_grow.hip.h): the matrix, the trees' lists and nodes of one batch; the packed nodes
-    u32 grow_batch = 0;      // pjb_set_option("grow_batch", n): trees grown side by side (tests; 0: as many as GROW_POOL_BYTES holds)
-    Buf n_data, n_part_d, n_part_i, n_out; // pjb_knn (pjb_knn.hip.h): the padded matrix, the chunks' lists (distances, indices), the neighbours
-    u32 knn_chunk = 0;       // pjb_set_option("knn_chunk", n): base rows per chunk (tests; 0: sized so that the grid fills the chip)
-    struct GrowOut {         // the forest of the last pjb_forest_grow: what pjb_grow_result points to
-        std::vector<uint8_t> is_ordered;
-        std::vector<int64_t> tree_off, count_off;
-        std::vector<int32_t> left, right, split_var;
-        std::vector<double> split_value, counts, class_values;
-    } grow_out;
+    ModelState model; // filt / train (pjb_model_api.hip)
     Buf x_pos, x_endx, x_q, x_prefq, x_ce, x_bound, x_de, x_dropped, x_zlist, x_cnt, x_tabk, x_tabc, x_rs, x_re, x_rr, x_tileoff;
     Buf x_xrall, x_tab; // x_tab: the name table (NameSlot), x_tab_slots slots, holding the codes of x_tab_n spliced records
     size_t x_tab_slots = 0, x_tab_n = 0;
@@ -427,12 +444,6 @@ inline int ensure(pjb_ctx *c, Buf &b, size_t bytes) {
         (void)hipDeviceSynchronize();
     }
     return PJB_OK;
-}
-
-inline void release(Buf &b) {
-    if (b.p) (void)hipFree(b.p);
-    b.p = nullptr;
-    b.cap = 0;
 }
 
 inline const char *err_text(int code) {

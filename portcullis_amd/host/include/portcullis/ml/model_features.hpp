@@ -49,6 +49,9 @@ public:
     std::vector<double> juncs2FeatureVectors(const JunctionList& x);
     // the columns of that matrix the reference's filter leaves active, in order: the variables of its forests (29, "Genuine" first)
     static const std::vector<int32_t>& activeFeatures();
+    // the features table (lib/src/model_features.cc:402-410): a header line, then per junction of x its intron and the active columns of
+    // its row of `rows` (full width: [x.size()][featureNames().size()]), default stream formatting
+    static void saveFeatures(const std::string& file, const JunctionList& x, const std::vector<double>& rows);
     // ForestProbability::predictInternal over the rows of x: row-major [x.size()][forest.classValues.size()], feature rows and walk on
     // the device in one call (pjb_filt_scores).  featuresOut (optional): the full matrix as juncs2FeatureVectors lays it out, with the
     // device's own columns 0 and 8.  Throws ForestException for a forest that cannot be walked or has other variables.

@@ -1,8 +1,6 @@
 // JunctionFilter: see portcullis/junction_filter.hpp.  Line numbers refer to src/junction_filter.cc of the reference.
 #include <portcullis/junction_filter.hpp>
 
-#include <sys/stat.h>
-
 #include <algorithm>
 #include <chrono>
 #include <cstdio>
@@ -13,6 +11,7 @@
 #include <unordered_set>
 
 #include "../../../include/portcullis_amd.h"
+#include "fs_util.hpp"
 #include "rule_filter.hpp"
 #include "self_train.hpp"
 
@@ -23,24 +22,6 @@ using std::string;
 namespace portcullis {
 
 namespace {
-bool exists(const string& p) {
-    struct stat st;
-    return stat(p.c_str(), &st) == 0;
-}
-bool isDirectory(const string& p) {
-    struct stat st;
-    return stat(p.c_str(), &st) == 0 && S_ISDIR(st.st_mode);
-}
-bool createDirectories(const string& p) {
-    string cur;
-    for (size_t i = 0; i <= p.size(); i++) {
-        if (i == p.size() || p[i] == '/') {
-            if (!cur.empty() && !exists(cur) && mkdir(cur.c_str(), 0777) != 0 && !exists(cur)) return false;
-        }
-        if (i < p.size()) cur.push_back(p[i]);
-    }
-    return isDirectory(p);
-}
 std::vector<string> splitOn(const string& s, char sep, bool compress) {
     std::vector<string> parts(1);
     for (const char c : s) {

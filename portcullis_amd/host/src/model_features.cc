@@ -167,18 +167,49 @@ static void openRun(DeviceRun& run, ModelFeatures& mf, bam::GenomeMapper* gmap, 
     m.acceptor_pw_size = (int32_t)mf.acceptorPWModel.size();
 }
 
+// The feature rows of x (not empty), full width: the device's (pjb_filt_features: what forestPredict walks), column 0 the junctions'
+// isGenuine().  `run` is opened here and stays the caller's: trainInstance goes on with its context.
+static std::vector<double> featureRows(DeviceRun& run, ModelFeatures& mf, bam::GenomeMapper* gmap, int device, const JunctionList& x) {
+    const size_t F = PJB_N_FEATURES;
+    std::vector<double> rows(x.size() * F, 0.0);
+    openRun(run, mf, gmap, device, x);
+    run.check(pjb_filt_features(run.ctx, run.rows.data(), (int64_t)run.rows.size(), x[0]->getMeanReadLength(), mf.L95, &run.m, rows.data()), "pjb_filt_features");
+    for (size_t i = 0; i < x.size(); i++) rows[i * F] = x[i]->isGenuine() ? 1.0 : 0.0;
+    return rows;
+}
+
+// full-width rows -> the columns of activeFeatures(), in their order
+static std::vector<double> projectActive(const std::vector<double>& rows) {
+    const size_t F = PJB_N_FEATURES, n = rows.size() / F;
+    const std::vector<int32_t>& active = ModelFeatures::activeFeatures();
+    std::vector<double> matrix(n * active.size());
+    for (size_t i = 0; i < n; i++)
+        for (size_t k = 0; k < active.size(); k++) matrix[i * active.size() + k] = rows[i * F + (size_t)active[k]];
+    return matrix;
+}
+
 std::vector<double> ModelFeatures::juncs2FeatureVectors(const JunctionList& x) {  // :214-230 with setRow :161-212
     if (!gmap) throw JunctionException("ModelFeatures: initGenomeMapper was not called");
-    std::vector<double> out(x.size() * PJB_N_FEATURES, 0.0);
-    if (x.empty()) return out;
+    if (x.empty()) return std::vector<double>();
     DeviceRun run;
-    openRun(run, *this, gmap, device, x);
-    run.check(pjb_filt_features(run.ctx, run.rows.data(), (int64_t)run.rows.size(), x[0]->getMeanReadLength(), L95, &run.m, out.data()), "pjb_filt_features");
-    for (size_t i = 0; i < x.size(); i++) {
-        out[i * PJB_N_FEATURES + 0] = x[i]->isGenuine() ? 1.0 : 0.0;
+    std::vector<double> out = featureRows(run, *this, gmap, device, x);
+    for (size_t i = 0; i < x.size(); i++)
         out[i * PJB_N_FEATURES + 8] = x[i]->getMeanMismatches();  // the junction's own value (a row parsed from a .tab has no integer sum)
-    }
     return out;
+}
+
+void ModelFeatures::saveFeatures(const std::string& file, const JunctionList& x, const std::vector<double>& rows) {
+    std::ofstream fout(file.c_str());
+    const std::vector<std::string> names = featureNames();
+    const std::vector<int32_t>& active = activeFeatures();
+    fout << Intron::locationOutputHeader();
+    for (const int32_t k : active) fout << "\t" << names[(size_t)k];
+    fout << std::endl;
+    for (size_t i = 0; i < x.size(); i++) {
+        fout << *(x[i]->getIntron());
+        for (const int32_t k : active) fout << "\t" << rows[i * names.size() + (size_t)k];
+        fout << std::endl;
+    }
 }
 
 const std::vector<int32_t>& ModelFeatures::activeFeatures() {  // src/junction_filter.cc:246-258 of the reference
@@ -219,22 +250,15 @@ std::vector<double> ModelFeatures::forestPredict(const JunctionList& x, const Fo
 
 Forest ModelFeatures::growForest(const JunctionList& x, int32_t nTrees, uint32_t seed, std::vector<double>* featuresOut) {
     if (x.empty()) throw ForestException("No junctions to grow a forest on");
-    const size_t F = PJB_N_FEATURES;
-    std::vector<double> rows(x.size() * F, 0.0);
     DeviceRun run;
-    openRun(run, *this, gmap, device, x);
-    run.check(pjb_filt_features(run.ctx, run.rows.data(), (int64_t)run.rows.size(), x[0]->getMeanReadLength(), L95, &run.m, rows.data()), "pjb_filt_features");
-    for (size_t i = 0; i < x.size(); i++) rows[i * F] = x[i]->isGenuine() ? 1.0 : 0.0;
-    const std::vector<int32_t>& active = activeFeatures();
-    std::vector<double> matrix(x.size() * active.size());
-    for (size_t i = 0; i < x.size(); i++)
-        for (size_t k = 0; k < active.size(); k++) matrix[i * active.size() + k] = rows[i * F + (size_t)active[k]];
+    std::vector<double> rows = featureRows(run, *this, gmap, device, x);
+    const std::vector<double> matrix = projectActive(rows);
     pjb_grow_params p;
     memset(&p, 0, sizeof p);
     p.n_trees = nTrees;
     p.seed = seed;
     pjb_grow_result r;
-    run.check(pjb_forest_grow(run.ctx, matrix.data(), (int64_t)x.size(), (int32_t)active.size(), &p, &r), "pjb_forest_grow");
+    run.check(pjb_forest_grow(run.ctx, matrix.data(), (int64_t)x.size(), (int32_t)activeFeatures().size(), &p, &r), "pjb_forest_grow");
     if (featuresOut) featuresOut->swap(rows);
     return Forest::fromView(r.forest, r.class_values);
 }
@@ -259,18 +283,10 @@ Forest ModelFeatures::trainInstance(const JunctionList& pos, const JunctionList&
     trainingSystem.sort();
     const JunctionList& x = trainingSystem.getJunctions();
     // the feature rows of the real junctions: the device's (what forestPredict walks), column 0 the genuine flag
-    const size_t F = PJB_N_FEATURES;
-    const std::vector<int32_t>& active = activeFeatures();
-    const size_t C = active.size(), SC = C - 1;
-    std::vector<double> rows(x.size() * F, 0.0);
-    DeviceRun run;
-    openRun(run, *this, gmap, device, x);
-    run.check(pjb_filt_features(run.ctx, run.rows.data(), (int64_t)run.rows.size(), x[0]->getMeanReadLength(), L95, &run.m, rows.data()), "pjb_filt_features");
-    std::vector<double> matrix(x.size() * C);
-    for (size_t i = 0; i < x.size(); i++) {
-        matrix[i * C] = x[i]->isGenuine() ? 1.0 : 0.0;
-        for (size_t k = 1; k < C; k++) matrix[i * C + k] = rows[i * F + (size_t)active[k]];
-    }
+    const size_t C = activeFeatures().size(), SC = C - 1;
+    DeviceRun run;  // (lives on: pjb_knn and pjb_forest_grow below run on its context)
+    const std::vector<double> rows = featureRows(run, *this, gmap, device, x);
+    std::vector<double> matrix = projectActive(rows);
     auto nearest = [&](const std::vector<double>& m, size_t n, int32_t defaultK, std::vector<uint32_t>& nn) {
         const int32_t k = selftrain::effectiveK(n, defaultK);
         nn.assign(n * (size_t)k, 0);
@@ -298,19 +314,10 @@ Forest ModelFeatures::trainInstance(const JunctionList& pos, const JunctionList&
         }
         cout << "Number of synthesized entries: " << nSynth << endl;
     }
-    if (o.saveFeatures) {  // :402-410: the real rows, default stream formatting
+    if (o.saveFeatures) {  // :402-410: the real rows (the synthetic ones have no junction)
         const std::string file = o.outputPrefix + ".features";
         if (o.verbose) cout << "Saving feature vector to disk: " << file << endl;
-        std::ofstream fout(file.c_str());
-        const std::vector<std::string> names = featureNames();
-        fout << Intron::locationOutputHeader();
-        for (const int32_t k : active) fout << "\t" << names[(size_t)k];
-        fout << endl;
-        for (size_t i = 0; i < x.size(); i++) {
-            fout << *(x[i]->getIntron());
-            for (size_t k = 0; k < C; k++) fout << "\t" << matrix[i * C + k];
-            fout << endl;
-        }
+        saveFeatures(file, x, rows);
     }
     if (o.enn) {
         const size_t n = matrix.size() / C;

@@ -2,22 +2,18 @@
 #include "self_train.hpp"
 
 #include <dirent.h>
-#include <sys/stat.h>
 
 #include <algorithm>
 #include <cmath>
 #include <cstdlib>
 
+#include "fs_util.hpp"
 #include "rule_filter.hpp"
 
 namespace portcullis {
 namespace selftrain {
 
 namespace {
-bool isDirectory(const std::string& p) {
-    struct stat st;
-    return stat(p.c_str(), &st) == 0 && S_ISDIR(st.st_mode);
-}
 // N of a name that ends in layerN.json (N: one digit or more), or -1
 long layerNumber(const std::string& name) {
     const std::string tail = ".json";

@@ -1,43 +1,20 @@
 // Train: see portcullis/train.hpp.
 #include <portcullis/train.hpp>
 
-#include <sys/stat.h>
-
 #include <chrono>
-#include <fstream>
 #include <iomanip>
 #include <iostream>
 
 #include <portcullis/ml/model_features.hpp>
 
 #include "../../../include/portcullis_amd.h"
+#include "fs_util.hpp"
 
 using std::cout;
 using std::endl;
 using std::string;
 
 namespace portcullis {
-
-namespace {
-bool exists(const string& p) {
-    struct stat st;
-    return stat(p.c_str(), &st) == 0;
-}
-bool isDirectory(const string& p) {
-    struct stat st;
-    return stat(p.c_str(), &st) == 0 && S_ISDIR(st.st_mode);
-}
-bool createDirectories(const string& p) {
-    string cur;
-    for (size_t i = 0; i <= p.size(); i++) {
-        if (i == p.size() || p[i] == '/') {
-            if (!cur.empty() && !exists(cur) && mkdir(cur.c_str(), 0777) != 0 && !exists(cur)) return false;
-        }
-        if (i < p.size()) cur.push_back(p[i]);
-    }
-    return isDirectory(p);
-}
-}  // namespace
 
 void Train::train() {
     size_t slash = output.find_last_of('/');
@@ -95,17 +72,7 @@ void Train::train() {
     if (saveFeatures) {  // lib/src/model_features.cc:402-410: the active columns, default stream formatting
         const string file = output + ".features.training";
         if (verbose) cout << "Saving feature vector to disk: " << file << endl;
-        std::ofstream fout(file.c_str());
-        const std::vector<string> names = ml::ModelFeatures::featureNames();
-        const std::vector<int32_t>& active = ml::ModelFeatures::activeFeatures();
-        fout << Intron::locationOutputHeader();
-        for (const int32_t k : active) fout << "\t" << names[(size_t)k];
-        fout << endl;
-        for (size_t i = 0; i < x.size(); i++) {
-            fout << *(x[i]->getIntron());
-            for (const int32_t k : active) fout << "\t" << features[i * names.size() + (size_t)k];
-            fout << endl;
-        }
+        ml::ModelFeatures::saveFeatures(file, x, features);
     }
     forest.save(output + ".forest");
     cout << "Saved forest to file " << output << ".forest" << endl;

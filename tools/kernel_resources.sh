@@ -2,10 +2,10 @@
 # Register / LDS / occupancy table of every kernel of libportcullis_amd.so (no GPU needed: hipcc's resource-usage remarks).
 #   bash tools/kernel_resources.sh [name-filter]      (k1_, kx_, kr_, kt_, kn_ ...: a kernel family by its prefix)
 cd "$(dirname "$0")/../portcullis_amd/csrc"
-#   UNITS="pjb_api" bash tools/kernel_resources.sh k1_   (one translation unit only: pjb_api | pjb_extra_api | pjb_ingest_api)
-#   UNITS="pjb_extra_api" bash tools/kernel_resources.sh kn_   (pjb_knn's kernels: profiles/selftrain_knn_resources.txt)
+#   UNITS="pjb_api" bash tools/kernel_resources.sh k1_   (one translation unit only: pjb_api | pjb_extra_api | pjb_model_api | pjb_ingest_api)
+#   UNITS="pjb_model_api" bash tools/kernel_resources.sh kn_   (pjb_knn's kernels: profiles/selftrain_knn_resources.txt, taken when they were in pjb_extra_api)
 : > /tmp/pjb_resource.txt
-for u in ${UNITS:-pjb_api pjb_extra_api pjb_ingest_api}; do
+for u in ${UNITS:-pjb_api pjb_extra_api pjb_model_api pjb_ingest_api}; do
   /opt/rocm/bin/hipcc -O3 -std=c++17 -fPIC --offload-arch=gfx950 -ffp-contract=off -Wno-unused-function -Rpass-analysis=kernel-resource-usage -c -o /tmp/${u}_res.o $u.hip 2>> /tmp/pjb_resource.txt &
 done
 wait
