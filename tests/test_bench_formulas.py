@@ -1,4 +1,6 @@
-"""bench.py's byte formulas: every kernel the chain launches (pjb_api.hip) has one, so that `roofline.step_alg_bytes` prices the whole step."""
+"""bench.py's byte formulas: every kernel the chain launches (the stages of pjb_chain.hip.h, read whole) has one, so that
+`roofline.step_alg_bytes` prices the whole step.  The sort's passes are launched by the names of the header's `rs_names` table (the run
+route's `ro_names` have no formula: bench.py lists them under kernels_without_formula)."""
 import os
 import re
 import sys
@@ -7,11 +9,9 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def chain_kernel_names():
-    src = open(os.path.join(ROOT, "portcullis_amd", "csrc", "pjb_api.hip")).read()
-    a = src.index("static int queue_contig(")
-    b = src.index("static void unqueue_followers(")
-    body = src[a:b]
+    body = open(os.path.join(ROOT, "portcullis_amd", "csrc", "pjb_chain.hip.h")).read()
     names = set(re.findall(r'LAUNCH(?:_LDS)?\(c, "([a-z0-9_]+)"', body))
+    names |= set(re.findall(r'"([a-z0-9_]+)"', re.search(r'rs_names\[4\] = \{([^}]*)\}', body).group(1)))
     for scan in re.findall(r'run_scan\(c, "([a-z0-9_]+)"', body):
         names |= {scan + "_reduce", scan + "_apply", scan + "_tiles"}
     return {n for n in names if not n.startswith(("kx_", "k0_"))}
@@ -21,7 +21,8 @@ def test_every_chain_kernel_has_a_byte_formula():
     import bench
 
     names = chain_kernel_names()
-    assert {"k1_count", "k1_emit", "k1_generic", "k4b_generic", "k4_pairs", "k6_rows_out"} <= names
+    assert {"k1_count", "k1_scan_tiles", "k1_emit", "k1_generic", "kd_assign", "rs_scatter", "k4b_generic", "k4_pairs", "k2_expand",
+            "k2_heads_reduce", "k5_finalize", "k6_rows_out"} <= names  # (a kernel of every stage: a scan that misses one fails here)
     missing = [n for n in sorted(names)
                if bench.algorithmic_bytes(n, 1e6, 3e6, 3e5, 1e6, 4e5, 1e4, 150, 1e4, 5e3, 1e5, 2e4, 5e4, True, 3e8) is None
                and not n.endswith("_tiles")]  # (the scan's middle kernel exists for inputs of more than 4096 tiles only)
