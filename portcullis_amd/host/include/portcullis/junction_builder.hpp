@@ -5,7 +5,10 @@
 #pragma once
 
 #include <future>
+#include <memory>
+#include <mutex>
 #include <string>
+#include <thread>
 #include <vector>
 
 #include "bam/bam_reader.hpp"
@@ -21,6 +24,27 @@ const uint16_t DEFAULT_JUNC_THREADS = 1;
 
 struct JunctionBuilderException : public PortcullisException {
     explicit JunctionBuilderException(const std::string& m) : PortcullisException(m) {}
+};
+
+// The end of a junc run's device side as something a caller can wait on: the threads that destroy the run's device contexts and give
+// its page-locked rings back.  A driver that runs another stage on the device in the same process (`full`) hands one to
+// setTeardown() and calls wait() where that stage first needs the device; the stage's host-only work runs beside the teardown.
+// wait() may be called more than once; the destructor waits too, so no thread outlives its owner inside the runtime.
+class JuncTeardown {
+    std::vector<std::thread> threads;
+    std::mutex mu;
+
+public:
+    JuncTeardown() = default;
+    JuncTeardown(const JuncTeardown&) = delete;
+    JuncTeardown& operator=(const JuncTeardown&) = delete;
+    ~JuncTeardown() { wait(); }
+    void add(std::thread t) {
+        std::lock_guard<std::mutex> lk(mu);
+        threads.push_back(std::move(t));
+    }
+    // returns the seconds this call spent waiting
+    double wait();
 };
 
 // per target sequence outcome (RegionResult, src/junction_builder.hpp:62-76)
@@ -59,6 +83,7 @@ class JunctionBuilder {
     std::shared_ptr<class PinnedPool> genomePool;  // a few page-locked buffers for the FASTA bytes of the target sequences (same runs)
     size_t pieceMinTarget = 0;                     // targets with fewer bytes go over in one (pageable) block
     bool backgroundTeardown = false;               // contexts and page-locked rings are taken down beside the merge and the writers (the program sets it: it leaves with _exit; a library caller that returns from main must not have a thread inside the runtime then)
+    std::shared_ptr<JuncTeardown> teardown;        // set: the background teardown's threads go here instead of being detached (setTeardown)
     bool deviceIngest = true;      // BGZF inflate + BAM record parse on the GPU (pjb_submit_bam); false: host threads
 
     std::shared_ptr<const struct JuncEnv> env;  // the environment's switches, read once by the constructor (src/junction_builder.cc)
@@ -135,6 +160,10 @@ public:
     // total host decode threads, independent of the number of target sequences (the reference's
     // --threads is capped at the number of targets; this one is not)
     void setHostThreads(int n) { hostThreads = n; }
+    // The contexts and the page-locked rings are taken down in the background, on threads that `t` owns: process() returns while they
+    // run, and t->wait() returns once every context of this run is destroyed and every ring given back.  Without it process() takes
+    // them down itself before it returns; only the `junc` command detaches the threads, because it leaves through _exit right after.
+    void setTeardown(const std::shared_ptr<JuncTeardown>& t) { teardown = t; }
 
     void process();
 

@@ -7,6 +7,7 @@
 // the way out.  Deviations: INTEGRATION.md, "Known deviations".
 #pragma once
 
+#include <functional>
 #include <string>
 
 #include "junction_system.hpp"
@@ -39,6 +40,7 @@ class JunctionFilter {
     double threshold = DEFAULT_FILTER_THRESHOLD;
     bool verbose = false;
     int device = 0;
+    std::function<void()> beforeDevice;  // (setBeforeDevice)
 
     void forestPredict(const JunctionList& all, JunctionList& pass, JunctionList& fail, ml::ModelFeatures& mf, const ml::Forest& forest);
     // src/junction_filter.cc:278-437: true if a forest was trained (mf holds L95 and the Markov models, <output>.selftrain.forest is
@@ -74,6 +76,10 @@ public:
     void setSaveFeatures(bool v) { saveFeatures = v; }
     void setThreshold(double v) { threshold = v; }
     void setDevice(int v) { device = v; }
+    // Called once, right before filter() first touches the device (never on a route that needs none): a driver that ran another stage
+    // on the device in this process waits here until that stage's memory is back.  Loading the table, the rule files and the initial
+    // sets come before it.
+    void setBeforeDevice(std::function<void()> f) { beforeDevice = std::move(f); }
 
     void filter();
 

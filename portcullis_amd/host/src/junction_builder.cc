@@ -772,6 +772,16 @@ void JunctionBuilder::calcExtraMetrics(JuncRun& run) {
 // rings with them, is 0.1-0.3 s of runtime and driver work that nothing waits for: it runs beside the merge and the
 // writers instead of before them.
 void JunctionBuilder::tearDown(JuncRun& run) {
+    if (teardown && run.firstError.empty()) {
+        // a driver that goes on in this process owns the two threads below and waits for them where its next stage needs the device
+        // (also under PJB_NORMAL_EXIT: it has joined them before main returns)
+        teardown->add(std::thread([pp = std::move(pinnedPool), gp = std::move(genomePool)]() mutable {
+            pp.reset();
+            gp.reset();
+        }));
+        teardown->add(std::thread([dts = std::move(run.deviceThreads)]() mutable { dts.clear(); }));
+        return;
+    }
     // (a process that will leave through exit handlers must not have a thread inside the runtime by then)
     if (!backgroundTeardown || env->normalExit || !run.firstError.empty()) {
         run.deviceThreads.clear();  // joins the device threads (destroys the contexts)
@@ -788,6 +798,17 @@ void JunctionBuilder::tearDown(JuncRun& run) {
         gp.reset();
     }).detach();
     std::thread([dts = std::move(run.deviceThreads)]() mutable { dts.clear(); }).detach();
+}
+
+double JuncTeardown::wait() {
+    const double t0 = HostProfile::now();
+    std::vector<std::thread> mine;
+    {
+        std::lock_guard<std::mutex> lk(mu);
+        mine.swap(threads);
+    }
+    for (auto& t : mine) t.join();
+    return HostProfile::now() - t0;
 }
 
 // the merge of the targets' systems and its console output (src/junction_builder.cc:258-290)

@@ -171,6 +171,7 @@ bool JunctionFilter::selfTrain(const JunctionList& all, ml::ModelFeatures& mf, m
         filterFile = lowJuncs;
         return false;
     }
+    if (beforeDevice) beforeDevice();
     if (pjb_device_count() <= 0)
         throw JuncFilterException("No MI355X (HIP device) is visible: self-training searches neighbours and grows its forest on the GPU and has no CPU fallback.  "
                                   "Run filt where the GPU is.");
@@ -271,6 +272,7 @@ void JunctionFilter::filter() {  // :153-596
         mf.initGenomeMapper(prepData.getGenomeFilePath());
         cout << "Predicting valid junctions using random forest model" << endl << "----------------------------------------------------" << endl << endl;
         JunctionList passJuncs, failJuncs;
+        if (beforeDevice) beforeDevice();
         forestPredict(currentJuncs, passJuncs, failJuncs, mf, forest);
         printFilteringResults(currentJuncs, passJuncs, failJuncs, "Random Forest filtering results");
         currentJuncs = passJuncs;

@@ -1,8 +1,10 @@
 // portcullis_amd: command line entry: the `junc` mode, `filt` with a saved model and / or rules, `train` (a model grown from two labelled
-// junction tables), `bamfilt` and `prep` for a BAM that is sorted already; filt's self-training is behind `filt --self_train`; prep's sort / merge remain the reference's programs and interoperate through the prep
-// directory, the .tab file and the saved .forest model.
+// junction tables), `bamfilt` and `prep` for a BAM that is sorted already; filt's self-training is behind `filt --self_train`;
+// `full` runs prep, junc, self-trained filt and (with -b) bamfilt as one pipeline in this one process; prep's sort / merge remain the
+// reference's programs and interoperate through the prep directory, the .tab file and the saved .forest model.
 #include <dirent.h>
 #include <portcullis/bam_filter.hpp>
+#include <portcullis/full.hpp>
 #include <portcullis/junction_builder.hpp>
 #include <portcullis/junction_filter.hpp>
 #include <portcullis/prepare.hpp>
@@ -113,12 +115,13 @@ int main(int argc, char* argv[]) {
         fprintf(stderr, "[host profile] main entered at epoch %.6f\n", (double)ts.tv_sec + ts.tv_nsec * 1e-9);
     }
     try {
-        if (argc < 2 || (strcmp(argv[1], "junc") != 0 && strcmp(argv[1], "bamfilt") != 0 && strcmp(argv[1], "prep") != 0 && strcmp(argv[1], "filt") != 0 && strcmp(argv[1], "train") != 0)) {
+        if (argc < 2 || (strcmp(argv[1], "junc") != 0 && strcmp(argv[1], "bamfilt") != 0 && strcmp(argv[1], "prep") != 0 && strcmp(argv[1], "filt") != 0 && strcmp(argv[1], "train") != 0 && strcmp(argv[1], "full") != 0)) {
             std::cerr << "Usage: portcullis_amd junc [options] <prep_data_dir>" << std::endl
                       << "       portcullis_amd bamfilt [options] <junction-file> <bam-file>" << std::endl
                       << "       portcullis_amd prep [options] <genome-file> <bam-file>" << std::endl
                       << "       portcullis_amd filt [options] <prep_data_dir> <junction_tab_file>" << std::endl
-                      << "       portcullis_amd train [options] <prep_data_dir> <positive_tab_file> <negative_tab_file>" << std::endl;
+                      << "       portcullis_amd train [options] <prep_data_dir> <positive_tab_file> <negative_tab_file>" << std::endl
+                      << "       portcullis_amd full [options] --self_train <data_dir> <genome-file> <bam-file>" << std::endl;
             return 1;
         }
         portcullis::JunctionSystem::version = PORTCULLIS_AMD_VERSION;
@@ -126,6 +129,7 @@ int main(int argc, char* argv[]) {
         else if (strcmp(argv[1], "prep") == 0) rc = portcullis::Prepare::main(argc - 1, argv + 1);
         else if (strcmp(argv[1], "filt") == 0) rc = portcullis::JunctionFilter::main(argc - 1, argv + 1);
         else if (strcmp(argv[1], "train") == 0) rc = portcullis::Train::main(argc - 1, argv + 1);
+        else if (strcmp(argv[1], "full") == 0) rc = portcullis::Full::main(argc - 1, argv + 1);
         else rc = portcullis::JunctionBuilder::main(argc - 1, argv + 1);
     } catch (const portcullis::PortcullisException& e) {
         std::cerr << "Error: " << e.what() << std::endl;
