@@ -1,5 +1,5 @@
 // pjb_chain.hip.h -- the launcher of a `junc` chain: queue_contig as named stages over one chain state (Chain).  Host code only, included by
-// pjb_api.hip behind pjb_kernels.hip.h and by nothing else.  The stages run in the order they stand in: plan (no HIP call), room (every
+// pjb_api.hip behind pjb_kernels.hip.h -- and before pjb_flight.hip.h, which calls queue_contig -- and by nothing else.  The stages run in the order they stand in: plan (no HIP call), room (every
 // allocation of the chain), front, K1, K2d, sort, the runs (dense ids or full keys), rows.
 #pragma once
 

@@ -665,4 +665,15 @@ __device__ __forceinline__ void fetch_clamp(int32_t glen, int32_t &b, int32_t &e
 constexpr int PUB_BASE_AT = 240, PUB_ERR_AT = 256, PUB_XCNT_AT = 320 /* --extra: the target's counters, 64 bytes */, PUB_CHECKED_AT = 384 /* reads on k4b_generic's second list */, PUB_GEN_AT = 512, PUB_MEMBERS_AT = 1536, PUB_GREADS_AT = 3072, PUB_BYTES = 4096; // byte offsets in the published block
 static_assert(PUB_MEMBERS_AT + GROUP_MAX * sizeof(MemberStats) <= PUB_BYTES && sizeof(MemberStats) % 8 == 0, "control block layout");
 
+// the read lists of a chain (EmitLists, pjb_kernels.hip.h): sub-lists, and the words of a sub-list's line of counters
+constexpr u32 GEN_SHARDS = 256, GEN_CNT_STRIDE = 32;
+// Room of a sub-list (before anything says otherwise): k1_emit deals its chunks of 256 spliced reads round-robin to the sub-lists
+// (up to 256 entries a chunk on list 2 and on list 3), k1_generic its chunks of 256 items of list 3 (up to 256 entries on list 1
+// or 2).  A sub-list that several full chunks of both kernels hit can want more than this: the appends count on, nothing is
+// written past the room, the chain is closed (OVF_LISTS, ContigStats::list_need) and repeated with the room it asked for.
+__host__ __device__ inline u32 gen_list_cap(u32 pair_limit) {
+    const u32 chunks = pair_limit / 256u + 2u;
+    return ((chunks + GEN_SHARDS - 1) / GEN_SHARDS) * 256u;
+}
+
 } // namespace pjb

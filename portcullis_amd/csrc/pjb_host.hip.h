@@ -1,5 +1,6 @@
 // pjb_host.hip.h -- what the translation units of the C ABI share: the context (pjb_ctx) and its parts, error / allocation / launch helpers.
-// The library is built from four units -- pjb_api.hip (contexts, uploads, batches, the kernel chains: pjb_kernels.hip.h), pjb_extra_api.hip
+// The library is built from four units -- pjb_api.hip (contexts, uploads, batches, the kernel chains: pjb_kernels.hip.h, and the host code
+// that queues and collects them: pjb_chain.hip.h, pjb_flight.hip.h, pjb_limits.hip.h), pjb_extra_api.hip
 // (--extra, bamfilt: pjb_extra.hip.h), pjb_model_api.hip (filt and train -- feature rows, the forest walk, forest growing, KNN:
 // pjb_features.hip.h, pjb_forest.hip.h, pjb_grow.hip.h, pjb_knn.hip.h) and pjb_ingest_api.hip (BGZF inflate / deflate, BAM records:
 // pjb_ingest.hip.h, pjb_deflate.hip.h) -- each of which includes its own kernel family behind this header and so is the only unit that compiles it; this header includes only what the

@@ -1305,7 +1305,6 @@ constexpr int K1E_LOOK = 16;
 constexpr int K1E_T = 256, K1E_SHIFT = 8; // threads of a block = list entries of one trip
 constexpr int KC_SLOTS = K1E_T;               // the block's candidate set (LDS), flushed when a quarter full: a slot per thread (two: 8.82 against 8.75 ms a step)
 constexpr u64 KD_EMPTY = ~0ull; // no key: a packed key has fewer than 64 bits
-constexpr u32 GEN_SHARDS = 256, GEN_CNT_STRIDE = 32;
 constexpr int KD_PAGE_SHIFT = 6; // a page of the start bitmap: 64 words, one wavefront
 struct EmitLists {
     u64 *cand;      // candidate keys (nullptr: the chain sorts the full keys and wants none); their count is ContigStats::n_cand
@@ -1320,14 +1319,6 @@ struct EmitLists {
     u32 gen_cap;    // room of one sub-list
     u32 pack_nn;    // 1 (chains of fewer than 2^28 slots): entries of the second list carry min(N operations, 15) in bits 28-31 of the slot
 };
-// Room of a sub-list (before anything says otherwise): k1_emit deals its chunks of 256 spliced reads round-robin to the sub-lists
-// (up to 256 entries a chunk on list 2 and on list 3), k1_generic its chunks of 256 items of list 3 (up to 256 entries on list 1
-// or 2).  A sub-list that several full chunks of both kernels hit can want more than this: the appends count on, nothing is
-// written past the room, the chain is closed (OVF_LISTS, ContigStats::list_need) and repeated with the room it asked for.
-__host__ __device__ inline u32 gen_list_cap(u32 pair_limit) {
-    const u32 chunks = pair_limit / 256u + 2u;
-    return ((chunks + GEN_SHARDS - 1) / GEN_SHARDS) * 256u;
-}
 // the fullest sub-list of the three lists' sub-lists `shard` (0: all within their room)
 __device__ __forceinline__ u32 lists_over(const u32 *gen_cnt, u32 shard, u32 cap) {
     const u32 a = gen_cnt[shard * GEN_CNT_STRIDE], b = gen_cnt[shard * GEN_CNT_STRIDE + 2], c = gen_cnt[shard * GEN_CNT_STRIDE + 4];

@@ -290,6 +290,8 @@ def test_pair_limit_overflow_inside_a_group(ffi, orc):
         ctx.finish_group_begin([0, 1])     # ~100 k pairs from 16 k alignments: over the limit
         ctx.finish_contig_begin(2)         # queued behind it
         regs = ctx.finish_group_end([0, 1])
+        t = ctx.timing()
+        assert t["repeats"] >= 1 and t["repeat_reasons"] & 1, t  # (OVF_PAIRS: queued again with the count it found)
         r2 = ctx.finish_contig_end(2)
         rows = ctx.collect()
     for tid in (0, 1):
