@@ -1378,8 +1378,10 @@ static size_t ctx_index(const char *s, int order) {
     for (int k = 0; k < order; k++) x = x * 5 + (size_t)clean_code(s[k]);
     return x;
 }
-static void kmm_count(kmm *m, const sbuf *clean) { /* train, :34-41: only strings longer than order + 1 */
-    if (clean->n > (size_t)m->order + 1)
+/* train, :34-41: only strings longer than order + 1 -- by markov_model.cc:36, `(uint16_t)s.size() > order + 1`, whose cast
+ * cuts the length to 16 bits for the gate alone: 65 539 bases (3 mod 65 536) train nothing, 65 543 are counted in full */
+static void kmm_count(kmm *m, const sbuf *clean) {
+    if ((uint16_t)clean->n > m->order + 1)
         for (size_t i = (size_t)m->order; i < clean->n; i++) {
             size_t c = ctx_index(clean->p + i - m->order, m->order);
             m->tab[c * 5 + (size_t)clean_code(clean->p[i])] += 1.0;

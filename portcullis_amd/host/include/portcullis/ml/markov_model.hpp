@@ -41,7 +41,9 @@ public:
         tab.assign(nCtx() * 5, 0.0);
         seen.assign(nCtx(), 0);
         for (const auto& s : input)
-            if (s.size() > (size_t)order + 1)
+            // markov_model.cc:36 tests `(uint16_t)s.size() > order + 1`: the length is cut to 16 bits for the gate alone, so a
+            // string of 65 539 bases (65 539 mod 65 536 = 3) trains nothing and one of 65 543 is counted in full
+            if ((uint16_t)s.size() > order + 1)
                 for (size_t i = order; i < s.size(); i++) {
                     const size_t c = ctx(s, i - order);
                     tab[c * 5 + (size_t)cleanCode(s[i])] += 1.0;

@@ -1,8 +1,9 @@
 """`portcullis_amd train` end to end with nothing but this repository: prep -> junc, the junction table split into a positive and a negative
 table by a fixed rule, train --trees 8 --save_features, then filt --model_file with the model it wrote.
 
-There is no reference pin at this level: the feature rows are SURVEY.md row f4, which DESIGN.md section 2 lists as unpinned (the device's rows
-are within 1e-6 of the oracle's, and a forest grown on them may split elsewhere).  What is pinned: the .forest file is byte for byte
+There is no reference pin at this level: the feature rows are SURVEY.md row f4, of which DESIGN.md section 2 lists the Markov scores as pinned
+by the reference's own code and the window coordinates and the other columns as a restatement (the device's rows are within 1e-6 of the
+oracle's, and a forest grown on them may split elsewhere).  What is pinned: the .forest file is byte for byte
 ffi.Forest.grow() of the matrix built from ffi.filt_features of the same junctions in sorted order -- and growing is pinned against ranger
 itself in test_gpu_forest_grow.py -- and filt's scores with that model are pjb_forest_predict's."""
 import os

@@ -1,7 +1,9 @@
 """Hand-worked checks of the oracle's restatement of the filt-stage Markov models and feature rows
 (lib/src/markov_model.cc, lib/src/model_features.cc:67-212, lib/src/junction.cc:953-956,1328-1391).  The reference holds
 no test or vector for this code (tests/kmer_tests.cpp is about the k-mer hash only), so these values are derived from the
-source by hand: row f4 of the oracle is "parity unpinned" in the sense of the project rules."""
+source by hand.  The Markov models themselves -- training, sizes, scores -- are pinned elsewhere, by the reference's own
+markov_model.cc (tests/test_oracle_markov_witness.py); what stays a hand-checked restatement in row f4 is the window
+coordinates, the two isEmpty gates and the other columns."""
 import math
 
 import numpy as np
