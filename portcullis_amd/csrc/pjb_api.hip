@@ -165,6 +165,11 @@ int pjb_create(pjb_ctx **out, const pjb_config *cfg) {
         int v = atoi(s);
         if (v >= 4 && v <= RS_MAX_BITS) c->radix_max_bits = v;
     }
+    if (const char *s = getenv("PJB_PAIR_RANGE")) { // (A/B runs of a command that sets no options: what pjb_set_option("pair_range", n) takes)
+        const int v = atoi(s);
+        for (int k = 0; k <= PAIR_RANGE_SHIFT_MAX; k++)
+            if (v == 1 << k) c->pair_range_shift = k;
+    }
     cmark("options");
     attr_thread.join();
     cmark("kernel attributes");
@@ -717,6 +722,12 @@ int pjb_set_option(pjb_ctx *c, const char *name, int64_t value) {
     else if (n == "run_window") {
         if (value < 0 || value > (int64_t)RUN_W) return fail(c, PJB_ERR_ARG, "set_option: run_window takes 0 (the default, %u) to %u", RUN_W, RUN_W);
         c->run_window = (u32)value;
+    } else if (n == "pair_range") {
+        int shift = -1;
+        for (int k = 0; k <= PAIR_RANGE_SHIFT_MAX; k++)
+            if (value == (int64_t)1 << k) shift = k;
+        if (shift < 0) return fail(c, PJB_ERR_ARG, "set_option: pair_range takes 1, 2, 4, 8, 16 or 32 slices a range (the default: %d)", 1 << PAIR_RANGE_SHIFT_DEFAULT);
+        c->pair_range_shift = shift;
     } else if (n == "grow_batch") {
         if (value < 0 || value > 32768) return fail(c, PJB_ERR_ARG, "set_option: grow_batch takes 0 (the default: what the pool holds) to 32768 trees");
         c->model.grow_batch = (u32)value;

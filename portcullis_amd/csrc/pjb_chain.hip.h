@@ -64,7 +64,8 @@ struct Chain {
     int32_t ref_len; // the sequence the chain works on: the target itself, or the group's virtual sequence (every member at its offset)
     KeyFmt kf;
     u32 PL, JL, SL; // (SL: ids the sort's digits cover)
-    u32 n_tiles, pair_blocks, slots_lim, n_slices_lim, gen_cap, pack_nn;
+    u32 n_tiles, pair_blocks, range_blocks, slots_lim, n_slices_lim, gen_cap, pack_nn;
+    int range_shift; // slices a range of k4_pairs, as a shift (frag_slot)
     size_t n_words;
     int64_t row_base, mirror_base;
     // the sort's plan: as few passes as the widest digit allows, bits spread evenly; the run route (ContigLimits::run_sort) sorts its
@@ -161,7 +162,9 @@ static int chain_plan(Chain &ch) {
     // entries per sub-list (list_cap_forced: the test hook pjb_set_option("list_cap", n) -- a first attempt with a room that overflows)
     ch.gen_cap = lim.list_cap ? lim.list_cap : (c->list_cap_forced ? c->list_cap_forced : gen_list_cap(PL));
     ch.pack_nn = (u64)ch.n_tiles * K1_TILE < (1ull << 28) ? 1u : 0u; // (EmitLists::pack_nn: the slots of the tiles' spliced lists fit 28 bits)
-    ch.slots_lim = JL + (PL + 63) / 64 + 1;
+    ch.range_shift = c->pair_range_shift;
+    ch.slots_lim = frag_slots_limit(JL, PL, ch.range_shift);
+    ch.range_blocks = std::max<u32>(1, (frag_ranges(PL, ch.range_shift) + 3) / 4); // k4_pairs: a wavefront a range
     ch.n_slices_lim = (PL + 63) / 64 + 1;
     ch.n_words = ((size_t)std::max(ch.ref_len, 1) + 63) / 64; // K2d's bitmap
     ch.stage_events = c->ktime && c->ktime_only.empty();
@@ -506,7 +509,7 @@ static int chain_k2d(Chain &ch) {
         return rc;
     LAUNCH(c, "kd_table", kd_table, dim3(cand_blocks), dim3(256), (const u64 *)cand, (const u64 *)S.ent.p, (const u32 *)cand_rank, kf, JL,
            (const u32 *)S.ends.p, (const u32 *)S.firstid.p, (const u64 *)S.total.p, (u64 *)S.jkey.p, (int32_t *)S.ancl.p, (int32_t *)S.ancr.p, ch.d_cs,
-           (const u32 *)ch.d_gen_cnt, ch.gen_cap, ch.SL, ch.ro.n_runs);
+           (const u32 *)ch.d_gen_cnt, ch.gen_cap, ch.SL, ch.ro.n_runs, ch.range_shift);
     // (a block per tile of the sort: it leaves the tile's counts of the ids' first digit -- the first pass of the sort has no rs_hist --,
     // or, on the run route, the tile's id runs)
     LAUNCH(c, "kd_assign", kd_assign, dim3(ch.rs_tiles), dim3(256), okey, ch.d_P, kf, (const u64 *)S.bitmap.p, (const u32 *)S.wrank.p,
@@ -664,8 +667,8 @@ static int chain_runs_dense(Chain &ch) {
 #ifdef PJB_DEBUG_LAUNCH
     debug_sort_check(ch);
 #endif
-    LAUNCH(c, "k4_pairs", k4_pairs, dim3(pair_blocks), dim3(256), f.sidx, f.jid_sorted, (const PairRec *)ch.pr.rec, (const u64 *)S.jkey.p, ch.kf, ch.d_P,
-           (u32 *)S.frag.p, (int32_t *)S.fragj.p, head_mask, run_mask, (const ContigStats *)ch.d_cs, ch.d_err);
+    LAUNCH(c, "k4_pairs", k4_pairs, dim3(ch.range_blocks), dim3(256), f.sidx, f.jid_sorted, (const PairRec *)ch.pr.rec, (const u64 *)S.jkey.p, ch.kf, ch.d_P,
+           (u32 *)S.frag.p, (int32_t *)S.fragj.p, head_mask, run_mask, (const ContigStats *)ch.d_cs, ch.d_err, ch.range_shift);
     if ((rc = run_scan(c, "k2_runs", Popc64Fn{(const u64 *)run_mask}, ExclusiveU32Sink{run_base}, (u64)n_slices_lim, (u64 *)S.total.p, &ch.d_cs->n_slices)))
         return rc;
     LAUNCH(c, "k2_expand", k2_expand, dim3((pair_blocks + K2E_PER - 1) / K2E_PER), dim3(256), f.jid_sorted, (const u64 *)head_mask, (const u64 *)run_mask, (const u32 *)run_base,
@@ -687,7 +690,7 @@ static int chain_runs_keys(Chain &ch) {
     HeadSink hs{(u32 *)S.jid.p, (u32 *)S.seg.p, (u32 *)S.runfirst.p, (u32 *)S.runstart.p, skey, (u64 *)S.jkey.p, JL};
     if ((rc = run_scan(c, "k2_heads", hf, hs, (u64)ch.PL, (u64 *)S.total.p, ch.d_P))) return rc;
     LAUNCH(c, "k2_close", k2_close, dim3(1), dim3(1), (u64 *)S.total.p, (u32 *)S.seg.p, (u32 *)S.runfirst.p,
-           (u32 *)S.runstart.p, ch.d_cs, JL, (const u32 *)ch.d_gen_cnt, ch.gen_cap);
+           (u32 *)S.runstart.p, ch.d_cs, JL, (const u32 *)ch.d_gen_cnt, ch.gen_cap, ch.range_shift);
     STAGE_EVENT(3);
     if ((rc = chain_fork(ch, S.ev_fork2, S.ev_join2, ch.entropy_forked, chain_entropy))) return rc;
     LAUNCH(c, "kf_init", kf_init, dim3(std::max<u32>(1, std::min<u32>((JL * F_WORDS + 255) / 256, 4096))), dim3(256), (u32 *)S.acc.p, ch.d_J, (int32_t *)S.ancl.p,
@@ -696,8 +699,8 @@ static int chain_runs_keys(Chain &ch) {
            (int32_t *)S.ancl.p, (int32_t *)S.ancr.p);
     if ((rc = chain_k4b(ch))) return rc;
     STAGE_EVENT(4);
-    LAUNCH(c, "k4_pairs", k4_pairs, dim3(pair_blocks), dim3(256), f.sidx, f.jid_sorted, (const PairRec *)ch.pr.rec, (const u64 *)S.jkey.p, ch.kf, ch.d_P,
-           (u32 *)S.frag.p, (int32_t *)S.fragj.p, (u64 *)nullptr, (u64 *)nullptr, (const ContigStats *)ch.d_cs, ch.d_err);
+    LAUNCH(c, "k4_pairs", k4_pairs, dim3(ch.range_blocks), dim3(256), f.sidx, f.jid_sorted, (const PairRec *)ch.pr.rec, (const u64 *)S.jkey.p, ch.kf, ch.d_P,
+           (u32 *)S.frag.p, (int32_t *)S.fragj.p, (u64 *)nullptr, (u64 *)nullptr, (const ContigStats *)ch.d_cs, ch.d_err, ch.range_shift);
     STAGE_EVENT(5);
     return PJB_OK;
 }

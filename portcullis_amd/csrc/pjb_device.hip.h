@@ -71,7 +71,7 @@ struct ContigStats {
     u32 n_junc, n_runs; // junctions / position runs found (whatever the limit)
     u32 P;         // pairs the pipeline works on: n_pairs, or 0 after an overflow
     u32 J, R;      // junctions / runs the pipeline works on
-    u32 n_slots;   // J + ceil(P / 64) fragment slots
+    u32 n_slots;   // fragment slots: J + the ranges of the sorted pair array (frag_slots)
     u32 overflow;  // OVF_*
     u32 n_cand;    // K2d: keys in the candidate list (every junction at least once, few of them more often)
     u32 n_slices;  // ceil(P / 64): 64-pair slices of the sorted pair array (fragments, run masks)
@@ -82,6 +82,32 @@ struct ContigStats {
                    // only where that can reach a neighbouring intron (window_reach).  All-ones: pjb_set_option("window_skip", 0), list them all
 };
 static_assert(sizeof(ContigStats) == 112, "ContigStats layout");
+
+// The fragment rule (k4_pairs writes the slots, k5_frag_reduce folds them).  A RANGE is 2^range_shift consecutive 64-pair slices of the
+// sorted pair array (pjb_set_option("pair_range", n)); a fragment is a maximal run of one junction inside one range.  Ids ascend along the
+// array in steps of 0 or 1 and every id occurs, so id + range index is unique and strictly increasing from fragment to fragment: that is
+// the fragment's slot.  One slot is skipped where a junction begins exactly at a range's start, and the last slot is never reached; whoever
+// sees either marks it unused (frag_j = -1), nothing is initialised.  Host and device, values in, values out: tests/cpp/pair_range_slots.cc.
+constexpr int PAIR_RANGE_SHIFT_MAX = 5; // 32 slices, 2 048 pairs a range
+constexpr int PAIR_RANGE_SHIFT_DEFAULT = 3;
+__host__ __device__ inline u32 frag_ranges(u32 n_pairs, int range_shift) { // ranges that hold a pair
+    return (u32)(((u64)n_pairs + ((u64)64 << range_shift) - 1) >> (6 + range_shift));
+}
+__host__ __device__ inline u32 frag_slot(u32 jid, u32 pair, int range_shift) { return jid + (pair >> (6 + range_shift)); }
+__host__ __device__ inline u32 frag_slots(u32 n_junc, u32 n_pairs, int range_shift) { return n_junc + frag_ranges(n_pairs, range_shift); }
+// the slot a pair leaves unused: the one before its own if it begins both a junction and a range (never the array's first pair), the one
+// behind its own if it is the array's last pair; -1: none
+__host__ __device__ inline int64_t frag_unused_before(u32 jid, u32 pair, bool junction_head, int range_shift) {
+    const bool range_head = (pair & (((u32)64 << range_shift) - 1u)) == 0;
+    return pair != 0 && range_head && junction_head ? (int64_t)frag_slot(jid, pair, range_shift) - 1 : -1;
+}
+__host__ __device__ inline int64_t frag_unused_behind(u32 jid, u32 pair, u32 n_pairs, int range_shift) {
+    return pair + 1 == n_pairs ? (int64_t)frag_slot(jid, pair, range_shift) + 1 : -1;
+}
+// room for the slots of any chain within its limits (one to spare: the grids that follow it divide it up)
+__host__ __device__ inline u32 frag_slots_limit(u32 junc_limit, u32 pair_limit, int range_shift) {
+    return frag_slots(junc_limit, pair_limit, range_shift) + 1;
+}
 // A closed read [S] B (N B)+ [S]: can some junction's window reach over the intron before / behind the block of `blk` reference positions
 // that lies between two of its introns (nl_prev, nl_next long)?  k4b_generic's tests: prev_istart >= anc_l[j], where prev_istart = istart -
 // blk - nl_prev and anc_l[j] >= istart - B; next_iend + 1 <= anc_r[j], where next_iend = iend + blk + nl_next and anc_r[j] <= iend + B.
@@ -359,15 +385,17 @@ struct DppMin {
     __device__ __forceinline__ static u32 op(u32 a, u32 b) { return a < b ? a : b; }
 };
 template <typename Op>
-__device__ __forceinline__ u32 wave_total(u32 v) {
+__device__ __forceinline__ u32 wave_fold(u32 v) { // the result where the steps leave it: in lane 63 (the other lanes: partial results)
     v = Op::op(v, dpp_move<0xB1, 0xf>(Op::ident, v));  // quad_perm [1,0,3,2]
     v = Op::op(v, dpp_move<0x4E, 0xf>(Op::ident, v));  // quad_perm [2,3,0,1]
     v = Op::op(v, dpp_move<0x141, 0xf>(Op::ident, v)); // row_half_mirror
     v = Op::op(v, dpp_move<0x140, 0xf>(Op::ident, v)); // row_mirror: every lane of a row holds the row's result
     v = Op::op(v, dpp_move<0x142, 0xa>(Op::ident, v)); // row_bcast:15 into rows 1 and 3
     v = Op::op(v, dpp_move<0x143, 0xc>(Op::ident, v)); // row_bcast:31 into rows 2 and 3
-    return (u32)__builtin_amdgcn_readlane((int)v, 63);
+    return v;
 }
+template <typename Op>
+__device__ __forceinline__ u32 wave_total(u32 v) { return (u32)__builtin_amdgcn_readlane((int)wave_fold<Op>(v), 63); }
 
 // exclusive scan over the 256 threads of a block in thread order; returns exclusive prefix, total in *total.
 // smem: at least 4 elements of T.  Contains __syncthreads (call uniformly).

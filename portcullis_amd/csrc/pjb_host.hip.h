@@ -329,7 +329,9 @@ struct pjb_ctx {
     bool run_sort = true;             // pjb_set_option("run_sort", 0): dense ids through the radix passes.  Cleared by a chain whose tiles' ids do not
                                       // lie in a window (OVF_RUNS): the chains behind it plan the radix route themselves
     u32 run_window = 0;               // pjb_set_option("run_window", n): a tile's ids must span less than n (tests; 0: RUN_W)
-    u32 list_cap_forced = 0;          // pjb_set_option("list_cap", n): the read lists' first room (tests of the OVF_LISTS repeat)
+    int pair_range_shift = PAIR_RANGE_SHIFT_DEFAULT; // pjb_set_option("pair_range", n): n = 1 << shift slices of 64 sorted pairs a wavefront of k4_pairs
+                                      // folds into fragments (frag_slot); read when a chain is planned
+    u32 list_cap_forced = 0;         // pjb_set_option("list_cap", n): the read lists' first room (tests of the OVF_LISTS repeat)
     bool k1_serial = true;            // PJB_K1_SERIAL=0: the chains' K1 stages side by side
     hipEvent_t last_k1_ev = nullptr;  // the K1 stage of the chain queued last
     int k1s_blocks_forced = 0;                   // PJB_K1S_BLOCKS (tests): k1_scan_tiles on this many blocks -- 1: every tile in one block's rounds

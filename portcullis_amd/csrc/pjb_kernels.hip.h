@@ -2241,7 +2241,7 @@ __device__ __forceinline__ void anchors_fold(bool valid, u32 j, int32_t l, int32
 // contig -- if a limit was exceeded while the ids were built
 __global__ __launch_bounds__(256) void kd_table(const u64 *cand, const u64 *cand_anc, const u32 *cand_rank, KeyFmt kf, u32 junc_limit, const u32 *ends,
                                                 const u32 *first_id, const u64 *total, u64 *jkey, int32_t *anc_l, int32_t *anc_r, ContigStats *cs,
-                                                const u32 *gen_cnt, u32 gen_cap, u32 sort_limit, u32 *n_runs) {
+                                                const u32 *gen_cnt, u32 gen_cap, u32 sort_limit, u32 *n_runs, int range_shift) {
     const u32 p = blockIdx.x * 256 + threadIdx.x;
     if (blockIdx.x == 0) { // (the read lists: every sub-list within its room?)
         static_assert(GEN_SHARDS == 256, "a shard per thread of the first block");
@@ -2265,7 +2265,7 @@ __global__ __launch_bounds__(256) void kd_table(const u64 *cand, const u64 *cand
             const u32 n_pairs = cs->P;
             cs->n_junc = cs->J = (u32)J;
             cs->n_slices = (n_pairs + 63) / 64;
-            cs->n_slots = (u32)J + (n_pairs + 63) / 64;
+            cs->n_slots = frag_slots((u32)J, n_pairs, range_shift);
         }
     }
     const u32 n = cs->n_cand;
@@ -2896,7 +2896,8 @@ struct HeadSink {
         if ((u32)v) run_start[r] = (u32)i;
     }
 };
-__global__ void k2_close(u64 *total, u32 *seg_off, u32 *run_first, u32 *run_start, ContigStats *cs, u32 junc_limit, const u32 *gen_cnt, u32 gen_cap) {
+__global__ void k2_close(u64 *total, u32 *seg_off, u32 *run_first, u32 *run_start, ContigStats *cs, u32 junc_limit, const u32 *gen_cnt, u32 gen_cap,
+                         int range_shift) {
     const u32 n_pairs = cs->P;
     if (n_pairs == 0) return;
     {
@@ -2922,7 +2923,7 @@ __global__ void k2_close(u64 *total, u32 *seg_off, u32 *run_first, u32 *run_star
     run_start[R] = n_pairs;
     cs->J = J;
     cs->R = R;
-    cs->n_slots = J + (n_pairs + 63) / 64;
+    cs->n_slots = frag_slots(J, n_pairs, range_shift);
 }
 
 // K2s for the chain on dense ids: k4_pairs left two bits per sorted pair (junction starts / position run starts), a scan over the
@@ -3321,195 +3322,241 @@ __global__ __launch_bounds__(256) void k4b_generic(const u64 *list, const u32 *g
     } // items
 }
 
-// K4: gather the pairs in sorted order -- one 32-byte record each -- and fold predicates and match statistics to fragment
-// heads with a segmented wave reduction (junction.cc:862-909 accumulators, :755-814 counters).
-// Fragments.  The sorted pair array is processed in fixed 64-pair slices (one wavefront each).  A fragment is a maximal
-// run of one junction inside one slice; its slot is jid + slice index, which is unique and increasing along the array.
-// A slot is skipped when a junction starts exactly on a slice boundary, and the very last slot is never used: the
-// wavefront that sees either marks the slot unused (frag_j = -1) itself, so nothing has to be initialised.
-// A second small kernel reduces slots -> junctions (segmented again, then one atomic per wave and junction), so a
-// junction with 10^6 pairs costs ~250 same-address atomics, not 10^6.
-// masks (nullptr: the chain that sorted the full keys has its runs from the head scan): per 64-pair slice, the lanes where a
-// junction starts and the lanes where a run of equal read positions starts (entropy, junction.cc:730-749) -- this kernel holds
-// every pair's record anyway, k2_expand turns the bits into seg_off / run_first / run_start without touching a pair.
-__global__ __launch_bounds__(256) void k4_pairs(const u32 *sidx, const u32 *jid_of, const PairRec *rec, const u64 *jkey, KeyFmt kf, const u32 *np,
-                                                 u32 *frag, int32_t *frag_j, u64 *head_mask, u64 *run_mask, const ContigStats *cs_chk, u64 *err_chk) {
-    const u32 n = *np;
-    if (blockIdx.x * 256u >= n) return;
-    const u32 i = blockIdx.x * 256 + threadIdx.x;
-    const bool valid = i < n;
-    const int lane = lane_id();
-    const u32 ic = valid ? i : n - 1; // (loads unconditional, masked after: see k1_count)
-    const u32 p = sidx[ic];
-    const u32 jv = jid_of[ic];
-#ifdef PJB_SELFCHECK // (debug builds: what the sort hands over must be a permutation of the pairs with ids below J that ascend in steps of 0 or 1)
-    {
-        const u32 Jc = cs_chk->J;
-        const u32 jb = ic ? jid_of[ic - 1] : jv;
-        int bad = 0;
-        if (p >= n) bad = 1;
-        else if (jv >= Jc) bad = 2;
-        else if (jv != jb && jv != jb + 1) bad = 3;
-        else if (ic == 0 && jv != 0) bad = 4;
-        else if (ic == n - 1 && jv != Jc - 1) bad = 5;
-        else if (jv + (ic >> 6) + 1 >= cs_chk->n_slots) bad = 6;
-        else if ((ic >> 6) >= cs_chk->n_slices) bad = 7;
-        else if (cs_chk->n_slots != Jc + (n + 63) / 64) bad = 8;
-        if (__ballot(bad != 0)) {
-            if (bad) set_error(err_chk, 0xffffe000u + (u32)bad, PJB_ERR_HIP);
-            return;
-        }
-    }
-#endif
-    const PairRec Rc = rec_load(rec + p);
-    const u64 jk = jkey[jv];
-    // the pair before this one in sorted order: the neighbouring lane's -- lane 0 fetches it
-    u32 jprev_v = __shfl_up(jv, 1, 64);
-    int32_t pos_prev = __shfl_up(Rc.pos, 1, 64), aend_prev = __shfl_up(Rc.aend, 1, 64);
-    if (lane == 0 && valid && i > 0) { // (valid: a wavefront past the end must not follow whatever lies behind the sorted indices)
-        jprev_v = jid_of[i - 1];
-        const uint4 q = reinterpret_cast<const uint4 *>(rec + sidx[i - 1])[1];
-        pos_prev = (int32_t)q.x;
-        aend_prev = (int32_t)q.y;
-    }
-    u32 j = 0xffffffffu;
-    u32 cnt[4] = {0, 0, 0, 0}, jadp[5] = {0, 0, 0, 0, 0}, mx[5] = {0, 0, 0, 0, 0};
-    u32 first_mis = 100000000u; // junction.cc:864
-    u64 mism64 = 0;
-    if (valid) {
-        j = jv;
-        int32_t istart, iend;
-        unpack_key(kf, jk, istart, iend);
-        const u64 rs = Rc.aux;
-        const u32 minMatch = (u32)(rs & 0xfffffu), mmes = (u32)((rs >> 20) & 0xfffffu), nbMis = (u32)(rs >> 40);
-        const u32 meta = Rc.meta;
-        const u32 cat = meta & META_CAT_MASK;
-        const u32 xs = (meta >> META_XS_SHIFT) & 3u;
-        // distinct alignment runs in BAM order (junction.cc:763-771): compare with the previous pair of the junction
-        const bool dist_head = i == 0 || jprev_v != j || pos_prev != Rc.pos || aend_prev != Rc.aend;
-        // 8-bit lanes: a wavefront adds at most 64 per field
-        cnt[0] = 1u | ((u32)(cat == 0) << 8) | ((u32)(cat == 1) << 16) | ((u32)(cat == 2) << 24);
-        cnt[1] = (u32)(cat == 3) | ((u32)((meta & META_MULTI) != 0) << 8) | ((u32)(xs == 1) << 16) | ((u32)(xs == 2) << 24);
-        cnt[2] = (u32)((meta & META_UM) != 0) | ((u32)((meta & META_BPP) != 0) << 8) | ((u32)((meta & META_PPP) != 0) << 16) |
-                 ((u32)((meta & META_REL) != 0) << 24);
-        cnt[3] = (u32)dist_head;
-#pragma unroll
-        for (int w = 0; w < 5; w++) // junction.cc:875-877: JAD[k]++ for k < min(20, minMatch)
-            jadp[w] = (u32)((u32)(4 * w) < minMatch) | ((u32)((u32)(4 * w + 1) < minMatch) << 8) |
-                      ((u32)((u32)(4 * w + 2) < minMatch) << 16) | ((u32)((u32)(4 * w + 3) < minMatch) << 24);
-        const int32_t la = istart - Rc.lstart, ra = Rc.rend - iend; // Intron::minAnchorLength intron.cc:81-83
-        mx[0] = (u32)(la < ra ? la : ra);
-        mx[1] = Rc.updown & 0xffffu;
-        mx[2] = Rc.updown >> 16;
-        mx[3] = mmes;
-        mx[4] = minMatch;
-        first_mis = minMatch > 0 ? minMatch : 100000000u;
-        mism64 = nbMis;
-        // unused fragment slots: the one skipped when a junction starts on a slice boundary, and the last one
-        if (lane == 0 && i > 0 && jprev_v != j) frag_j[j + (i >> 6) - 1] = -1;
-        if (i == n - 1) frag_j[j + (i >> 6) + 1] = -1;
-    }
-    if (head_mask) {
-        const bool hj = valid && (i == 0 || jprev_v != j);
-        const bool hr = valid && (hj || pos_prev != Rc.pos);
-        const u64 mj = __ballot(hj), mr = __ballot(hr);
-        if (lane == 0 && i < n) { // (a wavefront wholly past the end has no slice: the arrays hold ceil(n / 64) words)
-            head_mask[i >> 6] = mj;
-            run_mask[i >> 6] = mr;
-        }
-    }
-    auto store_fragment = [&](u32 hi_word) {
-        const u32 slot = j + (i >> 6);
-        u32 vals[F_WORDS];
-#pragma unroll
-        for (int k = 0; k < F_WORDS; k++) vals[k] = 0;
-        // a full wavefront of one junction makes the first field 64: it still fits its byte (max 64 < 256)
-#pragma unroll
-        for (int k = 0; k < 13; k++) vals[F_N + k] = (cnt[k >> 2] >> (8 * (k & 3))) & 0xffu;
-        vals[F_MAXMINANC] = mx[0];
-        vals[F_UP] = mx[1];
-        vals[F_DOWN] = mx[2];
-        vals[F_MAXMMES] = mx[3];
-        vals[F_MAXMINMATCH] = mx[4];
-        vals[F_FIRSTMIS] = first_mis;
-        vals[F_MISM_LO] = (u32)mism64;
-        vals[F_MISM_HI] = hi_word;
-#pragma unroll
-        for (int k = 0; k < 20; k++) vals[F_JAD0 + k] = (jadp[k >> 2] >> (8 * (k & 3))) & 0xffu;
-        uint4 *dst = reinterpret_cast<uint4 *>(frag + (size_t)slot * F_WORDS);
-#pragma unroll
-        for (int k = 0; k < F_WORDS / 4; k++) dst[k] = make_uint4(vals[4 * k], vals[4 * k + 1], vals[4 * k + 2], vals[4 * k + 3]);
-        frag_j[slot] = (int32_t)j;
-    };
-    // ---- a wavefront that holds pairs of ONE junction (the usual case: a junction has a few hundred pairs): plain
-    // whole-wave reductions on the DPP path, 16 x 6 VALU steps instead of 115 ds_bpermute round trips
-    const u32 j0 = (u32)__builtin_amdgcn_readfirstlane((int)j);
-    if (__ballot(valid && j != j0) == 0) {
-#pragma unroll
-        for (int w = 0; w < 4; w++) cnt[w] = wave_total<DppAdd>(cnt[w]);
-#pragma unroll
-        for (int w = 0; w < 5; w++) jadp[w] = wave_total<DppAdd>(jadp[w]);
-#pragma unroll
-        for (int w = 0; w < 5; w++) mx[w] = wave_total<DppMax>(mx[w]);
-        first_mis = wave_total<DppMin>(first_mis);
-        // (a pair has fewer than 2^24 mismatches: 64 of them fit 32 bits)
-        mism64 = (u64)wave_total<DppAdd>((u32)mism64);
-        if (valid && lane == 0) store_fragment(0u);
-        return;
-    }
-    // ---- several junctions in the wavefront: segmented wave reduce to fragment heads; the "same junction at distance
-    // o" tests are done once
-    u32 take = 0;
-#pragma unroll
-    for (int sft = 0; sft < 6; sft++) {
-        const int o = 1 << sft;
-        const u32 kk = __shfl_down(j, o, 64);
-        if (lane + o < 64 && kk == j) take |= 1u << sft;
-    }
-    auto red_add = [&](u32 v) {
-#pragma unroll
-        for (int sft = 0; sft < 6; sft++) {
-            const u32 t = __shfl_down(v, 1 << sft, 64);
-            if ((take >> sft) & 1u) v += t;
-        }
-        return v;
-    };
-    auto red_max = [&](u32 v) {
-#pragma unroll
-        for (int sft = 0; sft < 6; sft++) {
-            const u32 t = __shfl_down(v, 1 << sft, 64);
-            if (((take >> sft) & 1u) && t > v) v = t;
-        }
-        return v;
-    };
-#pragma unroll
-    for (int w = 0; w < 4; w++) cnt[w] = red_add(cnt[w]);
-#pragma unroll
-    for (int w = 0; w < 5; w++) jadp[w] = red_add(jadp[w]);
-#pragma unroll
-    for (int w = 0; w < 5; w++) mx[w] = red_max(mx[w]);
-#pragma unroll
-    for (int sft = 0; sft < 6; sft++) {
-        const u32 t = __shfl_down(first_mis, 1 << sft, 64);
-        const u64 t64 = __shfl_down(mism64, 1 << sft, 64);
-        if ((take >> sft) & 1u) {
-            first_mis = t < first_mis ? t : first_mis;
-            mism64 += t64;
-        }
-    }
-    const u32 jprev = __shfl_up(j, 1, 64);
-    if (valid && (lane == 0 || jprev != j)) store_fragment((u32)(mism64 >> 32));
-}
-
-// K5a: fragment slots -> junction accumulators (acc pre-initialised: sums 0, max 0, min 100000000).
-// One wavefront walks 64 consecutive slots; lane k owns word k of the 48-word record, so every
-// load is one coalesced 192-byte row and a junction's run of slots is folded in registers; the run
-// is flushed with one atomic per word when the junction changes (same-address chain <= P_j/4096).
+// how two values of word k of a fragment record combine (k4_pairs over a range's slices, k5_frag_reduce over a junction's fragments)
 __device__ __forceinline__ u32 frag_combine(int k, u32 a, u32 b) {
     if (k >= F_MAXMINANC && k <= F_MAXMINMATCH) return a > b ? a : b;
     if (k == F_FIRSTMIS) return a < b ? a : b;
     return a + b; // sums; F_MISM_LO/HI are handled as one 64-bit add by the caller
 }
+// A slice's totals for one junction, from the lane that holds them to one word of the fragment record a lane: the sixteen words (13 + 20
+// byte counters packed in nine, five maxima, the minimum, a zero) go through the wavefront's own 64 bytes of LDS, and lane k reads the one
+// its field lies in.  (Selecting among sixteen registers by lane number costs 30 compares whose masks the compiler keeps in SGPRs: the
+// kernel then spills.)  Wavefront-local: no barrier, the LDS unit serves a wavefront's instructions in order.
+// the sixteen words in LDS order: the four words of the first thirteen counters | the maxima | the last maximum, the minimum, the first
+// two words of the twenty JAD counters | their other three, a zero
+enum { FW_CNT = 0, FW_MAX = 4, FW_MIN = 9, FW_JAD = 10 };
+struct FragWordOf {
+    u32 word, shift, mask; // of lane k's field: the word among the sixteen, the byte's shift in it, all-ones / 0xff / 0 (no field)
+    __device__ __forceinline__ explicit FragWordOf(int k) {
+        const bool c = k <= F_DIST, a = k >= F_JAD0 && k < F_JAD0 + 20, m = k >= F_MAXMINANC && k <= F_FIRSTMIS;
+        const int q = a ? k - F_JAD0 : k;
+        word = c ? FW_CNT + (u32)(q >> 2) : a ? FW_JAD + (u32)(q >> 2) : m ? FW_MAX + (u32)(k - F_MAXMINANC) : 15u;
+        shift = c || a ? 8u * (u32)(q & 3) : 0u;
+        mask = c || a ? 0xffu : m ? 0xffffffffu : 0u;
+    }
+    // four of the sixteen words at a time, as soon as they are folded (all sixteen results held back at once cost sixteen registers)
+    __device__ __forceinline__ static void put(u32 *tot, int quad, bool holder, u32 a, u32 b, u32 c, u32 d) {
+        if (holder) reinterpret_cast<uint4 *>(tot)[quad] = make_uint4(a, b, c, d);
+        __builtin_amdgcn_sched_barrier(0);
+    }
+    __device__ __forceinline__ u32 get(const u32 *tot) const {
+        __builtin_amdgcn_wave_barrier();
+        const u32 w = (tot[word] >> shift) & mask;
+        __builtin_amdgcn_wave_barrier();
+        return w;
+    }
+};
+
+// K4: gather the pairs in sorted order -- one 32-byte record each -- and fold predicates and match statistics to fragments
+// (junction.cc:862-909 accumulators, :755-814 counters).
+// Fragments.  A wavefront owns a RANGE of 2^range_shift consecutive 64-pair slices of the sorted pair array and walks them in order.  A
+// fragment is a maximal run of one junction inside one range; its slot is jid + range index (frag_slot, pjb_device.hip.h, with the rule
+// for the slots that stay unused).  Per slice the 33 counters are folded in packed 8-bit form -- whole-wave reductions on the DPP path
+// where the slice holds one junction, a segmented reduce otherwise --; the fragment that is open across slices lives one word a lane
+// (lane k: word k, k5_frag_reduce's layout), takes each slice's totals with frag_combine and leaves with one coalesced 192-byte store
+// when its junction or the range ends.  While a slice is folded the next one's records and keys and the indices of the one after are on
+// their way; the pair before a slice is lane 63 of the slice before -- only a range's first slice fetches it.
+// A second small kernel reduces slots -> junctions (segmented again, then one atomic per wave and junction), so a
+// junction with 10^6 pairs costs a few dozen same-address atomics, not 10^6.
+// masks (nullptr: the chain that sorted the full keys has its runs from the head scan): per 64-pair slice, the lanes where a
+// junction starts and the lanes where a run of equal read positions starts (entropy, junction.cc:730-749) -- this kernel holds
+// every pair's record anyway, k2_expand turns the bits into seg_off / run_first / run_start without touching a pair.
+__global__ __launch_bounds__(256) void k4_pairs(const u32 *sidx, const u32 *jid_of, const PairRec *rec, const u64 *jkey, KeyFmt kf, const u32 *np,
+                                                 u32 *frag, int32_t *frag_j, u64 *head_mask, u64 *run_mask, const ContigStats *cs_chk, u64 *err_chk,
+                                                 int range_shift) {
+    __shared__ __attribute__((aligned(16))) u32 s_tot[4][16];
+    const u32 n = *np;
+    const int lane = lane_id();
+    const u32 wave = (u32)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)); // (in an SGPR: the range, its loop and its branches are scalar)
+    const u32 range = blockIdx.x * 4 + wave;
+    u32 *tot = s_tot[wave];
+    const FragWordOf word_of(lane);
+    const u64 first = (u64)range << (6 + range_shift);
+    if (first >= n) return;
+    const u32 i0 = (u32)first;
+    const u32 n_sl = min(1u << range_shift, (n - i0 + 63) >> 6); // slices of this range that hold a pair
+    // (loads unconditional, index clamped to n - 1, masked after: see k1_count.  Nothing behind the pairs is touched.)
+    // (32 bits do: n <= 0xffffff00 and at() is asked for the slice behind the range's last at the most)
+    auto at = [&](u32 s) { return min(i0 + 64u * s + (u32)lane, n - 1); };
+    auto key_of = [&](u32 jl) { // a slice of one junction (most are) asks for its key once
+        const u32 jf = (u32)__builtin_amdgcn_readfirstlane((int)jl);
+        return __ballot(jl != jf) == 0 ? jkey[jf] : jkey[jl];
+    };
+    u32 jv = jid_of[at(0)];
+    const u32 p0 = sidx[at(0)];
+    u32 j_nx = jid_of[at(1)], p_nx = sidx[at(1)];
+    // the pair before the range: j, pos, aend of the last pair a slice saw go to the next one's lane 0
+    u32 jprev_c = 0xffffffffu;
+    int32_t pos_c = 0, aend_c = 0;
+    if (i0 > 0) {
+        jprev_c = jid_of[i0 - 1];
+        const uint4 q = reinterpret_cast<const uint4 *>(rec + sidx[i0 - 1])[1];
+        pos_c = (int32_t)q.x;
+        aend_c = (int32_t)q.y;
+    }
+    PairRec Rc = rec_load(rec + p0);
+    u64 jk = key_of(jv);
+    // the open fragment: its junction, word `lane` of its record, the 64-bit sum of F_MISM_LO / F_MISM_HI
+    u32 open_j = 0xffffffffu, fv = 0;
+    u64 fm = 0;
+    auto flush = [&]() {
+        if (open_j == 0xffffffffu) return;
+        const u32 slot = open_j + range;
+        if (lane < F_WORDS) frag[(size_t)slot * F_WORDS + lane] = lane == F_MISM_LO ? (u32)fm : lane == F_MISM_HI ? (u32)(fm >> 32) : fv;
+        if (lane == 0) frag_j[slot] = (int32_t)open_j;
+    };
+    auto absorb = [&](u32 jh, u32 w, u64 m64) { // a slice's totals for junction jh (wave-uniform), this lane's word of them
+        if (jh != open_j) {
+            flush();
+            open_j = jh;
+            fv = w;
+            fm = m64;
+        } else {
+            fv = frag_combine(lane, fv, w);
+            fm += m64;
+        }
+    };
+    for (u32 s = 0; s < n_sl; s++) {
+        PairRec Rn = Rc;
+        u64 jkn = jk;
+        u32 j_n2 = j_nx, p_n2 = p_nx;
+        if (s + 1 < n_sl) {
+            Rn = rec_load(rec + p_nx);
+            jkn = key_of(j_nx);
+        }
+        if (s + 2 < n_sl) {
+            j_n2 = jid_of[at(s + 2)];
+            p_n2 = sidx[at(s + 2)];
+        }
+        const u32 i = i0 + 64u * s + (u32)lane; // (the slice's first pair lies below n <= 0xffffff00)
+        const bool valid = i < n;
+#ifdef PJB_SELFCHECK // (debug builds: what the sort hands over must be a permutation of the pairs with ids below J that ascend in steps of 0 or 1)
+        {
+            const u32 ic = valid ? i : n - 1;
+            const u32 Jc = cs_chk->J;
+            const u32 jb = ic ? jid_of[ic - 1] : jv;
+            int bad = 0;
+            if (sidx[ic] >= n) bad = 1;
+            else if (jv >= Jc) bad = 2;
+            else if (jv != jb && jv != jb + 1) bad = 3;
+            else if (ic == 0 && jv != 0) bad = 4;
+            else if (ic == n - 1 && jv != Jc - 1) bad = 5;
+            else if (frag_slot(jv, ic, range_shift) + 1 >= cs_chk->n_slots) bad = 6;
+            else if ((ic >> 6) >= cs_chk->n_slices) bad = 7;
+            else if (cs_chk->n_slots != frag_slots(Jc, n, range_shift)) bad = 8;
+            if (__ballot(bad != 0)) {
+                if (bad) set_error(err_chk, 0xffffe000u + (u32)bad, PJB_ERR_HIP);
+                return;
+            }
+        }
+#endif
+        // the pair before this one in sorted order: the neighbouring lane's -- lane 0 has it from the slice before
+        u32 jprev_v = __shfl_up(jv, 1, 64);
+        int32_t pos_prev = __shfl_up(Rc.pos, 1, 64), aend_prev = __shfl_up(Rc.aend, 1, 64);
+        if (lane == 0) {
+            jprev_v = jprev_c;
+            pos_prev = pos_c;
+            aend_prev = aend_c;
+        }
+        u32 j = 0xffffffffu;
+        u32 cnt[4] = {0, 0, 0, 0}, jadp[5] = {0, 0, 0, 0, 0}, mx[5] = {0, 0, 0, 0, 0};
+        u32 first_mis = 100000000u; // junction.cc:864
+        u32 nb_mis = 0;
+        if (valid) {
+            j = jv;
+            int32_t istart, iend;
+            unpack_key(kf, jk, istart, iend);
+            const u64 rs = Rc.aux;
+            const u32 minMatch = (u32)(rs & 0xfffffu), mmes = (u32)((rs >> 20) & 0xfffffu), nbMis = (u32)(rs >> 40);
+            const u32 meta = Rc.meta;
+            const u32 cat = meta & META_CAT_MASK;
+            const u32 xs = (meta >> META_XS_SHIFT) & 3u;
+            // distinct alignment runs in BAM order (junction.cc:763-771): compare with the previous pair of the junction
+            const bool dist_head = i == 0 || jprev_v != j || pos_prev != Rc.pos || aend_prev != Rc.aend;
+            // 8-bit lanes: a slice adds at most 64 per field
+            cnt[0] = 1u | ((u32)(cat == 0) << 8) | ((u32)(cat == 1) << 16) | ((u32)(cat == 2) << 24);
+            cnt[1] = (u32)(cat == 3) | ((u32)((meta & META_MULTI) != 0) << 8) | ((u32)(xs == 1) << 16) | ((u32)(xs == 2) << 24);
+            cnt[2] = (u32)((meta & META_UM) != 0) | ((u32)((meta & META_BPP) != 0) << 8) | ((u32)((meta & META_PPP) != 0) << 16) |
+                     ((u32)((meta & META_REL) != 0) << 24);
+            cnt[3] = (u32)dist_head;
+#pragma unroll
+            for (int w = 0; w < 5; w++) // junction.cc:875-877: JAD[k]++ for k < min(20, minMatch)
+                jadp[w] = (u32)((u32)(4 * w) < minMatch) | ((u32)((u32)(4 * w + 1) < minMatch) << 8) |
+                          ((u32)((u32)(4 * w + 2) < minMatch) << 16) | ((u32)((u32)(4 * w + 3) < minMatch) << 24);
+            const int32_t la = istart - Rc.lstart, ra = Rc.rend - iend; // Intron::minAnchorLength intron.cc:81-83
+            mx[0] = (u32)(la < ra ? la : ra);
+            mx[1] = Rc.updown & 0xffffu;
+            mx[2] = Rc.updown >> 16;
+            mx[3] = mmes;
+            mx[4] = minMatch;
+            first_mis = minMatch > 0 ? minMatch : 100000000u;
+            nb_mis = nbMis;
+            // unused fragment slots: the one skipped when a junction starts with the range, and the last one
+            if (s == 0 && lane == 0) {
+                const int64_t u = frag_unused_before(j, i, jprev_v != j, range_shift);
+                if (u >= 0) frag_j[u] = -1;
+            }
+            const int64_t u = frag_unused_behind(j, i, n, range_shift);
+            if (u >= 0) frag_j[u] = -1;
+        }
+        const bool hj = valid && (i == 0 || jprev_v != j);
+        if (head_mask) {
+            const bool hr = valid && (hj || pos_prev != Rc.pos);
+            const u64 mj = __ballot(hj), mr = __ballot(hr);
+            if (lane == 0) { // (a slice word per 64 pairs: the arrays hold ceil(n / 64) words, and s < n_sl)
+                head_mask[i >> 6] = mj;
+                run_mask[i >> 6] = mr;
+            }
+        }
+        // (a slice with a successor is full: lane 63 holds a pair)
+        jprev_c = (u32)__builtin_amdgcn_readlane((int)jv, 63);
+        pos_c = __builtin_amdgcn_readlane(Rc.pos, 63);
+        aend_c = __builtin_amdgcn_readlane(Rc.aend, 63);
+        // ---- the slice's segments -- one, usually: a junction has a few hundred pairs -- in order.  Lane 0 heads the first whether or
+        // not its junction began there: that one may continue the open fragment.  Each is folded by whole-wave reductions on the DPP
+        // path over its own lanes (16 x 6 VALU steps; the lanes outside contribute the identities, as the lanes past the end do);
+        // lane 63 ends up with the totals and hands them on.
+        u64 heads = __ballot(valid && (lane == 0 || jprev_v != j));
+        while (heads) {
+            const int h = __ffsll((unsigned long long)heads) - 1;
+            heads &= heads - 1;
+            const int e = heads ? __ffsll((unsigned long long)heads) - 1 : 64;
+            const bool in = lane >= h && lane < e;
+            const bool last = lane == 63;
+            auto add = [&](u32 v) { return wave_fold<DppAdd>(in ? v : 0u); };
+            auto top = [&](u32 v) { return wave_fold<DppMax>(in ? v : 0u); };
+            __builtin_amdgcn_wave_barrier(); // (the lanes' reads of the segment before are done)
+            FragWordOf::put(tot, FW_CNT / 4, last, add(cnt[0]), add(cnt[1]), add(cnt[2]), add(cnt[3]));
+            FragWordOf::put(tot, FW_MAX / 4, last, top(mx[0]), top(mx[1]), top(mx[2]), top(mx[3]));
+            FragWordOf::put(tot, 2, last, top(mx[4]), wave_fold<DppMin>(in ? first_mis : 100000000u), add(jadp[0]), add(jadp[1]));
+            FragWordOf::put(tot, 3, last, add(jadp[2]), add(jadp[3]), add(jadp[4]), 0u);
+            // (a pair has fewer than 2^24 mismatches: 64 of them fit 32 bits)
+            const u32 mis = wave_total<DppAdd>(in ? nb_mis : 0u);
+            absorb((u32)__builtin_amdgcn_readlane((int)j, h), word_of.get(tot), (u64)mis);
+        }
+        Rc = Rn;
+        jk = jkn;
+        jv = j_nx;
+        j_nx = j_n2;
+        p_nx = p_n2;
+    }
+    flush();
+}
+
+// K5a: fragment slots -> junction accumulators (acc pre-initialised: sums 0, max 0, min 100000000).
+// One wavefront walks FRAG_SLOTS_PER_WAVE consecutive slots; lane k owns word k of the 48-word record, so every
+// load is one coalesced 192-byte row and a junction's run of slots is folded in registers; the run
+// is flushed with one atomic per word when the junction changes.
 constexpr int FRAG_SLOTS_PER_WAVE = 16; // short per-wave chains keep enough wavefronts in flight
 __global__ __launch_bounds__(256) void k5_frag_reduce(const u32 *frag, const int32_t *frag_j, const u32 *n_slots_p, u32 *acc) {
     const u32 n_slots = *n_slots_p;
