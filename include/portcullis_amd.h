@@ -326,8 +326,55 @@ int pjb_plan_groups(const int32_t *ref_len, const int32_t *tids, int32_t n_tids,
  *   "sort_floor" 65536 (default): the sort's digits cover at least this many junction ids (and twice what the context's chains have
  *                had); n (test hook): a small floor, so that a chain with more junctions than planned for is repeated
  *   "list_cap"   0 (default): the kernels' read lists get the room the pair limit implies; n > 0 (test hook): the first attempt
- *                of every chain gets room for n entries per sub-list, so that the overflow-and-repeat path runs */
+ *                of every chain gets room for n entries per sub-list, so that the overflow-and-repeat path runs
+ *   "mem_limit"  0 (default): the context holds as much device memory as the runtime gives it; n > 0: an allocation that would take
+ *                pjb_memory.held beyond n bytes is treated exactly like a hipMalloc that failed (see pjb_memory_info) */
 int pjb_set_option(pjb_ctx *ctx, const char *name, int64_t value);
+
+/* The device memory this context holds, in bytes of capacity (what was allocated, not what is in use), category by category.  Every
+ * allocation of the context is counted, so `held` is exact and is the sum of the seven categories before it.
+ *
+ * When an allocation fails -- the runtime refuses it, or it would take `held` beyond `limit` -- the context first gives back what it
+ * holds without needing it: the buffers that were replaced by larger ones and wait for their release, the pooled slabs, the pooled
+ * stage buffers (no chain reads any of them), in that order and no more kinds than the request needs; then it asks once more; a slab
+ * or arena chunk that was asked for with room to spare is then asked for with exactly the bytes needed.  Only then does the call
+ * return PJB_ERR_NOMEM; pjb_last_error names the bytes wanted, `held` and `limit`.  (A request that the limit refuses and that all
+ * of the above would not make fit is refused at once, and the pools stay.)  One exception to that order: a slab of exactly the bytes
+ * needed leaves a target's records in one small allocation per array, so while another open target or a queued chain holds slabs --
+ * which collecting would return to the pool -- a slab request is refused BEFORE the exact size is tried.  The repeat of the refused
+ * call for the same target with nothing freed in between is then given the exact size (and fails again only if that does not fit
+ * either); the refusal is forgotten when the target is collected or released, by pjb_clear_rows and by pjb_set_refs.
+ *
+ * PJB_ERR_NOMEM from pjb_submit_batch, pjb_submit_bam, pjb_bam_begin and pjb_bam_end is RETRYABLE (pjb_bam_piece never returns it: it
+ * copies into the buffer pjb_bam_begin allocated, and an early inflate that finds no memory is left to pjb_bam_end).  The call leaves the
+ * target as it was before the call: no batch has been added, and what the call took from the target's slabs has gone back (bytes to the
+ * target's earlier slabs, slabs to the pool they came from or to the device).  pjb_memory_info reads as before the call, with two
+ * exceptions: what the release described above gave back is gone from `slabs_pooled`, `staging` and `scratch`, and a scratch buffer
+ * the call had enlarged before it failed stays enlarged (the repeat needs it).  For pjb_bam_end the staged pieces and a finished
+ * inflate stay: the same call can be repeated, no piece is sent again.  Free memory in between -- collect a queued chain
+ * (pjb_finish_contig_end / _group_end give the chain's slabs back to the pool), raise the limit -- and repeat the call; when nothing
+ * is left to free, repeat it once more: that repeat is the one that may take exact-size slabs (above), and its PJB_ERR_NOMEM is
+ * final.  Any other error of pjb_bam_piece / pjb_bam_end releases the stage as before; a
+ * stage that is never picked up again is released by pjb_destroy.  PJB_ERR_NOMEM from any other call (a genome upload, a chain that
+ * cannot get its scratch) is final for that call's target.
+ *   pjb_memory_info reads hipMemGetInfo on the context's device and leaves the calling thread's current device as it found it. */
+typedef struct pjb_memory {
+    uint64_t genomes;      /* bases and codes of the uploaded targets, and those kept for the next upload */
+    uint64_t slabs_open;   /* the records of targets that have not been collected yet */
+    uint64_t slabs_pooled; /* slabs of collected targets, kept for the next target */
+    uint64_t staging;      /* pjb_bam_*: staged BGZF bytes, inflated bytes and tables, in use and pooled */
+    uint64_t scratch;      /* the chains' and the ingest's working buffers, those waiting for their release included */
+    uint64_t rows;         /* the row table */
+    uint64_t other;        /* PJB_FLAG_EXTRA arenas and vectors, bamfilt's junction keys */
+    uint64_t held;         /* the sum of the above */
+    uint64_t limit;        /* pjb_set_option("mem_limit", n); 0: none */
+    uint64_t peak_held;    /* the largest `held` since pjb_create or the last pjb_clear_rows */
+    uint64_t peak_records; /* slabs_open + slabs_pooled at the moment peak_held was reached */
+    uint64_t largest_target_bytes; /* the most slab capacity one target has held when it was collected, since pjb_create or the last */
+    int64_t largest_target;        /* pjb_clear_rows, and that target (-1: none collected yet) */
+    uint64_t hip_free, hip_total; /* hipMemGetInfo now: the whole device, other contexts and processes included */
+} pjb_memory;
+int pjb_memory_info(const pjb_ctx *ctx, pjb_memory *out);
 
 /* All rows built so far, contig by contig in finish order, (start,end)-sorted
  * within a contig.  The pointer stays valid until the next finish/clear/destroy. */

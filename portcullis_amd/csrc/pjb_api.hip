@@ -198,15 +198,14 @@ void pjb_destroy(pjb_ctx *c) {
     while (!c->open.empty()) close_contig(c, c->open.begin()->first);
     extra_clear(c);
     for (auto &kv : c->filter_keys)
-        if (kv.second.first) (void)hipFree(kv.second.first);
+        if (kv.second.first) (void)dev_free(c, kv.second.first);
     c->filter_keys.clear();
-    for (auto &g : c->contigs) free_contig(g);
-    for (auto &b : c->genome_pool) release(b);
+    for (auto &g : c->contigs) free_contig(c, g);
+    for (auto &b : c->genome_pool) release(c, b);
     c->genome_pool.clear();
-    for (auto &sl : c->slab_pool)
-        if (sl.p) (void)hipFree(sl.p);
+    release_pooled_slabs(c);
     if (c->rows_pinned) (void)hipHostFree(c->rows_pinned);
-    if (c->rows_table) (void)hipFree(c->rows_table);
+    if (c->rows_table) (void)dev_free(c, c->rows_table);
     bam_stage_clear(c);
     for (int k = 0; k < PJB_MAX_QUEUED; k++) {
         CtlSlot &S = c->sl[k];
@@ -220,7 +219,7 @@ void pjb_destroy(pjb_ctx *c) {
                      &S.rec, &S.jidbam, &S.jkey, &S.total, &S.bitmap, &S.wrank, &S.pagecnt, &S.pagerank, &S.ends, &S.firstid,
                      &S.key[0], &S.key[1], &S.idx[0], &S.idx[1], &S.hist, &S.hist_scan, &S.hist_part, &S.bintotal, &S.scan_tiles, &S.jid, &S.seg, &S.runfirst,
                      &S.runstart, &S.ent, &S.entsum, &S.frag, &S.fragj, &S.masks, &S.acc, &S.ancl, &S.ancr, &S.genlist, &S.runs};
-        for (Buf *b : sb) release(*b);
+        for (Buf *b : sb) release(c, *b);
         hipEvent_t evs[] = {S.ev_k1, S.ev_xk1, S.ev_fork, S.ev_join, S.ev_fork2, S.ev_join2};
         for (hipEvent_t e : evs)
             if (e) (void)hipEventDestroy(e);
@@ -237,9 +236,9 @@ void pjb_destroy(pjb_ctx *c) {
                   &c->x_pos, &c->x_endx, &c->x_q, &c->x_prefq, &c->x_ce, &c->x_bound, &c->x_de, &c->x_dropped, &c->x_zlist, &c->x_cnt,
                   &c->x_tabk, &c->x_tabc, &c->x_rs, &c->x_re, &c->x_rr, &c->x_tileoff, &c->x_xrall, &c->x_tab,
                   &c->b_dfl_in, &c->b_dfl_sym, &c->b_dfl_slots, &c->b_dfl_size, &c->b_dfl_off, &c->b_dfl_packed};
-    for (Buf *b : all) release(*b);
-    c->model.release_all();
-    for (auto &ch : c->xarena.chunks) (void)hipFree(ch.p);
+    for (Buf *b : all) release(c, *b);
+    c->model.release_all(c);
+    for (auto &ch : c->xarena.chunks) (void)dev_free(c, ch.p);
     if (c->xrows_pinned) (void)hipHostFree(c->xrows_pinned);
     for (auto &pool : c->pools)
         for (auto &ev : pool.ev) (void)hipEventDestroy(ev);
@@ -259,7 +258,8 @@ int pjb_set_refs(pjb_ctx *c, int32_t n_refs, const int32_t *ref_len) {
     if (!c) return PJB_ERR_ARG;
     if (n_refs < 0 || (n_refs > 0 && !ref_len)) return fail(c, PJB_ERR_ARG, "pjb_set_refs: bad arguments");
     if (!c->open.empty()) return fail(c, PJB_ERR_STATE, "pjb_set_refs: contig %d is still open", c->open.begin()->first);
-    for (auto &g : c->contigs) free_contig(g);
+    for (auto &g : c->contigs) free_contig(c, g);
+    c->slab_refused_tid = -1;
     c->ref_len.assign(ref_len, ref_len + n_refs);
     c->contigs.assign((size_t)n_refs, Contig());
     return PJB_OK;
@@ -293,9 +293,9 @@ static int upload_common(pjb_ctx *c, int32_t tid, uint8_t *d, int64_t len, bool 
     const size_t c2_words = len > 0 && !no_seq2 ? (size_t)codes2_alloc_words(len) : 0;
     if (len > 0) {
         const double ta = wall_now();
-        codes = (u32 *)genome_take(c->genome_pool, (c2_at + c2_words) * 4, codes_cap);
+        codes = (u32 *)genome_take(c, (c2_at + c2_words) * 4, codes_cap);
         t_alloc = wall_now() - ta;
-        if (!codes) return fail(c, PJB_ERR_NOMEM, "hipMalloc(genome codes, %zu bytes) failed", (c2_at + c2_words) * 4);
+        if (!codes) return nomem(c, "genome codes", (c2_at + c2_words) * 4);
         (void)hipMemsetAsync(codes + n_words, 0, 8, c->stream);
         hipLaunchKernelGGL(k0_encode, dim3((unsigned)((n_words + 255) / 256)), dim3(256), 0, c->stream, (const uint8_t *)d, len,
                            codes, n_words, d_flags + 1);
@@ -316,24 +316,24 @@ static int upload_common(pjb_ctx *c, int32_t tid, uint8_t *d, int64_t len, bool 
     const double t_sync0 = wall_now();
     hipError_t se = hipStreamSynchronize(c->stream);
     if (se != hipSuccess) {
-        if (codes) (void)hipFree(codes);
+        if (codes) (void)dev_free(c, codes);
         return fail(c, PJB_ERR_HIP, "upload: %s", hipGetErrorString(se));
     }
     if (prof)
         fprintf(stderr, "[host profile] genome tid %d (%lld bases): codes allocation %.4f, launches %.4f, wait for the stream %.4f s\n", tid, (long long)len, t_alloc,
                 t_sync0 - t_up0 - t_alloc, wall_now() - t_sync0);
     if (fasta_flag && flags[3]) { // (the bytes were not a FASTA record of that geometry: nothing of this upload is kept)
-        if (codes) (void)hipFree(codes);
+        if (codes) (void)dev_free(c, codes);
         return 1;
     }
     const int hx = flags[0], exotic = flags[1], any_exc = codes2 ? flags[2] : 1;
     if (exotic && codes) {
-        (void)hipFree(codes);
+        (void)dev_free(c, codes);
         codes = nullptr;
         codes2 = nullptr;
     }
     Contig &g = c->contigs[(size_t)tid];
-    free_contig(g, &c->genome_pool);
+    free_contig(c, g, true);
     g.d = d;
     g.len = len;
     g.owned = owned;
@@ -353,8 +353,8 @@ int pjb_upload_contig(pjb_ctx *c, int32_t tid, const uint8_t *bases, int64_t len
         return fail(c, PJB_ERR_ARG, "pjb_upload_contig: bad arguments (tid %d)", tid);
     HIP_TRY(c, hipSetDevice(c->cfg.device));
     size_t d_cap = 0;
-    uint8_t *d = (uint8_t *)genome_take(c->genome_pool, (size_t)std::max<int64_t>(len, 16), d_cap);
-    if (!d) return fail(c, PJB_ERR_NOMEM, "hipMalloc(genome %lld) failed", (long long)len);
+    uint8_t *d = (uint8_t *)genome_take(c, (size_t)std::max<int64_t>(len, 16), d_cap);
+    if (!d) return nomem(c, "genome", (size_t)std::max<int64_t>(len, 16));
     hipError_t e = hipSuccess;
     // through the page-locked staging buffers in 32 MiB pieces (a pageable hipMemcpy is several times slower)
     const size_t PIECE = (size_t)32 << 20;
@@ -370,7 +370,7 @@ int pjb_upload_contig(pjb_ctx *c, int32_t tid, const uint8_t *bases, int64_t len
             c->stage[si] = nullptr;
             c->stage_cap[si] = 0;
             if (hipHostMalloc((void **)&c->stage[si], PIECE, hipHostMallocDefault) != hipSuccess) {
-                (void)hipFree(d);
+                (void)dev_free(c, d);
                 return fail(c, PJB_ERR_NOMEM, "upload: cannot allocate page-locked staging memory");
             }
             c->stage_cap[si] = PIECE;
@@ -379,14 +379,14 @@ int pjb_upload_contig(pjb_ctx *c, int32_t tid, const uint8_t *bases, int64_t len
         parallel_copy(c->stage[si], bases + off, n);
         e = hipMemcpyAsync(d + off, c->stage[si], n, hipMemcpyHostToDevice, c->stream);
         if (e != hipSuccess) {
-            (void)hipFree(d);
+            (void)dev_free(c, d);
             return fail(c, PJB_ERR_HIP, "hipMemcpy(genome): %s", hipGetErrorString(e));
         }
         (void)hipEventRecord(c->stage_ev[si], c->stream);
         c->stage_busy[si] = true;
     }
     int rc = upload_common(c, tid, d, len, true, true, d_cap);
-    if (rc) (void)hipFree(d);
+    if (rc) (void)dev_free(c, d);
     return rc;
 }
 
@@ -404,16 +404,17 @@ int pjb_upload_contig_fasta(pjb_ctx *c, int32_t tid, const uint8_t *raw, int64_t
     if ((rc = ensure(c, c->b_hasx, 4 * sizeof(int)))) return rc;
     size_t d_cap = 0;
     const double t_a0 = wall_now();
-    uint8_t *d = (uint8_t *)genome_take(c->genome_pool, (size_t)std::max<int64_t>(len, 16), d_cap);
-    if (!d) return fail(c, PJB_ERR_NOMEM, "hipMalloc(genome %lld) failed", (long long)len);
+    uint8_t *d = (uint8_t *)genome_take(c, (size_t)std::max<int64_t>(len, 16), d_cap);
+    if (!d) return nomem(c, "genome", (size_t)std::max<int64_t>(len, 16));
     if (getenv("PJB_PROFILE_HOST"))
         fprintf(stderr, "[host profile] genome tid %d: bases allocation %.4f s\n", tid, wall_now() - t_a0);
     struct Guard {
+        pjb_ctx *c;
         uint8_t *d;
         ~Guard() {
-            if (d) (void)hipFree(d);
+            if (d) (void)dev_free(c, d);
         }
-    } guard{d};
+    } guard{c, d};
     if (raw_bytes > 0 && (rc = upload_host(c, c->b_fasta_raw.p, raw, (size_t)raw_bytes))) return rc;
     // (k0_fasta's verdict is read with the other kernels' flags, behind the last of them: one wait a genome)
     HIP_TRY(c, hipMemsetAsync((int *)c->b_hasx.p + 3, 0, sizeof(int), c->stream));
@@ -442,7 +443,8 @@ int pjb_release_contig(pjb_ctx *c, int32_t tid) {
     if (tid < 0 || (size_t)tid >= c->contigs.size()) return fail(c, PJB_ERR_ARG, "pjb_release_contig: bad tid %d", tid);
     Contig &g = c->contigs[(size_t)tid];
     (void)hipStreamSynchronize(c->stream);
-    free_contig(g, &c->genome_pool);
+    if (c->slab_refused_tid == tid && !c->open.count(tid)) c->slab_refused_tid = -1;
+    free_contig(c, g, true);
     return PJB_OK;
 }
 
@@ -505,8 +507,12 @@ static int add_batch(pjb_ctx *c, int32_t tid, const pjb_batch *b, bool device) {
             c->stage_cap[si] = want;
         }
         if (!c->stage_ev[si]) HIP_TRY(c, hipEventCreateWithFlags(&c->stage_ev[si], hipEventDisableTiming));
+        const SlabMark mark = slab_mark(c, oc);
         uint8_t *dev = (uint8_t *)slab_alloc(c, oc, total_b);
-        if (!dev) return fail(c, PJB_ERR_NOMEM, "submit: out of device memory for a batch of %zu bytes", total_b);
+        if (!dev) { // (retryable: the target is as it was)
+            slab_rollback(c, oc, mark);
+            return nomem(c, "submit: a batch", total_b);
+        }
         void *ptrs[14];
         for (int k = 0; k < 14; k++) {
             if (bytes[k] && src[k]) parallel_copy(c->stage[si] + offs[k], src[k], bytes[k]);
@@ -667,6 +673,14 @@ int pjb_clear_rows(pjb_ctx *c) {
     (void)rows_sync(c);
     c->rows_n = 0;
     (void)exhume(c); // (nothing is queued: the buffers that were replaced while chains ran go back now)
+    {
+        std::lock_guard<std::mutex> lk(c->mem.mu);
+        c->mem.peak = c->mem.held;
+        c->mem.peak_slabs = c->mem.cat[MEM_SLABS_OPEN] + c->mem.cat[MEM_SLABS_POOLED];
+        c->mem.largest_bytes = 0;
+        c->mem.largest_tid = -1;
+    }
+    c->slab_refused_tid = -1;
     mirror_reset(c);
     if (c->extra) {
         (void)hipSetDevice(c->cfg.device);
@@ -734,8 +748,45 @@ int pjb_set_option(pjb_ctx *c, const char *name, int64_t value) {
     } else if (n == "knn_chunk") {
         if (value < 0 || value > (1 << 22)) return fail(c, PJB_ERR_ARG, "set_option: knn_chunk takes 0 (the default: sized to fill the chip) to %d base rows", 1 << 22);
         c->model.knn_chunk = (u32)value;
+    } else if (n == "mem_limit") {
+        if (value < 0) return fail(c, PJB_ERR_ARG, "set_option: mem_limit takes 0 (the default: no limit) or a number of bytes");
+        std::lock_guard<std::mutex> lk(c->mem.mu);
+        c->mem.limit = (size_t)value;
     } else if (n == "list_cap") c->list_cap_forced = (u32)std::max<int64_t>(0, std::min<int64_t>(value, 1 << 30));
     else return fail(c, PJB_ERR_ARG, "set_option: unknown option '%s'", name);
+    return PJB_OK;
+}
+
+int pjb_memory_info(const pjb_ctx *c, pjb_memory *out) {
+    if (!c || !out) return PJB_ERR_ARG;
+    memset(out, 0, sizeof *out);
+    {
+        std::lock_guard<std::mutex> lk(c->mem.mu);
+        const MemBook &m = c->mem;
+        out->genomes = m.cat[MEM_GENOMES];
+        out->slabs_open = m.cat[MEM_SLABS_OPEN];
+        out->slabs_pooled = m.cat[MEM_SLABS_POOLED];
+        out->staging = m.cat[MEM_STAGING];
+        out->scratch = m.cat[MEM_SCRATCH];
+        out->rows = m.cat[MEM_ROWS];
+        out->other = m.cat[MEM_OTHER];
+        out->held = m.held;
+        out->limit = m.limit;
+        out->peak_held = m.peak;
+        out->peak_records = m.peak_slabs;
+        out->largest_target_bytes = m.largest_bytes;
+        out->largest_target = m.largest_tid;
+    }
+    // (hipMemGetInfo answers for the calling thread's current device: the context's for the length of the call, the caller's again after it)
+    int was = -1;
+    size_t f = 0, t = 0;
+    if (hipGetDevice(&was) != hipSuccess) was = -1;
+    if ((was == c->cfg.device || hipSetDevice(c->cfg.device) == hipSuccess) && hipMemGetInfo(&f, &t) == hipSuccess) {
+        out->hip_free = f;
+        out->hip_total = t;
+    }
+    if (was >= 0 && was != c->cfg.device) (void)hipSetDevice(was);
+    (void)hipGetLastError();
     return PJB_OK;
 }
 

@@ -35,9 +35,8 @@ static int rows_table_reserve(pjb_ctx *c, Flight &f, u32 JL) {
     if (rc) return rc;
     old = std::min(old, c->rows_cap);
     const size_t ncap = std::max<size_t>((old + JL) * 3 / 2, 1024);
-    pjb_junction_row *nd = nullptr;
-    hipError_t e = hipMalloc((void **)&nd, ncap * sizeof(pjb_junction_row));
-    if (e != hipSuccess) return fail(c, PJB_ERR_NOMEM, "hipMalloc(row table): %s", hipGetErrorString(e));
+    pjb_junction_row *nd = (pjb_junction_row *)dev_alloc(c, MEM_ROWS, ncap * sizeof(pjb_junction_row));
+    if (!nd) return nomem(c, "row table", ncap * sizeof(pjb_junction_row));
     if (old) {
         // (a device-to-device hipMemcpy may return before it has run, and the chains' streams do not wait for the null stream: without
         // the wait the rows a chain appends below `old` -- `old` is a bound -- could be overwritten by the tail of this copy.  The

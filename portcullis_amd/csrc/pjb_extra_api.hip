@@ -43,19 +43,20 @@ static int extra_contig_dense(pjb_ctx *c, Flight &f, u64 n_spliced, u32 P, u32 J
     if ((rc = ensure(c, c->x_zlist, (size_t)X_ZCAP * 4))) return rc;
     if ((rc = ensure(c, c->x_cnt, sizeof(ExtraCounters)))) return rc;
     struct Guard { // frees what this contig allocated unless it is handed over to the context
+        pjb_ctx *c;
         ExtraContig *x;
         ~Guard() {
             if (!x) return;
-            if (x->cover) (void)hipFree(x->cover);
-            if (x->xr) (void)hipFree(x->xr);
-            if (x->pair_code) (void)hipFree(x->pair_code);
-            if (x->pair_row) (void)hipFree(x->pair_row);
-            if (x->spl_codes) (void)hipFree(x->spl_codes);
+            (void)dev_free(c, x->cover);
+            (void)dev_free(c, x->xr);
+            (void)dev_free(c, x->pair_code);
+            (void)dev_free(c, x->pair_row);
+            (void)dev_free(c, x->spl_codes);
         }
-    } guard{&X};
-    if (hipMalloc((void **)&X.cover, ((size_t)L + 2) * 4) != hipSuccess) return fail(c, PJB_ERR_NOMEM, "extra: depth array of target %d", tid);
-    if (hipMalloc((void **)&X.spl_codes, std::max<size_t>((size_t)n_spliced, 1) * 8) != hipSuccess)
-        return fail(c, PJB_ERR_NOMEM, "extra: name codes of target %d", tid);
+    } guard{c, &X};
+    if (!(X.cover = (u32 *)dev_alloc(c, MEM_OTHER, ((size_t)L + 2) * 4))) return nomem(c, "extra: depth array", ((size_t)L + 2) * 4);
+    if (!(X.spl_codes = (u64 *)dev_alloc(c, MEM_OTHER, std::max<size_t>((size_t)n_spliced, 1) * 8)))
+        return nomem(c, "extra: name codes", std::max<size_t>((size_t)n_spliced, 1) * 8);
     HIP_TRY(c, hipMemsetAsync(X.cover, 0, ((size_t)L + 2) * 4, st));
     HIP_TRY(c, hipMemsetAsync(c->x_ce.p, 0, ((size_t)L + 2) * 4, st));
     HIP_TRY(c, hipMemsetAsync((uint8_t *)c->x_q.p + N, 0, 1, st));
@@ -100,12 +101,12 @@ static int extra_contig_dense(pjb_ctx *c, Flight &f, u64 n_spliced, u32 P, u32 J
     X.has_unspliced = n_unspl > 0;
     X.n_spl = hc.n_spliced;
     if (J > 0) {
-        if (hipMalloc((void **)&X.xr, (size_t)J * sizeof(ExtraRow)) != hipSuccess) return fail(c, PJB_ERR_NOMEM, "extra: rows of target %d", tid);
+        if (!(X.xr = (ExtraRow *)dev_alloc(c, MEM_OTHER, (size_t)J * sizeof(ExtraRow)))) return nomem(c, "extra: rows", (size_t)J * sizeof(ExtraRow));
         HIP_TRY(c, hipMemsetAsync(X.xr, 0, (size_t)J * sizeof(ExtraRow), st));
         LAUNCH(c, "kx_flank", kx_flank, dim3((J + 255) / 256), dim3(256), (const pjb_junction_row *)c->sl[f.slot].rows.p, J, (const int32_t *)x_pos,
                (u32)N, (const u32 *)prefq, (const u32 *)ce, L, (const u32 *)c->x_zlist.p, (const ExtraCounters *)d_cnt, X_ZCAP, X.xr);
-        if (hipMalloc((void **)&X.pair_code, (size_t)P * 8) != hipSuccess || hipMalloc((void **)&X.pair_row, (size_t)P * 4) != hipSuccess)
-            return fail(c, PJB_ERR_NOMEM, "extra: pair codes of target %d", tid);
+        if (!(X.pair_code = (u64 *)dev_alloc(c, MEM_OTHER, (size_t)P * 8)) || !(X.pair_row = (u32 *)dev_alloc(c, MEM_OTHER, (size_t)P * 4)))
+            return nomem(c, "extra: pair codes", (size_t)P * 12);
         LAUNCH(c, "kx_pair_codes", kx_pair_codes, dim3((P + 255) / 256), dim3(256), f.sidx, f.jid_sorted, f.pr.g,
                (const DevBatch *)c->sl[f.slot].batches.p, (int)batches.size(), P, (u32)row_base, X.pair_code, X.pair_row);
     }
@@ -145,7 +146,7 @@ static int name_table_reserve(pjb_ctx *c, size_t add) {
                (u32)c->x_tab_slots, (NameSlot *)nb.p, (u32)slots);
     if (c->x_tab.p) {
         HIP_TRY(c, hipStreamSynchronize(st));
-        release(c->x_tab);
+        release(c, c->x_tab);
     }
     c->x_tab = nb;
     c->x_tab_slots = slots;
@@ -425,15 +426,15 @@ int pjb_filter_set_junctions(pjb_ctx *c, int32_t tid, const uint64_t *sorted_key
     auto it = c->filter_keys.find(tid);
     if (it != c->filter_keys.end()) {
         HIP_TRY(c, hipStreamSynchronize(c->stream));
-        if (it->second.first) (void)hipFree(it->second.first);
+        if (it->second.first) (void)dev_free(c, it->second.first);
         c->filter_keys.erase(it);
     }
     u64 *d = nullptr;
     if (n_keys) {
-        if (hipMalloc((void **)&d, (size_t)n_keys * 8) != hipSuccess) return fail(c, PJB_ERR_NOMEM, "pjb_filter_set_junctions: %lld keys", (long long)n_keys);
+        if (!(d = (u64 *)dev_alloc(c, MEM_OTHER, (size_t)n_keys * 8))) return nomem(c, "pjb_filter_set_junctions", (size_t)n_keys * 8);
         hipError_t e = hipMemcpy(d, sorted_keys, (size_t)n_keys * 8, hipMemcpyHostToDevice);
         if (e != hipSuccess) {
-            (void)hipFree(d);
+            (void)dev_free(c, d);
             return fail(c, PJB_ERR_HIP, "pjb_filter_set_junctions: %s", hipGetErrorString(e));
         }
     }

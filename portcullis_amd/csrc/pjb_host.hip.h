@@ -4,11 +4,12 @@
 // (--extra, bamfilt: pjb_extra.hip.h), pjb_model_api.hip (filt and train -- feature rows, the forest walk, forest growing, KNN:
 // pjb_features.hip.h, pjb_forest.hip.h, pjb_grow.hip.h, pjb_knn.hip.h) and pjb_ingest_api.hip (BGZF inflate / deflate, BAM records:
 // pjb_ingest.hip.h, pjb_deflate.hip.h) -- each of which includes its own kernel family behind this header and so is the only unit that compiles it; this header includes only what the
-// units share (pjb_device.hip.h, pjb_extra_types.hip.h).  (The Makefile makes every header a prerequisite of every unit: an edit to any of them
+// units share (pjb_device.hip.h, pjb_extra_types.hip.h, and pjb_memory.hip.h: the rule the counted allocator below follows).  (The Makefile makes every header a prerequisite of every unit: an edit to any of them
 // rebuilds the library.)  Helpers are inline functions of this header: one definition, one set of thread-local error strings for all units.
 #pragma once
 #include "pjb_device.hip.h"
 #include "pjb_extra_types.hip.h"
+#include "pjb_memory.hip.h"
 
 #include <algorithm>
 #include <sys/mman.h>
@@ -23,6 +24,7 @@
 #include <mutex>
 #include <string>
 #include <thread>
+#include <unordered_map>
 #include <vector>
 
 using namespace pjb;
@@ -52,49 +54,10 @@ struct Contig {
     size_t d_cap = 0, codes_cap = 0; // sizes of the allocations (they go back to the context's genome pool)
 };
 
-// The bases and codes of a released contig are kept for the next upload (targets come longest first, so the next genome
-// fits): a hipMalloc / hipFree pair of 250 MB is ~10 ms on the thread that serves every target.
-inline void free_contig(Contig &g, std::vector<Buf> *pool = nullptr) {
-    auto give = [&](void *p, size_t cap) {
-        if (!p) return;
-        if (pool && cap > 0 && pool->size() < 12) {
-            Buf b;
-            b.p = p;
-            b.cap = cap;
-            pool->push_back(b);
-        } else
-            (void)hipFree(p);
-    };
-    if (g.owned) give(g.d, g.d_cap);
-    give(g.codes, g.codes_cap); // (codes2 lies in the same allocation)
-    g = Contig();
-}
-// device memory for a genome array: the smallest pooled buffer that fits, else a new one
-inline void *genome_take(std::vector<Buf> &pool, size_t bytes, size_t &cap) {
-    int best = -1;
-    for (size_t k = 0; k < pool.size(); k++)
-        if (pool[k].cap >= bytes && (best < 0 || pool[k].cap < pool[(size_t)best].cap)) best = (int)k;
-    if (best >= 0) {
-        void *p = pool[(size_t)best].p;
-        cap = pool[(size_t)best].cap;
-        pool.erase(pool.begin() + best);
-        return p;
-    }
-    void *p = nullptr;
-    cap = bytes;
-    if (hipMalloc(&p, bytes) != hipSuccess) {
-        (void)hipGetLastError();
-        return nullptr;
-    }
-#ifdef PJB_DEBUG_ALLOC
-    fprintf(stderr, "[alloc] genome: %p .. %p (%zu bytes)\n", p, (void *)((char *)p + bytes), bytes);
-#endif
-    return p;
-}
-
 struct Slab { // device memory for the batches copied in by pjb_submit_batch; reused contig after contig
     uint8_t *p = nullptr;
     size_t cap = 0, used = 0;
+    u64 born = 0; // the submit call (pjb_ctx::slab_call) that allocated it: a call that fails for memory frees what it allocated itself
 };
 
 // a contig that has received batches and is not finished yet; several may be open at once
@@ -223,11 +186,8 @@ struct Flight {
     u32 x_gap_cap = 0;
 };
 
-inline void release(Buf &b) {
-    if (b.p) (void)hipFree(b.p);
-    b.p = nullptr;
-    b.cap = 0;
-}
+struct pjb_ctx;
+inline void release(pjb_ctx *c, Buf &b);
 
 // what a context keeps for `filt` and `train` (pjb_model_api.hip); a device buffer added here is added to release_all() below it
 struct ModelState {
@@ -244,16 +204,36 @@ struct ModelState {
         std::vector<int32_t> left, right, split_var;
         std::vector<double> split_value, counts, class_values;
     } grow_out;
-    void release_all() { // (pjb_destroy)
+    void release_all(pjb_ctx *c) { // (pjb_destroy)
         for (Buf *b : {&g_rows, &g_models, &g_refs, &g_out, &g_bad, &r_nodes, &r_leaf, &r_roots, &r_data, &r_pred, &r_colmap, &w_pool, &w_pack,
                        &n_data, &n_part_d, &n_part_i, &n_out})
-            release(*b);
+            release(c, *b);
     }
+};
+
+// The context's books of its device memory (pjb_memory_info): every allocation with its size and category.  Every hipMalloc / hipFree of a
+// context goes through dev_alloc / dev_free below, which keep them; `mu` guards them (pjb_bam_* allocate on the callers' threads).
+struct MemBook {
+    struct Entry {
+        size_t bytes;
+        int cat;
+    };
+    mutable std::mutex mu;
+    std::unordered_map<void *, Entry> live;
+    size_t cat[MEM_NCAT] = {};
+    size_t held = 0, peak = 0;
+    size_t peak_slabs = 0;   // slabs, open and pooled, at the moment `peak` was reached
+    size_t largest_bytes = 0; // the most slab capacity one collected target has held since the peak was last started, and that target
+    int32_t largest_tid = -1;
+    size_t limit = 0;        // pjb_set_option("mem_limit", n); 0: none
+    size_t parked = 0;       // of MEM_SCRATCH: in the graveyard
+    size_t pooled_stage = 0; // of MEM_STAGING: in stage_pool / out_pool / misc_pool
 };
 
 constexpr size_t PJB_UP_EVENTS = 64;
 struct pjb_ctx {
     pjb_config cfg;
+    MemBook mem;
     hipStream_t stream = nullptr;  // service stream: uploads, host batches, BAM ingest, filters, extra metrics; a contig's chain runs
                                    // on its slot's streams (CtlSlot::main / side)
     hipStream_t stream3 = nullptr; // rows stream: k6_rows_out + k6_rows_out (publish_chain) of a contig, beside the next contig's first kernels
@@ -290,6 +270,10 @@ struct pjb_ctx {
     int32_t cur_tid = -1; // contig of the call in progress (error messages)
     std::map<int32_t, OpenContig> open;
     std::vector<Slab> slab_pool; // free slabs, reused contig after contig
+    std::mutex slab_mu;          // guards slab_pool: an allocation that fails on a pjb_bam_* thread gives the pooled slabs back (make_room)
+    u64 slab_call = 0;           // number of the submit call in progress (Slab::born, SlabMark)
+    int32_t slab_refused_tid = -1; // the target whose last slab request was refused without trying the exact size (slab_exact_now), and
+    size_t slab_refused_held = 0;  // what the context held then: a repeat that finds no less has had nothing freed for it
     // two page-locked staging buffers: pjb_submit_batch packs the caller's arrays into one of them
     // (plain memcpy) and the DMA engine moves it to HBM while the caller decodes the next batch
     uint8_t *stage[2] = {nullptr, nullptr};
@@ -390,8 +374,81 @@ inline int fail(pjb_ctx *c, int code, const char *fmt, ...) {
                         __LINE__);                                                                         \
     } while (0)
 
+// ---- the context's device memory: ONE pair of counted helpers (dev_alloc / dev_free) around hipMalloc / hipFree -----------------------------
+// pjb_bam_begin / _piece / _end hold bam_mu on their own threads while they allocate; an allocation that fails there gives the pooled stage
+// buffers back without taking the lock again (BamLock counts what this thread holds)
+inline thread_local int g_bam_locked = 0;
+struct BamLock {
+    std::lock_guard<std::mutex> lk;
+    explicit BamLock(pjb_ctx *c) : lk(c->bam_mu) { g_bam_locked++; }
+    ~BamLock() { g_bam_locked--; }
+};
+
+// one request, as it is: refused by the context's own limit (*by_limit) or by the runtime, or booked under `cat`
+inline bool dev_try(pjb_ctx *c, MemCat cat, void **p, size_t bytes, bool *by_limit) {
+    MemBook &m = c->mem;
+    *p = nullptr;
+    {
+        std::lock_guard<std::mutex> lk(m.mu);
+        if (!fits_limit(bytes, m.held, m.limit)) {
+            *by_limit = true;
+            return false;
+        }
+        m.held += bytes; // (booked before the call: two threads must not pass the limit together)
+        m.cat[cat] += bytes;
+    }
+    *by_limit = false;
+    const hipError_t e = hipMalloc(p, bytes);
+    std::lock_guard<std::mutex> lk(m.mu);
+    if (e != hipSuccess) {
+        (void)hipGetLastError();
+        *p = nullptr;
+        m.held -= bytes;
+        m.cat[cat] -= bytes;
+        return false;
+    }
+    m.live[*p] = MemBook::Entry{bytes, (int)cat};
+    if (m.held > m.peak) {
+        m.peak = m.held;
+        m.peak_slabs = m.cat[MEM_SLABS_OPEN] + m.cat[MEM_SLABS_POOLED];
+    }
+    return true;
+}
+inline size_t dev_free(pjb_ctx *c, void *p) { // (the bytes that went)
+    if (!p) return 0;
+    MemBook &m = c->mem;
+    size_t bytes = 0;
+    {
+        std::lock_guard<std::mutex> lk(m.mu);
+        auto it = m.live.find(p);
+        if (it != m.live.end()) {
+            bytes = it->second.bytes;
+            m.held -= bytes;
+            m.cat[it->second.cat] -= bytes;
+            m.live.erase(it);
+        }
+    }
+    (void)hipFree(p);
+    return bytes;
+}
+inline size_t dev_recat(pjb_ctx *c, void *p, MemCat cat) { // an allocation changes its category (a slab is pooled, a buffer parked)
+    MemBook &m = c->mem;
+    std::lock_guard<std::mutex> lk(m.mu);
+    auto it = m.live.find(p);
+    if (it == m.live.end()) return 0;
+    m.cat[it->second.cat] -= it->second.bytes;
+    it->second.cat = (int)cat;
+    m.cat[cat] += it->second.bytes;
+    return it->second.bytes;
+}
+
 // the buffers ensure() has put aside go back to the device (hipFree waits for the device: call where that costs nothing)
 inline void bury(pjb_ctx *c, void *p) {
+    const size_t bytes = dev_recat(c, p, MEM_SCRATCH);
+    {
+        std::lock_guard<std::mutex> lk(c->mem.mu);
+        c->mem.parked += bytes;
+    }
     std::lock_guard<std::mutex> lk(c->grave_mu);
     c->graveyard.push_back(p);
 }
@@ -401,42 +458,138 @@ inline bool exhume(pjb_ctx *c) { // (true: something was freed)
         std::lock_guard<std::mutex> lk(c->grave_mu);
         g.swap(c->graveyard);
     }
-    for (void *p : g) (void)hipFree(p);
+    for (void *p : g) {
+        const size_t bytes = dev_free(c, p);
+        std::lock_guard<std::mutex> lk(c->mem.mu);
+        c->mem.parked -= std::min(bytes, c->mem.parked);
+    }
     return !g.empty();
 }
+inline void release(pjb_ctx *c, Buf &b) {
+    if (b.p) (void)dev_free(c, b.p);
+    b.p = nullptr;
+    b.cap = 0;
+}
+inline void release_pooled_slabs(pjb_ctx *c) {
+    std::vector<Slab> pool;
+    {
+        std::lock_guard<std::mutex> lk(c->slab_mu);
+        pool.swap(c->slab_pool);
+    }
+    for (auto &s : pool) (void)dev_free(c, s.p);
+}
+inline void release_pooled_stage(pjb_ctx *c) {
+    std::unique_lock<std::mutex> lk(c->bam_mu, std::defer_lock);
+    if (!g_bam_locked) lk.lock();
+    for (auto *pool : {&c->stage_pool, &c->out_pool, &c->misc_pool}) {
+        for (auto &b : *pool) release(c, b);
+        pool->clear();
+    }
+    std::lock_guard<std::mutex> lm(c->mem.mu);
+    c->mem.pooled_stage = 0;
+}
+// An allocation of `want` bytes failed: the context gives back what it holds without needing it (plan_room says what).  No chain of this
+// context reads any of it -- a pooled slab's target has been collected, a pooled stage buffer's records parsed -- and hipFree waits for
+// the device before a parked buffer goes.  true: ask once more.
+inline bool make_room(pjb_ctx *c, size_t want, bool by_limit) {
+    RoomState s;
+    {
+        std::lock_guard<std::mutex> lk(c->mem.mu);
+        s = RoomState{want, c->mem.held, c->mem.limit, by_limit, c->mem.parked, c->mem.cat[MEM_SLABS_POOLED], c->mem.pooled_stage};
+    }
+    const RoomPlan p = plan_room(s);
+    if (p.parked) (void)exhume(c);
+    if (p.slabs) release_pooled_slabs(c);
+    if (p.stage) release_pooled_stage(c);
+    return p.retry;
+}
+// `bytes` of device memory booked under `cat`; a request that fails is repeated once behind make_room.  nullptr: out of memory (nomem()).
+inline void *dev_alloc(pjb_ctx *c, MemCat cat, size_t bytes) {
+    void *p = nullptr;
+    bool by_limit = false;
+    if (dev_try(c, cat, &p, bytes, &by_limit)) return p;
+    if (make_room(c, bytes, by_limit) && dev_try(c, cat, &p, bytes, &by_limit)) return p;
+    return nullptr;
+}
+// PJB_ERR_NOMEM with the message every failed device allocation gets: the bytes wanted, what the context holds, its limit
+inline int nomem(pjb_ctx *c, const char *what, size_t bytes) {
+    size_t held, limit;
+    {
+        std::lock_guard<std::mutex> lk(c->mem.mu);
+        held = c->mem.held;
+        limit = c->mem.limit;
+    }
+    if (limit) return fail(c, PJB_ERR_NOMEM, "%s: out of device memory: wanted %zu bytes, held %zu, limit %zu", what, bytes, held, limit);
+    return fail(c, PJB_ERR_NOMEM, "%s: out of device memory: wanted %zu bytes, held %zu, limit none", what, bytes, held);
+}
+
+// The bases and codes of a released contig are kept for the next upload (targets come longest first, so the next genome
+// fits): a hipMalloc / hipFree pair of 250 MB is ~10 ms on the thread that serves every target.
+inline void free_contig(pjb_ctx *c, Contig &g, bool to_pool = false) {
+    auto give = [&](void *p, size_t cap) {
+        if (!p) return;
+        if (to_pool && cap > 0 && c->genome_pool.size() < 12) {
+            Buf b;
+            b.p = p;
+            b.cap = cap;
+            c->genome_pool.push_back(b);
+        } else
+            (void)dev_free(c, p);
+    };
+    if (g.owned) give(g.d, g.d_cap);
+    give(g.codes, g.codes_cap); // (codes2 lies in the same allocation)
+    g = Contig();
+}
+// device memory for a genome array: the smallest pooled buffer that fits, else a new one
+inline void *genome_take(pjb_ctx *c, size_t bytes, size_t &cap) {
+    std::vector<Buf> &pool = c->genome_pool;
+    int best = -1;
+    for (size_t k = 0; k < pool.size(); k++)
+        if (pool[k].cap >= bytes && (best < 0 || pool[k].cap < pool[(size_t)best].cap)) best = (int)k;
+    if (best >= 0) {
+        void *p = pool[(size_t)best].p;
+        cap = pool[(size_t)best].cap;
+        pool.erase(pool.begin() + best);
+        return p;
+    }
+    cap = bytes;
+    void *p = dev_alloc(c, MEM_GENOMES, bytes);
+#ifdef PJB_DEBUG_ALLOC
+    if (p) fprintf(stderr, "[alloc] genome: %p .. %p (%zu bytes)\n", p, (void *)((char *)p + bytes), bytes);
+#endif
+    return p;
+}
+
 #ifdef PJB_DEBUG_ALLOC // (debug builds: every device buffer with its range on stderr, so that a "Memory access fault ... on address" can be placed)
 #define ensure(c, b, bytes) ensure_named((c), (b), (bytes), #b, __LINE__)
-inline int ensure_named(pjb_ctx *c, Buf &b, size_t bytes, const char *what, int line);
-inline int ensure_impl(pjb_ctx *c, Buf &b, size_t bytes);
+inline int ensure_cat(pjb_ctx *c, Buf &b, size_t bytes, MemCat cat);
 inline int ensure_named(pjb_ctx *c, Buf &b, size_t bytes, const char *what, int line) {
     const void *was = b.p;
-    const int rc = ensure_impl(c, b, bytes);
+    const int rc = ensure_cat(c, b, bytes, MEM_SCRATCH);
     if (b.p != was) fprintf(stderr, "[alloc] %s (line %d): %p .. %p (%zu bytes, asked %zu)\n", what, line, b.p, (void *)((char *)b.p + b.cap), b.cap, bytes);
     return rc;
 }
-inline int ensure_impl(pjb_ctx *c, Buf &b, size_t bytes) {
 #else
-inline int ensure(pjb_ctx *c, Buf &b, size_t bytes) {
+inline int ensure_cat(pjb_ctx *c, Buf &b, size_t bytes, MemCat cat);
+inline int ensure(pjb_ctx *c, Buf &b, size_t bytes) { return ensure_cat(c, b, bytes, MEM_SCRATCH); }
 #endif
+inline int ensure_cat(pjb_ctx *c, Buf &b, size_t bytes, MemCat cat) {
     if (bytes <= b.cap && b.p) return PJB_OK;
     // A buffer that has to grow is not freed here: hipFree waits for the whole device -- the inflate of the next targets, the copies in
     // flight -- and every thread that calls into the runtime meanwhile waits with it (end to end: 15 - 40 ms of nothing at the first
     // chains).  The old buffer goes to the context's graveyard, which is emptied where a wait costs nothing (exhume: pjb_clear_rows,
-    // pjb_destroy) or when an allocation fails.  A buffer grows by a quarter at least, so what lies there is a few times the live size at most.
+    // pjb_destroy) or when an allocation fails (make_room).  A buffer grows by a quarter at least, so what lies there is a few times the live size at most.
     if (b.p) bury(c, b.p);
     b.p = nullptr;
     b.cap = 0;
     size_t want = std::max<size_t>(bytes + bytes / 4, 256);
-    hipError_t e = hipMalloc(&b.p, want);
-    if (e != hipSuccess) {
-        (void)hipGetLastError();
-        if (exhume(c)) e = hipMalloc(&b.p, want);
-    }
-    if (e != hipSuccess) {
+    b.p = dev_alloc(c, cat, want);
+    if (!b.p && std::max<size_t>(bytes, 256) < want) { // (what was held without need has gone: the exact size, once)
         want = std::max<size_t>(bytes, 256);
-        e = hipMalloc(&b.p, want);
-        if (e != hipSuccess) return fail(c, PJB_ERR_NOMEM, "hipMalloc(%zu) failed: %s", want, hipGetErrorString(e));
+        bool by_limit = false;
+        (void)dev_try(c, cat, &b.p, want, &by_limit);
     }
+    if (!b.p) return nomem(c, "device buffer", want);
     b.cap = want;
     // test hook (tests/test_gpu_poison.py): PJB_POISON=1 fills every new device buffer with a pattern.  Fresh device memory is
     // usually zero, and a kernel that reads what nobody wrote gets away with it until the allocator hands out a used page
@@ -610,6 +763,7 @@ inline void *slab_alloc(pjb_ctx *c, OpenContig &oc, size_t bytes) {
     {
         // (a target's first slab: the smallest pooled one that holds what the target is expected to take in all, else a new one of that size)
         const size_t want = oc.slabs.empty() ? std::max(bytes, oc.slab_hint) : bytes;
+        std::lock_guard<std::mutex> lk(c->slab_mu);
         long best = -1;
         for (size_t k = 0; k < c->slab_pool.size(); k++)
             if (c->slab_pool[k].cap >= want && (best < 0 || c->slab_pool[k].cap < c->slab_pool[(size_t)best].cap)) best = (long)k;
@@ -617,17 +771,39 @@ inline void *slab_alloc(pjb_ctx *c, OpenContig &oc, size_t bytes) {
             Slab s = c->slab_pool[(size_t)best];
             c->slab_pool.erase(c->slab_pool.begin() + best);
             s.used = bytes;
+            (void)dev_recat(c, s.p, MEM_SLABS_OPEN);
             oc.slabs.push_back(s);
             return s.p;
         }
     }
+    // (slab_sizes: 128 MB or the target's hint -- behind a failure, once more behind make_room --, then the exact size, once)
     Slab s;
-    s.cap = std::max<size_t>(bytes, std::max<size_t>((size_t)128 << 20, oc.slabs.empty() ? oc.slab_hint : 0));
-    if (hipMalloc((void **)&s.p, s.cap) != hipSuccess) {
-        s.cap = bytes;
-        if (hipMalloc((void **)&s.p, s.cap) != hipSuccess) return nullptr;
+    size_t sizes[2];
+    const int n_sizes = slab_sizes(bytes, oc.slab_hint, oc.slabs.empty(), sizes);
+    s.cap = sizes[0];
+    s.p = (uint8_t *)dev_alloc(c, MEM_SLABS_OPEN, s.cap);
+    if (!s.p && n_sizes > 1) {
+        size_t held;
+        {
+            std::lock_guard<std::mutex> lk(c->mem.mu);
+            held = c->mem.held;
+        }
+        bool others = false; // (a queued chain's targets stay open until it is collected)
+        for (auto &kv : c->open)
+            if (&kv.second != &oc && !kv.second.slabs.empty()) others = true;
+        if (!slab_exact_now(others, c->slab_refused_tid == c->cur_tid && held >= c->slab_refused_held)) {
+            c->slab_refused_tid = c->cur_tid;
+            c->slab_refused_held = held;
+            return nullptr;
+        }
+        bool by_limit = false;
+        s.cap = sizes[1];
+        (void)dev_try(c, MEM_SLABS_OPEN, (void **)&s.p, s.cap, &by_limit);
     }
+    if (!s.p) return nullptr;
+    if (c->slab_refused_tid == c->cur_tid) c->slab_refused_tid = -1;
     s.used = bytes;
+    s.born = c->slab_call;
     oc.slabs.push_back(s);
 #ifdef PJB_DEBUG_ALLOC
     fprintf(stderr, "[alloc] slab: %p .. %p (%zu bytes)\n", (void *)s.p, (void *)(s.p + s.cap), s.cap);
@@ -635,14 +811,48 @@ inline void *slab_alloc(pjb_ctx *c, OpenContig &oc, size_t bytes) {
     return s.p;
 }
 
+// What a submit call (pjb_submit_batch, pjb_submit_bam, pjb_bam_end) found of a target's slabs, so that a call that fails with
+// PJB_ERR_NOMEM leaves the target as it was (slab_rollback): what it took of slabs goes back -- to the target's earlier slabs their
+// bytes, to the pool the slabs that came from it, to the device the slabs the call allocated itself.
+struct SlabMark {
+    std::vector<size_t> used;
+    size_t n_batches;
+};
+inline SlabMark slab_mark(pjb_ctx *c, const OpenContig &oc) {
+    SlabMark m;
+    for (auto &s : oc.slabs) m.used.push_back(s.used);
+    m.n_batches = oc.batches.size();
+    c->slab_call++;
+    return m;
+}
+inline void slab_rollback(pjb_ctx *c, OpenContig &oc, const SlabMark &m) {
+    (void)hipStreamSynchronize(c->stream); // (what the call queued may still write to them)
+    while (oc.slabs.size() > m.used.size()) {
+        Slab s = oc.slabs.back();
+        oc.slabs.pop_back();
+        if (s.born == c->slab_call) {
+            (void)dev_free(c, s.p);
+            continue;
+        }
+        s.used = 0;
+        (void)dev_recat(c, s.p, MEM_SLABS_POOLED);
+        std::lock_guard<std::mutex> lk(c->slab_mu);
+        c->slab_pool.push_back(s);
+    }
+    for (size_t k = 0; k < oc.slabs.size(); k++) oc.slabs[k].used = m.used[k];
+    oc.batches.resize(m.n_batches);
+    oc.last_pos.resize(m.n_batches);
+    oc.last_known.resize(m.n_batches);
+}
+
 inline void extra_clear(pjb_ctx *c) {
     for (auto &x : c->xc) {
         if (!x.dense) continue; // (everything else is arena memory)
-        if (x.cover) (void)hipFree(x.cover);
-        if (x.xr) (void)hipFree(x.xr);
-        if (x.pair_code) (void)hipFree(x.pair_code);
-        if (x.pair_row) (void)hipFree(x.pair_row);
-        if (x.spl_codes) (void)hipFree(x.spl_codes);
+        (void)dev_free(c, x.cover);
+        (void)dev_free(c, x.xr);
+        (void)dev_free(c, x.pair_code);
+        (void)dev_free(c, x.pair_row);
+        (void)dev_free(c, x.spl_codes);
     }
     c->xc.clear();
     c->xarena.cur = c->xarena.used = 0;
@@ -661,10 +871,13 @@ inline void *xarena_alloc(pjb_ctx *c, size_t bytes) {
         }
     XArena::Chunk ch;
     ch.cap = std::max<size_t>(bytes, (size_t)256 << 20);
-    if (hipMalloc((void **)&ch.p, ch.cap) != hipSuccess) {
+    ch.p = (uint8_t *)dev_alloc(c, MEM_OTHER, ch.cap);
+    if (!ch.p && ch.cap > bytes) {
+        bool by_limit = false;
         ch.cap = bytes;
-        if (hipMalloc((void **)&ch.p, ch.cap) != hipSuccess) return nullptr;
+        (void)dev_try(c, MEM_OTHER, (void **)&ch.p, ch.cap, &by_limit);
     }
+    if (!ch.p) return nullptr;
     A.chunks.push_back(ch);
     A.cur = A.chunks.size() - 1;
     A.used = bytes;
@@ -674,13 +887,23 @@ inline void *xarena_alloc(pjb_ctx *c, size_t bytes) {
 inline int close_contig(pjb_ctx *c, int32_t tid) {
     auto it = c->open.find(tid);
     if (it == c->open.end()) return PJB_OK;
+    if (c->slab_refused_tid == tid) c->slab_refused_tid = -1; // (a refusal is remembered for the target's own repeat, not for its next life)
+    size_t cap = 0;
+    for (auto &s : it->second.slabs) cap += s.cap;
+    {
+        std::lock_guard<std::mutex> lk(c->mem.mu);
+        if (cap > c->mem.largest_bytes) c->mem.largest_bytes = cap, c->mem.largest_tid = tid;
+    }
     for (auto &s : it->second.slabs) {
         s.used = 0;
+        (void)dev_recat(c, s.p, MEM_SLABS_POOLED);
+        std::lock_guard<std::mutex> lk(c->slab_mu);
         c->slab_pool.push_back(s);
     }
     c->open.erase(it);
     return PJB_OK;
 }
+
 
 // ---- defined in one unit, used by another
 int upload_staged(pjb_ctx *c, void *dst, const uint8_t *src, size_t bytes);                                   // pjb_ingest_api.hip (pageable bytes through the staging buffers)

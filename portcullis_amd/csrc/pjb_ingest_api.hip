@@ -388,7 +388,7 @@ static int ingest_parse(pjb_ctx *c, int32_t tid, OpenContig &oc, const uint8_t *
     offs[8] = tot_b; // seq_off
     tot_b += (((n + 1) * 4) + 255) & ~(size_t)255;
     uint8_t *dev = (uint8_t *)slab_alloc(c, oc, tot_b);
-    if (!dev) return fail(c, PJB_ERR_NOMEM, "submit_bam: out of device memory for %zu alignments", n);
+    if (!dev) return nomem(c, "submit_bam: the alignments' fields", tot_b);
     BamSoA B;
     B.pos = (int32_t *)(dev + offs[0]);
     B.flag = (uint16_t *)(dev + offs[1]);
@@ -406,7 +406,7 @@ static int ingest_parse(pjb_ctx *c, int32_t tid, OpenContig &oc, const uint8_t *
     B.seq_exc = nullptr;
     if (c->extra) {
         B.name_hash = (iu64 *)slab_alloc(c, oc, n * 8 + 16);
-        if (!B.name_hash) return fail(c, PJB_ERR_NOMEM, "submit_bam: out of device memory for name codes");
+        if (!B.name_hash) return nomem(c, "submit_bam: name codes", n * 8 + 16);
     }
     if ((rc = run_scan(c, "bam_sizes", BamSizesFn{R.U, (const iu64 *)c->b_bam_rec.p}, BamOffsetsSink{B.cig_off, B.seq_off}, n, d_total)))
         return rc;
@@ -420,12 +420,12 @@ static int ingest_parse(pjb_ctx *c, int32_t tid, OpenContig &oc, const uint8_t *
     HIP_TRY(c, hipMemcpyAsync(B.seq_off + n, &tails[1], 4, hipMemcpyHostToDevice, st));
     B.cigar = (iu32 *)slab_alloc(c, oc, (size_t)n_ops * 4 + 16);
     B.seq4 = (uint8_t *)slab_alloc(c, oc, (size_t)n_words * 4 + 16);
-    if (!B.cigar || !B.seq4) return fail(c, PJB_ERR_NOMEM, "submit_bam: out of device memory for CIGARs / bases");
+    if (!B.cigar || !B.seq4) return nomem(c, "submit_bam: CIGARs / bases", ((size_t)n_ops + n_words) * 4 + 32);
     static const bool no_seq2 = getenv("PJB_NO_SEQ2") && atoi(getenv("PJB_NO_SEQ2")) != 0;
     if (!no_seq2) { // the bases in 2 bits as well (what pjb_batch.seq2 / .seq_exc hold): written where the 4-bit bases are
         B.seq2 = (unsigned short *)slab_alloc(c, oc, ((size_t)n_words + 2) * 2 + 16);
         B.seq_exc = (iu32 *)slab_alloc(c, oc, ((n + 31) / 32) * 4 + 16);
-        if (!B.seq2 || !B.seq_exc) return fail(c, PJB_ERR_NOMEM, "submit_bam: out of device memory for the 2-bit bases");
+        if (!B.seq2 || !B.seq_exc) return nomem(c, "submit_bam: the 2-bit bases", ((size_t)n_words + 2) * 2 + ((n + 31) / 32) * 4 + 32);
     }
     LAUNCH(c, "bam_transcode", bam_transcode, dim3((unsigned)((n + 255) / 256)), dim3(256), R.U, (const iu64 *)c->b_bam_rec.p, (iu64)n, B);
     HIP_TRY(c, hipStreamSynchronize(st)); // `tails` is on this stack frame
@@ -462,6 +462,8 @@ static int ingest_staged(pjb_ctx *c, int32_t tid, OpenContig &oc, const uint8_t 
     return ingest_parse(c, tid, oc, (const uint8_t *)c->b_inf_out.p, blocks.size(), comp_bytes, total, first_uoffset, n_records, t_scan, t_up, wall_now() - t0);
 }
 
+static int submit_bam_body(pjb_ctx *c, int32_t tid, OpenContig &oc, const uint8_t *comp, int64_t comp_bytes, int32_t first_uoffset, int64_t *n_records);
+
 extern "C" int pjb_submit_bam(pjb_ctx *c, int32_t tid, const uint8_t *comp, int64_t comp_bytes, int32_t first_uoffset,
                               int64_t *n_records) {
     if (!c) return PJB_ERR_ARG;
@@ -472,6 +474,13 @@ extern "C" int pjb_submit_bam(pjb_ctx *c, int32_t tid, const uint8_t *comp, int6
     HIP_TRY(c, hipSetDevice(c->cfg.device));
     OpenContig &oc = c->open[tid];
     if (!oc.batches.empty()) return fail(c, PJB_ERR_STATE, "submit_bam: target %d already has batches (one call per target)", tid);
+    const SlabMark mark = slab_mark(c, oc);
+    const int rc = submit_bam_body(c, tid, oc, comp, comp_bytes, first_uoffset, n_records);
+    if (rc == PJB_ERR_NOMEM) slab_rollback(c, oc, mark); // (retryable: the target is as it was)
+    return rc;
+}
+
+static int submit_bam_body(pjb_ctx *c, int32_t tid, OpenContig &oc, const uint8_t *comp, int64_t comp_bytes, int32_t first_uoffset, int64_t *n_records) {
     const bool prof = getenv("PJB_PROFILE_HOST") != nullptr;
     double t0 = wall_now(), t_scan, t_up;
     std::vector<InfBlock> blocks;
@@ -516,22 +525,28 @@ static int pool_take(pjb_ctx *c, std::vector<Buf> &pool, Buf &b, size_t bytes) {
     if (best >= 0) {
         b = pool[(size_t)best];
         pool.erase(pool.begin() + best);
+        std::lock_guard<std::mutex> lk(c->mem.mu);
+        c->mem.pooled_stage -= std::min(b.cap, c->mem.pooled_stage);
         return PJB_OK;
     }
-    return ensure(c, b, bytes);
+    return ensure_cat(c, b, bytes, MEM_STAGING);
 }
-static void pool_give(std::vector<Buf> &pool, Buf &b) {
-    if (b.p) pool.push_back(b);
+static void pool_give(pjb_ctx *c, std::vector<Buf> &pool, Buf &b) {
+    if (b.p) {
+        pool.push_back(b);
+        std::lock_guard<std::mutex> lk(c->mem.mu);
+        c->mem.pooled_stage += b.cap;
+    }
     b.p = nullptr;
     b.cap = 0;
 }
 static void stage_release(pjb_ctx *c, BamStage &st) { // (after the work that uses the buffers has completed)
-    pool_give(c->stage_pool, st.dev);
-    pool_give(c->out_pool, st.out);
-    pool_give(c->misc_pool, st.d_blocks);
-    pool_give(c->misc_pool, st.d_status);
-    pool_give(c->misc_pool, st.d_scratch);
-    pool_give(c->out_pool, st.d_bitmap); // (output-sized: an eighth of the inflated bytes)
+    pool_give(c, c->stage_pool, st.dev);
+    pool_give(c, c->out_pool, st.out);
+    pool_give(c, c->misc_pool, st.d_blocks);
+    pool_give(c, c->misc_pool, st.d_status);
+    pool_give(c, c->misc_pool, st.d_scratch);
+    pool_give(c, c->out_pool, st.d_bitmap); // (output-sized: an eighth of the inflated bytes)
     if (st.ev_inf) (void)hipEventDestroy(st.ev_inf);
     if (st.ev_last) (void)hipEventDestroy(st.ev_last);
     st.ev_inf = st.ev_last = nullptr;
@@ -604,10 +619,7 @@ void bam_stage_clear(pjb_ctx *c) {
         delete kv.second;
     }
     c->bam_stage.clear();
-    for (auto *pool : {&c->stage_pool, &c->out_pool, &c->misc_pool}) {
-        for (auto &b : *pool) release(b);
-        pool->clear();
-    }
+    release_pooled_stage(c);
     for (auto &is : c->inf_streams)
         if (is) (void)hipStreamDestroy(is);
     for (auto &ev : c->up_events)
@@ -619,7 +631,7 @@ void bam_stage_clear(pjb_ctx *c) {
 extern "C" int pjb_bam_begin(pjb_ctx *c, int32_t tid, int64_t total_bytes) {
     if (!c) return PJB_ERR_ARG;
     if (tid < 0 || (size_t)tid >= c->ref_len.size() || total_bytes <= 0) return fail(c, PJB_ERR_ARG, "bam_begin: bad arguments (tid %d)", tid);
-    std::lock_guard<std::mutex> lk(c->bam_mu);
+    BamLock lk(c);
     if (c->bam_stage.count(tid)) return fail(c, PJB_ERR_STATE, "bam_begin: target %d is being staged already", tid);
     // (that the target has no batches yet is checked by pjb_bam_end, on the thread that owns the open targets)
     HIP_TRY(c, hipSetDevice(c->cfg.device));
@@ -632,7 +644,7 @@ extern "C" int pjb_bam_begin(pjb_ctx *c, int32_t tid, int64_t total_bytes) {
     if (!c->stream_up) he = hipStreamCreateWithFlags(&c->stream_up, hipStreamNonBlocking);
     if (he == hipSuccess) he = hipMemsetAsync((uint8_t *)st->dev.p + total_bytes, 0, INF_PAD, c->stream_up);
     if (he != hipSuccess) {
-        pool_give(c->stage_pool, st->dev);
+        pool_give(c, c->stage_pool, st->dev);
         return fail(c, PJB_ERR_HIP, "bam_begin: %s", hipGetErrorString(he));
     }
     c->bam_stage[tid] = st.release();
@@ -643,7 +655,7 @@ static int bam_piece_body(pjb_ctx *c, int32_t tid, BamStage &st, const uint8_t *
 
 extern "C" int pjb_bam_piece(pjb_ctx *c, int32_t tid, const uint8_t *piece, int64_t bytes, int64_t *ticket) {
     if (!c || !piece || bytes <= 0) return fail(c, PJB_ERR_ARG, "bam_piece: bad arguments");
-    std::lock_guard<std::mutex> lk(c->bam_mu);
+    BamLock lk(c);
     auto it = c->bam_stage.find(tid);
     if (it == c->bam_stage.end()) return fail(c, PJB_ERR_STATE, "bam_piece: target %d was not begun (pjb_bam_begin)", tid);
     const int rc = bam_piece_body(c, tid, *it->second, piece, bytes, ticket);
@@ -701,7 +713,7 @@ static int bam_piece_body(pjb_ctx *c, int32_t tid, BamStage &st, const uint8_t *
 
 extern "C" int pjb_bam_inflate_done(pjb_ctx *c, int32_t tid) {
     if (!c) return 1;
-    std::lock_guard<std::mutex> lk(c->bam_mu);
+    BamLock lk(c);
     auto it = c->bam_stage.find(tid);
     if (it == c->bam_stage.end() || !it->second->launched) return 1; // (nothing in flight: pjb_bam_end does all the work)
     const bool done = hipEventQuery(it->second->ev_inf) == hipSuccess;
@@ -711,7 +723,7 @@ extern "C" int pjb_bam_inflate_done(pjb_ctx *c, int32_t tid) {
 
 extern "C" int pjb_bam_pieces_done(pjb_ctx *c, int64_t *completed_ticket) {
     if (!c || !completed_ticket) return PJB_ERR_ARG;
-    std::lock_guard<std::mutex> lk(c->bam_mu);
+    BamLock lk(c);
     while (c->up_done < c->up_ticket) {
         hipEvent_t ev = c->up_events[(size_t)((c->up_done + 1) % (int64_t)PJB_UP_EVENTS)];
         if (!ev || hipEventQuery(ev) != hipSuccess) break;
@@ -722,28 +734,41 @@ extern "C" int pjb_bam_pieces_done(pjb_ctx *c, int64_t *completed_ticket) {
     return PJB_OK;
 }
 
+static int bam_end_body(pjb_ctx *c, int32_t tid, BamStage &stage, int32_t first_uoffset, int64_t *n_records, bool *keep);
+
 extern "C" int pjb_bam_end(pjb_ctx *c, int32_t tid, int32_t first_uoffset, int64_t *n_records) {
     if (!c) return PJB_ERR_ARG;
     if (n_records) *n_records = 0;
     std::unique_ptr<BamStage> st;
     {
-        std::lock_guard<std::mutex> lk(c->bam_mu);
+        BamLock lk(c);
         auto it = c->bam_stage.find(tid);
         if (it == c->bam_stage.end()) return fail(c, PJB_ERR_STATE, "bam_end: target %d was not begun (pjb_bam_begin)", tid);
         st.reset(it->second);
         c->bam_stage.erase(it);
     }
-    struct Return { // the device buffer goes back to the pool whatever happens (after the work that reads it)
+    struct Return { // the device buffer goes back to the pool whatever happens (after the work that reads it) -- unless the call ran out of
+                    // device memory: then the stage is the context's again, pieces and inflate as they are, and the call can be repeated
         pjb_ctx *c;
-        BamStage *st;
+        std::unique_ptr<BamStage> &st;
+        int32_t tid;
+        bool keep;
         ~Return() {
             (void)hipStreamSynchronize(c->stream);
             if (st->launched) (void)hipEventSynchronize(st->ev_inf); // (the inflate waited for the target's last copy)
             else if (c->stream_up) (void)hipStreamSynchronize(c->stream_up); // early returns: the copies may still read the caller's buffers
-            std::lock_guard<std::mutex> lk(c->bam_mu);
-            stage_release(c, *st);
+            BamLock lk(c);
+            if (keep) c->bam_stage[tid] = st.release();
+            else stage_release(c, *st);
         }
-    } ret{c, st.get()};
+    } ret{c, st, tid, false};
+    const int rc = bam_end_body(c, tid, *st, first_uoffset, n_records, &ret.keep);
+    return rc;
+}
+
+// (*keep: the call failed with PJB_ERR_NOMEM behind its argument checks; the target's slabs are as they were)
+static int bam_end_body(pjb_ctx *c, int32_t tid, BamStage &stage, int32_t first_uoffset, int64_t *n_records, bool *keep) {
+    BamStage *st = &stage;
     c->cur_tid = tid;
     HIP_TRY(c, hipSetDevice(c->cfg.device));
     if (first_uoffset < 0) return fail(c, PJB_ERR_ARG, "bam_end: bad first_uoffset");
@@ -752,19 +777,28 @@ extern "C" int pjb_bam_end(pjb_ctx *c, int32_t tid, int32_t first_uoffset, int64
     OpenContig &oc = c->open[tid];
     if (!oc.batches.empty()) return fail(c, PJB_ERR_STATE, "bam_end: target %d already has batches (one call per target)", tid);
     if (st->total_out == 0 || (int64_t)first_uoffset >= st->total_out) return PJB_OK;
+    const SlabMark mark = slab_mark(c, oc);
+    int rc;
     if (st->launched) { // the inflate started with the last piece: wait for it, look at its status words, go on with the records
-            const double t0 = wall_now();
+        const double t0 = wall_now();
         HIP_TRY(c, hipEventSynchronize(st->ev_inf));
-        int rc = inflate_status(c, st->blocks, (const int *)st->d_status.p);
+        rc = inflate_status(c, st->blocks, (const int *)st->d_status.p);
         if (rc) return rc;
-        return ingest_parse(c, tid, oc, (const uint8_t *)st->out.p, st->blocks.size(), st->total, st->total_out, first_uoffset, n_records, st->t_scan, st->t_up,
-                            wall_now() - t0);
+        rc = ingest_parse(c, tid, oc, (const uint8_t *)st->out.p, st->blocks.size(), st->total, st->total_out, first_uoffset, n_records, st->t_scan, st->t_up,
+                          wall_now() - t0);
+    } else {
+        // the service stream picks up behind the last copy
+        if (!c->ev_up) HIP_TRY(c, hipEventCreateWithFlags(&c->ev_up, hipEventDisableTiming));
+        HIP_TRY(c, hipEventRecord(c->ev_up, c->stream_up));
+        HIP_TRY(c, hipStreamWaitEvent(c->stream, c->ev_up, 0));
+        rc = ingest_staged(c, tid, oc, (const uint8_t *)st->dev.p, st->blocks, st->total, st->total_out, first_uoffset, n_records, st->t_scan, st->t_up);
     }
-    // the service stream picks up behind the last copy
-    if (!c->ev_up) HIP_TRY(c, hipEventCreateWithFlags(&c->ev_up, hipEventDisableTiming));
-    HIP_TRY(c, hipEventRecord(c->ev_up, c->stream_up));
-    HIP_TRY(c, hipStreamWaitEvent(c->stream, c->ev_up, 0));
-    return ingest_staged(c, tid, oc, (const uint8_t *)st->dev.p, st->blocks, st->total, st->total_out, first_uoffset, n_records, st->t_scan, st->t_up);
+    if (rc == PJB_ERR_NOMEM) { // (retryable: the target and its stage are as they were)
+        slab_rollback(c, oc, mark);
+        if (n_records) *n_records = 0;
+        *keep = true;
+    }
+    return rc;
 }
 
 
@@ -796,7 +830,7 @@ static void index_clear(pjb_ctx *c) {
     if (!x) return;
     for (Buf *b : {&x->chunks, &x->lin, &x->ref_len, &x->lin_off, &x->key, &x->vs, &x->win, &x->w0, &x->heads, &x->tab, &x->ctl, &x->tile_max, &x->q[0], &x->q[1],
                    &x->q[2], &x->tid_start, &x->sorted})
-        release(*b);
+        release(c, *b);
     delete x;
     c->index = nullptr;
 }

@@ -28,7 +28,9 @@ EXPORTS = [
     "pjb_extra_finish", "pjb_set_option", "pjb_merge_rows", "pjb_plan_groups", "pjb_bam_begin", "pjb_bam_piece", "pjb_bam_pieces_done", "pjb_bam_end", "pjb_bam_inflate_done", "pjb_filter_set_junctions", "pjb_filter_batch", "pjb_filt_features",
     "pjb_index_begin", "pjb_index_piece", "pjb_index_end",
     "pjb_forest_check", "pjb_forest_load", "pjb_forest_predict", "pjb_filt_scores", "pjb_forest_grow", "pjb_knn",
+    "pjb_memory_info",
 ]
+ERR_NOMEM = -15  # PJB_ERR_NOMEM
 N_FEATURES = 34
 KMER_TABLE = 3125 * 5
 PW_LEN = 32
@@ -83,6 +85,12 @@ class PjbIndexResult(C.Structure):
     _fields_ = [("n_records", C.c_int64), ("n_chunks", C.c_int64), ("chunks", C.c_void_p), ("lin_off", C.c_void_p), ("lin", C.c_void_p)]
 
 
+class PjbMemory(C.Structure):  # pjb_memory
+    _fields_ = [(k, C.c_uint64) for k in ("genomes", "slabs_open", "slabs_pooled", "staging", "scratch", "rows", "other", "held", "limit",
+                                          "peak_held", "peak_records", "largest_target_bytes")] + [("largest_target", C.c_int64)] + \
+               [(k, C.c_uint64) for k in ("hip_free", "hip_total")]
+
+
 class PjbKernelTime(C.Structure):
     _fields_ = [("name", C.c_char * 32), ("launches", C.c_int64), ("total_ms", C.c_double)]
 
@@ -110,6 +118,8 @@ class PjbError(RuntimeError):
     def __init__(self, code, msg):
         super().__init__(f"pjb error {code}: {msg}")
         self.code = code
+        # PJB_ERR_NOMEM from a submit / piece / end call left the target as it was: free device memory (collect a chain), repeat the call
+        self.retryable = code == ERR_NOMEM
 
 
 _LIB = None
@@ -186,6 +196,7 @@ def load():
         L.pjb_get_kernel_timing.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(C.c_int32)]
         L.pjb_reset_kernel_timing.argtypes = [C.c_void_p]
         L.pjb_select_timed_kernels.argtypes = [C.c_void_p, C.c_char_p]
+        L.pjb_memory_info.argtypes = [C.c_void_p, C.POINTER(PjbMemory)]
         _LIB = L
     return _LIB
 
@@ -386,6 +397,12 @@ class Context:
     def set_option(self, name, value):
         self._check(self._L.pjb_set_option(self._h, name.encode(), int(value)))
 
+    def memory_info(self):
+        """The device memory the context holds, in bytes, category by category (pjb_memory_info): a dict of pjb_memory's fields."""
+        m = PjbMemory()
+        self._check(self._L.pjb_memory_info(self._h, C.byref(m)))
+        return {k: int(getattr(m, k)) for k, _ in PjbMemory._fields_}
+
     def finish_contig_begin(self, tid):
         """Queue the contig's kernel chain without waiting (at most MAX_QUEUED contigs queued; collect in the same order)."""
         try:
@@ -572,11 +589,17 @@ class Context:
             self._check(self._L.pjb_bam_piece(self._h, tid, piece.ctypes.data_as(C.c_void_p), nb, C.byref(last)))
             at += nb
             k += 1
-        n = C.c_int64()
-        self._check(self._L.pjb_bam_end(self._h, tid, first_uoffset, C.byref(n)))
+        n = self.bam_end(tid, first_uoffset)
         done = C.c_int64()
         self._check(self._L.pjb_bam_pieces_done(self._h, C.byref(done)))
         assert done.value >= last.value  # (everything was consumed by _end)
+        return n
+
+    def bam_end(self, tid, first_uoffset):
+        """pjb_bam_end alone: what submit_bam_pieces ends with.  After a PjbError with .retryable the target's staged pieces are still
+        the context's: free device memory and call this again -- no piece is sent twice."""
+        n = C.c_int64()
+        self._check(self._L.pjb_bam_end(self._h, tid, first_uoffset, C.byref(n)))
         return n.value
 
     def submit_bam(self, tid, comp, first_uoffset):

@@ -74,6 +74,7 @@ class JunctionBuilder {
     std::string source = DEFAULT_JUNC_SOURCE;
     bool verbose = false;
     int devices = 0;               // 0 = every visible GPU
+    uint64_t deviceMem = 0;        // --device_mem: bytes of device memory the run may hold on one GPU (0: no budget of its own)
     int hostThreads = 0;           // 0 = use `threads`; otherwise total host decode threads
     size_t batchRecords = 1 << 20; // alignments per batch sent to the device
     int innerThreads = 1;          // decode threads inside one target sequence (set by findJunctions)
@@ -154,6 +155,12 @@ public:
     // additions of this implementation
     int getDevices() const { return devices; }
     void setDevices(int n) { devices = n; }
+    // The device-memory budget per GPU, in bytes (0: none): contexts that share a GPU get equal shares of it (pjb_set_option "mem_limit").
+    // A run whose group chains do not fit falls back to a chain per target; it ends with an error only if one target alone does not fit.
+    void setDeviceMem(uint64_t bytes) { deviceMem = bytes; }
+    uint64_t getDeviceMem() const { return deviceMem; }
+    // the size grammar of --device_mem and PORTCULLIS_DEVICE_MEM: an integer with an optional K, M or G (powers of 1024); anything else throws
+    static uint64_t parseDeviceMem(const std::string& text);
     void setBatchRecords(size_t n) { batchRecords = n ? n : 1; }
     void setDeviceIngest(bool on) { deviceIngest = on; }
     bool isDeviceIngest() const { return deviceIngest; }

@@ -24,6 +24,9 @@ DeviceThread::DeviceThread(int device, const Setup& setup, std::vector<std::vect
         for (int32_t t : plan[g]) groupOf[t] = g;
     waiting.resize(plan.size());
     printPlan = setup.printPlan;
+    memLimit = setup.memLimit;
+    report = setup.report;
+    names = setup.names;
     th = std::thread([this, device, setup] { run(device, setup); });
 }
 
@@ -48,6 +51,8 @@ void DeviceThread::createContext(int device, const Setup& setup) {
         if (pjb_create(&ctx, &cfg) != PJB_OK) throw JunctionBuilderException(std::string("pjb_create: ") + pjb_last_error(nullptr));
         if (pjb_set_refs(ctx, (int32_t)setup.lens.size(), setup.lens.data()) != PJB_OK)
             throw JunctionBuilderException(std::string("pjb_set_refs: ") + pjb_last_error(ctx));
+        if (memLimit && pjb_set_option(ctx, "mem_limit", (int64_t)memLimit) != PJB_OK)
+            throw JunctionBuilderException(std::string("pjb_set_option: ") + pjb_last_error(ctx));
     } catch (const std::exception& e) {
         fatal = e.what();
     }
@@ -79,8 +84,8 @@ void DeviceThread::run(int device, const Setup& setup) {
         serve(c);
         const double t1 = HostProfile::now();
         tKind[(int)c.kind & 15] += t1 - t0;
-        static const char* names[] = {"GENOME", "BATCH", "BAM", "FINISH", "EXTRA", "STOP", "BAMEND", "FLUSH"};
-        if (g_prof.events_on) g_prof.event(t0, t1, "dev" + std::to_string(profId) + " " + names[c.kind] + " tid " + std::to_string(c.tid));
+        static const char* kinds[] = {"GENOME", "BATCH", "BAM", "FINISH", "EXTRA", "STOP", "BAMEND", "FLUSH", "ROOM"};
+        if (g_prof.events_on) g_prof.event(t0, t1, "dev" + std::to_string(profId) + " " + kinds[c.kind] + " tid " + std::to_string(c.tid));
         if (c.kind == Cmd::STOP) break;
     }
     if (ctx) pjb_destroy(ctx);
@@ -150,10 +155,53 @@ void DeviceThread::flushChains() {
     while (!pending.empty()) collectOldest();
 }
 
+// ---- device memory -----------------------------------------------------------------------------------------------------------
+
+bool DeviceThread::makeRoom() {
+    for (size_t g = 0; g < waiting.size(); g++) {
+        Waiting& w = waiting[g];
+        if (w.single || w.begun || plan[g].size() < 2) continue;
+        w.single = true;
+        flushedEarly++;
+        if (printPlan) {
+            std::string txt;
+            for (auto& x : w.got) txt += (txt.empty() ? "" : ",") + std::to_string(x.first);
+            cerr << "[chain] device memory ran short: group " << g << " of the plan goes target by target (present: " << (txt.empty() ? "none" : txt) << ")" << endl;
+        }
+        beginGroup(w);  // (what is present of it, as chains of their own)
+    }
+    if (pending.empty()) return false;
+    collectOldest();
+    return true;
+}
+
+std::string DeviceThread::memoryAdvice(int32_t tid) const {
+    const std::string name = tid >= 0 && (size_t)tid < names.size() ? names[(size_t)tid] : std::to_string(tid);
+    return " -- target " + name + " does not fit the device memory this run may hold (limit " + (memLimit ? std::to_string(memLimit) + " bytes" : std::string("none: the device is full")) +
+           "): give the run more with a larger --device_mem, or spread its targets over more GPUs with --devices N";
+}
+
+std::string DeviceThread::describe(const char* call, int rc, int32_t tid) const {
+    std::string msg = std::string(call) + ": " + pjb_last_error(ctx);
+    if (rc == PJB_ERR_NOMEM) msg += memoryAdvice(tid);
+    return msg;
+}
+
+// (one call, when the thread stops: the library keeps the peak, what the slabs held at that moment and the largest target itself)
+void DeviceThread::reportMemory() {
+    pjb_memory m;
+    if (!report || !ctx || pjb_memory_info(ctx, &m) != PJB_OK) return;
+    const int64_t big = m.largest_target;
+    std::lock_guard<std::mutex> lk(g_prof.mu);
+    cerr << "[memory] peak held " << m.peak_held << " (records " << m.peak_records << ", other " << m.peak_held - m.peak_records << "); limit "
+         << (m.limit ? std::to_string(m.limit) : std::string("none")) << "; groups flushed early: " << flushedEarly << "; largest target: "
+         << (big < 0 ? std::string("none") : (size_t)big < names.size() ? names[(size_t)big] : std::to_string(big)) << " " << m.largest_target_bytes << endl;
+}
+
 void DeviceThread::beginSingle(int32_t tid, std::promise<ContigDone>* done) {
     while (pending.size() >= kQueued) collectOldest();
-    if (pjb_finish_contig_begin(ctx, tid) != PJB_OK) {
-        const std::string err = std::string("pjb_finish_contig: ") + pjb_last_error(ctx);
+    if (const int rc = pjb_finish_contig_begin(ctx, tid)) {
+        const std::string err = describe("pjb_finish_contig", rc, tid);
         (void)pjb_release_contig(ctx, tid);
         done->set_exception(std::make_exception_ptr(JunctionBuilderException(err)));
     } else {
@@ -178,6 +226,7 @@ void DeviceThread::beginGroup(Waiting& w) {
             cerr << "[chain] group " << txt << endl;
         }
         g_prof.mark(("chain queued: group of " + std::to_string(tids.size()) + " from target " + std::to_string(tids[0])).c_str());
+        w.begun = true;
         pending.push_back(Pending{tids[0], nullptr, tids, dones});
         return;
     }
@@ -272,7 +321,7 @@ void DeviceThread::serve(Cmd& c) {
         if (err.empty()) {
             pjb_batch pb;
             c.batch.view(pb);
-            if (pjb_submit_batch(ctx, c.tid, &pb) != PJB_OK) failed[c.tid] = std::string("pjb_submit_batch: ") + pjb_last_error(ctx);
+            if (const int rc = withRoom([&] { return pjb_submit_batch(ctx, c.tid, &pb); })) failed[c.tid] = describe("pjb_submit_batch", rc, c.tid);
         }
         if (c.spare) {
             std::lock_guard<std::mutex> lk(*c.spareMu);
@@ -281,8 +330,10 @@ void DeviceThread::serve(Cmd& c) {
         break;
     case Cmd::BAM: {
         int64_t n = 0;
-        if (err.empty() && pjb_submit_bam(ctx, c.tid, c.bamBytes, (int64_t)c.bamSize, (int32_t)c.bamFirst, &n) != PJB_OK)
-            failed[c.tid] = std::string("pjb_submit_bam: ") + pjb_last_error(ctx) + kTryHostIngest;
+        if (err.empty()) {
+            if (const int rc = withRoom([&] { return pjb_submit_bam(ctx, c.tid, c.bamBytes, (int64_t)c.bamSize, (int32_t)c.bamFirst, &n); }))
+                failed[c.tid] = describe("pjb_submit_bam", rc, c.tid) + (rc == PJB_ERR_NOMEM ? "" : kTryHostIngest);
+        }
         bam::bigFree(c.bamBytes);
         c.bamDone->set_value(n);
         break;
@@ -290,12 +341,15 @@ void DeviceThread::serve(Cmd& c) {
     case Cmd::BAMEND: {
         int64_t n = 0;
         if (!err.empty() && ctx) (void)pjb_bam_end(ctx, c.tid, (int32_t)c.bamFirst, nullptr);  // (drops what was staged)
-        if (err.empty() && pjb_bam_end(ctx, c.tid, (int32_t)c.bamFirst, &n) != PJB_OK)
-            failed[c.tid] = std::string("pjb_bam_end: ") + pjb_last_error(ctx) + kTryHostIngest;
+        if (err.empty()) {
+            if (const int rc = withRoom([&] { return pjb_bam_end(ctx, c.tid, (int32_t)c.bamFirst, &n); }))
+                failed[c.tid] = describe("pjb_bam_end", rc, c.tid) + (rc == PJB_ERR_NOMEM ? "" : kTryHostIngest);
+        }
         c.bamDone->set_value(n);
         break;
     }
     case Cmd::FLUSH: flushChains(); break;  // (no more targets will come: what still waits for the rest of its group goes now)
+    case Cmd::ROOM: c.roomDone->set_value(ctx != nullptr && makeRoom()); break;
     case Cmd::FINISH: serveFinish(c, err); break;
     case Cmd::EXTRA: {
         while (!pending.empty()) collectOldest();
@@ -308,6 +362,7 @@ void DeviceThread::serve(Cmd& c) {
     }
     case Cmd::STOP:
         flushChains();
+        reportMemory();
         if (g_prof.on) {
             std::lock_guard<std::mutex> lk(g_prof.mu);
             cerr << "[host profile] device thread: alive " << (HostProfile::now() - tStart) << " s: idle " << tIdle << ", collect " << tCollect
@@ -321,15 +376,17 @@ void DeviceThread::serve(Cmd& c) {
 void DeviceThread::serveGenome(Cmd& c, const std::string& err) {
     if (c.rawDone) {
         int ok = 0;
-        if (err.empty() && pjb_upload_contig_fasta(ctx, c.tid, c.raw, (int64_t)c.rawBytes, c.lineBases, c.lineWidth, c.genomeLen, &ok) != PJB_OK) {
-            failed[c.tid] = std::string("pjb_upload_contig_fasta: ") + pjb_last_error(ctx);
+        int rc = PJB_OK;
+        if (err.empty() && (rc = pjb_upload_contig_fasta(ctx, c.tid, c.raw, (int64_t)c.rawBytes, c.lineBases, c.lineWidth, c.genomeLen, &ok)) != PJB_OK) {
+            failed[c.tid] = describe("pjb_upload_contig_fasta", rc, c.tid);
             ok = 1;  // (an error, not a malformed record: no second attempt)
         }
         if (c.rawPool) c.rawPool->release(c.raw);
         c.rawDone->set_value(ok != 0 || !err.empty());
     } else {
-        if (err.empty() && pjb_upload_contig(ctx, c.tid, (const uint8_t*)c.genome.data(), (int64_t)c.genome.size()) != PJB_OK)
-            failed[c.tid] = std::string("pjb_upload_contig: ") + pjb_last_error(ctx);
+        int rc = PJB_OK;
+        if (err.empty() && (rc = pjb_upload_contig(ctx, c.tid, (const uint8_t*)c.genome.data(), (int64_t)c.genome.size())) != PJB_OK)
+            failed[c.tid] = describe("pjb_upload_contig", rc, c.tid);
     }
 }
 

@@ -32,7 +32,7 @@ struct ContigDone {
 class DeviceThread {
 public:
     struct Cmd {
-        enum Kind { GENOME, BATCH, BAM, FINISH, EXTRA, STOP, BAMEND, FLUSH } kind;
+        enum Kind { GENOME, BATCH, BAM, FINISH, EXTRA, STOP, BAMEND, FLUSH, ROOM } kind;
         int32_t tid;
         explicit Cmd(Kind k, int32_t t = -1) : kind(k), tid(t) {}
         std::string genome;
@@ -55,6 +55,7 @@ public:
         uint32_t bamFirst = 0;
         std::promise<int64_t>* bamDone = nullptr;
         std::promise<std::vector<pjb_extra_row>>* extraDone = nullptr;  // EXTRA: calcExtraMetrics for every row so far
+        std::promise<bool>* roomDone = nullptr;  // ROOM: a worker's pjb_bam_begin ran out of device memory -- true: a chain was collected, try again
     };
 
     // what every device thread of a run is made with
@@ -66,6 +67,9 @@ public:
         bool extra = false;
         bool shareGpu = false;   // PORTCULLIS_DEVICES_SHARE_GPU
         bool printPlan = false;  // PJB_PRINT_CHAIN_PLAN
+        uint64_t memLimit = 0;   // --device_mem: this context's share (pjb_set_option "mem_limit"; 0: none)
+        bool report = false;     // -v / PJB_PROFILE_HOST: the [memory] line when the thread stops
+        std::vector<std::string> names;  // the targets' names (messages)
     };
     DeviceThread(int device, const Setup& setup, std::vector<std::vector<int32_t>> chainPlan = {});
     ~DeviceThread();  // STOP, then joins the thread (which destroys the context)
@@ -83,6 +87,18 @@ public:
         return sharedCtx;
     }
     bool grouped() const { return !plan.empty(); }
+    // A worker's own pjb_bam_begin returned PJB_ERR_NOMEM (pjb_bam_piece never does: it allocates nothing the target needs): this thread
+    // makes room as it does for its own calls (makeRoom).  true: something was collected, repeat the call.
+    bool askForRoom() {
+        std::promise<bool> p;
+        std::future<bool> f = p.get_future();
+        Cmd c(Cmd::ROOM);
+        c.roomDone = &p;
+        push(std::move(c));
+        return f.get();
+    }
+    // what a run that ends for want of device memory tells the user: the target, the library's figures, the ways out
+    std::string memoryAdvice(int32_t tid) const;
     int lane = 0;  // index among the device threads (the transfer gate of this context)
     void push(Cmd&& c) {
         std::unique_lock<std::mutex> lk(mu);
@@ -122,7 +138,8 @@ private:
     std::map<int32_t, size_t> groupOf;  // target -> its group in `plan`
     struct Waiting {                    // the members of a group that have been asked for so far
         std::vector<std::pair<int32_t, std::promise<ContigDone>*>> got;
-        bool single = false; // a member failed, or the library said "not as a group": the members go one by one
+        bool single = false; // a member failed, the library said "not as a group", or device memory ran short: the members go one by one
+        bool begun = false;  // the group has been queued as one chain
     };
     std::vector<Waiting> waiting;  // per group of `plan`
     // Targets are QUEUED on the device (pjb_finish_contig_begin) and collected later (_end): the kernel chains of up
@@ -144,6 +161,27 @@ private:
     void collectOldest();
     void collectReady();  // every chain that has completed, without waiting for one that has not
     void flushChains();   // what still waits for the rest of its group is queued, every queued chain is collected
+
+    // ---- device memory (--device_mem, or a device that is simply full)
+    // A submit call (pjb_submit_batch, pjb_submit_bam, pjb_bam_end) that returns PJB_ERR_NOMEM has left its target as it was: makeRoom marks
+    // every group that still waits for members as `single`, queues what is present of them as chains of their own, and collects the oldest
+    // queued chain -- whose slabs go back to the pool --; withRoom repeats the call until it succeeds or nothing is left to collect, and
+    // then once more.
+    bool makeRoom();
+    template <typename F>
+    int withRoom(F call) {
+        int rc;
+        while ((rc = call()) == PJB_ERR_NOMEM && makeRoom()) {
+        }
+        if (rc == PJB_ERR_NOMEM) rc = call();  // (nothing is left to collect: the repeat gets the library's last resort, slabs of exactly the bytes needed)
+        return rc;
+    }
+    std::string describe(const char* call, int rc, int32_t tid) const;  // "<call>: <the library's message>", with memoryAdvice after PJB_ERR_NOMEM
+    uint64_t memLimit = 0;
+    bool report = false;
+    std::vector<std::string> names;
+    size_t flushedEarly = 0;                 // groups that went target by target because memory ran short
+    void reportMemory();
 
     void run(int device, const Setup& setup);
     void createContext(int device, const Setup& setup);

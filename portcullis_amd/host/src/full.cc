@@ -26,6 +26,7 @@ string Full::helpMessage() {
            "System options:\n"
            "  -t [ --threads ] arg (=1)        The number of threads to use.  Note that increasing the number of threads will also increase memory requirements.  Default: 1\n"
            "  --devices arg                    Number of GPUs offered to junc and filt (default: all visible)\n"
+           "  --device_mem arg                 Device memory junc may hold on one GPU: an integer with an optional K, M or G, as junc --device_mem (default: no budget)\n"
            "  -v [ --verbose ]                 Print extra information\n"
            "  --help                           Produce help message\n\n"
            "Output options:\n"
@@ -65,6 +66,7 @@ int Full::main(int argc, char* argv[]) {
     string outputDir = DEFAULT_FULL_OUTPUT, referenceFile, strand = "UNKNOWN", ori = "UNKNOWN", source = "portcullis", canonical = "OFF";
     string selfTrainDir, trainingRule = "balanced";
     int threads = 1, devices = 0;
+    uint64_t deviceMem = 0;
     bool separate = false, extra = false, copy = false, keepTemp = false, force = false, useCsi = false, saveBad = false, exongff = false,
          introngff = false, bamFilter = false, saveLayers = false, saveFeatures = false, verbose = false, help = false;
     uint32_t maxLength = 0, minCov = 1;
@@ -84,6 +86,7 @@ int Full::main(int argc, char* argv[]) {
         };
         if (a == "-t" || a == "--threads") threads = std::stoi(need());
         else if (a == "--devices") devices = std::stoi(need());
+        else if (a == "--device_mem") deviceMem = JunctionBuilder::parseDeviceMem(need());
         else if (a == "-v" || a == "--verbose") verbose = true;
         else if (a == "--help") help = true;
         else if (a == "-o" || a == "--output") outputDir = need();
@@ -173,6 +176,7 @@ int Full::main(int argc, char* argv[]) {
         jb.setOutputIntronGFF(introngff);
         jb.setVerbose(verbose);
         if (devices > 0) jb.setDevices(devices);
+        if (deviceMem > 0) jb.setDeviceMem(deviceMem);
         jb.setTeardown(juncDown);
         jb.process();
     }

@@ -80,7 +80,27 @@ struct JuncEnv {
     int chainGroups = envIs("PORTCULLIS_CHAIN_PLAN", "groups");                        // [groups for file-piece ingest with one context, else targets]
     int64_t groupBases = getenv("PORTCULLIS_GROUP_BASES") ? atoll(getenv("PORTCULLIS_GROUP_BASES")) : 0;  // (0: pjb_plan_groups' own 2^30)
     bool printPlan = getenv("PJB_PRINT_CHAIN_PLAN") != nullptr;
+    const char* deviceMem = getenv("PORTCULLIS_DEVICE_MEM");                           // as --device_mem <size>
 };
+
+uint64_t JunctionBuilder::parseDeviceMem(const std::string& text) {
+    const std::string why = "--device_mem takes a number of bytes, optionally followed by K, M or G (powers of 1024): '" + text + "'";
+    size_t k = 0;
+    uint64_t v = 0;
+    for (; k < text.size() && text[k] >= '0' && text[k] <= '9'; k++) {
+        if (v > (UINT64_MAX - 9) / 10) throw JunctionBuilderException(why);
+        v = v * 10 + (uint64_t)(text[k] - '0');
+    }
+    if (k == 0 || text.size() > k + 1) throw JunctionBuilderException(why);
+    int shift = 0;
+    if (k < text.size()) {
+        const char u = text[k];
+        shift = u == 'K' || u == 'k' ? 10 : u == 'M' || u == 'm' ? 20 : u == 'G' || u == 'g' ? 30 : -1;
+        if (shift < 0) throw JunctionBuilderException(why);
+    }
+    if (v > ((uint64_t)INT64_MAX >> shift)) throw JunctionBuilderException(why);  // (the library's option is an int64_t)
+    return v << shift;
+}
 
 JunctionBuilder::JunctionBuilder(const std::string& prepDir, const std::string& output) : env(std::make_shared<const JuncEnv>()) {
     prepData = PreparedFiles(prepDir);
@@ -96,6 +116,7 @@ JunctionBuilder::JunctionBuilder(const std::string& prepDir, const std::string& 
     devices = env->gpus;
     if (env->testBatch) setBatchRecords((size_t)atol(env->testBatch));
     if (env->ingestDevice >= 0) setDeviceIngest(env->ingestDevice == 1);
+    if (env->deviceMem) setDeviceMem(parseDeviceMem(env->deviceMem));
 }
 
 void JunctionBuilder::process() {
@@ -136,8 +157,9 @@ void JunctionBuilder::process() {
          << " - BAM Read Orientation: " << bam::orientationToString(orientation) << endl
          << " - BAM Indexing mode: " << (useCsi ? "CSI" : "BAI") << endl
          << " - Threads: " << threads << endl
-         << " - Separate BAMs: " << separate << endl
-         << endl;
+         << " - Separate BAMs: " << separate << endl;
+    if (deviceMem) cout << " - Device memory: " << deviceMem << " bytes per GPU" << endl;
+    cout << endl;
     cout << reader.bamDetails() << endl;
     const double t_p1 = HostProfile::now();
     if (separate) separateBams();
@@ -352,7 +374,11 @@ void JunctionBuilder::streamPieces(DeviceThread& device, BamReader& reader, int3
         }
     };
     const double tb0 = HostProfile::now();
-    if (pjb_bam_begin(dctx, seq, (int64_t)nb) != PJB_OK) readError = std::string("pjb_bam_begin: ") + pjb_last_error(dctx);
+    // (out of device memory: the device thread collects a chain -- its groups go target by target from then on --, and the call is repeated)
+    int brc;
+    while ((brc = pjb_bam_begin(dctx, seq, (int64_t)nb)) == PJB_ERR_NOMEM && device.askForRoom()) {
+    }
+    if (brc != PJB_OK) readError = std::string("pjb_bam_begin: ") + pjb_last_error(dctx) + (brc == PJB_ERR_NOMEM ? device.memoryAdvice(seq) : std::string());
     g_prof.event(tb0, HostProfile::now(), "worker bam_begin tid " + std::to_string(seq));
     // (with the mapping: pieces end on page boundaries of the FILE, so that no two pieces share a page)
     const size_t firstPiece = fileMap ? piece - (size_t)(fileOff & 4095) : piece;
@@ -652,7 +678,12 @@ void JunctionBuilder::startDeviceThreads(JuncRun& run) {
             for (size_t k = 0; k < run.with.size(); k++) chainPlan[(size_t)groupOf[k]].push_back(run.with[k]);
         }
     }
-    DeviceThread::Setup setup{orientation, strandSpecific, lens, deviceCount, extra, env->shareGpu, env->printPlan};
+    DeviceThread::Setup setup{orientation, strandSpecific, lens, deviceCount, extra, env->shareGpu, env->printPlan, 0, false, {}};
+    // the budget of a GPU is divided evenly among the contexts on it
+    setup.memLimit = deviceMem / (uint64_t)(env->shareGpu ? nd * per : per);
+    if (deviceMem && !setup.memLimit) setup.memLimit = 1;
+    setup.report = verbose || g_prof.on;
+    for (auto& r : *refs) setup.names.push_back(r->name);
     for (int k = 0; k < per; k++)
         for (int d = 0; d < nd; d++) run.deviceThreads.emplace_back(new DeviceThread(d, setup, chainPlan));
     for (size_t k = 0; k < run.deviceThreads.size(); k++) run.deviceThreads[k]->lane = (int)k;
@@ -895,6 +926,8 @@ int JunctionBuilder::main(int argc, char* argv[]) {
     int threads = DEFAULT_JUNC_THREADS, devices = 0;
     size_t batch = 0;
     std::string ingest;
+    uint64_t deviceMem = 0;
+    bool haveDeviceMem = false;
     bool extra = false, separate = false, useCsi = false, exonGff = false, intronGff = false, verbose = false, help = false;
     auto need = [&](int& i) -> std::string {
         if (i + 1 >= argc) throw JunctionBuilderException(std::string("Missing value for option ") + argv[i]);
@@ -910,6 +943,7 @@ int JunctionBuilder::main(int argc, char* argv[]) {
         else if (a == "--devices") devices = atoi(need(i).c_str());
         else if (a == "--batch") batch = (size_t)atol(need(i).c_str());
         else if (a == "--ingest") ingest = need(i);
+        else if (a == "--device_mem") deviceMem = parseDeviceMem(need(i)), haveDeviceMem = true;
         else if (a == "--separate") separate = true;
         else if (a == "--extra") extra = true;
         else if (a == "-c" || a == "--use_csi") useCsi = true;
@@ -932,6 +966,8 @@ int JunctionBuilder::main(int argc, char* argv[]) {
              << "  -c, --use_csi              Use the CSI index of the prepared BAM instead of the BAI" << endl
              << "      --devices <n>          Number of GPUs to use (default: all visible)" << endl
              << "      --ingest <device|host> Where BGZF inflate and BAM record parsing run (default device; env PORTCULLIS_INGEST)" << endl
+             << "      --device_mem <size>    Device memory the run may hold on one GPU: an integer with an optional K, M or G (default: no" << endl
+             << "                             budget; env PORTCULLIS_DEVICE_MEM).  Group chains that do not fit are finished target by target" << endl
              << "  -v, --verbose" << endl;
         return help ? 0 : 1;
     }
@@ -951,6 +987,7 @@ int JunctionBuilder::main(int argc, char* argv[]) {
     jb.setOrientation(bam::orientationFromString(ori));
     jb.setStrandSpecific(bam::strandednessFromString(strand));
     if (devices > 0) jb.setDevices(devices);
+    if (haveDeviceMem) jb.setDeviceMem(deviceMem);
     if (batch > 0) jb.setBatchRecords(batch);
     if (!ingest.empty()) {
         if (ingest != "host" && ingest != "device") throw JunctionBuilderException("--ingest takes host or device");
