@@ -587,6 +587,29 @@ typedef struct pjb_markov_models {
 int pjb_filt_features(pjb_ctx *ctx, const pjb_junction_row *rows, int64_t n_rows, double mean_read_length, uint32_t l95,
                       const pjb_markov_models *models, double *features_out /* n_rows x PJB_N_FEATURES, host */);
 
+/* ---- the Markov models trained on the device -----------------------------------------------------------------
+ * ModelFeatures::trainCodingPotentialModel / trainSplicingModels (lib/src/model_features.cc:77-158) with KmerMarkovModel::train /
+ * PosMarkovModel::train (lib/src/markov_model.cc:31-54, 80-98).  rows: host; only refid, start, end and cons_strand are read.  The three
+ * lists index the rows: cp_idx trains exon ([start-202, start-2] and [end+1, end+201], each a string of its own) and intron
+ * ([start, end]); pass_idx trains donor_t, acceptor_t and the two position models, fail_idx donor_f and acceptor_f, on
+ * left = [start-3, start+20] and right = [end-20, end+2] (inclusive, 0-based; on the negative strand every window is read backwards
+ * and complemented, `right` is the donor and `left` the acceptor).  Windows are clamped as faidx_fetch_seq clamps them.  A k-mer
+ * model counts a window of n bases only if (uint16_t)n > 6 (markov_model.cc:36: the length cut to 16 bits for the gate alone), then
+ * every position 5 .. n-1; a position model counts positions 1 .. min(n, PJB_PW_LEN) - 1.  An index listed twice counts twice.  Each
+ * context / position whose counts sum to more than 0 is divided by that sum in f64; sizes[] counts those rows (the reference's
+ * model.size() after training).  The counts are integers, so the tables are bit for bit the host's and do not depend on scheduling.
+ * An empty list gives all-zero tables of size 0 (never NULL).  out: host memory owned by the context until its next pjb_markov_train /
+ * pjb_destroy; out->models is what pjb_filt_features / pjb_filt_scores take.
+ * PJB_ERR_ARG, found on the host before anything is launched: a negative count, an index outside the rows.  PJB_ERR_STATE: a junction
+ * lies on a target whose genome was not uploaded (pjb_upload_contig), as pjb_filt_features reports it. */
+typedef struct pjb_markov_tables {
+    pjb_markov_models models;
+    int32_t sizes[8];     /* exon, intron, donor_t, donor_f, acceptor_t, acceptor_f, donor_pw, acceptor_pw */
+    uint64_t transitions; /* what the six k-mer models counted in all: the bases walked, less five a window */
+} pjb_markov_tables;
+int pjb_markov_train(pjb_ctx *ctx, const pjb_junction_row *rows, int64_t n_rows, const int64_t *cp_idx, int64_t n_cp,
+                     const int64_t *pass_idx, int64_t n_pass, const int64_t *fail_idx, int64_t n_fail, pjb_markov_tables *out);
+
 /* ---- `portcullis filt` forest stage: a saved ranger probability forest walked on the device -------------------
  * Tree::predict (deps/ranger-0.3.8/src/Tree.cpp:125-180) and ForestProbability::predictInternal
  * (src/ForestProbability.cpp:111-131): from node 0, value <= split value goes left, anything else (a NaN too) right; at

@@ -198,6 +198,9 @@ struct ModelState {
     u32 grow_batch = 0;      // pjb_set_option("grow_batch", n): trees grown side by side (tests; 0: as many as GROW_POOL_BYTES holds)
     Buf n_data, n_part_d, n_part_i, n_out; // pjb_knn (pjb_knn.hip.h): the padded matrix, the chunks' lists (distances, indices), the neighbours
     u32 knn_chunk = 0;       // pjb_set_option("knn_chunk", n): base rows per chunk (tests; 0: sized so that the grid fills the chip)
+    Buf m_idx, m_nseg, m_off, m_counts, m_tables, m_sizes; // pjb_markov_train (pjb_markov.hip.h): the index lists, the windows' segments and their
+                             // prefix, the u64 counters, the normalised tables, sizes | transitions
+    std::vector<double> markov_out; // the tables of the last pjb_markov_train: what pjb_markov_tables points to
     struct GrowOut {         // the forest of the last pjb_forest_grow: what pjb_grow_result points to
         std::vector<uint8_t> is_ordered;
         std::vector<int64_t> tree_off, count_off;
@@ -206,7 +209,7 @@ struct ModelState {
     } grow_out;
     void release_all(pjb_ctx *c) { // (pjb_destroy)
         for (Buf *b : {&g_rows, &g_models, &g_refs, &g_out, &g_bad, &r_nodes, &r_leaf, &r_roots, &r_data, &r_pred, &r_colmap, &w_pool, &w_pack,
-                       &n_data, &n_part_d, &n_part_i, &n_out})
+                       &n_data, &n_part_d, &n_part_i, &n_out, &m_idx, &m_nseg, &m_off, &m_counts, &m_tables, &m_sizes})
             release(c, *b);
     }
 };

@@ -1,12 +1,29 @@
 // pjb_model_api.hip -- the part of the C ABI behind `filt` and `train`: feature rows and the walk of a saved forest (pjb_filt_features,
-// pjb_forest_check / _load / _predict, pjb_filt_scores), the growing of a forest (pjb_forest_grow) and self-training's nearest
-// neighbours (pjb_knn); kernels in pjb_features.hip.h, pjb_forest.hip.h, pjb_grow.hip.h and pjb_knn.hip.h.  What a context keeps for
-// them is pjb_ctx::model (ModelState, pjb_host.hip.h).
+// pjb_forest_check / _load / _predict, pjb_filt_scores), the training of the Markov models (pjb_markov_train), the growing of a forest
+// (pjb_forest_grow) and self-training's nearest neighbours (pjb_knn); kernels in pjb_features.hip.h, pjb_markov.hip.h, pjb_forest.hip.h,
+// pjb_grow.hip.h and pjb_knn.hip.h.  What a context keeps for them is pjb_ctx::model (ModelState, pjb_host.hip.h).
 #include "pjb_host.hip.h"
 #include "pjb_features.hip.h"
+#include "pjb_markov.hip.h"
 #include "pjb_forest.hip.h"
 #include "pjb_grow.hip.h"
 #include "pjb_knn.hip.h"
+
+// the uploaded genomes as the kernels of `filt` and `train` look them up (c->model.g_refs), and the "a genome is missing" flag cleared
+static int genome_refs_queue(pjb_ctx *c) {
+    hipStream_t st = c->stream;
+    int rc;
+    if ((rc = ensure(c, c->model.g_refs, std::max<size_t>(c->contigs.size(), 1) * sizeof(GenomeRef)))) return rc;
+    if ((rc = ensure(c, c->model.g_bad, sizeof(int)))) return rc;
+    std::vector<GenomeRef> refs(std::max<size_t>(c->contigs.size(), 1));
+    for (size_t t = 0; t < c->contigs.size(); t++) {
+        refs[t].d = c->contigs[t].present ? c->contigs[t].d : nullptr;
+        refs[t].len = (int32_t)c->contigs[t].len;
+    }
+    HIP_TRY(c, hipMemcpyAsync(c->model.g_refs.p, refs.data(), refs.size() * sizeof(GenomeRef), hipMemcpyHostToDevice, st));
+    HIP_TRY(c, hipMemsetAsync(c->model.g_bad.p, 0, sizeof(int), st));
+    return PJB_OK;
+}
 
 // `filt`: uploads the junctions and the models and queues kg_features on the context's stream; the rows are in c->model.g_out, the "a genome
 // is missing" flag in c->model.g_bad.  Nothing waits here (rows and models are pageable: the caller's wait comes before it returns).
@@ -15,9 +32,7 @@ static int features_queue(pjb_ctx *c, const pjb_junction_row *rows, size_t n, do
     int rc;
     if ((rc = ensure(c, c->model.g_rows, n * sizeof(pjb_junction_row)))) return rc;
     if ((rc = ensure(c, c->model.g_models, ((size_t)6 * PJB_KMER_TABLE + 2 * PJB_PW_LEN * 5) * sizeof(double)))) return rc;
-    if ((rc = ensure(c, c->model.g_refs, std::max<size_t>(c->contigs.size(), 1) * sizeof(GenomeRef)))) return rc;
     if ((rc = ensure(c, c->model.g_out, n * PJB_N_FEATURES * sizeof(double)))) return rc;
-    if ((rc = ensure(c, c->model.g_bad, sizeof(int)))) return rc;
     HIP_TRY(c, hipMemcpyAsync(c->model.g_rows.p, rows, n * sizeof(pjb_junction_row), hipMemcpyHostToDevice, st));
     DevModels M;
     memset(&M, 0, sizeof M);
@@ -38,13 +53,7 @@ static int features_queue(pjb_ctx *c, const pjb_junction_row *rows, size_t n, do
     M.intron_size = models->intron ? models->intron_size : 0;
     M.don_pw_size = models->donor_pw ? models->donor_pw_size : 0;
     M.acc_pw_size = models->acceptor_pw ? models->acceptor_pw_size : 0;
-    std::vector<GenomeRef> refs(std::max<size_t>(c->contigs.size(), 1));
-    for (size_t t = 0; t < c->contigs.size(); t++) {
-        refs[t].d = c->contigs[t].present ? c->contigs[t].d : nullptr;
-        refs[t].len = (int32_t)c->contigs[t].len;
-    }
-    HIP_TRY(c, hipMemcpyAsync(c->model.g_refs.p, refs.data(), refs.size() * sizeof(GenomeRef), hipMemcpyHostToDevice, st));
-    HIP_TRY(c, hipMemsetAsync(c->model.g_bad.p, 0, sizeof(int), st));
+    if ((rc = genome_refs_queue(c))) return rc;
     LAUNCH(c, "kg_features", kg_features, dim3((unsigned)((n + 255) / 256)), dim3(256), (const pjb_junction_row *)c->model.g_rows.p, (u32)n,
            (const GenomeRef *)c->model.g_refs.p, (int)c->contigs.size(), M, mean_read_length, (u32)l95, (double *)c->model.g_out.p, (int *)c->model.g_bad.p);
     return PJB_OK;
@@ -304,6 +313,109 @@ int pjb_filt_features(pjb_ctx *c, const pjb_junction_row *rows, int64_t n_rows, 
     HIP_TRY(c, hipStreamSynchronize(st));
     if (c->ktime) ev_collect(c, MISC_POOL);
     if (bad) return fail(c, PJB_ERR_STATE, "pjb_filt_features: a junction lies on a target whose genome was not uploaded");
+    return PJB_OK;
+}
+
+// Blocks km_count spreads one model's segments over: two fit a CU beside each other (LDS), and every block pays for clearing and
+// flushing 15 625 counters, so a block gets MARKOV_MIN_SEGS segments at least.
+static constexpr u64 MARKOV_MAX_BLOCKS = 512, MARKOV_MIN_SEGS = 16;
+// ... and at most this many: 2^19 segments of 4096 bases keep every u32 counter of a block's LDS below 2^31
+static constexpr u64 MARKOV_MAX_SEGS = (u64)1 << 19;
+
+int pjb_markov_train(pjb_ctx *c, const pjb_junction_row *rows, int64_t n_rows, const int64_t *cp_idx, int64_t n_cp, const int64_t *pass_idx,
+                     int64_t n_pass, const int64_t *fail_idx, int64_t n_fail, pjb_markov_tables *out) {
+    if (!c) return PJB_ERR_ARG;
+    const int64_t *idx[MK_LISTS] = {cp_idx, pass_idx, fail_idx};
+    const int64_t n_idx[MK_LISTS] = {n_cp, n_pass, n_fail};
+    static const char *const list_name[MK_LISTS] = {"cp", "pass", "fail"};
+    if (!out || n_rows < 0 || (n_rows > 0 && !rows) || n_rows > 0xfffffff0ll) return fail(c, PJB_ERR_ARG, "pjb_markov_train: bad arguments");
+    size_t n_all = 0;
+    for (int l = 0; l < MK_LISTS; l++) {
+        if (n_idx[l] < 0 || n_idx[l] > 0x3ffffff0ll || (n_idx[l] > 0 && !idx[l]))
+            return fail(c, PJB_ERR_ARG, "pjb_markov_train: the %s list has %lld entries", list_name[l], (long long)n_idx[l]);
+        for (int64_t k = 0; k < n_idx[l]; k++)
+            if (idx[l][k] < 0 || idx[l][k] >= n_rows)
+                return fail(c, PJB_ERR_ARG, "pjb_markov_train: entry %lld of the %s list is row %lld of %lld rows", (long long)k, list_name[l],
+                            (long long)idx[l][k], (long long)n_rows);
+        n_all += (size_t)n_idx[l];
+    }
+    HIP_TRY(c, hipSetDevice(c->cfg.device));
+    hipStream_t st = c->stream;
+    const size_t n = (size_t)n_rows, TAB = (size_t)MARKOV_ROWS * 5;
+    int rc;
+    if ((rc = ensure(c, c->model.g_rows, std::max<size_t>(n, 1) * sizeof(pjb_junction_row)))) return rc;
+    if ((rc = ensure(c, c->model.m_idx, std::max<size_t>(n_all, 1) * sizeof(int64_t)))) return rc;
+    if ((rc = ensure(c, c->model.m_counts, TAB * sizeof(u64)))) return rc;
+    if ((rc = ensure(c, c->model.m_tables, TAB * sizeof(double)))) return rc;
+    if ((rc = ensure(c, c->model.m_sizes, 8 * sizeof(int) + sizeof(u64)))) return rc;
+    MarkovJob J;
+    memset(&J, 0, sizeof J);
+    J.rows = (const pjb_junction_row *)c->model.g_rows.p;
+    J.n_refs = (int)c->contigs.size();
+    if (n) HIP_TRY(c, hipMemcpyAsync(c->model.g_rows.p, rows, n * sizeof(pjb_junction_row), hipMemcpyHostToDevice, st));
+    size_t at = 0;
+    for (int l = 0; l < MK_LISTS; l++) {
+        J.idx[l] = (const int64_t *)c->model.m_idx.p + at;
+        J.n_idx[l] = (u32)n_idx[l];
+        if (n_idx[l]) HIP_TRY(c, hipMemcpyAsync((int64_t *)c->model.m_idx.p + at, idx[l], (size_t)n_idx[l] * sizeof(int64_t), hipMemcpyHostToDevice, st));
+        at += (size_t)n_idx[l];
+    }
+    const u64 wins[MK_KMER_MODELS] = {2 * (u64)n_cp, (u64)n_cp, (u64)n_pass, (u64)n_fail, (u64)n_pass, (u64)n_fail};
+    u64 W = 0;
+    for (int m = 0; m < MK_KMER_MODELS; m++) {
+        J.win_off[m] = (u32)W;
+        W += wins[m];
+    }
+    if (W > 0xfffffff0ull) return fail(c, PJB_ERR_ARG, "pjb_markov_train: %llu windows", (unsigned long long)W);
+    J.win_off[MK_KMER_MODELS] = (u32)W;
+    if ((rc = ensure(c, c->model.m_nseg, std::max<size_t>((size_t)W, 1) * sizeof(u32)))) return rc;
+    if ((rc = ensure(c, c->model.m_off, ((size_t)W + 1) * sizeof(u64)))) return rc;
+    if ((rc = genome_refs_queue(c))) return rc;
+    J.genomes = (const GenomeRef *)c->model.g_refs.p;
+    u64 *counts = (u64 *)c->model.m_counts.p, *seg_off = (u64 *)c->model.m_off.p;
+    int *sizes = (int *)c->model.m_sizes.p, *bad_d = (int *)c->model.g_bad.p;
+    HIP_TRY(c, hipMemsetAsync(counts, 0, TAB * sizeof(u64), st));
+    HIP_TRY(c, hipMemsetAsync(sizes, 0, 8 * sizeof(int) + sizeof(u64), st));
+    // the windows' segments and their prefix; the six models' totals come back (one wait) to size the grids
+    u64 bound[MK_KMER_MODELS + 1] = {};
+    if (W) {
+        LAUNCH(c, "km_windows", km_windows, dim3((unsigned)((W + 255) / 256)), dim3(256), J, (u32 *)c->model.m_nseg.p, bad_d);
+        if ((rc = run_scan(c, "km_scan", ArrU32Fn{(const u32 *)c->model.m_nseg.p}, MarkovOffSink{seg_off}, W, seg_off + W))) return rc;
+        for (int m = 0; m <= MK_KMER_MODELS; m++) HIP_TRY(c, hipMemcpyAsync(&bound[m], seg_off + J.win_off[m], sizeof(u64), hipMemcpyDeviceToHost, st));
+        HIP_TRY(c, hipStreamSynchronize(st));
+    }
+    for (int m = 0; m < MK_KMER_MODELS; m++) {
+        const u64 segs = bound[m + 1] - bound[m];
+        if (!segs) continue;
+        const u64 blocks = std::max(std::min(MARKOV_MAX_BLOCKS, (segs + MARKOV_MIN_SEGS - 1) / MARKOV_MIN_SEGS), (segs + MARKOV_MAX_SEGS - 1) / MARKOV_MAX_SEGS);
+        if (blocks > 0x7fffffffull) return fail(c, PJB_ERR_ARG, "pjb_markov_train: %llu segments in one model", (unsigned long long)segs);
+        LAUNCH(c, "km_count", km_count, dim3((unsigned)blocks), dim3(256), J, m, (const u64 *)seg_off, counts);
+    }
+    if (n_pass) LAUNCH(c, "km_pos", km_pos, dim3((unsigned)((n_pass + 255) / 256)), dim3(256), J, counts, bad_d);
+    LAUNCH(c, "km_normalise", km_normalise, dim3((MARKOV_ROWS + 255) / 256), dim3(256), (const u64 *)counts, (double *)c->model.m_tables.p, sizes,
+           (unsigned long long *)(sizes + 8));
+    c->model.markov_out.assign(TAB, 0.0);
+    int bad = 0;
+    struct { int sizes[8]; u64 transitions; } tail;
+    HIP_TRY(c, hipMemcpyAsync(c->model.markov_out.data(), c->model.m_tables.p, TAB * sizeof(double), hipMemcpyDeviceToHost, st));
+    HIP_TRY(c, hipMemcpyAsync(&tail, sizes, sizeof tail, hipMemcpyDeviceToHost, st));
+    HIP_TRY(c, hipMemcpyAsync(&bad, bad_d, sizeof(int), hipMemcpyDeviceToHost, st));
+    HIP_TRY(c, hipStreamSynchronize(st));
+    if (c->ktime) ev_collect(c, MISC_POOL);
+    if (bad) return fail(c, PJB_ERR_STATE, "pjb_markov_train: a junction lies on a target whose genome was not uploaded");
+    const double *t = c->model.markov_out.data();
+    memset(out, 0, sizeof *out);
+    const double **dst[8] = {&out->models.exon, &out->models.intron, &out->models.donor_t, &out->models.donor_f, &out->models.acceptor_t,
+                             &out->models.acceptor_f, &out->models.donor_pw, &out->models.acceptor_pw};
+    for (int k = 0; k < 8; k++) {
+        *dst[k] = t + (k < 6 ? (size_t)k * PJB_KMER_TABLE : (size_t)6 * PJB_KMER_TABLE + (size_t)(k - 6) * PJB_PW_LEN * 5);
+        out->sizes[k] = tail.sizes[k];
+    }
+    out->models.exon_size = tail.sizes[0];
+    out->models.intron_size = tail.sizes[1];
+    out->models.donor_pw_size = tail.sizes[6];
+    out->models.acceptor_pw_size = tail.sizes[7];
+    out->transitions = tail.transitions;
     return PJB_OK;
 }
 

@@ -28,6 +28,7 @@ EXPORTS = [
     "pjb_extra_finish", "pjb_set_option", "pjb_merge_rows", "pjb_plan_groups", "pjb_bam_begin", "pjb_bam_piece", "pjb_bam_pieces_done", "pjb_bam_end", "pjb_bam_inflate_done", "pjb_filter_set_junctions", "pjb_filter_batch", "pjb_filt_features",
     "pjb_index_begin", "pjb_index_piece", "pjb_index_end",
     "pjb_forest_check", "pjb_forest_load", "pjb_forest_predict", "pjb_filt_scores", "pjb_forest_grow", "pjb_knn",
+    "pjb_markov_train",
     "pjb_memory_info",
 ]
 ERR_NOMEM = -15  # PJB_ERR_NOMEM
@@ -56,6 +57,13 @@ class PjbBatch(C.Structure):
 class PjbMarkovModels(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in ("exon", "intron", "donor_t", "donor_f", "acceptor_t", "acceptor_f", "donor_pw", "acceptor_pw")] + [
         (n, C.c_int32) for n in ("exon_size", "intron_size", "donor_pw_size", "acceptor_pw_size")]
+
+
+class PjbMarkovTables(C.Structure):  # pjb_markov_tables
+    _fields_ = [("models", PjbMarkovModels), ("sizes", C.c_int32 * 8), ("transitions", C.c_uint64)]
+
+
+MARKOV_TABLES = ("exon", "intron", "donor_t", "donor_f", "acceptor_t", "acceptor_f", "donor_pw", "acceptor_pw")  # the order of pjb_markov_tables.sizes
 
 
 class PjbForest(C.Structure):
@@ -173,6 +181,8 @@ def load():
         L.pjb_filter_set_junctions.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_int64]
         L.pjb_filter_batch.argtypes = [C.c_void_p, C.c_int32, C.POINTER(PjbBatch), C.c_int32, C.c_void_p]
         L.pjb_filt_features.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_double, C.c_uint32, C.POINTER(PjbMarkovModels), C.c_void_p]
+        L.pjb_markov_train.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64,
+                                       C.POINTER(PjbMarkovTables)]
         L.pjb_forest_check.argtypes = [C.POINTER(PjbForest), C.c_char_p, C.c_int]
         L.pjb_forest_load.argtypes = [C.c_void_p, C.POINTER(PjbForest)]
         L.pjb_forest_predict.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p]
@@ -528,6 +538,25 @@ class Context:
         self._check(self._L.pjb_filt_features(self._h, rows.ctypes.data_as(C.c_void_p), len(rows), float(mean_read_length), int(l95),
                                               C.byref(m), out.ctypes.data_as(C.c_void_p)))
         return out[: len(rows)]
+
+    def markov_train(self, rows, cp_idx, pass_idx, fail_idx):
+        """pjb_markov_train: the eight Markov models trained on the device from `rows` (ROW_DTYPE) and three lists of row indices.  Returns
+        the dict filt_features takes (and oracle.filt_features returns): the tables as float64 copies, exon_size, intron_size, donor_pw_size,
+        acceptor_pw_size; also <table>_size for every table and `transitions`."""
+        rows = np.ascontiguousarray(rows, dtype=ROW_DTYPE)
+        lists = [np.ascontiguousarray(a, dtype=np.int64).reshape(-1) for a in (cp_idx, pass_idx, fail_idx)]
+        t = PjbMarkovTables()
+        args = []
+        for a in lists:
+            args += [a.ctypes.data_as(C.c_void_p), len(a)]
+        self._check(self._L.pjb_markov_train(self._h, rows.ctypes.data_as(C.c_void_p), len(rows), *args, C.byref(t)))
+        out = {}
+        for k, name in enumerate(MARKOV_TABLES):
+            n = PW_LEN * 5 if name.endswith("_pw") else KMER_TABLE
+            out[name] = np.ctypeslib.as_array(C.cast(getattr(t.models, name), C.POINTER(C.c_double)), shape=(n,)).copy()
+            out[name + "_size"] = int(t.sizes[k])
+        out["transitions"] = int(t.transitions)
+        return out
 
     def forest_load(self, forest):
         """pjb_forest_load: `forest` is a Forest (checked first; one per context, a new one replaces the old)."""

@@ -4,7 +4,8 @@
 // .pass / .fail / .ref outputs.  Same setters, same messages, same order of stages.  Self-training -- the reference's default when
 // neither a model nor --no_ml is given -- is built behind --self_train <data_dir> (selfTrain(): the layered rule sets choose the
 // initial sets, ModelFeatures::trainInstance balances them and grows the forest on the device); without that flag it is refused with
-// the way out.  Deviations: INTEGRATION.md, "Known deviations".
+// the way out.  --save_models keeps what self-training trained beside the forest (L95 and the Markov models: ml/model_bundle.hpp), and
+// --model_file with --models_file scores with both, as the run that trained them did.  Deviations: INTEGRATION.md, "Known deviations".
 #pragma once
 
 #include <functional>
@@ -28,10 +29,11 @@ const double DEFAULT_FILTER_THRESHOLD = 0.5;
 class JunctionFilter {
     std::string junctionFile;
     PreparedFiles prepData;
-    std::string modelFile, filterFile, referenceFile, output;
+    std::string modelFile, modelsFile, filterFile, referenceFile, output;  // modelsFile: --models_file, the L95 and Markov models to score a saved forest with
     bool train = false;
     std::string selfTrainDir, trainingRule = "balanced";  // --self_train: the reference's data/ directory; a rule set in it (or a directory)
     bool smote = true, enn = false, saveLayers = false, saveMatrix = false;
+    bool saveModels = false;  // --save_models: <output>.selftrain.models beside <output>.selftrain.forest
     uint16_t threads = DEFAULT_FILTER_THREADS;
     bool saveBad = false, saveFeatures = false, outputExonGFF = false, outputIntronGFF = false;
     uint32_t maxLength = 0, minCov = 1;
@@ -65,6 +67,8 @@ public:
     void setOutputIntronGFF(bool v) { outputIntronGFF = v; }
     void setFilterFile(const std::string& v) { filterFile = v; }
     void setModelFile(const std::string& v) { modelFile = v; }
+    void setModelsFile(const std::string& v) { modelsFile = v; }
+    void setSaveModels(bool v) { saveModels = v; }
     void setReferenceFile(const std::string& v) { referenceFile = v; }
     void setTrain(bool v) { train = v; }
     void setSelfTrainDir(const std::string& v) { selfTrainDir = v; }

@@ -56,6 +56,15 @@ public:
                 for (int k = 0; k < 5; k++) tab[c * 5 + k] /= sum;
         }
     }
+    // the model a training elsewhere left (pjb_markov_train, a model file): `table` is [5^o][5] probabilities as train() leaves them; the
+    // contexts the map would hold are the rows that are not zero
+    void fill(const double* table, uint16_t o) {
+        order = o;
+        tab.assign(table, table + nCtx() * 5);
+        seen.assign(nCtx(), 0);
+        for (size_t c = 0; c < seen.size(); c++)
+            for (int k = 0; k < 5; k++) seen[c] |= tab[c * 5 + k] != 0.0;
+    }
     uint16_t getOrder() const { return order; }
     size_t size() const {
         size_t n = 0;
@@ -110,6 +119,13 @@ public:
             if (sum > 0)
                 for (int k = 0; k < 5; k++) tab[i * 5 + k] /= sum;
         }
+    }
+    void fill(const double* table, uint16_t o) {  // as KmerMarkovModel::fill: [LEN][5]
+        order = o;
+        tab.assign(table, table + LEN * 5);
+        seen.assign(LEN, 0);
+        for (size_t i = 0; i < LEN; i++)
+            for (int k = 0; k < 5; k++) seen[i] |= tab[i * 5 + k] != 0.0;
     }
     uint16_t getOrder() const { return order; }
     size_t size() const {

@@ -1,7 +1,9 @@
 // ModelFeatures: the feature side of the filt stage (lib/include/portcullis/ml/model_features.hpp,
 // lib/src/model_features.cc:42-235): intron-size threshold, the Markov models trained from junction sets, and the
-// feature matrix.  Training walks genome windows on the host (it is a k-mer count); the matrix -- every junction's
-// windows scored against six k-mer and two position models -- comes from the device (pjb_filt_features).
+// feature matrix.  Training counts the windows' k-mers on the device (pjb_markov_train: the tables are bit for bit what the
+// models' own train() makes of the same strings); the matrix -- every junction's windows scored against six k-mer and two position
+// models -- comes from the device too (pjb_filt_features).  One device context serves a ModelFeatures from its first device call on:
+// it holds the genomes of the targets asked for so far, and is opened anew only for junctions on targets it does not hold.
 // juncs2FeatureVectors returns a plain row-major matrix whose columns are VAR_NAMES + Junction::JAD_NAMES.  The random-forest
 // side: a saved forest (ml/forest.hpp) is walked on the device over the same rows without the matrix leaving it (forestPredict);
 // growing a forest from labelled junctions (growForest, pjb_forest_grow) is `train`'s; trainInstance is self-training's: the two sets
@@ -15,6 +17,9 @@
 #include "../junction.hpp"
 #include "forest.hpp"
 #include "markov_model.hpp"
+#include "model_bundle.hpp"
+
+struct pjb_ctx;
 
 namespace portcullis {
 namespace ml {
@@ -25,7 +30,8 @@ class ModelFeatures {
     bam::GenomeMapper* gmap = nullptr;
     std::string genomeFile;
     int device = 0;
-    std::string oriented(const JunctionPtr& j, int start, int end) const;  // fetchBases (+ reverse complement on the negative strand)
+    pjb_ctx* ctx = nullptr;               // the device context (deviceContext)
+    std::vector<std::string> ctxTargets;  // by target index: the name of the target whose genome the context holds, "" = none
 
 public:
     uint32_t L95 = 0;
@@ -37,11 +43,20 @@ public:
     ModelFeatures(const ModelFeatures&) = delete;
     ModelFeatures& operator=(const ModelFeatures&) = delete;
 
-    void setDevice(int d) { device = d; }
+    void setDevice(int d);
+    // The context with the genomes of every target a junction of x lies on: the one kept, if it holds them all; else a new one (the old
+    // one is destroyed) with the genomes of x's targets.  Self-training calls openDevice(pos + neg) before it trains, so that the
+    // genomes are uploaded once for training and for trainInstance.
+    pjb_ctx* deviceContext(const JunctionList& x);
+    void openDevice(const JunctionList& x) { (void)deviceContext(x); }
+    // L95 and the eight models as a file holds them (sizes: the rows trained), and back
+    ModelBundle bundle() const;
+    void setBundle(const ModelBundle& b);
     bool isCodingPotentialModelEmpty() { return exonModel.size() == 0 || intronModel.size() == 0; }
     bool isPWModelEmpty() { return donorPWModel.size() == 0 || acceptorPWModel.size() == 0; }
     void initGenomeMapper(const std::string& genomeFile);
     uint32_t calcIntronThreshold(const JunctionList& juncs);
+    // model_features.cc:77-158 on the device; the models end as their own train() over the same windows would leave them
     void trainCodingPotentialModel(const JunctionList& in);
     void trainSplicingModels(const JunctionList& pass, const JunctionList& fail);
     static std::vector<std::string> featureNames();

@@ -1,9 +1,13 @@
 // Train: the `train` mode -- a random forest model for `filt --model_file` grown on the device from two junction tables, one of junctions
 // known to be genuine and one of junctions known not to be.  It is the last step of the reference's ModelFeatures::trainInstance
 // (lib/src/model_features.cc:297-304, 422-440): combine the sets, sort them, make the feature rows, grow a ranger probability forest of
-// `trees` trees and save it.  What the reference does before that step is not built: choosing the sets by layered rules,
-// L95 and the Markov models (the rows are made as `filt` makes them: untrained models, L95 = 0, so that model and scoring agree), SMOTE,
-// ENN, the under-sampling, variable importance and the out-of-bag error (every row is in bag: there is none to report).
+// `trees` trees and save it.  Without --markov the rows are made as `filt --model_file` alone makes them: untrained Markov models, L95 = 0,
+// so that model and scoring agree.  With --markov L95 is calcIntronThreshold of the positive set and the Markov models are trained on the
+// device from the two sets (coding potential and the true splicing models from the positives, the false ones from the negatives) as
+// self-training trains them from its initial sets; the rows carry those columns, and <prefix>.models (ml/model_bundle.hpp) is written
+// beside <prefix>.forest for `filt --model_file ... --models_file ...`.  What the reference does before that step and is not built
+// (INTEGRATION.md): choosing the sets by layered rules, SMOTE, ENN, the under-sampling, variable importance and the out-of-bag error
+// (every row is in bag: there is none to report).
 #pragma once
 
 #include <string>
@@ -26,7 +30,7 @@ class Train {
     std::string positiveFile, negativeFile, output;
     int32_t trees = DEFAULT_TRAIN_TREES;
     uint32_t seed = DEFAULT_TRAIN_SEED;
-    bool saveFeatures = false, verbose = false;
+    bool saveFeatures = false, verbose = false, markov = false;
     int device = 0;
 
 public:
@@ -37,6 +41,7 @@ public:
     void setSeed(uint32_t v) { seed = v; }
     void setSaveFeatures(bool v) { saveFeatures = v; }
     void setVerbose(bool v) { verbose = v; }
+    void setMarkov(bool v) { markov = v; }
     void setDevice(int v) { device = v; }
 
     void train();

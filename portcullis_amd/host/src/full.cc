@@ -53,6 +53,7 @@ string Full::helpMessage() {
            "  --canonical arg (=OFF)           Keep junctions based on their splice site status.  Valid options: OFF,C,S,N. Where C = Canonical junctions (GT-AG), S = Semi-canonical junctions (AT-AC, or  GC-AG), N = Non-canonical.  OFF means, keep all junctions (i.e. don't filter by canonical status).  User can separate options by a comma to keep two categories.\n"
            "  --min_cov arg (=1)               Only keep junctions with a number of split reads greater than or equal to this number\n"
            "  --save_bad                       Saves bad junctions (i.e. junctions that fail the filter), as well as good junctions (those that pass)\n"
+           "  --save_models                    Also save 3-filt/portcullis_filtered.selftrain.models: the L95 and the Markov models self-training trains, as filt --save_models\n"
            "  --training_rule arg (=balanced)  Pre-set to use for the self-training. Currently supported: balanced, precise. Default: balanced.\n\n"
            "Not built (refused, as in prep and filt): merging or sorting BAM files, CSI output, --genuine, a default data directory\n";
 }
@@ -68,7 +69,7 @@ int Full::main(int argc, char* argv[]) {
     int threads = 1, devices = 0;
     uint64_t deviceMem = 0;
     bool separate = false, extra = false, copy = false, keepTemp = false, force = false, useCsi = false, saveBad = false, exongff = false,
-         introngff = false, bamFilter = false, saveLayers = false, saveFeatures = false, verbose = false, help = false;
+         introngff = false, bamFilter = false, saveLayers = false, saveFeatures = false, saveModels = false, verbose = false, help = false;
     uint32_t maxLength = 0, minCov = 1;
     // long options take their value as the next argument or after '=' (as in filt)
     for (int i = 1; i < argc; i++) {
@@ -111,6 +112,7 @@ int Full::main(int argc, char* argv[]) {
         else if (a == "--self_train") selfTrainDir = need();
         else if (a == "--save_features") saveFeatures = true;  // (hidden, as in the reference)
         else if (a == "--save_layers") saveLayers = true;      // (hidden, as in the reference)
+        else if (a == "--save_models") saveModels = true;
         else if (!a.empty() && a[0] == '-' && a.size() > 1) throw FullException("Unknown option: " + a);
         else positional.push_back(a);
     }
@@ -204,6 +206,7 @@ int Full::main(int argc, char* argv[]) {
         filter.setSaveBad(saveBad);
         filter.setSaveLayers(saveLayers);
         filter.setSaveFeatures(saveFeatures);
+        filter.setSaveModels(saveModels);
         filter.setReferenceFile(referenceFile);
         filter.setBeforeDevice([&] { waited += juncDown->wait(); });
         filter.filter();

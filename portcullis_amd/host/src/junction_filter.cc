@@ -186,6 +186,12 @@ bool JunctionFilter::selfTrain(const JunctionList& all, ml::ModelFeatures& mf, m
     cout << "Confirming intron length L95 is: " << mf.L95 << endl;
     cout << "Feature learning from training set ...";
     cout.flush();
+    mf.setDevice(device);
+    {  // one context for the training and for trainInstance: the genomes of both sets' targets are uploaded once
+        JunctionList both = pos;
+        both.insert(both.end(), neg.begin(), neg.end());
+        mf.openDevice(both);
+    }
     mf.trainCodingPotentialModel(pos);
     mf.trainSplicingModels(pos, neg);
     cout << " done." << endl << endl;
@@ -206,6 +212,10 @@ bool JunctionFilter::selfTrain(const JunctionList& all, ml::ModelFeatures& mf, m
     }
     forest.save(output + ".selftrain.forest");
     cout << "Saved forest to file " << output << ".selftrain.forest" << endl << endl;
+    if (saveModels) {
+        mf.bundle().save(output + ".selftrain.models");
+        cout << "Saved L95 and Markov models to file " << output << ".selftrain.models" << endl << endl;
+    }
     return true;
 }
 
@@ -222,12 +232,15 @@ void JunctionFilter::filter() {  // :153-596
     if (!exists(junctionFile)) throw JuncFilterException("Could not find junction file at: " + junctionFile);
     if (!exists(prepData.getGenomeFilePath())) throw JuncFilterException("Could not find prepared genome file at: " + prepData.getGenomeFilePath());
     if (!modelFile.empty() && !exists(modelFile)) throw JuncFilterException("Could not find filter model file at: " + modelFile);
+    if (!modelsFile.empty() && !exists(modelsFile)) throw JuncFilterException("Could not find Markov model file at: " + modelsFile);
     if (!filterFile.empty() && !exists(filterFile)) throw JuncFilterException("Could not find filter configuration file at: " + filterFile);
     if (!referenceFile.empty() && !exists(referenceFile)) throw JuncFilterException("Could not find reference BED file at: " + referenceFile);
     if (!exists(outputDir)) {
         if (!createDirectories(outputDir)) throw JuncFilterException("Could not create output directory at: " + outputDir);
     } else if (!isDirectory(outputDir))
         throw JuncFilterException("File exists with name of suggested output directory: " + outputDir);
+    ml::ModelBundle bundle;  // --models_file: read and checked on the host, before the table is loaded or a device looked for
+    if (!modelsFile.empty()) bundle = ml::ModelBundle::load(modelsFile);
     cout << "Loading junctions from " << junctionFile << " ...";
     cout.flush();
     JunctionSystem originalJuncs(junctionFile);
@@ -268,7 +281,8 @@ void JunctionFilter::filter() {  // :153-596
     if (!modelFile.empty()) {  // :441-456
         const ml::Forest forest = ml::Forest::load(modelFile);  // (read and checked before the genome or a device is touched)
         ml::ModelFeatures::checkForest(forest);
-        ml::ModelFeatures mf;  // L95 = 0, untrained Markov models: nothing was trained in this run
+        ml::ModelFeatures mf;  // L95 = 0, untrained Markov models: nothing was trained in this run ...
+        if (!modelsFile.empty()) mf.setBundle(bundle);  // ... unless the run that trained the forest left them
         mf.initGenomeMapper(prepData.getGenomeFilePath());
         cout << "Predicting valid junctions using random forest model" << endl << "----------------------------------------------------" << endl << endl;
         JunctionList passJuncs, failJuncs;
@@ -401,6 +415,8 @@ string JunctionFilter::helpMessage() {
            "  --max_length arg (=0)                Filter junctions longer than this value.  Default (0) is to not filter based on length.\n"
            "  --canonical arg (=OFF)               Keep junctions based on their splice site status.  Valid options: OFF,C,S,N.  User can separate options by a comma to keep two categories.\n"
            "  --min_cov arg (=1)                   Only keep junctions with a number of split reads greater than or equal to this number\n"
+           "  --models_file arg                    With --model_file: the L95 and Markov models to score with (<prefix>.selftrain.models of a --save_models run,\n"
+           "                                       or <prefix>.models of train --markov).  Without it a saved forest is applied with L95 = 0 and untrained models.\n"
            "  --threshold arg (=0.5)               The threshold score at which we determine a junction to be genuine or not.\n"
            "  --save_features                      Save the feature rows of all junctions to <output>.features.testing\n\n"
            "Self-training options (refused without --self_train):\n"
@@ -411,6 +427,7 @@ string JunctionFilter::helpMessage() {
            "  --no_smote                           Disable the balancing of the two sets (synthetic oversampling, or under-sampling)\n"
            "  --enn                                Enable Edited Nearest Neighbour to clean the decision region\n"
            "  --save_layers                        Save each layer produced when creating the training set\n"
+           "  --save_models                        Save <output>.selftrain.models: the L95 and the Markov models the forest's rows were made with (for --models_file)\n"
            "  --save_matrix                        Save <output>.selftrain.matrix.f64 (the training matrix, rows x 29) and <output>.testing.matrix.f64\n"
            "                                       (the 29 columns of every junction as scored): little-endian doubles, no header\n\n"
            "Not built (refused): self-training without --self_train (neither --model_file nor --no_ml), -g [ --genuine ]\n";
@@ -419,9 +436,9 @@ string JunctionFilter::helpMessage() {
 int JunctionFilter::main(int argc, char* argv[]) {
     std::vector<string> positional;
     string output = DEFAULT_FILTER_OUTPUT, source = DEFAULT_FILTER_SOURCE, filterFile, referenceFile, modelFile, canonical = "OFF";
-    string selfTrainDir, trainingRule = "balanced";
+    string selfTrainDir, trainingRule = "balanced", modelsFile;
     bool saveBad = false, exongff = false, introngff = false, noMl = false, saveFeatures = false, verbose = false, help = false;
-    bool noSmote = false, enn = false, saveLayers = false, saveMatrix = false;
+    bool noSmote = false, enn = false, saveLayers = false, saveMatrix = false, saveModels = false;
     std::vector<std::pair<string, string>> selfTrainOnly;  // the options that belong to self-training, as given: refused without --self_train
     int threads = DEFAULT_FILTER_THREADS;
     uint32_t maxLength = 0, minCov = 1;
@@ -453,6 +470,7 @@ int JunctionFilter::main(int argc, char* argv[]) {
         else if (a == "-r" || a == "--reference") referenceFile = need();
         else if (a == "-n" || a == "--no_ml") noMl = true;
         else if (a == "-m" || a == "--model_file") modelFile = need();
+        else if (a == "--models_file") modelsFile = need();
         else if (a == "--max_length") maxLength = (uint32_t)std::stoul(need());
         else if (a == "--canonical") canonical = need();
         else if (a == "--min_cov") minCov = (uint32_t)std::stoul(need());
@@ -475,6 +493,9 @@ int JunctionFilter::main(int argc, char* argv[]) {
         } else if (a == "--save_layers") {
             saveLayers = true;
             selfTrainOnly.emplace_back("--save_layers (the layers of the training set)", selfTrainOut);
+        } else if (a == "--save_models") {
+            saveModels = true;
+            selfTrainOnly.emplace_back("--save_models (the L95 and the Markov models self-training trains)", selfTrainOut);
         } else if (a == "--save_matrix") {
             saveMatrix = true;
             selfTrainOnly.emplace_back("--save_matrix (the training and the testing matrix of self-training)", selfTrainOut);
@@ -492,6 +513,9 @@ int JunctionFilter::main(int argc, char* argv[]) {
         throw JuncFilterException(selfTrainOnly[0].first + " is not built into portcullis_amd filt without --self_train <data_dir>.  " + selfTrainOnly[0].second);
     if (!selfTrainDir.empty() && (noMl || !modelFile.empty()))
         throw JuncFilterException("--self_train trains the model on the input: it cannot be combined with --no_ml or --model_file.");
+    if (!modelsFile.empty() && (!selfTrainDir.empty() || noMl || modelFile.empty()))
+        throw JuncFilterException("--models_file " + modelsFile + " holds the L95 and the Markov models a saved forest is scored with: it needs --model_file and cannot be "
+                                  "combined with --self_train (which trains its own) or --no_ml.");
     const auto t0 = std::chrono::steady_clock::now();
     cout << "Running portcullis in junction filter mode" << endl << "------------------------------------------" << endl << endl;
     JunctionFilter filter(positional[0], positional[1], output);
@@ -509,6 +533,7 @@ int JunctionFilter::main(int argc, char* argv[]) {
     else {
         filter.setTrain(false);
         if (!noMl) filter.setModelFile(modelFile);
+        filter.setModelsFile(modelsFile);
     }
     filter.setSelfTrainDir(selfTrainDir);
     filter.setTrainingRule(trainingRule);
@@ -516,6 +541,7 @@ int JunctionFilter::main(int argc, char* argv[]) {
     filter.setENN(enn);
     filter.setSaveLayers(saveLayers);
     filter.setSaveMatrix(saveMatrix);
+    filter.setSaveModels(saveModels);
     filter.setSaveFeatures(saveFeatures);
     filter.setReferenceFile(referenceFile);
     filter.setThreshold(threshold);

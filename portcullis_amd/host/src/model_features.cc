@@ -8,7 +8,6 @@
 #include <iostream>
 
 #include <portcullis/junction_system.hpp>
-#include <portcullis/seq_utils.hpp>
 
 #include "../../../include/portcullis_amd.h"
 #include "self_train.hpp"
@@ -20,13 +19,28 @@ const std::vector<std::string> VAR_NAMES = {"Genuine",       "rna_usrs",    "rna
                                             "rna_rel2raw",   "rna_maxminanc", "rna_maxmmes", "rna_missmatch", "rna_intron",
                                             "dna_minhamm",   "dna_coding",  "dna_pws",       "dna_ss"};
 
-ModelFeatures::~ModelFeatures() { delete gmap; }
+ModelFeatures::~ModelFeatures() {
+    pjb_destroy(ctx);
+    delete gmap;
+}
+
+void ModelFeatures::setDevice(int d) {
+    if (d != device) {  // (a context lives on one device)
+        pjb_destroy(ctx);
+        ctx = nullptr;
+        ctxTargets.clear();
+    }
+    device = d;
+}
 
 void ModelFeatures::initGenomeMapper(const std::string& file) {  // :60-65
     delete gmap;
     genomeFile = file;
     gmap = new bam::GenomeMapper(file);
     gmap->loadFastaIndex();
+    pjb_destroy(ctx);  // (the genomes it holds are another file's)
+    ctx = nullptr;
+    ctxTargets.clear();
 }
 
 uint32_t ModelFeatures::calcIntronThreshold(const JunctionList& juncs) {  // :67-75
@@ -37,81 +51,12 @@ uint32_t ModelFeatures::calcIntronThreshold(const JunctionList& juncs) {  // :67
     return L95;
 }
 
-// gmap.fetchBases(...) and SeqUtils::reverseComplement when the consensus strand is negative.  The bases are upper-cased
-// first (the reference indexes its complement table with whatever case the FASTA has: out of bounds for lower case).
-std::string ModelFeatures::oriented(const JunctionPtr& j, int start, int end) const {
+static void checkRc(pjb_ctx* ctx, int rc, const char* what) {
+    if (rc != PJB_OK) throw JunctionException(std::string(what) + ": " + pjb_last_error(ctx));
+}
+
+pjb_ctx* ModelFeatures::deviceContext(const JunctionList& x) {
     if (!gmap) throw JunctionException("ModelFeatures: initGenomeMapper was not called");
-    std::string s = gmap->fetchBases(j->getIntron()->ref.name.c_str(), start, end);
-    for (auto& c : s)
-        if (c >= 'a' && c <= 'z') c = (char)(c - 32);
-    if (j->getConsensusStrand() == bam::Strand::NEGATIVE) s = SeqUtils::reverseComplement(s);
-    return s;
-}
-
-void ModelFeatures::trainCodingPotentialModel(const JunctionList& in) {  // :77-112
-    std::vector<std::string> exons, introns;
-    for (const auto& j : in) {
-        const int s = j->getIntron()->start, e = j->getIntron()->end;
-        exons.push_back(oriented(j, s - 202, s - 2));
-        introns.push_back(oriented(j, s, e));
-        exons.push_back(oriented(j, e + 1, e + 201));
-    }
-    exonModel.train(exons, 5);
-    intronModel.train(introns, 5);
-}
-
-void ModelFeatures::trainSplicingModels(const JunctionList& pass, const JunctionList& fail) {  // :114-158
-    std::vector<std::string> donors, acceptors;
-    auto collect = [&](const JunctionList& l) {
-        donors.clear();
-        acceptors.clear();
-        for (const auto& j : l) {
-            const int s = j->getIntron()->start, e = j->getIntron()->end;
-            std::string left = oriented(j, s - 3, s + 20), right = oriented(j, e - 20, e + 2);
-            const bool neg = j->getConsensusStrand() == bam::Strand::NEGATIVE;
-            donors.push_back(neg ? right : left);
-            acceptors.push_back(neg ? left : right);
-        }
-    };
-    collect(pass);
-    donorPWModel.train(donors, 1);
-    acceptorPWModel.train(acceptors, 1);
-    donorTModel.train(donors, 5);
-    acceptorTModel.train(acceptors, 5);
-    collect(fail);
-    donorFModel.train(donors, 5);
-    acceptorFModel.train(acceptors, 5);
-}
-
-std::vector<std::string> ModelFeatures::featureNames() {
-    std::vector<std::string> n = VAR_NAMES;
-    n.insert(n.end(), Junction::JAD_NAMES.begin(), Junction::JAD_NAMES.end());
-    return n;
-}
-
-// One context with the genomes of the targets the junctions lie on, the junctions as device rows and the models as the C ABI takes them:
-// what the feature matrix and the fused forest walk both start from.
-namespace {
-struct DeviceRun {
-    pjb_ctx* ctx = nullptr;
-    std::vector<pjb_junction_row> rows;
-    pjb_markov_models m;
-    ~DeviceRun() { pjb_destroy(ctx); }
-    void check(int rc, const char* what) const {
-        if (rc != PJB_OK) throw JunctionException(std::string(what) + ": " + pjb_last_error(ctx));
-    }
-};
-}  // namespace
-
-static void openRun(DeviceRun& run, ModelFeatures& mf, bam::GenomeMapper* gmap, int device, const JunctionList& x) {
-    if (!gmap) throw JunctionException("ModelFeatures: initGenomeMapper was not called");
-    pjb_config cfg;
-    memset(&cfg, 0, sizeof cfg);
-    cfg.abi_version = PJB_ABI_VERSION;
-    cfg.device = device;
-    cfg.orientation = PJB_OR_UNKNOWN;
-    cfg.strandedness = PJB_SS_UNKNOWN;
-    if (pjb_create(&run.ctx, &cfg) != PJB_OK) throw JunctionException(std::string("pjb_create: ") + pjb_last_error(nullptr));
     int32_t maxRef = 0;
     for (const auto& j : x) maxRef = std::max(maxRef, j->getIntron()->ref.index);
     std::vector<int32_t> lens((size_t)maxRef + 1, 0);
@@ -120,17 +65,37 @@ static void openRun(DeviceRun& run, ModelFeatures& mf, bam::GenomeMapper* gmap, 
         lens[(size_t)j->getIntron()->ref.index] = j->getIntron()->ref.length;
         names[(size_t)j->getIntron()->ref.index] = j->getIntron()->ref.name;
     }
-    run.check(pjb_set_refs(run.ctx, (int32_t)lens.size(), lens.data()), "pjb_set_refs");
+    bool held = ctx != nullptr && names.size() <= ctxTargets.size();
+    for (size_t t = 0; held && t < names.size(); t++) held = names[t].empty() || names[t] == ctxTargets[t];
+    if (held) return ctx;
+    pjb_destroy(ctx);
+    ctx = nullptr;
+    ctxTargets.clear();
+    pjb_config cfg;
+    memset(&cfg, 0, sizeof cfg);
+    cfg.abi_version = PJB_ABI_VERSION;
+    cfg.device = device;
+    cfg.orientation = PJB_OR_UNKNOWN;
+    cfg.strandedness = PJB_SS_UNKNOWN;
+    if (pjb_create(&ctx, &cfg) != PJB_OK) throw JunctionException(std::string("pjb_create: ") + pjb_last_error(nullptr));
+    checkRc(ctx, pjb_set_refs(ctx, (int32_t)lens.size(), lens.data()), "pjb_set_refs");
+    ctxTargets.assign(names.size(), std::string());
     for (size_t t = 0; t < lens.size(); t++) {
         if (names[t].empty()) continue;
         const std::string contig = gmap->fetchContig(names[t]);
-        run.check(pjb_upload_contig(run.ctx, (int32_t)t, (const uint8_t*)contig.data(), (int64_t)contig.size()), "pjb_upload_contig");
+        checkRc(ctx, pjb_upload_contig(ctx, (int32_t)t, (const uint8_t*)contig.data(), (int64_t)contig.size()), "pjb_upload_contig");
+        ctxTargets[t] = names[t];
     }
-    run.rows.resize(x.size());
-    memset(run.rows.data(), 0, run.rows.size() * sizeof(pjb_junction_row));
+    return ctx;
+}
+
+// the junctions as device rows
+static void fillRows(std::vector<pjb_junction_row>& rows, const JunctionList& x) {
+    rows.resize(x.size());
+    memset(rows.data(), 0, rows.size() * sizeof(pjb_junction_row));
     for (size_t i = 0; i < x.size(); i++) {
         const Junction& j = *x[i];
-        pjb_junction_row& r = run.rows[i];
+        pjb_junction_row& r = rows[i];
         r.refid = j.getIntron()->ref.index;
         r.start = j.getIntron()->start;
         r.end = j.getIntron()->end;
@@ -151,6 +116,88 @@ static void openRun(DeviceRun& run, ModelFeatures& mf, bam::GenomeMapper* gmap, 
         r.sum_mismatches = sum > 0.0 && sum < 4294967295.0 ? (uint64_t)std::llround(sum) : 0;
         for (int k = 0; k < 20; k++) r.jad[k] = j.getJunctionAnchorDepth((size_t)k);
     }
+}
+
+// The windows of the three lists counted on the device (pjb_markov_train: the bases are upper-cased when a genome is uploaded, the
+// windows clamped as faidx_fetch_seq clamps them and reverse-complemented on the negative strand).  The tables are the context's until
+// its next training.
+static pjb_markov_tables trainOnDevice(ModelFeatures& mf, const JunctionList& cp, const JunctionList& pass, const JunctionList& fail) {
+    JunctionList x;
+    x.reserve(cp.size() + pass.size() + fail.size());
+    x.insert(x.end(), cp.begin(), cp.end());
+    x.insert(x.end(), pass.begin(), pass.end());
+    x.insert(x.end(), fail.begin(), fail.end());
+    pjb_ctx* c = mf.deviceContext(x);
+    std::vector<pjb_junction_row> rows;
+    fillRows(rows, x);
+    std::vector<int64_t> idx(x.size());
+    for (size_t i = 0; i < idx.size(); i++) idx[i] = (int64_t)i;
+    pjb_markov_tables t;
+    checkRc(c, pjb_markov_train(c, rows.data(), (int64_t)rows.size(), idx.data(), (int64_t)cp.size(), idx.data() + cp.size(), (int64_t)pass.size(),
+                               idx.data() + cp.size() + pass.size(), (int64_t)fail.size(), &t),
+            "pjb_markov_train");
+    return t;
+}
+
+void ModelFeatures::trainCodingPotentialModel(const JunctionList& in) {  // :77-112
+    const pjb_markov_tables t = trainOnDevice(*this, in, JunctionList(), JunctionList());
+    exonModel.fill(t.models.exon, PJB_KMER_ORDER);
+    intronModel.fill(t.models.intron, PJB_KMER_ORDER);
+}
+
+void ModelFeatures::trainSplicingModels(const JunctionList& pass, const JunctionList& fail) {  // :114-158
+    const pjb_markov_tables t = trainOnDevice(*this, JunctionList(), pass, fail);
+    donorPWModel.fill(t.models.donor_pw, 1);
+    acceptorPWModel.fill(t.models.acceptor_pw, 1);
+    donorTModel.fill(t.models.donor_t, PJB_KMER_ORDER);
+    acceptorTModel.fill(t.models.acceptor_t, PJB_KMER_ORDER);
+    donorFModel.fill(t.models.donor_f, PJB_KMER_ORDER);
+    acceptorFModel.fill(t.models.acceptor_f, PJB_KMER_ORDER);
+}
+
+ModelBundle ModelFeatures::bundle() const {
+    ModelBundle b;
+    b.L95 = L95;
+    const double* src[8] = {exonModel.table(),      intronModel.table(),    donorTModel.table(),  donorFModel.table(),
+                            acceptorTModel.table(), acceptorFModel.table(), donorPWModel.table(), acceptorPWModel.table()};
+    for (size_t m = 0; m < 8; m++)
+        if (src[m]) std::copy(src[m], src[m] + (m < ModelBundle::KMER_MODELS ? ModelBundle::KMER_TABLE : ModelBundle::POS_TABLE), b.table(m));
+    b.countSizes();
+    return b;
+}
+
+void ModelFeatures::setBundle(const ModelBundle& b) {
+    L95 = b.L95;
+    exonModel.fill(b.table(0), PJB_KMER_ORDER);
+    intronModel.fill(b.table(1), PJB_KMER_ORDER);
+    donorTModel.fill(b.table(2), PJB_KMER_ORDER);
+    donorFModel.fill(b.table(3), PJB_KMER_ORDER);
+    acceptorTModel.fill(b.table(4), PJB_KMER_ORDER);
+    acceptorFModel.fill(b.table(5), PJB_KMER_ORDER);
+    donorPWModel.fill(b.table(6), 1);
+    acceptorPWModel.fill(b.table(7), 1);
+}
+
+std::vector<std::string> ModelFeatures::featureNames() {
+    std::vector<std::string> n = VAR_NAMES;
+    n.insert(n.end(), Junction::JAD_NAMES.begin(), Junction::JAD_NAMES.end());
+    return n;
+}
+
+// The context with the genomes of the targets the junctions lie on (the ModelFeatures' own: deviceContext), the junctions as device rows
+// and the models as the C ABI takes them: what the feature matrix and the fused forest walk both start from.
+namespace {
+struct DeviceRun {
+    pjb_ctx* ctx = nullptr;
+    std::vector<pjb_junction_row> rows;
+    pjb_markov_models m;
+    void check(int rc, const char* what) const { checkRc(ctx, rc, what); }
+};
+}  // namespace
+
+static void openRun(DeviceRun& run, ModelFeatures& mf, const JunctionList& x) {
+    run.ctx = mf.deviceContext(x);
+    fillRows(run.rows, x);
     pjb_markov_models& m = run.m;
     memset(&m, 0, sizeof m);
     m.exon = mf.exonModel.table();
@@ -169,10 +216,10 @@ static void openRun(DeviceRun& run, ModelFeatures& mf, bam::GenomeMapper* gmap, 
 
 // The feature rows of x (not empty), full width: the device's (pjb_filt_features: what forestPredict walks), column 0 the junctions'
 // isGenuine().  `run` is opened here and stays the caller's: trainInstance goes on with its context.
-static std::vector<double> featureRows(DeviceRun& run, ModelFeatures& mf, bam::GenomeMapper* gmap, int device, const JunctionList& x) {
+static std::vector<double> featureRows(DeviceRun& run, ModelFeatures& mf, const JunctionList& x) {
     const size_t F = PJB_N_FEATURES;
     std::vector<double> rows(x.size() * F, 0.0);
-    openRun(run, mf, gmap, device, x);
+    openRun(run, mf, x);
     run.check(pjb_filt_features(run.ctx, run.rows.data(), (int64_t)run.rows.size(), x[0]->getMeanReadLength(), mf.L95, &run.m, rows.data()), "pjb_filt_features");
     for (size_t i = 0; i < x.size(); i++) rows[i * F] = x[i]->isGenuine() ? 1.0 : 0.0;
     return rows;
@@ -192,7 +239,7 @@ std::vector<double> ModelFeatures::juncs2FeatureVectors(const JunctionList& x) {
     if (!gmap) throw JunctionException("ModelFeatures: initGenomeMapper was not called");
     if (x.empty()) return std::vector<double>();
     DeviceRun run;
-    std::vector<double> out = featureRows(run, *this, gmap, device, x);
+    std::vector<double> out = featureRows(run, *this, x);
     for (size_t i = 0; i < x.size(); i++)
         out[i * PJB_N_FEATURES + 8] = x[i]->getMeanMismatches();  // the junction's own value (a row parsed from a .tab has no integer sum)
     return out;
@@ -240,7 +287,7 @@ std::vector<double> ModelFeatures::forestPredict(const JunctionList& x, const Fo
     pjb_forest view;
     forest.view(view);
     DeviceRun run;
-    openRun(run, *this, gmap, device, x);
+    openRun(run, *this, x);
     run.check(pjb_forest_load(run.ctx, &view), "pjb_forest_load");
     run.check(pjb_filt_scores(run.ctx, run.rows.data(), (int64_t)run.rows.size(), x[0]->getMeanReadLength(), L95, &run.m, activeFeatures().data(), pred.data(),
                               featuresOut ? featuresOut->data() : nullptr),
@@ -251,7 +298,7 @@ std::vector<double> ModelFeatures::forestPredict(const JunctionList& x, const Fo
 Forest ModelFeatures::growForest(const JunctionList& x, int32_t nTrees, uint32_t seed, std::vector<double>* featuresOut) {
     if (x.empty()) throw ForestException("No junctions to grow a forest on");
     DeviceRun run;
-    std::vector<double> rows = featureRows(run, *this, gmap, device, x);
+    std::vector<double> rows = featureRows(run, *this, x);
     const std::vector<double> matrix = projectActive(rows);
     pjb_grow_params p;
     memset(&p, 0, sizeof p);
@@ -285,7 +332,7 @@ Forest ModelFeatures::trainInstance(const JunctionList& pos, const JunctionList&
     // the feature rows of the real junctions: the device's (what forestPredict walks), column 0 the genuine flag
     const size_t C = activeFeatures().size(), SC = C - 1;
     DeviceRun run;  // (lives on: pjb_knn and pjb_forest_grow below run on its context)
-    const std::vector<double> rows = featureRows(run, *this, gmap, device, x);
+    const std::vector<double> rows = featureRows(run, *this, x);
     std::vector<double> matrix = projectActive(rows);
     auto nearest = [&](const std::vector<double>& m, size_t n, int32_t defaultK, std::vector<uint32_t>& nn) {
         const int32_t k = selftrain::effectiveK(n, defaultK);

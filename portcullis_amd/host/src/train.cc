@@ -61,9 +61,18 @@ void Train::train() {
     cout << "Training a random forest model" << endl << "------------------------------" << endl << endl;
     cout << "Creating feature vector for " << x.size() << " junctions (" << pos.getJunctions().size() << " positive, " << neg.getJunctions().size()
          << " negative)" << endl;
-    ml::ModelFeatures mf;  // L95 = 0, untrained Markov models: the rows `filt --model_file` scores
+    ml::ModelFeatures mf;  // L95 = 0, untrained Markov models: the rows `filt --model_file` scores ...
     mf.setDevice(device);
     mf.initGenomeMapper(prepData.getGenomeFilePath());
+    if (markov) {  // ... or, with --markov, the rows `filt --model_file --models_file` scores: trained as self-training trains on its initial sets
+        cout << "Intron length L95 of the positive set: " << mf.calcIntronThreshold(pos.getJunctions()) << endl;
+        cout << "Feature learning from training set ...";
+        cout.flush();
+        mf.openDevice(x);  // (one context for the training and for the forest: every target's genome is uploaded once)
+        mf.trainCodingPotentialModel(pos.getJunctions());
+        mf.trainSplicingModels(pos.getJunctions(), neg.getJunctions());
+        cout << " done." << endl;
+    }
     std::vector<double> features;
     cout << "Growing " << trees << " trees" << endl;
     const ml::Forest forest = mf.growForest(x, trees, seed, saveFeatures ? &features : nullptr);
@@ -76,6 +85,10 @@ void Train::train() {
     }
     forest.save(output + ".forest");
     cout << "Saved forest to file " << output << ".forest" << endl;
+    if (markov) {
+        mf.bundle().save(output + ".models");
+        cout << "Saved L95 and Markov models to file " << output << ".models" << endl;
+    }
 }
 
 string Train::helpMessage() {
@@ -88,10 +101,12 @@ string Train::helpMessage() {
            "  -o [ --output ] arg (=" + DEFAULT_TRAIN_OUTPUT + ")  Output prefix: <prefix>.forest is written.\n"
            "  --trees arg (=250)                   The number of trees in the forest.\n"
            "  --seed arg (=1236456789)             The forest's seed (the reference's is the default).\n"
+           "  --markov                             Train L95 and the Markov models on the two sets first (on the GPU), grow the forest on rows that\n"
+           "                                       carry them, and write <prefix>.models for filt --model_file <prefix>.forest --models_file <prefix>.models.\n"
            "  --save_features                      Also write <prefix>.features.training: the feature rows the forest was grown on.\n"
            "  -v [ --verbose ]                     Print extra information\n"
            "  --help                               Produce help message\n\n"
-           "Not built: choosing the two sets (the reference's self-training layers), L95 and Markov model training, SMOTE, ENN,\n"
+           "Not built: choosing the two sets (the reference's self-training layers), SMOTE, ENN,\n"
            "under-sampling, --genuine, variable importance and the out-of-bag error (every row is in bag).\n";
 }
 
@@ -100,7 +115,7 @@ int Train::main(int argc, char* argv[]) {
     string output = DEFAULT_TRAIN_OUTPUT;
     int32_t trees = DEFAULT_TRAIN_TREES;
     uint32_t seed = DEFAULT_TRAIN_SEED;
-    bool saveFeatures = false, verbose = false, help = false;
+    bool saveFeatures = false, verbose = false, help = false, markov = false;
     // long options take their value as the next argument or after '='
     for (int i = 1; i < argc; i++) {
         string a = argv[i], inlineValue;
@@ -119,6 +134,7 @@ int Train::main(int argc, char* argv[]) {
         else if (a == "--trees") trees = (int32_t)std::stol(need());
         else if (a == "--seed") seed = (uint32_t)std::stoul(need());
         else if (a == "--save_features") saveFeatures = true;
+        else if (a == "--markov") markov = true;
         else if (a == "--devices") (void)need();
         else if (a == "-v" || a == "--verbose") verbose = true;
         else if (a == "--help") help = true;
@@ -136,6 +152,7 @@ int Train::main(int argc, char* argv[]) {
     t.setSeed(seed);
     t.setSaveFeatures(saveFeatures);
     t.setVerbose(verbose);
+    t.setMarkov(markov);
     t.train();
     const double s = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
     std::ios::fmtflags f(cout.flags());
