@@ -1,7 +1,8 @@
 // pjb_device.hip.h -- what more than one translation unit needs on the device side: the types the units share (batches, control block,
 // pairs, groups, key format), the wave / block primitives, the generic multi-block scan (pjb_host.hip.h launches it for every unit) and the
-// constants that two units size buffers from.  The kernels themselves are in the headers of their family: pjb_kernels.hip.h (the junc chain),
-// pjb_extra.hip.h, pjb_features.hip.h / pjb_forest.hip.h / pjb_grow.hip.h / pjb_knn.hip.h (filt and train), pjb_ingest.hip.h / pjb_deflate.hip.h.
+// constants that two units size buffers from -- and what more than one stage of the junc chain uses (the end of this file).  The kernels
+// themselves are in the headers of their family: pjb_kernels.hip.h (the junc chain; its stages K2d, K2, K2s and K4 in pjb_k2d_ids.hip.h,
+// pjb_k2_sort.hip.h, pjb_k2s_runs.hip.h and pjb_k4_pairs.hip.h, which include this file and no other stage), pjb_extra.hip.h, pjb_features.hip.h / pjb_forest.hip.h / pjb_grow.hip.h / pjb_knn.hip.h (filt and train), pjb_ingest.hip.h / pjb_deflate.hip.h.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -271,6 +272,7 @@ __device__ __forceinline__ T gload(const T *p) {
 // A batch descriptor fetched from device memory (one launch per chain: the block looks its batch up): the same fields as
 // pointers into GLOBAL memory, so that what is read through them are global_load / s_load instructions.
 #define PJB_GLOBAL __attribute__((address_space(1)))
+#define PJB_LDS __attribute__((address_space(3)))
 template <class T>
 __device__ __forceinline__ const PJB_GLOBAL T *as_global(const T *p) {
     return (const PJB_GLOBAL T *)p;
@@ -693,7 +695,7 @@ __device__ __forceinline__ void fetch_clamp(int32_t glen, int32_t &b, int32_t &e
 constexpr int PUB_BASE_AT = 240, PUB_ERR_AT = 256, PUB_XCNT_AT = 320 /* --extra: the target's counters, 64 bytes */, PUB_CHECKED_AT = 384 /* reads on k4b_generic's second list */, PUB_GEN_AT = 512, PUB_MEMBERS_AT = 1536, PUB_GREADS_AT = 3072, PUB_BYTES = 4096; // byte offsets in the published block
 static_assert(PUB_MEMBERS_AT + GROUP_MAX * sizeof(MemberStats) <= PUB_BYTES && sizeof(MemberStats) % 8 == 0, "control block layout");
 
-// the read lists of a chain (EmitLists, pjb_kernels.hip.h): sub-lists, and the words of a sub-list's line of counters
+// the read lists of a chain (EmitLists, below): sub-lists, and the words of a sub-list's line of counters
 constexpr u32 GEN_SHARDS = 256, GEN_CNT_STRIDE = 32;
 // Room of a sub-list (before anything says otherwise): k1_emit deals its chunks of 256 spliced reads round-robin to the sub-lists
 // (up to 256 entries a chunk on list 2 and on list 3), k1_generic its chunks of 256 items of list 3 (up to 256 entries on list 1
@@ -702,6 +704,98 @@ constexpr u32 GEN_SHARDS = 256, GEN_CNT_STRIDE = 32;
 __host__ __device__ inline u32 gen_list_cap(u32 pair_limit) {
     const u32 chunks = pair_limit / 256u + 2u;
     return ((chunks + GEN_SHARDS - 1) / GEN_SHARDS) * 256u;
+}
+
+// ---------------------------------------------------------------------------------------------
+// What more than one stage of the junc chain uses (a stage header includes this file and no other stage): each definition
+// stands here once, beside the stages that share it
+// ---------------------------------------------------------------------------------------------
+// What k1_emit and k1_generic leave beside the pairs: the candidate keys with their start bitmap for K2d (kd_*), the read lists for k1_generic and
+// k4b_generic; kd_table and k2_close ask lists_over whether every sub-list stayed within its room
+constexpr u64 KD_EMPTY = ~0ull; // no key: a packed key has fewer than 64 bits
+constexpr int KD_PAGE_SHIFT = 6; // a page of the start bitmap: 64 words, one wavefront
+struct EmitLists {
+    u64 *cand;      // candidate keys (nullptr: the chain sorts the full keys and wants none); their count is ContigStats::n_cand
+    u64 *bitmap;    // K2d's bitmap of intron starts (all-clear at rest): every candidate sets its start's bit as it is listed
+    u32 *page_cnt;  // starts per PAGE of the bitmap (64 words = 4 096 bases; all-zero at rest): counted as their bits are set for the first time
+    u64 *cand_anc;  // per candidate: min lStart | max rEnd << 32 over the pairs it stands for (the junction anchors' first level)
+    u64 *gen_list;  // [3][GEN_SHARDS][gen_cap], every entry the read's slot in the tiles' spliced lists (spl_idx, spl_rec: what k1_count kept of it)
+                    // | index of its first pair << 32.  Lists 1 and 2, for k4b_generic: the reads whose pairs need the generic walks; the reads
+                    // whose closed form waits for the window check.  List 3, for k1_generic.
+    u32 *gen_cnt;   // [GEN_SHARDS][GEN_CNT_STRIDE]: words 2 l - 2, 2 l - 1 = entries of list l's sub-list, pairs of those reads -- a cache
+                    // line per shard: atomics on one line are served one after the other, whatever the address in it
+    u32 gen_cap;    // room of one sub-list
+    u32 pack_nn;    // 1 (chains of fewer than 2^28 slots): entries of the second list carry min(N operations, 15) in bits 28-31 of the slot
+};
+// the fullest sub-list of the three lists' sub-lists `shard` (0: all within their room)
+__device__ __forceinline__ u32 lists_over(const u32 *gen_cnt, u32 shard, u32 cap) {
+    const u32 a = gen_cnt[shard * GEN_CNT_STRIDE], b = gen_cnt[shard * GEN_CNT_STRIDE + 2], c = gen_cnt[shard * GEN_CNT_STRIDE + 4];
+    // (the entries of list 3 that found no room were not walked by k1_generic: each of them would have gone on list 1 or 2 -- an
+    // upper bound, so that ONE repeat settles the lists)
+    const u32 dropped = c > cap ? c - cap : 0u;
+    const u32 ab = (a > b ? a : b) + dropped;
+    const u32 m = ab > c ? ab : c;
+    return m > cap ? m : 0u;
+}
+
+// The sort's tile and its digit counter (pjb_k2_sort.hip.h); kd_assign (pjb_k2d_ids.hip.h) works on the same tiles and counts the first digit
+// of the ids it hands out
+constexpr int RS_ITEMS = 16;
+constexpr int RS_TILE = 256 * RS_ITEMS; // 4096 keys per block
+constexpr int RS_MAX_BITS = 12;
+constexpr int RS_MAX_BINS = 1 << RS_MAX_BITS;
+constexpr int KDA_TILE = RS_TILE; // kd_assign's tile is the sort's
+static_assert(RS_MAX_BINS <= 4096, "kd_assign counts the sort's first digit tile by tile"); // (its table in LDS: s_h[4096])
+
+// Histogram add of one digit per lane.  Keys arrive nearly sorted and deep junctions repeat one key
+// thousands of times, so most lanes of a wave often hold the same digit: the two most common
+// leading digits are counted by one lane each (no 64-way same-address LDS conflict), the rest
+// with plain LDS atomics.
+__device__ __forceinline__ void wave_hist_add(u32 *h, u32 d, bool valid) {
+    u64 rem = __ballot(valid);
+    const int lane = lane_id();
+#pragma unroll
+    for (int it = 0; it < 2; it++) {
+        if (rem == 0) return;
+        const int first = __ffsll((long long)rem) - 1;
+        const u32 d0 = __shfl(d, first, 64);
+        const u64 m = __ballot(valid && d == d0) & rem;
+        if (lane == first) atomicAdd(&h[d0], (u32)__popcll(m));
+        rem &= ~m;
+    }
+    if ((rem >> lane) & 1ull) atomicAdd(&h[d], 1u);
+}
+
+// The id runs of the tiles (the run route of the sort, see rs_place): pairs arrive in BAM order and ids are handed out in (start, end)
+// order, so the 4 096 ids of a tile lie in a window of a few dozen consecutive ids.  kd_assign counts them in a table indexed by
+// id & (RUN_W - 1) -- exact while max - min < RUN_W -- and appends one entry per (tile, id) to the chain's run list: the key
+// id << tile_bits | tile and the number of pairs.  Sorted by key, the exclusive prefix sum of the counts is where the run's first
+// pair belongs in the sorted pair array.
+constexpr u32 RUN_W = 2048;
+struct RunOut {
+    u64 *key;         // [cap] id << tile_bits | tile, in the order the tiles reserved their room
+    u32 *cnt;         // [cap] pairs of the run
+    u32 *tile_first;  // [tiles] the tile's first entry,
+    u32 *tile_n;      //         and how many it has (ascending ids)
+    u32 *n_runs;      // entries reserved so far (kd_table zeroes it)
+    u32 cap;
+    u32 window;       // 0: the radix route (nothing of the above is touched); else a tile's ids must span less than this (<= RUN_W)
+    int tile_bits;
+};
+
+// fragment record of the per-junction reductions: 48 words (see k4_pairs)
+enum {
+    F_N = 0, F_R1P, F_R1N, F_R2P, F_R2N, F_MS, F_XSP, F_XSN, F_UM, F_BPP, F_PPP, F_REL, F_DIST, // sums
+    F_MAXMINANC, F_UP, F_DOWN, F_MAXMMES, F_MAXMINMATCH,                                       // max
+    F_FIRSTMIS,                                                                                 // min
+    F_PAD19,                                                                                    // keeps the next pair 8-byte aligned
+    F_MISM_LO, F_MISM_HI,                                                                       // 64-bit sum
+    F_JAD0,                                                                                     // 20 sums
+    F_WORDS = 48
+};
+__device__ __forceinline__ void acc_rest_state(u32 *acc, u64 n_junc) { // what k5_frag_reduce's atomics start from: sums 0, max 0, min 100000000
+    const u64 n = n_junc * F_WORDS, step = (u64)gridDim.x * blockDim.x;
+    for (u64 t = (u64)blockIdx.x * blockDim.x + threadIdx.x; t < n; t += step) acc[t] = (t % F_WORDS) == F_FIRSTMIS ? 100000000u : 0u;
 }
 
 } // namespace pjb

@@ -1,6 +1,11 @@
 // pjb_kernels.hip.h -- hand-written HIP kernels (gfx950 / CDNA4, wave64) for the
 // Portcullis `junc` hot path.  Integer / byte work bounded by HBM bandwidth; no MFMA.
 //
+//   K2d, K2, K2s and K4 have a header each, included below where their text stood, so that the unit's kernels keep their order.  A stage
+// header includes pjb_device.hip.h -- where what two stages use stands: constants, wave primitives, the layouts of buffers that pass from
+// stage to stage --, the helpers pjb_basecmp.hip.h / pjb_readops.hip.h where it compares bases or walks reads, and no other stage header;
+// each compiles on its own (tests/test_kernel_headers_standalone.py).  K0, K1 and K5 / K6 stand in this file.
+//
 // The chain of one target or group of targets (DESIGN.md section 4 has the table, the data layout and the byte counts):
 //   K1   k1_count, k1_scan_tiles   per-read CIGAR walk: N-op count, length stats, sortedness, the block-span bound B;
 //                                  the tiles' spliced lists                                                               (a1,a2)
@@ -17,6 +22,8 @@
 #pragma once
 
 #include "pjb_device.hip.h"
+#include "pjb_basecmp.hip.h"
+#include "pjb_readops.hip.h"
 
 namespace pjb {
 
@@ -229,7 +236,6 @@ __device__ __forceinline__ u32 wave_iscan_dpp(u32 v) {
     o += dpp_shift0<0x143, 0xc, 0xf>(o); // row_bcast:31
     return o;
 }
-#define PJB_LDS __attribute__((address_space(3)))
 #ifndef K1C_OPSW
 #define K1C_OPSW 3072 // operations of a tile that the fast path of k1_count keeps in LDS (a tile of 1024 reads has ~1 700)
 #endif
@@ -866,136 +872,6 @@ __global__ __launch_bounds__(K1S_THREADS) void k1_scan_tiles(u32 *tile_cnt, cons
 }
 
 // ---------------------------------------------------------------------------------------------
-// Packed-base compare helpers (used by k1_emit for the simple shape and by the generic walks of k4b_generic)
-// ---------------------------------------------------------------------------------------------
-__device__ __forceinline__ u32 nt16_ascii(u32 c) { // seq_nt16_str "=ACMGRSVTWYHKDBN"
-    // bytes: '=' 3D, 'A' 41, 'C' 43, 'M' 4D, 'G' 47, 'R' 52, 'S' 53, 'V' 56 | 'T' 54,'W' 57,'Y' 59,'H' 48,'K' 4B,'D' 44,'B' 42,'N' 4E
-    const u64 t0 = 0x565352474D43413DULL;
-    const u64 t1 = 0x4E42444B48595754ULL;
-    const u64 t = (c & 8u) ? t1 : t0;
-    return (u32)(t >> ((c & 7u) * 8)) & 0xffu;
-}
-
-// Read nibbles [qi, qi+l) (BAM order: high nibble first) against genome codes [gi, gi+l) (low nibble first), 64 bases
-// = 9 words of each per round; mismatch positions are reported relative to `out_base`.
-//   A lane's words are consecutive but the next lane's are somewhere else, so every load instruction of the wave
-// touches 64 cache lines whatever its width, and the number of load INSTRUCTIONS sets the pace (measured in
-// k4a_simple: 19 per-word loads per read cost 80 us per contig, the compare itself nothing).  So the words come as two
-// 16-byte loads and one 4-byte load per stream -- 4-byte aligned (reads start on word boundaries), which
-// global_load_dwordx4 accepts -- guarded so that nothing is read past the read's last word / the contig's last code
-// word; the short tail of a stream takes guarded word loads.
-__device__ __forceinline__ u32 swap_nibbles(u32 x) { return ((x & 0x0F0F0F0Fu) << 4) | ((x >> 4) & 0x0F0F0F0Fu); }
-// A chunk = NW consecutive words of each stream = (NW - 1) * 8 anchor bases per round (the extra word feeds the funnel
-// shift of the last one): NW = 9 -> two 16-byte loads and one word per stream, NW = 5 -> one 16-byte load and one word.
-template <int NW>
-struct CmpChunkT {
-    u32 qw[NW], gg[NW];
-};
-// d[k] = p[first + k] for 0 <= first + k <= last, else 0
-template <int NW>
-__device__ __forceinline__ void load_words(u32 (&d)[NW], const u32 *p, int32_t first, int32_t last) {
-    static_assert(NW == 9 || NW == 8 || NW == 5, "chunk width");
-    if (first >= 0 && first + NW - 1 <= last) {
-        const Words4 a = gload(reinterpret_cast<const Words4 *>(p + first));
-        d[0] = a.x, d[1] = a.y, d[2] = a.z, d[3] = a.w;
-        if constexpr (NW >= 8) {
-            const Words4 b = gload(reinterpret_cast<const Words4 *>(p + first + 4));
-            d[4] = b.x, d[5] = b.y, d[6] = b.z, d[7] = b.w;
-        }
-        if constexpr (NW != 8) d[NW - 1] = gload(p + first + NW - 1); // (NW = 8: two 16-byte loads and nothing else -- 56 bases a round)
-    } else {
-#pragma unroll
-        for (int k = 0; k < NW; k++) d[k] = (first + k >= 0 && first + k <= last) ? gload(p + first + k) : 0u;
-    }
-}
-// anchor bases [t, t + 8 (NW - 1)) of an anchor of l bases: read bases from qi (words of the read up to word q_last may be
-// touched: whatever lies past the anchor only feeds bits that the length mask removes), genome from gi
-// TO_BUFFER_END: q_last is the last word of the batch's bases (relative to the read) and the genome may be read up to its last
-// code word, not only to the anchor's: the last round of an anchor then takes the 16-byte loads too instead of one guarded
-// load per word (what lies past the anchor is masked either way).
-template <int NW, bool TO_BUFFER_END = false>
-__device__ __forceinline__ void chunk_load(CmpChunkT<NW> &C, const u32 *seqw, int32_t qi, int32_t q_last, const u32 *gw, int32_t gi, int32_t g_words,
-                                           int32_t l, int32_t t) {
-    const int32_t lastg = (gi + l - 1) >> 3;
-    load_words<NW>(C.qw, seqw, (qi + t) >> 3, q_last);
-    // (genome words outside [0, g_words) and -- but for TO_BUFFER_END -- past the anchor's last word read as 0, as they always did)
-    load_words<NW>(C.gg, gw, (gi + t) >> 3, !TO_BUFFER_END && lastg < g_words - 1 ? lastg : g_words - 1);
-}
-template <int NW>
-__device__ __forceinline__ void chunk_cmp(CmpChunkT<NW> &C, int32_t qi, int32_t gi, int32_t l, int32_t t, int32_t out_base, int32_t &mism,
-                                          int32_t &first_mis, int32_t &last_mis) {
-    const u32 shq = (u32)(qi & 7) * 4u, shg = (u32)(gi & 7) * 4u; // (t is a multiple of 8: the shifts do not move)
-#pragma unroll
-    for (int k = 0; k < NW; k++) C.qw[k] = swap_nibbles(C.qw[k]);
-#pragma unroll
-    for (int c = 0; c < NW - 1; c++) {
-        const int32_t rem = l - t - 8 * c;
-        if (rem > 0) {
-            const u32 q = __builtin_amdgcn_alignbit(C.qw[c + 1], C.qw[c], shq);
-            const u32 g = __builtin_amdgcn_alignbit(C.gg[c + 1], C.gg[c], shg);
-            const u32 x = q ^ g;
-            u32 m = (((x & 0x77777777u) + 0x77777777u) | x) & 0x88888888u; // top bit of every nibble that differs
-            if (rem < 8) m &= (1u << (4 * rem)) - 1u;
-            if (m) {
-                mism += __popc(m);
-                if (first_mis < 0) first_mis = out_base + t + 8 * c + ((__ffs((int)m) - 1) >> 2);
-                last_mis = out_base + t + 8 * c + ((31 - __clz((int)m)) >> 2);
-            }
-        }
-    }
-}
-// v_ffbl_b32 / v_ffbh_u32 as the hardware defines them: 0xffffffff for 0 (the language's count-zeros builtins leave 0 undefined or
-// cost a second instruction)
-__device__ __forceinline__ u32 ffbl_hw(u32 x) {
-    u32 r;
-    asm("v_ffbl_b32 %0, %1" : "=v"(r) : "v"(x));
-    return r;
-}
-__device__ __forceinline__ u32 ffbh_hw(u32 x) {
-    u32 r;
-    asm("v_ffbh_u32 %0, %1" : "=v"(r) : "v"(x));
-    return r;
-}
-// chunk_cmp without a branch: the words' flags (top bit of every nibble that differs) are cut to the anchor's length by a shift pair
-// (no compare / select, nothing skipped), and the first / last mismatch are kept as BIT positions 4 * base + 3 from the anchor's
-// start -- fbit: the lowest (0xffffffff: none), lbit1: the highest + 1 (0: none) -- folded with saturating adds and min / max, which
-// make a word without mismatches neutral (v_ffbl / v_ffbh return 0xffffffff for it).  base = (int32_t)fbit >> 2 and
-// ((int32_t)lbit1 - 1) >> 2, -1 for none.  20 vector instructions a word where chunk_cmp takes 26 and seven scalar ones.
-template <int NW>
-__device__ __forceinline__ void chunk_cmp_bits(CmpChunkT<NW> &C, int32_t qi, int32_t gi, int32_t l, int32_t t, u32 &mism, u32 &fbit, u32 &lbit1) {
-    const u32 shq = (u32)(qi & 7) * 4u, shg = (u32)(gi & 7) * 4u;
-#pragma unroll
-    for (int k = 0; k < NW; k++) C.qw[k] = swap_nibbles(C.qw[k]);
-    const int32_t rem2 = 2 * (l - t); // twice the bases left from the chunk's first
-    u32 fw = 0xffffffffu, lw = 0;
-#pragma unroll
-    for (int c = 0; c < NW - 1; c++) {
-        int32_t w2 = rem2 - 16 * c; // twice the word's valid bases, 0 .. 16
-        w2 = w2 < 0 ? 0 : (w2 > 16 ? 16 : w2);
-        const u32 inval = (0xffffffffu << (u32)w2) << (u32)w2; // (two shifts: a shift by 32 would not move)
-        const u32 q = __builtin_amdgcn_alignbit(C.qw[c + 1], C.qw[c], shq);
-        const u32 g = __builtin_amdgcn_alignbit(C.gg[c + 1], C.gg[c], shg);
-        const u32 x = q ^ g;
-        const u32 m = (((x & 0x77777777u) + 0x77777777u) | x) & (0x88888888u & ~inval);
-        mism += (u32)__popc(m);
-        fw = min(fw, __builtin_elementwise_add_sat(ffbl_hw(m), 32u * (u32)c));
-        lw = max(lw, __builtin_elementwise_sub_sat(32u * (u32)c + 32u, ffbh_hw(m)));
-    }
-    fbit = min(fbit, __builtin_elementwise_add_sat(fw, 4u * (u32)t));
-    lbit1 = lw ? lw + 4u * (u32)t : lbit1; // (rounds ascend)
-}
-// one stretch of l bases
-template <int NW, bool TO_BUFFER_END = false>
-__device__ __forceinline__ void cmp_words(const u32 *seqw, int32_t qi, int32_t q_last, const u32 *gw, int32_t gi, int32_t g_words, int32_t l,
-                                          int32_t out_base, int32_t &mism, int32_t &first_mis, int32_t &last_mis) {
-    for (int32_t t = 0; t < l; t += 8 * (NW - 1)) {
-        CmpChunkT<NW> C;
-        chunk_load<NW, TO_BUFFER_END>(C, seqw, qi, q_last, gw, gi, g_words, l, t);
-        chunk_cmp<NW>(C, qi, gi, l, t, out_base, mism, first_mis, last_mis);
-    }
-}
-
-// ---------------------------------------------------------------------------------------------
 // K1b: per-read CIGAR walk, pass 2: emit one pair per N op in BAM order
 // (JunctionSystem::addJunctions junction_system.cc:140-210 restated iteratively:
 //  after an N op the next left anchor starts at the CLAMPED rStart; rEndExc is the UNCLAMPED
@@ -1006,97 +882,6 @@ __device__ __forceinline__ void cmp_words(const u32 *seqw, int32_t qi, int32_t q
 // of a read of the common [S] M N M [S] shape with the genome (AlignmentInfo::calcMatchStats,
 // junction.cc:147-240): the pair's record leaves this kernel complete.
 // ---------------------------------------------------------------------------------------------
-// CIGAR ops of one alignment: the first OPS_LDS ops are staged in LDS (one column per thread), the
-// rest (long reads) are read from global memory
-constexpr int OPS_LDS = 8;
-template <int STRIDE, int NLDS>
-struct OpsViewT {
-    const uint32_t *g;
-    const u32 *lds; // &s_ops[0][column]: NLDS rows of STRIDE columns
-    __device__ __forceinline__ u32 operator[](u32 k) const { return k < (u32)NLDS ? lds[k * STRIDE] : gload(g + k); }
-};
-typedef OpsViewT<256, OPS_LDS> OpsView;
-// The first OPS_LDS operations of a read whose operations start at word c0 of its batch's `cig_words` words: two 16-byte loads (a lane's
-// eight words are neighbours: eight word gathers cost the addresser eight times as much).  The batch's last operations are read from
-// eight words before its end and shifted -- the loads never leave the array --; what lies behind the read's last operation is the next
-// read's, the caller masks it.
-__device__ __forceinline__ void fetch_ops8(const PJB_GLOBAL u32 *cigar, u32 c0, u32 cig_words, u32 (&w)[OPS_LDS]) {
-    static_assert(OPS_LDS == 8, "two 16-byte loads");
-    if (cig_words >= (u32)OPS_LDS) {
-        const u32 c0c = c0 + (u32)OPS_LDS <= cig_words ? c0 : cig_words - (u32)OPS_LDS;
-        const Words4 lo4 = gload_as<Words4>(cigar + c0c), hi4 = gload_as<Words4>(cigar + c0c + 4);
-        w[0] = lo4.x, w[1] = lo4.y, w[2] = lo4.z, w[3] = lo4.w, w[4] = hi4.x, w[5] = hi4.y, w[6] = hi4.z, w[7] = hi4.w;
-        if (c0c != c0) { // (shifted: at most seven words)
-            const u32 sh = c0 - c0c;
-#pragma unroll
-            for (int q = 0; q < OPS_LDS; q++) {
-                u32 v = 0;
-#pragma unroll
-                for (int j = q; j < OPS_LDS; j++) v = (u32)(j - q) == sh ? w[j] : v;
-                w[q] = v;
-            }
-        }
-    } else { // (a batch of fewer than eight operations: word by word, guarded)
-#pragma unroll
-        for (int q = 0; q < OPS_LDS; q++) w[q] = c0 + (u32)q < cig_words ? cigar[c0 + (u32)q] : 0u;
-    }
-}
-// What k1_generic and k4b_generic keep of the chain's batches in LDS, filled once per block (256 threads): a read's batch is found from
-// its tile without a load, and the ends of the batch's arrays -- nothing reads past them -- are at hand.  A chain of more batches than
-// the table holds searches the descriptors in device memory.
-constexpr int GEN_MAXB = 256;
-struct BatchTab {
-    u32 tbase[GEN_MAXB], seqw[GEN_MAXB], cigw[GEN_MAXB]; // the batch's first tile; words of packed bases / of operations in it
-    __device__ __forceinline__ void fill(const DevBatch *batches, int n_batches) { // (the caller's barrier follows)
-        if ((int)threadIdx.x < n_batches && threadIdx.x < (u32)GEN_MAXB) {
-            const PJB_GLOBAL DevBatch *d = as_global(batches + threadIdx.x);
-            tbase[threadIdx.x] = d->tile_base;
-            seqw[threadIdx.x] = as_global(d->seq_off)[d->n];
-            cigw[threadIdx.x] = as_global(d->cig_off)[d->n];
-        }
-    }
-    __device__ __forceinline__ int find(const DevBatch *batches, int n_batches, u32 tile) const { // the last batch with tile_base <= tile
-        int lo = 0, hi = n_batches - 1;
-        if (n_batches <= GEN_MAXB) {
-            while (lo < hi) {
-                const int mid = (lo + hi + 1) >> 1;
-                if (tbase[mid] <= tile) lo = mid;
-                else hi = mid - 1;
-            }
-        } else {
-            while (lo < hi) {
-                const int mid = (lo + hi + 1) >> 1;
-                if (gload(&batches[mid].tile_base) <= tile) lo = mid;
-                else hi = mid - 1;
-            }
-        }
-        return lo;
-    }
-    __device__ __forceinline__ u32 seq_words(const DevBatch &b, int bi) const { return bi < GEN_MAXB ? seqw[bi] : gload(b.seq_off + b.n); }
-    __device__ __forceinline__ u32 cig_words(const DevBatch &b, int bi) const { return bi < GEN_MAXB ? cigw[bi] : gload(b.cig_off + b.n); }
-};
-
-struct NCursor { // walks the N ops of one CIGAR yielding the unclamped position after each N
-    u32 i;
-    int32_t acc;
-    bool has;
-    int32_t peek;
-};
-template <typename Ops>
-__device__ __forceinline__ void ncursor_advance(NCursor &c, const Ops cig, u32 n) {
-    c.has = false;
-    while (c.i < n) {
-        u32 op = cig[c.i++];
-        u32 ty = op & 15u;
-        if (op_consumes_ref(ty)) c.acc += (int32_t)(op >> 4);
-        if (ty == OP_N) {
-            c.has = true;
-            c.peek = c.acc;
-            return;
-        }
-    }
-}
-
 // (profiles/r04e_compare_variants.txt: 32 bases a round with both anchors' words in flight together / 56 together / 32 one anchor
 // after the other / 56 one after the other = 10.56 / 11.56 / 10.07 / 9.97 ms a step; since then an anchor is a block compared on
 // its own, one after the other)
@@ -1304,31 +1089,6 @@ constexpr int K1E_LOOK = 16;
 #endif
 constexpr int K1E_T = 256, K1E_SHIFT = 8; // threads of a block = list entries of one trip
 constexpr int KC_SLOTS = K1E_T;               // the block's candidate set (LDS), flushed when a quarter full: a slot per thread (two: 8.82 against 8.75 ms a step)
-constexpr u64 KD_EMPTY = ~0ull; // no key: a packed key has fewer than 64 bits
-constexpr int KD_PAGE_SHIFT = 6; // a page of the start bitmap: 64 words, one wavefront
-struct EmitLists {
-    u64 *cand;      // candidate keys (nullptr: the chain sorts the full keys and wants none); their count is ContigStats::n_cand
-    u64 *bitmap;    // K2d's bitmap of intron starts (all-clear at rest): every candidate sets its start's bit as it is listed
-    u32 *page_cnt;  // starts per PAGE of the bitmap (64 words = 4 096 bases; all-zero at rest): counted as their bits are set for the first time
-    u64 *cand_anc;  // per candidate: min lStart | max rEnd << 32 over the pairs it stands for (the junction anchors' first level)
-    u64 *gen_list;  // [3][GEN_SHARDS][gen_cap], every entry the read's slot in the tiles' spliced lists (spl_idx, spl_rec: what k1_count kept of it)
-                    // | index of its first pair << 32.  Lists 1 and 2, for k4b_generic: the reads whose pairs need the generic walks; the reads
-                    // whose closed form waits for the window check.  List 3, for k1_generic.
-    u32 *gen_cnt;   // [GEN_SHARDS][GEN_CNT_STRIDE]: words 2 l - 2, 2 l - 1 = entries of list l's sub-list, pairs of those reads -- a cache
-                    // line per shard: atomics on one line are served one after the other, whatever the address in it
-    u32 gen_cap;    // room of one sub-list
-    u32 pack_nn;    // 1 (chains of fewer than 2^28 slots): entries of the second list carry min(N operations, 15) in bits 28-31 of the slot
-};
-// the fullest sub-list of the three lists' sub-lists `shard` (0: all within their room)
-__device__ __forceinline__ u32 lists_over(const u32 *gen_cnt, u32 shard, u32 cap) {
-    const u32 a = gen_cnt[shard * GEN_CNT_STRIDE], b = gen_cnt[shard * GEN_CNT_STRIDE + 2], c = gen_cnt[shard * GEN_CNT_STRIDE + 4];
-    // (the entries of list 3 that found no room were not walked by k1_generic: each of them would have gone on list 1 or 2 -- an
-    // upper bound, so that ONE repeat settles the lists)
-    const u32 dropped = c > cap ? c - cap : 0u;
-    const u32 ab = (a > b ? a : b) + dropped;
-    const u32 m = ab > c ? ab : c;
-    return m > cap ? m : 0u;
-}
 // What k1_emit and k1_generic share: the block's candidate set (LDS) and the appends to k4b_generic's / k1_generic's lists.
 struct EmitShared {
     u64 set[KC_SLOTS];
@@ -2099,1514 +1859,14 @@ __global__ __launch_bounds__(256) void kg_member_stats(const u32 *tile_off, cons
     }
 }
 
-// ---------------------------------------------------------------------------------------------
-// K2d: ordered dense junction ids.  The intron key is 46-48 bits wide (contig coordinate + intron length): five radix
-// passes, the first of them over digits that differ for every junction of a tile.  But a contig has 10^4-10^5
-// distinct introns, and their RANK in (start, end) order needs 15-19 bits: two passes -- and because the ranks of
-// the junctions a tile touches are neighbours (pairs arrive in BAM order, ranks are ordered by start), both passes
-// scatter into a few long runs per tile.  The rank comes without sorting anything:
-//   k1_emit    pairs -> candidate keys (distinct per block residency; see there)
-//   (k1_emit / k1_generic also set one bit per contig base where an intron of a listed candidate starts)
-//   scan       prefix popcount over the bitmap words  -> rank of a start among the distinct starts
-//   kd_ends    per start rank, the distinct intron ends seen (alternative acceptors: a handful; DENSE_ENDS slots)
-//   scan       number of ends per start rank           -> first junction id of every start (+ the anchors' rest state)
-//   kd_table   junction id -> intron key and the junction's anchors (min lStart, max rEnd over its pairs, junction.cc:477-529),
-//              from the candidates; closes the chain if a limit was exceeded
-//   kd_assign  id of a pair = first id of its start + number of that start's ends below its own end
-// Grouping by id is grouping by (start, end), id order is (start, end) order, so everything downstream -- segment
-// heads, fragments, row order -- works on the ids as it did on the keys.  A start with more than DENSE_ENDS different
-// ends raises OVF_DENSE and the contig is repeated with the full-key sort.
-// ---------------------------------------------------------------------------------------------
-constexpr int DENSE_ENDS = 8;
-constexpr u32 DENSE_EMPTY = 0xffffffffu;
+} // namespace pjb
 
-__device__ __forceinline__ u32 start_rank(const u64 *bitmap, const u32 *wrank, int32_t start) {
-    const u32 w = (u32)start >> 6;
-    return wrank[w] + (u32)__popcll(bitmap[w] & ((1ull << (start & 63)) - 1ull));
-}
-// Pairs arrive in BAM order, so the pairs of a junction sit close together, and a deep junction is one key repeated 10^5
-// times.  Operations on device memory that many waves aim at one address (or one cache line: the bitmap words of
-// neighbouring starts) are served one after the other by a single L2 channel -- measured, 0.5 ns each, 1.4 ms for the
-// pairs of one contig.  So only the CANDIDATE list (1-3x the number of junctions) touches the bitmap and the end slots.
-// candidates -> one bit per contig base: an intron starts here
-struct PopcFn {
-    const u64 *words;
-    __device__ u64 operator()(u64 i) const { return (u64)__popcll(words[i]); }
-};
-__global__ __launch_bounds__(256) void kd_ends(const u64 *cand, KeyFmt kf, const u64 *bitmap, const u32 *wrank, u32 junc_limit, u32 *ends,
-                                               u32 *cand_rank, ContigStats *cs) {
-    const u32 n = cs->n_cand; // (a few candidates per junction: the grid is small and strides)
-    for (u32 p = blockIdx.x * 256 + threadIdx.x; p < n; p += gridDim.x * 256) {
-        int32_t s, e;
-        unpack_key(kf, cand[p], s, e);
-        const u32 rs = start_rank(bitmap, wrank, s);
-        cand_rank[p] = rs;
-        if (rs >= junc_limit) {
-            atomicOr(&cs->overflow, OVF_JUNC);
-            continue;
-        }
-        u32 *slot = ends + (size_t)rs * DENSE_ENDS;
-        const u32 ue = (u32)e;
-        bool placed = false;
-        for (int k = 0; k < DENSE_ENDS && !placed; k++) {
-            const u32 cur = atomicCAS(&slot[k], DENSE_EMPTY, ue);
-            placed = cur == DENSE_EMPTY || cur == ue; // else: the slot holds another end (slots never change once set)
-        }
-        if (!placed) atomicOr(&cs->overflow, OVF_DENSE);
-    }
-}
-// The ranks of the bitmap's words, page by page: the starts are few (a third of the pages of a human-sized chain hold one, fewer
-// where genes cluster), so the prefix sum runs over the PAGES' counts (k1_emit / k1_generic count a start when its bit is set for
-// the first time) and only the pages that hold a start are read: a wavefront per page, lane = word, the word's rank = the page's
-// rank + the popcounts of the page's words before it.  Words of pages without a start keep whatever rank they had: nobody asks
-// for it (kd_ends, kd_assign look up the words of their own starts).  (Until round 5 a three-kernel scan read all of the bitmap
-// twice and wrote every word's rank: 320 MB and 90 us a 1-Gb chain.)
-__global__ __launch_bounds__(256) void kd_rank_pages(const u64 *bitmap, const u32 *page_cnt, const u32 *page_rank, u32 *wrank, u32 n_pages, u32 n_words) {
-    const u32 page = blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (page >= n_pages) return;
-    if (page_cnt[page] == 0) return; // (uniform per wavefront)
-    const u32 w = (page << KD_PAGE_SHIFT) + (u32)lane_id();
-    const u32 c = w < n_words ? (u32)__popcll(bitmap[w]) : 0u;
-    const u32 inc = wave_iscan(c);
-    if (w < n_words) wrank[w] = page_rank[page] + inc - c;
-}
-// Bitmap, page counts and end slots are all-clear at rest: instead of memsets over contig-sized buffers per contig, the
-// candidates wipe exactly what they set (after kd_assign has read it).
-__global__ __launch_bounds__(256) void kd_reset(const u64 *cand, const u32 *cand_rank, KeyFmt kf, u32 junc_limit, const ContigStats *cs,
-                                                u64 *bitmap, u32 *ends, u32 *page_cnt) {
-    const u32 n = cs->n_cand;
-    for (u32 p = blockIdx.x * 256 + threadIdx.x; p < n; p += gridDim.x * 256) {
-        int32_t s, e;
-        unpack_key(kf, cand[p], s, e);
-        bitmap[(u32)s >> 6] = 0;
-        page_cnt[(u32)s >> (6 + KD_PAGE_SHIFT)] = 0;
-        const u32 rs = cand_rank[p];
-        if (rs < junc_limit) {
-            uint4 *q = reinterpret_cast<uint4 *>(ends + (size_t)rs * DENSE_ENDS);
-            q[0] = q[1] = make_uint4(DENSE_EMPTY, DENSE_EMPTY, DENSE_EMPTY, DENSE_EMPTY);
-        }
-    }
-}
-struct EndsCountFn {
-    const u32 *ends;
-    __device__ u64 operator()(u64 rs) const {
-        const uint4 *q = reinterpret_cast<const uint4 *>(ends + rs * DENSE_ENDS);
-        const uint4 a = q[0], b = q[1];
-        return (u64)((a.x != DENSE_EMPTY) + (a.y != DENSE_EMPTY) + (a.z != DENSE_EMPTY) + (a.w != DENSE_EMPTY) + (b.x != DENSE_EMPTY) +
-                     (b.y != DENSE_EMPTY) + (b.z != DENSE_EMPTY) + (b.w != DENSE_EMPTY));
-    }
-};
-// sink of the scan over the start ranks (junc_limit entries): first junction id of the start, and -- entry i of the
-// junction-sized anchor arrays -- the rest state kd_assign's atomics start from
-struct FirstIdSink {
-    u32 *first_id;
-    int32_t *anc_l, *anc_r;
-    __device__ void operator()(u64 i, u64, u64 ex) const {
-        first_id[i] = (u32)ex;
-        anc_l[i] = INT32_MAX;
-        anc_r[i] = INT32_MIN;
-    }
-};
-__device__ __forceinline__ u32 ends_below(const u32 *ends, u32 rs, u32 ue) { // (DENSE_EMPTY slots compare as larger than any end)
-    const uint4 *q = reinterpret_cast<const uint4 *>(ends + (size_t)rs * DENSE_ENDS);
-    const uint4 a = q[0], b = q[1];
-    return (a.x < ue) + (a.y < ue) + (a.z < ue) + (a.w < ue) + (b.x < ue) + (b.y < ue) + (b.z < ue) + (b.w < ue);
-}
-// Junction anchors from pairs that sit in the lanes of a wavefront (any order): leftAncStart = min lStart, rightAncEnd = max
-// rEnd (junction.cc:477-529).  In BAM order the pairs of the two or three junctions of a locus alternate from lane to lane, so
-// the wavefront takes its DISTINCT junctions one after the other -- all lanes of one junction are folded on the DPP path,
-// whatever lies between them -- and one lane per junction touches the arrays, and only if the value would move them (a
-// read at L2 first: the arrays only ever move one way, so an older value errs on the side of one atomic too many).  (Folding
-// neighbouring lanes only left one atomic per lane wherever junctions alternate: 1.4 ms per chain on one L2 channel.)
-__device__ __forceinline__ void anchors_fold(bool valid, u32 j, int32_t l, int32_t r, int32_t *anc_l, int32_t *anc_r) {
-    const u32 lk = (u32)l ^ 0x80000000u, rk = (u32)r ^ 0x80000000u; // (signed order through the sign bit)
-    u64 todo = __ballot(valid);
-    while (todo) {
-        const int first = __ffsll((long long)todo) - 1;
-        const u32 jc = (u32)__builtin_amdgcn_readlane((int)j, first);
-        const bool mine = valid && j == jc;
-        const u64 m = __ballot(mine);
-        const int32_t lo = (int32_t)(wave_total<DppMin>(mine ? lk : 0xffffffffu) ^ 0x80000000u);
-        const int32_t hi = (int32_t)(wave_total<DppMax>(mine ? rk : 0u) ^ 0x80000000u);
-        if (lane_id() == first) { // (the look goes to L2, where the atomics are done: a CU's L1 would keep showing it the line it fetched first)
-            if (lo < __hip_atomic_load(&anc_l[jc], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) atomicMin(&anc_l[jc], lo);
-            if (hi > __hip_atomic_load(&anc_r[jc], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) atomicMax(&anc_r[jc], hi);
-        }
-        todo &= ~m;
-    }
-}
+#include "pjb_k2d_ids.hip.h"  // K2d  kd_*
+#include "pjb_k2_sort.hip.h"   // K2   rs_*
+#include "pjb_k2s_runs.hip.h"  // K2s  k2_*, kf_*
+#include "pjb_k4_pairs.hip.h"  // K4b, K4, K5a  k4b_generic, k4_pairs, k5_frag_reduce
 
-// junction id -> intron key (every candidate writes its junction's entry: duplicates write the same value) and the junction's
-// anchors from the candidates' partial ones; thread 0 closes the chain -- P = 0, nothing downstream runs, the host repeats the
-// contig -- if a limit was exceeded while the ids were built
-__global__ __launch_bounds__(256) void kd_table(const u64 *cand, const u64 *cand_anc, const u32 *cand_rank, KeyFmt kf, u32 junc_limit, const u32 *ends,
-                                                const u32 *first_id, const u64 *total, u64 *jkey, int32_t *anc_l, int32_t *anc_r, ContigStats *cs,
-                                                const u32 *gen_cnt, u32 gen_cap, u32 sort_limit, u32 *n_runs, int range_shift) {
-    const u32 p = blockIdx.x * 256 + threadIdx.x;
-    if (blockIdx.x == 0) { // (the read lists: every sub-list within its room?)
-        static_assert(GEN_SHARDS == 256, "a shard per thread of the first block");
-        const u32 over = lists_over(gen_cnt, threadIdx.x, gen_cap);
-        if (over) atomicMax(&cs->list_need, over);
-        if (__syncthreads_or((int)over) && threadIdx.x == 0) cs->overflow |= OVF_LISTS;
-    }
-    if (p == 0) {
-        if (n_runs) *n_runs = 0; // (the run list kd_assign fills: see RunOut)
-        const u64 J = *total;
-        u32 ovf = cs->overflow;
-        // (sort_limit: the ids the sort's digits were planned for -- what chains of this context have had so far, with room; junc_limit:
-        // what the buffers hold)
-        if (cs->P != 0 && (J > (u64)junc_limit || J > (u64)sort_limit)) {
-            ovf |= OVF_JUNC;
-            cs->overflow = ovf;
-            cs->n_junc = (u32)(J < 0xffffffffull ? J : 0xffffffffull);
-        }
-        if (ovf) cs->P = 0;
-        else if (cs->P) { // the ids ARE the junctions: their number and the fragment slots are known from here on
-            const u32 n_pairs = cs->P;
-            cs->n_junc = cs->J = (u32)J;
-            cs->n_slices = (n_pairs + 63) / 64;
-            cs->n_slots = frag_slots((u32)J, n_pairs, range_shift);
-        }
-    }
-    const u32 n = cs->n_cand;
-    for (u32 base = blockIdx.x * 256u; base < n; base += gridDim.x * 256u) {
-        const u32 q = base + threadIdx.x;
-        const bool on = q < n;
-        const u32 pc = on ? q : n - 1;
-        const u32 rs = cand_rank[pc];
-        const u64 k = cand[pc], a = cand_anc[pc];
-        bool valid = on && rs < junc_limit;
-        u32 id = 0xffffffffu;
-        if (valid) {
-            int32_t s, e;
-            unpack_key(kf, k, s, e);
-            id = first_id[rs] + ends_below(ends, rs, (u32)e);
-            valid = id < junc_limit;
-            if (valid) jkey[id] = k;
-        }
-        // (a junction has a candidate or two: the lanes of a wavefront hold different junctions, there is nothing to fold -- each lane
-        // moves its junction's anchors itself, and only if its value would move them)
-        if (valid) {
-            const int32_t lo = (int32_t)(u32)a, hi = (int32_t)(u32)(a >> 32);
-            if (lo < __hip_atomic_load(&anc_l[id], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) atomicMin(&anc_l[id], lo);
-            if (hi > __hip_atomic_load(&anc_r[id], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) atomicMax(&anc_r[id], hi);
-        }
-    }
-}
-
-// fragment record of the per-junction reductions: 48 words (see k4_pairs)
-enum {
-    F_N = 0, F_R1P, F_R1N, F_R2P, F_R2N, F_MS, F_XSP, F_XSN, F_UM, F_BPP, F_PPP, F_REL, F_DIST, // sums
-    F_MAXMINANC, F_UP, F_DOWN, F_MAXMMES, F_MAXMINMATCH,                                       // max
-    F_FIRSTMIS,                                                                                 // min
-    F_PAD19,                                                                                    // keeps the next pair 8-byte aligned
-    F_MISM_LO, F_MISM_HI,                                                                       // 64-bit sum
-    F_JAD0,                                                                                     // 20 sums
-    F_WORDS = 48
-};
-__device__ __forceinline__ void acc_rest_state(u32 *acc, u64 n_junc) { // what k5_frag_reduce's atomics start from: sums 0, max 0, min 100000000
-    const u64 n = n_junc * F_WORDS, step = (u64)gridDim.x * blockDim.x;
-    for (u64 t = (u64)blockIdx.x * blockDim.x + threadIdx.x; t < n; t += step) acc[t] = (t % F_WORDS) == F_FIRSTMIS ? 100000000u : 0u;
-}
-
-// (the sort's tile and its digit counter, defined with the sort below: kd_assign counts the first digit of the ids it hands out)
-constexpr int KDA_TILE = 4096; // = RS_TILE
-__device__ __forceinline__ void wave_hist_add(u32 *h, u32 d, bool valid);
-constexpr int KDA_PER = 4;
-// The id runs of the tiles (the run route of the sort, see rs_place): pairs arrive in BAM order and ids are handed out in (start, end)
-// order, so the 4 096 ids of a tile lie in a window of a few dozen consecutive ids.  kd_assign counts them in a table indexed by
-// id & (RUN_W - 1) -- exact while max - min < RUN_W -- and appends one entry per (tile, id) to the chain's run list: the key
-// id << tile_bits | tile and the number of pairs.  Sorted by key, the exclusive prefix sum of the counts is where the run's first
-// pair belongs in the sorted pair array.
-constexpr u32 RUN_W = 2048;
-struct RunOut {
-    u64 *key;         // [cap] id << tile_bits | tile, in the order the tiles reserved their room
-    u32 *cnt;         // [cap] pairs of the run
-    u32 *tile_first;  // [tiles] the tile's first entry,
-    u32 *tile_n;      //         and how many it has (ascending ids)
-    u32 *n_runs;      // entries reserved so far (kd_table zeroes it)
-    u32 cap;
-    u32 window;       // 0: the radix route (nothing of the above is touched); else a tile's ids must span less than this (<= RUN_W)
-    int tile_bits;
-};
-static_assert(RUN_W == 256 * 8, "kd_assign compacts eight table entries a thread");
-// a tile's ids span more than the window, or the run list is full: the chain is closed (as kd_table closes it) and repeated on the radix route
-__device__ __forceinline__ void runs_close_chain(ContigStats *cs) {
-    atomicOr(&cs->overflow, OVF_RUNS);
-    cs->P = 0;
-    cs->J = 0;
-    cs->n_slots = 0;
-    cs->n_slices = 0;
-}
-__global__ __launch_bounds__(256) void kd_assign(const u64 *key, const u32 *np, KeyFmt kf, const u64 *bitmap, const u32 *wrank, const u32 *ends,
-                                                 const u32 *first_id, u32 junc_limit, const u64 *total, u32 *jid_bam, u32 *acc, const u64 *jkey,
-                                                 const int32_t *anc_l, const int32_t *anc_r, u64 *err, ContigStats *cs_chk, int hist_bits, u32 *hist,
-                                                 RunOut ro) {
-    // A block takes one TILE of the sort (4 096 pairs, four chunks of 1 024) and leaves the tile's counts of the ids' first digit
-    // where rs_hist would have put them (hist_bits > 0): the sort's first pass starts at its scan -- the ids are not read a second
-    // time to be counted.  On the run route (ro.window, hist_bits = 0) it leaves the tile's id runs instead.
-    __shared__ u32 s_h[4096]; // (RS_MAX_BINS; the run route: RUN_W counters)
-    __shared__ u32 s_run[4];  // the tile's least and largest id, its first entry in the run list
-    __shared__ u32 s_rscan[4];
-    const u32 n = *np;
-    if (n == 0) { // (a chain without pairs, or closed by an overflow: the tile's counts are still this kernel's to write -- zeros --, the
-                  // panel kernels behind it read them)
-        if (hist_bits > 0)
-            for (u32 d = threadIdx.x; d < (1u << hist_bits); d += 256) hist[(size_t)blockIdx.x * (1u << hist_bits) + d] = 0;
-        return;
-    }
-    {
-        const u64 J = *total;
-        acc_rest_state(acc, J < (u64)junc_limit ? J : (u64)junc_limit);
-    }
-    const u32 nb = hist_bits > 0 ? 1u << hist_bits : 0u;
-    for (u32 d = threadIdx.x; d < (ro.window ? RUN_W : nb); d += 256) s_h[d] = 0;
-    if (threadIdx.x == 0) {
-        s_run[0] = 0xffffffffu;
-        s_run[1] = 0u;
-    }
-    if (nb || ro.window) __syncthreads();
-    u32 id_lo = 0xffffffffu, id_hi = 0u; // (this thread's pairs)
-    for (u32 chunk = blockIdx.x * (KDA_TILE / (KDA_PER * 256)); chunk < (blockIdx.x + 1) * (KDA_TILE / (KDA_PER * 256)); chunk++) {
-    if (chunk * (KDA_PER * 256) >= n) break;
-    // KDA_PER pairs a thread, their loads side by side: a pair is a chain of three dependent look-ups (key -> bitmap word and rank ->
-    // end slots and first id), and a wavefront with one pair per lane (651 k of them a chain) spent its life waiting for them one
-    // after the other -- 134 us a chain (round 4) for 267 MB
-    // Pairs arrive in BAM order: the lanes of a wavefront mostly hold the pairs of one or two junctions.  Only the first lane of a run
-    // of equal keys (a "leader") looks its junction up -- the look-ups are gathers of 56 bytes a pair, and their cost follows the
-    // lanes that take part -- the others take the leader's answer (one ds_bpermute).
-    u64 kk[KDA_PER];
-    u32 pp[KDA_PER];
-#pragma unroll
-    for (int q = 0; q < KDA_PER; q++) {
-        pp[q] = (chunk * KDA_PER + q) * 256 + threadIdx.x;
-        kk[q] = key[pp[q] < n ? pp[q] : n - 1];
-    }
-    bool lead[KDA_PER];
-    int32_t ss[KDA_PER], ee[KDA_PER];
-    u64 bw[KDA_PER];
-    u32 wr[KDA_PER];
-#pragma unroll
-    for (int q = 0; q < KDA_PER; q++) {
-        const u32 plo = (u32)__builtin_amdgcn_update_dpp(0, (int)(u32)kk[q], 0x138, 0xf, 0xf, false);         // wave_shr:1
-        const u32 phi = (u32)__builtin_amdgcn_update_dpp(0, (int)(u32)(kk[q] >> 32), 0x138, 0xf, 0xf, false);
-        lead[q] = lane_id() == 0 || plo != (u32)kk[q] || phi != (u32)(kk[q] >> 32);
-        unpack_key(kf, kk[q], ss[q], ee[q]);
-        bw[q] = 0;
-        wr[q] = 0;
-        if (lead[q]) {
-            bw[q] = bitmap[(u32)ss[q] >> 6];
-            wr[q] = wrank[(u32)ss[q] >> 6];
-        }
-    }
-    u32 rs_[KDA_PER], fi[KDA_PER], eb[KDA_PER];
-#pragma unroll
-    for (int q = 0; q < KDA_PER; q++) {
-        rs_[q] = wr[q] + (u32)__popcll(bw[q] & ((1ull << (ss[q] & 63)) - 1ull));
-        fi[q] = eb[q] = 0;
-        if (lead[q]) {
-            fi[q] = first_id[rs_[q]];
-            eb[q] = ends_below(ends, rs_[q], (u32)ee[q]);
-        }
-    }
-#pragma unroll
-    for (int q = 0; q < KDA_PER; q++) {
-        const u64 lm = __ballot(lead[q]) & ((2ull << lane_id()) - 1ull); // (lane 0 always leads)
-        const u32 id = (u32)__shfl((int)(fi[q] + eb[q]), 63 - __clzll((long long)lm), 64);
-        fi[q] = id;
-        eb[q] = 0;
-        if (pp[q] < n) jid_bam[pp[q]] = id; // (the sort's first pass reads the ids from here; k4b_generic looks its pairs' junctions up)
-        if (nb) wave_hist_add(s_h, id & (nb - 1u), pp[q] < n);
-        if (ro.window) {
-            wave_hist_add(s_h, id & (RUN_W - 1u), pp[q] < n);
-            if (pp[q] < n) {
-                id_lo = id < id_lo ? id : id_lo;
-                id_hi = id > id_hi ? id : id_hi;
-            }
-        }
-    }
-#ifdef PJB_SELFCHECK
-    const u32 p = pp[0];
-    if (p < n) {
-    const int32_t s = ss[0], e = ee[0];
-    const u32 rs = rs_[0], id = fi[0] + eb[0]; // (debug builds: the junction table kd_table made must know this pair's junction -- its start bit, its end slot, its key,
-                     // anchors that enclose the intron; a failure stops the chain (P = 0) so that the report gets out)
-    {
-        int bad = 0;
-        const uint4 *q = reinterpret_cast<const uint4 *>(ends + (size_t)rs * DENSE_ENDS);
-        const uint4 a = q[0], b = q[1];
-        const u32 ue = (u32)e;
-        if (!((bitmap[(u32)s >> 6] >> (s & 63)) & 1ull)) bad = 6;
-        else if (!(a.x == ue || a.y == ue || a.z == ue || a.w == ue || b.x == ue || b.y == ue || b.z == ue || b.w == ue)) bad = 7;
-        else if (id >= junc_limit || id >= (u32)*total) bad = 1;
-        else if (jkey[id] != key[p]) bad = 2;
-        else if (anc_l[id] > s || anc_r[id] < e) bad = 3;
-        if (bad) {
-            set_error(err, 0xfffff000u + (u32)bad, PJB_ERR_HIP);
-            cs_chk->P = 0;
-        }
-    }
-    }
-#endif
-    } // chunks
-    if (nb) {
-        __syncthreads();
-        for (u32 d = threadIdx.x; d < nb; d += 256) hist[(size_t)blockIdx.x * nb + d] = s_h[d];
-    }
-    if (ro.window) {
-        // the tile's runs: the non-zero counters of [least id, largest id], in id order
-        id_lo = wave_total<DppMin>(id_lo);
-        id_hi = wave_total<DppMax>(id_hi);
-        if (lane_id() == 0) {
-            atomicMin(&s_run[0], id_lo);
-            atomicMax(&s_run[1], id_hi);
-        }
-        __syncthreads();
-        const u32 lo = s_run[0], hi = s_run[1];
-        if (lo > hi) { // (a tile past the pairs)
-            if (threadIdx.x == 0) ro.tile_n[blockIdx.x] = 0;
-            return;
-        }
-        if (hi - lo >= ro.window) {
-            if (threadIdx.x == 0) {
-                ro.tile_n[blockIdx.x] = 0;
-                runs_close_chain(cs_chk);
-            }
-            return;
-        }
-        const u32 span = hi - lo + 1u; // (<= RUN_W)
-        u32 c[8], nz = 0;
-#pragma unroll
-        for (int k = 0; k < 8; k++) {
-            const u32 o = threadIdx.x * 8u + (u32)k;
-            c[k] = o < span ? s_h[(lo + o) & (RUN_W - 1u)] : 0u;
-            nz += c[k] != 0u;
-        }
-        u32 tot;
-        u32 at = block_escan_256<u32>(nz, s_rscan, &tot);
-        if (threadIdx.x == 0) { // room in the chain's run list (a reservation that does not fit is taken back: the count never stays above the room)
-            u32 b = atomicAdd(ro.n_runs, tot);
-            if (b > ro.cap || tot > ro.cap - b) {
-                atomicSub(ro.n_runs, tot);
-                b = 0xffffffffu;
-                runs_close_chain(cs_chk);
-            }
-            s_run[2] = b;
-            ro.tile_first[blockIdx.x] = b == 0xffffffffu ? 0u : b;
-            ro.tile_n[blockIdx.x] = b == 0xffffffffu ? 0u : tot;
-        }
-        __syncthreads();
-        const u32 first = s_run[2];
-        if (first == 0xffffffffu) return;
-        at += first;
-#pragma unroll
-        for (int k = 0; k < 8; k++)
-            if (c[k]) {
-                ro.key[at] = ((u64)(lo + threadIdx.x * 8u + (u32)k) << ro.tile_bits) | (u64)blockIdx.x;
-                ro.cnt[at] = c[k];
-                at++;
-            }
-    }
-}
-
-// ---------------------------------------------------------------------------------------------
-// K2: stable LSD radix sort of (key, pair index).  Classic 3-step passes: per-tile digit
-// histogram -> exclusive scan of the bin-major count matrix -> ranked scatter.  Stability comes
-// from ranking in memory order: wave w of a tile owns a contiguous 1/4 of it, rounds are
-// contiguous 64-element slices, and equal digits inside a round are ranked by lane with a
-// ballot-based match-any.
-// ---------------------------------------------------------------------------------------------
-constexpr int RS_ITEMS = 16;
-constexpr int RS_TILE = 256 * RS_ITEMS; // 4096 keys per block
-constexpr int RS_MAX_BITS = 12;
-constexpr int RS_MAX_BINS = 1 << RS_MAX_BITS;
-static_assert(KDA_TILE == RS_TILE && RS_MAX_BINS <= 4096, "kd_assign counts the sort's first digit tile by tile");
-
-// Histogram add of one digit per lane.  Keys arrive nearly sorted and deep junctions repeat one key
-// thousands of times, so most lanes of a wave often hold the same digit: the two most common
-// leading digits are counted by one lane each (no 64-way same-address LDS conflict), the rest
-// with plain LDS atomics.
-__device__ __forceinline__ void wave_hist_add(u32 *h, u32 d, bool valid) {
-    u64 rem = __ballot(valid);
-    const int lane = lane_id();
-#pragma unroll
-    for (int it = 0; it < 2; it++) {
-        if (rem == 0) return;
-        const int first = __ffsll((long long)rem) - 1;
-        const u32 d0 = __shfl(d, first, 64);
-        const u64 m = __ballot(valid && d == d0) & rem;
-        if (lane == first) atomicAdd(&h[d0], (u32)__popcll(m));
-        rem &= ~m;
-    }
-    if ((rem >> lane) & 1ull) atomicAdd(&h[d], 1u);
-}
-
-template <typename K>
-__global__ __launch_bounds__(256) void rs_hist(const K *keys, const u32 *np, int shift, int bits, u32 *hist, u32 n_tiles) {
-    __shared__ u32 h[RS_MAX_BINS];
-    const u32 n = *np; // the grid covers the host's limit; tiles past the data count nothing
-    const u32 nb = 1u << bits;
-    for (u32 d = threadIdx.x; d < nb; d += 256) h[d] = 0;
-    __syncthreads();
-    const u32 base = blockIdx.x * RS_TILE;
-    const u32 mask = nb - 1;
-    K kk[RS_ITEMS];
-#pragma unroll
-    for (int k = 0; k < RS_ITEMS; k++) {
-        const u32 i = base + k * 256 + threadIdx.x;
-        kk[k] = i < n ? keys[i] : (K)0;
-    }
-#pragma unroll
-    for (int k = 0; k < RS_ITEMS; k++) {
-        const u32 i = base + k * 256 + threadIdx.x;
-        wave_hist_add(h, (u32)(kk[k] >> shift) & mask, i < n);
-    }
-    __syncthreads();
-    // tile-major: a tile's counts are one contiguous run (bin-major, every 4-byte store was a write granule of its own:
-    // twice the algorithmic traffic, PMC round 2), and rs_scatter reads its tile's scanned counts the same way
-    for (u32 d = threadIdx.x; d < nb; d += 256) hist[(size_t)blockIdx.x * nb + d] = h[d];
-}
-
-// Exclusive scan over the tiles of every digit's counts (tile order) and the digit totals, on the tile-major matrix, in two
-// small kernels over PANELS of RSP_TILES tiles x 64 digits (one wavefront each, lane = digit, so every load is 256
-// contiguous bytes of a tile's row): rs_panel_sums adds up each panel's columns; rs_panel_scan lets every panel add the
-// sums of the panels before it itself (a few hundred at most) and writes its tiles' exclusive counts; the last panel
-// also leaves the digit totals.  (One block per digit walking all tiles -- round 2 -- took 8 us for one chromosome's 650
-// tiles and 144 us for a 0.5 Gb chain's 4 400.)  The scatter adds the number of keys with a smaller digit itself (a
-// block scan of the 2^bits totals), so the pass needs neither a scan of the whole matrix nor global atomics.
-constexpr u32 RSP_TILES = 64;
-__global__ __launch_bounds__(256) void rs_panel_sums(const u32 *hist, u32 n_tiles, u32 nb, u32 *psum) {
-    const u32 d = blockIdx.y * 256 + threadIdx.x;
-    if (d >= nb) return;
-    const u32 t0 = blockIdx.x * RSP_TILES, t1 = t0 + RSP_TILES < n_tiles ? t0 + RSP_TILES : n_tiles;
-    u32 sum = 0;
-    for (u32 t = t0; t < t1; t += 8) { // eight loads in flight per lane
-        u32 v[8];
-#pragma unroll
-        for (int k = 0; k < 8; k++) v[k] = t + k < t1 ? hist[(size_t)(t + k) * nb + d] : 0u;
-#pragma unroll
-        for (int k = 0; k < 8; k++) sum += v[k];
-    }
-    psum[(size_t)blockIdx.x * nb + d] = sum;
-}
-__global__ __launch_bounds__(256) void rs_panel_scan(const u32 *hist, const u32 *psum, u32 n_tiles, u32 nb, u32 *hist_scan, u32 *row_total) {
-    const u32 d = blockIdx.y * 256 + threadIdx.x;
-    if (d >= nb) return;
-    const u32 panel = blockIdx.x;
-    u32 run = 0;
-    for (u32 q = 0; q < panel; q += 8) {
-        u32 v[8];
-#pragma unroll
-        for (int k = 0; k < 8; k++) v[k] = q + k < panel ? psum[(size_t)(q + k) * nb + d] : 0u;
-#pragma unroll
-        for (int k = 0; k < 8; k++) run += v[k];
-    }
-    const u32 t0 = panel * RSP_TILES, t1 = t0 + RSP_TILES < n_tiles ? t0 + RSP_TILES : n_tiles;
-    for (u32 t = t0; t < t1; t += 8) {
-        u32 v[8];
-#pragma unroll
-        for (int k = 0; k < 8; k++) v[k] = t + k < t1 ? hist[(size_t)(t + k) * nb + d] : 0u;
-#pragma unroll
-        for (int k = 0; k < 8; k++) {
-            if (t + k < t1) hist_scan[(size_t)(t + k) * nb + d] = run;
-            run += v[k];
-        }
-    }
-    if (t1 == n_tiles) row_total[d] = run; // (the last panel)
-}
-
-// LDS of one rs_scatter block: the tile's keys in digit order (reused for the pair indices), the offset
-// "global position - tile-local position" of every digit, and the digit counters of the 4 waves
-// (16 bit: a wave owns 1024 keys, a tile 4096).
-__host__ __device__ constexpr size_t rs_scatter_lds_bytes(int bits, size_t key_bytes = 8) {
-    return (size_t)RS_TILE * key_bytes + ((size_t)4 << bits) + ((size_t)8 << bits);
-}
-constexpr int RS_PF = 2; // digits per thread whose scan entries are prefetched (9-bit digits: all of them)
-
-// Lanes of the wave holding the same digit as this lane ("match any"), one ballot per digit bit:
-// peers &= bit set ? ballot : ~ballot, written as peers &= ~(ballot ^ m) with m = 0 / -1 from a signed
-// bit-field extract.  BITS > 0 unrolls the loop; BITS == 0 takes the width at run time.
-template <int BITS>
-__device__ __forceinline__ u64 wave_match_digit(u32 d, bool valid, int bits) {
-    u64 peers = __ballot(valid);
-    u32 lo = (u32)peers, hi = (u32)(peers >> 32);
-    auto step = [&](int bit) {
-        const int m = __builtin_amdgcn_sbfe((int)d, bit, 1); // -1 if the bit is set
-        const u64 bb = __ballot(m != 0);
-        lo &= ~((u32)bb ^ (u32)m);
-        hi &= ~((u32)(bb >> 32) ^ (u32)m);
-    };
-    if constexpr (BITS > 0) {
-#pragma unroll
-        for (int bit = 0; bit < BITS; bit++) step(bit);
-    } else {
-        for (int bit = 0; bit < bits; bit++) step(bit);
-    }
-    return ((u64)hi << 32) | lo;
-}
-
-// One radix pass over a 4096-key tile: rank (stable, in memory order), exchange through LDS so that
-// the tile leaves in digit order, write out with consecutive lanes on consecutive addresses inside a
-// digit run.  The first output slot of (digit, tile) = keys of the whole array with a smaller digit
-// (block scan over row_total) + keys with that digit in earlier tiles (hist_scan, bin-major).
-// A single-launch variant (digit totals up front, earlier tiles' counts by decoupled look-back over
-// 8-byte {epoch, count} granules) was measured at 0.064 ms per pass against 0.058 ms for
-// hist + rowscan + scatter: with every tile resident at once the look-back chain costs more than the
-// two small kernels, so it was dropped.
-// K: u64 (full intron keys) or u32 (dense junction ids: half the key traffic, half the key registers)
-template <int BITS, typename K>
-__global__ __launch_bounds__(256, 3) void rs_scatter(const K *kin, const u32 *vin, K *kout, u32 *vout, const u32 *np, int shift,
-                                                      int bits, const u32 *hist_scan, const u32 *row_total, u32 n_tiles) {
-    extern __shared__ __attribute__((aligned(16))) unsigned char rs_smem[];
-    __shared__ u64 s_scan[4];
-    const u32 n = *np;
-    if ((u64)blockIdx.x * RS_TILE >= n) return; // the grid covers the host's limit
-    if (BITS > 0) bits = BITS;
-    const u32 nb = 1u << bits;
-    const u32 mask = nb - 1;
-    K *kbuf = (K *)rs_smem;
-    u32 *ibuf = (u32 *)rs_smem;
-    u32 *delta = (u32 *)(rs_smem + (size_t)RS_TILE * sizeof(K));
-    unsigned short *wcnt = (unsigned short *)(delta + nb); // [4][nb]
-    for (u32 d = threadIdx.x; d < 2 * nb; d += 256) ((u32 *)wcnt)[d] = 0;
-    __syncthreads();
-    const u32 tile = blockIdx.x;
-    const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = lane_id(); // w in an SGPR: scalar base addresses
-    unsigned short *wc = wcnt + (size_t)w * nb;
-    const u32 base = tile * RS_TILE + w * (RS_TILE / 4);
-    const u64 lt = (1ull << lane) - 1;
-    K key[RS_ITEMS];
-    u32 val[RS_ITEMS];
-    u32 rkp[RS_ITEMS / 2]; // tile-local ranks (< 4096), two per register: the kernel must stay under 128 VGPRs
-    // the key / index buffers are allocated with one tile of slack, so the last tile loads unguarded too
-    // (lanes past n are masked below): 16 independent loads from one scalar base
-    const K *kp = kin + base;
-#pragma unroll
-    for (int r = 0; r < RS_ITEMS; r++) key[r] = kp[r * 64 + lane];
-    // digits [d0, d0 + per) belong to this thread in the digit phase (consecutive, so that one block
-    // scan orders them); their row totals / scanned counts are fetched now, behind the ranking
-    const u32 per = (nb + 255) / 256;
-    const u32 d0 = threadIdx.x * per;
-    u32 pf_rt[RS_PF], pf_hs[RS_PF];
-#pragma unroll
-    for (int k = 0; k < RS_PF; k++) {
-        const u32 d = d0 + k;
-        const bool on = (u32)k < per && d < nb;
-        pf_rt[k] = on ? row_total[d] : 0u;
-        pf_hs[k] = on ? hist_scan[(size_t)tile * nb + d] : 0u;
-    }
-#pragma unroll
-    for (int r = 0; r < RS_ITEMS; r++) {
-        const u32 i = base + r * 64 + lane;
-        const bool valid = i < n;
-        const u32 d = (u32)(key[r] >> shift) & mask;
-        const u64 peers = wave_match_digit<BITS>(d, valid, bits);
-        // only scalars of the peer mask stay live across the LDS round trip
-        const u32 lower = (u32)__popcll(peers & lt), group = (u32)__popcll(peers);
-        const int leader = valid ? __ffsll((long long)peers) - 1 : lane;
-        u32 before = 0;
-        if (valid && lane == leader) {
-            before = wc[d];
-            wc[d] = (unsigned short)(before + group);
-        }
-        const u32 rank = __shfl(before, leader, 64) + lower;
-        rkp[r >> 1] = (r & 1) ? (rkp[r >> 1] | (rank << 16)) : rank;
-    }
-    // the pair indices are not needed before the second exchange: their latency hides behind the digit phase
-    if (vin) {
-        const u32 *vp = vin + base;
-#pragma unroll
-        for (int r = 0; r < RS_ITEMS; r++) val[r] = vp[r * 64 + lane];
-    } else {
-#pragma unroll
-        for (int r = 0; r < RS_ITEMS; r++) val[r] = base + r * 64 + lane;
-    }
-    __syncthreads();
-    u32 mine = 0, below = 0;
-    for (u32 k = 0; k < per; k++) {
-        const u32 d = d0 + k;
-        if (d < nb) {
-            mine += (u32)wcnt[d] + wcnt[nb + d] + wcnt[2 * nb + d] + wcnt[3 * nb + d];
-            below += k < RS_PF ? pf_rt[k < RS_PF ? k : 0] : row_total[d];
-        }
-    }
-    u64 tot; // one scan carries both: tile-local start of the digit | keys of the whole array with a smaller digit
-    const u64 both = block_escan_256<u64>((u64)mine | ((u64)below << 32), s_scan, &tot);
-    u32 tstart = (u32)both, dbase = (u32)(both >> 32);
-    for (u32 k = 0; k < per; k++) {
-        const u32 d = d0 + k;
-        if (d >= nb) break;
-        const u32 c0 = wcnt[d], c1 = wcnt[nb + d], c2 = wcnt[2 * nb + d], c3 = wcnt[3 * nb + d];
-        // first output slot of this tile's keys with digit d
-        const u32 gfirst = dbase + (k < RS_PF ? pf_hs[k < RS_PF ? k : 0] : hist_scan[(size_t)tile * nb + d]);
-        dbase += k < RS_PF ? pf_rt[k < RS_PF ? k : 0] : row_total[d];
-        delta[d] = gfirst - tstart;
-        wcnt[d] = (unsigned short)tstart;
-        wcnt[nb + d] = (unsigned short)(tstart + c0);
-        wcnt[2 * nb + d] = (unsigned short)(tstart + c0 + c1);
-        wcnt[3 * nb + d] = (unsigned short)(tstart + c0 + c1 + c2);
-        tstart += c0 + c1 + c2 + c3;
-    }
-    __syncthreads();
-    // exchange: keys to their tile-local sorted position
-#pragma unroll
-    for (int r = 0; r < RS_ITEMS; r++) {
-        const u32 i = base + r * 64 + lane;
-        const u32 lp = ((rkp[r >> 1] >> ((r & 1) * 16)) & 0xffffu) + wc[(u32)(key[r] >> shift) & mask];
-        rkp[r >> 1] = (r & 1) ? ((rkp[r >> 1] & 0xffffu) | (lp << 16)) : ((rkp[r >> 1] & 0xffff0000u) | lp);
-        if (i < n) kbuf[lp] = key[r];
-    }
-    __syncthreads();
-    const u32 cnt = min((u32)RS_TILE, n - tile * RS_TILE);
-    u32 digp[RS_ITEMS / 2]; // digit of the key in slot j, two per register (for the second write-out)
-#pragma unroll
-    for (int r = 0; r < RS_ITEMS; r++) {
-        const u32 j = r * 256 + threadIdx.x;
-        const K kk = j < cnt ? kbuf[j] : (K)0;
-        const u32 d = (u32)(kk >> shift) & mask;
-        digp[r >> 1] = (r & 1) ? (digp[r >> 1] | (d << 16)) : d;
-        if (j < cnt) kout[delta[d] + j] = kk;
-    }
-    __syncthreads();
-#pragma unroll
-    for (int r = 0; r < RS_ITEMS; r++) {
-        const u32 i = base + r * 64 + lane;
-        if (i < n) ibuf[(rkp[r >> 1] >> ((r & 1) * 16)) & 0xffffu] = val[r];
-    }
-    __syncthreads();
-#pragma unroll
-    for (int r = 0; r < RS_ITEMS; r++) {
-        const u32 j = r * 256 + threadIdx.x;
-        if (j < cnt) vout[delta[(digp[r >> 1] >> ((r & 1) * 16)) & 0xffffu] + j] = ibuf[j];
-    }
-}
-
-// ---------------------------------------------------------------------------------------------
-// The run route of the dense-id sort: a stable counting sort in ONE pass over the pairs.  kd_assign left one entry per
-// (tile, id) run; the run list -- about as many entries as the chain has junctions -- is sorted by id << tile_bits | tile with
-// the radix kernels above, and a scan of the counts in that order gives every run the place of its first pair (RunDestSink
-// writes it back at the run's own index).  rs_place then ranks the pairs of a tile within their runs -- wave w owns the w-th
-// quarter of the tile, rounds are contiguous 64-pair slices, equal ids inside a round are ranked by lane: memory order, as in
-// rs_scatter, so the result is the stable sort's, bit for bit -- and writes id and pair index straight to their places.  A
-// slice holds one or two distinct ids: the lanes of an id write consecutive addresses without an exchange through LDS, and
-// instead of one ballot per digit bit the wavefront takes its distinct ids one after the other.
-// ---------------------------------------------------------------------------------------------
-struct RunCountFn { // counts in sorted order
-    const u32 *cnt, *order;
-    __device__ u64 operator()(u64 i) const { return cnt[order[i]]; }
-};
-struct RunDestSink {
-    u32 *dest;
-    const u32 *order;
-    __device__ void operator()(u64 i, u64, u64 ex) const { dest[order[i]] = (u32)ex; }
-};
-__global__ __launch_bounds__(256) void rs_place(const u32 *jid_bam, const u32 *np, const u64 *run_key, const u32 *run_dest, const u32 *tile_first,
-                                                const u32 *tile_n, u32 run_cap, int tile_bits, u32 *kout, u32 *vout) {
-    __shared__ u32 s_dest[RUN_W];               // first place of the tile's pairs of id d, at d & (RUN_W - 1)
-    __shared__ unsigned short s_wcnt[4][RUN_W]; // pairs of that id per wave (16 bit: a wave owns 1 024 pairs)
-    const u32 n = *np;
-    const u32 tile = blockIdx.x;
-    if ((u64)tile * RS_TILE >= n) return; // the grid covers the host's limit (and a closed chain has no pairs)
-    for (u32 d = threadIdx.x; d < 2 * RUN_W; d += 256) ((u32 *)&s_wcnt[0][0])[d] = 0;
-    const u32 tf = tile_first[tile], tn = tf < run_cap ? min(tile_n[tile], min(RUN_W, run_cap - tf)) : 0u;
-    for (u32 e = threadIdx.x; e < tn; e += 256) s_dest[(u32)(run_key[tf + e] >> tile_bits) & (RUN_W - 1u)] = run_dest[tf + e];
-    const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = lane_id();
-    unsigned short *wc = s_wcnt[w];
-    const u32 base = tile * RS_TILE + w * (RS_TILE / 4);
-    const u64 lt = (1ull << lane) - 1;
-    u32 id[RS_ITEMS];
-    u32 rkp[RS_ITEMS / 2]; // ranks within the wave's quarter (< 1 024), two per register
-    // (the id buffer has one tile of slack: the last tile loads unguarded, lanes past n are masked below)
-    const u32 *kp = jid_bam + base;
-#pragma unroll
-    for (int r = 0; r < RS_ITEMS; r++) id[r] = kp[r * 64 + lane];
-    __syncthreads();
-#pragma unroll
-    for (int r = 0; r < RS_ITEMS; r++) {
-        const bool valid = base + r * 64 + lane < n;
-        const u32 d = id[r] & (RUN_W - 1u);
-        u32 rank = 0;
-        u64 todo = __ballot(valid);
-        while (todo) {
-            const int first = __ffsll((long long)todo) - 1;
-            const u32 idc = (u32)__builtin_amdgcn_readlane((int)id[r], first);
-            const bool mine = valid && id[r] == idc;
-            const u64 m = __ballot(mine);
-            u32 before = 0;
-            if (lane == first) {
-                before = wc[d];
-                wc[d] = (unsigned short)(before + (u32)__popcll(m));
-            }
-            before = (u32)__builtin_amdgcn_readlane((int)before, first);
-            if (mine) rank = before + (u32)__popcll(m & lt);
-            todo &= ~m;
-        }
-        rkp[r >> 1] = (r & 1) ? (rkp[r >> 1] | (rank << 16)) : rank;
-    }
-    __syncthreads();
-#pragma unroll
-    for (int r = 0; r < RS_ITEMS; r++) {
-        const u32 i = base + r * 64 + lane;
-        const u32 d = id[r] & (RUN_W - 1u);
-        u32 dst = s_dest[d] + ((rkp[r >> 1] >> ((r & 1) * 16)) & 0xffffu);
-        for (int q = 0; q < w; q++) dst += s_wcnt[q][d]; // the id's pairs in the waves before this one
-        if (i < n && dst < n) { // (dst < n always: every id of the tile has its entry)
-            kout[dst] = id[r];
-            vout[dst] = i;
-        }
-    }
-}
-
-// ---------------------------------------------------------------------------------------------
-// K2s: segment heads.  For sorted position i:  head_j = new intron key; head_r = head_j or read
-// position differs from the previous pair of the junction (entropy runs, junction.cc:730-749).
-// One u64 scan carries both counters (junction count << 32 | run count).
-// ---------------------------------------------------------------------------------------------
-struct HeadFn {
-    const u64 *skey;
-    const u32 *sidx;
-    const PairRec *rec;
-    __device__ u64 operator()(u64 i) const {
-        const u64 im = i ? i - 1 : 0; // (every load unconditional)
-        const u64 ka = skey[i], kb = skey[im];
-        const u32 sa = sidx[i], sb = sidx[im];
-        const int32_t pa = rec[sa].pos, pb = rec[sb].pos;
-        const bool hj = i == 0 || ka != kb;
-        const bool hr = hj || pa != pb;
-        return ((u64)hj << 32) | (u64)hr;
-    }
-};
-struct HeadSink {
-    u32 *jid_of;    // [P]   junction id per sorted pair
-    u32 *seg_off;   // [J+1] first sorted pair of junction
-    u32 *run_first; // [J+1] first run of junction
-    u32 *run_start; // [R+1] first sorted pair of run
-    const u64 *skey;
-    u64 *jkey;      // [J]   intron key of the junction -- when the sort ran on the full keys (nullptr: K2d left the table)
-    u32 junc_limit; //       entries jkey has (the other arrays are pair-sized; k2_close stops the chain when there are more heads)
-    __device__ void operator()(u64 i, u64 v, u64 ex) const {
-        const u32 j = (u32)(ex >> 32) + (u32)(v >> 32) - 1; // inclusive count - 1
-        const u32 r = (u32)ex + (u32)v - 1;
-        jid_of[i] = j;
-        if (v >> 32) {
-            seg_off[j] = (u32)i;
-            run_first[j] = r;
-            if (jkey && j < junc_limit) jkey[j] = skey[i];
-        }
-        if ((u32)v) run_start[r] = (u32)i;
-    }
-};
-__global__ void k2_close(u64 *total, u32 *seg_off, u32 *run_first, u32 *run_start, ContigStats *cs, u32 junc_limit, const u32 *gen_cnt, u32 gen_cap,
-                         int range_shift) {
-    const u32 n_pairs = cs->P;
-    if (n_pairs == 0) return;
-    {
-        u32 need = 0;
-        for (u32 sh = 0; sh < GEN_SHARDS; sh++) need = max(need, lists_over(gen_cnt, sh, gen_cap));
-        if (need) { // a read list overflowed: the chain is repeated with more room
-            cs->list_need = need;
-            cs->overflow |= OVF_LISTS;
-            cs->P = 0;
-            return;
-        }
-    }
-    const u32 J = (u32)(*total >> 32), R = (u32)*total;
-    cs->n_junc = J;
-    cs->n_runs = R;
-    if (J > junc_limit) { // the junction-sized buffers are too small: everything downstream stands still
-        cs->overflow |= OVF_JUNC;
-        cs->P = 0;
-        return;
-    }
-    seg_off[J] = n_pairs;
-    run_first[J] = R;
-    run_start[R] = n_pairs;
-    cs->J = J;
-    cs->R = R;
-    cs->n_slots = frag_slots(J, n_pairs, range_shift);
-}
-
-// K2s for the chain on dense ids: k4_pairs left two bits per sorted pair (junction starts / position run starts), a scan over the
-// slices' popcounts numbers the runs, and this kernel writes what HeadSink writes -- from the masks and the sorted ids alone.
-struct Popc64Fn {
-    const u64 *words;
-    __device__ u64 operator()(u64 i) const { return (u64)__popcll(words[i]); }
-};
-constexpr int K2E_PER = 4;
-__global__ __launch_bounds__(256) void k2_expand(const u32 *sid, const u64 *head_mask, const u64 *run_mask, const u32 *run_base, const u64 *total,
-                                                 u32 *seg_off, u32 *run_first, u32 *run_start, ContigStats *cs) {
-    const u32 n = cs->P;
-#pragma unroll
-    for (int q = 0; q < K2E_PER; q++) { // (a wavefront takes K2E_PER slices: their mask words' loads travel together)
-        const u32 i = (blockIdx.x * K2E_PER + q) * 256 + threadIdx.x;
-        if (i >= n) continue;
-        const u32 sl = i >> 6, bit = i & 63u;
-        const u64 mr = run_mask[sl], mj = head_mask[sl];
-        if ((mr >> bit) & 1ull) {
-            const u32 r = run_base[sl] + (u32)__popcll(mr & ((1ull << bit) - 1ull));
-            run_start[r] = i;
-            if ((mj >> bit) & 1ull) {
-                const u32 j = sid[i];
-                seg_off[j] = i;
-                run_first[j] = r;
-            }
-        }
-    }
-    if (n > 0 && (n - 1) / (256u * K2E_PER) == blockIdx.x && threadIdx.x == 0) { // (k2_close's part: once, by the block that holds the last pair)
-        const u32 R = (u32)*total, J = cs->J;
-        seg_off[J] = n;
-        run_first[J] = R;
-        run_start[R] = n;
-        cs->n_runs = cs->R = R;
-    }
-}
-
-// ---------------------------------------------------------------------------------------------
-// The chain that sorted the FULL keys (PJB_DENSE_IDS off, raw keys, or a donor with more acceptors than K2d keeps) has its
-// junction ids only now: two small kernels give it what kd_assign gives the usual chain -- the rest state of anchors and
-// accumulators, the junction id of every pair in BAM order (k4b_generic works in BAM order) and the anchors.
-// ---------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void kf_init(u32 *acc, const u32 *n_junc_p, int32_t *anc_l, int32_t *anc_r) {
-    const u32 n_junc = *n_junc_p;
-    acc_rest_state(acc, n_junc);
-    for (u64 t = (u64)blockIdx.x * 256 + threadIdx.x; t < n_junc; t += (u64)gridDim.x * 256) {
-        anc_l[t] = INT32_MAX;
-        anc_r[t] = INT32_MIN;
-    }
-}
-__global__ __launch_bounds__(256) void kf_anchors(const u32 *sidx, const u32 *jid_of, const PairRec *rec, const u32 *np, u32 *jid_bam, int32_t *anc_l,
-                                                   int32_t *anc_r) {
-    const u32 n = *np;
-    if (blockIdx.x * 256u >= n) return;
-    const u32 i = blockIdx.x * 256 + threadIdx.x;
-    const bool valid = i < n;
-    const u32 ic = valid ? i : n - 1;
-    const u32 p = sidx[ic], j = jid_of[ic];
-    const uint4 ra = *reinterpret_cast<const uint4 *>(rec + p);
-    if (valid) jid_bam[p] = j;
-    anchors_fold(valid, j, (int32_t)ra.z, (int32_t)ra.w, anc_l, anc_r);
-}
-
-// ---------------------------------------------------------------------------------------------
-// K4: per-pair match statistics (AlignmentInfo::calcMatchStats junction.cc:147-240 on top of
-// BamAlignment::getPaddedQuerySeq / getPaddedGenomeSeq bam_alignment.cc:341-462), computed by
-// counting instead of building strings: the query walk and the genome walk are advanced in
-// lock-step over the CIGAR and their emissions compared op by op.
-// ---------------------------------------------------------------------------------------------
-constexpr int GENERIC_NW = 8; // (as the closed form: two 16-byte loads per stream and round, loads may run to the buffers' ends)
-struct Side {
-    int32_t len, mism, first_mis, last_mis;
-    int err;
-};
-
-// (k0, r0, q0): the operation the walks start at and the reference / query position there -- (0, position, 0), or, from the
-// pair's hint, the first operation that starts inside the window: everything before it the walks only step over
-__device__ Side anchor_side(const OpsView cig, u32 n, int32_t position, int32_t aligned, const uint8_t *seq, int32_t lq,
-                            const uint8_t *genome, int32_t glen, bool genome_has_x, const u32 *gcodes, int32_t start,
-                            int32_t end, u32 k0, int32_t r0, int32_t q0, int32_t q_limit /* last word behind seq that may be read */) {
-    Side S;
-    S.len = 0;
-    S.mism = 0;
-    S.first_mis = -1;
-    S.last_mis = -1;
-    S.err = 0;
-    const int32_t get_end = position + aligned - 1;
-    if (start > get_end || end < position) { // bam_alignment.cc:342
-        S.err = PJB_ERR_NO_PRESENCE;
-        return S;
-    }
-    // getQuerySeqAfterClipping, bam_alignment.cc:256-264 (size_t arithmetic incl. the "+1")
-    int32_t dS = 0, dE = 0;
-    if ((cig[0] & 15u) == OP_S) dS = (int32_t)(cig[0] >> 4);
-    if ((cig[n - 1] & 15u) == OP_S) dE = (int32_t)(cig[n - 1] >> 4);
-    if (dS > lq) {
-        S.err = PJB_ERR_CLIP_RANGE;
-        return S;
-    }
-    const u64 cnt = (u64)(int64_t)lq - (u64)(int64_t)dS - (u64)(int64_t)dE + 1ull;
-    const u64 avail = (u64)(lq - dS);
-    const int32_t clen = (int32_t)(cnt < avail ? cnt : avail);
-    // ---- pass A: query walk over ops only -> where it stops (actual_start / actual_end)
-    int32_t rPos = r0, qPos = q0;
-    for (u32 k = k0; k < n; k++) {
-        const u32 op = cig[k], ty = op & 15u;
-        const int32_t ln = (int32_t)(op >> 4);
-        const bool cRef = op_consumes_ref(ty);
-        const bool cQry = op_consumes_query(ty) && ty != OP_S;
-        if (rPos < start) {
-            if (cRef) rPos += ln;
-            if (cQry) qPos += ln;
-            continue;
-        }
-        if ((rPos > end && ty != OP_I) || (ty == OP_N && rPos + ln > end)) break; // :359
-        if (cQry) {
-            const int32_t l = (rPos + ln > end && ty != OP_I) ? end - rPos + 1 : ln;
-            if (l == 0) {
-                S.err = PJB_ERR_ZERO_LEN_OP;
-                return S;
-            }
-            if (qPos < 0 || qPos + l > clen) {
-                S.err = PJB_ERR_QUERY_RANGE;
-                return S;
-            }
-        }
-        if (cRef) rPos += ln;
-        if (cQry) qPos += ln;
-    }
-    const int32_t q_start = position > start ? position : start; // :400
-    const int32_t q_end = rPos <= end ? rPos - 1 : end;          // :401
-    if (q_start - start < 0 || end - q_end < 0) {                // :414-421 (unreachable, kept for parity)
-        S.err = PJB_ERR_QREGION;
-        return S;
-    }
-    const int32_t gsize = end - start + 1; // length of the fetched anchor string
-    // ---- pass B: both walks in lock-step, comparing emissions
-    rPos = r0;
-    qPos = q0;
-    bool qDone = false, gDone = false, diverged = false;
-    int32_t qTot = 0, gTot = 0, mism = 0, first_mis = -1, last_mis = -1;
-    for (u32 k = k0; k < n; k++) {
-        const u32 op = cig[k], ty = op & 15u;
-        const int32_t ln = (int32_t)(op >> 4);
-        const bool cRef = op_consumes_ref(ty);
-        const bool cQry = op_consumes_query(ty) && ty != OP_S;
-        int32_t qEmit = 0, gEmit = 0;
-        int qKind = 0, gKind = 0; // 1 = bases, 2 = 'X' padding
-        if (!qDone && rPos >= start) {
-            if ((rPos > end && ty != OP_I) || (ty == OP_N && rPos + ln > end)) qDone = true;
-            else if (cQry) {
-                qEmit = (rPos + ln > end && ty != OP_I) ? end - rPos + 1 : ln;
-                qKind = 1;
-            } else if (cRef) {
-                qEmit = rPos + ln > end ? end - rPos + 1 : ln;
-                qKind = 2;
-            }
-        }
-        if (!gDone && rPos >= q_start) {
-            if (rPos > q_end && ty != OP_I) gDone = true;
-            else if (cRef) {
-                const int32_t so = rPos - start;
-                gEmit = rPos + ln > q_end ? q_end - rPos + 1 : ln;
-                if (so < 0 || so + gEmit > gsize) { // :437
-                    S.err = PJB_ERR_GENOME_RANGE;
-                    return S;
-                }
-                gKind = 1;
-            } else if (cQry) {
-                gEmit = ln;
-                gKind = 2;
-            }
-        }
-        if (qEmit != gEmit) diverged = true;
-        if (!diverged && qEmit > 0) {
-            if (qKind == 1 && gKind == 1 && gcodes != nullptr && rPos >= 0 && rPos + qEmit <= glen) {
-                cmp_words<GENERIC_NW, true>(reinterpret_cast<const u32 *>(seq), dS + qPos, q_limit, gcodes, rPos, (glen + 7) / 8 + 1, qEmit, qTot,
-                                      mism, first_mis, last_mis);
-            } else if (qKind == 1 && gKind == 1) {
-                const int32_t qb = dS + qPos;
-                for (int32_t t = 0; t < qEmit; t++) {
-                    const int32_t qi = qb + t;
-                    const u32 byte = gload(seq + (qi >> 1));
-                    const u32 code = (qi & 1) ? (byte & 15u) : (byte >> 4);
-                    const int32_t gi = rPos + t;
-                    const u32 gc = (gi >= 0 && gi < glen) ? (u32)gload(genome + gi) : 0u;
-                    if (nt16_ascii(code) != gc) {
-                        mism++;
-                        if (first_mis < 0) first_mis = qTot + t;
-                        last_mis = qTot + t;
-                    }
-                }
-            } else if (qKind == 1) { // read letters vs 'X' (insertion): never equal
-                mism += qEmit;
-                if (first_mis < 0) first_mis = qTot;
-                last_mis = qTot + qEmit - 1;
-            } else if (!genome_has_x) { // 'X' padding (deletion / enclosed intron) vs genome bases without any 'X'
-                mism += qEmit;
-                if (first_mis < 0) first_mis = qTot;
-                last_mis = qTot + qEmit - 1;
-            } else { // contig really contains 'X' characters: compare byte by byte
-                for (int32_t t = 0; t < qEmit; t++) {
-                    const int32_t gi = rPos + t;
-                    const u32 gc = (gi >= 0 && gi < glen) ? (u32)gload(genome + gi) : 0u;
-                    if (gc != (u32)'X') {
-                        mism++;
-                        if (first_mis < 0) first_mis = qTot + t;
-                        last_mis = qTot + t;
-                    }
-                }
-            }
-        }
-        qTot += qEmit;
-        gTot += gEmit;
-        if (cRef) rPos += ln;
-        if (cQry) qPos += ln;
-        if (qDone && gDone) break;
-    }
-    if (qTot != gTot || qTot == 0) { // junction.cc:192,208
-        S.err = PJB_ERR_ANCHOR_MISMATCH;
-        return S;
-    }
-    if (diverged) {
-        S.err = PJB_ERR_DIVERGENT;
-        return S;
-    }
-    S.len = qTot;
-    S.mism = mism;
-    S.first_mis = first_mis;
-    S.last_mis = last_mis;
-    return S;
-}
-
-// per-pair match statistics through the generic lock-step walks (any CIGAR)
-__device__ __forceinline__ u64 pair_stats_generic(const OpsView cig, u32 nc, int32_t pos, int32_t aligned, const uint8_t *seq,
-                                                  int32_t lq, const uint8_t *genome, int32_t glen, bool has_x, const u32 *gcodes,
-                                                  int32_t left, int32_t istart, int32_t iend, int32_t right, u32 g, u64 *err, u32 opi,
-                                                  int32_t qN, int32_t q_limit) {
-    if (lq <= 1) { // junction.cc:168-185
-        const u32 totUp = (u32)((istart - 1) - left + 1);
-        const u32 totDown = (u32)(right - (iend + 1) + 1);
-        return pack_res(0, totUp < totDown ? totUp : totDown, 0);
-    }
-    // Where the walks start.  The pair's N operation is operation `opi`; it starts at istart, qN query bases into the read.  The
-    // left side walks BACK from it to the first operation that starts inside the window -- an operation that starts before the
-    // window is stepped over whole by the walks, and so is everything before it --, the right side starts at the operation
-    // behind the N.  (A read of 95 operations and 15 introns walked all 95 four times per pair.)
-    u32 kL = opi, kR = 0;
-    int32_t rL = istart, qL = qN, rR = pos, qR = 0;
-    while (kL > 0) {
-        const u32 op = cig[kL - 1], ty = op & 15u;
-        const int32_t ln = (int32_t)(op >> 4);
-        const int32_t rp = rL - (op_consumes_ref(ty) ? ln : 0);
-        if (rp < left) break; // (it starts before the window: stepped over, like all before it)
-        kL--;
-        rL = rp;
-        if (op_consumes_query(ty) && ty != OP_S) qL -= ln;
-    }
-    const int32_t after = istart + (int32_t)(cig[opi] >> 4); // the walks' position behind the N (iend + 1 unless it was clamped)
-    if (after == iend + 1) {
-        kR = opi + 1;
-        rR = after;
-        qR = qN;
-    }
-    const Side L = anchor_side(cig, nc, pos, aligned, seq, lq, genome, glen, has_x, gcodes, left, istart - 1, kL, rL, qL, q_limit);
-    if (L.err) {
-        set_error(err, g, L.err);
-        return 0;
-    }
-    const Side R = anchor_side(cig, nc, pos, aligned, seq, lq, genome, glen, has_x, gcodes, iend + 1, right, kR, rR, qR, q_limit);
-    if (R.err) {
-        set_error(err, g, R.err);
-        return 0;
-    }
-    const u32 upM = L.last_mis < 0 ? (u32)L.len : (u32)(L.len - 1 - L.last_mis);  // getNbMatchesFromEnd :272
-    const u32 downM = R.first_mis < 0 ? (u32)R.len : (u32)R.first_mis;            // getNbMatchesFromStart :263
-    const u32 tu = (u32)(L.len - L.mism), td = (u32)(R.len - R.mism);
-    return pack_res(upM < downM ? upM : downM, tu < td ? tu : td, (u32)(L.mism + R.mism));
-}
-
-// K4b: every pair that is not of the simple shape (multi-junction reads, indels, = X P H ops, exotic contigs, SEQ '*'), one
-// thread per READ of the lists k1_emit and k1_generic compacted -- the second list holds only the closed reads whose window check
-// the chain's bound B could not rule out (ContigStats::max_span) --: the read's fields come from the record k1_count kept of it
-// (spl_rec), its batch from the block's table, its operations are fetched once (two 16-byte loads into an LDS column) and
-// walked once; at every N operation the pair's junction-level anchors (kd_assign) are looked up and the two lock-step
-// walks start right there (op index and query offset are at hand: no hint has to travel with the pair).  The result
-// goes into the pair's record.  Runs on the side stream, beside the sort.
-__global__ __launch_bounds__(256) void k4b_generic(const u64 *list, const u32 *gen_cnt, u32 cap, const u64 *key, PairRec *rec, const u32 *jid_bam,
-                                                    KeyFmt kf, const DevBatch *batches, int n_batches, const int32_t *anc_l, const int32_t *anc_r,
-                                                    GroupTab G, int genome_has_x, int use_codes, u64 *err, const ContigStats *cs, u32 pack_nn,
-                                                    const u32 *spl_idx, const uint4 *spl_rec) {
-    __shared__ u32 s_ops[OPS_LDS][256];
-    __shared__ u32 s_first[2 * GEN_SHARDS + 1]; // item index of every sub-list's first entry (both lists, one index space)
-    __shared__ u32 s_wsum[4];
-    __shared__ BatchTab s_bt;
-    if (cs->P == 0) return; // (a limit was exceeded while the junction ids were built: there are no ids, the chain is repeated)
-    // The sub-lists are filled to different heights (sub-list `shard` of list `l` occupies [(l GEN_SHARDS + shard) cap, ... + its
-    // count)): every block numbers their entries -- an exclusive scan over the 512 counts -- and the grid strides over the items.
-    {
-        const u32 i0 = threadIdx.x * 2;
-        const u32 c0 = gen_cnt[(i0 % GEN_SHARDS) * GEN_CNT_STRIDE + (i0 / GEN_SHARDS) * 2];
-        const u32 c1 = gen_cnt[((i0 + 1) % GEN_SHARDS) * GEN_CNT_STRIDE + ((i0 + 1) / GEN_SHARDS) * 2];
-        const u32 n0 = c0 < cap ? c0 : cap, n1 = c1 < cap ? c1 : cap;
-        s_bt.fill(batches, n_batches);
-        u32 total;
-        const u32 ex = block_escan<4>(n0 + n1, s_wsum, &total);
-        s_first[i0] = ex;
-        s_first[i0 + 1] = ex + n0;
-        if (threadIdx.x == 255) s_first[2 * GEN_SHARDS] = total;
-        __syncthreads();
-    }
-    static_assert(GEN_SHARDS == 256, "two sub-lists per thread of the block");
-    const u32 n_items = s_first[2 * GEN_SHARDS];
-    for (u32 item0 = blockIdx.x * 256; item0 < n_items; item0 += gridDim.x * 256) {
-    const u32 item = item0 + threadIdx.x;
-    if (item >= n_items) continue; // (no barrier below)
-    u32 sub = 0; // the last sub-list with s_first[sub] <= item
-#pragma unroll
-    for (u32 step = GEN_SHARDS; step > 0; step >>= 1)
-        if (sub + step < 2 * GEN_SHARDS && s_first[sub + step] <= item) sub += step;
-    const bool check_only = sub >= GEN_SHARDS;
-    const u64 entry = list[(size_t)sub * cap + (item - s_first[sub])];
-    const u32 p0 = (u32)(entry >> 32);
-    const u32 slot = check_only && pack_nn ? (u32)entry & 0x0fffffffu : (u32)entry; // the read's place in the tiles' spliced lists
-    if (check_only) {
-        // A read [S] M (N M)+ [S] whose pairs k1_emit finished with the M blocks as anchors.  That is what the walks produce
-        // unless the junction's window reaches over a neighbouring intron of the read: on the left the walk starts at the
-        // first operation that begins inside the window (the previous N begins at its istart), on the right it stops at an N
-        // that ends outside it (bam_alignment.cc:359).  A read that fails the test takes the walks below -- all its pairs.
-        // N operations of the read: in the entry, or from its first pair's record (no junction of the read ends before that pair, one is its own)
-        const u32 code = pack_nn ? (u32)entry >> 28 : 15u;
-        const u32 nN = code < 15u ? code : (reinterpret_cast<const uint4 *>(rec + p0)[1].w >> 16) + 1u;
-        bool ok = true;
-        int32_t prev_istart = 0, is, ie;
-        unpack_key(kf, key[p0], is, ie);
-        for (u32 k = 0; k < nN; k++) {
-            const u32 j = jid_bam[p0 + k];
-            int32_t nis = 0, nie = 0;
-            if (k + 1 < nN) unpack_key(kf, key[p0 + k + 1], nis, nie);
-            if (k > 0 && prev_istart >= anc_l[j]) ok = false;
-            if (k + 1 < nN && nie + 1 <= anc_r[j]) ok = false;
-            prev_istart = is;
-            is = nis;
-            ie = nie;
-        }
-        if (ok) continue;
-    }
-    // what k1_count kept of the read (spl_rec: first operation, position, first word of the bases, operations | bases present | l_qseq --
-    // no gathers of cig_off, l_qseq, seq_off) and its batch, from the slot's tile
-    const int bi = s_bt.find(batches, n_batches, slot / (u32)K1_TILE);
-    const DevBatch &b = batches[bi];
-    const u32 r = spl_idx[slot];
-    const uint4 sr = spl_rec[slot];
-    const u32 g = gload(&b.base) + r;
-    const u32 c0 = sr.x;
-    u32 nc = sr.w & 0x7fffu;
-    if (nc == 0x7fffu) nc = gload(b.cig_off + r + 1) - c0; // (a count that did not fit the record)
-    OpsView cig;
-    cig.g = b.cigar + c0;
-    cig.lds = &s_ops[0][threadIdx.x];
-    {
-        u32 w[OPS_LDS];
-        fetch_ops8(as_global(b.cigar), c0, s_bt.cig_words(b, bi), w);
-#pragma unroll
-        for (int k = 0; k < OPS_LDS; k++) s_ops[k][threadIdx.x] = (u32)k < nc ? w[k] : 0u;
-    }
-    const uint4 rb = reinterpret_cast<const uint4 *>(rec + p0)[1]; // pos | aend | meta | updown of the read's first pair
-    const int32_t vpos = (int32_t)rb.x, aend = (int32_t)rb.y;
-    const Member M = member_of(G, vpos); // the read's target: everything below is in the target's own coordinates
-    const int32_t pos = vpos - M.voff;
-    int32_t lq = (int32_t)(sr.w >> 16);
-    if (lq == 0xffff) lq = gload(b.l_qseq + r);
-    const u32 so0 = sr.z;
-    if (lq > 1 && !(sr.w & 0x8000u)) { // (the record carries fewer than lq bases)
-        set_error(err, g, PJB_ERR_NO_SEQ);
-        continue; // (the records keep aux = 0)
-    }
-    const uint8_t *seq = b.seq4 + (size_t)so0 * 4;
-    const int32_t q_limit = (int32_t)min(s_bt.seq_words(b, bi) - 1u - so0, 0x7fffffffu); // (to the end of the batch's bases: chunk_load)
-    u32 k = 0;
-    int32_t qsum = 0; // query bases before the operation, soft clips not counted (anchor_side's qPos)
-    for (u32 i = 0; i < nc; i++) {
-        const u32 op = cig[i], ty = op & 15u;
-        if (ty == OP_N) {
-            const u32 p = p0 + k;
-            const u32 j = jid_bam[p];
-            int32_t istart, iend;
-            unpack_key(kf, key[p], istart, iend);
-            const u64 res = pair_stats_generic(cig, nc, pos, aend - vpos + 1, seq, lq, M.d, M.len, genome_has_x != 0, use_codes ? M.codes : (const u32 *)nullptr,
-                                               anc_l[j] - M.voff, istart - M.voff, iend - M.voff, anc_r[j] - M.voff, g, err, i, qsum, q_limit);
-            *reinterpret_cast<u64 *>(rec + p) = res; // PairRec::aux
-            k++;
-        }
-        if (op_consumes_query(ty) && ty != OP_S) qsum += (int32_t)(op >> 4);
-    }
-    } // items
-}
-
-// how two values of word k of a fragment record combine (k4_pairs over a range's slices, k5_frag_reduce over a junction's fragments)
-__device__ __forceinline__ u32 frag_combine(int k, u32 a, u32 b) {
-    if (k >= F_MAXMINANC && k <= F_MAXMINMATCH) return a > b ? a : b;
-    if (k == F_FIRSTMIS) return a < b ? a : b;
-    return a + b; // sums; F_MISM_LO/HI are handled as one 64-bit add by the caller
-}
-// A slice's totals for one junction, from the lane that holds them to one word of the fragment record a lane: the sixteen words (13 + 20
-// byte counters packed in nine, five maxima, the minimum, a zero) go through the wavefront's own 64 bytes of LDS, and lane k reads the one
-// its field lies in.  (Selecting among sixteen registers by lane number costs 30 compares whose masks the compiler keeps in SGPRs: the
-// kernel then spills.)  Wavefront-local: no barrier, the LDS unit serves a wavefront's instructions in order.
-// the sixteen words in LDS order: the four words of the first thirteen counters | the maxima | the last maximum, the minimum, the first
-// two words of the twenty JAD counters | their other three, a zero
-enum { FW_CNT = 0, FW_MAX = 4, FW_MIN = 9, FW_JAD = 10 };
-struct FragWordOf {
-    u32 word, shift, mask; // of lane k's field: the word among the sixteen, the byte's shift in it, all-ones / 0xff / 0 (no field)
-    __device__ __forceinline__ explicit FragWordOf(int k) {
-        const bool c = k <= F_DIST, a = k >= F_JAD0 && k < F_JAD0 + 20, m = k >= F_MAXMINANC && k <= F_FIRSTMIS;
-        const int q = a ? k - F_JAD0 : k;
-        word = c ? FW_CNT + (u32)(q >> 2) : a ? FW_JAD + (u32)(q >> 2) : m ? FW_MAX + (u32)(k - F_MAXMINANC) : 15u;
-        shift = c || a ? 8u * (u32)(q & 3) : 0u;
-        mask = c || a ? 0xffu : m ? 0xffffffffu : 0u;
-    }
-    // four of the sixteen words at a time, as soon as they are folded (all sixteen results held back at once cost sixteen registers)
-    __device__ __forceinline__ static void put(u32 *tot, int quad, bool holder, u32 a, u32 b, u32 c, u32 d) {
-        if (holder) reinterpret_cast<uint4 *>(tot)[quad] = make_uint4(a, b, c, d);
-        __builtin_amdgcn_sched_barrier(0);
-    }
-    __device__ __forceinline__ u32 get(const u32 *tot) const {
-        __builtin_amdgcn_wave_barrier();
-        const u32 w = (tot[word] >> shift) & mask;
-        __builtin_amdgcn_wave_barrier();
-        return w;
-    }
-};
-
-// K4: gather the pairs in sorted order -- one 32-byte record each -- and fold predicates and match statistics to fragments
-// (junction.cc:862-909 accumulators, :755-814 counters).
-// Fragments.  A wavefront owns a RANGE of 2^range_shift consecutive 64-pair slices of the sorted pair array and walks them in order.  A
-// fragment is a maximal run of one junction inside one range; its slot is jid + range index (frag_slot, pjb_device.hip.h, with the rule
-// for the slots that stay unused).  Per slice the 33 counters are folded in packed 8-bit form -- whole-wave reductions on the DPP path
-// where the slice holds one junction, a segmented reduce otherwise --; the fragment that is open across slices lives one word a lane
-// (lane k: word k, k5_frag_reduce's layout), takes each slice's totals with frag_combine and leaves with one coalesced 192-byte store
-// when its junction or the range ends.  While a slice is folded the next one's records and keys and the indices of the one after are on
-// their way; the pair before a slice is lane 63 of the slice before -- only a range's first slice fetches it.
-// A second small kernel reduces slots -> junctions (segmented again, then one atomic per wave and junction), so a
-// junction with 10^6 pairs costs a few dozen same-address atomics, not 10^6.
-// masks (nullptr: the chain that sorted the full keys has its runs from the head scan): per 64-pair slice, the lanes where a
-// junction starts and the lanes where a run of equal read positions starts (entropy, junction.cc:730-749) -- this kernel holds
-// every pair's record anyway, k2_expand turns the bits into seg_off / run_first / run_start without touching a pair.
-__global__ __launch_bounds__(256) void k4_pairs(const u32 *sidx, const u32 *jid_of, const PairRec *rec, const u64 *jkey, KeyFmt kf, const u32 *np,
-                                                 u32 *frag, int32_t *frag_j, u64 *head_mask, u64 *run_mask, const ContigStats *cs_chk, u64 *err_chk,
-                                                 int range_shift) {
-    __shared__ __attribute__((aligned(16))) u32 s_tot[4][16];
-    const u32 n = *np;
-    const int lane = lane_id();
-    const u32 wave = (u32)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)); // (in an SGPR: the range, its loop and its branches are scalar)
-    const u32 range = blockIdx.x * 4 + wave;
-    u32 *tot = s_tot[wave];
-    const FragWordOf word_of(lane);
-    const u64 first = (u64)range << (6 + range_shift);
-    if (first >= n) return;
-    const u32 i0 = (u32)first;
-    const u32 n_sl = min(1u << range_shift, (n - i0 + 63) >> 6); // slices of this range that hold a pair
-    // (loads unconditional, index clamped to n - 1, masked after: see k1_count.  Nothing behind the pairs is touched.)
-    // (32 bits do: n <= 0xffffff00 and at() is asked for the slice behind the range's last at the most)
-    auto at = [&](u32 s) { return min(i0 + 64u * s + (u32)lane, n - 1); };
-    auto key_of = [&](u32 jl) { // a slice of one junction (most are) asks for its key once
-        const u32 jf = (u32)__builtin_amdgcn_readfirstlane((int)jl);
-        return __ballot(jl != jf) == 0 ? jkey[jf] : jkey[jl];
-    };
-    u32 jv = jid_of[at(0)];
-    const u32 p0 = sidx[at(0)];
-    u32 j_nx = jid_of[at(1)], p_nx = sidx[at(1)];
-    // the pair before the range: j, pos, aend of the last pair a slice saw go to the next one's lane 0
-    u32 jprev_c = 0xffffffffu;
-    int32_t pos_c = 0, aend_c = 0;
-    if (i0 > 0) {
-        jprev_c = jid_of[i0 - 1];
-        const uint4 q = reinterpret_cast<const uint4 *>(rec + sidx[i0 - 1])[1];
-        pos_c = (int32_t)q.x;
-        aend_c = (int32_t)q.y;
-    }
-    PairRec Rc = rec_load(rec + p0);
-    u64 jk = key_of(jv);
-    // the open fragment: its junction, word `lane` of its record, the 64-bit sum of F_MISM_LO / F_MISM_HI
-    u32 open_j = 0xffffffffu, fv = 0;
-    u64 fm = 0;
-    auto flush = [&]() {
-        if (open_j == 0xffffffffu) return;
-        const u32 slot = open_j + range;
-        if (lane < F_WORDS) frag[(size_t)slot * F_WORDS + lane] = lane == F_MISM_LO ? (u32)fm : lane == F_MISM_HI ? (u32)(fm >> 32) : fv;
-        if (lane == 0) frag_j[slot] = (int32_t)open_j;
-    };
-    auto absorb = [&](u32 jh, u32 w, u64 m64) { // a slice's totals for junction jh (wave-uniform), this lane's word of them
-        if (jh != open_j) {
-            flush();
-            open_j = jh;
-            fv = w;
-            fm = m64;
-        } else {
-            fv = frag_combine(lane, fv, w);
-            fm += m64;
-        }
-    };
-    for (u32 s = 0; s < n_sl; s++) {
-        PairRec Rn = Rc;
-        u64 jkn = jk;
-        u32 j_n2 = j_nx, p_n2 = p_nx;
-        if (s + 1 < n_sl) {
-            Rn = rec_load(rec + p_nx);
-            jkn = key_of(j_nx);
-        }
-        if (s + 2 < n_sl) {
-            j_n2 = jid_of[at(s + 2)];
-            p_n2 = sidx[at(s + 2)];
-        }
-        const u32 i = i0 + 64u * s + (u32)lane; // (the slice's first pair lies below n <= 0xffffff00)
-        const bool valid = i < n;
-#ifdef PJB_SELFCHECK // (debug builds: what the sort hands over must be a permutation of the pairs with ids below J that ascend in steps of 0 or 1)
-        {
-            const u32 ic = valid ? i : n - 1;
-            const u32 Jc = cs_chk->J;
-            const u32 jb = ic ? jid_of[ic - 1] : jv;
-            int bad = 0;
-            if (sidx[ic] >= n) bad = 1;
-            else if (jv >= Jc) bad = 2;
-            else if (jv != jb && jv != jb + 1) bad = 3;
-            else if (ic == 0 && jv != 0) bad = 4;
-            else if (ic == n - 1 && jv != Jc - 1) bad = 5;
-            else if (frag_slot(jv, ic, range_shift) + 1 >= cs_chk->n_slots) bad = 6;
-            else if ((ic >> 6) >= cs_chk->n_slices) bad = 7;
-            else if (cs_chk->n_slots != frag_slots(Jc, n, range_shift)) bad = 8;
-            if (__ballot(bad != 0)) {
-                if (bad) set_error(err_chk, 0xffffe000u + (u32)bad, PJB_ERR_HIP);
-                return;
-            }
-        }
-#endif
-        // the pair before this one in sorted order: the neighbouring lane's -- lane 0 has it from the slice before
-        u32 jprev_v = __shfl_up(jv, 1, 64);
-        int32_t pos_prev = __shfl_up(Rc.pos, 1, 64), aend_prev = __shfl_up(Rc.aend, 1, 64);
-        if (lane == 0) {
-            jprev_v = jprev_c;
-            pos_prev = pos_c;
-            aend_prev = aend_c;
-        }
-        u32 j = 0xffffffffu;
-        u32 cnt[4] = {0, 0, 0, 0}, jadp[5] = {0, 0, 0, 0, 0}, mx[5] = {0, 0, 0, 0, 0};
-        u32 first_mis = 100000000u; // junction.cc:864
-        u32 nb_mis = 0;
-        if (valid) {
-            j = jv;
-            int32_t istart, iend;
-            unpack_key(kf, jk, istart, iend);
-            const u64 rs = Rc.aux;
-            const u32 minMatch = (u32)(rs & 0xfffffu), mmes = (u32)((rs >> 20) & 0xfffffu), nbMis = (u32)(rs >> 40);
-            const u32 meta = Rc.meta;
-            const u32 cat = meta & META_CAT_MASK;
-            const u32 xs = (meta >> META_XS_SHIFT) & 3u;
-            // distinct alignment runs in BAM order (junction.cc:763-771): compare with the previous pair of the junction
-            const bool dist_head = i == 0 || jprev_v != j || pos_prev != Rc.pos || aend_prev != Rc.aend;
-            // 8-bit lanes: a slice adds at most 64 per field
-            cnt[0] = 1u | ((u32)(cat == 0) << 8) | ((u32)(cat == 1) << 16) | ((u32)(cat == 2) << 24);
-            cnt[1] = (u32)(cat == 3) | ((u32)((meta & META_MULTI) != 0) << 8) | ((u32)(xs == 1) << 16) | ((u32)(xs == 2) << 24);
-            cnt[2] = (u32)((meta & META_UM) != 0) | ((u32)((meta & META_BPP) != 0) << 8) | ((u32)((meta & META_PPP) != 0) << 16) |
-                     ((u32)((meta & META_REL) != 0) << 24);
-            cnt[3] = (u32)dist_head;
-#pragma unroll
-            for (int w = 0; w < 5; w++) // junction.cc:875-877: JAD[k]++ for k < min(20, minMatch)
-                jadp[w] = (u32)((u32)(4 * w) < minMatch) | ((u32)((u32)(4 * w + 1) < minMatch) << 8) |
-                          ((u32)((u32)(4 * w + 2) < minMatch) << 16) | ((u32)((u32)(4 * w + 3) < minMatch) << 24);
-            const int32_t la = istart - Rc.lstart, ra = Rc.rend - iend; // Intron::minAnchorLength intron.cc:81-83
-            mx[0] = (u32)(la < ra ? la : ra);
-            mx[1] = Rc.updown & 0xffffu;
-            mx[2] = Rc.updown >> 16;
-            mx[3] = mmes;
-            mx[4] = minMatch;
-            first_mis = minMatch > 0 ? minMatch : 100000000u;
-            nb_mis = nbMis;
-            // unused fragment slots: the one skipped when a junction starts with the range, and the last one
-            if (s == 0 && lane == 0) {
-                const int64_t u = frag_unused_before(j, i, jprev_v != j, range_shift);
-                if (u >= 0) frag_j[u] = -1;
-            }
-            const int64_t u = frag_unused_behind(j, i, n, range_shift);
-            if (u >= 0) frag_j[u] = -1;
-        }
-        const bool hj = valid && (i == 0 || jprev_v != j);
-        if (head_mask) {
-            const bool hr = valid && (hj || pos_prev != Rc.pos);
-            const u64 mj = __ballot(hj), mr = __ballot(hr);
-            if (lane == 0) { // (a slice word per 64 pairs: the arrays hold ceil(n / 64) words, and s < n_sl)
-                head_mask[i >> 6] = mj;
-                run_mask[i >> 6] = mr;
-            }
-        }
-        // (a slice with a successor is full: lane 63 holds a pair)
-        jprev_c = (u32)__builtin_amdgcn_readlane((int)jv, 63);
-        pos_c = __builtin_amdgcn_readlane(Rc.pos, 63);
-        aend_c = __builtin_amdgcn_readlane(Rc.aend, 63);
-        // ---- the slice's segments -- one, usually: a junction has a few hundred pairs -- in order.  Lane 0 heads the first whether or
-        // not its junction began there: that one may continue the open fragment.  Each is folded by whole-wave reductions on the DPP
-        // path over its own lanes (16 x 6 VALU steps; the lanes outside contribute the identities, as the lanes past the end do);
-        // lane 63 ends up with the totals and hands them on.
-        u64 heads = __ballot(valid && (lane == 0 || jprev_v != j));
-        while (heads) {
-            const int h = __ffsll((unsigned long long)heads) - 1;
-            heads &= heads - 1;
-            const int e = heads ? __ffsll((unsigned long long)heads) - 1 : 64;
-            const bool in = lane >= h && lane < e;
-            const bool last = lane == 63;
-            auto add = [&](u32 v) { return wave_fold<DppAdd>(in ? v : 0u); };
-            auto top = [&](u32 v) { return wave_fold<DppMax>(in ? v : 0u); };
-            __builtin_amdgcn_wave_barrier(); // (the lanes' reads of the segment before are done)
-            FragWordOf::put(tot, FW_CNT / 4, last, add(cnt[0]), add(cnt[1]), add(cnt[2]), add(cnt[3]));
-            FragWordOf::put(tot, FW_MAX / 4, last, top(mx[0]), top(mx[1]), top(mx[2]), top(mx[3]));
-            FragWordOf::put(tot, 2, last, top(mx[4]), wave_fold<DppMin>(in ? first_mis : 100000000u), add(jadp[0]), add(jadp[1]));
-            FragWordOf::put(tot, 3, last, add(jadp[2]), add(jadp[3]), add(jadp[4]), 0u);
-            // (a pair has fewer than 2^24 mismatches: 64 of them fit 32 bits)
-            const u32 mis = wave_total<DppAdd>(in ? nb_mis : 0u);
-            absorb((u32)__builtin_amdgcn_readlane((int)j, h), word_of.get(tot), (u64)mis);
-        }
-        Rc = Rn;
-        jk = jkn;
-        jv = j_nx;
-        j_nx = j_n2;
-        p_nx = p_n2;
-    }
-    flush();
-}
-
-// K5a: fragment slots -> junction accumulators (acc pre-initialised: sums 0, max 0, min 100000000).
-// One wavefront walks FRAG_SLOTS_PER_WAVE consecutive slots; lane k owns word k of the 48-word record, so every
-// load is one coalesced 192-byte row and a junction's run of slots is folded in registers; the run
-// is flushed with one atomic per word when the junction changes.
-constexpr int FRAG_SLOTS_PER_WAVE = 16; // short per-wave chains keep enough wavefronts in flight
-__global__ __launch_bounds__(256) void k5_frag_reduce(const u32 *frag, const int32_t *frag_j, const u32 *n_slots_p, u32 *acc) {
-    const u32 n_slots = *n_slots_p;
-    const u32 wave = (blockIdx.x * 256 + threadIdx.x) >> 6;
-    const int k = lane_id();
-    const u32 s0 = wave * FRAG_SLOTS_PER_WAVE;
-    if (s0 >= n_slots) return;
-    const int32_t myj = (k < FRAG_SLOTS_PER_WAVE && s0 + k < n_slots) ? frag_j[s0 + k] : -1;
-    int32_t cur = -1;
-    u32 v = 0, carry_lo = 0; // lane F_MISM_HI also keeps the low word to do the 64-bit add
-    auto flush = [&](int32_t j) {
-        if (j < 0 || k >= F_JAD0 + 20) return;
-        u32 *dst = acc + (size_t)j * F_WORDS + k;
-        if (k == F_MISM_LO) return; // done by lane F_MISM_HI as one 64-bit atomic
-        if (k == F_MISM_HI) {
-            atomicAdd(reinterpret_cast<u64 *>(dst - 1), ((u64)v << 32) | carry_lo);
-        } else if (k >= F_MAXMINANC && k <= F_MAXMINMATCH) atomicMax(dst, v);
-        else if (k == F_FIRSTMIS) atomicMin(dst, v);
-        else if (v) atomicAdd(dst, v);
-    };
-    // (the rows of all sixteen slots are asked for before the first is folded: sixteen loads on their way at once, not a chain of
-    // sixteen round trips)
-    u32 row[FRAG_SLOTS_PER_WAVE];
-#pragma unroll
-    for (int q = 0; q < FRAG_SLOTS_PER_WAVE; q++) {
-        const int32_t jq = __shfl(myj, q, 64);
-        row[q] = (jq >= 0 && k < F_WORDS) ? frag[(size_t)(s0 + (u32)q) * F_WORDS + k] : 0u;
-    }
-#pragma unroll
-    for (int q = 0; q < FRAG_SLOTS_PER_WAVE; q++) { // (no break / continue: the loop unrolls and row[] stays in registers)
-        const int32_t j = __shfl(myj, q, 64);
-        if (j >= 0) { // (unused slots and those past the last have -1)
-            const u32 w = row[q];
-            const u32 wlo = __shfl(w, F_MISM_LO, 64);
-            if (j != cur) {
-                flush(cur);
-                cur = j;
-                v = w;
-                carry_lo = wlo;
-            } else if (k == F_MISM_HI) {
-                const u64 sum = (((u64)v << 32) | carry_lo) + (((u64)w << 32) | wlo);
-                v = (u32)(sum >> 32);
-                carry_lo = (u32)sum;
-            } else {
-                v = frag_combine(k, v, w);
-            }
-        }
-    }
-    flush(cur);
-}
+namespace pjb {
 
 // ---------------------------------------------------------------------------------------------
 // K5b: one thread per junction: strand from reads, entropy over position runs, splice motif,
