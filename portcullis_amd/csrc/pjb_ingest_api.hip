@@ -188,14 +188,14 @@ extern "C" int pjb_inflate_bgzf(pjb_ctx *c, const uint8_t *comp, int64_t comp_by
     if (rc) return rc;
     *out_bytes = total;
     if (total > out_cap) return fail(c, PJB_ERR_ARG, "inflate_bgzf: output needs %lld bytes, capacity is %lld", (long long)total, (long long)out_cap);
-    if (total == 0) return PJB_OK;
-    if (!out) return fail(c, PJB_ERR_ARG, "inflate_bgzf: no output buffer");
+    if (blocks.empty()) return PJB_OK;
+    if (total && !out) return fail(c, PJB_ERR_ARG, "inflate_bgzf: no output buffer"); // (blocks of ISIZE 0 are decoded too: their streams must be valid)
     if ((rc = ensure(c, c->b_inf_comp, (size_t)comp_bytes + INF_PAD))) return rc;
     if ((rc = ensure(c, c->b_inf_out, (size_t)total + 64))) return rc;
     HIP_TRY(c, hipMemcpyAsync(c->b_inf_comp.p, comp, (size_t)comp_bytes, hipMemcpyHostToDevice, c->stream));
     HIP_TRY(c, hipMemsetAsync((uint8_t *)c->b_inf_comp.p + comp_bytes, 0, INF_PAD, c->stream));
     if ((rc = inflate_on_device(c, (const uint8_t *)c->b_inf_comp.p, blocks, (uint8_t *)c->b_inf_out.p))) return rc;
-    HIP_TRY(c, hipMemcpy(out, c->b_inf_out.p, (size_t)total, hipMemcpyDeviceToHost));
+    if (total) HIP_TRY(c, hipMemcpy(out, c->b_inf_out.p, (size_t)total, hipMemcpyDeviceToHost));
     return PJB_OK;
 }
 

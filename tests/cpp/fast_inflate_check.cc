@@ -2,6 +2,9 @@
 //   fast_inflate_check <seed> <cases>    -- differential cases: zlib's own output at every level / strategy / window, stored
 //                                            blocks, multi-block streams, then damaged copies of each (truncated, bits flipped)
 //   fast_inflate_check speed <MB> [threads] -- MB/s of both decoders on BAM-like data in 64 KB blocks
+//   fast_inflate_check corpus <file>     -- hand-made streams (tests/inflate_cases.py), records of u32 in_len, u32 out_len, u8 accept,
+//                                            the stream: an accept record must be taken (not declined) and give zlib's bytes, any
+//                                            other must be declined; exact-size buffers with guard bytes, as below
 // A case passes if fastInflate either declines (the callers then ask zlib) or returns exactly what zlib's inflate returns
 // for the same input and output size; on undamaged streams it must not decline.
 #include <portcullis/bam/fast_inflate.hpp>
@@ -85,7 +88,69 @@ static std::vector<uint8_t> makeData(std::mt19937_64& rng, int kind, size_t n) {
     return d;
 }
 
+// 0: every record of the corpus file behaves as its accept byte says
+static int checkCorpus(const char* path) {
+    FILE* f = fopen(path, "rb");
+    if (!f) {
+        printf("cannot open %s\n", path);
+        return 1;
+    }
+    std::vector<uint8_t> file;
+    uint8_t buf[1 << 16];
+    for (size_t n; (n = fread(buf, 1, sizeof buf, f)) > 0;) file.insert(file.end(), buf, buf + n);
+    fclose(f);
+    long accepted = 0, refused = 0;
+    for (size_t at = 0, rec = 0; at < file.size(); rec++) {
+        if (file.size() - at < 9) {
+            printf("record %zu: the file ends inside its header\n", rec);
+            return 1;
+        }
+        uint32_t inLen, outLen;
+        memcpy(&inLen, file.data() + at, 4);
+        memcpy(&outLen, file.data() + at + 4, 4);
+        const bool accept = file[at + 8] != 0;
+        at += 9;
+        if (file.size() - at < inLen) {
+            printf("record %zu: the file ends inside its stream\n", rec);
+            return 1;
+        }
+        const std::vector<uint8_t> exact(file.begin() + (long)at, file.begin() + (long)(at + inLen));  // (a read past its end is ASan's to report)
+        at += inLen;
+        std::vector<uint8_t> out((size_t)outLen + 32, 0xA5), ref((size_t)outLen + 1, 0);
+        const bool took = fastInflate(exact.data(), exact.size(), out.data() + 16, outLen);
+        for (int k = 0; k < 16; k++)
+            if (out[(size_t)k] != 0xA5 || out[16 + (size_t)outLen + (size_t)k] != 0xA5) {
+                printf("record %zu: wrote outside the output\n", rec);
+                return 1;
+            }
+        if (!accept) {
+            if (took) {
+                printf("record %zu: accepted a stream that must be refused\n", rec);
+                return 1;
+            }
+            refused++;
+            continue;
+        }
+        if (!zlibInflate(exact.data(), exact.size(), ref.data(), outLen)) {
+            printf("record %zu: zlib does not take an accept record\n", rec);
+            return 1;
+        }
+        if (!took) {
+            printf("record %zu: declined a valid stream (%u -> %u bytes)\n", rec, inLen, outLen);
+            return 1;
+        }
+        if (outLen && memcmp(out.data() + 16, ref.data(), outLen) != 0) {
+            printf("record %zu: wrong bytes (%u -> %u bytes)\n", rec, inLen, outLen);
+            return 1;
+        }
+        accepted++;
+    }
+    printf("ok: %ld streams accepted with zlib's bytes, %ld refused\n", accepted, refused);
+    return 0;
+}
+
 int main(int argc, char** argv) {
+    if (argc >= 3 && std::string(argv[1]) == "corpus") return checkCorpus(argv[2]);
     if (argc >= 3 && std::string(argv[1]) == "speed") {
         std::mt19937_64 rng(7);
         const size_t total = (size_t)atoi(argv[2]) << 20, blk = 0xff00;

@@ -1,6 +1,7 @@
-"""Device-side BGZF inflate against zlib: every DEFLATE block type, long and short
+"""Device-side BGZF inflate against zlib: every DEFLATE block type as zlib's encoder writes it, long and short
 match distances, many blocks per call, the reference's own BAM fixture, and corrupt input (must fail
-with PJB_ERR_BGZF, never hang)."""
+with PJB_ERR_BGZF, never hang).  What zlib cannot produce -- 15-bit codes, one or no distance code, chains of overlapping
+3-byte matches, every malformed header -- is in test_gpu_inflate_handmade.py (the corpus of inflate_cases.py)."""
 import gzip
 import os
 import struct
@@ -9,6 +10,7 @@ import zlib
 import numpy as np
 import pytest
 
+from deflate_writer import Bits as _Bits, bgzf_member as _raw_block
 from fuzzgen import make_reads
 from util_bam import BGZF_EOF, _bgzf_block, write_bam
 
@@ -129,35 +131,6 @@ def test_corrupt_input_fails_cleanly(ctx):
     with pytest.raises(ffi.PjbError):
         ctx.inflate_bgzf(b"\x1f\x8b\x08\x00" + bytes(40))  # gzip without the BGZF extra field
     assert ctx.inflate_bgzf(good) == data  # the context still works afterwards
-
-
-class _Bits:
-    """LSB-first bit packing of a DEFLATE stream; Huffman codes go in MSB-first."""
-
-    def __init__(self):
-        self.acc, self.n, self.out = 0, 0, bytearray()
-
-    def put(self, value, nbits):
-        self.acc |= value << self.n
-        self.n += nbits
-        while self.n >= 8:
-            self.out.append(self.acc & 0xff)
-            self.acc >>= 8
-            self.n -= 8
-
-    def code(self, code, nbits):
-        for k in range(nbits - 1, -1, -1):
-            self.put((code >> k) & 1, 1)
-
-    def bytes(self):
-        return bytes(self.out) + (bytes([self.acc & 0xff]) if self.n else b"")
-
-
-def _raw_block(payload, isize):
-    """A BGZF block around a hand-made DEFLATE payload (CRC is not checked by either decoder here)."""
-    hdr = bytes([31, 139, 8, 4, 0, 0, 0, 0, 0, 255, 6, 0, 66, 67, 2, 0])
-    total = len(hdr) + 2 + len(payload) + 8
-    return hdr + struct.pack("<H", total - 1) + payload + struct.pack("<II", 0, isize)
 
 
 def _endless_literals_header():
