@@ -154,6 +154,8 @@ def lib():
         L.orc_depth.argtypes = [C.c_int32, C.POINTER(OrcReads), C.c_void_p]
         L.orc_calc_coverage.restype = C.c_double
         L.orc_calc_coverage.argtypes = [C.c_int32, C.c_int32, C.c_void_p, C.c_size_t]
+        L.orc_fetch_bases.restype = C.c_int64
+        L.orc_fetch_bases.argtypes = [C.c_char_p, C.c_int32, C.c_int32, C.c_int32, C.c_char_p, C.c_size_t]
         L.orc_extra.argtypes = [C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32]
         _LIB = L
     return _LIB
@@ -224,6 +226,16 @@ def revcomp(s):
     out = C.create_string_buffer(len(s) + 1)
     lib().orc_revcomp(s.encode(), len(s), out)
     return out.raw[: len(s)]
+
+
+def fetch_bases(genome, beg, end):
+    """The oracle's faidx_fetch_seq on an in-memory sequence (0-based inclusive, clamped): the bases as bytes."""
+    g = genome.encode() if isinstance(genome, str) else bytes(genome)
+    out = C.create_string_buffer(len(g) + 2)
+    n = lib().orc_fetch_bases(g, len(g), beg, end, out, len(out))
+    if n < 0:
+        _err(int(n))
+    return out.raw[:n]
 
 
 def min_anchor(start, end, left, right):

@@ -691,6 +691,18 @@ static void fetch_bases(const char *genome, int32_t glen, int32_t beg, int32_t e
     sb_put(out, genome + beg, (size_t)(end - beg + 1));
 }
 
+/* fetch_bases for tests that hold it against faidx_fetch_seq itself: the bases, NUL-terminated, and their number. */
+int64_t orc_fetch_bases(const char *genome, int32_t glen, int32_t beg, int32_t end, char *out, size_t out_cap) {
+    sbuf s = {0};
+    fetch_bases(genome, glen, beg, end, &s);
+    if (s.n + 1 > out_cap) { sb_free(&s); return fail(ORC_ERR_ARG, "fetch_bases: output too small"); }
+    memcpy(out, s.p, s.n);
+    out[s.n] = 0;
+    const int64_t n = (int64_t)s.n;
+    sb_free(&s);
+    return n;
+}
+
 static void to_upper(sbuf *s) {
     for (size_t i = 0; i < s->n; i++) s->p[i] = up(s->p[i]);
 }
@@ -962,17 +974,24 @@ static int has_refskip(const orc_reads *rd, int64_t i) { /* BamAlignment::isSpli
 /* a record of unspliced.bam: not spliced, and mapped (src/junction_builder.cc:168-186) */
 static int is_unspliced_mapped(const orc_reads *rd, int64_t i) { return !has_refskip(rd, i) && !(rd->flag[i] & 0x4); }
 
-/* bam_endpos (deps/htslib-1.3/sam.c: bam_cigar2rlen, 0 -> pos + 1) */
+/* bam_endpos of a mapped record, deps/htslib-1.3/sam.c:336-342: pos + bam_cigar2rlen where there is a CIGAR -- pos itself
+ * where its operations span nothing (5S, 3I) --, pos + 1 where there is none. */
 static int32_t end_excl(const orc_reads *rd, int64_t i) {
-    int32_t a = aligned_length(rd, i);
-    return rd->pos[i] + (a > 0 ? a : 1);
+    if (rd->cig_off[i + 1] == rd->cig_off[i]) return rd->pos[i] + 1;
+    return rd->pos[i] + aligned_length(rd, i);
 }
+/* a record of unspliced.bam that the pileup reports at some position: one with a reference span.  A record whose CIGAR
+ * spans nothing is freed before its position is piled up (sam.c:1861-1864, end <= pos); at a mapped record without a
+ * CIGAR the reference stops (the assertion of resolve_cigar2, sam.c:1537), so nothing is defined behind it. */
+static int is_piled(const orc_reads *rd, int64_t i) { return is_unspliced_mapped(rd, i) && aligned_length(rd, i) > 0; }
 
 /* The pileup of unspliced.bam for one target, deps/htslib-1.3/sam.c:1853-1975 driven by
  * DepthParser::read_bam_skip_gapped (depth_parser.cc:60-83; min_mapQ 0 and min_len 0 filter nothing).
  * bam_plp_push keeps every mapped record except: one that starts at the position the iterator stands on
  * (the start of the last record it kept) while more than maxcnt = 8000 list nodes are allocated -- the
- * records not yet passed (end > every position already piled up) plus the list's sentinel and the dummy.
+ * records not yet passed (bam_endpos > every position already piled up; a record without a span, whose bam_endpos is
+ * its own position, therefore counts for the records that follow it at that position and for no others) plus the
+ * list's sentinel and the dummy.  Held to htslib itself by tests/test_oracle_htslib_witness.py.
  * Every position covered by a kept record is reported; its depth is the number of kept records there
  * minus those in a deletion (is_del; is_refskip cannot occur without N operations). */
 int64_t orc_depth(int32_t ref_len, const orc_reads *rd, uint32_t *depth) {
@@ -998,8 +1017,14 @@ int64_t orc_depth(int32_t ref_len, const orc_reads *rd, uint32_t *depth) {
         }
         if (iter_pos == p && in_list + 2 > 8000) continue; /* sam.c:1906-1910 */
         kept++;
-        in_list++;
-        { int32_t ce = e > ref_len + 1 ? ref_len + 1 : e; if (ce < swept) ce = swept; cnt_end[ce]++; }
+        /* sam.c:1930: the node joins the list only if its end lies behind the iterator's position -- always with a span;
+         * a record whose CIGAR spans nothing (end == p) only where it is the first one kept at p */
+        if (e > iter_pos) {
+            in_list++;
+            int32_t ce = e > ref_len + 1 ? ref_len + 1 : e;
+            if (ce < swept) ce = swept;
+            cnt_end[ce]++;
+        }
         iter_pos = p;
         /* depth contribution: M / = / X runs */
         int32_t x = p;
@@ -1146,12 +1171,12 @@ int orc_extra(int32_t n_refs, const int32_t *ref_len, const orc_reads *reads, co
         int32_t last = -1;
         for (int32_t t = 0; t < n_refs; t++) {
             int any = 0;
-            for (int64_t i = 0; i < reads[t].n && !any; i++) any = is_unspliced_mapped(&reads[t], i);
+            for (int64_t i = 0; i < reads[t].n && !any; i++) any = is_piled(&reads[t], i);
             if (any) last = t;
         }
         for (int32_t t = 0; t < n_refs && !rc; t++) {
             int any = 0;
-            for (int64_t i = 0; i < reads[t].n && !any; i++) any = is_unspliced_mapped(&reads[t], i);
+            for (int64_t i = 0; i < reads[t].n && !any; i++) any = is_piled(&reads[t], i);
             if (!any) continue;
             uint32_t *depth = (uint32_t *)malloc(((size_t)ref_len[t] + 1) * sizeof(uint32_t));
             if (!depth) { rc = fail(ORC_ERR_NOMEM, "oom"); break; }

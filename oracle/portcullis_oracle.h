@@ -125,6 +125,10 @@ int orc_padded_genome_seq(const uint32_t *cigar, int n_cigar, int32_t position, 
 int orc_hamming(const char *a, size_t na, const char *b, size_t nb);
 void orc_revcomp(const char *in, size_t n, char *out);
 
+/* The oracle's faidx_fetch_seq (deps/htslib-1.3/faidx.c:439-476) on an in-memory sequence: 0-based inclusive ends, both
+ * clamped to the sequence, end < beg fetches one base.  Returns the number of bases written (NUL-terminated). */
+int64_t orc_fetch_bases(const char *genome, int32_t glen, int32_t beg, int32_t end, char *out, size_t out_cap);
+
 /* Intron::minAnchorLength (lib/src/intron.cc:67-83); negative error if it throws. */
 int64_t orc_min_anchor(int32_t start, int32_t end, int32_t left, int32_t right);
 

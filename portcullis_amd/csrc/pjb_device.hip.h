@@ -586,6 +586,10 @@ struct ArrU8Fn {
     const uint8_t *a;
     __device__ u64 operator()(u64 i) const { return a[i]; }
 };
+struct ArrU8Bit0Fn { // bit 0 of every byte
+    const uint8_t *a;
+    __device__ u64 operator()(u64 i) const { return a[i] & 1u; }
+};
 struct ArrI32Fn { // signed terms, summed modulo 2^64
     const int32_t *a;
     __device__ u64 operator()(u64 i) const { return (u64)(int64_t)a[i]; }

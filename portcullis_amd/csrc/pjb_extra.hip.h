@@ -63,8 +63,11 @@ __global__ __launch_bounds__(256) void kx_classify(DevBatch b, int32_t ref_len, 
         const bool unspliced = !spliced && mapped; // a record of unspliced.bam
         const bool spans = unspliced && aligned > 0 && pos >= 0;
         x_pos[g] = pos;
-        x_endx[g] = pos + (aligned > 0 ? aligned : 1); // bam_endpos
-        q_flag[g] = spans ? 1 : 0;
+        // bam_endpos (sam.c:336-342): pos + span with a CIGAR -- pos itself where it spans nothing --, pos + 1 without one
+        x_endx[g] = c1 > c0 ? pos + aligned : pos + 1;
+        // bit 0: a record with a span (depth, rank queries); bit 1: one without, which the pileup still holds in its list while
+        // it stands on the record's position (kx_cap_*)
+        q_flag[g] = spans ? 1 : (unspliced && aligned == 0 && pos >= 0 ? 2 : 0);
         if (unspliced && aligned == 0) { // getEnd() == pos - 1: handled one by one in kx_flank (practically never)
             const u32 z = atomicAdd(&cnt->n_zero, 1u);
             if (z < zcap) zlist[z] = (u32)pos;
@@ -120,6 +123,9 @@ __global__ __launch_bounds__(256) void kx_spliced_codes(DevBatch b, const TileSt
 // endpos >= pos_i, kept or not = (unspliced records before i) - (unspliced records with endpos < pos_i).  If
 // the bound stays below maxcnt - 1 everywhere, nothing is dropped and the difference array already holds the
 // reference's depth (the normal case: it takes 8000-fold coverage of unspliced records).
+//   prefix_q and pe count the records with a span.  One without a span (q_flag 2: its bam_endpos is its own position, or
+// the next where it has no CIGAR) is in the list only for the records that follow it there; there are at most n_zero of
+// them (a target with more than X_ZCAP is refused), so the bound is this one plus n_zero, and the replay counts them one by one.
 __global__ __launch_bounds__(256) void kx_cap_bound(const int32_t *x_pos, const uint8_t *q_flag, const u32 *prefix_q,
                                                      const u32 *pe, u32 n, int32_t ref_len, u32 *bound, ExtraCounters *cnt) {
     const u32 g = blockIdx.x * 256 + threadIdx.x;
@@ -131,7 +137,7 @@ __global__ __launch_bounds__(256) void kx_cap_bound(const int32_t *x_pos, const 
         const int32_t idx = p - 1 < 0 ? 0 : (p - 1 > ref_len + 1 ? ref_len + 1 : p - 1);
         u = prefix_q[g] - pe[idx];
         if (bound) bound[g] = u;
-        hot = u + 2 > PLP_MAXCNT;
+        hot = u + cnt->n_zero + 2 > PLP_MAXCNT; // (n_zero: written by kx_classify, the launch before)
     }
     // (one counter for every wavefront of records: look first -- the maximum settles after a few waves, and 156 k
     // atomics on one address are served one at a time; a stale look only costs an atomic)
@@ -147,36 +153,54 @@ __global__ __launch_bounds__(256) void kx_cap_bound(const int32_t *x_pos, const 
 // is kept whatever happened before: its list is at most its bound).  Sequential by nature -- whether a record is
 // kept depends on which earlier ones were -- so one lane walks the span; `de` (zeroed, ref_len + 2 entries)
 // counts dropped records by endpos.  Kept records inside the list = bound - dropped records still inside.
+//   The bound leaves out the records without a span (q_flag 2).  bam_plp_push links a kept record into the list only if its
+// endpos lies behind the position the iterator stands on (sam.c:1930) -- every record with a span; one without a CIGAR, whose
+// endpos is pos + 1; and one whose CIGAR spans nothing only where it is the first record kept at its position.  Such a record is
+// in the list up to its endpos like any other, so it goes into `de` with the opposite sign (the sums are modulo 2^32): "dropped and
+// still inside" minus "without a span, linked and still inside".  Those in front of the walked span that are still inside where it
+// begins -- kept, like everything in front of it -- start at its first position or one base before it.
 __global__ void kx_cap_replay(const int32_t *x_pos, const int32_t *x_endx, const uint8_t *q_flag, const u32 *bound, u32 n,
                               int32_t ref_len, u32 *de, uint8_t *dropped, ExtraCounters *cnt) {
     if (blockIdx.x != 0 || threadIdx.x != 0) return;
     const u32 g0 = cnt->hot_first, g1 = cnt->hot_last;
     if (g0 > g1 || g0 >= n) return;
-    // start of the last unspliced record before the span (it was kept: nothing before the span is dropped)
+    auto slot = [&](int32_t e, int32_t sweep) { // where endpos e is counted: at or behind the sweep, inside the array
+        if (e < sweep) e = sweep;
+        return e > ref_len + 1 ? ref_len + 1 : e;
+    };
+    u32 dtotal = 0, dgone = 0, n_dropped = 0;
+    int32_t sweep = x_pos[g0];
+    // the records in front of the span that start at most one base before it, and the start of the last unspliced record
+    // before them (kept: nothing before the span is dropped)
+    u32 gs = g0;
+    while (gs > 0 && x_pos[gs - 1] >= sweep - 1) gs--;
     int32_t last_kept_pos = -1;
-    for (u32 g = g0; g-- > 0;)
+    for (u32 g = gs; g-- > 0;)
         if (q_flag[g]) {
             last_kept_pos = x_pos[g];
             break;
         }
-    u32 dtotal = 0, dgone = 0;
-    int32_t sweep = x_pos[g0];
+    for (u32 g = gs; g < g0; g++) {
+        if (!q_flag[g]) continue;
+        if (q_flag[g] == 2 && x_endx[g] > last_kept_pos && x_endx[g] >= sweep) de[slot(x_endx[g], sweep)]--, dtotal--;
+        last_kept_pos = x_pos[g];
+    }
     for (u32 g = g0; g <= g1; g++) {
         if (!q_flag[g]) continue;
         const int32_t p = x_pos[g];
         while (sweep < p && sweep <= ref_len + 1) dgone += de[sweep++];
         const u32 in_list = bound[g] - (dtotal - dgone);
+        const bool spanless = q_flag[g] == 2;
         if (p == last_kept_pos && in_list + 2 > PLP_MAXCNT) {
-            dropped[g] = 1;
-            int32_t e = x_endx[g];
-            if (e > ref_len + 1) e = ref_len + 1;
-            if (e < sweep) e = sweep;
-            de[e]++;
-            dtotal++;
-        } else
+            dropped[g] = 1; // (one without a span has no run to take back: kx_undo_dropped finds none)
+            n_dropped++;
+            if (!spanless) de[slot(x_endx[g], sweep)]++, dtotal++; // (the bound never held one without a span)
+        } else {
+            if (spanless && x_endx[g] > last_kept_pos) de[slot(x_endx[g], sweep)]--, dtotal--;
             last_kept_pos = p;
+        }
     }
-    cnt->n_dropped = dtotal;
+    cnt->n_dropped = n_dropped;
 }
 
 // KX3c: take the dropped records' M / = / X runs back out of the difference array (before the scan).
@@ -342,9 +366,10 @@ __global__ __launch_bounds__(256) void kx_gaps(DevBatch b, int32_t voff, const u
     }
 }
 
-// the pileup's cap can only bite where PLP_MAXCNT - 1 records with a span start within max_span bases of each other
+// the pileup's cap can only bite where PLP_MAXCNT - 1 records start within max_span bases of each other; those without a span
+// are not in the list walked here, so each of them may stand for one that is
 __global__ __launch_bounds__(256) void kx_cap_check(const int32_t *comp_pos, SparseCounters *cnt) {
-    const u32 n = (u32)cnt->total, K = PLP_MAXCNT - 1;
+    const u32 n = (u32)cnt->total, K = PLP_MAXCNT - 1 - min(cnt->n_zero, PLP_MAXCNT - 2);
     const u32 r = blockIdx.x * 256 + threadIdx.x + K;
     if (r >= n) return;
     if ((int64_t)comp_pos[r] - (int64_t)comp_pos[r - K] <= (int64_t)cnt->max_span) atomicOr(&cnt->need_dense, 1u);

@@ -73,7 +73,7 @@ static int extra_contig_dense(pjb_ctx *c, Flight &f, u64 n_spliced, u32 P, u32 J
                (int32_t *)X.cover, (u32 *)c->x_zlist.p, X_ZCAP, d_cnt);
     if ((rc = spliced_codes(c, f, d_cnt, X.spl_codes))) return rc;
     if ((rc = run_scan(c, "kx_ends", ArrU32Fn{ce}, ExclusiveU32Sink{ce}, (u64)L + 2, (u64 *)c->b_xtotal.p))) return rc;
-    if ((rc = run_scan(c, "kx_unspl", ArrU8Fn{x_q}, ExclusiveU32Sink{prefq}, (u64)N + 1, (u64 *)c->b_xtotal.p))) return rc;
+    if ((rc = run_scan(c, "kx_unspl", ArrU8Bit0Fn{x_q}, ExclusiveU32Sink{prefq}, (u64)N + 1, (u64 *)c->b_xtotal.p))) return rc;
     LAUNCH(c, "kx_cap_bound", kx_cap_bound, dim3((unsigned)((N + 255) / 256)), dim3(256), (const int32_t *)x_pos, (const uint8_t *)x_q,
            (const u32 *)prefq, (const u32 *)ce, (u32)N, L, (u32 *)nullptr, d_cnt);
     u32 n_unspl = 0;
@@ -82,7 +82,7 @@ static int extra_contig_dense(pjb_ctx *c, Flight &f, u64 n_spliced, u32 P, u32 J
     HIP_TRY(c, hipStreamSynchronize(st));
     if (hc.n_zero > X_ZCAP)
         return fail(c, PJB_ERR_ARG, "extra: target %d has %u mapped records without a reference span (limit %u)", tid, hc.n_zero, X_ZCAP);
-    if (hc.max_buffered + 2 > PLP_MAXCNT) { // the pileup's record cap may bite: replay it over the hot span
+    if (hc.max_buffered + hc.n_zero + 2 > PLP_MAXCNT) { // the pileup's record cap may bite: replay it over the hot span
         if ((rc = ensure(c, c->x_bound, N * 4 + 16))) return rc;
         if ((rc = ensure(c, c->x_de, ((size_t)L + 2) * 4))) return rc;
         if ((rc = ensure(c, c->x_dropped, N + 16))) return rc;

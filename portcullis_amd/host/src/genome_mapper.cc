@@ -9,6 +9,7 @@
 #include <cstring>
 #include <cstdio>
 #include <fstream>
+#include <set>
 #include <sstream>
 
 namespace portcullis {
@@ -21,34 +22,67 @@ GenomeMapper::~GenomeMapper() {
 void GenomeMapper::buildFastaIndex() {
     std::ifstream in(genomeFile.c_str(), std::ios::binary);
     if (!in) throw BamException("Could not open genome file: " + genomeFile);
-    std::ofstream out(getFastaIndexFile().c_str());
+    // The rules of fai_build (deps/htslib-1.3/faidx.c:82-155), which writes the reference's .fai: the same lines for the
+    // files it takes, and a refusal for the files it refuses.  A line's bases are its graphic characters and its width
+    // every byte up to and including the newline (a last line without one counts as if it had it).  A record's first
+    // sequence line sets both columns; a line that differs from it (a shorter last line, an empty line) may be followed
+    // by empty lines only.  Empty lines between a header and its sequence move the offset.  A record without sequence
+    // keeps the columns of the record before it (-1 where there is none), as htslib's does.
+    enum { AFTER_HEADER, UNIFORM, CLOSED, CLOSED_BLANK } state = UNIFORM;
+    std::ostringstream out;
+    std::set<std::string> seen;
     std::string line, name;
-    int64_t off = 0, len = 0, seqOff = 0;
-    int32_t lb = 0, lw = 0;
+    int64_t off = 0, len = -1, seqOff = 0;
+    int64_t lb = -1, lw = -1;
+    auto refuse = [&](const std::string& why) { throw BamException("Could not index genome file " + genomeFile + ": " + why); };
     auto flush = [&]() {
-        if (!name.empty()) out << name << "\t" << len << "\t" << seqOff << "\t" << lb << "\t" << lw << "\n";
+        if (len >= 0 && seen.insert(name).second) out << name << "\t" << len << "\t" << seqOff << "\t" << lb << "\t" << lw << "\n";
     };
     while (std::getline(in, line)) {
-        const int64_t raw = (int64_t)line.size() + 1;
-        if (!line.empty() && line[0] == '>') {
-            flush();
-            std::stringstream ss(line.substr(1));
-            ss >> name;
-            len = 0;
-            lb = lw = 0;
-            seqOff = off + raw;
-        } else {
-            size_t n = line.size();
-            while (n && (line[n - 1] == '\r')) n--;
-            if (lb == 0 && n) {
-                lb = (int32_t)n;
-                lw = (int32_t)raw;
-            }
-            len += (int64_t)n;
-        }
+        const bool newline = !in.eof();  // (getline sets eofbit when the file ended before a newline)
+        const int64_t raw = (int64_t)line.size() + (newline ? 1 : 0);
         off += raw;
+        if (line.empty()) {
+            if (state == AFTER_HEADER) seqOff = off;
+            else if (state == UNIFORM && len >= 0) state = CLOSED;
+            else if (state == CLOSED_BLANK) refuse("an empty line inside sequence '" + name + "'");
+            continue;
+        }
+        if (line[0] == '>') {
+            flush();
+            size_t a = 1;
+            while (a < line.size() && isspace((unsigned char)line[a])) a++;
+            size_t b = a;
+            while (b < line.size() && !isspace((unsigned char)line[b])) b++;
+            if (b == line.size() && !newline) refuse("the last entry has no sequence");
+            name = line.substr(a, b - a);
+            state = AFTER_HEADER;
+            len = 0;
+            seqOff = off;
+            continue;
+        }
+        if (len < 0) refuse("sequence before the first header");
+        if (state == CLOSED_BLANK) refuse("an empty line inside sequence '" + name + "'");
+        int64_t bases = 0;
+        for (const char ch : line) bases += isgraph((unsigned char)ch) ? 1 : 0;
+        if (state == CLOSED) {
+            if (bases) refuse("different line length in sequence '" + name + "'");
+            state = CLOSED_BLANK;
+        }
+        const int64_t width = (int64_t)line.size() + 1;
+        len += bases;
+        if (state == AFTER_HEADER) {
+            lb = bases;
+            lw = width;
+            state = UNIFORM;
+        } else if (state == UNIFORM && (width != lw || bases != lb)) state = CLOSED;
     }
+    if (len < 0) refuse("no sequence record");
     flush();
+    std::ofstream f(getFastaIndexFile().c_str(), std::ios::binary);
+    f << out.str();
+    f.close();
+    if (!f) throw BamException("Could not write genome index: " + getFastaIndexFile());
 }
 
 void GenomeMapper::loadFastaIndex() {

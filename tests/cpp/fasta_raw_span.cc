@@ -11,7 +11,7 @@
 int main(int argc, char** argv) {
     if (argc < 4) return 2;
     portcullis::bam::GenomeMapper g(argv[1]);
-    g.buildFastaIndex();
+    if (!std::ifstream(g.getFastaIndexFile().c_str())) g.buildFastaIndex();  // (as prep does: an index beside the file is taken as it is)
     g.loadFastaIndex();
     const std::string out = argv[2];
     for (int k = 3; k < argc; k++) {

@@ -260,3 +260,29 @@ def make_reads(seed, glen=30000, n_reads=3000, paired=False, opts=None, L=(30, 1
 
 def to_batch(reads):
     return ReadBatch.from_reads(reads)
+
+
+def aux_rich_targets():
+    """Three targets of fuzz reads for write_bam, as (refs, genomes {tid: bytes}, reads): every CIGAR op, SEQ '*', names of
+    assorted lengths, and aux fields of several types (C, Z, B:s) behind the XS tag or in front of it."""
+    import struct
+
+    reads, refs, genomes = [], [], {}
+    for tid in range(3):
+        genome, rs = make_reads(40 + tid, n_reads=1500 + 900 * tid, paired=(tid == 1))
+        refs.append((f"chr{tid + 1}", len(genome)))
+        genomes[tid] = genome.encode() if isinstance(genome, str) else genome
+        for k, r in enumerate(rs):
+            r = dict(r)
+            r["tid"] = tid
+            if r.get("mtid", -1) >= 0:
+                r["mtid"] = tid
+            r["name"] = f"t{tid}r{k}" + "x" * (k % 23)
+            other = b"NMC\x03" + b"MDZ" + b"10A5^AC6\x00" + b"ZBBs" + struct.pack("<i", 3) + b"\x01\x00\x02\x00\x03\x00"
+            if k % 3 == 0:   # aux fields of several types after XS ...
+                r["aux"] = other
+            elif k % 3 == 1 and r.get("xs") is not None:   # ... or before it
+                r["aux"] = other + b"XSA" + r["xs"].encode()
+                r["xs"] = None
+            reads.append(r)
+    return refs, genomes, reads

@@ -168,3 +168,20 @@ def test_bamfilt_program(tmp_path, orc, mode, threads, route, monkeypatch):
     assert p3.returncode == 0, p3.stderr[-2000:]
     n_junc2 = len([l for l in open(out2 + ".junctions.tab").read().split("\n")[1:] if l.strip()])
     assert 0 < n_junc2 <= len(body)
+    import hts_witness as hts
+
+    if (mode, route) == ("HARD", "handover") and hts.available():
+        # the file -- BGZF members deflated on the device, one hand-over after the other -- and its .bai as the reference's own
+        # htslib-1.3 reads them (oracle/_ref/hts_witness): the EOF marker, every record, and region queries through the
+        # program's index against the same queries through the index htslib builds of the file.  (Where nothing could have
+        # built the witness the test ends here with what it asserted above, as it did before the witness existed.)
+        from test_oracle_htslib_witness import assert_records, regions_for
+
+        assert hts.eof(outbam) == 1
+        assert len(assert_records(outbam)) == n_out
+        own = str(tmp_path / "htslib.bai")
+        hts.index(outbam, own)
+        regions = regions_for(refs)
+        answers = hts.query(outbam, outbam + ".bai", regions)
+        assert answers == hts.query(outbam, own, regions)
+        assert sum(len(hits) for _, hits in answers) > n_out

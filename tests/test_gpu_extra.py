@@ -91,6 +91,38 @@ def test_extra_pileup_cap(ffi, orc):
     assert_extra_equal(rows, extra, orows)
 
 
+@pytest.mark.parametrize("dense", [False, True])
+def test_extra_pileup_cap_with_records_without_a_span(ffi, orc, dense):
+    """Mapped records whose CIGAR spans nothing (5S, 3I), and one without a CIGAR, among the records of a capped pile.  The
+    pileup holds such a record in its list only while it stands on the record's position, and one with a CIGAR only if it is
+    the first record there (sam.c:336-342,1930; tests/test_oracle_htslib_witness.py holds the oracle to htslib on these): the
+    number of records the cap drops behind them shifts by one for each."""
+    genome, reads = make_reads(11, glen=6000, n_reads=1500, L=(60, 120))
+    rng = np.random.default_rng(3)
+    spliced = [r for r in reads if "N" in r["cigar"]]
+    anchor = max(50, spliced[len(spliced) // 2]["pos"])
+    deep = []
+    for p in range(anchor - 42, anchor - 34):   # first at their position (stable sort), in front of the pile and inside it ...
+        deep += [dict(pos=p, cigar="5S", seq="ACGTA", flag=0), dict(pos=p, cigar="3I", seq="ACG", flag=0)]
+    deep.append(dict(pos=anchor - 39, cigar="", seq="ACGT", flag=0))
+    for k in range(12000):
+        p = anchor - 40 + k // 2000
+        deep.append(dict(pos=p, cigar=f"{int(rng.integers(40, 90))}M", seq=None, l_qseq=0, flag=0))
+        if k % 1500 == 700:                     # ... and behind records of their own position
+            deep.append(dict(pos=p, cigar="4S", seq="ACGT", flag=0))
+    allr = sorted(deep + reads, key=lambda r: r["pos"])
+    add_names(allr, rng, "d", unmapped_frac=0.0)
+    contigs = [(genome, allr)]
+    orows, _ = oracle_extra(orc, contigs)
+    with_z, kept = orc.depth(len(genome), batch_with_names(orc, allr))
+    without_z, _ = orc.depth(len(genome), batch_with_names(orc, [r for r in allr if r["cigar"] not in ("5S", "3I", "4S", "")]))
+    assert with_z.max() >= 7990 and (with_z != without_z).any()   # the cap drops records, and not the same ones without them
+    blind, _ = oracle_extra(orc, [(genome, [r for r in allr if r["cigar"] not in ("5S", "3I", "4S", "")])])
+    assert (blind["coverage"] != orows["coverage"]).any()         # ... which a junction's coverage shows
+    rows, extra = device_extra(ffi, orc, contigs, dense=dense)
+    assert_extra_equal(rows, extra, orows)
+
+
 def test_extra_zero_span_and_edges(ffi, orc):
     """Mapped records without a reference span (getEnd() == pos - 1), junctions at the contig edge (windows clipped by
     the bounds test of calcCoverage), SEQ '*'."""

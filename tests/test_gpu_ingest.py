@@ -301,27 +301,10 @@ def orc():
 def test_submit_bam_matches_oracle(orc, tmp_path, block_size):
     """Three targets of fuzz reads (every CIGAR op, aux tags of every type before / after XS, SEQ '*'),
     BGZF blocks that cut records anywhere: the device ingest must give the oracle's rows."""
-    from fuzzgen import make_reads
+    from fuzzgen import aux_rich_targets
     from portcullis_amd import ffi
     from util_bam import write_bam
-    reads, refs, genomes = [], [], {}
-    for tid in range(3):
-        genome, rs = make_reads(40 + tid, n_reads=1500 + 900 * tid, paired=(tid == 1))
-        refs.append((f"chr{tid + 1}", len(genome)))
-        genomes[tid] = genome.encode() if isinstance(genome, str) else genome
-        for k, r in enumerate(rs):
-            r = dict(r)
-            r["tid"] = tid
-            if r.get("mtid", -1) >= 0:
-                r["mtid"] = tid
-            r["name"] = f"t{tid}r{k}" + "x" * (k % 23)
-            other = b"NMC\x03" + b"MDZ" + b"10A5^AC6\x00" + b"ZBBs" + struct.pack("<i", 3) + b"\x01\x00\x02\x00\x03\x00"
-            if k % 3 == 0:   # aux fields of several types after XS ...
-                r["aux"] = other
-            elif k % 3 == 1 and r.get("xs") is not None:   # ... or before it
-                r["aux"] = other + b"XSA" + r["xs"].encode()
-                r["xs"] = None
-            reads.append(r)
+    refs, genomes, reads = aux_rich_targets()
     path = str(tmp_path / "a.bam")
     write_bam(path, refs, reads, block_size=block_size)
     with ffi.Context(0, "FR") as ctx:

@@ -91,14 +91,24 @@ def test_fasta_raw_spans(tmp_path):
 
 def test_fasta_records_not_laid_out_as_indexed(tmp_path):
     """A record whose lines are not all of the first line's width: the index describes the first line only, the rule must
-    refuse the record (fetchContig's character filter still reads it correctly)."""
+    refuse the record (fetchContig's character filter still reads it correctly).  GenomeMapper::buildFastaIndex refuses such
+    a file, as htslib's fai_build does (tests/test_oracle_htslib_witness.py), so the index here is one that came with the file:
+    prep links a .fai it finds beside the genome without looking into it."""
     exe = build(tmp_path)
     seq = "ACGT" * 100
     fa = tmp_path / "r.fa"
+    ragged = ">ragged\n" + seq[:60] + "\n" + seq[60:130] + "\n" + seq[130:] + "\n"   # second line is 70 wide
     with open(fa, "w") as f:
-        f.write(">ragged\n" + seq[:60] + "\n" + seq[60:130] + "\n" + seq[130:] + "\n")   # second line is 70 wide
+        f.write(ragged)
         f.write(">blank\n" + seq[:60] + "\n" + seq[60:90] + " " + seq[91:120] + "\n" + seq[120:] + "\n")
     out = tmp_path / "out"
+    out.mkdir()
+    assert subprocess.run([exe, str(fa), str(out), "ragged", "blank"], stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL).returncode != 0
+    assert not os.path.exists(str(fa) + ".fai")                                      # the writer refused, and left nothing
+    out.rmdir()
+    with open(str(fa) + ".fai", "w") as f:  # a tool that looks at each record's first line only, and counts the blank as a base
+        f.write(f"ragged\t400\t{len('>ragged') + 1}\t60\t61\n")
+        f.write(f"blank\t400\t{len(ragged) + len('>blank') + 1}\t60\t61\n")
     out.mkdir()
     lines = [l for l in subprocess.check_output([exe, str(fa), str(out), "ragged", "blank"], text=True).split("\n") if l]
     seen = set()

@@ -82,7 +82,12 @@ def test_model_against_the_samtools_indexes(name):
     assert_same_where_it_counts(ours, theirs, im.build(p)[3])
 
 
-def assert_same_where_it_counts(ours, theirs, records):
+def assert_same_where_it_counts(ours, theirs, records, merged_bins=False):
+    """merged_bins: `theirs` comes straight from htslib's writer, which moves the chunks of a bin whose data lies within 64 KB of
+    the file into the bin's parent before it saves (compress_binning, deps/htslib-1.3/hts.c); the samtools-made fixtures are too
+    sparse for that to have happened.  Then a bin of ours may be found in its nearest ancestor that theirs holds -- which must hold
+    nothing else -- and each of our chunks must lie inside one chunk of that bin; where nothing was moved this is the equality
+    asked for without the flag."""
     assert len(ours) == len(theirs)
     touched = [set() for _ in ours]
     for tid, pos, end, _ in records:
@@ -90,7 +95,17 @@ def assert_same_where_it_counts(ours, theirs, records):
             touched[tid].update(range(pos >> 14, ((end - 1) >> 14) + 1))
     for t, ((b1, l1, _), (b2, l2, _)) in enumerate(zip(ours, theirs)):
         b2 = {b: c for b, c in b2.items() if b != 37450}  # the pseudo-bin
-        assert set(b1) == set(b2), t
+        if merged_bins:
+            def home(b):  # the nearest of b, its parent, its parent's parent ... that theirs holds
+                while b not in b2 and b > 0:
+                    b = (b - 1) >> 3
+                return b
+            assert {home(b) for b in b1} == set(b2), t
+            for b, chunks in b1.items():
+                for vs, ve in chunks:
+                    assert any(u <= vs and ve <= v for u, v in b2[home(b)]), (t, b, vs, ve)
+        else:
+            assert set(b1) == set(b2), t
         if b1:
             assert min(c[0][0] for c in b1.values()) == min(c[0][0] for c in b2.values()), t
         assert len(l1) == len(l2), t

@@ -1,9 +1,14 @@
-"""Pure-Python BAM / BGZF / BAI / FASTA helpers for tests (no htslib in the image).
+"""Pure-Python BAM / BGZF / BAI / FASTA helpers for tests.
 
 The reader feeds the CPU oracle; the writer builds prep directories
 (`portcullis.sorted.alignments.bam[.bai]`, `portcullis.genome.fa[.fai]`,
 names from src/prepare.hpp:114-140) for the product's own C++ BAM reader, so
 the two sides parse files with independent code.
+
+Both are held to the reference's own htslib-1.3 (oracle/_ref/hts_witness, see tests/hts_witness.py) by
+tests/test_oracle_htslib_witness.py: read_bam's fields, its XS rule and the record's end against sam_read1, bam_aux_get /
+bam_aux2A and bam_endpos; the files write_bam writes and its .bai against sam_index_build2 and sam_itr_queryi; write_fasta's
+.fai against fai_build.  The tests that use these helpers need no htslib: only that one module does.
 """
 import gzip
 import os
@@ -131,18 +136,31 @@ def _bgzf_block(payload, level=1):
 BGZF_EOF = bytes.fromhex("1f8b08040000000000ff0600424302001b0003000000000000000000")
 
 
+def bam_header(refs, header_text=None):
+    """The inflated bytes in front of the first record: magic, header text, reference table."""
+    if header_text is None:
+        header_text = "@HD\tVN:1.4\tSO:coordinate\n" + "".join(f"@SQ\tSN:{n}\tLN:{l}\n" for n, l in refs)
+    ht = header_text.encode()
+    out = bytearray(b"BAM\x01" + struct.pack("<i", len(ht)) + ht + struct.pack("<i", len(refs)))
+    for n, l in refs:
+        nb = n.encode() + b"\x00"
+        out += struct.pack("<i", len(nb)) + nb + struct.pack("<i", l)
+    return bytes(out)
+
+
+def write_bgzf(path, stream, block_size=0xFF00, level=1):
+    """An inflated stream as a BGZF file: a plain byte cut every block_size bytes, zlib members, the EOF block."""
+    with open(path, "wb") as f:
+        for u in range(0, len(stream), block_size):
+            f.write(_bgzf_block(bytes(stream[u:u + block_size]), level))
+        f.write(BGZF_EOF)
+
+
 def write_bam(path, refs, reads, block_size=0xFF00, header_text=None, write_index=True, level=1):
     """reads: dicts with tid,pos,cigar(str|array),seq(str|None),flag,mapq,xs,mtid,mpos,name,
     optionally aux (raw bytes appended).  Must already be coordinate sorted.
     Records may straddle BGZF blocks (block_size is a plain byte cut)."""
-    if header_text is None:
-        header_text = "@HD\tVN:1.4\tSO:coordinate\n" + "".join(f"@SQ\tSN:{n}\tLN:{l}\n" for n, l in refs)
-    ht = header_text.encode()
-    stream = bytearray()
-    stream += b"BAM\x01" + struct.pack("<i", len(ht)) + ht + struct.pack("<i", len(refs))
-    for n, l in refs:
-        nb = n.encode() + b"\x00"
-        stream += struct.pack("<i", len(nb)) + nb + struct.pack("<i", l)
+    stream = bytearray(bam_header(refs, header_text))
     starts = []  # (tid, pos, end, ustart)
     for k, r in enumerate(reads):
         cig = r["cigar"]
@@ -252,8 +270,11 @@ def bai_to_csi(bai_path, csi_path):
 
 
 def write_fasta(path, contigs, width=60, write_index=True):
-    """contigs: list of (name, sequence str/bytes)."""
+    """contigs: list of (name, sequence str/bytes).  The .fai is the one htslib's fai_build writes for the file
+    (tests/test_oracle_htslib_witness.py): the line columns are those of the record's first line, so a record shorter than
+    `width` has its own length there, and a record without bases repeats the record before it (-1 where there is none)."""
     fai = []
+    lb, lw = -1, -1
     with open(path, "wb") as f:
         for name, seq in contigs:
             if isinstance(seq, str):
@@ -262,7 +283,10 @@ def write_fasta(path, contigs, width=60, write_index=True):
             off = f.tell()
             for i in range(0, len(seq), width):
                 f.write(seq[i:i + width] + b"\n")
-            fai.append((name, len(seq), off, width, width + 1))
+            if len(seq):
+                lb = min(width, len(seq))
+                lw = lb + 1
+            fai.append((name, len(seq), off, lb, lw))
     if write_index:
         with open(path + ".fai", "w") as f:
             for name, ln, off, lb, lw in fai:
