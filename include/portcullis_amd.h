@@ -562,6 +562,46 @@ int pjb_index_piece(pjb_ctx *ctx, const uint8_t *comp, int64_t comp_bytes, int64
                     uint64_t *next_voffset);
 int pjb_index_end(pjb_ctx *ctx, pjb_index_result *out);
 
+/* ---- several coordinate-sorted files merged into one, target by target (`portcullis_amd prep --merge`) --------------
+ * What `samtools merge` does for the reference's prep (src/prepare.cc:154-195 shells out to it), for ONE target at a time and on
+ * the device: every file's share of the target is inflated and walked as by pjb_submit_bam, the records of all files are put in
+ * one order, gathered into one stream and deflated; only the finished BGZF members come back.
+ * The order: pos ascending; records of equal pos by the index of their file, then by their order inside the file.  (samtools
+ * also orders equal positions by strand; this does not, so the merge of ONE file is the identity on its record stream, and the
+ * merge of a stable split of a file is sorted(concatenation, key = pos) with a stable sort.)
+ *   pjb_bam_merge_begin  opens the merge of target `tid` (of pjb_set_refs) from `n_files` files; drops a merge that was open and
+ *                        the last result.
+ *   pjb_bam_merge_file   hands over file `file`'s share (0 <= file < n_files; each index at most once, in any order; a file
+ *                        that is not handed over contributes nothing): comp / comp_bytes / first_uoffset exactly as for
+ *                        pjb_submit_bam -- whole BGZF blocks from the block that holds the target's first record through (at
+ *                        least) the block that holds its last one, and that first record's offset in the first block's
+ *                        inflated bytes.  Records are taken until the first one whose refID is not `tid`, or the end of the
+ *                        data.  *n_records (optional): how many.
+ *   pjb_bam_merge_end    orders, gathers and deflates: the merged stream (per record its 4-byte block_size and its body) is cut
+ *                        every `block_bytes` bytes (as for pjb_deflate_bgzf: a multiple of 4, at most 0xff00), whatever the
+ *                        records' boundaries; every piece becomes one BGZF member, the last may be short, no EOF block is added.
+ *                        No records: no members.
+ * Errors: PJB_ERR_BGZF corrupt BGZF / DEFLATE / record data, a position outside the target (never a silent end of the run),
+ * data that ends inside one of the target's records; PJB_ERR_UNSORTED a record whose pos lies below its predecessor's in the
+ * same file -- the message names the file and the record's ordinal (0-based) among that file's records on the target;
+ * PJB_ERR_ARG bad arguments, or more than 2^32 - 256 records on the target; PJB_ERR_STATE calls out of order, or a file index
+ * handed over twice.  A failing call drops the merge: begin again.  The exception is PJB_ERR_NOMEM, which is retryable as
+ * elsewhere: the merge stays as it was before the call, the call can be repeated when memory has been freed.
+ * Device memory: the target's inflated bytes of all files, the merged stream and the deflate's scratch at once; the first two
+ * count as `staging` in pjb_memory_info, the rest as `scratch`.  Works on a PJB_FLAG_NO_CHAINS context (after pjb_set_refs).
+ * Threads: like pjb_bam_end, these calls belong to the thread that makes the context's other calls. */
+typedef struct pjb_bam_merge_result {
+    int64_t n_records;           /* records written for this target */
+    int64_t raw_bytes;           /* their inflated bytes (4-byte block_size + body each) */
+    int32_t n_members;           /* BGZF members: ceil(raw_bytes / block_bytes) */
+    const uint32_t *member_size; /* n_members lengths */
+    const uint8_t *members;      /* the members back to back; host memory owned by the context */
+    int64_t member_bytes;        /*   until the next pjb_bam_merge_begin / pjb_destroy */
+} pjb_bam_merge_result;
+int pjb_bam_merge_begin(pjb_ctx *ctx, int32_t tid, int32_t n_files);
+int pjb_bam_merge_file(pjb_ctx *ctx, int32_t file, const uint8_t *comp, int64_t comp_bytes, int32_t first_uoffset, int64_t *n_records);
+int pjb_bam_merge_end(pjb_ctx *ctx, int32_t block_bytes, pjb_bam_merge_result *out);
+
 /* ---- `portcullis filt` feature rows -------------------------------------------------------
  * ModelFeatures::setRow (lib/src/model_features.cc:161-212) for a list of junctions: the columns of VAR_NAMES +
  * JAD_NAMES (lib/include/portcullis/ml/model_features.hpp:45-60), i.e. the row getters, calcIntronScore

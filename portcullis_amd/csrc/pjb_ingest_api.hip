@@ -1,9 +1,11 @@
 // pjb_ingest_api.hip -- the part of the C ABI that takes file bytes: BGZF inflate / deflate on the device, BAM record boundaries and transcoding
-// (pjb_inflate_bgzf, pjb_deflate_bgzf, pjb_submit_bam, pjb_bam_*, pjb_index_*); kernels in pjb_ingest.hip.h, pjb_deflate.hip.h and pjb_index.hip.h.
+// (pjb_inflate_bgzf, pjb_deflate_bgzf, pjb_submit_bam, pjb_bam_*, pjb_index_*, pjb_bam_merge_*); kernels in pjb_ingest.hip.h, pjb_deflate.hip.h,
+// pjb_index.hip.h and pjb_merge.hip.h.
 #include "pjb_host.hip.h"
 #include "pjb_deflate.hip.h"
 #include "pjb_ingest.hip.h"
 #include "pjb_index.hip.h"
+#include "pjb_merge.hip.h"
 
 void ingest_kernel_attributes() { (void)hipFuncSetAttribute((const void *)bgzf_decode, hipFuncAttributeMaxDynamicSharedMemorySize, I3_LDS_BYTES); }
 int ingest_lds_bytes() { return I3_LDS_BYTES; }
@@ -201,29 +203,26 @@ extern "C" int pjb_inflate_bgzf(pjb_ctx *c, const uint8_t *comp, int64_t comp_by
 
 // BGZF deflate on the device (pjb_deflate.hip.h): at most DFL_LAUNCH_BLOCKS blocks per launch (1 GB of symbol scratch)
 constexpr int64_t DFL_LAUNCH_BLOCKS = 4096;
-extern "C" int pjb_deflate_bgzf(pjb_ctx *c, const uint8_t *in, int64_t n_bytes, int32_t block_bytes, uint8_t *out, int64_t out_cap, int64_t *out_bytes,
-                                uint32_t *member_size) {
-    if (!c || !out_bytes || n_bytes < 0 || (n_bytes && (!in || !out))) return fail(c, PJB_ERR_ARG, "deflate_bgzf: bad arguments");
-    if (block_bytes < 4 || block_bytes > (int32_t)DFL_IN_MAX || (block_bytes & 3))
-        return fail(c, PJB_ERR_ARG, "deflate_bgzf: block_bytes must be a multiple of 4 between 4 and %u", DFL_IN_MAX);
-    *out_bytes = 0;
-    if (n_bytes == 0) return PJB_OK;
-    HIP_TRY(c, hipSetDevice(c->cfg.device));
+// The launches of one deflate, whoever asks (pjb_deflate_bgzf: `host_in`, copied to b_dfl_in launch by launch; pjb_bam_merge_end: `dev_in`,
+// a stream that lies on the device already).  `n_bytes` are cut every `block_bytes`; for every launch `sink(b0, sizes, total, dst)` is
+// told the first block's number, the members' sizes and their sum, and says where in host memory the packed members go.
+template <typename Sink>
+static int deflate_launches(pjb_ctx *c, const uint8_t *host_in, const uint8_t *dev_in, int64_t n_bytes, int32_t block_bytes, Sink sink) {
     hipStream_t st = c->stream;
     const int64_t n_blocks = (n_bytes + block_bytes - 1) / block_bytes;
     int rc;
     std::vector<u32> sizes;
     std::vector<iu64> offs;
-    int64_t written = 0;
     for (int64_t b0 = 0; b0 < n_blocks; b0 += DFL_LAUNCH_BLOCKS) {
         const int64_t nb = std::min<int64_t>(DFL_LAUNCH_BLOCKS, n_blocks - b0);
         const int64_t in_off = b0 * block_bytes, in_len = std::min<int64_t>(n_bytes - in_off, nb * block_bytes);
-        if ((rc = ensure(c, c->b_dfl_in, (size_t)in_len + 64)) || (rc = ensure(c, c->b_dfl_sym, (size_t)nb * DFL_SYM_STRIDE * 4)) ||
+        if ((host_in && (rc = ensure(c, c->b_dfl_in, (size_t)in_len + 64))) || (rc = ensure(c, c->b_dfl_sym, (size_t)nb * DFL_SYM_STRIDE * 4)) ||
             (rc = ensure(c, c->b_dfl_slots, (size_t)nb * DFL_SLOT)) || (rc = ensure(c, c->b_dfl_size, (size_t)nb * 4)) ||
             (rc = ensure(c, c->b_dfl_off, (size_t)nb * 8)))
             return rc;
-        HIP_TRY(c, hipMemcpyAsync(c->b_dfl_in.p, in + in_off, (size_t)in_len, hipMemcpyHostToDevice, st));
-        LAUNCH(c, "bgzf_deflate", bgzf_deflate, dim3((unsigned)nb), dim3(64), (const uint8_t *)c->b_dfl_in.p, (iu64)in_len, (u32)block_bytes, (u32)nb,
+        if (host_in) HIP_TRY(c, hipMemcpyAsync(c->b_dfl_in.p, host_in + in_off, (size_t)in_len, hipMemcpyHostToDevice, st));
+        const uint8_t *d_in = host_in ? (const uint8_t *)c->b_dfl_in.p : dev_in + in_off;
+        LAUNCH(c, "bgzf_deflate", bgzf_deflate, dim3((unsigned)nb), dim3(64), d_in, (iu64)in_len, (u32)block_bytes, (u32)nb,
                (u32 *)c->b_dfl_sym.p, (uint8_t *)c->b_dfl_slots.p, (u32 *)c->b_dfl_size.p);
         sizes.resize((size_t)nb);
         HIP_TRY(c, hipMemcpyAsync(sizes.data(), c->b_dfl_size.p, (size_t)nb * 4, hipMemcpyDeviceToHost, st));
@@ -234,20 +233,39 @@ extern "C" int pjb_deflate_bgzf(pjb_ctx *c, const uint8_t *in, int64_t n_bytes, 
             if (sizes[(size_t)k] < 26 || sizes[(size_t)k] > 65536) return fail(c, PJB_ERR_STATE, "deflate_bgzf: block %lld came out with %u bytes", (long long)(b0 + k), sizes[(size_t)k]);
             offs[(size_t)k] = total;
             total += sizes[(size_t)k];
-            if (member_size) member_size[b0 + k] = sizes[(size_t)k];
         }
-        if (written + (int64_t)total > out_cap)
-            return fail(c, PJB_ERR_ARG, "deflate_bgzf: the output needs more than %lld bytes", (long long)out_cap);
+        uint8_t *dst = nullptr;
+        if ((rc = sink(b0, sizes, total, dst))) return rc;
         if ((rc = ensure(c, c->b_dfl_packed, (size_t)total + 64))) return rc;
         HIP_TRY(c, hipMemcpyAsync(c->b_dfl_off.p, offs.data(), (size_t)nb * 8, hipMemcpyHostToDevice, st));
         LAUNCH(c, "bgzf_pack", bgzf_pack, dim3((unsigned)nb), dim3(256), (const uint8_t *)c->b_dfl_slots.p, (const u32 *)c->b_dfl_size.p,
                (const iu64 *)c->b_dfl_off.p, (u32)nb, (uint8_t *)c->b_dfl_packed.p);
-        HIP_TRY(c, hipMemcpyAsync(out + written, c->b_dfl_packed.p, (size_t)total, hipMemcpyDeviceToHost, st));
+        HIP_TRY(c, hipMemcpyAsync(dst, c->b_dfl_packed.p, (size_t)total, hipMemcpyDeviceToHost, st));
         HIP_TRY(c, hipStreamSynchronize(st));
-        written += (int64_t)total;
     }
-    *out_bytes = written;
     if (c->ktime) ev_collect(c, MISC_POOL);
+    return PJB_OK;
+}
+
+extern "C" int pjb_deflate_bgzf(pjb_ctx *c, const uint8_t *in, int64_t n_bytes, int32_t block_bytes, uint8_t *out, int64_t out_cap, int64_t *out_bytes,
+                                uint32_t *member_size) {
+    if (!c || !out_bytes || n_bytes < 0 || (n_bytes && (!in || !out))) return fail(c, PJB_ERR_ARG, "deflate_bgzf: bad arguments");
+    if (block_bytes < 4 || block_bytes > (int32_t)DFL_IN_MAX || (block_bytes & 3))
+        return fail(c, PJB_ERR_ARG, "deflate_bgzf: block_bytes must be a multiple of 4 between 4 and %u", DFL_IN_MAX);
+    *out_bytes = 0;
+    if (n_bytes == 0) return PJB_OK;
+    HIP_TRY(c, hipSetDevice(c->cfg.device));
+    int64_t written = 0;
+    const int rc = deflate_launches(c, in, nullptr, n_bytes, block_bytes, [&](int64_t b0, const std::vector<u32> &sizes, iu64 total, uint8_t *&dst) {
+        if (member_size)
+            for (size_t k = 0; k < sizes.size(); k++) member_size[(size_t)b0 + k] = sizes[k];
+        if (written + (int64_t)total > out_cap) return fail(c, PJB_ERR_ARG, "deflate_bgzf: the output needs more than %lld bytes", (long long)out_cap);
+        dst = out + written;
+        written += (int64_t)total;
+        return (int)PJB_OK;
+    });
+    if (rc) return rc;
+    *out_bytes = written;
     return PJB_OK;
 }
 
@@ -610,8 +628,10 @@ static int stage_scan(pjb_ctx *c, BamStage &st, const uint8_t *p, int64_t p_at, 
 }
 
 static void index_clear(pjb_ctx *c);
+static void merge_clear(pjb_ctx *c);
 void bam_stage_clear(pjb_ctx *c) {
     index_clear(c);
+    merge_clear(c);
     for (auto &is : c->inf_streams)
         if (is) (void)hipStreamSynchronize(is);
     for (auto &kv : c->bam_stage) {
@@ -1069,5 +1089,236 @@ extern "C" int pjb_index_end(pjb_ctx *c, pjb_index_result *out) {
     out->chunks = x->r_chunks.data();
     out->lin_off = x->r_lin_off.data();
     out->lin = x->r_lin.data();
+    return PJB_OK;
+}
+
+
+// ---- several sorted files' records of one target as one stream (pjb_bam_merge_begin / _file / _end, see the header; kernels in pjb_merge.hip.h) ----
+struct MergeFile {
+    bool given = false;
+    size_t n = 0;       // its records on the target
+    Buf out;            // its inflated bytes, 64 zeroed bytes behind them
+    Buf key, size, src; // per record: pos | 4 + block_size | where it lies in `out`
+};
+struct MergeState {
+    bool active = false;
+    int32_t tid = -1;
+    std::vector<MergeFile> files;
+    SortU32 sort;                              // all files' keys, file after file, and what the passes need
+    Buf size, src;                             // all files' sizes and places
+    Buf dst, ctl, stream;                      // offsets in the merged stream | MG_CTL_* and the passes' record count | the merged stream
+    uint32_t h_n = 0;                          // (copied to the device asynchronously)
+    // the result
+    std::vector<uint32_t> r_size;
+    std::vector<uint8_t> r_members;
+};
+
+static void merge_file_release(pjb_ctx *c, MergeFile &f) {
+    for (Buf *b : {&f.out, &f.key, &f.size, &f.src}) release(c, *b);
+}
+static void merge_clear(pjb_ctx *c) {
+    MergeState *m = c->merge;
+    if (!m) return;
+    for (MergeFile &f : m->files) merge_file_release(c, f);
+    SortU32 &s = m->sort;
+    for (Buf *b : {&s.key[0], &s.key[1], &s.idx[0], &s.idx[1], &s.hist, &s.hist_part, &s.hist_scan, &s.bin_total, &m->size, &m->src, &m->dst, &m->ctl, &m->stream})
+        release(c, *b);
+    delete m;
+    c->merge = nullptr;
+}
+// what a failing call leaves: nothing to go on with, except after PJB_ERR_NOMEM (the call can be repeated)
+static int merge_leave(pjb_ctx *c, MergeState *m, int rc) {
+    if (rc && rc != PJB_ERR_NOMEM) {
+        (void)hipStreamSynchronize(c->stream);
+        m->active = false;
+    }
+    return rc;
+}
+
+extern "C" int pjb_bam_merge_begin(pjb_ctx *c, int32_t tid, int32_t n_files) {
+    if (!c) return PJB_ERR_ARG;
+    if (c->merge) c->merge->active = false;
+    if (tid < 0 || (size_t)tid >= c->ref_len.size() || n_files < 1) return fail(c, PJB_ERR_ARG, "bam_merge_begin: bad arguments (tid %d, %d files)", tid, n_files);
+    HIP_TRY(c, hipSetDevice(c->cfg.device));
+    if (!c->merge) c->merge = new (std::nothrow) MergeState();
+    MergeState *m = c->merge;
+    if (!m) return fail(c, PJB_ERR_NOMEM, "bam_merge_begin: out of host memory");
+    for (size_t k = (size_t)n_files; k < m->files.size(); k++) merge_file_release(c, m->files[k]);
+    m->files.resize((size_t)n_files);
+    for (MergeFile &f : m->files) {
+        f.given = false;
+        f.n = 0;
+    }
+    m->r_size.clear();
+    m->r_members.clear();
+    int rc = ensure(c, m->ctl, MG_CTL_WORDS * 8);
+    if (rc) return rc;
+    m->tid = tid;
+    m->active = true;
+    return PJB_OK;
+}
+
+static int merge_file_body(pjb_ctx *c, MergeState *m, int32_t file, const uint8_t *comp, int64_t comp_bytes, int32_t first_uoffset, int64_t *n_records) {
+    MergeFile &f = m->files[(size_t)file];
+    const int32_t tid = m->tid;
+    std::vector<InfBlock> blocks;
+    int64_t total = 0;
+    int rc = scan_bgzf(c, comp, comp_bytes, blocks, total);
+    if (rc) return rc;
+    if (total == 0 || (int64_t)first_uoffset >= total) {
+        f.given = true;
+        return PJB_OK;
+    }
+    hipStream_t st = c->stream;
+    if ((rc = ensure(c, c->b_inf_comp, (size_t)comp_bytes + INF_PAD))) return rc;
+    if ((rc = upload_host(c, c->b_inf_comp.p, comp, (size_t)comp_bytes))) return rc;
+    HIP_TRY(c, hipMemsetAsync((uint8_t *)c->b_inf_comp.p + comp_bytes, 0, INF_PAD, st));
+    if ((rc = ensure_cat(c, f.out, (size_t)total + 64, MEM_STAGING))) return rc;
+    HIP_TRY(c, hipMemsetAsync((uint8_t *)f.out.p + total, 0, 64, st));
+    if ((rc = inflate_on_device(c, (const uint8_t *)c->b_inf_comp.p, blocks, (uint8_t *)f.out.p))) return rc;
+    // the target's records: up to the first one of another target.  (The walk's other end test, a position past the target's end, is
+    // off: such a record is an error here, found by mg_keys.)
+    BamRegion R = bam_region(c, (const uint8_t *)f.out.p, total, first_uoffset, tid);
+    const int32_t ref_len = R.ref_len;
+    R.ref_len = INT32_MAX;
+    RecordWalk w;
+    if ((rc = walk_records(c, R, false, ("in file " + std::to_string(file) + " on target " + std::to_string(tid)).c_str(), w))) return rc;
+    if (w.end_seg == 0xffffffffu && w.cut_seg != 0xffffffffu) {
+        // The data ends inside a record and no record of another target was seen.  The walk asks for a record's 36 fixed bytes before it
+        // looks at it; a span that ends with the block in which the NEXT target begins may hold fewer of that target's first record.
+        // With its refID in reach (8 bytes) that record says itself whose it is.
+        const uint32_t n_seg = (uint32_t)(((iu64)total + BAM_SEG - 1) / BAM_SEG);
+        const iu64 *land = (const iu64 *)c->b_bam_seg.p + 2 * (size_t)n_seg; // (walk_records: seg_start | seg_base | land)
+        iu64 at = 0;
+        HIP_TRY(c, hipMemcpyAsync(&at, land + w.cut_seg, 8, hipMemcpyDeviceToHost, st));
+        HIP_TRY(c, hipStreamSynchronize(st));
+        int32_t head[2] = {0, tid};
+        if (at + 8 <= (iu64)total) HIP_TRY(c, hipMemcpy(head, (const uint8_t *)f.out.p + at, 8, hipMemcpyDeviceToHost));
+        if (head[1] == tid)
+            return fail(c, PJB_ERR_BGZF, "file %d: the data for target %d ends inside an alignment record (inflated offset %llu..): truncated "
+                                         "file, or the index's span for the target is too short", file, tid, (unsigned long long)at);
+    }
+    if (w.n >= 0xffffff00ull) return fail(c, PJB_ERR_ARG, "bam_merge_file: more than 2^32 alignments on one target are not supported");
+    const size_t n = w.n;
+    if (n) {
+        if ((rc = ensure(c, f.key, n * 4)) || (rc = ensure(c, f.size, n * 4)) || (rc = ensure(c, f.src, n * 8))) return rc;
+        iu64 *ctl = (iu64 *)m->ctl.p;
+        HIP_TRY(c, hipMemsetAsync(ctl, 0xff, MG_CTL_WORDS * 8, st));
+        LAUNCH(c, "mg_keys", mg_keys, dim3((unsigned)((n + 255) / 256)), dim3(256), (const uint8_t *)f.out.p, (const iu64 *)c->b_bam_rec.p, (iu64)n, ref_len,
+               (iu32 *)f.key.p, (iu32 *)f.size.p, (iu64 *)f.src.p, ctl);
+        iu64 h[MG_CTL_WORDS];
+        HIP_TRY(c, hipMemcpyAsync(h, ctl, sizeof h, hipMemcpyDeviceToHost, st));
+        HIP_TRY(c, hipStreamSynchronize(st));
+        if (c->ktime) ev_collect(c, MISC_POOL);
+        // the first offender decides
+        if (h[MG_CTL_BAD] != ~0ull && h[MG_CTL_BAD] <= h[MG_CTL_UNSORTED])
+            return fail(c, PJB_ERR_BGZF, "file %d: alignment record %llu on target %d has a position outside the target", file, (unsigned long long)h[MG_CTL_BAD], tid);
+        if (h[MG_CTL_UNSORTED] != ~0ull)
+            return fail(c, PJB_ERR_UNSORTED, "%s (file %d: alignment record %llu on target %d lies before its predecessor)", err_text(PJB_ERR_UNSORTED), file,
+                        (unsigned long long)h[MG_CTL_UNSORTED], tid);
+    }
+    f.n = n;
+    f.given = true;
+    if (n_records) *n_records = (int64_t)n;
+    return PJB_OK;
+}
+
+extern "C" int pjb_bam_merge_file(pjb_ctx *c, int32_t file, const uint8_t *comp, int64_t comp_bytes, int32_t first_uoffset, int64_t *n_records) {
+    if (!c) return PJB_ERR_ARG;
+    if (n_records) *n_records = 0;
+    MergeState *m = c->merge;
+    if (!m || !m->active) return fail(c, PJB_ERR_STATE, "bam_merge_file: no merge is open (pjb_bam_merge_begin)");
+    if (file < 0 || (size_t)file >= m->files.size() || comp_bytes < 0 || (comp_bytes && !comp) || first_uoffset < 0)
+        return merge_leave(c, m, fail(c, PJB_ERR_ARG, "bam_merge_file: bad arguments (file %d of %zu)", file, m->files.size()));
+    if (m->files[(size_t)file].given) return merge_leave(c, m, fail(c, PJB_ERR_STATE, "bam_merge_file: file %d was handed over already", file));
+    c->cur_tid = m->tid;
+    HIP_TRY(c, hipSetDevice(c->cfg.device));
+    return merge_leave(c, m, merge_file_body(c, m, file, comp, comp_bytes, first_uoffset, n_records));
+}
+
+static int merge_end_body(pjb_ctx *c, MergeState *m, int32_t block_bytes, pjb_bam_merge_result *out) {
+    hipStream_t st = c->stream;
+    int rc;
+    std::vector<MergeFile *> parts; // the files that have records, in file order
+    iu64 n64 = 0;
+    for (MergeFile &f : m->files)
+        if (f.given && f.n) {
+            parts.push_back(&f);
+            n64 += f.n;
+        }
+    if (n64 >= 0xffffff00ull) return fail(c, PJB_ERR_ARG, "bam_merge_end: more than 2^32 alignments on one target are not supported");
+    const size_t n = (size_t)n64;
+    if (n == 0) return PJB_OK;
+    iu64 *ctl = (iu64 *)m->ctl.p;
+    const iu32 *order = nullptr, *size = (const iu32 *)parts[0]->size.p;
+    const iu64 *src = (const iu64 *)parts[0]->src.p;
+    const int32_t ref_len = c->ref_len[(size_t)m->tid];
+    const int key_bits = ref_len > 1 ? bits_of((uint64_t)ref_len - 1) : 0;
+    if (parts.size() > 1) {
+        // one ordinal space, file after file
+        const size_t slack = n + RS_TILE; // (rs_scatter loads whole tiles unguarded)
+        if ((rc = ensure(c, m->sort.key[0], slack * 4)) || (rc = ensure(c, m->sort.key[1], slack * 4)) || (rc = ensure(c, m->sort.idx[0], slack * 4)) ||
+            (rc = ensure(c, m->sort.idx[1], slack * 4)) || (rc = ensure(c, m->size, n * 4)) || (rc = ensure(c, m->src, n * 8)))
+            return rc;
+        size_t at = 0;
+        for (MergeFile *f : parts) {
+            HIP_TRY(c, hipMemcpyAsync((iu32 *)m->sort.key[0].p + at, f->key.p, f->n * 4, hipMemcpyDeviceToDevice, st));
+            HIP_TRY(c, hipMemcpyAsync((iu32 *)m->size.p + at, f->size.p, f->n * 4, hipMemcpyDeviceToDevice, st));
+            HIP_TRY(c, hipMemcpyAsync((iu64 *)m->src.p + at, f->src.p, f->n * 8, hipMemcpyDeviceToDevice, st));
+            at += f->n;
+        }
+        size = (const iu32 *)m->size.p;
+        src = (const iu64 *)m->src.p;
+        if (key_bits > 0) { // (a target of one base: every key is 0, the ordinals are in order)
+            u32 *d_n = (u32 *)(ctl + MG_CTL_WORDS - 1);
+            m->h_n = (uint32_t)n;
+            HIP_TRY(c, hipMemcpyAsync(d_n, &m->h_n, 4, hipMemcpyHostToDevice, st));
+            int cur = 0;
+            if ((rc = sort_u32_pairs(c, m->sort, d_n, n, key_bits, &cur))) return rc;
+            order = (const iu32 *)m->sort.idx[cur].p;
+        }
+    }
+    // where every record goes, and how long the stream is
+    if ((rc = ensure(c, m->dst, n * 8))) return rc;
+    if ((rc = run_scan(c, "mg_off", MgSizeFn{size, order}, MgOffsetSink{(iu64 *)m->dst.p}, n, (u64 *)(ctl + MG_CTL_TOTAL)))) return rc;
+    iu64 raw = 0;
+    HIP_TRY(c, hipMemcpyAsync(&raw, ctl + MG_CTL_TOTAL, 8, hipMemcpyDeviceToHost, st));
+    HIP_TRY(c, hipStreamSynchronize(st));
+    if ((rc = ensure_cat(c, m->stream, (size_t)raw + 64, MEM_STAGING))) return rc;
+    LAUNCH(c, "mg_gather", mg_gather, dim3((unsigned)((n + 3) / 4)), dim3(256), src, size, order, (const iu64 *)m->dst.p, (iu64)n, (uint8_t *)m->stream.p);
+    rc = deflate_launches(c, nullptr, (const uint8_t *)m->stream.p, (int64_t)raw, block_bytes, [&](int64_t, const std::vector<u32> &sizes, iu64 total, uint8_t *&dst) {
+        const size_t had = m->r_members.size();
+        m->r_size.insert(m->r_size.end(), sizes.begin(), sizes.end());
+        m->r_members.resize(had + (size_t)total);
+        dst = m->r_members.data() + had;
+        return (int)PJB_OK;
+    });
+    if (rc) {
+        m->r_size.clear();
+        m->r_members.clear();
+        return rc;
+    }
+    out->n_records = (int64_t)n;
+    out->raw_bytes = (int64_t)raw;
+    return PJB_OK;
+}
+
+extern "C" int pjb_bam_merge_end(pjb_ctx *c, int32_t block_bytes, pjb_bam_merge_result *out) {
+    if (!c) return PJB_ERR_ARG;
+    MergeState *m = c->merge;
+    if (!m || !m->active) return fail(c, PJB_ERR_STATE, "bam_merge_end: no merge is open (pjb_bam_merge_begin)");
+    if (!out) return merge_leave(c, m, fail(c, PJB_ERR_ARG, "bam_merge_end: bad arguments"));
+    if (block_bytes < 4 || block_bytes > (int32_t)DFL_IN_MAX || (block_bytes & 3))
+        return merge_leave(c, m, fail(c, PJB_ERR_ARG, "bam_merge_end: block_bytes must be a multiple of 4 between 4 and %u", DFL_IN_MAX));
+    c->cur_tid = m->tid;
+    HIP_TRY(c, hipSetDevice(c->cfg.device));
+    memset(out, 0, sizeof *out);
+    const int rc = merge_leave(c, m, merge_end_body(c, m, block_bytes, out));
+    if (rc) return rc;
+    m->active = false;
+    out->n_members = (int32_t)m->r_size.size();
+    out->member_size = m->r_size.data();
+    out->members = m->r_members.data();
+    out->member_bytes = (int64_t)m->r_members.size();
     return PJB_OK;
 }

@@ -27,6 +27,7 @@ EXPORTS = [
     "pjb_select_timed_kernels", "pjb_host_alloc", "pjb_host_free", "pjb_host_register", "pjb_host_unregister", "pjb_inflate_bgzf", "pjb_deflate_bgzf", "pjb_submit_bam", "pjb_collect_device", "pjb_set_row_mirror",
     "pjb_extra_finish", "pjb_set_option", "pjb_merge_rows", "pjb_plan_groups", "pjb_bam_begin", "pjb_bam_piece", "pjb_bam_pieces_done", "pjb_bam_end", "pjb_bam_inflate_done", "pjb_filter_set_junctions", "pjb_filter_batch", "pjb_filt_features",
     "pjb_index_begin", "pjb_index_piece", "pjb_index_end",
+    "pjb_bam_merge_begin", "pjb_bam_merge_file", "pjb_bam_merge_end",
     "pjb_forest_check", "pjb_forest_load", "pjb_forest_predict", "pjb_filt_scores", "pjb_forest_grow", "pjb_knn",
     "pjb_markov_train",
     "pjb_memory_info",
@@ -91,6 +92,11 @@ class PjbTiming(C.Structure):
 
 class PjbIndexResult(C.Structure):
     _fields_ = [("n_records", C.c_int64), ("n_chunks", C.c_int64), ("chunks", C.c_void_p), ("lin_off", C.c_void_p), ("lin", C.c_void_p)]
+
+
+class PjbBamMergeResult(C.Structure):  # pjb_bam_merge_result
+    _fields_ = [("n_records", C.c_int64), ("raw_bytes", C.c_int64), ("n_members", C.c_int32), ("member_size", C.c_void_p), ("members", C.c_void_p),
+                ("member_bytes", C.c_int64)]
 
 
 class PjbMemory(C.Structure):  # pjb_memory
@@ -193,6 +199,9 @@ def load():
         L.pjb_index_begin.argtypes = [C.c_void_p]
         L.pjb_index_piece.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int32, C.c_int32, C.POINTER(C.c_uint64)]
         L.pjb_index_end.argtypes = [C.c_void_p, C.POINTER(PjbIndexResult)]
+        L.pjb_bam_merge_begin.argtypes = [C.c_void_p, C.c_int32, C.c_int32]
+        L.pjb_bam_merge_file.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_int64, C.c_int32, C.POINTER(C.c_int64)]
+        L.pjb_bam_merge_end.argtypes = [C.c_void_p, C.c_int32, C.POINTER(PjbBamMergeResult)]
         L.pjb_host_alloc.restype = C.c_void_p
         L.pjb_host_alloc.argtypes = [C.c_size_t]
         L.pjb_host_free.restype = None
@@ -685,6 +694,35 @@ class Context:
         out = self.index_end()
         out["next_voffsets"] = nvs
         return out
+
+    def bam_merge_begin(self, tid, n_files):
+        self._check(self._L.pjb_bam_merge_begin(self._h, tid, n_files))
+
+    def bam_merge_file(self, file, comp, first_uoffset):
+        """File `file`'s share of the target that bam_merge_begin named (pjb_bam_merge_file: BGZF bytes and the first record's offset,
+        as for submit_bam); returns the number of its records."""
+        comp = np.frombuffer(bytes(comp), dtype=np.uint8) if not isinstance(comp, np.ndarray) else comp
+        n = C.c_int64()
+        self._check(self._L.pjb_bam_merge_file(self._h, file, comp.ctypes.data_as(C.c_void_p), len(comp), first_uoffset, C.byref(n)))
+        return n.value
+
+    def bam_merge_end(self, block_bytes=0xff00):
+        """-> dict(n_records, raw_bytes, member_size [u32 per BGZF member], members [their bytes, back to back; copies])."""
+        r = PjbBamMergeResult()
+        self._check(self._L.pjb_bam_merge_end(self._h, block_bytes, C.byref(r)))
+        sizes = np.frombuffer((C.c_char * (4 * r.n_members)).from_address(r.member_size), dtype=np.uint32).copy() if r.n_members else np.zeros(0, np.uint32)
+        members = bytes((C.c_char * r.member_bytes).from_address(r.members)) if r.member_bytes else b""
+        return dict(n_records=r.n_records, raw_bytes=r.raw_bytes, member_size=sizes, members=members)
+
+    def bam_merge(self, tid, files, block_bytes=0xff00):
+        """Target `tid`'s records of several coordinate-sorted files as one stream of BGZF members: `files` holds, per file in
+        command-line order, (BGZF bytes, first record's offset) or None for a file without a record on the target.  Ties in pos
+        go to the earlier file, then to the order inside the file.  Returns bam_merge_end()'s dict."""
+        self.bam_merge_begin(tid, len(files))
+        for k, f in enumerate(files):
+            if f is not None:
+                self.bam_merge_file(k, f[0], f[1])
+        return self.bam_merge_end(block_bytes)
 
     def inflate_bgzf(self, comp):
         """Inflate a run of whole BGZF blocks (bytes-like) on the device; returns the inflated bytes."""

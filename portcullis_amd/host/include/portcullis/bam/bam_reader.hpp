@@ -127,6 +127,9 @@ public:
     // block_size + body).  false at the end of the file.
     void rewind();
     bool nextRecord(std::vector<uint8_t>& rec);
+    // Puts nextRecord() just behind the file's last placed record -- the largest chunk end the index names; behind the header if it
+    // names none --: what follows are the unplaced records (refID -1), which no index covers (prep --merge carries them over).
+    void seekUnplacedTail();
     const std::vector<RefSeq>& getTargets() const { return targets; }
 
     // Same visit as setRegion(tid) + nextBatch(...) but with `nthreads` workers inside the target:

@@ -2,8 +2,10 @@
 // src/prepare.hpp:147-230 and src/prepare.cc:89-332, 373-): the genome and its .fai, the coordinate-sorted BAM and its .bai,
 // linked or copied under the names of PreparedFiles.  Where the reference shells out to `samtools index`
 // (Prepare::bamIndex, src/prepare.cc:227-260) the index is built on the device: pjb_index_begin / _piece / _end over the
-// file's BGZF blocks, read through a ring of page-locked pieces.  Sorting and merging BAM files (bamSort / bamMerge,
-// src/prepare.cc:140-226) and CSI output are not built: such input is refused with a message that says what to do instead.
+// file's BGZF blocks, read through a ring of page-locked pieces.  With --merge several coordinate-sorted BAM files are merged into
+// the directory's one on the device (bamMerge, src/prepare.cc:154-195: pjb_bam_merge_*, a target at a time); without the flag a
+// second file is refused.  Sorting BAM files (bamSort, src/prepare.cc:140-153) and CSI output are not built: such input is refused
+// with a message that says what to do instead.
 #pragma once
 
 #include <cstdint>
@@ -24,12 +26,17 @@ class Prepare {
     uint16_t threads = DEFAULT_PREP_THREADS;
     bool useCsi = false;
     bool verbose = false;
+    bool merge = false;
 
     // link or copy `from` to `to` unless `to` is there already (src/prepare.cc:98-128); true if `to` exists afterwards
     bool copy(const std::string& from, const std::string& to, const std::string& msg, bool requireInputFileExists);
     bool genomeIndex();
     bool bamIndex(bool indexCopied);
     void buildIndexOnDevice(const std::string& bamFile, const std::string& baiFile);
+    // --merge: the header of the merged file (the inputs' headers checked against each other: portcullis/merge_header.hpp), and the
+    // merge itself -- every input's share of a target through pjb_bam_merge_*, target after target, then the unplaced tails
+    std::string mergedHeaderText(const std::vector<std::string>& bamFiles);
+    void mergeBams(const std::vector<std::string>& bamFiles, const std::string& headerText);
 
 public:
     explicit Prepare(const std::string& outputDir);
@@ -39,6 +46,7 @@ public:
     void setUseCsi(bool v) { useCsi = v; }
     void setThreads(uint16_t v) { threads = v; }
     void setVerbose(bool v) { verbose = v; }
+    void setMerge(bool v) { merge = v; }
     const PreparedFiles& getOutput() const { return output; }
 
     // removes what a previous run left in the directory (PreparedFiles::clean, src/prepare.cc:77-86)
@@ -48,7 +56,8 @@ public:
     static std::string title() { return "Portcullis Prepare Mode Help"; }
     static std::string description() {
         return "Prepares a genome and a coordinate-sorted BAM file for the junction analysis: links (or copies) both into the\n"
-               "output directory and indexes them.  A BAM index that is missing is built on the GPU.";
+               "output directory and indexes them.  A BAM index that is missing is built on the GPU.  With --merge several\n"
+               "coordinate-sorted BAM files are merged into one on the GPU first.";
     }
     static std::string usage() { return "portcullis_amd prep [options] <genome-file> <bam-file>"; }
     static int main(int argc, char* argv[]);

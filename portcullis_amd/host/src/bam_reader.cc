@@ -203,6 +203,13 @@ void BamReader::rewind() {
     regionDone = true;
 }
 
+void BamReader::seekUnplacedTail() {
+    uint64_t v = 0;
+    for (uint64_t e : lastOffset) v = std::max(v, e);
+    bgzf.seek(v ? v : firstRecordVoffset);
+    regionDone = true;
+}
+
 bool BamReader::nextRecord(std::vector<uint8_t>& out) {
     uint8_t b4[4];
     const size_t got = bgzf.read(b4, 4);

@@ -40,7 +40,8 @@ string Full::helpMessage() {
            "  --force                          Whether or not to clean the output directory before processing, thereby forcing full preparation of the genome and bam files.  By default portcullis will only do what it thinks it needs to.\n"
            "  --copy                           Whether to copy files from input data to prepared data where possible, otherwise will use symlinks.  Will require more time and disk space to prepare input but is potentially more robust.\n"
            "  --keep_temp                      Whether keep any temporary files created during the prepare stage of portcullis.  This might include BAM files and indexes.\n"
-           "  --use_csi                        Whether to use CSI indexing rather than BAI indexing (writing CSI is not built into prep: refused).\n\n"
+           "  --use_csi                        Whether to use CSI indexing rather than BAI indexing (writing CSI is not built into prep: refused).\n"
+           "  --merge                          Several coordinate-sorted BAM files may follow the genome: the prepare stage merges them into one on the GPU, as prep --merge does (ties in position go to the file given first).  Without it a second BAM file is refused.\n\n"
            "Analysis options:\n"
            "  --orientation arg (=UNKNOWN)     The orientation of the reads that produced the BAM alignments: \"F\" (Single-end forward orientation); \"R\" (single-end reverse orientation); \"FR\" (paired-end, with reads sequenced towards center of fragment -> <-.  This is usual setting for most Illumina paired end sequencing); \"RF\" (paired-end, reads sequenced away from center of fragment <- ->); \"FF\" (paired-end, reads both sequenced in forward orientation); \"RR\" (paired-end, reads both sequenced in reverse orientation); \"UNKNOWN\" (default, portcullis will workaround any calculations requiring orientation information)\n"
            "  --strandedness arg (=UNKNOWN)    Whether BAM alignments were generated using a type of strand specific RNAseq library: \"unstranded\" (Standard Illumina); \"firststrand\" (dUTP, NSR, NNSR); \"secondstrand\" (Ligation, Standard SOLiD, flux sim reads); \"UNKNOWN\" (default, portcullis will workaround any calculations requiring strandedness information)\n"
@@ -55,7 +56,7 @@ string Full::helpMessage() {
            "  --save_bad                       Saves bad junctions (i.e. junctions that fail the filter), as well as good junctions (those that pass)\n"
            "  --save_models                    Also save 3-filt/portcullis_filtered.selftrain.models: the L95 and the Markov models self-training trains, as filt --save_models\n"
            "  --training_rule arg (=balanced)  Pre-set to use for the self-training. Currently supported: balanced, precise. Default: balanced.\n\n"
-           "Not built (refused, as in prep and filt): merging or sorting BAM files, CSI output, --genuine, a default data directory\n";
+           "Not built (refused, as in prep and filt): sorting BAM files, CSI output, --genuine, a default data directory\n";
 }
 
 namespace {
@@ -68,7 +69,7 @@ int Full::main(int argc, char* argv[]) {
     string selfTrainDir, trainingRule = "balanced";
     int threads = 1, devices = 0;
     uint64_t deviceMem = 0;
-    bool separate = false, extra = false, copy = false, keepTemp = false, force = false, useCsi = false, saveBad = false, exongff = false,
+    bool separate = false, extra = false, copy = false, keepTemp = false, force = false, useCsi = false, merge = false, saveBad = false, exongff = false,
          introngff = false, bamFilter = false, saveLayers = false, saveFeatures = false, saveModels = false, verbose = false, help = false;
     uint32_t maxLength = 0, minCov = 1;
     // long options take their value as the next argument or after '=' (as in filt)
@@ -99,6 +100,7 @@ int Full::main(int argc, char* argv[]) {
         else if (a == "--copy") copy = true;
         else if (a == "--keep_temp") keepTemp = true;
         else if (a == "--use_csi") useCsi = true;
+        else if (a == "--merge") merge = true;
         else if (a == "--orientation") ori = need();
         else if (a == "--strandedness") strand = need();
         else if (a == "--separate") separate = true;
@@ -149,6 +151,7 @@ int Full::main(int argc, char* argv[]) {
     prep.setForce(force);
     prep.setUseLinks(!copy);
     prep.setUseCsi(useCsi);
+    prep.setMerge(merge);
     prep.setThreads((uint16_t)std::max(1, threads));
     prep.setVerbose(verbose);
     prep.prepare(bamFiles, genomeFile);

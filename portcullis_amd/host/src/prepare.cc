@@ -1,7 +1,10 @@
 // Prepare (`portcullis_amd prep`): see prepare.hpp.  Mirrors src/prepare.cc:89-332 (Prepare::copy, genomeIndex, bamIndex,
-// prepare) and 373- (Prepare::main) of the reference; the BAM index is built on the device instead of by `samtools index`.
+// prepare) and 373- (Prepare::main) of the reference; the BAM index is built on the device instead of by `samtools index`, and
+// --merge (src/prepare.cc:154-195, `samtools merge`) merges coordinate-sorted inputs on the device, target by target.
 #include <portcullis/bam/bam_writer.hpp>
+#include <portcullis/bam/bam_reader.hpp>
 #include <portcullis/bam/genome_mapper.hpp>
+#include <portcullis/merge_header.hpp>
 #include <portcullis/prepare.hpp>
 
 #include <fcntl.h>
@@ -19,6 +22,7 @@
 #include <deque>
 #include <fstream>
 #include <iostream>
+#include <memory>
 #include <mutex>
 #include <thread>
 
@@ -74,6 +78,7 @@ size_t bgzfBlockSize(const uint8_t* p, size_t n, int64_t fileOffset) {
 
 // What the indexer needs of a BAM file's header: the targets, and where the first alignment record starts.
 struct BamHead {
+    string text;  // the SAM header text
     std::vector<string> names;
     std::vector<int32_t> lens;
     int64_t firstBlock = 0;  // file offset of the block that holds the first record's first byte (or follows the header)
@@ -126,6 +131,7 @@ BamHead readBamHead(const string& bamFile) {
     p += 4;
     if (nRef < 0) throw PrepareException("Corrupt BAM header: " + bamFile);
     BamHead H;
+    H.text.assign((const char*)&head[8], (size_t)lText);
     for (int32_t t = 0; t < nRef; t++) {
         need(p + 4);
         const int32_t lName = rd32(p);
@@ -318,16 +324,27 @@ bool Prepare::bamIndex(bool indexCopied) {
     return lexists(indexFile);
 }
 
-void Prepare::buildIndexOnDevice(const string& bamFile, const string& baiFile) {
+namespace {
+
+const char* const NO_DEVICE_INDEX =
+    "No MI355X (HIP device) is visible: the BAM index is built on the GPU and has no CPU fallback.  Put an index made elsewhere "
+    "(samtools index) beside the BAM file, or run prep where the GPU is.";
+
+// The index of a coordinate-sorted BAM file, built on the device ...
+struct BuiltIndex {
+    bam::BaiBins bins;
+    bam::BaiLinear lin;
+    int64_t records = 0, chunks = 0;
+};
+// (nameFile: the refusal of an unsorted file says which file -- prep --merge has several)
+BuiltIndex buildIndex(const string& bamFile, bool nameFile) {
     const BamHead H = readBamHead(bamFile);
     for (size_t t = 0; t < H.lens.size(); t++)
         if ((int64_t)H.lens[t] >= BAI_MAX_TARGET)
             throw PrepareException("BAI cannot index this target: " + H.names[t] + " has " + std::to_string(H.lens[t]) +
                                    " bases, and a BAI index reaches 2^29.  Index the file with `samtools index -c` and use the CSI index (junc --use_csi): writing "
                                    "CSI is not built into portcullis_amd prep.");
-    if (pjb_device_count() <= 0)
-        throw PrepareException("No MI355X (HIP device) is visible: the BAM index is built on the GPU and has no CPU fallback.  Put an index made elsewhere "
-                               "(samtools index) beside the BAM file, or run prep where the GPU is.");
+    if (pjb_device_count() <= 0) throw PrepareException(NO_DEVICE_INDEX);
     struct Ctx {
         pjb_ctx* c = nullptr;
         ~Ctx() {
@@ -343,7 +360,8 @@ void Prepare::buildIndexOnDevice(const string& bamFile, const string& baiFile) {
         if (rc == PJB_OK) return;
         const string msg = pjb_last_error(ctx.c);
         if (rc == PJB_ERR_UNSORTED)
-            throw PrepareException("The BAM file is not in coordinate order: " + msg + ".  Sort it first (samtools sort): sorting is not built into portcullis_amd prep.");
+            throw PrepareException("The BAM file is not in coordinate order: " + msg + ".  Sort it first (samtools sort): sorting is not built into portcullis_amd prep." +
+                                   (nameFile ? "  (" + bamFile + ")" : string()));
         if (rc == PJB_ERR_ARG && msg.find("BAI cannot index") != string::npos)
             throw PrepareException(msg + ".  Index the file with `samtools index -c` and use the CSI index (junc --use_csi).");
         throw PrepareException(string(what) + ": " + msg);
@@ -430,17 +448,254 @@ void Prepare::buildIndexOnDevice(const string& bamFile, const string& baiFile) {
     check(pjb_index_end(ctx.c, &res), "pjb_index_end");
     // the chunk list is ordered by (target, bin, file order): the maps below only group it
     const size_t nRef = H.lens.size();
-    bam::BaiBins bins(nRef);
-    bam::BaiLinear lin(nRef);
+    BuiltIndex X;
+    X.bins.resize(nRef);
+    X.lin.resize(nRef);
     for (int64_t k = 0; k < res.n_chunks; k++) {
         const pjb_index_chunk& ch = res.chunks[k];
-        bins[(size_t)ch.tid][ch.bin].push_back({ch.vbeg, ch.vend});
+        X.bins[(size_t)ch.tid][ch.bin].push_back({ch.vbeg, ch.vend});
     }
-    for (size_t t = 0; t < nRef; t++) lin[t].assign(res.lin + res.lin_off[t], res.lin + res.lin_off[t + 1]);
+    for (size_t t = 0; t < nRef; t++) X.lin[t].assign(res.lin + res.lin_off[t], res.lin + res.lin_off[t + 1]);
+    X.records = res.n_records;
+    X.chunks = res.n_chunks;
+    return X;
+}
+
+// ... and written as a .bai
+void writeIndex(const BuiltIndex& X, const string& baiFile) {
     const string tmp = baiFile + ".tmp";
-    bam::writeBai(tmp, bins, lin);
+    bam::writeBai(tmp, X.bins, X.lin);
     if (rename(tmp.c_str(), baiFile.c_str()) != 0) throw PrepareException("Could not write BAM index: " + baiFile);
-    if (verbose) cout << endl << "Indexed " << res.n_records << " alignment records: " << res.n_chunks << " chunks." << endl;
+}
+
+}  // namespace
+
+void Prepare::buildIndexOnDevice(const string& bamFile, const string& baiFile) {
+    const BuiltIndex X = buildIndex(bamFile, false);
+    writeIndex(X, baiFile);
+    if (verbose) cout << endl << "Indexed " << X.records << " alignment records: " << X.chunks << " chunks." << endl;
+}
+
+// ---- prep --merge: several coordinate-sorted files into the prepared directory's one, target by target on the device ----------------
+namespace {
+
+struct Unlinker {  // the merge's temporary files: gone when it ends, however it ends
+    std::vector<string> paths;
+    ~Unlinker() {
+        for (const string& p : paths) unlink(p.c_str());
+    }
+};
+void writeAll(FILE* f, const void* p, size_t n, const string& path) {
+    if (n && fwrite(p, 1, n, f) != n) throw PrepareException("Could not write to " + path);
+}
+void put32(std::vector<uint8_t>& v, int32_t x) {
+    for (int k = 0; k < 4; k++) v.push_back((uint8_t)((uint32_t)x >> (8 * k)));
+}
+// the size of the whole BGZF block at `off` of a file (0: there is none, or it is not a plain one)
+size_t followingBlock(const string& path, uint64_t off) {
+    FILE* f = fopen(path.c_str(), "rb");
+    if (!f) return 0;
+    uint8_t h[18];
+    struct stat st;
+    size_t bs = 0;
+    if (fstat(fileno(f), &st) == 0 && fseeko(f, (off_t)off, SEEK_SET) == 0 && fread(h, 1, 18, f) == 18 && h[0] == 31 && h[1] == 139 && h[2] == 8 && (h[3] & 4) &&
+        h[10] == 6 && h[11] == 0 && h[12] == 'B' && h[13] == 'C')
+        bs = (size_t)(h[16] | (size_t)h[17] << 8) + 1;
+    fclose(f);
+    return bs && off + bs <= (uint64_t)st.st_size ? bs : 0;
+}
+const uint8_t BGZF_EOF_BLOCK[28] = {0x1f, 0x8b, 8, 4, 0, 0, 0, 0, 0, 0xff, 6, 0, 'B', 'C', 2, 0, 0x1b, 0, 3, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+
+}  // namespace
+
+string Prepare::mergedHeaderText(const std::vector<string>& bamFiles) {
+    std::vector<BamHeaderInfo> heads;
+    for (const string& f : bamFiles) {
+        BamHead H = readBamHead(f);
+        heads.push_back(BamHeaderInfo{f, std::move(H.text), std::move(H.names), std::move(H.lens)});
+    }
+    try {
+        return mergeBamHeaders(heads);
+    } catch (const MergeHeaderException& e) {
+        throw PrepareException(e.what());
+    }
+}
+
+void Prepare::mergeBams(const std::vector<string>& bamFiles, const string& headerText) {
+    const string sorted = output.getSortedBamFilePath();
+    if (lexists(sorted)) {
+        cout << "Pre-merged BAM detected: " << sorted << endl;
+        return;
+    }
+    if (pjb_device_count() <= 0)
+        throw PrepareException("No MI355X (HIP device) is visible: the BAM files are merged on the GPU and there is no CPU fallback.  Merge them elsewhere (samtools "
+                               "merge) and pass the one coordinate-sorted file, or run prep where the GPU is.");
+    const double t0 = nowSeconds();
+    cout << "Merging " << bamFiles.size() << " BAM files on the GPU ... ";
+    cout.flush();
+    const size_t nFiles = bamFiles.size();
+    Unlinker temps;
+    // where each input's targets lie: the index beside it if there is one (trusted, as prep trusts one today), else one built on the device;
+    // either way it is found beside a link to the input, under the reference's temp names
+    std::vector<std::unique_ptr<bam::BamReader>> readers;
+    for (size_t k = 0; k < nFiles; k++) {
+        const string link = output.getPrepDir() + "/temp" + std::to_string(k) + ".bam", bai = link + ".bai";
+        char real[PATH_MAX];
+        if (!realpath(bamFiles[k].c_str(), real)) throw PrepareException("Could not resolve BAM file: " + bamFiles[k]);
+        unlink(link.c_str());  // (what a killed run left)
+        unlink(bai.c_str());
+        temps.paths.push_back(link);
+        temps.paths.push_back(bai);
+        if (symlink(real, link.c_str()) != 0) throw PrepareException("Could not create symlink from " + bamFiles[k] + " to " + link);
+        if (fileExists(bamFiles[k] + ".bai")) {
+            char realBai[PATH_MAX];
+            if (!realpath((bamFiles[k] + ".bai").c_str(), realBai) || symlink(realBai, bai.c_str()) != 0)
+                throw PrepareException("Could not create symlink from " + bamFiles[k] + ".bai to " + bai);
+        } else
+            writeIndex(buildIndex(bamFiles[k], true), bai);
+        readers.emplace_back(new bam::BamReader(link));
+        try {
+            readers.back()->open(false);
+        } catch (const std::exception& e) {
+            throw PrepareException("Could not open " + bamFiles[k] + " with its index: " + e.what());
+        }
+    }
+    const std::vector<bam::RefSeq>& targets = readers[0]->getTargets();
+    std::vector<int32_t> lens;
+    for (const bam::RefSeq& t : targets) lens.push_back(t.length);
+
+    struct Ctx {
+        pjb_ctx* c = nullptr;
+        ~Ctx() {
+            if (c) pjb_destroy(c);
+        }
+    } ctx;
+    pjb_config cfg;
+    memset(&cfg, 0, sizeof cfg);
+    cfg.abi_version = PJB_ABI_VERSION;
+    cfg.flags = PJB_FLAG_NO_CHAINS;
+    if (pjb_create(&ctx.c, &cfg) != PJB_OK) throw PrepareException(string("pjb_create: ") + pjb_last_error(nullptr));
+    auto check = [&](int rc, const char* what) {
+        if (rc != PJB_OK) throw PrepareException(string(what) + ": " + pjb_last_error(ctx.c));
+    };
+    check(pjb_set_refs(ctx.c, (int32_t)lens.size(), lens.data()), "pjb_set_refs");
+
+    const string tmp = sorted + ".tmp";
+    temps.paths.push_back(tmp);  // (renamed away when all went well: the unlink then finds nothing)
+    FILE* out = fopen(tmp.c_str(), "wb");
+    if (!out) throw PrepareException("Could not create " + tmp);
+    struct Closer {
+        FILE*& f;
+        ~Closer() {
+            if (f) fclose(f);
+        }
+    } closer{out};
+    const int32_t BLOCK = 0xff00;
+    std::vector<uint8_t> packed;
+    auto deflateToFile = [&](const std::vector<uint8_t>& raw) {  // host bytes -> BGZF members -> the file
+        if (raw.empty()) return;
+        packed.resize(((raw.size() + BLOCK - 1) / BLOCK) * 65536);
+        int64_t n = 0;
+        check(pjb_deflate_bgzf(ctx.c, raw.data(), (int64_t)raw.size(), BLOCK, packed.data(), (int64_t)packed.size(), &n, nullptr), "pjb_deflate_bgzf");
+        writeAll(out, packed.data(), (size_t)n, tmp);
+    };
+    {  // the header
+        std::vector<uint8_t> h = {'B', 'A', 'M', 1};
+        put32(h, (int32_t)headerText.size());
+        h.insert(h.end(), headerText.begin(), headerText.end());
+        put32(h, (int32_t)targets.size());
+        for (const bam::RefSeq& t : targets) {
+            put32(h, (int32_t)t.name.size() + 1);
+            h.insert(h.end(), t.name.begin(), t.name.end());
+            h.push_back(0);
+            put32(h, t.length);
+        }
+        deflateToFile(h);
+    }
+    // target by target, in index order: what the device holds at a time is one target's records of all files
+    std::vector<int64_t> perFile(nFiles, 0), unplacedPerFile(nFiles, 0);
+    int64_t written = 0;
+    for (size_t t = 0; t < targets.size(); t++) {
+        std::vector<size_t> with;
+        for (size_t k = 0; k < nFiles; k++)
+            if (readers[k]->hasAlignments((int32_t)t)) with.push_back(k);
+        if (with.empty()) continue;
+        check(pjb_bam_merge_begin(ctx.c, (int32_t)t, (int32_t)nFiles), "pjb_bam_merge_begin");
+        size_t targetBytes = 0;
+        auto tooLarge = [&](int rc) {  // (no windowing inside a target: one that does not fit ends the run)
+            if (rc != PJB_ERR_NOMEM) return;
+            pjb_memory m;
+            memset(&m, 0, sizeof m);
+            (void)pjb_memory_info(ctx.c, &m);
+            throw PrepareException("prep --merge: target " + targets[t].name + " does not fit the device memory this run may hold: its records of all files have to be there at "
+                                   "once (" + std::to_string(targetBytes) + " compressed bytes; " + pjb_last_error(ctx.c) + "; held " + std::to_string(m.held) + ", limit " +
+                                   (m.limit ? std::to_string(m.limit) + " bytes" : string("none: the device is full")) + ").  Merge the files elsewhere (samtools merge).");
+        };
+        for (size_t k : with) {
+            uint64_t fileOff = 0;
+            size_t bytes = 0;
+            uint32_t firstU = 0;
+            if (!readers[k]->regionSpan((int32_t)t, fileOff, bytes, firstU)) continue;
+            // The span ends with the block in which the next target's first record begins.  If only a few bytes of that record lie in
+            // it the device cannot tell whose it is: the block behind goes along (the device stops at the first foreign record).
+            bytes += followingBlock(bamFiles[k], fileOff + bytes);
+            uint8_t* buf = (uint8_t*)bam::bigAlloc(bytes);
+            if (!buf) throw PrepareException("Out of memory reading " + bamFiles[k]);
+            struct Free {
+                uint8_t* p;
+                ~Free() { bam::bigFree(p); }
+            } fr{buf};
+            readers[k]->readSpan(fileOff, bytes, buf, threads);
+            targetBytes += bytes;
+            int64_t n = 0;
+            const int rc = pjb_bam_merge_file(ctx.c, (int32_t)k, buf, (int64_t)bytes, (int32_t)firstU, &n);
+            tooLarge(rc);
+            if (rc == PJB_ERR_UNSORTED)
+                throw PrepareException(string("The BAM file is not in coordinate order: ") + pjb_last_error(ctx.c) + ".  Sort it first (samtools sort): sorting is not built "
+                                       "into portcullis_amd prep.  (" + bamFiles[k] + ")");
+            if (rc != PJB_OK) throw PrepareException("pjb_bam_merge_file (" + bamFiles[k] + "): " + pjb_last_error(ctx.c));
+            perFile[k] += n;
+        }
+        pjb_bam_merge_result res;
+        const int rc = pjb_bam_merge_end(ctx.c, BLOCK, &res);
+        tooLarge(rc);
+        check(rc, "pjb_bam_merge_end");
+        writeAll(out, res.members, (size_t)res.member_bytes, tmp);
+        written += res.n_records;
+    }
+    // the unplaced records behind each file's last placed one, file by file: carried over (bamfilt copies them, as the reference's does)
+    const size_t PIECE = (size_t)64 << 20;
+    for (size_t k = 0; k < nFiles; k++) {
+        std::vector<uint8_t> raw, rec;
+        readers[k]->seekUnplacedTail();
+        while (readers[k]->nextRecord(rec)) {
+            const int32_t refID = (int32_t)((uint32_t)rec[4] | (uint32_t)rec[5] << 8 | (uint32_t)rec[6] << 16 | (uint32_t)rec[7] << 24);
+            if (refID >= 0)
+                throw PrepareException("A placed alignment record follows the last one the index of " + bamFiles[k] + " names: the index does not belong to the file");
+            raw.insert(raw.end(), rec.begin(), rec.end());
+            unplacedPerFile[k]++;
+            if (raw.size() >= PIECE) {  // (a multiple of the block size per piece would save a short member; records do not care)
+                deflateToFile(raw);
+                raw.clear();
+            }
+        }
+        deflateToFile(raw);
+    }
+    writeAll(out, BGZF_EOF_BLOCK, sizeof BGZF_EOF_BLOCK, tmp);
+    FILE* f = out;
+    out = nullptr;
+    if (fclose(f) != 0) throw PrepareException("Could not write to " + tmp);
+    if (rename(tmp.c_str(), sorted.c_str()) != 0) throw PrepareException("Could not write merged BAM file: " + sorted);
+    cout << "done." << endl << "Merged BAM file created at: " << sorted << endl;
+    if (verbose) {
+        int64_t unplaced = 0;
+        for (size_t k = 0; k < nFiles; k++) {
+            cout << " - " << bamFiles[k] << ": " << perFile[k] << " placed alignment records, " << unplacedPerFile[k] << " unplaced" << endl;
+            unplaced += unplacedPerFile[k];
+        }
+        cout << " - written: " << written + unplaced << " alignment records, " << unplaced << " of them unplaced" << endl;
+    }
+    printf(" - BAM Merge - Wall time taken: %.1fs\n\n", nowSeconds() - t0);
 }
 
 void Prepare::prepare(const std::vector<string>& bamFiles, const string& genomeFile) {
@@ -448,10 +703,14 @@ void Prepare::prepare(const std::vector<string>& bamFiles, const string& genomeF
         throw PrepareException("Writing CSI indexes is not built into portcullis_amd prep.  Build the directory without --use_csi (a BAI index covers targets "
                                "below 2^29 bases), or put a CSI index made with `samtools index -c` beside the BAM file and link the files by hand.");
     if (bamFiles.empty()) throw PrepareException("No BAM files to process");
-    if (bamFiles.size() > 1)
+    if (bamFiles.size() > 1 && !merge)
         throw PrepareException("More than one BAM file was given, and merging is not built into portcullis_amd prep.  Merge them first (samtools merge) and "
                                "pass the one coordinate-sorted file.");
-    if (!fileExists(bamFiles[0])) throw PrepareException("Could not find BAM file at: " + bamFiles[0]);
+    for (const string& b : bamFiles)
+        if (!fileExists(b)) throw PrepareException("Could not find BAM file at: " + b);
+    // --merge with several files: what their headers refuse is refused before a file is written or a device opened
+    const bool merging = bamFiles.size() > 1;
+    const string mergedText = merging ? mergedHeaderText(bamFiles) : string();
     if (force) {
         cout << "Cleaning output dir " << output.getPrepDir() << " ... ";
         cout.flush();
@@ -461,6 +720,12 @@ void Prepare::prepare(const std::vector<string>& bamFiles, const string& genomeF
     if (!copy(genomeFile, output.getGenomeFilePath(), "genome", true)) throw PrepareException("Could not copy/symlink genome file to: " + output.getGenomeFilePath());
     copy(genomeFile + ".fai", output.getGenomeIndexFilePath(), "genome index", false);
     if (!genomeIndex()) throw PrepareException("Could not create genome index");
+    if (merging) {
+        // the result is a regular file under the sorted BAM's name; its index is then built like any input's (a second inflate of the output)
+        mergeBams(bamFiles, mergedText);
+        if (!bamIndex(false)) throw PrepareException("Failed to index: " + output.getSortedBamFilePath());
+        return;
+    }
     if (!copy(bamFiles[0], output.getSortedBamFilePath(), "BAM", true)) throw PrepareException("Could not copy/symlink BAM file to: " + output.getSortedBamFilePath());
     // the index beside the input if there is one (src/prepare.cc:316), else it is built (no device is touched before this point)
     const bool indexCopied = copy(bamFiles[0] + ".bai", output.getBamIndexFilePath(false), "BAM index", false);
@@ -470,7 +735,7 @@ void Prepare::prepare(const std::vector<string>& bamFiles, const string& genomeF
 int Prepare::main(int argc, char* argv[]) {
     std::vector<string> positional;
     string outputDir = DEFAULT_PREP_OUTPUT_DIR;
-    bool force = false, copy = false, useCsi = false, verbose = false, help = false;
+    bool force = false, copy = false, useCsi = false, verbose = false, help = false, merge = false;
     int threads = DEFAULT_PREP_THREADS;
     auto need = [&](int& i) -> string {
         if (i + 1 >= argc) throw PrepareException(string("Missing value for option ") + argv[i]);
@@ -481,6 +746,7 @@ int Prepare::main(int argc, char* argv[]) {
         if (a == "-o" || a == "--output") outputDir = need(i);
         else if (a == "--force") force = true;
         else if (a == "--copy") copy = true;
+        else if (a == "--merge") merge = true;
         else if (a == "-c" || a == "--use_csi") useCsi = true;
         else if (a == "-t" || a == "--threads") threads = atoi(need(i).c_str());
         else if (a == "-v" || a == "--verbose") verbose = true;
@@ -493,8 +759,10 @@ int Prepare::main(int argc, char* argv[]) {
              << "  -o, --output <dir>   Output directory for prepared files (default " << DEFAULT_PREP_OUTPUT_DIR << ")" << endl
              << "      --force          Clean the output directory first, so that everything is prepared again" << endl
              << "      --copy           Copy the input files into the output directory instead of linking them" << endl
+             << "      --merge          Several coordinate-sorted BAM files may follow the genome: they are merged into one on the GPU" << endl
+             << "                       (ties in position go to the file given first; without the flag a second BAM file is refused)" << endl
              << "  -c, --use_csi        CSI instead of BAI indexing (not built: refused)" << endl
-             << "  -t, --threads <n>    Accepted for compatibility (the index is built on the GPU)" << endl
+             << "  -t, --threads <n>    Threads that read the BAM files for --merge (the index is built on the GPU)" << endl
              << "  -v, --verbose        Print extra information" << endl
              << "      --help           Produce this message" << endl;
         return help ? 0 : 1;
@@ -508,6 +776,7 @@ int Prepare::main(int argc, char* argv[]) {
     prep.setForce(force);
     prep.setUseLinks(!copy);
     prep.setUseCsi(useCsi);
+    prep.setMerge(merge);
     prep.setThreads((uint16_t)std::max(1, threads));
     prep.setVerbose(verbose);
     prep.prepare(bamFiles, genomeFile);
