@@ -602,6 +602,53 @@ int pjb_bam_merge_begin(pjb_ctx *ctx, int32_t tid, int32_t n_files);
 int pjb_bam_merge_file(pjb_ctx *ctx, int32_t file, const uint8_t *comp, int64_t comp_bytes, int32_t first_uoffset, int64_t *n_records);
 int pjb_bam_merge_end(pjb_ctx *ctx, int32_t block_bytes, pjb_bam_merge_result *out);
 
+/* ---- an unsorted file's records put in coordinate order, run by run (`portcullis_amd prep --sort`) --------------------
+ * What `samtools sort` does for the reference's prep (src/prepare.cc: Prepare::bamSort shells out to it), for one RUN at a time
+ * and on the device: a run is as much of the file, in file order, as the caller hands over between _begin and _end.  Its pieces
+ * are inflated and walked as by pjb_index_piece, every record gets one key, the keys are sorted with the passes the merge uses,
+ * the records are gathered into one stream and deflated; only the finished BGZF members come back.  A file that is one run is
+ * sorted by that; the runs of a longer file are merged afterwards (pjb_bam_merge_*: each run is a sorted file).
+ * The order: (refID as unsigned, pos) ascending, so unplaced records (refID -1) come last; records of equal key keep the order
+ * they were handed over in, unplaced records among themselves too.  It is sorted(records, key = (refID & 0xffffffff, pos)) with a
+ * stable sort -- the order pjb_bam_merge_* keeps.  (samtools also orders equal positions by strand; this does not.)
+ *   pjb_bam_sort_begin  opens a run over the targets of pjb_set_refs; drops a run that was open and the last result.
+ *   pjb_bam_sort_piece  a run of whole BGZF blocks, in file order (host memory, as for pjb_index_piece):
+ *                         first_uoffset : where the first record not yet taken starts in the piece's inflated bytes (the low 16
+ *                                         bits of the last call's *next_voffset; behind the BAM header for a file's first piece);
+ *                         last          : non-zero for the piece that ends the file.
+ *                       Every record that lies COMPLETELY inside the piece is taken.  *next_voffset receives where the first
+ *                       record that was not begins -- or the end of the data --, as (offset of its BGZF block IN THE PIECE) << 16 |
+ *                       offset in the block's inflated bytes: the next piece starts with that block.  *n_records (optional): how
+ *                       many were taken.  The piece's inflated bytes stay on the device until pjb_bam_sort_end.
+ *   pjb_bam_sort_end    orders the run's records, gathers them and deflates the stream, cut every `block_bytes` bytes as by
+ *                       pjb_bam_merge_end (a multiple of 4, at most 0xff00; the last member may be short; no EOF block; no
+ *                       records: no members).  A run whose records were in order already is not sorted (was_sorted = 1): its
+ *                       stream is the input's.
+ * Errors: PJB_ERR_BGZF corrupt BGZF / DEFLATE / record data, a refID outside [-1, n_refs), a placed record whose pos lies
+ * outside its target (the message names the record's ordinal in the run, 0-based; never a silent drop), data that ends inside
+ * a record when last != 0; PJB_ERR_ARG bad arguments, or 2^32 - 256 records or more in a run; PJB_ERR_STATE calls out of order.
+ * A failing call drops the run: begin again.  Two exceptions leave the run as it was before the call: a piece whose first
+ * record is longer than the piece fails with PJB_ERR_ARG and a message that says so and sets *next_voffset to that record -- the
+ * same blocks may be handed over again with more behind them --; and PJB_ERR_NOMEM, retryable as elsewhere: the caller may close
+ * the run (pjb_bam_sort_end) and hand the piece to a fresh one.
+ * Device memory: the run's inflated bytes, 36 to 44 bytes a record for keys, order, sizes, addresses and offsets, the sorted stream and the deflate's scratch; the
+ * inflated bytes and the stream count as `staging` in pjb_memory_info, the rest as `scratch`.  Works on a PJB_FLAG_NO_CHAINS
+ * context.  Threads: like pjb_bam_end, these calls belong to the thread that makes the context's other calls. */
+typedef struct pjb_bam_sort_result {
+    int64_t n_records;           /* records of the run, unplaced ones included */
+    int64_t raw_bytes;           /* their inflated bytes (4-byte block_size + body each) */
+    int32_t n_members;           /* BGZF members: ceil(raw_bytes / block_bytes) */
+    int32_t was_sorted;          /* 1: no record lay before its predecessor; the stream is the input's */
+    const uint32_t *member_size; /* n_members lengths */
+    const uint8_t *members;      /* the members back to back; host memory owned by the context */
+    int64_t member_bytes;        /*   until the next pjb_bam_sort_begin / pjb_destroy */
+    int64_t n_unplaced;          /* records with refID -1: the stream's tail */
+} pjb_bam_sort_result;
+int pjb_bam_sort_begin(pjb_ctx *ctx);
+int pjb_bam_sort_piece(pjb_ctx *ctx, const uint8_t *comp, int64_t comp_bytes, int32_t first_uoffset, int32_t last, uint64_t *next_voffset,
+                       int64_t *n_records);
+int pjb_bam_sort_end(pjb_ctx *ctx, int32_t block_bytes, pjb_bam_sort_result *out);
+
 /* ---- `portcullis filt` feature rows -------------------------------------------------------
  * ModelFeatures::setRow (lib/src/model_features.cc:161-212) for a list of junctions: the columns of VAR_NAMES +
  * JAD_NAMES (lib/include/portcullis/ml/model_features.hpp:45-60), i.e. the row getters, calcIntronScore

@@ -6,11 +6,13 @@
 #include "pjb_chain.hip.h"
 #include "pjb_flight.hip.h"
 
-// The sort passes for a caller in another unit (pjb_bam_merge_end: the non-template rs_* kernels live in this unit only).  Stable LSD
-// sort of (32-bit key, index) over the low `key_bits` bits: the keys lie in key[0], the first pass hands out the indices 0, 1, 2, ..;
-// returns 0 / 1: which of key[] / idx[] holds the result.  d_n: the count `n` on the device; key[] and idx[] have a sort tile of slack.
-int sort_u32_pairs(pjb_ctx *c, SortU32 &S, const u32 *d_n, size_t n, int key_bits, int *result) {
-    // passes of equal width, at most 11 bits (rs_scatter's LDS for 4-byte keys then stays under 64 KB and needs no attribute)
+// The sort passes for a caller in another unit (pjb_bam_merge_end, pjb_bam_sort_end: the non-template rs_* kernels live in this unit
+// only).  Stable LSD sort of (key of type K, index) over the low `key_bits` bits: the keys lie in key[0], the first pass hands out the
+// indices 0, 1, 2, ..; returns 0 / 1: which of key[] / idx[] holds the result.  d_n: the count `n` on the device; key[] and idx[] have a
+// sort tile of slack.
+template <typename K>
+static int sort_pairs(pjb_ctx *c, SortU32 &S, const u32 *d_n, size_t n, int key_bits, int *result) {
+    // passes of equal width, at most 11 bits (rs_scatter's LDS then stays under 64 KB for 4- and 8-byte keys and needs no attribute)
     const int n_pass = (key_bits + 10) / 11, bits = (key_bits + n_pass - 1) / n_pass;
     const u32 nb = 1u << bits, tiles = (u32)((n + RS_TILE - 1) / RS_TILE), n_panels = (tiles + RSP_TILES - 1) / RSP_TILES;
     int rc;
@@ -20,14 +22,16 @@ int sort_u32_pairs(pjb_ctx *c, SortU32 &S, const u32 *d_n, size_t n, int key_bit
     int cur = 0;
     for (int p = 0; p < n_pass; p++) {
         const int shift = p * bits;
-        const u32 *kin = (const u32 *)S.key[cur].p, *vin = p == 0 ? nullptr : (const u32 *)S.idx[cur].p;
-        u32 *kout = (u32 *)S.key[cur ^ 1].p, *vout = (u32 *)S.idx[cur ^ 1].p;
-        LAUNCH(c, rs_names[0], rs_hist<u32>, dim3(tiles), dim3(256), kin, d_n, shift, bits, (u32 *)S.hist.p, tiles);
+        const K *kin = (const K *)S.key[cur].p;
+        const u32 *vin = p == 0 ? nullptr : (const u32 *)S.idx[cur].p;
+        K *kout = (K *)S.key[cur ^ 1].p;
+        u32 *vout = (u32 *)S.idx[cur ^ 1].p;
+        LAUNCH(c, rs_names[0], rs_hist<K>, dim3(tiles), dim3(256), kin, d_n, shift, bits, (u32 *)S.hist.p, tiles);
         LAUNCH(c, rs_names[1], rs_panel_sums, dim3(n_panels, (nb + 255) / 256), dim3(256), (const u32 *)S.hist.p, tiles, nb, (u32 *)S.hist_part.p);
         LAUNCH(c, rs_names[2], rs_panel_scan, dim3(n_panels, (nb + 255) / 256), dim3(256), (const u32 *)S.hist.p, (const u32 *)S.hist_part.p, tiles, nb,
                (u32 *)S.hist_scan.p, (u32 *)S.bin_total.p);
 #define RS_SCATTER(B)                                                                                                                     \
-    LAUNCH_LDS(c, rs_names[3], (rs_scatter<B, u32>), dim3(tiles), dim3(256), rs_scatter_lds_bytes(bits, 4), kin, vin, kout, vout, d_n, \
+    LAUNCH_LDS(c, rs_names[3], (rs_scatter<B, K>), dim3(tiles), dim3(256), rs_scatter_lds_bytes(bits, sizeof(K)), kin, vin, kout, vout, d_n, \
                shift, bits, (const u32 *)S.hist_scan.p, (const u32 *)S.bin_total.p, tiles)
         switch (bits) { // the usual digit widths get an unrolled match loop
         case 9: RS_SCATTER(9); break;
@@ -41,6 +45,8 @@ int sort_u32_pairs(pjb_ctx *c, SortU32 &S, const u32 *d_n, size_t n, int key_bit
     *result = cur;
     return PJB_OK;
 }
+int sort_u32_pairs(pjb_ctx *c, SortU32 &S, const u32 *d_n, size_t n, int key_bits, int *result) { return sort_pairs<u32>(c, S, d_n, n, key_bits, result); }
+int sort_u64_pairs(pjb_ctx *c, SortU32 &S, const u32 *d_n, size_t n, int key_bits, int *result) { return sort_pairs<u64>(c, S, d_n, n, key_bits, result); }
 
 extern "C" {
 

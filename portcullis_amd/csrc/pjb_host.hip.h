@@ -335,6 +335,7 @@ struct pjb_ctx {
     Buf b_dfl_in, b_dfl_sym, b_dfl_slots, b_dfl_size, b_dfl_off, b_dfl_packed;           // device-side BGZF deflate
     Buf b_bam_seg, b_bam_rec, b_bam_ctl;                                  // device-side BAM record parse
     struct IndexState *index = nullptr;                                   // pjb_index_begin / _piece / _end (pjb_ingest_api.hip)
+    struct SortRun *sort_run = nullptr;                                   // pjb_bam_sort_begin / _piece / _end (pjb_ingest_api.hip)
     struct MergeState *merge = nullptr;                                   // pjb_bam_merge_begin / _file / _end (pjb_ingest_api.hip)
     // --extra
     bool extra = false;
@@ -912,10 +913,11 @@ inline int close_contig(pjb_ctx *c, int32_t tid) {
 // ---- defined in one unit, used by another
 int upload_staged(pjb_ctx *c, void *dst, const uint8_t *src, size_t bytes);                                   // pjb_ingest_api.hip (pageable bytes through the staging buffers)
 int upload_host(pjb_ctx *c, void *dst, const uint8_t *src, size_t bytes);                                     // pjb_ingest_api.hip (page-locked bytes: one DMA, else upload_staged)
-struct SortU32 { // the buffers of sort_u32_pairs: keys and indices ping-pong (a sort tile of slack each), the passes' counts
+struct SortU32 { // the buffers of sort_u32_pairs / sort_u64_pairs: keys and indices ping-pong (a sort tile of slack each), the passes' counts
     Buf key[2], idx[2], hist, hist_part, hist_scan, bin_total;
 };
-int sort_u32_pairs(pjb_ctx *c, SortU32 &S, const u32 *d_n, size_t n, int key_bits, int *result);             // pjb_api.hip (the rs_* passes over 32-bit keys: pjb_bam_merge_end)
+int sort_u32_pairs(pjb_ctx *c, SortU32 &S, const u32 *d_n, size_t n, int key_bits, int *result);             // pjb_api.hip (the rs_* passes over 32-bit keys: pjb_bam_merge_end, pjb_bam_sort_end)
+int sort_u64_pairs(pjb_ctx *c, SortU32 &S, const u32 *d_n, size_t n, int key_bits, int *result);             // pjb_api.hip (the same over 64-bit keys: pjb_bam_sort_end)
 void bam_stage_clear(pjb_ctx *c);                                                                              // pjb_ingest_api.hip (pjb_destroy)
 int extra_pre(pjb_ctx *c, Flight &f);                                                                          // pjb_extra_api.hip (the chain queues a target's extra metrics)
 int extra_contig(pjb_ctx *c, Flight &f, const pjb_region_result *res, u64 n_spliced, u32 P, u32 J, size_t row_base); // pjb_extra_api.hip (res: one per member)

@@ -1,5 +1,5 @@
 // pjb_ingest_api.hip -- the part of the C ABI that takes file bytes: BGZF inflate / deflate on the device, BAM record boundaries and transcoding
-// (pjb_inflate_bgzf, pjb_deflate_bgzf, pjb_submit_bam, pjb_bam_*, pjb_index_*, pjb_bam_merge_*); kernels in pjb_ingest.hip.h, pjb_deflate.hip.h,
+// (pjb_inflate_bgzf, pjb_deflate_bgzf, pjb_submit_bam, pjb_bam_*, pjb_index_*, pjb_bam_merge_*, pjb_bam_sort_*); kernels in pjb_ingest.hip.h, pjb_deflate.hip.h,
 // pjb_index.hip.h and pjb_merge.hip.h.
 #include "pjb_host.hip.h"
 #include "pjb_deflate.hip.h"
@@ -629,9 +629,11 @@ static int stage_scan(pjb_ctx *c, BamStage &st, const uint8_t *p, int64_t p_at, 
 
 static void index_clear(pjb_ctx *c);
 static void merge_clear(pjb_ctx *c);
+static void sort_clear(pjb_ctx *c);
 void bam_stage_clear(pjb_ctx *c) {
     index_clear(c);
     merge_clear(c);
+    sort_clear(c);
     for (auto &is : c->inf_streams)
         if (is) (void)hipStreamSynchronize(is);
     for (auto &kv : c->bam_stage) {
@@ -1320,5 +1322,278 @@ extern "C" int pjb_bam_merge_end(pjb_ctx *c, int32_t block_bytes, pjb_bam_merge_
     out->member_size = m->r_size.data();
     out->members = m->r_members.data();
     out->member_bytes = (int64_t)m->r_members.size();
+    return PJB_OK;
+}
+
+
+// ---- an unsorted file's records in coordinate order, run by run (pjb_bam_sort_begin / _piece / _end, see the header; sr_keys in pjb_merge.hip.h) ----
+struct SortRun {
+    bool active = false;
+    bool keep_on_error = false;      // the failing piece call left the run as it was
+    int pos_bits = 0, key_bits = 0;  // bits_of(longest target - 1) | + bits_of(n_ref): what the sort runs over
+    bool wide = false;               // key_bits > 32: 64-bit keys
+    size_t n = 0, cap = 0;           // records taken | room in sort.key[0], size, src
+    int64_t n_unplaced = 0;
+    iu64 prev = 0;                   // the key of the last record taken
+    iu64 descent = ~0ull;            // the first ordinal whose key lies below its predecessor's
+    bool ordered = false;            // pjb_bam_sort_end has run the passes: the order lies in sort.idx[order_in]
+    int order_in = 0;
+    std::vector<Buf> pieces;         // every piece's inflated bytes, 64 zeroed bytes behind them
+    SortU32 sort;                    // key[0]: the run's keys in input order
+    Buf size, src;                   // per record: 4 + block_size | where it lies in its piece
+    Buf ref_len, dst, ctl, stream;   // i32[n_ref] | offsets in the sorted stream | SR_CTL_* | the sorted stream
+    uint32_t h_n = 0;                // (copied to the device asynchronously)
+    // the result
+    std::vector<uint32_t> r_size;
+    std::vector<uint8_t> r_members;
+};
+
+static void sort_drop_pieces(pjb_ctx *c, SortRun *r) {
+    for (Buf &b : r->pieces) release(c, b);
+    r->pieces.clear();
+}
+static void sort_clear(pjb_ctx *c) {
+    SortRun *r = c->sort_run;
+    if (!r) return;
+    sort_drop_pieces(c, r);
+    SortU32 &s = r->sort;
+    for (Buf *b : {&s.key[0], &s.key[1], &s.idx[0], &s.idx[1], &s.hist, &s.hist_part, &s.hist_scan, &s.bin_total, &r->size, &r->src, &r->ref_len, &r->dst, &r->ctl, &r->stream})
+        release(c, *b);
+    delete r;
+    c->sort_run = nullptr;
+}
+// what a failing call leaves: nothing to go on with, except after PJB_ERR_NOMEM and a first record longer than its piece
+static int sort_leave(pjb_ctx *c, SortRun *r, int rc) {
+    if (rc && rc != PJB_ERR_NOMEM && !r->keep_on_error) {
+        (void)hipStreamSynchronize(c->stream);
+        r->active = false;
+        sort_drop_pieces(c, r);
+    }
+    return rc;
+}
+
+extern "C" int pjb_bam_sort_begin(pjb_ctx *c) {
+    if (!c) return PJB_ERR_ARG;
+    HIP_TRY(c, hipSetDevice(c->cfg.device));
+    if (!c->sort_run) c->sort_run = new (std::nothrow) SortRun();
+    SortRun *r = c->sort_run;
+    if (!r) return fail(c, PJB_ERR_NOMEM, "bam_sort_begin: out of host memory");
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    r->active = false;
+    sort_drop_pieces(c, r);
+    r->n = 0;
+    r->n_unplaced = 0;
+    r->prev = 0;
+    r->descent = ~0ull;
+    r->ordered = false;
+    r->r_size.clear();
+    r->r_members.clear();
+    const size_t n_ref = c->ref_len.size();
+    int32_t longest = 0;
+    for (int32_t len : c->ref_len) longest = std::max(longest, len);
+    r->pos_bits = longest > 1 ? bits_of((uint64_t)longest - 1) : 0;
+    r->key_bits = r->pos_bits + bits_of((uint64_t)n_ref);
+    const bool wide = r->key_bits > 32;
+    if (wide != r->wide) { // the keys' buffers are typed by what they hold
+        for (Buf *b : {&r->sort.key[0], &r->sort.key[1]}) release(c, *b);
+        r->cap = 0;
+        r->wide = wide;
+    }
+    int rc;
+    if ((rc = ensure(c, r->ctl, SR_CTL_WORDS * 8)) || (rc = ensure(c, r->ref_len, n_ref * 4 + 4))) return rc;
+    if (n_ref) HIP_TRY(c, hipMemcpy(r->ref_len.p, c->ref_len.data(), n_ref * 4, hipMemcpyHostToDevice));
+    r->active = true;
+    return PJB_OK;
+}
+
+// room for `need` records in the run's arrays: larger buffers take over what the arrays hold
+static int sort_grow(pjb_ctx *c, SortRun *r, size_t need) {
+    if (need <= r->cap && r->sort.key[0].p) return PJB_OK;
+    const size_t cap = std::max<size_t>(need + need / 2, (size_t)1 << 16), ksz = r->wide ? 8 : 4;
+    Buf nk, ns, nr;
+    int rc;
+    if ((rc = ensure(c, nk, (cap + RS_TILE) * ksz)) || (rc = ensure(c, ns, cap * 4)) || (rc = ensure(c, nr, cap * 8))) {
+        for (Buf *b : {&nk, &ns, &nr}) release(c, *b);
+        return rc;
+    }
+    hipStream_t st = c->stream;
+    if (r->n) {
+        HIP_TRY(c, hipMemcpyAsync(nk.p, r->sort.key[0].p, r->n * ksz, hipMemcpyDeviceToDevice, st));
+        HIP_TRY(c, hipMemcpyAsync(ns.p, r->size.p, r->n * 4, hipMemcpyDeviceToDevice, st));
+        HIP_TRY(c, hipMemcpyAsync(nr.p, r->src.p, r->n * 8, hipMemcpyDeviceToDevice, st));
+    }
+    for (Buf *b : {&r->sort.key[0], &r->size, &r->src})
+        if (b->p) bury(c, b->p); // (the copies are on the stream: freed where a wait costs nothing)
+    r->sort.key[0] = nk;
+    r->size = ns;
+    r->src = nr;
+    r->cap = cap;
+    return PJB_OK;
+}
+
+static int sort_piece_body(pjb_ctx *c, SortRun *r, Buf &out, const uint8_t *comp, int64_t comp_bytes, int32_t first_uoffset, int32_t last, uint64_t *next_voffset,
+                           int64_t *n_records) {
+    std::vector<InfBlock> blocks;
+    int64_t total = 0;
+    int rc = scan_bgzf(c, comp, comp_bytes, blocks, total);
+    if (rc) return rc;
+    if ((int64_t)first_uoffset > total) return fail(c, PJB_ERR_ARG, "bam_sort_piece: first_uoffset %d lies behind the piece's %lld inflated bytes", first_uoffset, (long long)total);
+    const size_t nb = blocks.size();
+    // inflated byte u of the piece as (offset of its block in the piece) << 16 | offset in the block; the end of the data: the piece's end
+    auto voffset_of = [&](iu64 u) -> uint64_t {
+        if (u >= (iu64)total) return (uint64_t)comp_bytes << 16;
+        size_t lo = 0, hi = nb;
+        while (lo < hi) { // the first block that begins behind u; the one before it holds u (empty blocks lie before the block they share a start with)
+            const size_t mid = lo + (hi - lo) / 2;
+            if (blocks[mid].out_off <= u) lo = mid + 1;
+            else hi = mid;
+        }
+        const size_t k = lo - 1;
+        const iu64 start = k == 0 ? 0 : blocks[k - 1].in_off + blocks[k - 1].in_len + 8; // (behind the payload, CRC32 and ISIZE of the block before)
+        return (uint64_t)start << 16 | (u - blocks[k].out_off);
+    };
+    size_t n = 0;
+    iu64 next_u = (iu64)first_uoffset;
+    hipStream_t st = c->stream;
+    if ((int64_t)first_uoffset < total) {
+        if ((rc = ensure(c, c->b_inf_comp, (size_t)comp_bytes + INF_PAD))) return rc;
+        if ((rc = upload_host(c, c->b_inf_comp.p, comp, (size_t)comp_bytes))) return rc;
+        HIP_TRY(c, hipMemsetAsync((uint8_t *)c->b_inf_comp.p + comp_bytes, 0, INF_PAD, st));
+        if ((rc = ensure_cat(c, out, (size_t)total + 64, MEM_STAGING))) return rc;
+        HIP_TRY(c, hipMemsetAsync((uint8_t *)out.p + total, 0, 64, st));
+        if ((rc = inflate_on_device(c, (const uint8_t *)c->b_inf_comp.p, blocks, (uint8_t *)out.p))) return rc;
+        RecordWalk w;
+        if ((rc = walk_records(c, bam_region(c, (const uint8_t *)out.p, total, first_uoffset, -1), true, "in the piece", w))) return rc;
+        if (w.n >= 0xffffff00ull || r->n + w.n >= 0xffffff00ull) return fail(c, PJB_ERR_ARG, "bam_sort_piece: 2^32 - 256 alignments or more in one run are not supported");
+        n = w.n;
+        next_u = w.next_u;
+    }
+    if (next_u < (iu64)total) { // the data ends inside a record
+        if (last) return fail(c, PJB_ERR_BGZF, "the data ends inside an alignment record (inflated offset %llu of the last piece): truncated file", (unsigned long long)next_u);
+        if (n == 0) { // nothing was taken and nothing changed: the caller may hand the same blocks over again with more behind them
+            r->keep_on_error = true;
+            if (next_voffset) *next_voffset = voffset_of(next_u);
+            return fail(c, PJB_ERR_ARG, "bam_sort_piece: the alignment record at inflated offset %llu is longer than the piece (%lld bytes): hand over more blocks at once",
+                        (unsigned long long)next_u, (long long)comp_bytes);
+        }
+    }
+    if (n > 0) {
+        if ((rc = sort_grow(c, r, r->n + n))) return rc;
+        iu64 *ctl = (iu64 *)r->ctl.p;
+        HIP_TRY(c, hipMemsetAsync(ctl, 0xff, SR_CTL_WORDS * 8, st));
+        HIP_TRY(c, hipMemsetAsync(ctl + SR_CTL_UNPLACED, 0, 8, st));
+        const dim3 grid((unsigned)((n + 255) / 256));
+        const iu64 *rec_off = (const iu64 *)c->b_bam_rec.p;
+        if (r->wide)
+            LAUNCH(c, "sr_keys", sr_keys<u64>, grid, dim3(256), (const uint8_t *)out.p, rec_off, (iu64)n, (const int32_t *)r->ref_len.p, (int32_t)c->ref_len.size(), r->pos_bits,
+                   r->prev, (u64 *)r->sort.key[0].p + r->n, (iu32 *)r->size.p + r->n, (iu64 *)r->src.p + r->n, ctl);
+        else
+            LAUNCH(c, "sr_keys", sr_keys<u32>, grid, dim3(256), (const uint8_t *)out.p, rec_off, (iu64)n, (const int32_t *)r->ref_len.p, (int32_t)c->ref_len.size(), r->pos_bits,
+                   r->prev, (u32 *)r->sort.key[0].p + r->n, (iu32 *)r->size.p + r->n, (iu64 *)r->src.p + r->n, ctl);
+        iu64 h[SR_CTL_WORDS];
+        HIP_TRY(c, hipMemcpyAsync(h, ctl, sizeof h, hipMemcpyDeviceToHost, st));
+        HIP_TRY(c, hipStreamSynchronize(st));
+        if (c->ktime) ev_collect(c, MISC_POOL);
+        // the first offender decides
+        if (h[SR_CTL_BAD_TID] != ~0ull && h[SR_CTL_BAD_TID] <= h[SR_CTL_BAD_POS])
+            return fail(c, PJB_ERR_BGZF, "alignment record %llu names a target the header does not have (its refID lies outside the %zu targets)",
+                        (unsigned long long)(r->n + h[SR_CTL_BAD_TID]), c->ref_len.size());
+        if (h[SR_CTL_BAD_POS] != ~0ull)
+            return fail(c, PJB_ERR_BGZF, "alignment record %llu has a position outside its target", (unsigned long long)(r->n + h[SR_CTL_BAD_POS]));
+        if (h[SR_CTL_DESCENT] != ~0ull) r->descent = std::min(r->descent, (iu64)r->n + h[SR_CTL_DESCENT]);
+        r->prev = h[SR_CTL_LAST];
+        r->n_unplaced += (int64_t)h[SR_CTL_UNPLACED];
+        r->n += n;
+        r->pieces.push_back(out);
+        out = Buf();
+    }
+    if (next_voffset) *next_voffset = voffset_of(next_u);
+    if (n_records) *n_records = (int64_t)n;
+    return PJB_OK;
+}
+
+extern "C" int pjb_bam_sort_piece(pjb_ctx *c, const uint8_t *comp, int64_t comp_bytes, int32_t first_uoffset, int32_t last, uint64_t *next_voffset,
+                                  int64_t *n_records) {
+    if (!c) return PJB_ERR_ARG;
+    if (n_records) *n_records = 0;
+    SortRun *r = c->sort_run;
+    if (!r || !r->active) return fail(c, PJB_ERR_STATE, "bam_sort_piece: no run is open (pjb_bam_sort_begin)");
+    r->keep_on_error = false;
+    if (comp_bytes < 0 || (comp_bytes && !comp) || first_uoffset < 0) return sort_leave(c, r, fail(c, PJB_ERR_ARG, "bam_sort_piece: bad arguments"));
+    HIP_TRY(c, hipSetDevice(c->cfg.device));
+    Buf out;
+    const int rc = sort_piece_body(c, r, out, comp, comp_bytes, first_uoffset, last, next_voffset, n_records);
+    if (out.p) { // the piece was not taken: its bytes go when nothing reads them any more
+        (void)hipStreamSynchronize(c->stream);
+        release(c, out);
+    }
+    return sort_leave(c, r, rc);
+}
+
+static int sort_end_body(pjb_ctx *c, SortRun *r, int32_t block_bytes, pjb_bam_sort_result *out) {
+    hipStream_t st = c->stream;
+    int rc;
+    const size_t n = r->n;
+    out->was_sorted = r->descent == ~0ull;
+    if (n == 0) return PJB_OK;
+    iu64 *ctl = (iu64 *)r->ctl.p;
+    const iu32 *order = nullptr;
+    if (!out->was_sorted) { // (a descent needs two different keys: key_bits > 0)
+        const size_t slack = n + RS_TILE, ksz = r->wide ? 8 : 4; // (rs_scatter loads whole tiles unguarded)
+        if ((rc = ensure(c, r->sort.key[1], slack * ksz)) || (rc = ensure(c, r->sort.idx[0], slack * 4)) || (rc = ensure(c, r->sort.idx[1], slack * 4))) return rc;
+        u32 *d_n = (u32 *)(ctl + SR_CTL_N);
+        r->h_n = (uint32_t)n;
+        HIP_TRY(c, hipMemcpyAsync(d_n, &r->h_n, 4, hipMemcpyHostToDevice, st));
+        // (the passes leave key[0] permuted: a call repeated after PJB_ERR_NOMEM goes on with the order it has)
+        if (!r->ordered && (rc = r->wide ? sort_u64_pairs(c, r->sort, d_n, n, r->key_bits, &r->order_in) : sort_u32_pairs(c, r->sort, d_n, n, r->key_bits, &r->order_in)))
+            return rc;
+        r->ordered = true;
+        order = (const iu32 *)r->sort.idx[r->order_in].p;
+    }
+    if ((rc = ensure(c, r->dst, n * 8))) return rc;
+    if ((rc = run_scan(c, "sr_off", MgSizeFn{(const iu32 *)r->size.p, order}, MgOffsetSink{(iu64 *)r->dst.p}, n, (u64 *)(ctl + SR_CTL_TOTAL)))) return rc;
+    iu64 raw = 0;
+    HIP_TRY(c, hipMemcpyAsync(&raw, ctl + SR_CTL_TOTAL, 8, hipMemcpyDeviceToHost, st));
+    HIP_TRY(c, hipStreamSynchronize(st));
+    if ((rc = ensure_cat(c, r->stream, (size_t)raw + 64, MEM_STAGING))) return rc;
+    LAUNCH(c, "mg_gather", mg_gather, dim3((unsigned)((n + 3) / 4)), dim3(256), (const iu64 *)r->src.p, (const iu32 *)r->size.p, order, (const iu64 *)r->dst.p, (iu64)n,
+           (uint8_t *)r->stream.p);
+    rc = deflate_launches(c, nullptr, (const uint8_t *)r->stream.p, (int64_t)raw, block_bytes, [&](int64_t, const std::vector<u32> &sizes, iu64 total, uint8_t *&dst) {
+        const size_t had = r->r_members.size();
+        r->r_size.insert(r->r_size.end(), sizes.begin(), sizes.end());
+        r->r_members.resize(had + (size_t)total);
+        dst = r->r_members.data() + had;
+        return (int)PJB_OK;
+    });
+    if (rc) {
+        r->r_size.clear();
+        r->r_members.clear();
+        return rc;
+    }
+    out->n_records = (int64_t)n;
+    out->raw_bytes = (int64_t)raw;
+    out->n_unplaced = r->n_unplaced;
+    return PJB_OK;
+}
+
+extern "C" int pjb_bam_sort_end(pjb_ctx *c, int32_t block_bytes, pjb_bam_sort_result *out) {
+    if (!c) return PJB_ERR_ARG;
+    SortRun *r = c->sort_run;
+    if (!r || !r->active) return fail(c, PJB_ERR_STATE, "bam_sort_end: no run is open (pjb_bam_sort_begin)");
+    r->keep_on_error = false;
+    if (!out) return sort_leave(c, r, fail(c, PJB_ERR_ARG, "bam_sort_end: bad arguments"));
+    if (block_bytes < 4 || block_bytes > (int32_t)DFL_IN_MAX || (block_bytes & 3))
+        return sort_leave(c, r, fail(c, PJB_ERR_ARG, "bam_sort_end: block_bytes must be a multiple of 4 between 4 and %u", DFL_IN_MAX));
+    HIP_TRY(c, hipSetDevice(c->cfg.device));
+    memset(out, 0, sizeof *out);
+    const int rc = sort_leave(c, r, sort_end_body(c, r, block_bytes, out));
+    if (rc) return rc;
+    r->active = false;
+    (void)hipStreamSynchronize(c->stream);
+    sort_drop_pieces(c, r); // (the stream has been copied out: the run's inflated bytes make room for the next run's)
+    out->n_members = (int32_t)r->r_size.size();
+    out->member_size = r->r_size.data();
+    out->members = r->r_members.data();
+    out->member_bytes = (int64_t)r->r_members.size();
     return PJB_OK;
 }

@@ -15,6 +15,9 @@
 //   mg_off scan    : run_scan over the sizes in sorted order: every record's offset in the merged stream, and the stream's length
 //   mg_gather      : a wavefront per record copies it to its place (the one pass over the record bytes)
 //   bgzf_deflate / bgzf_pack : the merged stream cut every block_bytes bytes, straight from device memory (pjb_deflate.hip.h)
+//
+// `prep --sort` (pjb_bam_sort_begin / _piece / _end) orders the records of ALL targets of an unsorted file's run with the same passes,
+// scan, gather and deflate; what it adds is sr_keys, which puts target and pos into one key.
 #pragma once
 #include "pjb_ingest.hip.h"
 
@@ -39,6 +42,52 @@ __global__ __launch_bounds__(256) void mg_keys(const uint8_t *U, const iu64 *rec
     if (pos < 0 || pos >= ref_len) atomicMin(&ctl[MG_CTL_BAD], i);
     if (i && pos < (int32_t)ld32u(U + rec_off[i - 1] + 8)) atomicMin(&ctl[MG_CTL_UNSORTED], i);
     key[i] = (iu32)pos;
+    size[i] = 4u + ld32u(U + off);
+    src[i] = (iu64)(uintptr_t)(U + off);
+}
+
+// ctl words (u64) of a piece's sr_keys
+enum : int {
+    SR_CTL_DESCENT = 0, // smallest ordinal (within the piece) of a record whose key lies below its predecessor's, ~0 if none
+    SR_CTL_BAD_TID = 1, // ... of a record whose refID lies outside [-1, n_ref)
+    SR_CTL_BAD_POS = 2, // ... of a placed record whose pos lies outside its target
+    SR_CTL_LAST = 3,    // the key of the piece's last record
+    SR_CTL_UNPLACED = 4, // records with refID == -1 (a count; zeroed, not ~0)
+    SR_CTL_TOTAL = 5,   // the offset scan's total: bytes of the sorted stream
+    SR_CTL_N = 6,       // the passes' record count (u32)
+    SR_CTL_WORDS = 8,
+};
+
+// The key of the record at p: (target << pos_bits) | pos, unplaced records (refID -1) behind every target with pos 0.  A record the
+// header has no place for gets a key as well (its target or pos clamped): the caller fails the piece, the key only has to stay inside
+// the bits the sort runs over.
+__device__ __forceinline__ iu64 sr_key_of(const uint8_t *p, const int32_t *ref_len, int32_t n_ref, int pos_bits, bool &bad_tid, bool &bad_pos) {
+    const int32_t tid = (int32_t)ld32u(p + 4), pos = (int32_t)ld32u(p + 8);
+    bad_tid = tid < -1 || tid >= n_ref;
+    bad_pos = false;
+    if (tid < 0 || tid >= n_ref) return (iu64)(iu32)n_ref << pos_bits;
+    const int32_t len = ref_len[tid];
+    bad_pos = pos < 0 || pos >= len;
+    return (iu64)(iu32)tid << pos_bits | (bad_pos ? 0u : (iu32)pos);
+}
+
+// A thread per record of one piece of a run.  U: the piece's inflated bytes, rec_off: its complete records (bam_walk_all), prev: the key
+// of the run's last record before the piece (0 for the first: no key lies below it).  K: u32 where pos_bits + bits_of(n_ref) <= 32.
+template <typename K>
+__global__ __launch_bounds__(256) void sr_keys(const uint8_t *U, const iu64 *rec_off, iu64 n, const int32_t *ref_len, int32_t n_ref, int pos_bits, iu64 prev,
+                                               K *key, iu32 *size, iu64 *src, iu64 *ctl) {
+    const iu64 i = (iu64)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    const iu64 off = rec_off[i];
+    bool bad_tid, bad_pos, b0, b1;
+    const iu64 k = sr_key_of(U + off, ref_len, n_ref, pos_bits, bad_tid, bad_pos);
+    if (i) prev = sr_key_of(U + rec_off[i - 1], ref_len, n_ref, pos_bits, b0, b1);
+    if (k < prev) atomicMin(&ctl[SR_CTL_DESCENT], i);
+    if (bad_tid) atomicMin(&ctl[SR_CTL_BAD_TID], i);
+    if (bad_pos) atomicMin(&ctl[SR_CTL_BAD_POS], i);
+    if ((int32_t)ld32u(U + off + 4) == -1) atomicAdd(&ctl[SR_CTL_UNPLACED], 1ull);
+    if (i == n - 1) ctl[SR_CTL_LAST] = k;
+    key[i] = (K)k;
     size[i] = 4u + ld32u(U + off);
     src[i] = (iu64)(uintptr_t)(U + off);
 }

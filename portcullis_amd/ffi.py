@@ -28,11 +28,13 @@ EXPORTS = [
     "pjb_extra_finish", "pjb_set_option", "pjb_merge_rows", "pjb_plan_groups", "pjb_bam_begin", "pjb_bam_piece", "pjb_bam_pieces_done", "pjb_bam_end", "pjb_bam_inflate_done", "pjb_filter_set_junctions", "pjb_filter_batch", "pjb_filt_features",
     "pjb_index_begin", "pjb_index_piece", "pjb_index_end",
     "pjb_bam_merge_begin", "pjb_bam_merge_file", "pjb_bam_merge_end",
+    "pjb_bam_sort_begin", "pjb_bam_sort_piece", "pjb_bam_sort_end",
     "pjb_forest_check", "pjb_forest_load", "pjb_forest_predict", "pjb_filt_scores", "pjb_forest_grow", "pjb_knn",
     "pjb_markov_train",
     "pjb_memory_info",
 ]
 ERR_NOMEM = -15  # PJB_ERR_NOMEM
+ERR_ARG = -16  # PJB_ERR_ARG
 N_FEATURES = 34
 KMER_TABLE = 3125 * 5
 PW_LEN = 32
@@ -97,6 +99,11 @@ class PjbIndexResult(C.Structure):
 class PjbBamMergeResult(C.Structure):  # pjb_bam_merge_result
     _fields_ = [("n_records", C.c_int64), ("raw_bytes", C.c_int64), ("n_members", C.c_int32), ("member_size", C.c_void_p), ("members", C.c_void_p),
                 ("member_bytes", C.c_int64)]
+
+
+class PjbBamSortResult(C.Structure):  # pjb_bam_sort_result
+    _fields_ = [("n_records", C.c_int64), ("raw_bytes", C.c_int64), ("n_members", C.c_int32), ("was_sorted", C.c_int32), ("member_size", C.c_void_p),
+                ("members", C.c_void_p), ("member_bytes", C.c_int64), ("n_unplaced", C.c_int64)]
 
 
 class PjbMemory(C.Structure):  # pjb_memory
@@ -202,6 +209,9 @@ def load():
         L.pjb_bam_merge_begin.argtypes = [C.c_void_p, C.c_int32, C.c_int32]
         L.pjb_bam_merge_file.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_int64, C.c_int32, C.POINTER(C.c_int64)]
         L.pjb_bam_merge_end.argtypes = [C.c_void_p, C.c_int32, C.POINTER(PjbBamMergeResult)]
+        L.pjb_bam_sort_begin.argtypes = [C.c_void_p]
+        L.pjb_bam_sort_piece.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.POINTER(C.c_uint64), C.POINTER(C.c_int64)]
+        L.pjb_bam_sort_end.argtypes = [C.c_void_p, C.c_int32, C.POINTER(PjbBamSortResult)]
         L.pjb_host_alloc.restype = C.c_void_p
         L.pjb_host_alloc.argtypes = [C.c_size_t]
         L.pjb_host_free.restype = None
@@ -723,6 +733,61 @@ class Context:
             if f is not None:
                 self.bam_merge_file(k, f[0], f[1])
         return self.bam_merge_end(block_bytes)
+
+    def bam_sort_begin(self):
+        self._check(self._L.pjb_bam_sort_begin(self._h))
+
+    def bam_sort_piece(self, comp, first_uoffset, last):
+        """One run of whole BGZF blocks of an unsorted file (pjb_bam_sort_piece); returns (next_voffset, records taken).  next_voffset
+        counts the block's offset from the piece's first byte.  A first record longer than the piece raises PjbError with code
+        ERR_ARG and leaves the run as it was: hand the same blocks over again with more behind them."""
+        comp = np.frombuffer(bytes(comp), dtype=np.uint8) if not isinstance(comp, np.ndarray) else comp
+        nv, n = C.c_uint64(), C.c_int64()
+        self._check(self._L.pjb_bam_sort_piece(self._h, comp.ctypes.data_as(C.c_void_p), len(comp), first_uoffset, int(bool(last)), C.byref(nv), C.byref(n)))
+        return nv.value, n.value
+
+    def bam_sort_end(self, block_bytes=0xff00):
+        """-> dict(n_records, n_unplaced, was_sorted, raw_bytes, member_size [u32 per BGZF member], members [their bytes, back to back; copies])."""
+        r = PjbBamSortResult()
+        self._check(self._L.pjb_bam_sort_end(self._h, block_bytes, C.byref(r)))
+        sizes = np.frombuffer((C.c_char * (4 * r.n_members)).from_address(r.member_size), dtype=np.uint32).copy() if r.n_members else np.zeros(0, np.uint32)
+        members = bytes((C.c_char * r.member_bytes).from_address(r.members)) if r.member_bytes else b""
+        return dict(n_records=r.n_records, n_unplaced=r.n_unplaced, was_sorted=r.was_sorted, raw_bytes=r.raw_bytes, member_size=sizes, members=members)
+
+    def bam_sort(self, data, piece_blocks=None, block_bytes=0xff00):
+        """The records of a BAM file's bytes, in whatever order, as one coordinate-sorted stream of BGZF members (pjb_bam_sort_begin /
+        _piece / _end; one run): stable by (refID as unsigned, pos).  The targets come from the file's header (set_refs); the file
+        is handed over in pieces of `piece_blocks` BGZF blocks (None: one piece), a piece growing by a block while its first record
+        is longer than it.  Returns bam_sort_end()'s dict plus `pieces`, the number of piece calls that took records or ended the file."""
+        data = data if isinstance(data, (bytes, bytearray)) else open(data, "rb").read()
+        starts = bgzf_block_starts(data)
+        ref_lens, header_bytes = bam_header(data, starts)
+        self.set_refs(ref_lens)
+        self.bam_sort_begin()
+        at = {o: k for k, o in enumerate(starts)}  # block start -> its number
+        nb = len(starts) - 1
+        k, uoff, pieces = 0, header_bytes, 0
+        while k < nb and uoff >= int.from_bytes(data[starts[k + 1] - 4:starts[k + 1]], "little"):  # (a long header: the first record's block)
+            uoff -= int.from_bytes(data[starts[k + 1] - 4:starts[k + 1]], "little")
+            k += 1
+        width = nb if piece_blocks is None else int(piece_blocks)
+        while True:
+            k1 = min(k + width, nb)
+            try:
+                nv, _ = self.bam_sort_piece(data[starts[k]:starts[k1]], uoff, k1 == nb)
+            except PjbError as e:
+                if e.code != ERR_ARG or "longer than the piece" not in str(e) or k1 == nb:
+                    raise
+                width += 1
+                continue
+            pieces += 1
+            if k1 == nb:
+                break
+            k, uoff = at[starts[k] + (nv >> 16)], nv & 0xFFFF
+            width = nb if piece_blocks is None else int(piece_blocks)
+        out = self.bam_sort_end(block_bytes)
+        out["pieces"] = pieces
+        return out
 
     def inflate_bgzf(self, comp):
         """Inflate a run of whole BGZF blocks (bytes-like) on the device; returns the inflated bytes."""

@@ -4,8 +4,9 @@
 // (Prepare::bamIndex, src/prepare.cc:227-260) the index is built on the device: pjb_index_begin / _piece / _end over the
 // file's BGZF blocks, read through a ring of page-locked pieces.  With --merge several coordinate-sorted BAM files are merged into
 // the directory's one on the device (bamMerge, src/prepare.cc:154-195: pjb_bam_merge_*, a target at a time); without the flag a
-// second file is refused.  Sorting BAM files (bamSort, src/prepare.cc:140-153) and CSI output are not built: such input is refused
-// with a message that says what to do instead.
+// second file is refused.  With --sort a file the index build finds unsorted is sorted on the device (bamSort, src/prepare.cc:140-153:
+// pjb_bam_sort_*, a run of the file at a time; several runs go through the merge); without the flag it is refused.  CSI output is not
+// built: it is refused with a message that says what to do instead.
 #pragma once
 
 #include <cstdint>
@@ -27,6 +28,7 @@ class Prepare {
     bool useCsi = false;
     bool verbose = false;
     bool merge = false;
+    bool sort = false;
 
     // link or copy `from` to `to` unless `to` is there already (src/prepare.cc:98-128); true if `to` exists afterwards
     bool copy(const std::string& from, const std::string& to, const std::string& msg, bool requireInputFileExists);
@@ -37,6 +39,10 @@ class Prepare {
     // merge itself -- every input's share of a target through pjb_bam_merge_*, target after target, then the unplaced tails
     std::string mergedHeaderText(const std::vector<std::string>& bamFiles);
     void mergeBams(const std::vector<std::string>& bamFiles, const std::string& headerText);
+    // --sort: `bamFile`, found unsorted, becomes the directory's sorted BAM: one read through the index build's piece reader feeds
+    // pjb_bam_sort_*; one run is renamed into place, several (sortrunN.bam) are merged by mergeBams.  Files still to be removed when the
+    // call returns or throws are added to tempPaths
+    void sortBam(const std::string& bamFile, std::vector<std::string>& tempPaths);
 
 public:
     explicit Prepare(const std::string& outputDir);
@@ -47,6 +53,7 @@ public:
     void setThreads(uint16_t v) { threads = v; }
     void setVerbose(bool v) { verbose = v; }
     void setMerge(bool v) { merge = v; }
+    void setSort(bool v) { sort = v; }
     const PreparedFiles& getOutput() const { return output; }
 
     // removes what a previous run left in the directory (PreparedFiles::clean, src/prepare.cc:77-86)
@@ -57,7 +64,8 @@ public:
     static std::string description() {
         return "Prepares a genome and a coordinate-sorted BAM file for the junction analysis: links (or copies) both into the\n"
                "output directory and indexes them.  A BAM index that is missing is built on the GPU.  With --merge several\n"
-               "coordinate-sorted BAM files are merged into one on the GPU first.";
+               "coordinate-sorted BAM files are merged into one on the GPU first; with --sort a BAM file that is not in coordinate\n"
+               "order is sorted on the GPU.";
     }
     static std::string usage() { return "portcullis_amd prep [options] <genome-file> <bam-file>"; }
     static int main(int argc, char* argv[]);

@@ -41,7 +41,8 @@ string Full::helpMessage() {
            "  --copy                           Whether to copy files from input data to prepared data where possible, otherwise will use symlinks.  Will require more time and disk space to prepare input but is potentially more robust.\n"
            "  --keep_temp                      Whether keep any temporary files created during the prepare stage of portcullis.  This might include BAM files and indexes.\n"
            "  --use_csi                        Whether to use CSI indexing rather than BAI indexing (writing CSI is not built into prep: refused).\n"
-           "  --merge                          Several coordinate-sorted BAM files may follow the genome: the prepare stage merges them into one on the GPU, as prep --merge does (ties in position go to the file given first).  Without it a second BAM file is refused.\n\n"
+           "  --merge                          Several coordinate-sorted BAM files may follow the genome: the prepare stage merges them into one on the GPU, as prep --merge does (ties in position go to the file given first).  Without it a second BAM file is refused.\n"
+           "  --sort                           A BAM file that is not in coordinate order is sorted on the GPU by the prepare stage, as prep --sort does (stable by target and position, unplaced records last).  Without it such a file is refused.\n\n"
            "Analysis options:\n"
            "  --orientation arg (=UNKNOWN)     The orientation of the reads that produced the BAM alignments: \"F\" (Single-end forward orientation); \"R\" (single-end reverse orientation); \"FR\" (paired-end, with reads sequenced towards center of fragment -> <-.  This is usual setting for most Illumina paired end sequencing); \"RF\" (paired-end, reads sequenced away from center of fragment <- ->); \"FF\" (paired-end, reads both sequenced in forward orientation); \"RR\" (paired-end, reads both sequenced in reverse orientation); \"UNKNOWN\" (default, portcullis will workaround any calculations requiring orientation information)\n"
            "  --strandedness arg (=UNKNOWN)    Whether BAM alignments were generated using a type of strand specific RNAseq library: \"unstranded\" (Standard Illumina); \"firststrand\" (dUTP, NSR, NNSR); \"secondstrand\" (Ligation, Standard SOLiD, flux sim reads); \"UNKNOWN\" (default, portcullis will workaround any calculations requiring strandedness information)\n"
@@ -69,7 +70,7 @@ int Full::main(int argc, char* argv[]) {
     string selfTrainDir, trainingRule = "balanced";
     int threads = 1, devices = 0;
     uint64_t deviceMem = 0;
-    bool separate = false, extra = false, copy = false, keepTemp = false, force = false, useCsi = false, merge = false, saveBad = false, exongff = false,
+    bool separate = false, extra = false, copy = false, keepTemp = false, force = false, useCsi = false, merge = false, sort = false, saveBad = false, exongff = false,
          introngff = false, bamFilter = false, saveLayers = false, saveFeatures = false, saveModels = false, verbose = false, help = false;
     uint32_t maxLength = 0, minCov = 1;
     // long options take their value as the next argument or after '=' (as in filt)
@@ -101,6 +102,7 @@ int Full::main(int argc, char* argv[]) {
         else if (a == "--keep_temp") keepTemp = true;
         else if (a == "--use_csi") useCsi = true;
         else if (a == "--merge") merge = true;
+        else if (a == "--sort") sort = true;
         else if (a == "--orientation") ori = need();
         else if (a == "--strandedness") strand = need();
         else if (a == "--separate") separate = true;
@@ -152,6 +154,7 @@ int Full::main(int argc, char* argv[]) {
     prep.setUseLinks(!copy);
     prep.setUseCsi(useCsi);
     prep.setMerge(merge);
+    prep.setSort(sort);
     prep.setThreads((uint16_t)std::max(1, threads));
     prep.setVerbose(verbose);
     prep.prepare(bamFiles, genomeFile);

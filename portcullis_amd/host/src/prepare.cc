@@ -1,6 +1,7 @@
 // Prepare (`portcullis_amd prep`): see prepare.hpp.  Mirrors src/prepare.cc:89-332 (Prepare::copy, genomeIndex, bamIndex,
-// prepare) and 373- (Prepare::main) of the reference; the BAM index is built on the device instead of by `samtools index`, and
-// --merge (src/prepare.cc:154-195, `samtools merge`) merges coordinate-sorted inputs on the device, target by target.
+// prepare) and 373- (Prepare::main) of the reference; the BAM index is built on the device instead of by `samtools index`,
+// --merge (src/prepare.cc:154-195, `samtools merge`) merges coordinate-sorted inputs on the device, target by target, and --sort
+// (Prepare::bamSort, `samtools sort`) sorts an unsorted input on the device, run by run, merging the runs where there are several.
 #include <portcullis/bam/bam_writer.hpp>
 #include <portcullis/bam/bam_reader.hpp>
 #include <portcullis/bam/genome_mapper.hpp>
@@ -21,6 +22,7 @@
 #include <cstring>
 #include <deque>
 #include <fstream>
+#include <functional>
 #include <iostream>
 #include <memory>
 #include <mutex>
@@ -330,45 +332,23 @@ const char* const NO_DEVICE_INDEX =
     "No MI355X (HIP device) is visible: the BAM index is built on the GPU and has no CPU fallback.  Put an index made elsewhere "
     "(samtools index) beside the BAM file, or run prep where the GPU is.";
 
-// The index of a coordinate-sorted BAM file, built on the device ...
-struct BuiltIndex {
-    bam::BaiBins bins;
-    bam::BaiLinear lin;
-    int64_t records = 0, chunks = 0;
+// A file that is not in coordinate order: what `prep --sort` catches and sorts, and everything else passes on as the refusal it is.
+struct UnsortedBam : PrepareException {
+    explicit UnsortedBam(const string& m) : PrepareException(m) {}
 };
-// (nameFile: the refusal of an unsorted file says which file -- prep --merge has several)
-BuiltIndex buildIndex(const string& bamFile, bool nameFile) {
-    const BamHead H = readBamHead(bamFile);
-    for (size_t t = 0; t < H.lens.size(); t++)
-        if ((int64_t)H.lens[t] >= BAI_MAX_TARGET)
-            throw PrepareException("BAI cannot index this target: " + H.names[t] + " has " + std::to_string(H.lens[t]) +
-                                   " bases, and a BAI index reaches 2^29.  Index the file with `samtools index -c` and use the CSI index (junc --use_csi): writing "
-                                   "CSI is not built into portcullis_amd prep.");
-    if (pjb_device_count() <= 0) throw PrepareException(NO_DEVICE_INDEX);
-    struct Ctx {
-        pjb_ctx* c = nullptr;
-        ~Ctx() {
-            if (c) pjb_destroy(c);
-        }
-    } ctx;
-    pjb_config cfg;
-    memset(&cfg, 0, sizeof cfg);
-    cfg.abi_version = PJB_ABI_VERSION;
-    cfg.flags = PJB_FLAG_NO_CHAINS;
-    if (pjb_create(&ctx.c, &cfg) != PJB_OK) throw PrepareException(string("pjb_create: ") + pjb_last_error(nullptr));
-    auto check = [&](int rc, const char* what) {
-        if (rc == PJB_OK) return;
-        const string msg = pjb_last_error(ctx.c);
-        if (rc == PJB_ERR_UNSORTED)
-            throw PrepareException("The BAM file is not in coordinate order: " + msg + ".  Sort it first (samtools sort): sorting is not built into portcullis_amd prep." +
-                                   (nameFile ? "  (" + bamFile + ")" : string()));
-        if (rc == PJB_ERR_ARG && msg.find("BAI cannot index") != string::npos)
-            throw PrepareException(msg + ".  Index the file with `samtools index -c` and use the CSI index (junc --use_csi).");
-        throw PrepareException(string(what) + ": " + msg);
-    };
-    check(pjb_set_refs(ctx.c, (int32_t)H.lens.size(), H.lens.data()), "pjb_set_refs");
-    check(pjb_index_begin(ctx.c), "pjb_index_begin");
+string unsortedMessage(const string& deviceMessage, const string& bamFile, bool nameFile) {
+    return "The BAM file is not in coordinate order: " + deviceMessage + ".  Sort it first (samtools sort), or pass --sort: prep then sorts it on the GPU." +
+           (nameFile ? "  (" + bamFile + ")" : string());
+}
 
+// The one read of a BAM file in pieces, for whoever takes them (the index build, the sort): the file from the block of its first record on,
+// through the ring of page-locked pieces, as runs of whole BGZF blocks in file order.  `feed(region, bytes, fileOffset, uoff, last, nv)`
+// gets a run of blocks that starts at fileOffset, the offset of the first record not yet taken in its inflated bytes, and whether the
+// file ends with it; it returns true and sets nv to the virtual offset (in the file) of the first record it did not take -- the next
+// run starts with that record's block --, or false: its first record is longer than these blocks, which then come again with the
+// next piece behind them.  `pieceCap` bounds the piece size (0: none).
+template <typename Feed>
+void walkPieces(const string& bamFile, const BamHead& H, size_t pieceCap, Feed feed) {
     const int fd = open(bamFile.c_str(), O_RDONLY);
     if (fd < 0) throw PrepareException("Could not open BAM file: " + bamFile);
     struct Fd {
@@ -384,66 +364,113 @@ BuiltIndex buildIndex(const string& bamFile, bool nameFile) {
     size_t piece = (size_t)std::max(1, getenv("PORTCULLIS_PIECE_MB") ? atoi(getenv("PORTCULLIS_PIECE_MB")) : 256) << 20;
     if (const char* e = getenv("PORTCULLIS_PIECE_BYTES"))
         if (atoi(e) > 0) piece = (size_t)std::max(64, atoi(e));
+    if (pieceCap) piece = std::min(piece, std::max<size_t>(pieceCap, 64));
     piece = (size_t)std::min<int64_t>((int64_t)piece, std::max<int64_t>(size - H.firstBlock, 64));
 
     // `carry`: the bytes from file offset carryOff on that have been read and not consumed
     std::vector<uint8_t> carry, big;
     int64_t carryOff = H.firstBlock;
     int32_t uoff = H.firstUoffset;
-    bool done = false;
     if (H.firstBlock >= size) {  // a header and nothing else (not even the EOF block)
         uint64_t nv = 0;
-        check(pjb_index_piece(ctx.c, nullptr, 0, H.firstBlock, 0, 1, &nv), "pjb_index_piece");
-        done = true;
+        feed((const uint8_t*)nullptr, (size_t)0, H.firstBlock, 0, true, nv);
+        return;
     }
-    if (!done) {
-        PieceReader reader(fd, H.firstBlock, size, piece);
-        while (!done) {
-            PieceReader::Piece pc = reader.next();
-            struct Release {
-                PieceReader& r;
-                uint8_t* b;
-                ~Release() { r.release(b); }
-            } rel{reader, pc.buf};
-            uint8_t* region;
-            const size_t regionBytes = carry.size() + pc.got;
-            if (carry.size() <= piece) {  // the usual case: in front of the piece, in its page-locked buffer
-                region = pc.buf + piece - carry.size();
-                if (!carry.empty()) memcpy(region, carry.data(), carry.size());
-            } else {  // a block or a record longer than a piece: a run of pageable memory as long as it takes
-                big.resize(regionBytes);
-                memcpy(big.data(), carry.data(), carry.size());
-                memcpy(big.data() + carry.size(), pc.buf + piece, pc.got);
-                region = big.data();
-            }
-            // whole blocks
-            size_t whole = 0;
-            while (whole < regionBytes) {
-                const size_t bs = bgzfBlockSize(region + whole, regionBytes - whole, carryOff + (int64_t)whole);
-                if (bs == 0 || whole + bs > regionBytes) break;
-                whole += bs;
-            }
-            if (pc.last && whole != regionBytes) throw PrepareException("The BAM file ends inside a BGZF block (truncated file): " + bamFile);
-            size_t consumed = 0;
-            if (whole > 0) {
-                uint64_t nv = ~0ull;
-                const int rc = pjb_index_piece(ctx.c, region, (int64_t)whole, carryOff, uoff, pc.last ? 1 : 0, &nv);
-                if (rc == PJB_ERR_ARG && nv != ~0ull && !pc.last) {
-                    // the first record is longer than these blocks: the same blocks again, with the next piece behind them
-                } else {
-                    check(rc, "pjb_index_piece");
-                    consumed = (size_t)((int64_t)(nv >> 16) - carryOff);
-                    uoff = (int32_t)(nv & 0xffff);
-                }
-            }
-            if (pc.last) done = true;
-            else {
-                std::vector<uint8_t> rest(region + consumed, region + regionBytes);
-                carry.swap(rest);
-                carryOff += (int64_t)consumed;
-            }
+    PieceReader reader(fd, H.firstBlock, size, piece);
+    for (bool done = false; !done;) {
+        PieceReader::Piece pc = reader.next();
+        struct Release {
+            PieceReader& r;
+            uint8_t* b;
+            ~Release() { r.release(b); }
+        } rel{reader, pc.buf};
+        uint8_t* region;
+        const size_t regionBytes = carry.size() + pc.got;
+        if (carry.size() <= piece) {  // the usual case: in front of the piece, in its page-locked buffer
+            region = pc.buf + piece - carry.size();
+            if (!carry.empty()) memcpy(region, carry.data(), carry.size());
+        } else {  // a block or a record longer than a piece: a run of pageable memory as long as it takes
+            big.resize(regionBytes);
+            memcpy(big.data(), carry.data(), carry.size());
+            memcpy(big.data() + carry.size(), pc.buf + piece, pc.got);
+            region = big.data();
+        }
+        // whole blocks
+        size_t whole = 0;
+        while (whole < regionBytes) {
+            const size_t bs = bgzfBlockSize(region + whole, regionBytes - whole, carryOff + (int64_t)whole);
+            if (bs == 0 || whole + bs > regionBytes) break;
+            whole += bs;
+        }
+        if (pc.last && whole != regionBytes) throw PrepareException("The BAM file ends inside a BGZF block (truncated file): " + bamFile);
+        size_t consumed = 0;
+        if (whole > 0) {
+            uint64_t nv = ~0ull;
+            if (feed((const uint8_t*)region, whole, carryOff, uoff, pc.last, nv)) {
+                consumed = (size_t)((int64_t)(nv >> 16) - carryOff);
+                uoff = (int32_t)(nv & 0xffff);
+            } else if (pc.last)
+                throw PrepareException("The BAM file ends inside an alignment record (truncated file): " + bamFile);
+            // (else: the first record is longer than these blocks: the same blocks again, with the next piece behind them)
+        }
+        if (pc.last) done = true;
+        else {
+            std::vector<uint8_t> rest(region + consumed, region + regionBytes);
+            carry.swap(rest);
+            carryOff += (int64_t)consumed;
         }
     }
+}
+
+struct DeviceCtx {  // a context without chains: what prep's index, merge and sort run on
+    pjb_ctx* c = nullptr;
+    DeviceCtx() {
+        pjb_config cfg;
+        memset(&cfg, 0, sizeof cfg);
+        cfg.abi_version = PJB_ABI_VERSION;
+        cfg.flags = PJB_FLAG_NO_CHAINS;
+        if (pjb_create(&c, &cfg) != PJB_OK) throw PrepareException(string("pjb_create: ") + pjb_last_error(nullptr));
+    }
+    ~DeviceCtx() {
+        if (c) pjb_destroy(c);
+    }
+    DeviceCtx(const DeviceCtx&) = delete;
+    DeviceCtx& operator=(const DeviceCtx&) = delete;
+};
+
+// The index of a coordinate-sorted BAM file, built on the device ...
+struct BuiltIndex {
+    bam::BaiBins bins;
+    bam::BaiLinear lin;
+    int64_t records = 0, chunks = 0;
+};
+// (nameFile: the refusal of an unsorted file says which file -- prep --merge has several)
+BuiltIndex buildIndex(const string& bamFile, bool nameFile) {
+    const BamHead H = readBamHead(bamFile);
+    for (size_t t = 0; t < H.lens.size(); t++)
+        if ((int64_t)H.lens[t] >= BAI_MAX_TARGET)
+            throw PrepareException("BAI cannot index this target: " + H.names[t] + " has " + std::to_string(H.lens[t]) +
+                                   " bases, and a BAI index reaches 2^29.  Index the file with `samtools index -c` and use the CSI index (junc --use_csi): writing "
+                                   "CSI is not built into portcullis_amd prep.");
+    if (pjb_device_count() <= 0) throw PrepareException(NO_DEVICE_INDEX);
+    DeviceCtx ctx;
+    auto check = [&](int rc, const char* what) {
+        if (rc == PJB_OK) return;
+        const string msg = pjb_last_error(ctx.c);
+        if (rc == PJB_ERR_UNSORTED) throw UnsortedBam(unsortedMessage(msg, bamFile, nameFile));
+        if (rc == PJB_ERR_ARG && msg.find("BAI cannot index") != string::npos)
+            throw PrepareException(msg + ".  Index the file with `samtools index -c` and use the CSI index (junc --use_csi).");
+        throw PrepareException(string(what) + ": " + msg);
+    };
+    check(pjb_set_refs(ctx.c, (int32_t)H.lens.size(), H.lens.data()), "pjb_set_refs");
+    check(pjb_index_begin(ctx.c), "pjb_index_begin");
+    walkPieces(bamFile, H, 0, [&](const uint8_t* region, size_t bytes, int64_t fileOffset, int32_t uoff, bool last, uint64_t& nv) {
+        nv = ~0ull;
+        const int rc = pjb_index_piece(ctx.c, region, (int64_t)bytes, fileOffset, uoff, last ? 1 : 0, &nv);
+        if (rc == PJB_ERR_ARG && nv != ~0ull && !last) return false;  // the first record is longer than these blocks
+        check(rc, "pjb_index_piece");
+        return true;
+    });
     pjb_index_result res;
     check(pjb_index_end(ctx.c, &res), "pjb_index_end");
     // the chunk list is ordered by (target, bin, file order): the maps below only group it
@@ -505,8 +532,177 @@ size_t followingBlock(const string& path, uint64_t off) {
     return bs && off + bs <= (uint64_t)st.st_size ? bs : 0;
 }
 const uint8_t BGZF_EOF_BLOCK[28] = {0x1f, 0x8b, 8, 4, 0, 0, 0, 0, 0, 0xff, 6, 0, 'B', 'C', 2, 0, 0x1b, 0, 3, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+const int32_t BGZF_CUT = 0xff00;  // inflated bytes a member of a file written here holds
+
+// the inflated bytes in front of a BAM file's first record
+std::vector<uint8_t> bamHeaderBytes(const string& text, const std::vector<string>& names, const std::vector<int32_t>& lens) {
+    std::vector<uint8_t> h = {'B', 'A', 'M', 1};
+    put32(h, (int32_t)text.size());
+    h.insert(h.end(), text.begin(), text.end());
+    put32(h, (int32_t)names.size());
+    for (size_t t = 0; t < names.size(); t++) {
+        put32(h, (int32_t)names[t].size() + 1);
+        h.insert(h.end(), names[t].begin(), names[t].end());
+        h.push_back(0);
+        put32(h, lens[t]);
+    }
+    return h;
+}
+// host bytes -> BGZF members (on the device) -> the file
+void deflateToFile(pjb_ctx* c, const std::vector<uint8_t>& raw, FILE* out, const string& path) {
+    if (raw.empty()) return;
+    std::vector<uint8_t> packed(((raw.size() + BGZF_CUT - 1) / BGZF_CUT) * 65536);
+    int64_t n = 0;
+    if (pjb_deflate_bgzf(c, raw.data(), (int64_t)raw.size(), BGZF_CUT, packed.data(), (int64_t)packed.size(), &n, nullptr) != PJB_OK)
+        throw PrepareException(string("pjb_deflate_bgzf: ") + pjb_last_error(c));
+    writeAll(out, packed.data(), (size_t)n, path);
+}
+
+const char* const NO_DEVICE_SORT =
+    "No MI355X (HIP device) is visible: the BAM file is sorted on the GPU and there is no CPU fallback.  Sort it elsewhere (samtools sort) and pass the "
+    "coordinate-sorted file, or run prep where the GPU is.";
+
+// What a run of the sort held and made (-v)
+struct SortRunInfo {
+    string path;
+    int64_t records = 0, unplaced = 0, compressedIn = 0;
+    bool wasSorted = false;
+    uint64_t peakHeld = 0;
+};
+
+// `prep --sort`: the records of an unsorted file in coordinate order, as one or several complete BAM files (runs: each holds a stretch
+// of the input, stable-sorted by (refID as unsigned, pos), under the header `headerText`).  One read of the file through walkPieces; a
+// run is closed before the compressed bytes handed over would pass `runBytes` (a piece is no longer than that; a run takes one piece at
+// least), or when the device has no room for the next piece.  The run
+// files are named by `runPath(k)` and listed in `tempPaths` before they are created.
+std::vector<SortRunInfo> sortBamToRuns(const string& bamFile, const string& headerText, int64_t runBytes, const std::function<string(size_t)>& runPath, std::vector<string>& tempPaths) {
+    const BamHead H = readBamHead(bamFile);
+    if (pjb_device_count() <= 0) throw PrepareException(NO_DEVICE_SORT);
+    DeviceCtx ctx;
+    auto check = [&](int rc, const char* what) {
+        if (rc != PJB_OK) throw PrepareException(string(what) + " (" + bamFile + "): " + pjb_last_error(ctx.c));
+    };
+    check(pjb_set_refs(ctx.c, (int32_t)H.lens.size(), H.lens.data()), "pjb_set_refs");
+    const std::vector<uint8_t> head = bamHeaderBytes(headerText, H.names, H.lens);
+    std::vector<SortRunInfo> runs;
+    bool open = false;
+    int64_t runIn = 0, runRecords = 0;
+    auto closeRun = [&] {
+        pjb_bam_sort_result res;
+        const int rc = pjb_bam_sort_end(ctx.c, BGZF_CUT, &res);
+        if (rc == PJB_ERR_NOMEM)
+            throw PrepareException("prep --sort: a run of " + std::to_string(runIn) + " compressed bytes does not fit the device memory this run may hold (" +
+                                   pjb_last_error(ctx.c) + ").  Set PORTCULLIS_SORT_RUN_BYTES to a smaller run, or sort the file elsewhere (samtools sort).");
+        check(rc, "pjb_bam_sort_end");
+        SortRunInfo info;
+        info.path = runPath(runs.size());
+        info.records = res.n_records;
+        info.unplaced = res.n_unplaced;
+        info.compressedIn = runIn;
+        info.wasSorted = res.was_sorted != 0;
+        unlink(info.path.c_str());  // (what a killed run left)
+        tempPaths.push_back(info.path);
+        FILE* out = fopen(info.path.c_str(), "wb");
+        if (!out) throw PrepareException("Could not create " + info.path);
+        struct Closer {
+            FILE*& f;
+            ~Closer() {
+                if (f) fclose(f);
+            }
+        } closer{out};
+        deflateToFile(ctx.c, head, out, info.path);
+        writeAll(out, res.members, (size_t)res.member_bytes, info.path);
+        writeAll(out, BGZF_EOF_BLOCK, sizeof BGZF_EOF_BLOCK, info.path);
+        FILE* f = out;
+        out = nullptr;
+        if (fclose(f) != 0) throw PrepareException("Could not write to " + info.path);
+        pjb_memory m;
+        memset(&m, 0, sizeof m);
+        (void)pjb_memory_info(ctx.c, &m);
+        info.peakHeld = m.peak_held;
+        runs.push_back(info);
+        open = false;
+        runIn = runRecords = 0;
+    };
+    walkPieces(bamFile, H, (size_t)std::min<int64_t>(runBytes, (int64_t)1 << 40), [&](const uint8_t* region, size_t bytes, int64_t fileOffset, int32_t uoff, bool last, uint64_t& nvFile) {
+        if (open && runRecords > 0 && runIn + (int64_t)bytes > runBytes) closeRun();  // (these blocks would take the run past its size)
+        for (;;) {
+            if (!open) {
+                check(pjb_bam_sort_begin(ctx.c), "pjb_bam_sort_begin");
+                open = true;
+            }
+            uint64_t nv = ~0ull;
+            int64_t n = 0;
+            const int rc = pjb_bam_sort_piece(ctx.c, region, (int64_t)bytes, uoff, last ? 1 : 0, &nv, &n);
+            if (rc == PJB_ERR_NOMEM) {  // the device is full: what the run holds is sorted and written, the piece goes to a fresh run
+                if (runRecords == 0)
+                    throw PrepareException("prep --sort: a piece of " + std::to_string(bytes) + " compressed bytes does not fit the device memory this run may hold (" +
+                                           pjb_last_error(ctx.c) + ").  Set PORTCULLIS_PIECE_MB to a smaller piece, or sort the file elsewhere (samtools sort).");
+                closeRun();
+                continue;
+            }
+            if (rc == PJB_ERR_ARG && nv != ~0ull && !last) return false;  // the first record is longer than these blocks
+            check(rc, "pjb_bam_sort_piece");
+            runRecords += n;
+            runIn += (int64_t)(nv >> 16);
+            nvFile = (uint64_t)(fileOffset + (int64_t)(nv >> 16)) << 16 | (nv & 0xffff);
+            if (runIn >= runBytes && !last) closeRun();
+            return true;
+        }
+    });
+    if (open || runs.empty()) {
+        if (!open) check(pjb_bam_sort_begin(ctx.c), "pjb_bam_sort_begin");  // (a header and nothing else)
+        open = true;
+        closeRun();
+    }
+    return runs;
+}
+
+// the size of a run of `prep --sort`, in compressed bytes of input.  The default, 1 GB, inflates to 2 - 5 GB of records; with the sorted
+// stream, 36 to 44 bytes a record for the sort and the deflate's scratch a run holds a few times that, far below the device's 288 GB
+// (measured, profiles/prep_sort.json: a run of 1.07 GB, 10 M records, 2.1 GB inflated, held 8.3 GB at the most).
+int64_t sortRunBytes() {
+    if (const char* e = getenv("PORTCULLIS_SORT_RUN_BYTES"))
+        if (atoll(e) > 0) return (int64_t)atoll(e);
+    return (int64_t)1 << 30;
+}
 
 }  // namespace
+
+// --sort: `bamFile` (found unsorted) as a list of coordinate-sorted files in the prepared directory, in input order; whoever owns
+// `tempPaths` removes them.  (`first`: the number of the first run file, so that several inputs' runs do not meet.)
+static std::vector<string> sortedRunsOf(const string& bamFile, const string& prepDir, size_t first, bool verbose, std::vector<string>& tempPaths) {
+    const double t0 = nowSeconds();
+    cout << "Sorting " << bamFile << " on the GPU ... ";
+    cout.flush();
+    BamHead H = readBamHead(bamFile);
+    string text;
+    try {
+        text = mergeBamHeaders({BamHeaderInfo{bamFile, std::move(H.text), std::move(H.names), std::move(H.lens)}});  // (@HD ... SO:coordinate)
+    } catch (const MergeHeaderException& e) {
+        throw PrepareException(e.what());
+    }
+    const std::vector<SortRunInfo> runs =
+        sortBamToRuns(bamFile, text, sortRunBytes(), [&](size_t k) { return prepDir + "/sortrun" + std::to_string(first + k) + ".bam"; }, tempPaths);
+    cout << "done." << endl;
+    std::vector<string> paths;
+    int64_t records = 0, unplaced = 0;
+    uint64_t peak = 0;
+    for (const SortRunInfo& r : runs) {
+        paths.push_back(r.path);
+        records += r.records;
+        unplaced += r.unplaced;
+        peak = std::max(peak, r.peakHeld);
+        if (verbose)
+            cout << " - sort run " << paths.size() << ": " << r.records << " alignment records, " << r.unplaced << " of them unplaced, from " << r.compressedIn
+                 << " compressed bytes" << (r.wasSorted ? " (in order already)" : "") << endl;
+    }
+    if (verbose)
+        cout << " - sorted: " << records << " alignment records, " << unplaced << " of them unplaced, in " << runs.size() << (runs.size() == 1 ? " run" : " runs")
+             << "; the device held at most " << peak << " bytes" << endl;
+    printf(" - BAM Sort - Wall time taken: %.1fs\n\n", nowSeconds() - t0);
+    return paths;
+}
 
 string Prepare::mergedHeaderText(const std::vector<string>& bamFiles) {
     std::vector<BamHeaderInfo> heads;
@@ -564,17 +760,7 @@ void Prepare::mergeBams(const std::vector<string>& bamFiles, const string& heade
     std::vector<int32_t> lens;
     for (const bam::RefSeq& t : targets) lens.push_back(t.length);
 
-    struct Ctx {
-        pjb_ctx* c = nullptr;
-        ~Ctx() {
-            if (c) pjb_destroy(c);
-        }
-    } ctx;
-    pjb_config cfg;
-    memset(&cfg, 0, sizeof cfg);
-    cfg.abi_version = PJB_ABI_VERSION;
-    cfg.flags = PJB_FLAG_NO_CHAINS;
-    if (pjb_create(&ctx.c, &cfg) != PJB_OK) throw PrepareException(string("pjb_create: ") + pjb_last_error(nullptr));
+    DeviceCtx ctx;
     auto check = [&](int rc, const char* what) {
         if (rc != PJB_OK) throw PrepareException(string(what) + ": " + pjb_last_error(ctx.c));
     };
@@ -590,27 +776,12 @@ void Prepare::mergeBams(const std::vector<string>& bamFiles, const string& heade
             if (f) fclose(f);
         }
     } closer{out};
-    const int32_t BLOCK = 0xff00;
-    std::vector<uint8_t> packed;
-    auto deflateToFile = [&](const std::vector<uint8_t>& raw) {  // host bytes -> BGZF members -> the file
-        if (raw.empty()) return;
-        packed.resize(((raw.size() + BLOCK - 1) / BLOCK) * 65536);
-        int64_t n = 0;
-        check(pjb_deflate_bgzf(ctx.c, raw.data(), (int64_t)raw.size(), BLOCK, packed.data(), (int64_t)packed.size(), &n, nullptr), "pjb_deflate_bgzf");
-        writeAll(out, packed.data(), (size_t)n, tmp);
-    };
+    const int32_t BLOCK = BGZF_CUT;
+    auto deflateToFile = [&](const std::vector<uint8_t>& raw) { portcullis::deflateToFile(ctx.c, raw, out, tmp); };
     {  // the header
-        std::vector<uint8_t> h = {'B', 'A', 'M', 1};
-        put32(h, (int32_t)headerText.size());
-        h.insert(h.end(), headerText.begin(), headerText.end());
-        put32(h, (int32_t)targets.size());
-        for (const bam::RefSeq& t : targets) {
-            put32(h, (int32_t)t.name.size() + 1);
-            h.insert(h.end(), t.name.begin(), t.name.end());
-            h.push_back(0);
-            put32(h, t.length);
-        }
-        deflateToFile(h);
+        std::vector<string> names;
+        for (const bam::RefSeq& t : targets) names.push_back(t.name);
+        deflateToFile(bamHeaderBytes(headerText, names, lens));
     }
     // target by target, in index order: what the device holds at a time is one target's records of all files
     std::vector<int64_t> perFile(nFiles, 0), unplacedPerFile(nFiles, 0);
@@ -651,8 +822,7 @@ void Prepare::mergeBams(const std::vector<string>& bamFiles, const string& heade
             const int rc = pjb_bam_merge_file(ctx.c, (int32_t)k, buf, (int64_t)bytes, (int32_t)firstU, &n);
             tooLarge(rc);
             if (rc == PJB_ERR_UNSORTED)
-                throw PrepareException(string("The BAM file is not in coordinate order: ") + pjb_last_error(ctx.c) + ".  Sort it first (samtools sort): sorting is not built "
-                                       "into portcullis_amd prep.  (" + bamFiles[k] + ")");
+                throw PrepareException(unsortedMessage(pjb_last_error(ctx.c), bamFiles[k], true));
             if (rc != PJB_OK) throw PrepareException("pjb_bam_merge_file (" + bamFiles[k] + "): " + pjb_last_error(ctx.c));
             perFile[k] += n;
         }
@@ -720,22 +890,65 @@ void Prepare::prepare(const std::vector<string>& bamFiles, const string& genomeF
     if (!copy(genomeFile, output.getGenomeFilePath(), "genome", true)) throw PrepareException("Could not copy/symlink genome file to: " + output.getGenomeFilePath());
     copy(genomeFile + ".fai", output.getGenomeIndexFilePath(), "genome index", false);
     if (!genomeIndex()) throw PrepareException("Could not create genome index");
+    Unlinker sortRuns;  // --sort: the sorted runs of unsorted inputs, gone however this ends
     if (merging) {
+        // --sort --merge: every input found unsorted gives way, in its place, to its sorted run or runs (the reference's tempN.bam).  An index
+        // beside an input is trusted, as everywhere; an input without one is probed by building its index
+        std::vector<string> inputs;
+        for (const string& b : bamFiles) {
+            bool unsorted = false;
+            if (sort && !lexists(output.getSortedBamFilePath()) && !fileExists(b + ".bai")) {
+                try {
+                    (void)buildIndex(b, true);
+                } catch (const UnsortedBam&) {
+                    unsorted = true;
+                }
+            }
+            if (!unsorted) inputs.push_back(b);
+            else
+                for (const string& run : sortedRunsOf(b, output.getPrepDir(), sortRuns.paths.size(), verbose, sortRuns.paths)) inputs.push_back(run);
+        }
         // the result is a regular file under the sorted BAM's name; its index is then built like any input's (a second inflate of the output)
-        mergeBams(bamFiles, mergedText);
+        mergeBams(inputs, mergedText);
         if (!bamIndex(false)) throw PrepareException("Failed to index: " + output.getSortedBamFilePath());
         return;
     }
-    if (!copy(bamFiles[0], output.getSortedBamFilePath(), "BAM", true)) throw PrepareException("Could not copy/symlink BAM file to: " + output.getSortedBamFilePath());
+    const string sorted = output.getSortedBamFilePath();
+    const bool bamWasThere = lexists(sorted);
+    if (!copy(bamFiles[0], sorted, "BAM", true)) throw PrepareException("Could not copy/symlink BAM file to: " + sorted);
     // the index beside the input if there is one (src/prepare.cc:316), else it is built (no device is touched before this point)
     const bool indexCopied = copy(bamFiles[0] + ".bai", output.getBamIndexFilePath(false), "BAM index", false);
-    if (!bamIndex(indexCopied)) throw PrepareException("Failed to index: " + output.getSortedBamFilePath());
+    try {
+        if (!bamIndex(indexCopied)) throw PrepareException("Failed to index: " + sorted);
+    } catch (const UnsortedBam&) {
+        struct stat st;
+        if (!sort || (bamWasThere && lstat(sorted.c_str(), &st) == 0 && !S_ISLNK(st.st_mode))) throw;  // (a file someone put there is not replaced)
+        // --sort: the index build found the file unsorted.  What was linked or copied under the sorted file's name goes, and the sorted
+        // file takes its place: the one run renamed, or the merge of several
+        cout << "not in coordinate order." << endl;
+        unlink(sorted.c_str());
+        sortBam(bamFiles[0], sortRuns.paths);
+        if (!bamIndex(false)) throw PrepareException("Failed to index: " + sorted);
+    }
+}
+
+void Prepare::sortBam(const string& bamFile, std::vector<string>& tempPaths) {
+    const string sorted = output.getSortedBamFilePath();
+    const std::vector<string> runs = sortedRunsOf(bamFile, output.getPrepDir(), 0, verbose, tempPaths);
+    if (runs.size() == 1) {
+        if (rename(runs[0].c_str(), sorted.c_str()) != 0) throw PrepareException("Could not write sorted BAM file: " + sorted);
+        cout << "Sorted BAM file created at: " << sorted << endl;
+        return;
+    }
+    // several runs: each is a sorted file, and run order is input order, so the merge's tie rule (the earlier file first) keeps the sort
+    // stable as a whole.  The merge indexes the runs on the device, as any input without an index.
+    mergeBams(runs, mergedHeaderText({runs[0]}));
 }
 
 int Prepare::main(int argc, char* argv[]) {
     std::vector<string> positional;
     string outputDir = DEFAULT_PREP_OUTPUT_DIR;
-    bool force = false, copy = false, useCsi = false, verbose = false, help = false, merge = false;
+    bool force = false, copy = false, useCsi = false, verbose = false, help = false, merge = false, sort = false;
     int threads = DEFAULT_PREP_THREADS;
     auto need = [&](int& i) -> string {
         if (i + 1 >= argc) throw PrepareException(string("Missing value for option ") + argv[i]);
@@ -747,6 +960,7 @@ int Prepare::main(int argc, char* argv[]) {
         else if (a == "--force") force = true;
         else if (a == "--copy") copy = true;
         else if (a == "--merge") merge = true;
+        else if (a == "--sort") sort = true;
         else if (a == "-c" || a == "--use_csi") useCsi = true;
         else if (a == "-t" || a == "--threads") threads = atoi(need(i).c_str());
         else if (a == "-v" || a == "--verbose") verbose = true;
@@ -761,8 +975,10 @@ int Prepare::main(int argc, char* argv[]) {
              << "      --copy           Copy the input files into the output directory instead of linking them" << endl
              << "      --merge          Several coordinate-sorted BAM files may follow the genome: they are merged into one on the GPU" << endl
              << "                       (ties in position go to the file given first; without the flag a second BAM file is refused)" << endl
+             << "      --sort           A BAM file that is not in coordinate order is sorted on the GPU (stable by target and position;" << endl
+             << "                       unplaced records last; without the flag such a file is refused).  A sorted file is left as it is" << endl
              << "  -c, --use_csi        CSI instead of BAI indexing (not built: refused)" << endl
-             << "  -t, --threads <n>    Threads that read the BAM files for --merge (the index is built on the GPU)" << endl
+             << "  -t, --threads <n>    Threads that read the BAM files for --merge and for the runs of --sort (index and sort run on the GPU)" << endl
              << "  -v, --verbose        Print extra information" << endl
              << "      --help           Produce this message" << endl;
         return help ? 0 : 1;
@@ -777,6 +993,7 @@ int Prepare::main(int argc, char* argv[]) {
     prep.setUseLinks(!copy);
     prep.setUseCsi(useCsi);
     prep.setMerge(merge);
+    prep.setSort(sort);
     prep.setThreads((uint16_t)std::max(1, threads));
     prep.setVerbose(verbose);
     prep.prepare(bamFiles, genomeFile);
