@@ -562,6 +562,29 @@ int pjb_index_piece(pjb_ctx *ctx, const uint8_t *comp, int64_t comp_bytes, int64
                     uint64_t *next_voffset);
 int pjb_index_end(pjb_ctx *ctx, pjb_index_result *out);
 
+/* The same index as a CSI (`portcullis_amd prep --build_csi`): for targets of 2^29 bases or more, which reg2bin cannot bin.
+ * min_shift is 14; bins are hts_reg2bin(beg, end, 14, depth) with the beg and end above, chunks as above, and instead of a
+ * linear index every bin carries `loffset`: the 16 kb windows are built as above, untouched ones take the entry before them
+ * (leading ones the virtual offset of the target's first record), and loffset is the entry at the bin's first window.
+ *   pjb_csi_depth        host arithmetic, no context: the depth htslib chooses, the smallest n with
+ *                        2^(14 + 3 n) >= (longest target) + 256 -- 5 for human, 6 from 2^29 - 255 bases up;
+ *   pjb_index_begin_csi  as pjb_index_begin; depth < 0: pjb_csi_depth of the pjb_set_refs targets.  PJB_ERR_ARG for a depth
+ *                        above 6 or, at a depth above 0, a target of 2^(14 + 3 depth) bases or more (the rule that keeps
+ *                        targets of 2^29 bases from a BAI; at depth 0 the one bin holds whatever there is);
+ *   pjb_index_piece      as above; no target is too long;
+ *   pjb_index_end_csi    as pjb_index_end.  pjb_index_end after pjb_index_begin_csi, and pjb_index_end_csi after
+ *                        pjb_index_begin, fail with PJB_ERR_STATE. */
+typedef struct pjb_csi_result {
+    int64_t n_records;
+    int64_t n_chunks;
+    const pjb_index_chunk *chunks; /* ordered by (tid, bin, file order) */
+    const uint64_t *loffset;       /* per chunk: its bin's */
+    int32_t min_shift, depth;
+} pjb_csi_result;
+int pjb_csi_depth(const int32_t *ref_len, int32_t n_ref);
+int pjb_index_begin_csi(pjb_ctx *ctx, int32_t depth);
+int pjb_index_end_csi(pjb_ctx *ctx, pjb_csi_result *out);
+
 /* ---- several coordinate-sorted files merged into one, target by target (`portcullis_amd prep --merge`) --------------
  * What `samtools merge` does for the reference's prep (src/prepare.cc:154-195 shells out to it), for ONE target at a time and on
  * the device: every file's share of the target is inflated and walked as by pjb_submit_bam, the records of all files are put in

@@ -17,6 +17,14 @@
 //   bai_chunks     : run heads open a chunk, the record behind a run closes it
 //   bai_win_*      : the running maximum in three kernels (tile maxima, their scan, apply), the last storing the windows
 //   bai_level scan, bai_tid_starts, bai_partition : the stable partition of the finished chunk list (pjb_index_end)
+//
+// The CSI mode (pjb_index_begin_csi / pjb_index_end_csi) shares all of it: bai_records bins by hts_reg2bin(beg, end, 14, depth)
+// for a depth of 0 .. 6 and keeps windows for targets of any length, the partition has depth + 1 levels, and three kernels
+// turn the windows into the `loffset` every bin carries instead of a linear index:
+//   csi_seed       : window 0 of every target with records takes its first record's virtual offset
+//   csi_fill_apply : untouched windows take the entry before them (a running maximum: virtual offsets ascend through the file;
+//                    the tile maxima are bai_win_reduce's and bai_win_tiles')
+//   csi_loffset    : every chunk of the ordered list reads the filled entry at its bin's first 16 kb window
 #pragma once
 #include "pjb_ingest.hip.h"
 
@@ -29,6 +37,8 @@ __global__ __launch_bounds__(256) void bam_walk_all(BamRegion R, iu32 n_seg, con
 
 constexpr iu64 BAI_NOKEY = ~0ull;       // run key of a record without a target
 constexpr int32_t BAI_MAX_LEN = 1 << 29; // reg2bin's range: targets of this many bases cannot be indexed
+constexpr int CSI_MIN_SHIFT = 14;        // the CSI's smallest bins are the BAI's: 16 kb
+constexpr int CSI_MAX_DEPTH = 6;         // 2^(14 + 3 * 6) covers every int32 position
 constexpr iu32 BAI_SLICE = 512;         // block-table entries a workgroup of bai_records keeps in LDS
 
 struct BaiChunk { // = pjb_index_chunk
@@ -58,7 +68,24 @@ __device__ __forceinline__ iu32 bai_reg2bin(iu32 beg, iu32 end) { // SAM spec 5.
     if (beg >> 26 == end >> 26) return 1u + (beg >> 26);
     return 0u;
 }
-__device__ __forceinline__ iu32 bai_level(iu32 bin) { return bin >= 4681u ? 5u : bin >= 585u ? 4u : bin >= 73u ? 3u : bin >= 9u ? 2u : bin >= 1u ? 1u : 0u; }
+// hts_reg2bin(beg, end, 14, depth); end exclusive, > beg, at most 2^(14 + 3 * depth).  Level l's first bin is (8^l - 1) / 7
+// whatever the depth, so depth 5 numbers the bins as bai_reg2bin does.
+__device__ __forceinline__ iu32 csi_level_first(int l) { return ((1u << (3 * l)) - 1u) / 7u; }
+__device__ __forceinline__ iu32 csi_reg2bin(iu32 beg, iu32 end, int depth) {
+    end--;
+    int s = CSI_MIN_SHIFT;
+    for (int l = depth; l > 0; l--, s += 3)
+        if (beg >> s == end >> s) return csi_level_first(l) + (beg >> s);
+    return 0u;
+}
+__device__ __forceinline__ iu32 bai_level(iu32 bin) {
+    return bin >= 37449u ? 6u : bin >= 4681u ? 5u : bin >= 585u ? 4u : bin >= 73u ? 3u : bin >= 9u ? 2u : bin >= 1u ? 1u : 0u;
+}
+// the first 16 kb window of a bin's interval
+__device__ __forceinline__ iu32 csi_first_window(iu32 bin, int depth) {
+    const int l = (int)bai_level(bin);
+    return l > depth ? 0u : (bin - csi_level_first(l)) << (3 * (depth - l));
+}
 
 // The block an inflated offset belongs to, in a table of block starts [lo, hi) that ends with the sentinel "end of the data, next
 // block of the file": the first entry that starts AT u (a record that starts where a block ends belongs to the block behind it,
@@ -90,8 +117,9 @@ struct BaiRecOut {
 
 __device__ __forceinline__ iu64 bai_sort_key(const uint8_t *U, iu64 off) { return (iu64)ld32u(U + off + 4) << 32 | ld32u(U + off + 8); }
 
+// csi_depth < 0: the BAI (reg2bin, targets of 2^29 bases or more refused); 0 .. 6: the CSI of that depth
 __global__ __launch_bounds__(256) void bai_records(const uint8_t *U, const iu64 *rec_off, iu64 n, BaiTable T, const int32_t *ref_len, int32_t n_ref,
-                                                   iu64 prev_sort, BaiRecOut O) {
+                                                   iu64 prev_sort, int csi_depth, BaiRecOut O) {
     __shared__ iu64 s_off[BAI_SLICE];
     __shared__ iu32 s_b0, s_nb;
     const iu64 i0 = (iu64)blockIdx.x * 256;
@@ -127,7 +155,7 @@ __global__ __launch_bounds__(256) void bai_records(const uint8_t *U, const iu64 
     if (tid >= n_ref || tid < -1) atomicMin(&O.ctl[BAI_CTL_BAD], i);
     else if (tid >= 0) {
         const int32_t len = ref_len[tid];
-        if (len >= BAI_MAX_LEN) atomicMin(&O.ctl[BAI_CTL_LONG], i);
+        if (csi_depth < 0 && len >= BAI_MAX_LEN) atomicMin(&O.ctl[BAI_CTL_LONG], i);
         else if (pos < 0 || pos >= len) atomicMin(&O.ctl[BAI_CTL_BAD], i);
         else {
             const uint8_t *cg = r + 32 + l_name;
@@ -138,7 +166,7 @@ __global__ __launch_bounds__(256) void bai_records(const uint8_t *U, const iu64 
             }
             iu64 end = (iu64)pos + (span ? span : 1);
             if (end > (iu64)len) end = (iu64)len; // (what hangs over the target's end is not indexed; pos < len)
-            const iu32 bin = bai_reg2bin((iu32)pos, (iu32)end);
+            const iu32 bin = csi_depth < 0 ? bai_reg2bin((iu32)pos, (iu32)end) : csi_reg2bin((iu32)pos, (iu32)end, csi_depth);
             key = (iu64)(iu32)tid << 32 | bin;
             w0 = (iu32)pos >> 14;
             win = (iu64)((iu32)tid + 1u) << 32 | ((((iu32)end - 1u) >> 14) + 1u);
@@ -279,7 +307,7 @@ __global__ __launch_bounds__(256) void bai_win_apply(const iu64 *win, const iu32
 }
 
 // ---- the finished chunk list (file order) -> (target, bin, file order)
-struct BaiLevelFn { // chunks of level 2p in the low half, of level 2p + 1 in the high half
+struct BaiLevelFn { // chunks of level 2p in the low half, of level 2p + 1 in the high half (p = 3: level 6 alone, the deepest CSI's)
     const BaiChunk *chunks;
     iu64 n;
     iu32 p;
@@ -300,15 +328,16 @@ __global__ __launch_bounds__(256) void bai_tid_starts(const BaiChunk *chunks, iu
     const int32_t before = j ? chunks[j - 1].tid : -1, cur = j < n ? chunks[j].tid : n_ref;
     for (int32_t t = before + 1; t <= cur && t <= n_ref; t++) tid_start[t] = (iu32)j;
 }
+// q3 (level 6) is read only where a chunk of level 6 exists: a CSI of depth 6
 __global__ __launch_bounds__(256) void bai_partition(const BaiChunk *chunks, iu64 n, int32_t n_ref, const iu32 *tid_start, const iu64 *q0, const iu64 *q1,
-                                                     const iu64 *q2, BaiChunk *out) {
+                                                     const iu64 *q2, const iu64 *q3, BaiChunk *out) {
     const iu64 j = (iu64)blockIdx.x * 256 + threadIdx.x;
     if (j >= n) return;
     const BaiChunk ch = chunks[j];
     if (ch.tid < 0 || ch.tid >= n_ref) return;
     const iu32 s = tid_start[ch.tid], e = tid_start[ch.tid + 1];
     const iu32 lvl = bai_level(ch.bin);
-    const iu64 *q[3] = {q0, q1, q2};
+    const iu64 *q[4] = {q0, q1, q2, q3};
     iu64 dest = s;
     for (iu32 l = 0; l <= lvl; l++) {
         const iu64 *a = q[l >> 1];
@@ -317,6 +346,56 @@ __global__ __launch_bounds__(256) void bai_partition(const BaiChunk *chunks, iu6
         dest += l < lvl ? (iu32)(a[e] >> sh) - ps : (iu32)(a[j] >> sh) - ps;
     }
     if (dest < n) out[dest] = ch;
+}
+
+// ---- the CSI's loffset: the windows filled from the left, read at every bin's first window
+// window 0 of a target with records <- its first record's virtual offset (the first chunk of the target in the file-order list):
+// what its leading untouched windows take.  Where the first record lies in window 0 the value is the one already there.
+__global__ __launch_bounds__(256) void csi_seed(const BaiChunk *chunks, const iu32 *tid_start, int32_t n_ref, const iu64 *lin_off, iu64 *lin, iu64 lin_total) {
+    const int32_t t = (int32_t)(blockIdx.x * 256 + threadIdx.x);
+    if (t >= n_ref) return;
+    const iu32 s = tid_start[t], e = tid_start[t + 1];
+    const iu64 at = lin_off[t];
+    if (s < e && at < lin_off[t + 1] && at < lin_total) lin[at] = chunks[s].vbeg;
+}
+// lin[i] <- the maximum of lin[0 .. i]: virtual offsets ascend through a sorted file, target by target and window by window, so the
+// maximum is the last touched entry at or before i, and csi_seed keeps it inside the target.  tile_max as for bai_win_apply.
+__global__ __launch_bounds__(256) void csi_fill_apply(iu64 *lin, iu64 n, const iu64 *tile_max) {
+    __shared__ iu64 sm[4];
+    const iu64 base = (iu64)blockIdx.x * SCAN_TILE;
+    if (base >= n) return;
+    iu64 run = tile_max[blockIdx.x];
+    const int w = threadIdx.x >> 6;
+#pragma unroll
+    for (int k = 0; k < 8; k++) {
+        const iu64 i = base + (iu64)k * 256 + threadIdx.x;
+        const iu64 v = i < n ? lin[i] : 0;
+        iu64 inc = wave_imax(v);
+        __syncthreads();
+        if (lane_id() == 63) sm[w] = inc;
+        __syncthreads();
+        iu64 all = run;
+        if (run > inc) inc = run;
+        for (int j = 0; j < 4; j++) {
+            const iu64 s = sm[j];
+            if (j < w && s > inc) inc = s;
+            if (s > all) all = s;
+        }
+        run = all;
+        if (i < n) lin[i] = inc;
+    }
+}
+__global__ __launch_bounds__(256) void csi_loffset(const BaiChunk *sorted, iu64 n, int32_t n_ref, int depth, const iu64 *lin_off, const iu64 *lin, iu64 lin_total,
+                                                   iu64 *loff) {
+    const iu64 j = (iu64)blockIdx.x * 256 + threadIdx.x;
+    if (j >= n) return;
+    const BaiChunk ch = sorted[j];
+    iu64 v = 0;
+    if (ch.tid >= 0 && ch.tid < n_ref) {
+        const iu64 at = lin_off[ch.tid] + csi_first_window(ch.bin, depth);
+        if (at < lin_off[ch.tid + 1] && at < lin_total) v = lin[at];
+    }
+    loff[j] = v;
 }
 
 } // namespace pjb

@@ -828,6 +828,7 @@ static int bam_end_body(pjb_ctx *c, int32_t tid, BamStage &stage, int32_t first_
 struct IndexState {
     bool active = false, saw_last = false;
     bool keep_on_error = false;   // the failing piece call left the index as it was
+    int csi_depth = -1;           // < 0: a BAI; 0 .. 6: a CSI of that depth (pjb_index_begin_csi)
     int64_t n_records = 0;
     iu64 prev_sort = 0;           // (refID unsigned) << 32 | pos of the last record seen
     iu64 open_key = BAI_NOKEY;    // (target, bin) of the run the last record belongs to: its chunk is the list's last, its end open
@@ -839,11 +840,13 @@ struct IndexState {
     size_t lin_total = 0;
     std::vector<iu64> h_lin_cap;  // lin_off on the host
     Buf key, vs, win, w0, heads, tab, ctl, tile_max; // a piece's scratch
-    Buf q[3], tid_start, sorted;  // pjb_index_end
+    Buf q[4], tid_start, sorted;  // pjb_index_end (q[3]: the seventh level, a CSI of depth 6)
+    Buf loff;                     // pjb_index_end_csi: u64 per ordered chunk
     // the result
     std::vector<pjb_index_chunk> r_chunks;
     std::vector<int64_t> r_lin_off;
     std::vector<uint64_t> r_lin;
+    std::vector<uint64_t> r_loff;
 };
 static_assert(sizeof(BaiChunk) == sizeof(pjb_index_chunk) && sizeof(pjb_index_chunk) == 24, "chunk layout");
 
@@ -851,20 +854,29 @@ static void index_clear(pjb_ctx *c) {
     IndexState *x = c->index;
     if (!x) return;
     for (Buf *b : {&x->chunks, &x->lin, &x->ref_len, &x->lin_off, &x->key, &x->vs, &x->win, &x->w0, &x->heads, &x->tab, &x->ctl, &x->tile_max, &x->q[0], &x->q[1],
-                   &x->q[2], &x->tid_start, &x->sorted})
+                   &x->q[2], &x->q[3], &x->tid_start, &x->sorted, &x->loff})
         release(c, *b);
     delete x;
     c->index = nullptr;
 }
 
-extern "C" int pjb_index_begin(pjb_ctx *c) {
-    if (!c) return PJB_ERR_ARG;
+extern "C" int pjb_csi_depth(const int32_t *ref_len, int32_t n_ref) {
+    int64_t longest = 0;
+    for (int32_t t = 0; ref_len && t < n_ref; t++) longest = std::max<int64_t>(longest, ref_len[t]);
+    longest += 256; // (htslib's margin, sam.c bam_index_build: the smallest depth whose root bin covers the longest target + 256)
+    int depth = 0;
+    for (int64_t s = 1ll << CSI_MIN_SHIFT; s < longest; s <<= 3) depth++;
+    return depth;
+}
+
+static int index_begin_body(pjb_ctx *c, int csi_depth) {
     HIP_TRY(c, hipSetDevice(c->cfg.device));
     if (!c->index) c->index = new (std::nothrow) IndexState();
     IndexState *x = c->index;
     if (!x) return fail(c, PJB_ERR_NOMEM, "index_begin: out of host memory");
     x->active = false;
     x->saw_last = false;
+    x->csi_depth = csi_depth;
     x->n_records = 0;
     x->prev_sort = 0;
     x->open_key = BAI_NOKEY;
@@ -874,12 +886,14 @@ extern "C" int pjb_index_begin(pjb_ctx *c) {
     x->r_chunks.clear();
     x->r_lin_off.clear();
     x->r_lin.clear();
-    // a window of 16 kb per 2^14 bases of every target reg2bin covers (a record on a longer one is refused when it is met)
+    x->r_loff.clear();
+    // a window of 16 kb per 2^14 bases of every target reg2bin covers (a record on a longer one is refused when it is met); of
+    // every target for a CSI
     const size_t n_ref = c->ref_len.size();
     x->h_lin_cap.assign(n_ref + 1, 0);
     for (size_t t = 0; t < n_ref; t++) {
         const int32_t len = c->ref_len[t];
-        x->h_lin_cap[t + 1] = x->h_lin_cap[t] + (len > 0 && len < BAI_MAX_LEN ? ((iu64)len + 16383) >> 14 : 0);
+        x->h_lin_cap[t + 1] = x->h_lin_cap[t] + (len > 0 && (csi_depth >= 0 || len < BAI_MAX_LEN) ? ((iu64)len + 16383) >> 14 : 0);
     }
     x->lin_total = (size_t)x->h_lin_cap[n_ref];
     int rc;
@@ -893,6 +907,26 @@ extern "C" int pjb_index_begin(pjb_ctx *c) {
     HIP_TRY(c, hipStreamSynchronize(st));
     x->active = true;
     return PJB_OK;
+}
+
+extern "C" int pjb_index_begin(pjb_ctx *c) {
+    if (!c) return PJB_ERR_ARG;
+    return index_begin_body(c, -1);
+}
+
+extern "C" int pjb_index_begin_csi(pjb_ctx *c, int32_t depth) {
+    if (!c) return PJB_ERR_ARG;
+    if (c->index) c->index->active = false; // (as pjb_index_begin: an index that was being built is dropped, whatever comes of this call)
+    if (depth > CSI_MAX_DEPTH) return fail(c, PJB_ERR_ARG, "index_begin_csi: a depth of %d is not supported (0 .. %d, or a negative one for the smallest that fits)", depth, CSI_MAX_DEPTH);
+    if (depth < 0) depth = pjb_csi_depth(c->ref_len.data(), (int32_t)c->ref_len.size());
+    if (depth > CSI_MAX_DEPTH) return fail(c, PJB_ERR_ARG, "index_begin_csi: no depth up to %d covers the longest target", CSI_MAX_DEPTH);
+    // the BAI's rule (BAI_MAX_LEN) at every depth: a target of 2^(14 + 3 depth) bases or more is not binned.  Depth 0 has the one bin
+    // that holds whatever there is.
+    for (size_t t = 0; depth > 0 && t < c->ref_len.size(); t++)
+        if ((int64_t)c->ref_len[t] >= 1ll << (CSI_MIN_SHIFT + 3 * depth))
+            return fail(c, PJB_ERR_ARG, "index_begin_csi: a CSI of depth %d bins targets of less than 2^%d bases, target %zu has %d", depth,
+                        CSI_MIN_SHIFT + 3 * depth, t, c->ref_len[t]);
+    return index_begin_body(c, depth);
 }
 
 // a chunk list that must hold `need` chunks: a larger buffer takes over what the list holds
@@ -983,7 +1017,7 @@ static int index_piece_body(pjb_ctx *c, IndexState *x, const uint8_t *comp, int6
         const iu64 *rec_off = (const iu64 *)c->b_bam_rec.p;
         const unsigned grid = (unsigned)((n + 255) / 256);
         LAUNCH(c, "bai_records", bai_records, dim3(grid), dim3(256), (const uint8_t *)c->b_inf_out.p, rec_off, (iu64)n, T, (const int32_t *)x->ref_len.p,
-               (int32_t)c->ref_len.size(), x->prev_sort, O);
+               (int32_t)c->ref_len.size(), x->prev_sort, x->csi_depth, O);
         if ((rc = run_scan(c, "bai_head", BaiHeadFn{O.key, x->open_key}, ExclusiveU32Sink{(u32 *)x->heads.p}, n, (u64 *)(ctl + BAI_CTL_HEADS)))) return rc;
         iu64 h[BAI_CTL_WORDS];
         HIP_TRY(c, hipMemcpyAsync(h, ctl, sizeof h, hipMemcpyDeviceToHost, st));
@@ -1046,13 +1080,8 @@ extern "C" int pjb_index_piece(pjb_ctx *c, const uint8_t *comp, int64_t comp_byt
     return rc;
 }
 
-extern "C" int pjb_index_end(pjb_ctx *c, pjb_index_result *out) {
-    if (!c || !out) return fail(c, PJB_ERR_ARG, "index_end: bad arguments");
-    IndexState *x = c->index;
-    if (!x || !x->active) return fail(c, PJB_ERR_STATE, "index_end: no index is being built (pjb_index_begin)");
-    if (!x->saw_last) return fail(c, PJB_ERR_STATE, "index_end: the last piece has not been handed over (pjb_index_piece with last != 0)");
-    HIP_TRY(c, hipSetDevice(c->cfg.device));
-    x->active = false;
+// closes the last chunk and orders the list by (target, bin, file order) into x->sorted, the copy to x->r_chunks queued
+static int index_order_chunks(pjb_ctx *c, IndexState *x) {
     hipStream_t st = c->stream;
     const size_t n = x->n_chunks, n_ref = c->ref_len.size();
     int rc;
@@ -1061,17 +1090,33 @@ extern "C" int pjb_index_end(pjb_ctx *c, pjb_index_result *out) {
         BaiChunk *chunks = (BaiChunk *)x->chunks.p;
         // the last run ends where the data ends
         if (x->open_key != BAI_NOKEY) HIP_TRY(c, hipMemcpyAsync(&chunks[n - 1].vend, &x->end_voffset, 8, hipMemcpyHostToDevice, st));
-        for (int p = 0; p < 3; p++)
+        const int n_scans = x->csi_depth > 5 ? 4 : 3; // two levels a scan
+        for (int p = 0; p < n_scans; p++)
             if ((rc = ensure(c, x->q[p], (n + 1) * 8))) return rc;
         if ((rc = ensure(c, x->tid_start, (n_ref + 1) * 4)) || (rc = ensure(c, x->sorted, n * sizeof(BaiChunk)))) return rc;
         iu64 *ctl = (iu64 *)x->ctl.p;
-        for (int p = 0; p < 3; p++)
+        for (int p = 0; p < n_scans; p++)
             if ((rc = run_scan(c, "bai_level", BaiLevelFn{chunks, (iu64)n, (iu32)p}, BaiLevelSink{(iu64 *)x->q[p].p}, n + 1, (u64 *)(ctl + BAI_CTL_HEADS)))) return rc;
         LAUNCH(c, "bai_tid_starts", bai_tid_starts, dim3((unsigned)((n + 256) / 256)), dim3(256), (const BaiChunk *)chunks, (iu64)n, (int32_t)n_ref, (iu32 *)x->tid_start.p);
         LAUNCH(c, "bai_partition", bai_partition, dim3((unsigned)((n + 255) / 256)), dim3(256), (const BaiChunk *)chunks, (iu64)n, (int32_t)n_ref,
-               (const iu32 *)x->tid_start.p, (const iu64 *)x->q[0].p, (const iu64 *)x->q[1].p, (const iu64 *)x->q[2].p, (BaiChunk *)x->sorted.p);
+               (const iu32 *)x->tid_start.p, (const iu64 *)x->q[0].p, (const iu64 *)x->q[1].p, (const iu64 *)x->q[2].p, (const iu64 *)(n_scans > 3 ? x->q[3].p : nullptr), (BaiChunk *)x->sorted.p);
         HIP_TRY(c, hipMemcpyAsync(x->r_chunks.data(), x->sorted.p, n * sizeof(BaiChunk), hipMemcpyDeviceToHost, st));
     }
+    return PJB_OK;
+}
+
+extern "C" int pjb_index_end(pjb_ctx *c, pjb_index_result *out) {
+    if (!c || !out) return fail(c, PJB_ERR_ARG, "index_end: bad arguments");
+    IndexState *x = c->index;
+    if (!x || !x->active) return fail(c, PJB_ERR_STATE, "index_end: no index is being built (pjb_index_begin)");
+    if (x->csi_depth >= 0) return fail(c, PJB_ERR_STATE, "index_end: a CSI is being built (pjb_index_end_csi)");
+    if (!x->saw_last) return fail(c, PJB_ERR_STATE, "index_end: the last piece has not been handed over (pjb_index_piece with last != 0)");
+    HIP_TRY(c, hipSetDevice(c->cfg.device));
+    x->active = false;
+    hipStream_t st = c->stream;
+    const size_t n = x->n_chunks, n_ref = c->ref_len.size();
+    int rc;
+    if ((rc = index_order_chunks(c, x))) return rc;
     // the windows: per target up to the last one a record touched (every touched window holds a virtual offset, and none is 0)
     std::vector<uint64_t> all(x->lin_total);
     if (x->lin_total) HIP_TRY(c, hipMemcpyAsync(all.data(), x->lin.p, x->lin_total * 8, hipMemcpyDeviceToHost, st));
@@ -1091,6 +1136,45 @@ extern "C" int pjb_index_end(pjb_ctx *c, pjb_index_result *out) {
     out->chunks = x->r_chunks.data();
     out->lin_off = x->r_lin_off.data();
     out->lin = x->r_lin.data();
+    return PJB_OK;
+}
+
+extern "C" int pjb_index_end_csi(pjb_ctx *c, pjb_csi_result *out) {
+    if (!c || !out) return fail(c, PJB_ERR_ARG, "index_end_csi: bad arguments");
+    IndexState *x = c->index;
+    if (!x || !x->active) return fail(c, PJB_ERR_STATE, "index_end_csi: no index is being built (pjb_index_begin_csi)");
+    if (x->csi_depth < 0) return fail(c, PJB_ERR_STATE, "index_end_csi: a BAI is being built (pjb_index_end)");
+    if (!x->saw_last) return fail(c, PJB_ERR_STATE, "index_end_csi: the last piece has not been handed over (pjb_index_piece with last != 0)");
+    HIP_TRY(c, hipSetDevice(c->cfg.device));
+    x->active = false;
+    hipStream_t st = c->stream;
+    const size_t n = x->n_chunks, n_ref = c->ref_len.size();
+    int rc;
+    if ((rc = index_order_chunks(c, x))) return rc;
+    x->r_loff.assign(n, 0);
+    if (n && x->lin_total) {
+        // the windows filled from the left (tid_start is index_order_chunks'), then every chunk's bin reads its first one
+        if ((rc = ensure(c, x->loff, n * 8))) return rc;
+        const iu32 nt = (iu32)((x->lin_total + SCAN_TILE - 1) / SCAN_TILE);
+        if ((rc = ensure(c, x->tile_max, (size_t)nt * 8))) return rc;
+        iu64 *ctl = (iu64 *)x->ctl.p, *lin = (iu64 *)x->lin.p;
+        LAUNCH(c, "csi_seed", csi_seed, dim3((unsigned)((n_ref + 255) / 256)), dim3(256), (const BaiChunk *)x->chunks.p, (const iu32 *)x->tid_start.p, (int32_t)n_ref,
+               (const iu64 *)x->lin_off.p, lin, (iu64)x->lin_total);
+        LAUNCH(c, "bai_win_reduce", bai_win_reduce, dim3(nt), dim3(256), (const iu64 *)lin, (iu64)x->lin_total, (iu64 *)x->tile_max.p);
+        LAUNCH(c, "bai_win_tiles", bai_win_tiles, dim3(1), dim3(1024), (iu64 *)x->tile_max.p, nt, (iu64)0, ctl + BAI_CTL_WINMAX);
+        LAUNCH(c, "csi_fill_apply", csi_fill_apply, dim3(nt), dim3(256), lin, (iu64)x->lin_total, (const iu64 *)x->tile_max.p);
+        LAUNCH(c, "csi_loffset", csi_loffset, dim3((unsigned)((n + 255) / 256)), dim3(256), (const BaiChunk *)x->sorted.p, (iu64)n, (int32_t)n_ref, x->csi_depth,
+               (const iu64 *)x->lin_off.p, (const iu64 *)lin, (iu64)x->lin_total, (iu64 *)x->loff.p);
+        HIP_TRY(c, hipMemcpyAsync(x->r_loff.data(), x->loff.p, n * 8, hipMemcpyDeviceToHost, st));
+    }
+    HIP_TRY(c, hipStreamSynchronize(st));
+    if (c->ktime) ev_collect(c, MISC_POOL);
+    out->n_records = x->n_records;
+    out->n_chunks = (int64_t)n;
+    out->chunks = x->r_chunks.data();
+    out->loffset = x->r_loff.data();
+    out->min_shift = CSI_MIN_SHIFT;
+    out->depth = x->csi_depth;
     return PJB_OK;
 }
 

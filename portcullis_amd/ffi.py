@@ -27,6 +27,7 @@ EXPORTS = [
     "pjb_select_timed_kernels", "pjb_host_alloc", "pjb_host_free", "pjb_host_register", "pjb_host_unregister", "pjb_inflate_bgzf", "pjb_deflate_bgzf", "pjb_submit_bam", "pjb_collect_device", "pjb_set_row_mirror",
     "pjb_extra_finish", "pjb_set_option", "pjb_merge_rows", "pjb_plan_groups", "pjb_bam_begin", "pjb_bam_piece", "pjb_bam_pieces_done", "pjb_bam_end", "pjb_bam_inflate_done", "pjb_filter_set_junctions", "pjb_filter_batch", "pjb_filt_features",
     "pjb_index_begin", "pjb_index_piece", "pjb_index_end",
+    "pjb_csi_depth", "pjb_index_begin_csi", "pjb_index_end_csi",
     "pjb_bam_merge_begin", "pjb_bam_merge_file", "pjb_bam_merge_end",
     "pjb_bam_sort_begin", "pjb_bam_sort_piece", "pjb_bam_sort_end",
     "pjb_forest_check", "pjb_forest_load", "pjb_forest_predict", "pjb_filt_scores", "pjb_forest_grow", "pjb_knn",
@@ -94,6 +95,11 @@ class PjbTiming(C.Structure):
 
 class PjbIndexResult(C.Structure):
     _fields_ = [("n_records", C.c_int64), ("n_chunks", C.c_int64), ("chunks", C.c_void_p), ("lin_off", C.c_void_p), ("lin", C.c_void_p)]
+
+
+class PjbCsiResult(C.Structure):  # pjb_csi_result
+    _fields_ = [("n_records", C.c_int64), ("n_chunks", C.c_int64), ("chunks", C.c_void_p), ("loffset", C.c_void_p), ("min_shift", C.c_int32),
+                ("depth", C.c_int32)]
 
 
 class PjbBamMergeResult(C.Structure):  # pjb_bam_merge_result
@@ -206,6 +212,9 @@ def load():
         L.pjb_index_begin.argtypes = [C.c_void_p]
         L.pjb_index_piece.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int32, C.c_int32, C.POINTER(C.c_uint64)]
         L.pjb_index_end.argtypes = [C.c_void_p, C.POINTER(PjbIndexResult)]
+        L.pjb_csi_depth.argtypes = [C.c_void_p, C.c_int32]
+        L.pjb_index_begin_csi.argtypes = [C.c_void_p, C.c_int32]
+        L.pjb_index_end_csi.argtypes = [C.c_void_p, C.POINTER(PjbCsiResult)]
         L.pjb_bam_merge_begin.argtypes = [C.c_void_p, C.c_int32, C.c_int32]
         L.pjb_bam_merge_file.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_int64, C.c_int32, C.POINTER(C.c_int64)]
         L.pjb_bam_merge_end.argtypes = [C.c_void_p, C.c_int32, C.POINTER(PjbBamMergeResult)]
@@ -232,6 +241,12 @@ def load():
 
 def device_count():
     return load().pjb_device_count()
+
+
+def csi_depth(ref_lens):
+    """pjb_csi_depth: the depth of the CSI htslib would write for these targets.  Host arithmetic; needs no context and no device."""
+    a = np.ascontiguousarray(ref_lens, dtype=np.int32)
+    return load().pjb_csi_depth(a.ctypes.data, len(a))
 
 
 def merge_rows(gathered, n_ranks, slot_stride_bytes):
@@ -659,8 +674,12 @@ class Context:
         self._check(self._L.pjb_submit_bam(self._h, tid, comp.ctypes.data_as(C.c_void_p), len(comp), first_uoffset, C.byref(n)))
         return n.value
 
-    def index_begin(self):
-        self._check(self._L.pjb_index_begin(self._h))
+    def index_begin(self, csi_depth=None):
+        """pjb_index_begin; with `csi_depth` pjb_index_begin_csi (negative: the depth csi_depth() gives for the targets)."""
+        if csi_depth is None:
+            self._check(self._L.pjb_index_begin(self._h))
+        else:
+            self._check(self._L.pjb_index_begin_csi(self._h, int(csi_depth)))
 
     def index_piece(self, comp, file_offset, first_uoffset, last):
         """One run of whole BGZF blocks (pjb_index_piece); returns next_voffset."""
@@ -683,15 +702,29 @@ class Context:
         lin_off = view(r.lin_off, self._n_refs + 1, np.int64)
         return dict(n_records=r.n_records, chunks=view(r.chunks, r.n_chunks, CHUNK_DTYPE), lin_off=lin_off, lin=view(r.lin, int(lin_off[-1]), np.uint64))
 
-    def index_bam(self, path_or_bytes, piece_blocks=None):
+    def index_end_csi(self):
+        """-> dict(n_records, chunks [CHUNK_DTYPE, ordered by (tid, bin, file order)], loffset [per chunk, its bin's], min_shift,
+        depth): views of the context's memory, valid until the next index_begin / close."""
+        r = PjbCsiResult()
+        self._check(self._L.pjb_index_end_csi(self._h, C.byref(r)))
+
+        def view(p, count, dt):
+            if count == 0:
+                return np.zeros(0, dtype=dt)
+            return np.frombuffer((C.c_char * (count * np.dtype(dt).itemsize)).from_address(p), dtype=dt, count=count)
+
+        return dict(n_records=r.n_records, chunks=view(r.chunks, r.n_chunks, CHUNK_DTYPE), loffset=view(r.loffset, r.n_chunks, np.uint64),
+                    min_shift=r.min_shift, depth=r.depth)
+
+    def index_bam(self, path_or_bytes, piece_blocks=None, csi_depth=None):
         """The BAI of a coordinate-sorted BAM (pjb_index_begin / _piece / _end), the file handed over in pieces of `piece_blocks`
         BGZF blocks (None: one piece).  The targets come from the file's header (set_refs).  Returns index_end()'s dict plus
-        `next_voffsets`, what each piece call returned."""
+        `next_voffsets`, what each piece call returned.  With `csi_depth` the CSI of that depth (index_end_csi()'s dict)."""
         data = path_or_bytes if isinstance(path_or_bytes, (bytes, bytearray)) else open(path_or_bytes, "rb").read()
         starts = bgzf_block_starts(data)
         ref_lens, header_bytes = bam_header(data, starts)
         self.set_refs(ref_lens)
-        self.index_begin()
+        self.index_begin(csi_depth)
         at = {o: k for k, o in enumerate(starts)}  # block start -> its number
         k, uoff, nvs = 0, header_bytes, []
         while True:
@@ -701,7 +734,7 @@ class Context:
             if k1 == len(starts) - 1:
                 break
             k, uoff = at[nv >> 16], nv & 0xFFFF
-        out = self.index_end()
+        out = self.index_end() if csi_depth is None else self.index_end_csi()
         out["next_voffsets"] = nvs
         return out
 

@@ -1,7 +1,8 @@
 // BamWriter: BGZF + BAM writer for the stages that emit alignments (bamfilt; lib/src/bam_writer.cc of the reference:
 // bgzf_open("w") + bam_hdr_write + bam_write1).  Records are appended as their raw BAM bytes; blocks of 0xff00
 // uncompressed bytes are deflated by a pool of threads and written in order.  close() adds the BGZF EOF block and,
-// where the reference shells out to `samtools index` (src/bam_filter.cc:236-244), writes the .bai itself.
+// where the reference shells out to `samtools index` (src/bam_filter.cc:236-244), writes the .bai itself -- and with
+// setWriteCsi the .csi (bamfilt --use_csi), which is the only index where a target has 2^29 bases or more.
 #pragma once
 
 #include <cstdint>
@@ -58,6 +59,23 @@ using BaiBins = std::vector<std::map<uint32_t, std::vector<std::pair<uint64_t, u
 using BaiLinear = std::vector<std::vector<uint64_t>>;
 void writeBai(const std::string& baiPath, const BaiBins& bins, const BaiLinear& lin);
 
+// A CSI index (min_shift 14): bins of hts_reg2bin(beg, end, 14, depth) with the chunks a BAI would have, and per bin `loffset`:
+// the linear index's entry at the bin's first 16 kb window, untouched windows taking the entry before them and leading ones the
+// virtual offset of the target's first record (htslib's update_loff).  csiPayload serialises it -- "CSI\1", min_shift, depth,
+// l_aux = 0, n_ref; per target n_bin and the bins ascending as (bin, loffset, n_chunk, chunks); no metadata pseudo-bin, no count
+// of unplaced records.  The file is that payload in BGZF members with the EOF block behind them: csiFileZlib makes it on the
+// host (BamWriter), `prep --build_csi` deflates the payload on the device that built the index; writeCsi writes either.
+using CsiLoffsets = std::vector<std::map<uint32_t, uint64_t>>;
+constexpr int CSI_MIN_SHIFT = 14;
+int csiDepthFor(const std::vector<int32_t>& targetLengths);  // htslib's choice: the smallest n with 2^(14 + 3 n) >= longest + 256
+uint32_t csiReg2bin(int64_t beg, int64_t end, int depth);    // end exclusive
+uint32_t csiFirstWindow(uint32_t bin, int depth);            // the first 16 kb window of the bin's interval
+// loffset of every bin from a linear index as BamWriter and the device build it (0: untouched) and each target's first record
+CsiLoffsets csiLoffsets(const BaiBins& bins, const BaiLinear& lin, const std::vector<uint64_t>& firstRecord, int depth);
+std::vector<uint8_t> csiPayload(int minShift, int depth, const BaiBins& bins, const CsiLoffsets& loff);
+std::vector<uint8_t> csiFileZlib(const std::vector<uint8_t>& payload);
+void writeCsi(const std::string& csiPath, const std::vector<uint8_t>& fileBytes);
+
 class BamWriter {
     struct RecInfo {
         int32_t tid, pos, end;
@@ -69,6 +87,11 @@ class BamWriter {
     FILE* fp = nullptr;
     int threads = 1, level = 6;
     bool wantIndex = true;
+    bool wantCsi = false;              // also <path>.csi
+    bool wantBai = true;               // false where a target has 2^29 bases or more: reg2bin does not reach it
+    int csiDepth = 0;
+    BaiBins csiBins;
+    std::vector<uint64_t> firstRecord; // per target the virtual offset of its first record (0: none yet)
     ByteBuf pending;                   // uncompressed bytes not yet flushed
     uint64_t uflushed = 0;             // uncompressed bytes already compressed and written
     uint64_t cwritten = 0;             // compressed bytes written
@@ -114,6 +137,9 @@ public:
     BamWriter(const std::string& path, int threads = 1, int level = 6) : path(path), threads(threads < 1 ? 1 : threads), level(level) {}
     ~BamWriter();
     void setWriteIndex(bool on) { wantIndex = on; }
+    // close() also writes <path>.csi (with the index on).  Where a target has 2^29 bases or more no .bai is written beside it
+    void setWriteCsi(bool on) { wantCsi = on; }
+    bool writesBai() const { return wantIndex && wantBai; }
     // BGZF blocks compressed somewhere else (BamFilter: on the device, pjb_deflate_bgzf) instead of by zlib in this process
     void setBlockCompressor(std::function<bool(const uint8_t*, size_t, size_t, ByteBuf&, std::vector<uint32_t>&)> f) { compressor = std::move(f); }
     const std::string& getPath() const { return path; }

@@ -5,8 +5,9 @@
 // file's BGZF blocks, read through a ring of page-locked pieces.  With --merge several coordinate-sorted BAM files are merged into
 // the directory's one on the device (bamMerge, src/prepare.cc:154-195: pjb_bam_merge_*, a target at a time); without the flag a
 // second file is refused.  With --sort a file the index build finds unsorted is sorted on the device (bamSort, src/prepare.cc:140-153:
-// pjb_bam_sort_*, a run of the file at a time; several runs go through the merge); without the flag it is refused.  CSI output is not
-// built: it is refused with a message that says what to do instead.
+// pjb_bam_sort_*, a run of the file at a time; several runs go through the merge); without the flag it is refused.  With --build_csi
+// every index prep builds is a CSI (pjb_index_begin_csi / _end_csi: the depth htslib would choose), which also covers targets of 2^29
+// bases or more; --use_csi without that flag stays refused, with a message that says what to do instead.
 #pragma once
 
 #include <cstdint>
@@ -26,6 +27,7 @@ class Prepare {
     bool useLinks = true;
     uint16_t threads = DEFAULT_PREP_THREADS;
     bool useCsi = false;
+    bool buildCsi = false;
     bool verbose = false;
     bool merge = false;
     bool sort = false;
@@ -50,6 +52,7 @@ public:
     void setForce(bool v) { force = v; }
     void setUseLinks(bool v) { useLinks = v; }
     void setUseCsi(bool v) { useCsi = v; }
+    void setBuildCsi(bool v) { buildCsi = v; }
     void setThreads(uint16_t v) { threads = v; }
     void setVerbose(bool v) { verbose = v; }
     void setMerge(bool v) { merge = v; }
@@ -63,7 +66,8 @@ public:
     static std::string title() { return "Portcullis Prepare Mode Help"; }
     static std::string description() {
         return "Prepares a genome and a coordinate-sorted BAM file for the junction analysis: links (or copies) both into the\n"
-               "output directory and indexes them.  A BAM index that is missing is built on the GPU.  With --merge several\n"
+               "output directory and indexes them.  A BAM index that is missing is built on the GPU (a BAI, or with --build_csi a CSI,\n"
+               "which also covers targets of 2^29 bases or more).  With --merge several\n"
                "coordinate-sorted BAM files are merged into one on the GPU first; with --sort a BAM file that is not in coordinate\n"
                "order is sorted on the GPU.";
     }

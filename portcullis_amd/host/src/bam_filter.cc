@@ -170,6 +170,7 @@ void BamFilter::filter() {
     ScopeMark sm_closer2{"closer2", profTop, tTop};
     std::unique_ptr<bam::BamWriter> writerHold(new bam::BamWriter(outputBam, threads));
     bam::BamWriter& writer = *writerHold;
+    writer.setWriteCsi(useCsi);  // --use_csi: <out>.csi beside the .bai
     ScopeMark sm_writer{"writer", profTop, tTop};
     auto deflateOn = [](pjb_ctx* ctx, const uint8_t* in, size_t n, size_t block, bam::ByteBuf& out, std::vector<uint32_t>& sizes) -> bool {
         const size_t nblk = (n + block - 1) / block;
@@ -360,7 +361,9 @@ void BamFilter::filter() {
     cout << "Filtered out " << diff << " alignments.  In: " << nbReadsIn << "; Out: " << nbReadsOut << " (Modified: " << nbReadsModifiedOut
          << ");" << endl
          << endl;
-    cout << "Indexing:" << endl << " - filtered alignments ... done." << endl;  // the .bai was written by BamWriter::close
+    cout << "Indexing:" << endl << " - filtered alignments ... done." << endl;  // the .bai (and the .csi) were written by BamWriter::close
+    if (!writer.writesBai())
+        cout << " - no .bai was written: a target has 2^29 bases or more, which a BAI cannot index" << (useCsi ? " (the .csi covers it)" : "; pass --use_csi for a .csi") << endl;
     if (leaves) {
         (void)jsHold.release();
         (void)readerHold.release();
@@ -379,7 +382,8 @@ std::string BamFilter::helpMessage() {
            "  -o [ --output ] arg (=filtered.bam)  Output BAM file generated by this program.\n"
            "  -c [ --clip_mode ] arg (=HARD)       How to clip reads associated with bad junctions: HARD, SOFT or COMPLETE\n"
            "  -m [ --save_msrs ]                   Whether or not to output modified MSRs to a separate file.\n"
-           "  --use_csi                            Whether to use CSI indexing rather than BAI indexing (input side).\n"
+           "  --use_csi                            Whether to use CSI indexing rather than BAI indexing: the input's .csi is read, and\n"
+           "                                       <output>.csi is written beside the .bai (no .bai where a target has 2^29 bases or more).\n"
            "  -t [ --threads ] arg (=1)            Threads that compress the output.\n"
            "  -v [ --verbose ]                     Print extra information\n"
            "  --help                               Produce help message\n";

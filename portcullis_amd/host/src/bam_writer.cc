@@ -103,6 +103,16 @@ void BamWriter::open(const std::string& headerText, const std::vector<RefSeq>& t
     nTargets = targets.size();
     bins.assign(nTargets, {});
     lin.assign(nTargets, {});
+    csiBins.assign(wantCsi ? nTargets : 0, {});
+    firstRecord.assign(nTargets, 0);
+    {
+        std::vector<int32_t> lens;
+        for (const auto& t : targets) lens.push_back(t.length);
+        csiDepth = csiDepthFor(lens);
+        wantBai = true;
+        for (int32_t len : lens)
+            if ((int64_t)len >= (int64_t)1 << 29) wantBai = false;
+    }
     cacheChunks = nullptr;
     cacheTid = -1;
     pending.clear();
@@ -222,15 +232,23 @@ void BamWriter::settle() {
 
 void BamWriter::indexRecord(const RecInfo& r, uint64_t vs, uint64_t ve) {
     if (r.tid < 0 || (size_t)r.tid >= nTargets) return;
-    const uint32_t bin = (uint32_t)reg2bin(r.pos, r.end);
-    if (r.tid != cacheTid || bin != cacheBin || !cacheChunks) {
-        cacheChunks = &bins[(size_t)r.tid][bin];  // (std::map: references stay valid while other bins are added)
-        cacheTid = r.tid;
-        cacheBin = bin;
+    if (wantBai) {
+        const uint32_t bin = (uint32_t)reg2bin(r.pos, r.end);
+        if (r.tid != cacheTid || bin != cacheBin || !cacheChunks) {
+            cacheChunks = &bins[(size_t)r.tid][bin];  // (std::map: references stay valid while other bins are added)
+            cacheTid = r.tid;
+            cacheBin = bin;
+        }
+        auto& ch = *cacheChunks;
+        if (!ch.empty() && ch.back().second == vs) ch.back().second = ve;
+        else ch.push_back({vs, ve});
     }
-    auto& ch = *cacheChunks;
-    if (!ch.empty() && ch.back().second == vs) ch.back().second = ve;
-    else ch.push_back({vs, ve});
+    if (wantCsi) {
+        auto& ch = csiBins[(size_t)r.tid][csiReg2bin(std::max(r.pos, 0), std::max(r.end, 1), csiDepth)];
+        if (!ch.empty() && ch.back().second == vs) ch.back().second = ve;
+        else ch.push_back({vs, ve});
+    }
+    if (firstRecord[(size_t)r.tid] == 0) firstRecord[(size_t)r.tid] = vs;
     const size_t w0 = (size_t)(std::max(r.pos, 0) >> 14), w1 = (size_t)(std::max(r.end - 1, 0) >> 14);
     auto& L = lin[(size_t)r.tid];
     if (L.size() <= w1) L.resize(w1 + 1, 0);
@@ -371,7 +389,108 @@ void BamWriter::close() {
         fprintf(stderr, "[writer profile] %s: gather %.3f s, compress %.3f s, fwrite %.3f s, index %.3f s, tail %.3f s\n", path.c_str(), g_prof.gather,
                 g_prof.compress, g_prof.fwrite_, g_prof.index, g_prof.tail);
     if (!wantIndex) return;
-    writeBai(path + ".bai", bins, lin);
+    if (wantBai) writeBai(path + ".bai", bins, lin);
+    if (wantCsi) writeCsi(path + ".csi", csiFileZlib(csiPayload(CSI_MIN_SHIFT, csiDepth, csiBins, csiLoffsets(csiBins, lin, firstRecord, csiDepth))));
+}
+
+int csiDepthFor(const std::vector<int32_t>& targetLengths) {
+    int64_t longest = 0;
+    for (int32_t len : targetLengths) longest = std::max<int64_t>(longest, len);
+    longest += 256;
+    int depth = 0;
+    for (int64_t s = (int64_t)1 << CSI_MIN_SHIFT; s < longest; s <<= 3) depth++;
+    return depth;
+}
+
+static inline uint32_t csiLevelFirst(int level) { return (((uint32_t)1 << (3 * level)) - 1) / 7; }
+
+uint32_t csiReg2bin(int64_t beg, int64_t end, int depth) {  // hts_reg2bin with min_shift 14
+    --end;
+    int s = CSI_MIN_SHIFT;
+    for (int l = depth; l > 0; --l, s += 3)
+        if (beg >> s == end >> s) return csiLevelFirst(l) + (uint32_t)(beg >> s);
+    return 0;
+}
+
+uint32_t csiFirstWindow(uint32_t bin, int depth) {
+    int l = 0;
+    while (l < depth && csiLevelFirst(l + 1) <= bin) l++;
+    return (bin - csiLevelFirst(l)) << (3 * (depth - l));
+}
+
+CsiLoffsets csiLoffsets(const BaiBins& bins, const BaiLinear& lin, const std::vector<uint64_t>& firstRecord, int depth) {
+    CsiLoffsets loff(bins.size());
+    for (size_t c = 0; c < bins.size(); c++) {
+        std::vector<uint64_t> filled(c < lin.size() ? lin[c] : std::vector<uint64_t>());
+        uint64_t last = c < firstRecord.size() ? firstRecord[c] : 0;
+        for (uint64_t& v : filled) {
+            if (v) last = v;
+            v = last;
+        }
+        for (const auto& kv : bins[c]) {
+            const size_t w = csiFirstWindow(kv.first, depth);
+            loff[c][kv.first] = w < filled.size() ? filled[w] : 0;
+        }
+    }
+    return loff;
+}
+
+std::vector<uint8_t> csiPayload(int minShift, int depth, const BaiBins& bins, const CsiLoffsets& loff) {
+    std::vector<uint8_t> o = {'C', 'S', 'I', 1};
+    put32(o, (uint32_t)minShift);
+    put32(o, (uint32_t)depth);
+    put32(o, 0);
+    put32(o, (uint32_t)bins.size());
+    for (size_t c = 0; c < bins.size(); c++) {
+        put32(o, (uint32_t)bins[c].size());
+        for (const auto& kv : bins[c]) {
+            const auto at = loff[c].find(kv.first);
+            put32(o, kv.first);
+            put64(o, at == loff[c].end() ? 0 : at->second);
+            put32(o, (uint32_t)kv.second.size());
+            for (const auto& ch : kv.second) {
+                put64(o, ch.first);
+                put64(o, ch.second);
+            }
+        }
+    }
+    return o;
+}
+
+std::vector<uint8_t> csiFileZlib(const std::vector<uint8_t>& payload) {
+    const size_t BLOCK = 0xff00;
+    std::vector<uint8_t> o, out(70000);
+    for (size_t off = 0; off < payload.size(); off += BLOCK) {
+        const size_t len = std::min(BLOCK, payload.size() - off);
+        z_stream zs;
+        memset(&zs, 0, sizeof zs);
+        if (deflateInit2(&zs, 6, Z_DEFLATED, -15, 8, Z_DEFAULT_STRATEGY) != Z_OK) throw BamException("zlib: deflateInit2 failed");
+        zs.next_in = const_cast<uint8_t*>(&payload[off]);
+        zs.avail_in = (uInt)len;
+        zs.next_out = out.data();
+        zs.avail_out = (uInt)out.size();
+        const int zr = deflate(&zs, Z_FINISH);
+        const size_t clen = out.size() - zs.avail_out;
+        deflateEnd(&zs);
+        if (zr != Z_STREAM_END) throw BamException("zlib: deflate failed");
+        const uint8_t hdr[16] = {31, 139, 8, 4, 0, 0, 0, 0, 0, 255, 6, 0, 'B', 'C', 2, 0};
+        o.insert(o.end(), hdr, hdr + 16);
+        o.push_back((uint8_t)((clen + 25) & 0xff));
+        o.push_back((uint8_t)((clen + 25) >> 8));
+        o.insert(o.end(), out.begin(), out.begin() + (long)clen);
+        put32(o, (uint32_t)crc32(crc32(0L, Z_NULL, 0), &payload[off], (uInt)len));
+        put32(o, (uint32_t)len);
+    }
+    static const uint8_t eof[28] = {0x1f, 0x8b, 0x08, 0x04, 0, 0, 0, 0, 0, 0xff, 0x06, 0, 0x42, 0x43, 0x02, 0, 0x1b, 0, 0x03, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+    o.insert(o.end(), eof, eof + 28);
+    return o;
+}
+
+void writeCsi(const std::string& csiPath, const std::vector<uint8_t>& fileBytes) {
+    FILE* f = fopen(csiPath.c_str(), "wb");
+    if (!f) throw BamException("Could not write BAM index: " + csiPath);
+    const bool ok = fwrite(fileBytes.data(), 1, fileBytes.size(), f) == fileBytes.size();
+    if (fclose(f) != 0 || !ok) throw BamException("Could not write BAM index: " + csiPath);
 }
 
 void writeBai(const std::string& baiPath, const BaiBins& bins, const BaiLinear& lin) {

@@ -40,7 +40,8 @@ string Full::helpMessage() {
            "  --force                          Whether or not to clean the output directory before processing, thereby forcing full preparation of the genome and bam files.  By default portcullis will only do what it thinks it needs to.\n"
            "  --copy                           Whether to copy files from input data to prepared data where possible, otherwise will use symlinks.  Will require more time and disk space to prepare input but is potentially more robust.\n"
            "  --keep_temp                      Whether keep any temporary files created during the prepare stage of portcullis.  This might include BAM files and indexes.\n"
-           "  --use_csi                        Whether to use CSI indexing rather than BAI indexing (writing CSI is not built into prep: refused).\n"
+           "  --use_csi                        Whether to use CSI indexing rather than BAI indexing (refused without --build_csi; with it, the same as --build_csi).\n"
+           "  --build_csi                      The prepare stage builds CSI indexes on the GPU, as prep --build_csi does (also for targets of 2^29 bases or more, which a BAI cannot index), and the later stages read and write CSI.\n"
            "  --merge                          Several coordinate-sorted BAM files may follow the genome: the prepare stage merges them into one on the GPU, as prep --merge does (ties in position go to the file given first).  Without it a second BAM file is refused.\n"
            "  --sort                           A BAM file that is not in coordinate order is sorted on the GPU by the prepare stage, as prep --sort does (stable by target and position, unplaced records last).  Without it such a file is refused.\n\n"
            "Analysis options:\n"
@@ -57,7 +58,7 @@ string Full::helpMessage() {
            "  --save_bad                       Saves bad junctions (i.e. junctions that fail the filter), as well as good junctions (those that pass)\n"
            "  --save_models                    Also save 3-filt/portcullis_filtered.selftrain.models: the L95 and the Markov models self-training trains, as filt --save_models\n"
            "  --training_rule arg (=balanced)  Pre-set to use for the self-training. Currently supported: balanced, precise. Default: balanced.\n\n"
-           "Not built (refused, as in prep and filt): sorting BAM files, CSI output, --genuine, a default data directory\n";
+           "Not built (refused, as in prep and filt): --genuine, a default data directory\n";
 }
 
 namespace {
@@ -70,7 +71,7 @@ int Full::main(int argc, char* argv[]) {
     string selfTrainDir, trainingRule = "balanced";
     int threads = 1, devices = 0;
     uint64_t deviceMem = 0;
-    bool separate = false, extra = false, copy = false, keepTemp = false, force = false, useCsi = false, merge = false, sort = false, saveBad = false, exongff = false,
+    bool separate = false, extra = false, copy = false, keepTemp = false, force = false, useCsi = false, buildCsi = false, merge = false, sort = false, saveBad = false, exongff = false,
          introngff = false, bamFilter = false, saveLayers = false, saveFeatures = false, saveModels = false, verbose = false, help = false;
     uint32_t maxLength = 0, minCov = 1;
     // long options take their value as the next argument or after '=' (as in filt)
@@ -101,6 +102,7 @@ int Full::main(int argc, char* argv[]) {
         else if (a == "--copy") copy = true;
         else if (a == "--keep_temp") keepTemp = true;
         else if (a == "--use_csi") useCsi = true;
+        else if (a == "--build_csi") buildCsi = true;
         else if (a == "--merge") merge = true;
         else if (a == "--sort") sort = true;
         else if (a == "--orientation") ori = need();
@@ -153,11 +155,13 @@ int Full::main(int argc, char* argv[]) {
     prep.setForce(force);
     prep.setUseLinks(!copy);
     prep.setUseCsi(useCsi);
+    prep.setBuildCsi(buildCsi);
     prep.setMerge(merge);
     prep.setSort(sort);
     prep.setThreads((uint16_t)std::max(1, threads));
     prep.setVerbose(verbose);
-    prep.prepare(bamFiles, genomeFile);
+    prep.prepare(bamFiles, genomeFile);  // (refuses --use_csi without --build_csi)
+    useCsi = useCsi || buildCsi;
     const double t1 = HostProfile::now();
 
     // ---- 2-junc (:329-348).  The run's contexts (up to ~100 GB of device memory) and page-locked rings are taken down on threads that

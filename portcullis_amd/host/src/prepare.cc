@@ -2,6 +2,7 @@
 // prepare) and 373- (Prepare::main) of the reference; the BAM index is built on the device instead of by `samtools index`,
 // --merge (src/prepare.cc:154-195, `samtools merge`) merges coordinate-sorted inputs on the device, target by target, and --sort
 // (Prepare::bamSort, `samtools sort`) sorts an unsorted input on the device, run by run, merging the runs where there are several.
+// --build_csi makes every index built here a CSI (pjb_index_begin_csi / _end_csi; `samtools index -c`), which also covers targets of 2^29 bases or more.
 #include <portcullis/bam/bam_writer.hpp>
 #include <portcullis/bam/bam_reader.hpp>
 #include <portcullis/bam/genome_mapper.hpp>
@@ -441,17 +442,21 @@ struct DeviceCtx {  // a context without chains: what prep's index, merge and so
 // The index of a coordinate-sorted BAM file, built on the device ...
 struct BuiltIndex {
     bam::BaiBins bins;
-    bam::BaiLinear lin;
+    bam::BaiLinear lin;    // a BAI's
+    bam::CsiLoffsets loff; // a CSI's, with its depth
+    int32_t csiDepth = -1;
+    std::vector<uint8_t> csiFile;  // the CSI as the bytes of its file: deflated on the context that built it
     int64_t records = 0, chunks = 0;
 };
 // (nameFile: the refusal of an unsorted file says which file -- prep --merge has several)
-BuiltIndex buildIndex(const string& bamFile, bool nameFile) {
+// (csi: a CSI of the depth htslib would choose, for targets of any length)
+BuiltIndex buildIndex(const string& bamFile, bool nameFile, bool csi) {
     const BamHead H = readBamHead(bamFile);
-    for (size_t t = 0; t < H.lens.size(); t++)
+    for (size_t t = 0; !csi && t < H.lens.size(); t++)
         if ((int64_t)H.lens[t] >= BAI_MAX_TARGET)
             throw PrepareException("BAI cannot index this target: " + H.names[t] + " has " + std::to_string(H.lens[t]) +
                                    " bases, and a BAI index reaches 2^29.  Index the file with `samtools index -c` and use the CSI index (junc --use_csi): writing "
-                                   "CSI is not built into portcullis_amd prep.");
+                                   "CSI is not built into portcullis_amd prep.  Or pass --build_csi: prep then builds a CSI index on the GPU.");
     if (pjb_device_count() <= 0) throw PrepareException(NO_DEVICE_INDEX);
     DeviceCtx ctx;
     auto check = [&](int rc, const char* what) {
@@ -459,11 +464,11 @@ BuiltIndex buildIndex(const string& bamFile, bool nameFile) {
         const string msg = pjb_last_error(ctx.c);
         if (rc == PJB_ERR_UNSORTED) throw UnsortedBam(unsortedMessage(msg, bamFile, nameFile));
         if (rc == PJB_ERR_ARG && msg.find("BAI cannot index") != string::npos)
-            throw PrepareException(msg + ".  Index the file with `samtools index -c` and use the CSI index (junc --use_csi).");
+            throw PrepareException(msg + ".  Index the file with `samtools index -c` and use the CSI index (junc --use_csi), or pass --build_csi.");
         throw PrepareException(string(what) + ": " + msg);
     };
     check(pjb_set_refs(ctx.c, (int32_t)H.lens.size(), H.lens.data()), "pjb_set_refs");
-    check(pjb_index_begin(ctx.c), "pjb_index_begin");
+    check(csi ? pjb_index_begin_csi(ctx.c, -1) : pjb_index_begin(ctx.c), csi ? "pjb_index_begin_csi" : "pjb_index_begin");
     walkPieces(bamFile, H, 0, [&](const uint8_t* region, size_t bytes, int64_t fileOffset, int32_t uoff, bool last, uint64_t& nv) {
         nv = ~0ull;
         const int rc = pjb_index_piece(ctx.c, region, (int64_t)bytes, fileOffset, uoff, last ? 1 : 0, &nv);
@@ -471,12 +476,34 @@ BuiltIndex buildIndex(const string& bamFile, bool nameFile) {
         check(rc, "pjb_index_piece");
         return true;
     });
-    pjb_index_result res;
-    check(pjb_index_end(ctx.c, &res), "pjb_index_end");
-    // the chunk list is ordered by (target, bin, file order): the maps below only group it
     const size_t nRef = H.lens.size();
     BuiltIndex X;
     X.bins.resize(nRef);
+    if (csi) {
+        pjb_csi_result res;
+        check(pjb_index_end_csi(ctx.c, &res), "pjb_index_end_csi");
+        X.loff.resize(nRef);
+        for (int64_t k = 0; k < res.n_chunks; k++) {
+            const pjb_index_chunk& ch = res.chunks[k];
+            X.bins[(size_t)ch.tid][ch.bin].push_back({ch.vbeg, ch.vend});
+            X.loff[(size_t)ch.tid][ch.bin] = res.loffset[k];
+        }
+        X.csiDepth = res.depth;
+        X.records = res.n_records;
+        X.chunks = res.n_chunks;
+        // the file's bytes: the payload in BGZF members deflated on the device, the EOF block behind them
+        const std::vector<uint8_t> raw = bam::csiPayload(res.min_shift, res.depth, X.bins, X.loff);
+        X.csiFile.resize(((raw.size() + 0xff00 - 1) / 0xff00) * 65536 + 28);
+        int64_t n = 0;
+        check(pjb_deflate_bgzf(ctx.c, raw.data(), (int64_t)raw.size(), 0xff00, X.csiFile.data(), (int64_t)X.csiFile.size() - 28, &n, nullptr), "pjb_deflate_bgzf");
+        static const uint8_t eof[28] = {0x1f, 0x8b, 8, 4, 0, 0, 0, 0, 0, 0xff, 6, 0, 'B', 'C', 2, 0, 0x1b, 0, 3, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+        memcpy(X.csiFile.data() + n, eof, 28);
+        X.csiFile.resize((size_t)n + 28);
+        return X;
+    }
+    pjb_index_result res;
+    check(pjb_index_end(ctx.c, &res), "pjb_index_end");
+    // the chunk list is ordered by (target, bin, file order): the maps below only group it
     X.lin.resize(nRef);
     for (int64_t k = 0; k < res.n_chunks; k++) {
         const pjb_index_chunk& ch = res.chunks[k];
@@ -488,19 +515,24 @@ BuiltIndex buildIndex(const string& bamFile, bool nameFile) {
     return X;
 }
 
-// ... and written as a .bai
+// ... and written as a .bai, or as the .csi it was built as
 void writeIndex(const BuiltIndex& X, const string& baiFile) {
     const string tmp = baiFile + ".tmp";
-    bam::writeBai(tmp, X.bins, X.lin);
+    if (X.csiDepth >= 0) bam::writeCsi(tmp, X.csiFile);
+    else bam::writeBai(tmp, X.bins, X.lin);
     if (rename(tmp.c_str(), baiFile.c_str()) != 0) throw PrepareException("Could not write BAM index: " + baiFile);
 }
 
 }  // namespace
 
 void Prepare::buildIndexOnDevice(const string& bamFile, const string& baiFile) {
-    const BuiltIndex X = buildIndex(bamFile, false);
+    const BuiltIndex X = buildIndex(bamFile, false, buildCsi);
     writeIndex(X, baiFile);
-    if (verbose) cout << endl << "Indexed " << X.records << " alignment records: " << X.chunks << " chunks." << endl;
+    if (verbose) {
+        cout << endl << "Indexed " << X.records << " alignment records: " << X.chunks << " chunks";
+        if (X.csiDepth >= 0) cout << ", a CSI of depth " << X.csiDepth;
+        cout << "." << endl;
+    }
 }
 
 // ---- prep --merge: several coordinate-sorted files into the prepared directory's one, target by target on the device ----------------
@@ -735,7 +767,8 @@ void Prepare::mergeBams(const std::vector<string>& bamFiles, const string& heade
     // either way it is found beside a link to the input, under the reference's temp names
     std::vector<std::unique_ptr<bam::BamReader>> readers;
     for (size_t k = 0; k < nFiles; k++) {
-        const string link = output.getPrepDir() + "/temp" + std::to_string(k) + ".bam", bai = link + ".bai";
+        const string ext = buildCsi ? ".csi" : ".bai";
+        const string link = output.getPrepDir() + "/temp" + std::to_string(k) + ".bam", bai = link + ext;
         char real[PATH_MAX];
         if (!realpath(bamFiles[k].c_str(), real)) throw PrepareException("Could not resolve BAM file: " + bamFiles[k]);
         unlink(link.c_str());  // (what a killed run left)
@@ -743,15 +776,15 @@ void Prepare::mergeBams(const std::vector<string>& bamFiles, const string& heade
         temps.paths.push_back(link);
         temps.paths.push_back(bai);
         if (symlink(real, link.c_str()) != 0) throw PrepareException("Could not create symlink from " + bamFiles[k] + " to " + link);
-        if (fileExists(bamFiles[k] + ".bai")) {
+        if (fileExists(bamFiles[k] + ext)) {
             char realBai[PATH_MAX];
-            if (!realpath((bamFiles[k] + ".bai").c_str(), realBai) || symlink(realBai, bai.c_str()) != 0)
-                throw PrepareException("Could not create symlink from " + bamFiles[k] + ".bai to " + bai);
+            if (!realpath((bamFiles[k] + ext).c_str(), realBai) || symlink(realBai, bai.c_str()) != 0)
+                throw PrepareException("Could not create symlink from " + bamFiles[k] + ext + " to " + bai);
         } else
-            writeIndex(buildIndex(bamFiles[k], true), bai);
+            writeIndex(buildIndex(bamFiles[k], true, buildCsi), bai);
         readers.emplace_back(new bam::BamReader(link));
         try {
-            readers.back()->open(false);
+            readers.back()->open(buildCsi);
         } catch (const std::exception& e) {
             throw PrepareException("Could not open " + bamFiles[k] + " with its index: " + e.what());
         }
@@ -869,9 +902,12 @@ void Prepare::mergeBams(const std::vector<string>& bamFiles, const string& heade
 }
 
 void Prepare::prepare(const std::vector<string>& bamFiles, const string& genomeFile) {
-    if (useCsi)
+    if (useCsi && !buildCsi)
         throw PrepareException("Writing CSI indexes is not built into portcullis_amd prep.  Build the directory without --use_csi (a BAI index covers targets "
-                               "below 2^29 bases), or put a CSI index made with `samtools index -c` beside the BAM file and link the files by hand.");
+                               "below 2^29 bases), or put a CSI index made with `samtools index -c` beside the BAM file and link the files by hand, or pass "
+                               "--build_csi: prep then builds the CSI index on the GPU.");
+    useCsi = buildCsi;  // (every index path below is the CSI's with --build_csi)
+    const string indexExt = buildCsi ? ".csi" : ".bai";
     if (bamFiles.empty()) throw PrepareException("No BAM files to process");
     if (bamFiles.size() > 1 && !merge)
         throw PrepareException("More than one BAM file was given, and merging is not built into portcullis_amd prep.  Merge them first (samtools merge) and "
@@ -897,9 +933,9 @@ void Prepare::prepare(const std::vector<string>& bamFiles, const string& genomeF
         std::vector<string> inputs;
         for (const string& b : bamFiles) {
             bool unsorted = false;
-            if (sort && !lexists(output.getSortedBamFilePath()) && !fileExists(b + ".bai")) {
+            if (sort && !lexists(output.getSortedBamFilePath()) && !fileExists(b + indexExt)) {
                 try {
-                    (void)buildIndex(b, true);
+                    (void)buildIndex(b, true, buildCsi);
                 } catch (const UnsortedBam&) {
                     unsorted = true;
                 }
@@ -917,7 +953,7 @@ void Prepare::prepare(const std::vector<string>& bamFiles, const string& genomeF
     const bool bamWasThere = lexists(sorted);
     if (!copy(bamFiles[0], sorted, "BAM", true)) throw PrepareException("Could not copy/symlink BAM file to: " + sorted);
     // the index beside the input if there is one (src/prepare.cc:316), else it is built (no device is touched before this point)
-    const bool indexCopied = copy(bamFiles[0] + ".bai", output.getBamIndexFilePath(false), "BAM index", false);
+    const bool indexCopied = copy(bamFiles[0] + indexExt, output.getBamIndexFilePath(buildCsi), "BAM index", false);
     try {
         if (!bamIndex(indexCopied)) throw PrepareException("Failed to index: " + sorted);
     } catch (const UnsortedBam&) {
@@ -948,7 +984,7 @@ void Prepare::sortBam(const string& bamFile, std::vector<string>& tempPaths) {
 int Prepare::main(int argc, char* argv[]) {
     std::vector<string> positional;
     string outputDir = DEFAULT_PREP_OUTPUT_DIR;
-    bool force = false, copy = false, useCsi = false, verbose = false, help = false, merge = false, sort = false;
+    bool force = false, copy = false, useCsi = false, buildCsi = false, verbose = false, help = false, merge = false, sort = false;
     int threads = DEFAULT_PREP_THREADS;
     auto need = [&](int& i) -> string {
         if (i + 1 >= argc) throw PrepareException(string("Missing value for option ") + argv[i]);
@@ -962,6 +998,7 @@ int Prepare::main(int argc, char* argv[]) {
         else if (a == "--merge") merge = true;
         else if (a == "--sort") sort = true;
         else if (a == "-c" || a == "--use_csi") useCsi = true;
+        else if (a == "-C" || a == "--build_csi") buildCsi = true;
         else if (a == "-t" || a == "--threads") threads = atoi(need(i).c_str());
         else if (a == "-v" || a == "--verbose") verbose = true;
         else if (a == "--help" || a == "-h") help = true;
@@ -977,7 +1014,10 @@ int Prepare::main(int argc, char* argv[]) {
              << "                       (ties in position go to the file given first; without the flag a second BAM file is refused)" << endl
              << "      --sort           A BAM file that is not in coordinate order is sorted on the GPU (stable by target and position;" << endl
              << "                       unplaced records last; without the flag such a file is refused).  A sorted file is left as it is" << endl
-             << "  -c, --use_csi        CSI instead of BAI indexing (not built: refused)" << endl
+             << "  -c, --use_csi        CSI instead of BAI indexing (refused without --build_csi; with it, the same as --build_csi)" << endl
+             << "  -C, --build_csi      Every index prep builds is a CSI (<bam>.csi, no .bai), built on the GPU: min_shift 14 and the depth" << endl
+             << "                       htslib chooses.  It also covers targets of 2^29 bases or more, which a BAI cannot.  A .csi beside" << endl
+             << "                       the input is linked or copied instead.  Run junc with --use_csi on the result" << endl
              << "  -t, --threads <n>    Threads that read the BAM files for --merge and for the runs of --sort (index and sort run on the GPU)" << endl
              << "  -v, --verbose        Print extra information" << endl
              << "      --help           Produce this message" << endl;
@@ -992,12 +1032,13 @@ int Prepare::main(int argc, char* argv[]) {
     prep.setForce(force);
     prep.setUseLinks(!copy);
     prep.setUseCsi(useCsi);
+    prep.setBuildCsi(buildCsi);
     prep.setMerge(merge);
     prep.setSort(sort);
     prep.setThreads((uint16_t)std::max(1, threads));
     prep.setVerbose(verbose);
     prep.prepare(bamFiles, genomeFile);
-    prep.getOutput().valid(false);
+    prep.getOutput().valid(buildCsi);
     printf("\nPortcullis prep completed.\nTotal runtime: %.1fs\n\n", nowSeconds() - t0);
     return 0;
 }
