@@ -3,7 +3,8 @@
 // that queues and collects them: pjb_chain.hip.h, pjb_flight.hip.h, pjb_limits.hip.h), pjb_extra_api.hip
 // (--extra, bamfilt: pjb_extra.hip.h), pjb_model_api.hip (filt and train -- feature rows, the forest walk, forest growing, KNN:
 // pjb_features.hip.h, pjb_forest.hip.h, pjb_grow.hip.h, pjb_knn.hip.h) and pjb_ingest_api.hip (BGZF inflate / deflate, BAM records:
-// pjb_ingest.hip.h, pjb_deflate.hip.h) -- each of which includes its own kernel family behind this header and so is the only unit that compiles it; this header includes only what the
+// pjb_ingest.hip.h, pjb_deflate.hip.h; prep's index, merge and sort: pjb_index.hip.h, pjb_merge.hip.h, and the host code that drives them:
+// pjb_index_api.hip.h, pjb_merge_api.hip.h, pjb_sort_api.hip.h) -- each of which includes its own kernel family behind this header and so is the only unit that compiles it; this header includes only what the
 // units share (pjb_device.hip.h, pjb_extra_types.hip.h, and pjb_memory.hip.h: the rule the counted allocator below follows).  (The Makefile makes every header a prerequisite of every unit: an edit to any of them
 // rebuilds the library.)  Helpers are inline functions of this header: one definition, one set of thread-local error strings for all units.
 #pragma once
@@ -334,9 +335,9 @@ struct pjb_ctx {
     Buf b_inf_comp, b_inf_out, b_inf_blocks, b_inf_status, b_inf_scratch, b_inf_bitmap; // device-side BGZF inflate
     Buf b_dfl_in, b_dfl_sym, b_dfl_slots, b_dfl_size, b_dfl_off, b_dfl_packed;           // device-side BGZF deflate
     Buf b_bam_seg, b_bam_rec, b_bam_ctl;                                  // device-side BAM record parse
-    struct IndexState *index = nullptr;                                   // pjb_index_begin / _piece / _end (pjb_ingest_api.hip)
-    struct SortRun *sort_run = nullptr;                                   // pjb_bam_sort_begin / _piece / _end (pjb_ingest_api.hip)
-    struct MergeState *merge = nullptr;                                   // pjb_bam_merge_begin / _file / _end (pjb_ingest_api.hip)
+    struct IndexState *index = nullptr;                                   // pjb_index_begin / _piece / _end (pjb_index_api.hip.h)
+    struct SortRun *sort_run = nullptr;                                   // pjb_bam_sort_begin / _piece / _end (pjb_sort_api.hip.h)
+    struct MergeState *merge = nullptr;                                   // pjb_bam_merge_begin / _file / _end (pjb_merge_api.hip.h)
     // --extra
     bool extra = false;
     std::vector<ExtraContig> xc;
@@ -915,6 +916,7 @@ int upload_staged(pjb_ctx *c, void *dst, const uint8_t *src, size_t bytes);     
 int upload_host(pjb_ctx *c, void *dst, const uint8_t *src, size_t bytes);                                     // pjb_ingest_api.hip (page-locked bytes: one DMA, else upload_staged)
 struct SortU32 { // the buffers of sort_u32_pairs / sort_u64_pairs: keys and indices ping-pong (a sort tile of slack each), the passes' counts
     Buf key[2], idx[2], hist, hist_part, hist_scan, bin_total;
+    void release_all(pjb_ctx *c) { for (Buf *b : {&key[0], &key[1], &idx[0], &idx[1], &hist, &hist_part, &hist_scan, &bin_total}) release(c, *b); }
 };
 int sort_u32_pairs(pjb_ctx *c, SortU32 &S, const u32 *d_n, size_t n, int key_bits, int *result);             // pjb_api.hip (the rs_* passes over 32-bit keys: pjb_bam_merge_end, pjb_bam_sort_end)
 int sort_u64_pairs(pjb_ctx *c, SortU32 &S, const u32 *d_n, size_t n, int key_bits, int *result);             // pjb_api.hip (the same over 64-bit keys: pjb_bam_sort_end)

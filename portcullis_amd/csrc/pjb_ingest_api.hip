@@ -1,6 +1,7 @@
 // pjb_ingest_api.hip -- the part of the C ABI that takes file bytes: BGZF inflate / deflate on the device, BAM record boundaries and transcoding
-// (pjb_inflate_bgzf, pjb_deflate_bgzf, pjb_submit_bam, pjb_bam_*, pjb_index_*, pjb_bam_merge_*, pjb_bam_sort_*); kernels in pjb_ingest.hip.h, pjb_deflate.hip.h,
-// pjb_index.hip.h and pjb_merge.hip.h.
+// (pjb_inflate_bgzf, pjb_deflate_bgzf, pjb_submit_bam, pjb_bam_begin / _piece / _end here; pjb_index_* in pjb_index_api.hip.h, pjb_bam_merge_* in
+// pjb_merge_api.hip.h, pjb_bam_sort_* in pjb_sort_api.hip.h, host code included below, behind the drivers they share); kernels in pjb_ingest.hip.h,
+// pjb_deflate.hip.h, pjb_index.hip.h and pjb_merge.hip.h.
 #include "pjb_host.hip.h"
 #include "pjb_deflate.hip.h"
 #include "pjb_ingest.hip.h"
@@ -14,7 +15,10 @@ int ingest_lds_bytes() { return I3_LDS_BYTES; }
 // ---- device-side ingest ---------------------------------------------------------------------------
 // Each step has one driver, whoever asks: bgzf_header (a block header through a byte reader: scan_bgzf over a buffer, stage_scan over
 // pieces), inflate_queue (one inflate launch on a stream: inflate_on_device waits for it, inflate_early does not), walk_records (record
-// boundaries of a target's region or, `all`, of an indexer's piece), upload_host (host bytes to the device).
+// boundaries of a target's region or, `all`, of an indexer's piece), upload_host (host bytes to the device), upload_padded + inflate_into
+// (the piece prologue: a call's BGZF bytes up, padded, and inflated into the buffer the caller names), piece_records (every complete
+// record of a piece: the index and the sort), write_members (ordered records -> BGZF members: the merge and the sort), op_leave (what a
+// failing call of a piece-wise operation leaves).
 const char *inf_text(int code) {
     switch (code) {
     case INF_ERR_BTYPE: return "reserved DEFLATE block type";
@@ -203,7 +207,7 @@ extern "C" int pjb_inflate_bgzf(pjb_ctx *c, const uint8_t *comp, int64_t comp_by
 
 // BGZF deflate on the device (pjb_deflate.hip.h): at most DFL_LAUNCH_BLOCKS blocks per launch (1 GB of symbol scratch)
 constexpr int64_t DFL_LAUNCH_BLOCKS = 4096;
-// The launches of one deflate, whoever asks (pjb_deflate_bgzf: `host_in`, copied to b_dfl_in launch by launch; pjb_bam_merge_end: `dev_in`,
+// The launches of one deflate, whoever asks (pjb_deflate_bgzf: `host_in`, copied to b_dfl_in launch by launch; write_members: `dev_in`,
 // a stream that lies on the device already).  `n_bytes` are cut every `block_bytes`; for every launch `sink(b0, sizes, total, dst)` is
 // told the first block's number, the members' sizes and their sum, and says where in host memory the packed members go.
 template <typename Sink>
@@ -371,6 +375,117 @@ static int walk_records(pjb_ctx *c, const BamRegion &R, bool all, const char *wh
     return PJB_OK;
 }
 
+// ---- what the calls that take BGZF bytes share --------------------------------------------------------------------
+// The piece prologue in two halves (pjb_submit_bam times them apart): a call's BGZF bytes to b_inf_comp, INF_PAD zeroed bytes behind them;
+// then `blocks` of d_comp inflated into `out` -- b_inf_out or a Buf of the caller's, grown under the category the caller names -- with 64
+// zeroed bytes behind the `total` inflated ones.
+static int upload_padded(pjb_ctx *c, const uint8_t *comp, int64_t comp_bytes) {
+    int rc;
+    if ((rc = ensure(c, c->b_inf_comp, (size_t)comp_bytes + INF_PAD)) || (rc = upload_host(c, c->b_inf_comp.p, comp, (size_t)comp_bytes))) return rc;
+    HIP_TRY(c, hipMemsetAsync((uint8_t *)c->b_inf_comp.p + comp_bytes, 0, INF_PAD, c->stream));
+    return PJB_OK;
+}
+static int inflate_into(pjb_ctx *c, const uint8_t *d_comp, const std::vector<InfBlock> &blocks, int64_t total, Buf &out, MemCat cat) {
+    if (const int rc = ensure_cat(c, out, (size_t)total + 64, cat)) return rc;
+    HIP_TRY(c, hipMemsetAsync((uint8_t *)out.p + total, 0, 64, c->stream));
+    return inflate_on_device(c, d_comp, blocks, (uint8_t *)out.p);
+}
+
+// Every complete record of a piece, of whatever target (pjb_index_piece, pjb_bam_sort_piece): the blocks' layout, the inflated bytes in
+// `out`, the records' offsets in b_bam_rec, and how the piece ended -- PIECE_TAKEN: records up to next_u (`total`: the data ends on a
+// record's end; less: the rest starts the next piece); PIECE_CUT_AT_EOF: the last piece ends inside a record; PIECE_RECORD_TOO_LONG: the
+// first record is longer than the piece, nothing was taken.  The callers word what a cut means, each with its own offsets.
+enum PieceEnd { PIECE_TAKEN, PIECE_CUT_AT_EOF, PIECE_RECORD_TOO_LONG };
+struct PieceRecords {
+    std::vector<InfBlock> blocks;
+    int64_t total = 0; // inflated bytes
+    size_t n = 0;      // records
+    iu64 next_u = 0;   // the first byte that belongs to no complete record
+    PieceEnd end = PIECE_TAKEN;
+};
+// `who` heads the refusals; `held` records are the caller's already, and `too_many` refuses more than the ordinals hold
+static int piece_records(pjb_ctx *c, const char *who, const uint8_t *comp, int64_t comp_bytes, int32_t first_uoffset, int32_t last, Buf &out, MemCat cat, size_t held,
+                         const char *too_many, PieceRecords &P) {
+    int rc = scan_bgzf(c, comp, comp_bytes, P.blocks, P.total);
+    if (rc) return rc;
+    if ((int64_t)first_uoffset > P.total) return fail(c, PJB_ERR_ARG, "%s: first_uoffset %d lies behind the piece's %lld inflated bytes", who, first_uoffset, (long long)P.total);
+    P.next_u = (iu64)first_uoffset;
+    if ((int64_t)first_uoffset < P.total) {
+        if ((rc = upload_padded(c, comp, comp_bytes)) || (rc = inflate_into(c, (const uint8_t *)c->b_inf_comp.p, P.blocks, P.total, out, cat))) return rc;
+        RecordWalk w;
+        if ((rc = walk_records(c, bam_region(c, (const uint8_t *)out.p, P.total, first_uoffset, -1), true, "in the piece", w))) return rc;
+        if (w.n >= 0xffffff00ull || held + w.n >= 0xffffff00ull) return fail(c, PJB_ERR_ARG, "%s", too_many);
+        P.n = w.n;
+        P.next_u = w.next_u;
+    }
+    if (P.next_u < (iu64)P.total) P.end = last ? PIECE_CUT_AT_EOF : P.n == 0 ? PIECE_RECORD_TOO_LONG : PIECE_TAKEN;
+    return PJB_OK;
+}
+
+// What a piece-wise operation's state (IndexState, MergeState, SortRun) starts with, and what a failing call leaves of it: nothing to go
+// on with -- begin again -- unless the call set keep_on_error or, `spare_nomem`, ran out of device memory (the call can be repeated).
+struct PieceOp {
+    bool active = false;
+    bool keep_on_error = false; // the failing call left the operation as it was
+};
+static int op_leave(pjb_ctx *c, PieceOp *s, int rc, bool spare_nomem) {
+    if (rc && !(spare_nomem && rc == PJB_ERR_NOMEM) && !s->keep_on_error) {
+        (void)hipStreamSynchronize(c->stream);
+        s->active = false;
+    }
+    return rc;
+}
+template <typename State>
+static void op_clear(pjb_ctx *c, State *&s) { // (pjb_destroy: every state releases its own buffers)
+    if (s) s->release_all(c);
+    delete s;
+    s = nullptr;
+}
+
+// Ordered records as BGZF members (pjb_bam_merge_end, pjb_bam_sort_end): what the writer holds on the device and the result on the host.
+struct MemberWriter {
+    Buf dst, stream;                // every record's offset in the stream | the stream, 64 bytes of slack behind it
+    std::vector<uint32_t> r_size;   // the result: the members' sizes
+    std::vector<uint8_t> r_members; // and the members back to back
+    void release_all(pjb_ctx *c) { release(c, dst), release(c, stream); } // (a device buffer added above is added here)
+    void clear_result() { r_size.clear(), r_members.clear(); }
+    static int check_block_bytes(pjb_ctx *c, const char *who, int32_t block_bytes) {
+        if (block_bytes >= 4 && block_bytes <= (int32_t)DFL_IN_MAX && !(block_bytes & 3)) return PJB_OK;
+        return fail(c, PJB_ERR_ARG, "%s: block_bytes must be a multiple of 4 between 4 and %u", who, DFL_IN_MAX);
+    }
+    template <typename Result>
+    void result_to(Result *out) const { // (pjb_bam_merge_result, pjb_bam_sort_result)
+        out->n_members = (int32_t)r_size.size();
+        out->member_size = r_size.data();
+        out->members = r_members.data();
+        out->member_bytes = (int64_t)r_members.size();
+    }
+};
+// Records i = 0 .. n - 1 of `size[i]` bytes at `src[i]`, taken in `order` (null: as they are), gathered into one stream and deflated in
+// members of `block_bytes`: the scan (timed as `scan_label`, its total in `d_total`) places them, mg_gather copies them.
+static int write_members(pjb_ctx *c, MemberWriter &w, const iu32 *size, const iu64 *src, const iu32 *order, size_t n, const char *scan_label, u64 *d_total,
+                         int32_t block_bytes, int64_t *raw_bytes) {
+    hipStream_t st = c->stream;
+    int rc;
+    if ((rc = ensure(c, w.dst, n * 8))) return rc;
+    if ((rc = run_scan(c, scan_label, MgSizeFn{size, order}, MgOffsetSink{(iu64 *)w.dst.p}, n, d_total))) return rc;
+    iu64 raw = 0;
+    HIP_TRY(c, hipMemcpyAsync(&raw, d_total, 8, hipMemcpyDeviceToHost, st));
+    HIP_TRY(c, hipStreamSynchronize(st));
+    if ((rc = ensure_cat(c, w.stream, (size_t)raw + 64, MEM_STAGING))) return rc;
+    LAUNCH(c, "mg_gather", mg_gather, dim3((unsigned)((n + 3) / 4)), dim3(256), src, size, order, (const iu64 *)w.dst.p, (iu64)n, (uint8_t *)w.stream.p);
+    rc = deflate_launches(c, nullptr, (const uint8_t *)w.stream.p, (int64_t)raw, block_bytes, [&](int64_t, const std::vector<u32> &sizes, iu64 total, uint8_t *&dst) {
+        const size_t had = w.r_members.size();
+        w.r_size.insert(w.r_size.end(), sizes.begin(), sizes.end());
+        w.r_members.resize(had + (size_t)total);
+        dst = w.r_members.data() + had;
+        return (int)PJB_OK;
+    });
+    if (rc) w.clear_result();
+    else *raw_bytes = (int64_t)raw;
+    return rc;
+}
+
 // the inflated bytes of one target's region (d_out, `total` of them followed by 64 zero bytes) -> the SoA batch of the target
 static int ingest_parse(pjb_ctx *c, int32_t tid, OpenContig &oc, const uint8_t *d_out, size_t n_blocks, int64_t comp_bytes, int64_t total,
                         int32_t first_uoffset, int64_t *n_records, double t_scan, double t_up, double t_inf) {
@@ -473,10 +588,8 @@ static int ingest_parse(pjb_ctx *c, int32_t tid, OpenContig &oc, const uint8_t *
 static int ingest_staged(pjb_ctx *c, int32_t tid, OpenContig &oc, const uint8_t *d_comp, const std::vector<InfBlock> &blocks, int64_t comp_bytes,
                          int64_t total, int32_t first_uoffset, int64_t *n_records, double t_scan, double t_up) {
     const double t0 = wall_now();
-    int rc;
-    if ((rc = ensure(c, c->b_inf_out, (size_t)total + 64))) return rc;
-    HIP_TRY(c, hipMemsetAsync((uint8_t *)c->b_inf_out.p + total, 0, 64, c->stream));
-    if ((rc = inflate_on_device(c, d_comp, blocks, (uint8_t *)c->b_inf_out.p))) return rc;
+    const int rc = inflate_into(c, d_comp, blocks, total, c->b_inf_out, MEM_SCRATCH);
+    if (rc) return rc;
     return ingest_parse(c, tid, oc, (const uint8_t *)c->b_inf_out.p, blocks.size(), comp_bytes, total, first_uoffset, n_records, t_scan, t_up, wall_now() - t0);
 }
 
@@ -508,11 +621,8 @@ static int submit_bam_body(pjb_ctx *c, int32_t tid, OpenContig &oc, const uint8_
     if (total == 0 || (int64_t)first_uoffset >= total) return PJB_OK;
     t_scan = wall_now() - t0;
     t0 = wall_now();
-    hipStream_t st = c->stream;
-    if ((rc = ensure(c, c->b_inf_comp, (size_t)comp_bytes + INF_PAD))) return rc;
-    if ((rc = upload_host(c, c->b_inf_comp.p, comp, (size_t)comp_bytes))) return rc;
-    HIP_TRY(c, hipMemsetAsync((uint8_t *)c->b_inf_comp.p + comp_bytes, 0, INF_PAD, st));
-    if (prof) (void)hipStreamSynchronize(st);
+    if ((rc = upload_padded(c, comp, comp_bytes))) return rc;
+    if (prof) (void)hipStreamSynchronize(c->stream);
     t_up = wall_now() - t0;
     return ingest_staged(c, tid, oc, (const uint8_t *)c->b_inf_comp.p, blocks, comp_bytes, total, first_uoffset, n_records, t_scan, t_up);
 }
@@ -625,29 +735,6 @@ static int stage_scan(pjb_ctx *c, BamStage &st, const uint8_t *p, int64_t p_at, 
         st.next += bsize;
     }
     return PJB_OK;
-}
-
-static void index_clear(pjb_ctx *c);
-static void merge_clear(pjb_ctx *c);
-static void sort_clear(pjb_ctx *c);
-void bam_stage_clear(pjb_ctx *c) {
-    index_clear(c);
-    merge_clear(c);
-    sort_clear(c);
-    for (auto &is : c->inf_streams)
-        if (is) (void)hipStreamSynchronize(is);
-    for (auto &kv : c->bam_stage) {
-        stage_release(c, *kv.second);
-        delete kv.second;
-    }
-    c->bam_stage.clear();
-    release_pooled_stage(c);
-    for (auto &is : c->inf_streams)
-        if (is) (void)hipStreamDestroy(is);
-    for (auto &ev : c->up_events)
-        if (ev) (void)hipEventDestroy(ev);
-    if (c->ev_up) (void)hipEventDestroy(c->ev_up);
-    if (c->stream_up) (void)hipStreamDestroy(c->stream_up);
 }
 
 extern "C" int pjb_bam_begin(pjb_ctx *c, int32_t tid, int64_t total_bytes) {
@@ -824,860 +911,27 @@ static int bam_end_body(pjb_ctx *c, int32_t tid, BamStage &stage, int32_t first_
 }
 
 
-// ---- the BAM index of a sorted file, piece by piece (pjb_index_begin / _piece / _end, see the header; kernels in pjb_index.hip.h) ---------
-struct IndexState {
-    bool active = false, saw_last = false;
-    bool keep_on_error = false;   // the failing piece call left the index as it was
-    int csi_depth = -1;           // < 0: a BAI; 0 .. 6: a CSI of that depth (pjb_index_begin_csi)
-    int64_t n_records = 0;
-    iu64 prev_sort = 0;           // (refID unsigned) << 32 | pos of the last record seen
-    iu64 open_key = BAI_NOKEY;    // (target, bin) of the run the last record belongs to: its chunk is the list's last, its end open
-    iu64 win_carry = 0;           // running window maximum
-    iu64 end_voffset = 0;         // where the data ended (the last piece)
-    size_t n_chunks = 0;
-    Buf chunks;                   // BaiChunk[n_chunks], file order
-    Buf lin, ref_len, lin_off;    // u64 per window of every target (0: untouched) | i32[n_ref] | u64[n_ref + 1]
-    size_t lin_total = 0;
-    std::vector<iu64> h_lin_cap;  // lin_off on the host
-    Buf key, vs, win, w0, heads, tab, ctl, tile_max; // a piece's scratch
-    Buf q[4], tid_start, sorted;  // pjb_index_end (q[3]: the seventh level, a CSI of depth 6)
-    Buf loff;                     // pjb_index_end_csi: u64 per ordered chunk
-    // the result
-    std::vector<pjb_index_chunk> r_chunks;
-    std::vector<int64_t> r_lin_off;
-    std::vector<uint64_t> r_lin;
-    std::vector<uint64_t> r_loff;
-};
-static_assert(sizeof(BaiChunk) == sizeof(pjb_index_chunk) && sizeof(pjb_index_chunk) == 24, "chunk layout");
+// ---- prep's operations: a header each, host code over the drivers above ----------------------------------------
+#include "pjb_index_api.hip.h" // pjb_index_*: the BAI / CSI of a sorted file
+#include "pjb_merge_api.hip.h" // pjb_bam_merge_*: one target of several sorted files
+#include "pjb_sort_api.hip.h"  // pjb_bam_sort_*: an unsorted file, run by run
 
-static void index_clear(pjb_ctx *c) {
-    IndexState *x = c->index;
-    if (!x) return;
-    for (Buf *b : {&x->chunks, &x->lin, &x->ref_len, &x->lin_off, &x->key, &x->vs, &x->win, &x->w0, &x->heads, &x->tab, &x->ctl, &x->tile_max, &x->q[0], &x->q[1],
-                   &x->q[2], &x->q[3], &x->tid_start, &x->sorted, &x->loff})
-        release(c, *b);
-    delete x;
-    c->index = nullptr;
-}
-
-extern "C" int pjb_csi_depth(const int32_t *ref_len, int32_t n_ref) {
-    int64_t longest = 0;
-    for (int32_t t = 0; ref_len && t < n_ref; t++) longest = std::max<int64_t>(longest, ref_len[t]);
-    longest += 256; // (htslib's margin, sam.c bam_index_build: the smallest depth whose root bin covers the longest target + 256)
-    int depth = 0;
-    for (int64_t s = 1ll << CSI_MIN_SHIFT; s < longest; s <<= 3) depth++;
-    return depth;
-}
-
-static int index_begin_body(pjb_ctx *c, int csi_depth) {
-    HIP_TRY(c, hipSetDevice(c->cfg.device));
-    if (!c->index) c->index = new (std::nothrow) IndexState();
-    IndexState *x = c->index;
-    if (!x) return fail(c, PJB_ERR_NOMEM, "index_begin: out of host memory");
-    x->active = false;
-    x->saw_last = false;
-    x->csi_depth = csi_depth;
-    x->n_records = 0;
-    x->prev_sort = 0;
-    x->open_key = BAI_NOKEY;
-    x->win_carry = 0;
-    x->end_voffset = 0;
-    x->n_chunks = 0;
-    x->r_chunks.clear();
-    x->r_lin_off.clear();
-    x->r_lin.clear();
-    x->r_loff.clear();
-    // a window of 16 kb per 2^14 bases of every target reg2bin covers (a record on a longer one is refused when it is met); of
-    // every target for a CSI
-    const size_t n_ref = c->ref_len.size();
-    x->h_lin_cap.assign(n_ref + 1, 0);
-    for (size_t t = 0; t < n_ref; t++) {
-        const int32_t len = c->ref_len[t];
-        x->h_lin_cap[t + 1] = x->h_lin_cap[t] + (len > 0 && (csi_depth >= 0 || len < BAI_MAX_LEN) ? ((iu64)len + 16383) >> 14 : 0);
+void bam_stage_clear(pjb_ctx *c) {
+    op_clear(c, c->index);
+    op_clear(c, c->merge);
+    op_clear(c, c->sort_run);
+    for (auto &is : c->inf_streams)
+        if (is) (void)hipStreamSynchronize(is);
+    for (auto &kv : c->bam_stage) {
+        stage_release(c, *kv.second);
+        delete kv.second;
     }
-    x->lin_total = (size_t)x->h_lin_cap[n_ref];
-    int rc;
-    if ((rc = ensure(c, x->lin, x->lin_total * 8 + 8)) || (rc = ensure(c, x->ref_len, n_ref * 4 + 4)) || (rc = ensure(c, x->lin_off, (n_ref + 1) * 8)) ||
-        (rc = ensure(c, x->ctl, BAI_CTL_WORDS * 8)))
-        return rc;
-    hipStream_t st = c->stream;
-    HIP_TRY(c, hipMemsetAsync(x->lin.p, 0, x->lin_total * 8 + 8, st));
-    if (n_ref) HIP_TRY(c, hipMemcpyAsync(x->ref_len.p, c->ref_len.data(), n_ref * 4, hipMemcpyHostToDevice, st));
-    HIP_TRY(c, hipMemcpyAsync(x->lin_off.p, x->h_lin_cap.data(), (n_ref + 1) * 8, hipMemcpyHostToDevice, st));
-    HIP_TRY(c, hipStreamSynchronize(st));
-    x->active = true;
-    return PJB_OK;
-}
-
-extern "C" int pjb_index_begin(pjb_ctx *c) {
-    if (!c) return PJB_ERR_ARG;
-    return index_begin_body(c, -1);
-}
-
-extern "C" int pjb_index_begin_csi(pjb_ctx *c, int32_t depth) {
-    if (!c) return PJB_ERR_ARG;
-    if (c->index) c->index->active = false; // (as pjb_index_begin: an index that was being built is dropped, whatever comes of this call)
-    if (depth > CSI_MAX_DEPTH) return fail(c, PJB_ERR_ARG, "index_begin_csi: a depth of %d is not supported (0 .. %d, or a negative one for the smallest that fits)", depth, CSI_MAX_DEPTH);
-    if (depth < 0) depth = pjb_csi_depth(c->ref_len.data(), (int32_t)c->ref_len.size());
-    if (depth > CSI_MAX_DEPTH) return fail(c, PJB_ERR_ARG, "index_begin_csi: no depth up to %d covers the longest target", CSI_MAX_DEPTH);
-    // the BAI's rule (BAI_MAX_LEN) at every depth: a target of 2^(14 + 3 depth) bases or more is not binned.  Depth 0 has the one bin
-    // that holds whatever there is.
-    for (size_t t = 0; depth > 0 && t < c->ref_len.size(); t++)
-        if ((int64_t)c->ref_len[t] >= 1ll << (CSI_MIN_SHIFT + 3 * depth))
-            return fail(c, PJB_ERR_ARG, "index_begin_csi: a CSI of depth %d bins targets of less than 2^%d bases, target %zu has %d", depth,
-                        CSI_MIN_SHIFT + 3 * depth, t, c->ref_len[t]);
-    return index_begin_body(c, depth);
-}
-
-// a chunk list that must hold `need` chunks: a larger buffer takes over what the list holds
-static int index_grow_chunks(pjb_ctx *c, IndexState *x, size_t need) {
-    if (need * sizeof(BaiChunk) <= x->chunks.cap && x->chunks.p) return PJB_OK;
-    Buf nb;
-    int rc = ensure(c, nb, std::max<size_t>(need * 2, 4096) * sizeof(BaiChunk));
-    if (rc) return rc;
-    if (x->n_chunks) HIP_TRY(c, hipMemcpyAsync(nb.p, x->chunks.p, x->n_chunks * sizeof(BaiChunk), hipMemcpyDeviceToDevice, c->stream));
-    if (x->chunks.p) bury(c, x->chunks.p); // (the copy is on the stream: freed where a wait costs nothing)
-    x->chunks = nb;
-    return PJB_OK;
-}
-
-static int index_piece_body(pjb_ctx *c, IndexState *x, const uint8_t *comp, int64_t comp_bytes, int64_t file_offset, int32_t first_uoffset, int32_t last,
-                            uint64_t *next_voffset) {
-    std::vector<InfBlock> blocks;
-    int64_t total = 0;
-    int rc = scan_bgzf(c, comp, comp_bytes, blocks, total);
-    if (rc) return rc;
-    if ((int64_t)first_uoffset > total) return fail(c, PJB_ERR_ARG, "index_piece: first_uoffset %d lies behind the piece's %lld inflated bytes", first_uoffset, (long long)total);
-    // block starts: inflated offset | file offset, + the sentinel "end of the data, the file's next block"
-    const size_t nb = blocks.size();
-    std::vector<iu64> tab(2 * (nb + 1));
-    {
-        int64_t off = 0;
-        for (size_t b = 0; b < nb; b++) {
-            tab[b] = blocks[b].out_off;
-            tab[nb + 1 + b] = (iu64)(file_offset + off);
-            off = (int64_t)blocks[b].in_off + blocks[b].in_len + 8; // (the payload, CRC32 and ISIZE: the next block's first byte)
-        }
-        tab[nb] = (iu64)total;
-        tab[2 * nb + 1] = (iu64)(file_offset + comp_bytes);
-    }
-    auto voffset_of = [&](iu64 u) -> uint64_t { // bai_block_of on the host
-        size_t lo = 0, hi = nb + 1;
-        while (lo < hi) {
-            const size_t mid = lo + (hi - lo) / 2;
-            if (tab[mid] < u) lo = mid + 1;
-            else hi = mid;
-        }
-        if ((lo == nb + 1 || tab[lo] > u) && lo > 0) lo--;
-        return tab[nb + 1 + lo] << 16 | (u - tab[lo]);
-    };
-    size_t n = 0;
-    iu64 next_u = (iu64)first_uoffset;
-    hipStream_t st = c->stream;
-    if ((int64_t)first_uoffset < total) {
-        if ((rc = ensure(c, c->b_inf_comp, (size_t)comp_bytes + INF_PAD))) return rc;
-        if ((rc = upload_host(c, c->b_inf_comp.p, comp, (size_t)comp_bytes))) return rc;
-        HIP_TRY(c, hipMemsetAsync((uint8_t *)c->b_inf_comp.p + comp_bytes, 0, INF_PAD, st));
-        if ((rc = ensure(c, c->b_inf_out, (size_t)total + 64))) return rc;
-        HIP_TRY(c, hipMemsetAsync((uint8_t *)c->b_inf_out.p + total, 0, 64, st));
-        if ((rc = inflate_on_device(c, (const uint8_t *)c->b_inf_comp.p, blocks, (uint8_t *)c->b_inf_out.p))) return rc;
-        // every record that lies completely in the inflated bytes, of whatever target
-        RecordWalk w;
-        if ((rc = walk_records(c, bam_region(c, (const uint8_t *)c->b_inf_out.p, total, first_uoffset, -1), true, "in the piece", w))) return rc;
-        if (w.n >= 0xffffff00ull) return fail(c, PJB_ERR_ARG, "index_piece: more than 2^32 alignments in one piece are not supported");
-        n = w.n;
-        next_u = w.next_u;
-    }
-    if (next_u < (iu64)total) { // the data ends inside a record
-        if (last) return fail(c, PJB_ERR_BGZF, "the data ends inside an alignment record (virtual offset 0x%llx): truncated file", (unsigned long long)voffset_of(next_u));
-        if (n == 0) { // nothing was indexed and nothing changed: the caller may hand the same blocks over again with more behind them
-            x->keep_on_error = true;
-            if (next_voffset) *next_voffset = voffset_of(next_u);
-            return fail(c, PJB_ERR_ARG, "index_piece: the alignment record at virtual offset 0x%llx is longer than the piece (%lld bytes): hand over more blocks at once",
-                        (unsigned long long)voffset_of(next_u), (long long)comp_bytes);
-        }
-    }
-    if (n > 0) {
-        if ((rc = ensure(c, x->key, n * 8)) || (rc = ensure(c, x->vs, n * 8)) || (rc = ensure(c, x->win, n * 8)) || (rc = ensure(c, x->w0, n * 4)) ||
-            (rc = ensure(c, x->heads, n * 4)) || (rc = ensure(c, x->tab, tab.size() * 8)))
-            return rc;
-        iu64 *ctl = (iu64 *)x->ctl.p;
-        HIP_TRY(c, hipMemsetAsync(ctl, 0xff, BAI_CTL_WORDS * 8, st));
-        HIP_TRY(c, hipMemcpyAsync(x->tab.p, tab.data(), tab.size() * 8, hipMemcpyHostToDevice, st));
-        BaiTable T;
-        T.out_off = (const iu64 *)x->tab.p;
-        T.cstart = T.out_off + nb + 1;
-        T.n = (iu32)(nb + 1);
-        BaiRecOut O;
-        O.key = (iu64 *)x->key.p;
-        O.vs = (iu64 *)x->vs.p;
-        O.win = (iu64 *)x->win.p;
-        O.w0 = (iu32 *)x->w0.p;
-        O.ctl = ctl;
-        const iu64 *rec_off = (const iu64 *)c->b_bam_rec.p;
-        const unsigned grid = (unsigned)((n + 255) / 256);
-        LAUNCH(c, "bai_records", bai_records, dim3(grid), dim3(256), (const uint8_t *)c->b_inf_out.p, rec_off, (iu64)n, T, (const int32_t *)x->ref_len.p,
-               (int32_t)c->ref_len.size(), x->prev_sort, x->csi_depth, O);
-        if ((rc = run_scan(c, "bai_head", BaiHeadFn{O.key, x->open_key}, ExclusiveU32Sink{(u32 *)x->heads.p}, n, (u64 *)(ctl + BAI_CTL_HEADS)))) return rc;
-        iu64 h[BAI_CTL_WORDS];
-        HIP_TRY(c, hipMemcpyAsync(h, ctl, sizeof h, hipMemcpyDeviceToHost, st));
-        HIP_TRY(c, hipStreamSynchronize(st));
-        // the first offender decides (a record that cannot be is usually out of order as well)
-        const iu64 first_err = std::min(h[BAI_CTL_UNSORTED], std::min(h[BAI_CTL_BAD], h[BAI_CTL_LONG]));
-        if (first_err != ~0ull) {
-            const long long ord = (long long)(x->n_records + (int64_t)first_err);
-            if (h[BAI_CTL_BAD] == first_err)
-                return fail(c, PJB_ERR_BGZF, "alignment record %lld names a target or a position the header does not have (refID beyond the %zu targets, or pos outside its target)",
-                            ord, c->ref_len.size());
-            if (h[BAI_CTL_LONG] == first_err)
-                return fail(c, PJB_ERR_ARG, "BAI cannot index this target: alignment record %lld lies on a target of 2^29 bases or more (a CSI index is needed)", ord);
-            return fail(c, PJB_ERR_UNSORTED, "%s (alignment record %lld lies before its predecessor)", err_text(PJB_ERR_UNSORTED), ord);
-        }
-        const size_t n_heads = (size_t)h[BAI_CTL_HEADS];
-        if (x->n_chunks + n_heads >= 0xffffff00ull) return fail(c, PJB_ERR_ARG, "index_piece: more than 2^32 chunks are not supported");
-        if ((rc = index_grow_chunks(c, x, x->n_chunks + n_heads))) return rc;
-        LAUNCH(c, "bai_chunks", bai_chunks, dim3(grid), dim3(256), (const iu64 *)O.key, (const iu64 *)O.vs, (const iu32 *)x->heads.p, (iu64)n, x->open_key,
-               (BaiChunk *)x->chunks.p, (iu64)x->n_chunks, (iu64)(x->n_chunks + n_heads));
-        const iu32 nt = (iu32)((n + SCAN_TILE - 1) / SCAN_TILE);
-        if ((rc = ensure(c, x->tile_max, (size_t)nt * 8))) return rc;
-        LAUNCH(c, "bai_win_reduce", bai_win_reduce, dim3(nt), dim3(256), (const iu64 *)O.win, (iu64)n, (iu64 *)x->tile_max.p);
-        LAUNCH(c, "bai_win_tiles", bai_win_tiles, dim3(1), dim3(1024), (iu64 *)x->tile_max.p, nt, x->win_carry, ctl + BAI_CTL_WINMAX);
-        LAUNCH(c, "bai_win_apply", bai_win_apply, dim3(nt), dim3(256), (const iu64 *)O.win, (const iu32 *)O.w0, (const iu64 *)O.vs, (iu64)n,
-               (const iu64 *)x->tile_max.p, (const iu64 *)x->lin_off.p, (iu64 *)x->lin.p, (iu64)x->lin_total);
-        iu64 win_max = 0;
-        HIP_TRY(c, hipMemcpyAsync(&win_max, ctl + BAI_CTL_WINMAX, 8, hipMemcpyDeviceToHost, st));
-        HIP_TRY(c, hipStreamSynchronize(st));
-        if (c->ktime) ev_collect(c, MISC_POOL);
-        x->n_chunks += n_heads;
-        x->n_records += (int64_t)n;
-        x->prev_sort = h[BAI_CTL_LASTSORT];
-        x->open_key = h[BAI_CTL_LASTKEY];
-        x->win_carry = win_max;
-    }
-    const uint64_t nv = voffset_of(next_u);
-    if (next_voffset) *next_voffset = nv;
-    if (last) {
-        x->saw_last = true;
-        x->end_voffset = nv;
-    }
-    return PJB_OK;
-}
-
-extern "C" int pjb_index_piece(pjb_ctx *c, const uint8_t *comp, int64_t comp_bytes, int64_t file_offset, int32_t first_uoffset, int32_t last,
-                               uint64_t *next_voffset) {
-    if (!c) return PJB_ERR_ARG;
-    IndexState *x = c->index;
-    if (!x || !x->active) return fail(c, PJB_ERR_STATE, "index_piece: no index is being built (pjb_index_begin)");
-    if (x->saw_last) return fail(c, PJB_ERR_STATE, "index_piece: the last piece has been handed over (pjb_index_end)");
-    if (comp_bytes < 0 || (comp_bytes && !comp) || file_offset < 0 || first_uoffset < 0) return fail(c, PJB_ERR_ARG, "index_piece: bad arguments");
-    HIP_TRY(c, hipSetDevice(c->cfg.device));
-    x->keep_on_error = false;
-    const int rc = index_piece_body(c, x, comp, comp_bytes, file_offset, first_uoffset, last, next_voffset);
-    if (rc && !x->keep_on_error) { // the index is dropped: begin again
-        (void)hipStreamSynchronize(c->stream);
-        x->active = false;
-    }
-    return rc;
-}
-
-// closes the last chunk and orders the list by (target, bin, file order) into x->sorted, the copy to x->r_chunks queued
-static int index_order_chunks(pjb_ctx *c, IndexState *x) {
-    hipStream_t st = c->stream;
-    const size_t n = x->n_chunks, n_ref = c->ref_len.size();
-    int rc;
-    x->r_chunks.assign(n, pjb_index_chunk());
-    if (n) {
-        BaiChunk *chunks = (BaiChunk *)x->chunks.p;
-        // the last run ends where the data ends
-        if (x->open_key != BAI_NOKEY) HIP_TRY(c, hipMemcpyAsync(&chunks[n - 1].vend, &x->end_voffset, 8, hipMemcpyHostToDevice, st));
-        const int n_scans = x->csi_depth > 5 ? 4 : 3; // two levels a scan
-        for (int p = 0; p < n_scans; p++)
-            if ((rc = ensure(c, x->q[p], (n + 1) * 8))) return rc;
-        if ((rc = ensure(c, x->tid_start, (n_ref + 1) * 4)) || (rc = ensure(c, x->sorted, n * sizeof(BaiChunk)))) return rc;
-        iu64 *ctl = (iu64 *)x->ctl.p;
-        for (int p = 0; p < n_scans; p++)
-            if ((rc = run_scan(c, "bai_level", BaiLevelFn{chunks, (iu64)n, (iu32)p}, BaiLevelSink{(iu64 *)x->q[p].p}, n + 1, (u64 *)(ctl + BAI_CTL_HEADS)))) return rc;
-        LAUNCH(c, "bai_tid_starts", bai_tid_starts, dim3((unsigned)((n + 256) / 256)), dim3(256), (const BaiChunk *)chunks, (iu64)n, (int32_t)n_ref, (iu32 *)x->tid_start.p);
-        LAUNCH(c, "bai_partition", bai_partition, dim3((unsigned)((n + 255) / 256)), dim3(256), (const BaiChunk *)chunks, (iu64)n, (int32_t)n_ref,
-               (const iu32 *)x->tid_start.p, (const iu64 *)x->q[0].p, (const iu64 *)x->q[1].p, (const iu64 *)x->q[2].p, (const iu64 *)(n_scans > 3 ? x->q[3].p : nullptr), (BaiChunk *)x->sorted.p);
-        HIP_TRY(c, hipMemcpyAsync(x->r_chunks.data(), x->sorted.p, n * sizeof(BaiChunk), hipMemcpyDeviceToHost, st));
-    }
-    return PJB_OK;
-}
-
-extern "C" int pjb_index_end(pjb_ctx *c, pjb_index_result *out) {
-    if (!c || !out) return fail(c, PJB_ERR_ARG, "index_end: bad arguments");
-    IndexState *x = c->index;
-    if (!x || !x->active) return fail(c, PJB_ERR_STATE, "index_end: no index is being built (pjb_index_begin)");
-    if (x->csi_depth >= 0) return fail(c, PJB_ERR_STATE, "index_end: a CSI is being built (pjb_index_end_csi)");
-    if (!x->saw_last) return fail(c, PJB_ERR_STATE, "index_end: the last piece has not been handed over (pjb_index_piece with last != 0)");
-    HIP_TRY(c, hipSetDevice(c->cfg.device));
-    x->active = false;
-    hipStream_t st = c->stream;
-    const size_t n = x->n_chunks, n_ref = c->ref_len.size();
-    int rc;
-    if ((rc = index_order_chunks(c, x))) return rc;
-    // the windows: per target up to the last one a record touched (every touched window holds a virtual offset, and none is 0)
-    std::vector<uint64_t> all(x->lin_total);
-    if (x->lin_total) HIP_TRY(c, hipMemcpyAsync(all.data(), x->lin.p, x->lin_total * 8, hipMemcpyDeviceToHost, st));
-    HIP_TRY(c, hipStreamSynchronize(st));
-    if (c->ktime) ev_collect(c, MISC_POOL);
-    x->r_lin_off.assign(n_ref + 1, 0);
-    x->r_lin.clear();
-    for (size_t t = 0; t < n_ref; t++) {
-        const size_t a = (size_t)x->h_lin_cap[t];
-        size_t k = (size_t)x->h_lin_cap[t + 1] - a;
-        while (k > 0 && all[a + k - 1] == 0) k--;
-        x->r_lin.insert(x->r_lin.end(), all.begin() + (long)a, all.begin() + (long)(a + k));
-        x->r_lin_off[t + 1] = (int64_t)x->r_lin.size();
-    }
-    out->n_records = x->n_records;
-    out->n_chunks = (int64_t)n;
-    out->chunks = x->r_chunks.data();
-    out->lin_off = x->r_lin_off.data();
-    out->lin = x->r_lin.data();
-    return PJB_OK;
-}
-
-extern "C" int pjb_index_end_csi(pjb_ctx *c, pjb_csi_result *out) {
-    if (!c || !out) return fail(c, PJB_ERR_ARG, "index_end_csi: bad arguments");
-    IndexState *x = c->index;
-    if (!x || !x->active) return fail(c, PJB_ERR_STATE, "index_end_csi: no index is being built (pjb_index_begin_csi)");
-    if (x->csi_depth < 0) return fail(c, PJB_ERR_STATE, "index_end_csi: a BAI is being built (pjb_index_end)");
-    if (!x->saw_last) return fail(c, PJB_ERR_STATE, "index_end_csi: the last piece has not been handed over (pjb_index_piece with last != 0)");
-    HIP_TRY(c, hipSetDevice(c->cfg.device));
-    x->active = false;
-    hipStream_t st = c->stream;
-    const size_t n = x->n_chunks, n_ref = c->ref_len.size();
-    int rc;
-    if ((rc = index_order_chunks(c, x))) return rc;
-    x->r_loff.assign(n, 0);
-    if (n && x->lin_total) {
-        // the windows filled from the left (tid_start is index_order_chunks'), then every chunk's bin reads its first one
-        if ((rc = ensure(c, x->loff, n * 8))) return rc;
-        const iu32 nt = (iu32)((x->lin_total + SCAN_TILE - 1) / SCAN_TILE);
-        if ((rc = ensure(c, x->tile_max, (size_t)nt * 8))) return rc;
-        iu64 *ctl = (iu64 *)x->ctl.p, *lin = (iu64 *)x->lin.p;
-        LAUNCH(c, "csi_seed", csi_seed, dim3((unsigned)((n_ref + 255) / 256)), dim3(256), (const BaiChunk *)x->chunks.p, (const iu32 *)x->tid_start.p, (int32_t)n_ref,
-               (const iu64 *)x->lin_off.p, lin, (iu64)x->lin_total);
-        LAUNCH(c, "bai_win_reduce", bai_win_reduce, dim3(nt), dim3(256), (const iu64 *)lin, (iu64)x->lin_total, (iu64 *)x->tile_max.p);
-        LAUNCH(c, "bai_win_tiles", bai_win_tiles, dim3(1), dim3(1024), (iu64 *)x->tile_max.p, nt, (iu64)0, ctl + BAI_CTL_WINMAX);
-        LAUNCH(c, "csi_fill_apply", csi_fill_apply, dim3(nt), dim3(256), lin, (iu64)x->lin_total, (const iu64 *)x->tile_max.p);
-        LAUNCH(c, "csi_loffset", csi_loffset, dim3((unsigned)((n + 255) / 256)), dim3(256), (const BaiChunk *)x->sorted.p, (iu64)n, (int32_t)n_ref, x->csi_depth,
-               (const iu64 *)x->lin_off.p, (const iu64 *)lin, (iu64)x->lin_total, (iu64 *)x->loff.p);
-        HIP_TRY(c, hipMemcpyAsync(x->r_loff.data(), x->loff.p, n * 8, hipMemcpyDeviceToHost, st));
-    }
-    HIP_TRY(c, hipStreamSynchronize(st));
-    if (c->ktime) ev_collect(c, MISC_POOL);
-    out->n_records = x->n_records;
-    out->n_chunks = (int64_t)n;
-    out->chunks = x->r_chunks.data();
-    out->loffset = x->r_loff.data();
-    out->min_shift = CSI_MIN_SHIFT;
-    out->depth = x->csi_depth;
-    return PJB_OK;
-}
-
-
-// ---- several sorted files' records of one target as one stream (pjb_bam_merge_begin / _file / _end, see the header; kernels in pjb_merge.hip.h) ----
-struct MergeFile {
-    bool given = false;
-    size_t n = 0;       // its records on the target
-    Buf out;            // its inflated bytes, 64 zeroed bytes behind them
-    Buf key, size, src; // per record: pos | 4 + block_size | where it lies in `out`
-};
-struct MergeState {
-    bool active = false;
-    int32_t tid = -1;
-    std::vector<MergeFile> files;
-    SortU32 sort;                              // all files' keys, file after file, and what the passes need
-    Buf size, src;                             // all files' sizes and places
-    Buf dst, ctl, stream;                      // offsets in the merged stream | MG_CTL_* and the passes' record count | the merged stream
-    uint32_t h_n = 0;                          // (copied to the device asynchronously)
-    // the result
-    std::vector<uint32_t> r_size;
-    std::vector<uint8_t> r_members;
-};
-
-static void merge_file_release(pjb_ctx *c, MergeFile &f) {
-    for (Buf *b : {&f.out, &f.key, &f.size, &f.src}) release(c, *b);
-}
-static void merge_clear(pjb_ctx *c) {
-    MergeState *m = c->merge;
-    if (!m) return;
-    for (MergeFile &f : m->files) merge_file_release(c, f);
-    SortU32 &s = m->sort;
-    for (Buf *b : {&s.key[0], &s.key[1], &s.idx[0], &s.idx[1], &s.hist, &s.hist_part, &s.hist_scan, &s.bin_total, &m->size, &m->src, &m->dst, &m->ctl, &m->stream})
-        release(c, *b);
-    delete m;
-    c->merge = nullptr;
-}
-// what a failing call leaves: nothing to go on with, except after PJB_ERR_NOMEM (the call can be repeated)
-static int merge_leave(pjb_ctx *c, MergeState *m, int rc) {
-    if (rc && rc != PJB_ERR_NOMEM) {
-        (void)hipStreamSynchronize(c->stream);
-        m->active = false;
-    }
-    return rc;
-}
-
-extern "C" int pjb_bam_merge_begin(pjb_ctx *c, int32_t tid, int32_t n_files) {
-    if (!c) return PJB_ERR_ARG;
-    if (c->merge) c->merge->active = false;
-    if (tid < 0 || (size_t)tid >= c->ref_len.size() || n_files < 1) return fail(c, PJB_ERR_ARG, "bam_merge_begin: bad arguments (tid %d, %d files)", tid, n_files);
-    HIP_TRY(c, hipSetDevice(c->cfg.device));
-    if (!c->merge) c->merge = new (std::nothrow) MergeState();
-    MergeState *m = c->merge;
-    if (!m) return fail(c, PJB_ERR_NOMEM, "bam_merge_begin: out of host memory");
-    for (size_t k = (size_t)n_files; k < m->files.size(); k++) merge_file_release(c, m->files[k]);
-    m->files.resize((size_t)n_files);
-    for (MergeFile &f : m->files) {
-        f.given = false;
-        f.n = 0;
-    }
-    m->r_size.clear();
-    m->r_members.clear();
-    int rc = ensure(c, m->ctl, MG_CTL_WORDS * 8);
-    if (rc) return rc;
-    m->tid = tid;
-    m->active = true;
-    return PJB_OK;
-}
-
-static int merge_file_body(pjb_ctx *c, MergeState *m, int32_t file, const uint8_t *comp, int64_t comp_bytes, int32_t first_uoffset, int64_t *n_records) {
-    MergeFile &f = m->files[(size_t)file];
-    const int32_t tid = m->tid;
-    std::vector<InfBlock> blocks;
-    int64_t total = 0;
-    int rc = scan_bgzf(c, comp, comp_bytes, blocks, total);
-    if (rc) return rc;
-    if (total == 0 || (int64_t)first_uoffset >= total) {
-        f.given = true;
-        return PJB_OK;
-    }
-    hipStream_t st = c->stream;
-    if ((rc = ensure(c, c->b_inf_comp, (size_t)comp_bytes + INF_PAD))) return rc;
-    if ((rc = upload_host(c, c->b_inf_comp.p, comp, (size_t)comp_bytes))) return rc;
-    HIP_TRY(c, hipMemsetAsync((uint8_t *)c->b_inf_comp.p + comp_bytes, 0, INF_PAD, st));
-    if ((rc = ensure_cat(c, f.out, (size_t)total + 64, MEM_STAGING))) return rc;
-    HIP_TRY(c, hipMemsetAsync((uint8_t *)f.out.p + total, 0, 64, st));
-    if ((rc = inflate_on_device(c, (const uint8_t *)c->b_inf_comp.p, blocks, (uint8_t *)f.out.p))) return rc;
-    // the target's records: up to the first one of another target.  (The walk's other end test, a position past the target's end, is
-    // off: such a record is an error here, found by mg_keys.)
-    BamRegion R = bam_region(c, (const uint8_t *)f.out.p, total, first_uoffset, tid);
-    const int32_t ref_len = R.ref_len;
-    R.ref_len = INT32_MAX;
-    RecordWalk w;
-    if ((rc = walk_records(c, R, false, ("in file " + std::to_string(file) + " on target " + std::to_string(tid)).c_str(), w))) return rc;
-    if (w.end_seg == 0xffffffffu && w.cut_seg != 0xffffffffu) {
-        // The data ends inside a record and no record of another target was seen.  The walk asks for a record's 36 fixed bytes before it
-        // looks at it; a span that ends with the block in which the NEXT target begins may hold fewer of that target's first record.
-        // With its refID in reach (8 bytes) that record says itself whose it is.
-        const uint32_t n_seg = (uint32_t)(((iu64)total + BAM_SEG - 1) / BAM_SEG);
-        const iu64 *land = (const iu64 *)c->b_bam_seg.p + 2 * (size_t)n_seg; // (walk_records: seg_start | seg_base | land)
-        iu64 at = 0;
-        HIP_TRY(c, hipMemcpyAsync(&at, land + w.cut_seg, 8, hipMemcpyDeviceToHost, st));
-        HIP_TRY(c, hipStreamSynchronize(st));
-        int32_t head[2] = {0, tid};
-        if (at + 8 <= (iu64)total) HIP_TRY(c, hipMemcpy(head, (const uint8_t *)f.out.p + at, 8, hipMemcpyDeviceToHost));
-        if (head[1] == tid)
-            return fail(c, PJB_ERR_BGZF, "file %d: the data for target %d ends inside an alignment record (inflated offset %llu..): truncated "
-                                         "file, or the index's span for the target is too short", file, tid, (unsigned long long)at);
-    }
-    if (w.n >= 0xffffff00ull) return fail(c, PJB_ERR_ARG, "bam_merge_file: more than 2^32 alignments on one target are not supported");
-    const size_t n = w.n;
-    if (n) {
-        if ((rc = ensure(c, f.key, n * 4)) || (rc = ensure(c, f.size, n * 4)) || (rc = ensure(c, f.src, n * 8))) return rc;
-        iu64 *ctl = (iu64 *)m->ctl.p;
-        HIP_TRY(c, hipMemsetAsync(ctl, 0xff, MG_CTL_WORDS * 8, st));
-        LAUNCH(c, "mg_keys", mg_keys, dim3((unsigned)((n + 255) / 256)), dim3(256), (const uint8_t *)f.out.p, (const iu64 *)c->b_bam_rec.p, (iu64)n, ref_len,
-               (iu32 *)f.key.p, (iu32 *)f.size.p, (iu64 *)f.src.p, ctl);
-        iu64 h[MG_CTL_WORDS];
-        HIP_TRY(c, hipMemcpyAsync(h, ctl, sizeof h, hipMemcpyDeviceToHost, st));
-        HIP_TRY(c, hipStreamSynchronize(st));
-        if (c->ktime) ev_collect(c, MISC_POOL);
-        // the first offender decides
-        if (h[MG_CTL_BAD] != ~0ull && h[MG_CTL_BAD] <= h[MG_CTL_UNSORTED])
-            return fail(c, PJB_ERR_BGZF, "file %d: alignment record %llu on target %d has a position outside the target", file, (unsigned long long)h[MG_CTL_BAD], tid);
-        if (h[MG_CTL_UNSORTED] != ~0ull)
-            return fail(c, PJB_ERR_UNSORTED, "%s (file %d: alignment record %llu on target %d lies before its predecessor)", err_text(PJB_ERR_UNSORTED), file,
-                        (unsigned long long)h[MG_CTL_UNSORTED], tid);
-    }
-    f.n = n;
-    f.given = true;
-    if (n_records) *n_records = (int64_t)n;
-    return PJB_OK;
-}
-
-extern "C" int pjb_bam_merge_file(pjb_ctx *c, int32_t file, const uint8_t *comp, int64_t comp_bytes, int32_t first_uoffset, int64_t *n_records) {
-    if (!c) return PJB_ERR_ARG;
-    if (n_records) *n_records = 0;
-    MergeState *m = c->merge;
-    if (!m || !m->active) return fail(c, PJB_ERR_STATE, "bam_merge_file: no merge is open (pjb_bam_merge_begin)");
-    if (file < 0 || (size_t)file >= m->files.size() || comp_bytes < 0 || (comp_bytes && !comp) || first_uoffset < 0)
-        return merge_leave(c, m, fail(c, PJB_ERR_ARG, "bam_merge_file: bad arguments (file %d of %zu)", file, m->files.size()));
-    if (m->files[(size_t)file].given) return merge_leave(c, m, fail(c, PJB_ERR_STATE, "bam_merge_file: file %d was handed over already", file));
-    c->cur_tid = m->tid;
-    HIP_TRY(c, hipSetDevice(c->cfg.device));
-    return merge_leave(c, m, merge_file_body(c, m, file, comp, comp_bytes, first_uoffset, n_records));
-}
-
-static int merge_end_body(pjb_ctx *c, MergeState *m, int32_t block_bytes, pjb_bam_merge_result *out) {
-    hipStream_t st = c->stream;
-    int rc;
-    std::vector<MergeFile *> parts; // the files that have records, in file order
-    iu64 n64 = 0;
-    for (MergeFile &f : m->files)
-        if (f.given && f.n) {
-            parts.push_back(&f);
-            n64 += f.n;
-        }
-    if (n64 >= 0xffffff00ull) return fail(c, PJB_ERR_ARG, "bam_merge_end: more than 2^32 alignments on one target are not supported");
-    const size_t n = (size_t)n64;
-    if (n == 0) return PJB_OK;
-    iu64 *ctl = (iu64 *)m->ctl.p;
-    const iu32 *order = nullptr, *size = (const iu32 *)parts[0]->size.p;
-    const iu64 *src = (const iu64 *)parts[0]->src.p;
-    const int32_t ref_len = c->ref_len[(size_t)m->tid];
-    const int key_bits = ref_len > 1 ? bits_of((uint64_t)ref_len - 1) : 0;
-    if (parts.size() > 1) {
-        // one ordinal space, file after file
-        const size_t slack = n + RS_TILE; // (rs_scatter loads whole tiles unguarded)
-        if ((rc = ensure(c, m->sort.key[0], slack * 4)) || (rc = ensure(c, m->sort.key[1], slack * 4)) || (rc = ensure(c, m->sort.idx[0], slack * 4)) ||
-            (rc = ensure(c, m->sort.idx[1], slack * 4)) || (rc = ensure(c, m->size, n * 4)) || (rc = ensure(c, m->src, n * 8)))
-            return rc;
-        size_t at = 0;
-        for (MergeFile *f : parts) {
-            HIP_TRY(c, hipMemcpyAsync((iu32 *)m->sort.key[0].p + at, f->key.p, f->n * 4, hipMemcpyDeviceToDevice, st));
-            HIP_TRY(c, hipMemcpyAsync((iu32 *)m->size.p + at, f->size.p, f->n * 4, hipMemcpyDeviceToDevice, st));
-            HIP_TRY(c, hipMemcpyAsync((iu64 *)m->src.p + at, f->src.p, f->n * 8, hipMemcpyDeviceToDevice, st));
-            at += f->n;
-        }
-        size = (const iu32 *)m->size.p;
-        src = (const iu64 *)m->src.p;
-        if (key_bits > 0) { // (a target of one base: every key is 0, the ordinals are in order)
-            u32 *d_n = (u32 *)(ctl + MG_CTL_WORDS - 1);
-            m->h_n = (uint32_t)n;
-            HIP_TRY(c, hipMemcpyAsync(d_n, &m->h_n, 4, hipMemcpyHostToDevice, st));
-            int cur = 0;
-            if ((rc = sort_u32_pairs(c, m->sort, d_n, n, key_bits, &cur))) return rc;
-            order = (const iu32 *)m->sort.idx[cur].p;
-        }
-    }
-    // where every record goes, and how long the stream is
-    if ((rc = ensure(c, m->dst, n * 8))) return rc;
-    if ((rc = run_scan(c, "mg_off", MgSizeFn{size, order}, MgOffsetSink{(iu64 *)m->dst.p}, n, (u64 *)(ctl + MG_CTL_TOTAL)))) return rc;
-    iu64 raw = 0;
-    HIP_TRY(c, hipMemcpyAsync(&raw, ctl + MG_CTL_TOTAL, 8, hipMemcpyDeviceToHost, st));
-    HIP_TRY(c, hipStreamSynchronize(st));
-    if ((rc = ensure_cat(c, m->stream, (size_t)raw + 64, MEM_STAGING))) return rc;
-    LAUNCH(c, "mg_gather", mg_gather, dim3((unsigned)((n + 3) / 4)), dim3(256), src, size, order, (const iu64 *)m->dst.p, (iu64)n, (uint8_t *)m->stream.p);
-    rc = deflate_launches(c, nullptr, (const uint8_t *)m->stream.p, (int64_t)raw, block_bytes, [&](int64_t, const std::vector<u32> &sizes, iu64 total, uint8_t *&dst) {
-        const size_t had = m->r_members.size();
-        m->r_size.insert(m->r_size.end(), sizes.begin(), sizes.end());
-        m->r_members.resize(had + (size_t)total);
-        dst = m->r_members.data() + had;
-        return (int)PJB_OK;
-    });
-    if (rc) {
-        m->r_size.clear();
-        m->r_members.clear();
-        return rc;
-    }
-    out->n_records = (int64_t)n;
-    out->raw_bytes = (int64_t)raw;
-    return PJB_OK;
-}
-
-extern "C" int pjb_bam_merge_end(pjb_ctx *c, int32_t block_bytes, pjb_bam_merge_result *out) {
-    if (!c) return PJB_ERR_ARG;
-    MergeState *m = c->merge;
-    if (!m || !m->active) return fail(c, PJB_ERR_STATE, "bam_merge_end: no merge is open (pjb_bam_merge_begin)");
-    if (!out) return merge_leave(c, m, fail(c, PJB_ERR_ARG, "bam_merge_end: bad arguments"));
-    if (block_bytes < 4 || block_bytes > (int32_t)DFL_IN_MAX || (block_bytes & 3))
-        return merge_leave(c, m, fail(c, PJB_ERR_ARG, "bam_merge_end: block_bytes must be a multiple of 4 between 4 and %u", DFL_IN_MAX));
-    c->cur_tid = m->tid;
-    HIP_TRY(c, hipSetDevice(c->cfg.device));
-    memset(out, 0, sizeof *out);
-    const int rc = merge_leave(c, m, merge_end_body(c, m, block_bytes, out));
-    if (rc) return rc;
-    m->active = false;
-    out->n_members = (int32_t)m->r_size.size();
-    out->member_size = m->r_size.data();
-    out->members = m->r_members.data();
-    out->member_bytes = (int64_t)m->r_members.size();
-    return PJB_OK;
-}
-
-
-// ---- an unsorted file's records in coordinate order, run by run (pjb_bam_sort_begin / _piece / _end, see the header; sr_keys in pjb_merge.hip.h) ----
-struct SortRun {
-    bool active = false;
-    bool keep_on_error = false;      // the failing piece call left the run as it was
-    int pos_bits = 0, key_bits = 0;  // bits_of(longest target - 1) | + bits_of(n_ref): what the sort runs over
-    bool wide = false;               // key_bits > 32: 64-bit keys
-    size_t n = 0, cap = 0;           // records taken | room in sort.key[0], size, src
-    int64_t n_unplaced = 0;
-    iu64 prev = 0;                   // the key of the last record taken
-    iu64 descent = ~0ull;            // the first ordinal whose key lies below its predecessor's
-    bool ordered = false;            // pjb_bam_sort_end has run the passes: the order lies in sort.idx[order_in]
-    int order_in = 0;
-    std::vector<Buf> pieces;         // every piece's inflated bytes, 64 zeroed bytes behind them
-    SortU32 sort;                    // key[0]: the run's keys in input order
-    Buf size, src;                   // per record: 4 + block_size | where it lies in its piece
-    Buf ref_len, dst, ctl, stream;   // i32[n_ref] | offsets in the sorted stream | SR_CTL_* | the sorted stream
-    uint32_t h_n = 0;                // (copied to the device asynchronously)
-    // the result
-    std::vector<uint32_t> r_size;
-    std::vector<uint8_t> r_members;
-};
-
-static void sort_drop_pieces(pjb_ctx *c, SortRun *r) {
-    for (Buf &b : r->pieces) release(c, b);
-    r->pieces.clear();
-}
-static void sort_clear(pjb_ctx *c) {
-    SortRun *r = c->sort_run;
-    if (!r) return;
-    sort_drop_pieces(c, r);
-    SortU32 &s = r->sort;
-    for (Buf *b : {&s.key[0], &s.key[1], &s.idx[0], &s.idx[1], &s.hist, &s.hist_part, &s.hist_scan, &s.bin_total, &r->size, &r->src, &r->ref_len, &r->dst, &r->ctl, &r->stream})
-        release(c, *b);
-    delete r;
-    c->sort_run = nullptr;
-}
-// what a failing call leaves: nothing to go on with, except after PJB_ERR_NOMEM and a first record longer than its piece
-static int sort_leave(pjb_ctx *c, SortRun *r, int rc) {
-    if (rc && rc != PJB_ERR_NOMEM && !r->keep_on_error) {
-        (void)hipStreamSynchronize(c->stream);
-        r->active = false;
-        sort_drop_pieces(c, r);
-    }
-    return rc;
-}
-
-extern "C" int pjb_bam_sort_begin(pjb_ctx *c) {
-    if (!c) return PJB_ERR_ARG;
-    HIP_TRY(c, hipSetDevice(c->cfg.device));
-    if (!c->sort_run) c->sort_run = new (std::nothrow) SortRun();
-    SortRun *r = c->sort_run;
-    if (!r) return fail(c, PJB_ERR_NOMEM, "bam_sort_begin: out of host memory");
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
-    r->active = false;
-    sort_drop_pieces(c, r);
-    r->n = 0;
-    r->n_unplaced = 0;
-    r->prev = 0;
-    r->descent = ~0ull;
-    r->ordered = false;
-    r->r_size.clear();
-    r->r_members.clear();
-    const size_t n_ref = c->ref_len.size();
-    int32_t longest = 0;
-    for (int32_t len : c->ref_len) longest = std::max(longest, len);
-    r->pos_bits = longest > 1 ? bits_of((uint64_t)longest - 1) : 0;
-    r->key_bits = r->pos_bits + bits_of((uint64_t)n_ref);
-    const bool wide = r->key_bits > 32;
-    if (wide != r->wide) { // the keys' buffers are typed by what they hold
-        for (Buf *b : {&r->sort.key[0], &r->sort.key[1]}) release(c, *b);
-        r->cap = 0;
-        r->wide = wide;
-    }
-    int rc;
-    if ((rc = ensure(c, r->ctl, SR_CTL_WORDS * 8)) || (rc = ensure(c, r->ref_len, n_ref * 4 + 4))) return rc;
-    if (n_ref) HIP_TRY(c, hipMemcpy(r->ref_len.p, c->ref_len.data(), n_ref * 4, hipMemcpyHostToDevice));
-    r->active = true;
-    return PJB_OK;
-}
-
-// room for `need` records in the run's arrays: larger buffers take over what the arrays hold
-static int sort_grow(pjb_ctx *c, SortRun *r, size_t need) {
-    if (need <= r->cap && r->sort.key[0].p) return PJB_OK;
-    const size_t cap = std::max<size_t>(need + need / 2, (size_t)1 << 16), ksz = r->wide ? 8 : 4;
-    Buf nk, ns, nr;
-    int rc;
-    if ((rc = ensure(c, nk, (cap + RS_TILE) * ksz)) || (rc = ensure(c, ns, cap * 4)) || (rc = ensure(c, nr, cap * 8))) {
-        for (Buf *b : {&nk, &ns, &nr}) release(c, *b);
-        return rc;
-    }
-    hipStream_t st = c->stream;
-    if (r->n) {
-        HIP_TRY(c, hipMemcpyAsync(nk.p, r->sort.key[0].p, r->n * ksz, hipMemcpyDeviceToDevice, st));
-        HIP_TRY(c, hipMemcpyAsync(ns.p, r->size.p, r->n * 4, hipMemcpyDeviceToDevice, st));
-        HIP_TRY(c, hipMemcpyAsync(nr.p, r->src.p, r->n * 8, hipMemcpyDeviceToDevice, st));
-    }
-    for (Buf *b : {&r->sort.key[0], &r->size, &r->src})
-        if (b->p) bury(c, b->p); // (the copies are on the stream: freed where a wait costs nothing)
-    r->sort.key[0] = nk;
-    r->size = ns;
-    r->src = nr;
-    r->cap = cap;
-    return PJB_OK;
-}
-
-static int sort_piece_body(pjb_ctx *c, SortRun *r, Buf &out, const uint8_t *comp, int64_t comp_bytes, int32_t first_uoffset, int32_t last, uint64_t *next_voffset,
-                           int64_t *n_records) {
-    std::vector<InfBlock> blocks;
-    int64_t total = 0;
-    int rc = scan_bgzf(c, comp, comp_bytes, blocks, total);
-    if (rc) return rc;
-    if ((int64_t)first_uoffset > total) return fail(c, PJB_ERR_ARG, "bam_sort_piece: first_uoffset %d lies behind the piece's %lld inflated bytes", first_uoffset, (long long)total);
-    const size_t nb = blocks.size();
-    // inflated byte u of the piece as (offset of its block in the piece) << 16 | offset in the block; the end of the data: the piece's end
-    auto voffset_of = [&](iu64 u) -> uint64_t {
-        if (u >= (iu64)total) return (uint64_t)comp_bytes << 16;
-        size_t lo = 0, hi = nb;
-        while (lo < hi) { // the first block that begins behind u; the one before it holds u (empty blocks lie before the block they share a start with)
-            const size_t mid = lo + (hi - lo) / 2;
-            if (blocks[mid].out_off <= u) lo = mid + 1;
-            else hi = mid;
-        }
-        const size_t k = lo - 1;
-        const iu64 start = k == 0 ? 0 : blocks[k - 1].in_off + blocks[k - 1].in_len + 8; // (behind the payload, CRC32 and ISIZE of the block before)
-        return (uint64_t)start << 16 | (u - blocks[k].out_off);
-    };
-    size_t n = 0;
-    iu64 next_u = (iu64)first_uoffset;
-    hipStream_t st = c->stream;
-    if ((int64_t)first_uoffset < total) {
-        if ((rc = ensure(c, c->b_inf_comp, (size_t)comp_bytes + INF_PAD))) return rc;
-        if ((rc = upload_host(c, c->b_inf_comp.p, comp, (size_t)comp_bytes))) return rc;
-        HIP_TRY(c, hipMemsetAsync((uint8_t *)c->b_inf_comp.p + comp_bytes, 0, INF_PAD, st));
-        if ((rc = ensure_cat(c, out, (size_t)total + 64, MEM_STAGING))) return rc;
-        HIP_TRY(c, hipMemsetAsync((uint8_t *)out.p + total, 0, 64, st));
-        if ((rc = inflate_on_device(c, (const uint8_t *)c->b_inf_comp.p, blocks, (uint8_t *)out.p))) return rc;
-        RecordWalk w;
-        if ((rc = walk_records(c, bam_region(c, (const uint8_t *)out.p, total, first_uoffset, -1), true, "in the piece", w))) return rc;
-        if (w.n >= 0xffffff00ull || r->n + w.n >= 0xffffff00ull) return fail(c, PJB_ERR_ARG, "bam_sort_piece: 2^32 - 256 alignments or more in one run are not supported");
-        n = w.n;
-        next_u = w.next_u;
-    }
-    if (next_u < (iu64)total) { // the data ends inside a record
-        if (last) return fail(c, PJB_ERR_BGZF, "the data ends inside an alignment record (inflated offset %llu of the last piece): truncated file", (unsigned long long)next_u);
-        if (n == 0) { // nothing was taken and nothing changed: the caller may hand the same blocks over again with more behind them
-            r->keep_on_error = true;
-            if (next_voffset) *next_voffset = voffset_of(next_u);
-            return fail(c, PJB_ERR_ARG, "bam_sort_piece: the alignment record at inflated offset %llu is longer than the piece (%lld bytes): hand over more blocks at once",
-                        (unsigned long long)next_u, (long long)comp_bytes);
-        }
-    }
-    if (n > 0) {
-        if ((rc = sort_grow(c, r, r->n + n))) return rc;
-        iu64 *ctl = (iu64 *)r->ctl.p;
-        HIP_TRY(c, hipMemsetAsync(ctl, 0xff, SR_CTL_WORDS * 8, st));
-        HIP_TRY(c, hipMemsetAsync(ctl + SR_CTL_UNPLACED, 0, 8, st));
-        const dim3 grid((unsigned)((n + 255) / 256));
-        const iu64 *rec_off = (const iu64 *)c->b_bam_rec.p;
-        if (r->wide)
-            LAUNCH(c, "sr_keys", sr_keys<u64>, grid, dim3(256), (const uint8_t *)out.p, rec_off, (iu64)n, (const int32_t *)r->ref_len.p, (int32_t)c->ref_len.size(), r->pos_bits,
-                   r->prev, (u64 *)r->sort.key[0].p + r->n, (iu32 *)r->size.p + r->n, (iu64 *)r->src.p + r->n, ctl);
-        else
-            LAUNCH(c, "sr_keys", sr_keys<u32>, grid, dim3(256), (const uint8_t *)out.p, rec_off, (iu64)n, (const int32_t *)r->ref_len.p, (int32_t)c->ref_len.size(), r->pos_bits,
-                   r->prev, (u32 *)r->sort.key[0].p + r->n, (iu32 *)r->size.p + r->n, (iu64 *)r->src.p + r->n, ctl);
-        iu64 h[SR_CTL_WORDS];
-        HIP_TRY(c, hipMemcpyAsync(h, ctl, sizeof h, hipMemcpyDeviceToHost, st));
-        HIP_TRY(c, hipStreamSynchronize(st));
-        if (c->ktime) ev_collect(c, MISC_POOL);
-        // the first offender decides
-        if (h[SR_CTL_BAD_TID] != ~0ull && h[SR_CTL_BAD_TID] <= h[SR_CTL_BAD_POS])
-            return fail(c, PJB_ERR_BGZF, "alignment record %llu names a target the header does not have (its refID lies outside the %zu targets)",
-                        (unsigned long long)(r->n + h[SR_CTL_BAD_TID]), c->ref_len.size());
-        if (h[SR_CTL_BAD_POS] != ~0ull)
-            return fail(c, PJB_ERR_BGZF, "alignment record %llu has a position outside its target", (unsigned long long)(r->n + h[SR_CTL_BAD_POS]));
-        if (h[SR_CTL_DESCENT] != ~0ull) r->descent = std::min(r->descent, (iu64)r->n + h[SR_CTL_DESCENT]);
-        r->prev = h[SR_CTL_LAST];
-        r->n_unplaced += (int64_t)h[SR_CTL_UNPLACED];
-        r->n += n;
-        r->pieces.push_back(out);
-        out = Buf();
-    }
-    if (next_voffset) *next_voffset = voffset_of(next_u);
-    if (n_records) *n_records = (int64_t)n;
-    return PJB_OK;
-}
-
-extern "C" int pjb_bam_sort_piece(pjb_ctx *c, const uint8_t *comp, int64_t comp_bytes, int32_t first_uoffset, int32_t last, uint64_t *next_voffset,
-                                  int64_t *n_records) {
-    if (!c) return PJB_ERR_ARG;
-    if (n_records) *n_records = 0;
-    SortRun *r = c->sort_run;
-    if (!r || !r->active) return fail(c, PJB_ERR_STATE, "bam_sort_piece: no run is open (pjb_bam_sort_begin)");
-    r->keep_on_error = false;
-    if (comp_bytes < 0 || (comp_bytes && !comp) || first_uoffset < 0) return sort_leave(c, r, fail(c, PJB_ERR_ARG, "bam_sort_piece: bad arguments"));
-    HIP_TRY(c, hipSetDevice(c->cfg.device));
-    Buf out;
-    const int rc = sort_piece_body(c, r, out, comp, comp_bytes, first_uoffset, last, next_voffset, n_records);
-    if (out.p) { // the piece was not taken: its bytes go when nothing reads them any more
-        (void)hipStreamSynchronize(c->stream);
-        release(c, out);
-    }
-    return sort_leave(c, r, rc);
-}
-
-static int sort_end_body(pjb_ctx *c, SortRun *r, int32_t block_bytes, pjb_bam_sort_result *out) {
-    hipStream_t st = c->stream;
-    int rc;
-    const size_t n = r->n;
-    out->was_sorted = r->descent == ~0ull;
-    if (n == 0) return PJB_OK;
-    iu64 *ctl = (iu64 *)r->ctl.p;
-    const iu32 *order = nullptr;
-    if (!out->was_sorted) { // (a descent needs two different keys: key_bits > 0)
-        const size_t slack = n + RS_TILE, ksz = r->wide ? 8 : 4; // (rs_scatter loads whole tiles unguarded)
-        if ((rc = ensure(c, r->sort.key[1], slack * ksz)) || (rc = ensure(c, r->sort.idx[0], slack * 4)) || (rc = ensure(c, r->sort.idx[1], slack * 4))) return rc;
-        u32 *d_n = (u32 *)(ctl + SR_CTL_N);
-        r->h_n = (uint32_t)n;
-        HIP_TRY(c, hipMemcpyAsync(d_n, &r->h_n, 4, hipMemcpyHostToDevice, st));
-        // (the passes leave key[0] permuted: a call repeated after PJB_ERR_NOMEM goes on with the order it has)
-        if (!r->ordered && (rc = r->wide ? sort_u64_pairs(c, r->sort, d_n, n, r->key_bits, &r->order_in) : sort_u32_pairs(c, r->sort, d_n, n, r->key_bits, &r->order_in)))
-            return rc;
-        r->ordered = true;
-        order = (const iu32 *)r->sort.idx[r->order_in].p;
-    }
-    if ((rc = ensure(c, r->dst, n * 8))) return rc;
-    if ((rc = run_scan(c, "sr_off", MgSizeFn{(const iu32 *)r->size.p, order}, MgOffsetSink{(iu64 *)r->dst.p}, n, (u64 *)(ctl + SR_CTL_TOTAL)))) return rc;
-    iu64 raw = 0;
-    HIP_TRY(c, hipMemcpyAsync(&raw, ctl + SR_CTL_TOTAL, 8, hipMemcpyDeviceToHost, st));
-    HIP_TRY(c, hipStreamSynchronize(st));
-    if ((rc = ensure_cat(c, r->stream, (size_t)raw + 64, MEM_STAGING))) return rc;
-    LAUNCH(c, "mg_gather", mg_gather, dim3((unsigned)((n + 3) / 4)), dim3(256), (const iu64 *)r->src.p, (const iu32 *)r->size.p, order, (const iu64 *)r->dst.p, (iu64)n,
-           (uint8_t *)r->stream.p);
-    rc = deflate_launches(c, nullptr, (const uint8_t *)r->stream.p, (int64_t)raw, block_bytes, [&](int64_t, const std::vector<u32> &sizes, iu64 total, uint8_t *&dst) {
-        const size_t had = r->r_members.size();
-        r->r_size.insert(r->r_size.end(), sizes.begin(), sizes.end());
-        r->r_members.resize(had + (size_t)total);
-        dst = r->r_members.data() + had;
-        return (int)PJB_OK;
-    });
-    if (rc) {
-        r->r_size.clear();
-        r->r_members.clear();
-        return rc;
-    }
-    out->n_records = (int64_t)n;
-    out->raw_bytes = (int64_t)raw;
-    out->n_unplaced = r->n_unplaced;
-    return PJB_OK;
-}
-
-extern "C" int pjb_bam_sort_end(pjb_ctx *c, int32_t block_bytes, pjb_bam_sort_result *out) {
-    if (!c) return PJB_ERR_ARG;
-    SortRun *r = c->sort_run;
-    if (!r || !r->active) return fail(c, PJB_ERR_STATE, "bam_sort_end: no run is open (pjb_bam_sort_begin)");
-    r->keep_on_error = false;
-    if (!out) return sort_leave(c, r, fail(c, PJB_ERR_ARG, "bam_sort_end: bad arguments"));
-    if (block_bytes < 4 || block_bytes > (int32_t)DFL_IN_MAX || (block_bytes & 3))
-        return sort_leave(c, r, fail(c, PJB_ERR_ARG, "bam_sort_end: block_bytes must be a multiple of 4 between 4 and %u", DFL_IN_MAX));
-    HIP_TRY(c, hipSetDevice(c->cfg.device));
-    memset(out, 0, sizeof *out);
-    const int rc = sort_leave(c, r, sort_end_body(c, r, block_bytes, out));
-    if (rc) return rc;
-    r->active = false;
-    (void)hipStreamSynchronize(c->stream);
-    sort_drop_pieces(c, r); // (the stream has been copied out: the run's inflated bytes make room for the next run's)
-    out->n_members = (int32_t)r->r_size.size();
-    out->member_size = r->r_size.data();
-    out->members = r->r_members.data();
-    out->member_bytes = (int64_t)r->r_members.size();
-    return PJB_OK;
+    c->bam_stage.clear();
+    release_pooled_stage(c);
+    for (auto &is : c->inf_streams)
+        if (is) (void)hipStreamDestroy(is);
+    for (auto &ev : c->up_events)
+        if (ev) (void)hipEventDestroy(ev);
+    if (c->ev_up) (void)hipEventDestroy(c->ev_up);
+    if (c->stream_up) (void)hipStreamDestroy(c->stream_up);
 }

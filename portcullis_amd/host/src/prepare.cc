@@ -439,6 +439,18 @@ struct DeviceCtx {  // a context without chains: what prep's index, merge and so
     DeviceCtx& operator=(const DeviceCtx&) = delete;
 };
 
+const uint8_t BGZF_EOF_BLOCK[28] = {0x1f, 0x8b, 8, 4, 0, 0, 0, 0, 0, 0xff, 6, 0, 'B', 'C', 2, 0, 0x1b, 0, 3, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+const int32_t BGZF_CUT = 0xff00;  // inflated bytes a member of a file written here holds
+// host bytes -> BGZF members, deflated on the device (no EOF block)
+std::vector<uint8_t> deflateMembers(pjb_ctx* c, const std::vector<uint8_t>& raw) {
+    std::vector<uint8_t> packed(((raw.size() + BGZF_CUT - 1) / BGZF_CUT) * 65536);
+    int64_t n = 0;
+    if (pjb_deflate_bgzf(c, raw.data(), (int64_t)raw.size(), BGZF_CUT, packed.data(), (int64_t)packed.size(), &n, nullptr) != PJB_OK)
+        throw PrepareException(string("pjb_deflate_bgzf: ") + pjb_last_error(c));
+    packed.resize((size_t)n);
+    return packed;
+}
+
 // The index of a coordinate-sorted BAM file, built on the device ...
 struct BuiltIndex {
     bam::BaiBins bins;
@@ -492,13 +504,8 @@ BuiltIndex buildIndex(const string& bamFile, bool nameFile, bool csi) {
         X.records = res.n_records;
         X.chunks = res.n_chunks;
         // the file's bytes: the payload in BGZF members deflated on the device, the EOF block behind them
-        const std::vector<uint8_t> raw = bam::csiPayload(res.min_shift, res.depth, X.bins, X.loff);
-        X.csiFile.resize(((raw.size() + 0xff00 - 1) / 0xff00) * 65536 + 28);
-        int64_t n = 0;
-        check(pjb_deflate_bgzf(ctx.c, raw.data(), (int64_t)raw.size(), 0xff00, X.csiFile.data(), (int64_t)X.csiFile.size() - 28, &n, nullptr), "pjb_deflate_bgzf");
-        static const uint8_t eof[28] = {0x1f, 0x8b, 8, 4, 0, 0, 0, 0, 0, 0xff, 6, 0, 'B', 'C', 2, 0, 0x1b, 0, 3, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-        memcpy(X.csiFile.data() + n, eof, 28);
-        X.csiFile.resize((size_t)n + 28);
+        X.csiFile = deflateMembers(ctx.c, bam::csiPayload(res.min_shift, res.depth, X.bins, X.loff));
+        X.csiFile.insert(X.csiFile.end(), BGZF_EOF_BLOCK, BGZF_EOF_BLOCK + sizeof BGZF_EOF_BLOCK);
         return X;
     }
     pjb_index_result res;
@@ -563,9 +570,6 @@ size_t followingBlock(const string& path, uint64_t off) {
     fclose(f);
     return bs && off + bs <= (uint64_t)st.st_size ? bs : 0;
 }
-const uint8_t BGZF_EOF_BLOCK[28] = {0x1f, 0x8b, 8, 4, 0, 0, 0, 0, 0, 0xff, 6, 0, 'B', 'C', 2, 0, 0x1b, 0, 3, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-const int32_t BGZF_CUT = 0xff00;  // inflated bytes a member of a file written here holds
-
 // the inflated bytes in front of a BAM file's first record
 std::vector<uint8_t> bamHeaderBytes(const string& text, const std::vector<string>& names, const std::vector<int32_t>& lens) {
     std::vector<uint8_t> h = {'B', 'A', 'M', 1};
@@ -583,11 +587,8 @@ std::vector<uint8_t> bamHeaderBytes(const string& text, const std::vector<string
 // host bytes -> BGZF members (on the device) -> the file
 void deflateToFile(pjb_ctx* c, const std::vector<uint8_t>& raw, FILE* out, const string& path) {
     if (raw.empty()) return;
-    std::vector<uint8_t> packed(((raw.size() + BGZF_CUT - 1) / BGZF_CUT) * 65536);
-    int64_t n = 0;
-    if (pjb_deflate_bgzf(c, raw.data(), (int64_t)raw.size(), BGZF_CUT, packed.data(), (int64_t)packed.size(), &n, nullptr) != PJB_OK)
-        throw PrepareException(string("pjb_deflate_bgzf: ") + pjb_last_error(c));
-    writeAll(out, packed.data(), (size_t)n, path);
+    const std::vector<uint8_t> packed = deflateMembers(c, raw);
+    writeAll(out, packed.data(), packed.size(), path);
 }
 
 const char* const NO_DEVICE_SORT =
