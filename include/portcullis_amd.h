@@ -781,6 +781,23 @@ typedef struct pjb_grow_result {
 } pjb_grow_result;
 int pjb_forest_grow(pjb_ctx *ctx, const double *data, int64_t n_rows, int32_t n_cols, const pjb_grow_params *p, pjb_grow_result *out);
 
+/* ---- `train --folds`: k-fold cross-validation, the folds' forests grown side by side ----------------------------
+ * data, p: as pjb_forest_grow.  fold[r] in 0 .. n_folds-1: the fold that holds row r out.
+ * forests (optional, n_folds entries): forests[f] is, bit for bit, the forest pjb_forest_grow returns for the sub-matrix of the rows
+ * with fold[r] != f, in their original order, with the same params (every fold's tree i has the seed (i + 1) * seed).  Host memory
+ * owned by the context until its next pjb_forest_cv / pjb_destroy.
+ * pred: n_rows x 2, host: row r as pjb_forest_load(forests[fold[r]]) + pjb_forest_predict give it -- the quotients counts[c] / n_trees
+ * made once each and added tree after tree in tree order -- without a forest leaving the device for it: the held-out rows are walked
+ * through the grown nodes there.
+ * One call grows n_folds * n_trees trees through one level loop (one read-back per level for every fold's trees together), in
+ * batches that may cut through folds; nothing depends on where they cut ("grow_batch").  The forest pjb_forest_load put on the device
+ * is left alone.  The call may invalidate the result of the context's last pjb_forest_grow: copy it first.
+ * PJB_ERR_ARG, found on the host before anything is launched, the fold named in the message: n_folds < 2 or > n_rows; a fold id
+ * outside 0 .. n_folds-1; a fold that holds no row; a fold whose training rows all have one label (so every forest has two
+ * classes); and everything pjb_forest_grow refuses. */
+int pjb_forest_cv(pjb_ctx *ctx, const double *data, int64_t n_rows, int32_t n_cols, const pjb_grow_params *p, const int32_t *fold,
+                  int32_t n_folds, double *pred, pjb_grow_result *forests);
+
 /* ---- self-training: brute-force K nearest neighbours, the search under SMOTE and ENN ---------------------------
  * KNN::doSlice (lib/src/knn.cc:46-99).  data: row-major n_rows x n_cols, host.  The distance of two rows is
  * s = sum over the columns, in ascending column order, of (base[c] - test[c])^2 in f64, the subtraction, the product and the sum

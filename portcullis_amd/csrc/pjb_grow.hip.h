@@ -42,12 +42,11 @@ struct GrowNodes {
     double *val;
 };
 
-// mt state in global memory between levels: word i of tree t at state[i * T + t]; word 312 is the position
-__global__ __launch_bounds__(64) void kt_seed(u64 *state, u32 T, u32 tree0, u32 seed, GrowNodes nd, u32 M, u32 *lvl, u32 n, u32 label_sum) {
-    const u32 t = blockIdx.x * 64 + threadIdx.x;
-    if (t >= T) return;
+// mt state in global memory between levels: word i of tree t at state[i * T + t]; word 312 is the position.  Tree t of the batch gets
+// the generator of the forest's tree `index` and a root of `count` rows, `sum` of them of label 1 (kt_seed; kc_seed of pjb_cv.hip.h).
+__device__ inline void grow_seed_tree(u64 *state, u32 T, u32 t, u32 index, u32 seed, GrowNodes nd, u32 M, u32 *lvl, u32 count, u32 sum) {
     // Forest.cpp:409-416: tree_seed = (uint)((i + 1) * seed); std::mt19937_64::seed(value)
-    u64 x = (u64)(u32)((tree0 + t + 1u) * seed);
+    u64 x = (u64)(u32)((index + 1u) * seed);
     state[t] = x;
     for (u32 i = 1; i < GROW_MT_N; i++) {
         x = 6364136223846793005ull * (x ^ (x >> 62)) + i;
@@ -56,13 +55,18 @@ __global__ __launch_bounds__(64) void kt_seed(u64 *state, u32 T, u32 tree0, u32 
     state[(size_t)GROW_MT_N * T + t] = GROW_MT_N;
     const size_t r = (size_t)t * M;
     nd.start[r] = 0;
-    nd.count[r] = n;
-    nd.sum[r] = label_sum;
+    nd.count[r] = count;
+    nd.sum[r] = sum;
     nd.child[r] = 0;
     nd.var[r] = 0;
     nd.val[r] = 0.0;
     lvl[t] = 0;
     lvl[T + t] = 1;
+}
+
+__global__ __launch_bounds__(64) void kt_seed(u64 *state, u32 T, u32 tree0, u32 seed, GrowNodes nd, u32 M, u32 *lvl, u32 n, u32 label_sum) {
+    const u32 t = blockIdx.x * 64 + threadIdx.x;
+    if (t < T) grow_seed_tree(state, T, t, tree0 + t, seed, nd, M, lvl, n, label_sum);
 }
 
 __global__ __launch_bounds__(256) void kt_fill(const u32 *sorted, u32 *lists, u64 per_tree, u64 total) {

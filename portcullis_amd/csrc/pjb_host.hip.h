@@ -2,7 +2,7 @@
 // The library is built from four units -- pjb_api.hip (contexts, uploads, batches, the kernel chains: pjb_kernels.hip.h, and the host code
 // that queues and collects them: pjb_chain.hip.h, pjb_flight.hip.h, pjb_limits.hip.h), pjb_extra_api.hip
 // (--extra, bamfilt: pjb_extra.hip.h), pjb_model_api.hip (filt and train -- feature rows, the forest walk, forest growing, KNN:
-// pjb_features.hip.h, pjb_forest.hip.h, pjb_grow.hip.h, pjb_knn.hip.h) and pjb_ingest_api.hip (BGZF inflate / deflate, BAM records:
+// pjb_features.hip.h, pjb_forest.hip.h, pjb_grow.hip.h, pjb_cv.hip.h, pjb_knn.hip.h) and pjb_ingest_api.hip (BGZF inflate / deflate, BAM records:
 // pjb_ingest.hip.h, pjb_deflate.hip.h; prep's index, merge and sort: pjb_index.hip.h, pjb_merge.hip.h, and the host code that drives them:
 // pjb_index_api.hip.h, pjb_merge_api.hip.h, pjb_sort_api.hip.h) -- each of which includes its own kernel family behind this header and so is the only unit that compiles it; this header includes only what the
 // units share (pjb_device.hip.h, pjb_extra_types.hip.h, and pjb_memory.hip.h: the rule the counted allocator below follows).  (The Makefile makes every header a prerequisite of every unit: an edit to any of them
@@ -208,6 +208,7 @@ struct ModelState {
         std::vector<int32_t> left, right, split_var;
         std::vector<double> split_value, counts, class_values;
     } grow_out;
+    std::vector<GrowOut> cv_out; // the folds' forests of the last pjb_forest_cv: what its pjb_grow_results point to
     void release_all(pjb_ctx *c) { // (pjb_destroy)
         for (Buf *b : {&g_rows, &g_models, &g_refs, &g_out, &g_bad, &r_nodes, &r_leaf, &r_roots, &r_data, &r_pred, &r_colmap, &w_pool, &w_pack,
                        &n_data, &n_part_d, &n_part_i, &n_out, &m_idx, &m_nseg, &m_off, &m_counts, &m_tables, &m_sizes})

@@ -1,12 +1,13 @@
 // pjb_model_api.hip -- the part of the C ABI behind `filt` and `train`: feature rows and the walk of a saved forest (pjb_filt_features,
 // pjb_forest_check / _load / _predict, pjb_filt_scores), the training of the Markov models (pjb_markov_train), the growing of a forest
-// (pjb_forest_grow) and self-training's nearest neighbours (pjb_knn); kernels in pjb_features.hip.h, pjb_markov.hip.h, pjb_forest.hip.h,
-// pjb_grow.hip.h and pjb_knn.hip.h.  What a context keeps for them is pjb_ctx::model (ModelState, pjb_host.hip.h).
+// (pjb_forest_grow), cross-validation (pjb_forest_cv) and self-training's nearest neighbours (pjb_knn); kernels in pjb_features.hip.h,
+// pjb_markov.hip.h, pjb_forest.hip.h, pjb_grow.hip.h, pjb_cv.hip.h and pjb_knn.hip.h.  What a context keeps for them is pjb_ctx::model (ModelState, pjb_host.hip.h).
 #include "pjb_host.hip.h"
 #include "pjb_features.hip.h"
 #include "pjb_markov.hip.h"
 #include "pjb_forest.hip.h"
 #include "pjb_grow.hip.h"
+#include "pjb_cv.hip.h"
 #include "pjb_knn.hip.h"
 
 // the uploaded genomes as the kernels of `filt` and `train` look them up (c->model.g_refs), and the "a genome is missing" flag cleared
@@ -70,16 +71,22 @@ static int forest_queue(pjb_ctx *c, const double *data, size_t n, u32 stride, co
     return PJB_OK;
 }
 
-// ---- the stages of pjb_forest_grow, in the order it calls them -------------------------------------------------------
+// ---- the stages of pjb_forest_grow and pjb_forest_cv, in the order they call them ------------------------------------
 // Device memory one batch of trees may take (lists, nodes, candidates, scores); more trees than fit are grown batch after batch.
 static constexpr size_t GROW_POOL_BYTES = (size_t)6 << 30;
 static size_t up256(size_t b) { return (b + 255) & ~(size_t)255; }
 
 struct GrowPlan { // a call that passed its checks
+    const char *who;  // the entry point, for the messages
     size_t n, C, dep; // rows, columns, the dependent column
     size_t M;         // node slots of a tree
-    size_t n_trees;
+    size_t n_trees;   // of a forest
     u32 seed, mtry, min_node;
+    size_t n_folds;   // pjb_forest_cv: the forests grown side by side, n_folds * n_trees trees in all (pjb_cv.hip.h); 0: pjb_forest_grow
+    size_t trees_all() const { return n_trees * std::max<size_t>(n_folds, 1); }
+};
+struct GrowFolds { // pjb_forest_cv: per row the fold that holds it out; per fold the rows it trains on and those of label 1 among them
+    std::vector<u32> fold, train_n, train_sum;
 };
 struct GrowInput { // the caller's matrix as the kernels read it
     std::vector<double> colmajor;
@@ -97,25 +104,27 @@ struct GrowRoom { // c->model.w_pool, carved for `batch` trees side by side
     GrowBest *best;
     u64 *state;
     u32 *lvl;
+    u32 *fold, *fold_n, *fold_sum; // pjb_forest_cv: GrowFolds on the device ...
+    double *pred;                  // ... and the held-out rows' sums, n x 2
 };
 
 // the argument checks and ranger's defaults
-static int grow_plan(pjb_ctx *c, const double *data, int64_t n_rows, int32_t n_cols, const pjb_grow_params *p, const pjb_grow_result *out, GrowPlan &P) {
-    if (!p || !out) return fail(c, PJB_ERR_ARG, "pjb_forest_grow: bad arguments");
-    if (p->n_trees < 1) return fail(c, PJB_ERR_ARG, "pjb_forest_grow: %d trees (at least one is needed)", p->n_trees);
-    if (n_rows < 1) return fail(c, PJB_ERR_ARG, "pjb_forest_grow: %lld rows (at least one is needed)", (long long)n_rows);
-    if (n_cols < 2) return fail(c, PJB_ERR_ARG, "pjb_forest_grow: %d columns (the labels and one variable at least)", n_cols);
-    if (n_cols > PJB_FOREST_MAX_VARS) return fail(c, PJB_ERR_ARG, "pjb_forest_grow: %d variables (1 to %d can be walked)", n_cols, PJB_FOREST_MAX_VARS);
-    if (!data || n_rows > (1ll << 28) || p->n_trees > (1 << 24)) return fail(c, PJB_ERR_ARG, "pjb_forest_grow: bad arguments");
+static int grow_plan(pjb_ctx *c, const char *who, const double *data, int64_t n_rows, int32_t n_cols, const pjb_grow_params *p, const void *out, GrowPlan &P) {
+    if (!p || !out) return fail(c, PJB_ERR_ARG, "%s: bad arguments", who);
+    if (p->n_trees < 1) return fail(c, PJB_ERR_ARG, "%s: %d trees (at least one is needed)", who, p->n_trees);
+    if (n_rows < 1) return fail(c, PJB_ERR_ARG, "%s: %lld rows (at least one is needed)", who, (long long)n_rows);
+    if (n_cols < 2) return fail(c, PJB_ERR_ARG, "%s: %d columns (the labels and one variable at least)", who, n_cols);
+    if (n_cols > PJB_FOREST_MAX_VARS) return fail(c, PJB_ERR_ARG, "%s: %d variables (1 to %d can be walked)", who, n_cols, PJB_FOREST_MAX_VARS);
+    if (!data || n_rows > (1ll << 28) || p->n_trees > (1 << 24)) return fail(c, PJB_ERR_ARG, "%s: bad arguments", who);
     if (p->dependent_col < 0 || p->dependent_col >= n_cols)
-        return fail(c, PJB_ERR_ARG, "pjb_forest_grow: dependent column %d of %d columns", p->dependent_col, n_cols);
-    if (p->mtry < 0 || p->min_node_size < 0) return fail(c, PJB_ERR_ARG, "pjb_forest_grow: mtry %d, node size %d", p->mtry, p->min_node_size);
+        return fail(c, PJB_ERR_ARG, "%s: dependent column %d of %d columns", who, p->dependent_col, n_cols);
+    if (p->mtry < 0 || p->min_node_size < 0) return fail(c, PJB_ERR_ARG, "%s: mtry %d, node size %d", who, p->mtry, p->min_node_size);
     // ForestProbability::initInternal (ForestProbability.cpp:64-75)
     const u32 mtry = p->mtry ? (u32)p->mtry : std::max<u32>(1, (u32)sqrt((double)(n_cols - 1)));
     const u32 min_node = p->min_node_size ? (u32)p->min_node_size : 10u;
     if (mtry >= (u32)n_cols / 2)
-        return fail(c, PJB_ERR_ARG, "pjb_forest_grow: mtry %u of %d columns: from n_cols / 2 on ranger draws by Knuth's algorithm, which is not built", mtry, n_cols);
-    P = GrowPlan{(size_t)n_rows, (size_t)n_cols, (size_t)p->dependent_col, 2 * (size_t)n_rows, (size_t)p->n_trees, (u32)p->seed, mtry, min_node};
+        return fail(c, PJB_ERR_ARG, "%s: mtry %u of %d columns: from n_cols / 2 on ranger draws by Knuth's algorithm, which is not built", who, mtry, n_cols);
+    P = GrowPlan{who, (size_t)n_rows, (size_t)n_cols, (size_t)p->dependent_col, 2 * (size_t)n_rows, (size_t)p->n_trees, (u32)p->seed, mtry, min_node, 0};
     return PJB_OK;
 }
 
@@ -127,9 +136,9 @@ static int grow_input(pjb_ctx *c, const double *data, const GrowPlan &P, GrowInp
     for (size_t r = 0; r < n; r++)
         for (size_t k = 0; k < C; k++) {
             const double v = data[r * C + k];
-            if (!std::isfinite(v)) return fail(c, PJB_ERR_ARG, "pjb_forest_grow: row %zu, column %zu is not finite", r, k);
+            if (!std::isfinite(v)) return fail(c, PJB_ERR_ARG, "%s: row %zu, column %zu is not finite", P.who, r, k);
             if (k == dep) {
-                if (v != 0.0 && v != 1.0) return fail(c, PJB_ERR_ARG, "pjb_forest_grow: row %zu has the label %g (0 or 1)", r, v);
+                if (v != 0.0 && v != 1.0) return fail(c, PJB_ERR_ARG, "%s: row %zu has the label %g (0 or 1)", P.who, r, v);
                 in.label[r] = v == 1.0;
                 in.label_sum += in.label[r];
             }
@@ -151,10 +160,12 @@ static int grow_input(pjb_ctx *c, const double *data, const GrowPlan &P, GrowInp
 static int grow_room(pjb_ctx *c, const GrowPlan &P, GrowRoom &R) {
     const size_t n = P.n, C = P.C, M = P.M;
     const u32 mtry = P.mtry;
-    const size_t shared_bytes = up256(C * n * 8) + up256(n) + up256(C * n * 4) + 256;
+    // (pjb_forest_cv adds nothing to a tree: the held-out rows lie in the tails of its lists, and are scored from its nodes)
+    const size_t cv_bytes = P.n_folds ? up256(n * 4) + 2 * up256(P.n_folds * 4) + up256(n * 16) : 0;
+    const size_t shared_bytes = up256(C * n * 8) + up256(n) + up256(C * n * 4) + 256 + cv_bytes;
     const size_t tree_bytes = 2 * C * n * 4 + n * 4 + M * (5 * 4 + 8) + M * mtry * (2 + sizeof(GrowBest)) + (GROW_MT_N + 1) * 8 + 2 * 4;
     size_t batch = c->model.grow_batch ? c->model.grow_batch : std::max<size_t>(1, GROW_POOL_BYTES / tree_bytes);
-    batch = std::min<size_t>(std::min<size_t>(batch, P.n_trees), 32768);
+    batch = std::min<size_t>(std::min<size_t>(batch, P.trees_all()), 32768);
     int rc;
     if ((rc = ensure(c, c->model.w_pool, shared_bytes + batch * tree_bytes + 16 * 256))) return rc;
     uint8_t *at = (uint8_t *)c->model.w_pool.p;
@@ -181,18 +192,35 @@ static int grow_room(pjb_ctx *c, const GrowPlan &P, GrowRoom &R) {
     R.best = (GrowBest *)carve(batch * M * mtry * sizeof(GrowBest));
     R.state = (u64 *)carve(batch * (GROW_MT_N + 1) * 8);
     R.lvl = (u32 *)carve(batch * 2 * 4);
+    R.fold = R.fold_n = R.fold_sum = nullptr;
+    R.pred = nullptr;
+    if (P.n_folds) {
+        R.fold = (u32 *)carve(n * 4);
+        R.fold_n = (u32 *)carve(P.n_folds * 4);
+        R.fold_sum = (u32 *)carve(P.n_folds * 4);
+        R.pred = (double *)carve(n * 16);
+    }
     return PJB_OK;
 }
 
-// grows the trees t0 .. t0 + T - 1 level by level until none of them makes a node: one wait per level
+// grows the trees t0 .. t0 + T - 1 level by level until none of them makes a node: one wait per level.  Trees of pjb_forest_cv are
+// numbered fold after fold and start from their fold's rows (pjb_cv.hip.h); the level loop is the same and does not know of folds.
 static int grow_batch(pjb_ctx *c, const GrowPlan &P, const GrowRoom &R, u32 label_sum, size_t t0, u32 T) {
     hipStream_t st = c->stream;
     const size_t n = P.n, C = P.C, dep = P.dep, M = P.M;
     const u32 mtry = P.mtry;
-    LAUNCH(c, "kt_seed", kt_seed, dim3((T + 63) / 64), dim3(64), R.state, T, (u32)t0, P.seed, R.nd, (u32)M, R.lvl, (u32)n, label_sum);
-    const u64 total = (u64)T * C * n;
-    LAUNCH(c, "kt_fill", kt_fill, dim3((unsigned)((total + 255) / 256)), dim3(256), (const u32 *)R.sorted, R.lists[0], (u64)(C * n), total);
-    HIP_TRY(c, hipMemsetAsync(R.node_of, 0, (size_t)T * n * 4, st));
+    if (P.n_folds) {
+        LAUNCH(c, "kc_seed", kc_seed, dim3((T + 63) / 64), dim3(64), R.state, T, (u32)t0, (u32)P.n_trees, P.seed, R.nd, (u32)M, R.lvl, (const u32 *)R.fold_n,
+               (const u32 *)R.fold_sum);
+        LAUNCH(c, "kc_lists", kc_lists, dim3((unsigned)C, T), dim3(64), (const u32 *)R.sorted, R.lists[0], (const u32 *)R.fold, (const u32 *)R.fold_n, (u32)t0,
+               (u32)P.n_trees, (u32)n, (u32)C, (u32)dep);
+        LAUNCH(c, "kc_park", kc_park, dim3((unsigned)((n + 255) / 256), T), dim3(256), R.node_of, (const u32 *)R.fold, (u32)t0, (u32)P.n_trees, (u32)n, (u32)M);
+    } else {
+        LAUNCH(c, "kt_seed", kt_seed, dim3((T + 63) / 64), dim3(64), R.state, T, (u32)t0, P.seed, R.nd, (u32)M, R.lvl, (u32)n, label_sum);
+        const u64 total = (u64)T * C * n;
+        LAUNCH(c, "kt_fill", kt_fill, dim3((unsigned)((total + 255) / 256)), dim3(256), (const u32 *)R.sorted, R.lists[0], (u64)(C * n), total);
+        HIP_TRY(c, hipMemsetAsync(R.node_of, 0, (size_t)T * n * 4, st));
+    }
     int cur = 0;
     // one trip per level: at most n_rows levels (every split leaves both children smaller); the one read-back says whether nodes were made
     for (size_t level = 0; level <= n; level++) {
@@ -216,19 +244,26 @@ static int grow_batch(pjb_ctx *c, const GrowPlan &P, const GrowRoom &R, u32 labe
     return PJB_OK;
 }
 
-// the nodes of the batch's trees, packed one tree after the other on the device, read back and appended to G: two waits
-static int grow_collect(pjb_ctx *c, const GrowPlan &P, const GrowRoom &R, u32 label_sum, size_t t0, u32 T, ModelState::GrowOut &G) {
+struct GrowPacked { // the nodes of a batch's trees on the host: tree t owns off[t] .. off[t + 1]
+    std::vector<u64> off;
+    std::vector<u32> child, var, count, sum;
+    std::vector<double> val;
+};
+
+// the nodes of the batch's trees, packed one tree after the other on the device and read back: two waits
+static int grow_read(pjb_ctx *c, const GrowPlan &P, const GrowRoom &R, size_t t0, u32 T, GrowPacked &K) {
     hipStream_t st = c->stream;
-    const size_t M = P.M, K = G.class_values.size();
+    const size_t M = P.M;
     int rc;
     std::vector<u32> lvl((size_t)2 * T);
     HIP_TRY(c, hipMemcpyAsync(lvl.data(), R.lvl, (size_t)2 * T * 4, hipMemcpyDeviceToHost, st));
     HIP_TRY(c, hipStreamSynchronize(st));
-    std::vector<u64> off((size_t)T + 1, 0);
+    std::vector<u64> &off = K.off;
+    off.assign((size_t)T + 1, 0);
     u32 most = 0;
     for (u32 t = 0; t < T; t++) {
         const u32 nodes = lvl[(size_t)T + t]; // (the end of the last level: the tree's node count)
-        if (lvl[t] != nodes || nodes < 1 || nodes >= M) return fail(c, PJB_ERR_STATE, "pjb_forest_grow: tree %zu did not finish (%u nodes)", t0 + t, nodes);
+        if (lvl[t] != nodes || nodes < 1 || nodes >= M) return fail(c, PJB_ERR_STATE, "%s: tree %zu did not finish (%u nodes)", P.who, t0 + t, nodes);
         off[t + 1] = off[t] + nodes;
         most = std::max(most, nodes);
     }
@@ -241,8 +276,10 @@ static int grow_collect(pjb_ctx *c, const GrowPlan &P, const GrowRoom &R, u32 la
     double *p_val = (double *)(q + 4 * up256(N * 4));
     HIP_TRY(c, hipMemcpyAsync(d_off, off.data(), (T + 1) * 8, hipMemcpyHostToDevice, st));
     LAUNCH(c, "kt_pack", kt_pack, dim3((most + 255) / 256, T), dim3(256), R.nd, (u32)M, (const u64 *)d_off, p_child, p_var, p_val, p_count, p_sum);
-    std::vector<u32> h_child(N), h_var(N), h_count(N), h_sum(N);
-    std::vector<double> h_val(N);
+    std::vector<u32> &h_child = K.child, &h_var = K.var, &h_count = K.count, &h_sum = K.sum;
+    std::vector<double> &h_val = K.val;
+    for (std::vector<u32> *v : {&h_child, &h_var, &h_count, &h_sum}) v->resize(N);
+    h_val.resize(N);
     HIP_TRY(c, hipMemcpyAsync(h_child.data(), p_child, N * 4, hipMemcpyDeviceToHost, st));
     HIP_TRY(c, hipMemcpyAsync(h_var.data(), p_var, N * 4, hipMemcpyDeviceToHost, st));
     HIP_TRY(c, hipMemcpyAsync(h_count.data(), p_count, N * 4, hipMemcpyDeviceToHost, st));
@@ -250,7 +287,16 @@ static int grow_collect(pjb_ctx *c, const GrowPlan &P, const GrowRoom &R, u32 la
     HIP_TRY(c, hipMemcpyAsync(h_val.data(), p_val, N * 8, hipMemcpyDeviceToHost, st));
     HIP_TRY(c, hipStreamSynchronize(st));
     if (c->ktime) ev_collect(c, MISC_POOL);
-    for (u32 t = 0; t < T; t++) {
+    return PJB_OK;
+}
+
+// the batch's trees ta .. tb - 1 appended to G
+static void grow_append(const GrowPacked &B, u32 ta, u32 tb, u32 label_sum, ModelState::GrowOut &G) {
+    const std::vector<u64> &off = B.off;
+    const std::vector<u32> &h_child = B.child, &h_var = B.var, &h_count = B.count, &h_sum = B.sum;
+    const std::vector<double> &h_val = B.val;
+    const size_t K = G.class_values.size();
+    for (u32 t = ta; t < tb; t++) {
         for (u64 k = off[t]; k < off[t + 1]; k++) {
             if (h_child[k]) {
                 G.left.push_back((int32_t)h_child[k]);
@@ -269,10 +315,9 @@ static int grow_collect(pjb_ctx *c, const GrowPlan &P, const GrowRoom &R, u32 la
         }
         G.tree_off.push_back((int64_t)G.left.size());
     }
-    return PJB_OK;
 }
 
-// what the caller gets: a view of G (it lives until the context's next pjb_forest_grow), checked like a forest from a file
+// what the caller gets: a view of G (it lives until the context's next call of the same entry point), checked like a forest from a file
 static int grow_view(pjb_ctx *c, const GrowPlan &P, const ModelState::GrowOut &G, pjb_grow_result *out) {
     pjb_forest &f = out->forest;
     memset(&f, 0, sizeof f);
@@ -291,7 +336,7 @@ static int grow_view(pjb_ctx *c, const GrowPlan &P, const ModelState::GrowOut &G
     f.n_counts = (int64_t)G.counts.size();
     out->class_values = G.class_values.data();
     char msg[200] = "";
-    if (pjb_forest_check(&f, msg, (int)sizeof msg) != PJB_OK) return fail(c, PJB_ERR_STATE, "pjb_forest_grow: the grown forest cannot be walked: %s", msg);
+    if (pjb_forest_check(&f, msg, (int)sizeof msg) != PJB_OK) return fail(c, PJB_ERR_STATE, "%s: the grown forest cannot be walked: %s", P.who, msg);
     return PJB_OK;
 }
 
@@ -571,7 +616,8 @@ int pjb_forest_grow(pjb_ctx *c, const double *data, int64_t n_rows, int32_t n_co
     GrowInput in;
     GrowRoom R;
     int rc;
-    if ((rc = grow_plan(c, data, n_rows, n_cols, p, out, P))) return rc;
+    GrowPacked B;
+    if ((rc = grow_plan(c, "pjb_forest_grow", data, n_rows, n_cols, p, out, P))) return rc;
     if ((rc = grow_input(c, data, P, in))) return rc;
     HIP_TRY(c, hipSetDevice(c->cfg.device));
     hipStream_t st = c->stream;
@@ -589,9 +635,84 @@ int pjb_forest_grow(pjb_ctx *c, const double *data, int64_t n_rows, int32_t n_co
     for (size_t t0 = 0; t0 < P.n_trees; t0 += R.batch) {
         const u32 T = (u32)std::min<size_t>(R.batch, P.n_trees - t0);
         if ((rc = grow_batch(c, P, R, in.label_sum, t0, T))) return rc;
-        if ((rc = grow_collect(c, P, R, in.label_sum, t0, T, G))) return rc;
+        if ((rc = grow_read(c, P, R, t0, T, B))) return rc;
+        grow_append(B, 0, T, in.label_sum, G);
     }
     return grow_view(c, P, G, out);
+}
+
+// k-fold cross-validation: see include/portcullis_amd.h and pjb_cv.hip.h.
+int pjb_forest_cv(pjb_ctx *c, const double *data, int64_t n_rows, int32_t n_cols, const pjb_grow_params *p, const int32_t *fold, int32_t n_folds,
+                  double *pred, pjb_grow_result *forests) {
+    if (!c) return PJB_ERR_ARG;
+    static const char *const who = "pjb_forest_cv";
+    GrowPlan P;
+    GrowInput in;
+    GrowFolds F;
+    GrowRoom R;
+    GrowPacked B;
+    int rc;
+    if ((rc = grow_plan(c, who, data, n_rows, n_cols, p, pred, P))) return rc;
+    if (!fold) return fail(c, PJB_ERR_ARG, "%s: bad arguments", who);
+    if (n_folds < 2 || n_folds > n_rows) return fail(c, PJB_ERR_ARG, "%s: %d folds of %lld rows (2 to the number of rows)", who, n_folds, (long long)n_rows);
+    P.n_folds = (size_t)n_folds;
+    if (P.trees_all() > ((size_t)1 << 30)) return fail(c, PJB_ERR_ARG, "%s: %d folds of %d trees", who, n_folds, p->n_trees);
+    std::vector<u32> held(P.n_folds, 0), held_sum(P.n_folds, 0);
+    F.fold.resize(P.n);
+    for (size_t r = 0; r < P.n; r++) {
+        if (fold[r] < 0 || fold[r] >= n_folds) return fail(c, PJB_ERR_ARG, "%s: row %zu is in fold %d (0 to %d)", who, r, fold[r], n_folds - 1);
+        F.fold[r] = (u32)fold[r];
+        held[F.fold[r]]++;
+    }
+    for (size_t f = 0; f < P.n_folds; f++)
+        if (!held[f]) return fail(c, PJB_ERR_ARG, "%s: fold %zu holds no row", who, f);
+    if ((rc = grow_input(c, data, P, in))) return rc;
+    for (size_t r = 0; r < P.n; r++) held_sum[F.fold[r]] += in.label[r];
+    F.train_n.resize(P.n_folds);
+    F.train_sum.resize(P.n_folds);
+    for (size_t f = 0; f < P.n_folds; f++) {
+        F.train_n[f] = (u32)P.n - held[f];
+        F.train_sum[f] = in.label_sum - held_sum[f];
+        if (F.train_sum[f] == 0 || F.train_sum[f] == F.train_n[f])
+            return fail(c, PJB_ERR_ARG, "%s: the %u rows fold %zu trains on all have the label %d", who, F.train_n[f], f, F.train_sum[f] ? 1 : 0);
+    }
+    HIP_TRY(c, hipSetDevice(c->cfg.device));
+    hipStream_t st = c->stream;
+    if ((rc = grow_room(c, P, R))) return rc;
+    HIP_TRY(c, hipMemcpyAsync(R.col, in.colmajor.data(), P.C * P.n * 8, hipMemcpyHostToDevice, st));
+    HIP_TRY(c, hipMemcpyAsync(R.label, in.label.data(), P.n, hipMemcpyHostToDevice, st));
+    HIP_TRY(c, hipMemcpyAsync(R.sorted, in.sorted.data(), P.C * P.n * 4, hipMemcpyHostToDevice, st));
+    HIP_TRY(c, hipMemcpyAsync(R.fold, F.fold.data(), P.n * 4, hipMemcpyHostToDevice, st));
+    HIP_TRY(c, hipMemcpyAsync(R.fold_n, F.train_n.data(), P.n_folds * 4, hipMemcpyHostToDevice, st));
+    HIP_TRY(c, hipMemcpyAsync(R.fold_sum, F.train_sum.data(), P.n_folds * 4, hipMemcpyHostToDevice, st));
+    HIP_TRY(c, hipMemsetAsync(R.pred, 0, P.n * 16, st));
+
+    std::vector<ModelState::GrowOut> &GG = c->model.cv_out;
+    GG.assign(P.n_folds, ModelState::GrowOut());
+    for (ModelState::GrowOut &G : GG) {
+        G.is_ordered.assign(P.C, 1);
+        G.class_values = {0.0, 1.0};
+        G.tree_off.push_back(0);
+    }
+    const size_t all = P.trees_all();
+    for (size_t t0 = 0; t0 < all; t0 += R.batch) {
+        const u32 T = (u32)std::min<size_t>(R.batch, all - t0);
+        if ((rc = grow_batch(c, P, R, 0, t0, T))) return rc;
+        LAUNCH(c, "kc_score", kc_score, dim3((unsigned)((P.n + 255) / 256)), dim3(256), R.nd, (u32)P.M, (const double *)R.col, (const u32 *)R.fold, (u32)t0, T,
+               (u32)P.n_trees, (u32)P.n, R.pred);
+        if ((rc = grow_read(c, P, R, t0, T, B))) return rc;
+        for (size_t f = t0 / P.n_trees; f * P.n_trees < t0 + T; f++) { // the folds the batch cuts through
+            const size_t ta = std::max(f * P.n_trees, t0) - t0, tb = std::min((f + 1) * P.n_trees, t0 + T) - t0;
+            grow_append(B, (u32)ta, (u32)tb, F.train_sum[f], GG[f]);
+        }
+    }
+    HIP_TRY(c, hipMemcpyAsync(pred, R.pred, P.n * 16, hipMemcpyDeviceToHost, st));
+    HIP_TRY(c, hipStreamSynchronize(st));
+    if (c->ktime) ev_collect(c, MISC_POOL);
+    if (forests)
+        for (size_t f = 0; f < P.n_folds; f++)
+            if ((rc = grow_view(c, P, GG[f], &forests[f]))) return rc;
+    return PJB_OK;
 }
 
 // Waves the default chunking of pjb_knn aims at: 256 CUs x 4 SIMDs x 4 waves, so that scalar-load latency has other waves to hide behind.

@@ -30,7 +30,7 @@ EXPORTS = [
     "pjb_csi_depth", "pjb_index_begin_csi", "pjb_index_end_csi",
     "pjb_bam_merge_begin", "pjb_bam_merge_file", "pjb_bam_merge_end",
     "pjb_bam_sort_begin", "pjb_bam_sort_piece", "pjb_bam_sort_end",
-    "pjb_forest_check", "pjb_forest_load", "pjb_forest_predict", "pjb_filt_scores", "pjb_forest_grow", "pjb_knn",
+    "pjb_forest_check", "pjb_forest_load", "pjb_forest_predict", "pjb_filt_scores", "pjb_forest_grow", "pjb_forest_cv", "pjb_knn",
     "pjb_markov_train",
     "pjb_memory_info",
 ]
@@ -208,6 +208,8 @@ def load():
         L.pjb_filt_scores.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_double, C.c_uint32, C.POINTER(PjbMarkovModels), C.c_void_p, C.c_void_p,
                                       C.c_void_p]
         L.pjb_forest_grow.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.POINTER(PjbGrowParams), C.POINTER(PjbGrowResult)]
+        L.pjb_forest_cv.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.POINTER(PjbGrowParams), C.c_void_p, C.c_int32, C.c_void_p,
+                                    C.POINTER(PjbGrowResult)]
         L.pjb_knn.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_void_p]
         L.pjb_index_begin.argtypes = [C.c_void_p]
         L.pjb_index_piece.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int32, C.c_int32, C.POINTER(C.c_uint64)]
@@ -614,6 +616,21 @@ class Context:
         r = PjbGrowResult()
         self._check(self._L.pjb_forest_grow(self._h, data.ctypes.data_as(C.c_void_p), data.shape[0], data.shape[1], C.byref(p), C.byref(r)))
         return Forest._from_struct(r.forest, r.class_values)
+
+    def forest_cv(self, data, fold, n_folds, n_trees, seed=1236456789, mtry=0, min_node_size=0, dependent_col=0):
+        """pjb_forest_cv: data as forest_grow takes it, fold int32 [n] (the fold that holds a row out) -> (pred float64 [n, 2], the
+        n_folds Forests, copies): row r of pred is forest fold[r]'s prediction of row r, forest f the one forest_grow grows on the rows
+        of the other folds; all of them grown through one level loop."""
+        data = np.ascontiguousarray(data, dtype=np.float64)
+        assert data.ndim == 2
+        fold = np.ascontiguousarray(fold, dtype=np.int32).reshape(-1)
+        assert len(fold) == len(data)
+        p = PjbGrowParams(int(n_trees), int(seed) & 0xFFFFFFFF, int(mtry), int(min_node_size), int(dependent_col))
+        r = (PjbGrowResult * max(int(n_folds), 1))()
+        pred = np.zeros((max(len(data), 1), 2), dtype=np.float64)
+        self._check(self._L.pjb_forest_cv(self._h, data.ctypes.data_as(C.c_void_p), data.shape[0], data.shape[1], C.byref(p), fold.ctypes.data_as(C.c_void_p),
+                                          int(n_folds), pred.ctypes.data_as(C.c_void_p), r))
+        return pred[: len(data)], [Forest._from_struct(r[f].forest, r[f].class_values) for f in range(int(n_folds))]
 
     def knn(self, data, k):
         """pjb_knn: data float64 [n, n_cols] -> uint32 [n, k], per row the k rows nearest under (squared distance, index), the row

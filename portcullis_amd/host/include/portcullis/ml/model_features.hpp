@@ -76,7 +76,15 @@ public:
     // ForestProbability grown as trainInstance grows it (lib/src/model_features.cc:422-440) on the rows of x: the feature rows are the
     // device's (pjb_filt_features: what forestPredict walks), column 0 the junctions' isGenuine(), the variables activeFeatures();
     // the forest is grown on the same device (pjb_forest_grow).  featuresOut (optional): the full matrix, as forestPredict returns it.
-    Forest growForest(const JunctionList& x, int32_t nTrees, uint32_t seed, std::vector<double>* featuresOut = nullptr);
+    // cv (optional): k-fold cross-validation of the same matrix with the same parameters (pjb_forest_cv, one call: the folds' forests
+    // grow side by side): fold[i] is the fold that holds x[i] out, pred comes back as [x.size()][2], row i from the forest grown without
+    // x[i]'s fold.  The caller has made sure that every fold is held out somewhere and trains on both labels.
+    struct CrossValidation {
+        int32_t nFolds = 0;
+        std::vector<int32_t> fold;
+        std::vector<double> pred;
+    };
+    Forest growForest(const JunctionList& x, int32_t nTrees, uint32_t seed, std::vector<double>* featuresOut = nullptr, CrossValidation* cv = nullptr);
     // ModelFeatures::trainInstance (lib/src/model_features.cc:252-447) for a probability forest.  pos / neg: sorted, genuine flags set.
     // N = |pos| / |neg| - 1.  With smote: N > 0 adds N synthetic rows per negative (Smote, k = 5), N <= 0 erases random negatives until
     // there are no more than positives.  With enn: rows whose 3 nearest neighbours (itself among them) do not all carry their label

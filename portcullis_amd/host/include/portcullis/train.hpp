@@ -8,9 +8,16 @@
 // beside <prefix>.forest for `filt --model_file ... --models_file ...`.  What the reference does before that step and is not built
 // (INTEGRATION.md): choosing the sets by layered rules, SMOTE, ENN, the under-sampling, variable importance and the out-of-bag error
 // (every row is in bag: there is none to report).
+//   --folds k (the reference's own `train` mode, src/train.cc:145-192): k-fold cross-validation of the same rows with the same
+// parameters.  Every junction is scored by a forest grown without its fold (pjb_forest_cv: the k forests grow side by side on the
+// device), called genuine when its score reaches --threshold, and <prefix>.cv_results holds the folds' confusion matrices and rates
+// (ml/performance.hpp) and their means, <prefix>.cv_scores every junction's fold and score.  <prefix>.forest is what it is without
+// --folds.  The deviations from the reference (a seeded shuffle, probability forests with a threshold, no NaN, no --markov, no folds
+// by default) are in INTEGRATION.md.
 #pragma once
 
 #include <string>
+#include <vector>
 
 #include "junction_system.hpp"
 #include "prepared_files.hpp"
@@ -24,6 +31,8 @@ struct TrainException : public PortcullisException {
 const std::string DEFAULT_TRAIN_OUTPUT = "portcullis_train/portcullis";
 const int32_t DEFAULT_TRAIN_TREES = 250;
 const uint32_t DEFAULT_TRAIN_SEED = 1236456789;  // ModelFeatures::trainInstance
+const int32_t DEFAULT_TRAIN_FOLDS = 0;           // no cross-validation (the reference: 5)
+const double DEFAULT_TRAIN_THRESHOLD = 0.5;      // JunctionFilter::categorise
 
 class Train {
     PreparedFiles prepData;
@@ -31,6 +40,8 @@ class Train {
     int32_t trees = DEFAULT_TRAIN_TREES;
     uint32_t seed = DEFAULT_TRAIN_SEED;
     bool saveFeatures = false, verbose = false, markov = false;
+    int32_t folds = DEFAULT_TRAIN_FOLDS;
+    double threshold = DEFAULT_TRAIN_THRESHOLD;
     int device = 0;
 
 public:
@@ -43,6 +54,12 @@ public:
     void setVerbose(bool v) { verbose = v; }
     void setMarkov(bool v) { markov = v; }
     void setDevice(int v) { device = v; }
+    void setFolds(int32_t v) { folds = v; }
+    void setThreshold(double v) { threshold = v; }
+
+    // The fold that holds out each of n rows: row i starts in fold i % k, then the vector is shuffled by Fisher-Yates from the back
+    // (for i = n-1 .. 1: swap v[i] with v[next() % (i + 1)]) with std::mt19937_64 seeded with `seed`.
+    static std::vector<int32_t> assignFolds(size_t n, int32_t k, uint32_t seed);
 
     void train();
 

@@ -295,7 +295,7 @@ std::vector<double> ModelFeatures::forestPredict(const JunctionList& x, const Fo
     return pred;
 }
 
-Forest ModelFeatures::growForest(const JunctionList& x, int32_t nTrees, uint32_t seed, std::vector<double>* featuresOut) {
+Forest ModelFeatures::growForest(const JunctionList& x, int32_t nTrees, uint32_t seed, std::vector<double>* featuresOut, CrossValidation* cv) {
     if (x.empty()) throw ForestException("No junctions to grow a forest on");
     DeviceRun run;
     std::vector<double> rows = featureRows(run, *this, x);
@@ -307,7 +307,14 @@ Forest ModelFeatures::growForest(const JunctionList& x, int32_t nTrees, uint32_t
     pjb_grow_result r;
     run.check(pjb_forest_grow(run.ctx, matrix.data(), (int64_t)x.size(), (int32_t)activeFeatures().size(), &p, &r), "pjb_forest_grow");
     if (featuresOut) featuresOut->swap(rows);
-    return Forest::fromView(r.forest, r.class_values);
+    const Forest forest = Forest::fromView(r.forest, r.class_values);  // (a copy: pjb_forest_cv may take the result away)
+    if (cv) {
+        if (cv->fold.size() != x.size()) throw ForestException("growForest: " + std::to_string(cv->fold.size()) + " fold ids for " + std::to_string(x.size()) + " junctions");
+        cv->pred.assign(x.size() * 2, 0.0);
+        run.check(pjb_forest_cv(run.ctx, matrix.data(), (int64_t)x.size(), (int32_t)activeFeatures().size(), &p, cv->fold.data(), cv->nFolds, cv->pred.data(), nullptr),
+                  "pjb_forest_cv");
+    }
+    return forest;
 }
 
 Forest ModelFeatures::trainInstance(const JunctionList& pos, const JunctionList& neg, const TrainOptions& o, std::vector<double>* matrixOut) {

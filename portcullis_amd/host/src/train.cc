@@ -2,10 +2,15 @@
 #include <portcullis/train.hpp>
 
 #include <chrono>
+#include <cstdio>
+#include <fstream>
 #include <iomanip>
 #include <iostream>
+#include <random>
+#include <sstream>
 
 #include <portcullis/ml/model_features.hpp>
+#include <portcullis/ml/performance.hpp>
 
 #include "../../../include/portcullis_amd.h"
 #include "fs_util.hpp"
@@ -16,11 +21,42 @@ using std::string;
 
 namespace portcullis {
 
+std::vector<int32_t> Train::assignFolds(size_t n, int32_t k, uint32_t seed) {
+    std::vector<int32_t> v(n);
+    for (size_t i = 0; i < n; i++) v[i] = (int32_t)(i % (size_t)k);
+    std::mt19937_64 next(seed);
+    for (size_t i = n; i-- > 1;) std::swap(v[i], v[(size_t)(next() % (uint64_t)(i + 1))]);
+    return v;
+}
+
+// <prefix>.cv_results as the reference lays it out (src/train.cc:153-190): the header, a line per fold (numbered from 1), the ten means
+static string cvResults(const JunctionList& x, const std::vector<int32_t>& fold, int32_t folds, const std::vector<double>& score, double threshold) {
+    std::vector<uint32_t> tp((size_t)folds, 0), tn(tp), fp(tp), fn(tp);
+    for (size_t i = 0; i < x.size(); i++) {
+        const bool called = score[i] >= threshold, genuine = x[i]->isGenuine();
+        (genuine ? (called ? tp : fn) : (called ? fp : tn))[(size_t)fold[i]]++;
+    }
+    std::ostringstream out;
+    out << "Fold\t" << ml::Performance::longHeader() << "\n";
+    ml::PerformanceList perfs;
+    for (size_t f = 0; f < (size_t)folds; f++) {
+        auto p = std::make_shared<ml::Performance>(tp[f], tn[f], fp[f], fn[f]);
+        out << f + 1 << "\t" << p->toLongString() << "\n";
+        perfs.add(p);
+    }
+    perfs.outputMeanPerformance(out);
+    return out.str();
+}
+
 void Train::train() {
     size_t slash = output.find_last_of('/');
     string outputDir = slash == string::npos ? string(".") : output.substr(0, slash);
     if (outputDir.empty()) outputDir = "/";
     if (trees < 1) throw TrainException("--trees must be at least 1");
+    if (folds < 0 || folds == 1) throw TrainException("--folds must be 0 (no cross-validation) or at least 2: " + std::to_string(folds));
+    if (!(threshold >= 0.0 && threshold <= 1.0)) throw TrainException("--threshold must lie between 0 and 1");
+    if (folds && markov)
+        throw TrainException("--folds cannot be combined with --markov: the Markov models would have seen the held-out junctions, and training them fold by fold is not built");
     if (!exists(positiveFile)) throw TrainException("Could not find positive junction file at: " + positiveFile);
     if (!exists(negativeFile)) throw TrainException("Could not find negative junction file at: " + negativeFile);
     if (!exists(prepData.getGenomeFilePath())) throw TrainException("Could not find prepared genome file at: " + prepData.getGenomeFilePath());
@@ -41,9 +77,6 @@ void Train::train() {
     for (const auto& j : neg.getJunctions())
         if (pos.getJunction(*(j->getIntron())) != nullptr)
             throw TrainException("Junction " + j->getIntron()->toString() + " is in the positive and in the negative set");
-    // no device: said before the genome is read, in the words `prep` has for it
-    if (pjb_device_count() <= 0)
-        throw TrainException("No MI355X (HIP device) is visible: the forest is grown on the GPU and has no CPU fallback.  Run train where the GPU is.");
     // lib/src/model_features.cc:297-304: positives, then negatives, sorted as one system
     JunctionList training;
     training.reserve(pos.getJunctions().size() + neg.getJunctions().size());
@@ -58,6 +91,26 @@ void Train::train() {
     JunctionSystem trainingSystem(training);
     trainingSystem.sort();
     const JunctionList& x = trainingSystem.getJunctions();
+    ml::ModelFeatures::CrossValidation cv;
+    if (folds) {
+        if ((size_t)folds > x.size()) throw TrainException("--folds " + std::to_string(folds) + " is more than the " + std::to_string(x.size()) + " junctions");
+        cv.nFolds = folds;
+        cv.fold = assignFolds(x.size(), folds, seed);
+        std::vector<size_t> held((size_t)folds, 0), heldGenuine((size_t)folds, 0);
+        for (size_t i = 0; i < x.size(); i++) {
+            held[(size_t)cv.fold[i]]++;
+            heldGenuine[(size_t)cv.fold[i]] += x[i]->isGenuine() ? 1 : 0;
+        }
+        for (size_t f = 0; f < (size_t)folds; f++) {
+            const size_t n = x.size() - held[f], genuine = pos.getJunctions().size() - heldGenuine[f];
+            if (genuine == 0 || genuine == n)
+                throw TrainException("Fold " + std::to_string(f + 1) + " of " + std::to_string(folds) + " would train on " + (genuine ? "positive" : "negative") +
+                                     " junctions only (" + std::to_string(n) + " junctions): use fewer folds or another --seed");
+        }
+    }
+    // no device: said before the genome is read, in the words `prep` has for it
+    if (pjb_device_count() <= 0)
+        throw TrainException("No MI355X (HIP device) is visible: the forest is grown on the GPU and has no CPU fallback.  Run train where the GPU is.");
     cout << "Training a random forest model" << endl << "------------------------------" << endl << endl;
     cout << "Creating feature vector for " << x.size() << " junctions (" << pos.getJunctions().size() << " positive, " << neg.getJunctions().size()
          << " negative)" << endl;
@@ -75,7 +128,7 @@ void Train::train() {
     }
     std::vector<double> features;
     cout << "Growing " << trees << " trees" << endl;
-    const ml::Forest forest = mf.growForest(x, trees, seed, saveFeatures ? &features : nullptr);
+    const ml::Forest forest = mf.growForest(x, trees, seed, saveFeatures ? &features : nullptr, folds ? &cv : nullptr);
     ml::ModelFeatures::checkForest(forest);  // (what filt will ask of it)
     if (verbose) cout << "Grown " << forest.treeOff.back() << " nodes in " << forest.nTrees << " trees" << endl;
     if (saveFeatures) {  // lib/src/model_features.cc:402-410: the active columns, default stream formatting
@@ -88,6 +141,29 @@ void Train::train() {
     if (markov) {
         mf.bundle().save(output + ".models");
         cout << "Saved L95 and Markov models to file " << output << ".models" << endl;
+    }
+    if (folds) {
+        std::vector<double> score(x.size());
+        for (size_t i = 0; i < x.size(); i++) score[i] = 1.0 - cv.pred[i * 2];  // JunctionFilter::categorise
+        const string table = cvResults(x, cv.fold, folds, score, threshold);
+        cout << endl << "Starting " << folds << "-fold cross validation" << endl << table << "Cross validation completed" << endl << endl;
+        std::ofstream resout((output + ".cv_results").c_str());
+        resout << table;
+        resout.close();
+        if (!resout) throw TrainException("Could not write to output file: " + output + ".cv_results");
+        cout << "Saved cross validation results to file " << output << ".cv_results" << endl;
+        std::ofstream sout((output + ".cv_scores").c_str());
+        sout << "refid\tstart\tend\tstrand\tfold\tgenuine\tscore\n";
+        for (size_t i = 0; i < x.size(); i++) {
+            char num[40];
+            snprintf(num, sizeof num, "%.17g", score[i]);
+            const Intron& in = *(x[i]->getIntron());
+            sout << in.ref.index << "\t" << in.start << "\t" << in.end << "\t" << bam::strandToChar(x[i]->getConsensusStrand()) << "\t" << cv.fold[i] + 1 << "\t"
+                 << (x[i]->isGenuine() ? 1 : 0) << "\t" << num << "\n";
+        }
+        sout.close();
+        if (!sout) throw TrainException("Could not write to output file: " + output + ".cv_scores");
+        cout << "Saved the held-out scores to file " << output << ".cv_scores" << endl;
     }
 }
 
@@ -104,10 +180,17 @@ string Train::helpMessage() {
            "  --markov                             Train L95 and the Markov models on the two sets first (on the GPU), grow the forest on rows that\n"
            "                                       carry them, and write <prefix>.models for filt --model_file <prefix>.forest --models_file <prefix>.models.\n"
            "  --save_features                      Also write <prefix>.features.training: the feature rows the forest was grown on.\n"
+           "  -k [ --folds ] arg (=0)              k-fold cross-validation: every junction is scored by a forest grown without its fold (the k\n"
+           "                                       forests grow side by side on the GPU); <prefix>.cv_results gets the folds' TP / TN / FP / FN and\n"
+           "                                       rates and their means, <prefix>.cv_scores every junction's fold and score.  0: none; else 2 or more.\n"
+           "                                       The folds are dealt round and shuffled with --seed.  Not with --markov.\n"
+           "  --threshold arg (=0.5)               With --folds: a held-out junction is called genuine when its score reaches this (0 to 1).\n"
            "  -v [ --verbose ]                     Print extra information\n"
            "  --help                               Produce help message\n\n"
            "Not built: choosing the two sets (the reference's self-training layers), SMOTE, ENN,\n"
-           "under-sampling, --genuine, variable importance and the out-of-bag error (every row is in bag).\n";
+           "under-sampling, --genuine (a table of known labels for one junction file: the labels are the two tables\n"
+           "here), --fraction, cross-validation with --markov, variable importance and the out-of-bag error (every\n"
+           "row is in bag).\n";
 }
 
 int Train::main(int argc, char* argv[]) {
@@ -116,6 +199,8 @@ int Train::main(int argc, char* argv[]) {
     int32_t trees = DEFAULT_TRAIN_TREES;
     uint32_t seed = DEFAULT_TRAIN_SEED;
     bool saveFeatures = false, verbose = false, help = false, markov = false;
+    int32_t folds = DEFAULT_TRAIN_FOLDS;
+    double threshold = DEFAULT_TRAIN_THRESHOLD;
     // long options take their value as the next argument or after '='
     for (int i = 1; i < argc; i++) {
         string a = argv[i], inlineValue;
@@ -134,6 +219,8 @@ int Train::main(int argc, char* argv[]) {
         else if (a == "--trees") trees = (int32_t)std::stol(need());
         else if (a == "--seed") seed = (uint32_t)std::stoul(need());
         else if (a == "--save_features") saveFeatures = true;
+        else if (a == "-k" || a == "--folds") folds = (int32_t)std::stol(need());
+        else if (a == "--threshold") threshold = std::stod(need());
         else if (a == "--markov") markov = true;
         else if (a == "--devices") (void)need();
         else if (a == "-v" || a == "--verbose") verbose = true;
@@ -153,6 +240,8 @@ int Train::main(int argc, char* argv[]) {
     t.setSaveFeatures(saveFeatures);
     t.setVerbose(verbose);
     t.setMarkov(markov);
+    t.setFolds(folds);
+    t.setThreshold(threshold);
     t.train();
     const double s = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
     std::ios::fmtflags f(cout.flags());
